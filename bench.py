@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- SpMV throughput on MI355X, the reference's protocol, one JSON line.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload nlpkkt|cant|cant_hll|powerlaw]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload nlpkkt|cant|cant_hll|powerlaw] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one SpMV y = A x over the whole matrix (x = 1, the reference's input,
@@ -135,7 +135,33 @@ def parse_args():
     p.add_argument("--fail-rank", type=int, default=-1,
                    help="TEST ONLY: this rank raises before the timed region (the job must end non-zero, not hang)")
     p.add_argument("--no-box-state", action="store_true", help="skip the sysfs / stream-probe record of the box")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last one computed (the gathered y) to DIR/y.npy; "
+                        "a y over the size limit is written as DIR/y_sample.npy, a fixed seeded sample of its rows")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6 - 4096     # all .npy files of --dump-outputs together, headers included
+DUMP_SAMPLE_SEED = 20251015
+
+
+def dump_outputs(out_dir, y):
+    """y as the caller of the timed path receives it, in its own dtype (float32 / float64).  Whole when it fits
+    DUMP_LIMIT_BYTES; else the rows picked by a fixed seed (the same rows for the same M), in row order."""
+    os.makedirs(out_dir, exist_ok=True)
+    y = np.ascontiguousarray(y)
+    if y.nbytes <= DUMP_LIMIT_BYTES:
+        path = os.path.join(out_dir, "y.npy")
+        np.save(path, y)
+    else:
+        rows = np.random.default_rng(DUMP_SAMPLE_SEED).choice(len(y), DUMP_LIMIT_BYTES // 2 // y.itemsize,
+                                                              replace=False)
+        path = os.path.join(out_dir, "y_sample.npy")
+        np.save(path, y[np.sort(rows)])
+    log(f"[bench] outputs of the last timed step: {path}")
 
 
 # ----------------------------------------------------------------- workloads
@@ -741,6 +767,8 @@ def main():
 
     # ---- parity spot check on this rank's rows (checker: the oracle)
     y_gpu = dev.get_y() if exchange != "torch" else y_t.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, y_gpu)
     if args.check:
         # every rank: the gathered y against the serial oracle on the WHOLE matrix
         from oracle.oracle import Oracle

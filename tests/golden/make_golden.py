@@ -19,6 +19,13 @@ compiled reference computed from that file:
   part_T<k>_{s,e}        prepare_thread_distribution     (src/csr_matrix.c:167)
   hpart_T<k>_{s,e}       prepare_thread_distribution_hll (src/hll_matrix.c:410)
 
+    python tests/golden/make_golden.py --digests
+
+writes only reference_digests.json: what the compiled reference computes from the
+seeded inputs of tests/_util.py (random .mtx files through its parser, CSR and HLL
+builders and serial kernels; sort_row; computeDifferenceMetrics; the parser on
+files over 1 MiB), as SHA-256 digests of each output array plus the scalars.
+
 Only data is stored -- no reference source text.
 """
 import ctypes as C
@@ -31,9 +38,11 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from oracle.oracle import Reference  # noqa: E402
 from sparsematrixvectormultiplication_amd import _native as nat  # noqa: E402
+import _util  # noqa: E402
 
 REF_MTX = "/root/reference/matrix_generated/general_matrix.mtx"
 
@@ -183,5 +192,49 @@ def main():
         print(f"{name:18s} M={M:4d} N={N:4d} nz={nz:5d} hacks={hll.num_blocks}")
 
 
+def make_digests():
+    import json
+    import tempfile
+
+    ref = Reference()
+    dg = _util.digest
+    out = {"random_mtx": [], "sort_row": [], "parser": {}}
+    with tempfile.TemporaryDirectory() as tmp:
+        for trial, path, M, N, x in _util.random_mtx_trials(tmp):
+            pre, csr, hll = ref.load(path)
+            nz = csr.nz
+            blocks = []
+            for b in range(hll.num_blocks):
+                blk = hll.blocks[b]
+                n = blk.M * blk.MAXNZ
+                blocks.append([blk.M, blk.MAXNZ, dg(view(blk.JA, n, np.int32)), dg(view(blk.AS, n, np.float64))])
+            out["random_mtx"].append({
+                "M": M, "N": N, "nz": nz, "x": dg(x),
+                "row_ptr": dg(view(csr.row_ptr, M + 1, np.int32)), "col_idx": dg(view(csr.col_idx, nz, np.int32)),
+                "values": dg(view(csr.values, nz, np.float64)), "hll_blocks": blocks,
+                "y": dg(ref.csr_serial(csr, x)), "yh": dg(ref.hll_serial(hll, M, x))})
+        for field, symmetry, ragged in _util.PARSER_CASES:
+            path = os.path.join(tmp, "big.mtx")
+            _util.write_parser_case(path, field, symmetry, ragged)
+            pre = nat.PreMatrix()
+            assert ref.L.read_matrix_market(path.encode(), C.byref(pre)) == 0
+            out["parser"][_util.parser_case_key(field, symmetry, ragged)] = {
+                "M": pre.M, "N": pre.N, "nz": pre.nz, "I": dg(view(pre.I, pre.nz, np.int32)),
+                "J": dg(view(pre.J, pre.nz, np.int32)), "val": dg(view(pre.val, pre.nz, np.float64))}
+    for n, cols, vals in _util.sort_row_inputs():
+        ref.L.sort_row(cols.ctypes.data_as(nat.c_int_p), vals.ctypes.data_as(nat.c_double_p), 0, n - 1)
+        out["sort_row"].append({"n": n, "cols": dg(cols), "vals": dg(vals)})
+    a, b = _util.difference_metrics_inputs()
+    m = ref.L.computeDifferenceMetrics(a.ctypes.data_as(nat.c_double_p), b.ctypes.data_as(nat.c_double_p),
+                                       len(a), 1e-5, 1e-4, False)
+    out["difference_metrics"] = {"a": dg(a), "b": dg(b), "significant_diffs": m.significant_diffs,
+                                 "mean_rel_err": m.mean_rel_err, "mean_abs_err": m.mean_abs_err,
+                                 "flops_1234567_0.0321": ref.L.calculate_flops(1234567, 0.0321)}
+    with open(_util.REFERENCE_DIGESTS, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(f"wrote {_util.REFERENCE_DIGESTS}")
+
+
 if __name__ == "__main__":
-    main()
+    make_digests() if "--digests" in sys.argv[1:] else main()

@@ -1,8 +1,11 @@
-"""Host-side logic of bench.py that needs no GPU: the traffic table's stamps and the self-launcher."""
+"""Host-side logic of bench.py that needs no GPU: the traffic table's stamps, the self-launcher and the
+output dump."""
 import json
 import os
 import subprocess
 import sys
+
+import numpy as np
 
 import bench
 from conftest import ROOT
@@ -59,3 +62,21 @@ def test_self_launch_starts_child_ranks_and_relays_one_json_line(tmp_path):
     assert "starting 2 ranks" in proc.stderr and "--nproc-per-node=2" in proc.stderr
     assert "needs a HIP device" in proc.stderr
     assert proc.stdout.strip() == ""
+
+
+def test_dump_outputs_whole_or_a_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs writes y whole in its own dtype while it fits the limit; a larger y becomes the same
+    seeded sample of rows, in row order, on every run."""
+    y32 = np.linspace(-1, 1, 1000, dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "a"), y32)
+    got = np.load(tmp_path / "a" / "y.npy")
+    assert got.dtype == np.float32 and got.tobytes() == y32.tobytes()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 800)
+    y64 = np.arange(1000, dtype=np.float64)
+    for run in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / run), y64)
+        assert os.listdir(tmp_path / run) == ["y_sample.npy"]
+    s1, s2 = np.load(tmp_path / "b" / "y_sample.npy"), np.load(tmp_path / "c" / "y_sample.npy")
+    assert s1.dtype == np.float64 and s1.nbytes <= 800 and len(s1) == 50
+    assert np.all(np.diff(s1) > 0) and np.all(np.isin(s1, y64))
+    assert s1.tobytes() == s2.tobytes()

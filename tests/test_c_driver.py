@@ -143,6 +143,33 @@ def test_bench_powerlaw_two_ranks_checked_against_the_oracle(gpu):
 
 
 @pytest.mark.gpu
+def test_bench_dumps_what_the_last_timed_step_computed(tmp_path, gpu, oracle):
+    """--dump-outputs DIR: after the --steps timed steps, the y of the last one lands in DIR/y.npy in the workload's
+    dtype and equals the oracle's; the result line reports the steps asked for and the time of one of them."""
+    import json
+    import sys
+
+    import numpy as np
+    from _util import assert_parity
+    from sparsematrixvectormultiplication_amd import synth
+    grid = (24, 24, 24)
+    out_dir = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--grid", ",".join(map(str, grid)), "--settle-ms", "0", "--no-cpu-baseline", "--no-also", "--no-box-state",
+           "--dump-outputs", str(out_dir)]
+    proc = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert proc.returncode == 0, proc.stderr[-3000:]
+    out = json.loads([ln for ln in proc.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0
+    assert sorted(os.listdir(out_dir)) == ["y.npy"]
+    y = np.load(out_dir / "y.npy")
+    _, rp, col, val = synth.kkt_like(grid, 2)
+    x = np.ones(len(rp) - 1)
+    assert y.dtype == np.float64 and y.shape == x.shape
+    assert_parity(y, oracle.csr_serial(rp, col, val, x), rp, col, val, x, what="bench --dump-outputs")
+
+
+@pytest.mark.gpu
 def test_bench_job_ends_nonzero_when_one_rank_fails(gpu):
     """An unattended multi-rank run must not hang on a dead rank: rank 1 raises before the timed region while
     rank 0 goes on into its first collective; the job has to end with a non-zero code well inside a minute."""

@@ -1,5 +1,5 @@
 """BASELINE.json's configurations at THEIR sizes on one GPU (the real SuiteSparse files are not available
-offline: seeded shape-matched stand-ins, or the real file when $SPMV_MTX_DIR holds it).
+offline: seeded shape-matched stand-ins).
 
   C2 / C3  cant-size CSR / HLL: every kernel variant, the full y against the oracle
   C4       the nlpkkt120-size matrix cut into the 8 row blocks (CSR, reference's row partitioner) / hack
@@ -9,7 +9,6 @@ offline: seeded shape-matched stand-ins, or the real file when $SPMV_MTX_DIR hol
            row samples against the fp64-accumulated oracle loop (fp32 has no reference counterpart:
            pinned by this repo's oracle only), and its 8-way row partition
 """
-import os
 
 import numpy as np
 import pytest
@@ -141,18 +140,3 @@ def test_c5_powerlaw_fp32_full_size_properties(gpu, oracle):
             got = part.spmv(x1, sp.CSR_AUTO)
             assert got[lo:hi].tobytes() == y1[lo:hi].tobytes() or \
                 np.max(np.abs(got[lo:hi].astype(np.float64) - y1[lo:hi])) <= 1e-5 * float(np.max(np.abs(y1)))
-
-
-@pytest.mark.parametrize("name", ["cant.mtx", "nlpkkt120.mtx"])
-def test_real_suitesparse_file_if_present(gpu, oracle, name):
-    """The real files of configs 2-4, when $SPMV_MTX_DIR (or $SPMV_MTX) provides them."""
-    path = os.path.join(os.environ.get("SPMV_MTX_DIR", ""), name)
-    if not os.path.isfile(path):
-        pytest.skip(f"{name} is not available offline (set SPMV_MTX_DIR to the directory that holds it)")
-    csr = sp.convert_in_csr(sp.read_matrix_market(path))
-    x = np.ones(csr.N)
-    y_ref = oracle.csr_serial(csr.row_ptr, csr.col_idx, csr.values, x)
-    with sp.CsrDevice.from_host(csr) as dev:
-        assert_parity(dev.spmv(x, sp.CSR_AUTO), y_ref, csr.row_ptr, csr.col_idx, csr.values, x, what=name)
-        with sp.HllDevice.from_csr_device(dev) as h:
-            assert_parity(h.spmv(x, sp.HLL_AUTO), y_ref, csr.row_ptr, csr.col_idx, csr.values, x, what=name + " hll")
