@@ -288,6 +288,16 @@ void *spmv_hip_csr_y_ptr(spmv_csr_dev *m);
  * caller's stream (NULL = library stream) */
 int spmv_hip_csr_run_on(spmv_csr_dev *m, int variant, const void *d_x, void *d_y, void *stream);
 
+/* ---- CSR: several vectors per pass over the matrix (SpMM) ----------------- */
+/* Y = A X for k vectors at once.  X: N x k, Y: M_total x k, both row-major (element (i, j) at i * k + j), values of the
+ * handle's dtype.  The handle writes rows [row0, row0 + M_local) of Y and no other row.  Each row of a handle is read
+ * from HBM once per call, whatever k is.  k = 1 is exactly spmv_hip_csr_run_on(m, SPMV_CSR_AUTO, ...) (same bits).
+ * -1 for k < 1, NULL arguments, pointers not aligned to the element size, or a tiles-only handle. */
+int spmv_hip_csr_spmm_on(spmv_csr_dev *m, int k, const void *d_X, void *d_Y, void *stream); /* NULL stream = library's */
+int spmv_hip_csr_spmm(spmv_csr_dev *m, int k, const void *X_host, void *Y_host);  /* host arrays; syncs */
+/* the reference timing protocol of spmv_hip_csr_time, for the k-vector product on library-owned scratch X / Y */
+int spmv_hip_csr_spmm_time(spmv_csr_dev *m, int k, int warmup, int iters, float *ms_each);
+
 /* The reference's timing protocol (main_cuda.cu:159-200): per iteration
  * [zero y if zero_y], record an event, launch, record an event; `warmup`
  * untimed iterations first.  ms_each receives `iters` kernel durations in

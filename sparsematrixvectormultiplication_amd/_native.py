@@ -179,6 +179,9 @@ _PROTOTYPES = {
     "spmv_hip_csr_y_ptr": (C.c_void_p, [C.c_void_p]),
     "spmv_hip_csr_run_on": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spmv_hip_csr_time": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p]),
+    "spmv_hip_csr_spmm_on": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spmv_hip_csr_spmm": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "spmv_hip_csr_spmm_time": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_float_p]),
     "spmv_hip_csr_step_time": (C.c_int, [C.c_void_p, C.c_int, c_int_p, C.c_int, C.c_int, c_float_p,
                                          c_float_p]),
     "spmv_hip_hll_upload": (C.c_int, [C.POINTER(HLLMatrix), C.c_int, C.c_int,

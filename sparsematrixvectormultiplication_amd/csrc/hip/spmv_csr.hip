@@ -1686,6 +1686,7 @@ extern "C" void spmv_hip_csr_free(spmv_csr_dev *m) {
     (void)hipFree(m->long_rows);
     (void)hipFree(m->pieces);
     (void)hipFree(m->partial);
+    (void)hipFree(m->spmm_partial);
     (void)hipFree(m->x);
     (void)hipFree(m->y);
     delete m;

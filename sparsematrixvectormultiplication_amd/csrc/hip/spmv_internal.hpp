@@ -187,6 +187,8 @@ struct spmv_csr_dev {
     int4 *pieces = nullptr;
     void *partial = nullptr;
     int num_partial = 0;
+    void *spmm_partial = nullptr;  // the k-wide partial sums of the pieces for SpMM (spmv_spmm.hip): grows only
+    size_t spmm_partial_bytes = 0;
     int stream_cap = 2048;
     bool ring_ok = false;  // blocks respect the ring kernel's row limit
     // stream kernel with the x window in LDS (csr_stream_local): own blocks, 16-bit local columns

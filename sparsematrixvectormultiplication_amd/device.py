@@ -289,6 +289,35 @@ class CsrDevice(_Handle):
                "csr_time_graph")
         return float(ms.value)
 
+    def spmm(self, X):
+        """Y = A X for the k columns of X (N x k, or a vector of N: k = 1) in one pass over the matrix
+        (spmv_hip_csr_spmm).  Returns an (M_total, k) array; rows outside the handle's are zero."""
+        X = np.asarray(X)
+        if X.dtype != self.dtype:
+            raise ValueError(f"X has dtype {X.dtype}, the handle holds {np.dtype(self.dtype)}")
+        if X.ndim == 1:
+            X = X.reshape(-1, 1)
+        if X.ndim != 2 or X.shape[0] != self.N or X.shape[1] < 1:
+            raise ValueError(f"X must be {self.N} x k with k >= 1, got shape {X.shape}")
+        X = np.ascontiguousarray(X)
+        Y = np.zeros((self.M, X.shape[1]), dtype=self.dtype)
+        _check(nat.lib().spmv_hip_csr_spmm(self.h, int(X.shape[1]), X.ctypes.data_as(C.c_void_p),
+                                           Y.ctypes.data_as(C.c_void_p)), "spmv_hip_csr_spmm")
+        return Y
+
+    def spmm_on(self, d_X: int, d_Y: int, k: int, stream: int = 0):
+        """Y = A X on device buffers (row-major N x k and M_total x k, e.g. spmv_hip_malloc or a torch tensor's
+        data_ptr()), asynchronous on `stream` (0 = the library's)."""
+        _check(nat.lib().spmv_hip_csr_spmm_on(self.h, int(k), C.c_void_p(d_X), C.c_void_p(d_Y), C.c_void_p(stream)),
+               "spmv_hip_csr_spmm_on")
+
+    def time_spmm(self, k, warmup=5, iters=95):
+        """Per-launch milliseconds of the k-vector product on library-owned X / Y (spmv_hip_csr_spmm_time)."""
+        ms = np.zeros(iters, dtype=np.float32)
+        _check(nat.lib().spmv_hip_csr_spmm_time(self.h, int(k), int(warmup), int(iters),
+                                                ms.ctypes.data_as(nat.c_float_p)), "csr_spmm_time")
+        return ms
+
     def power_iterate(self, iters, variant=CSR_AUTO, bounds=None, use_graph=True):
         """iters steps of x <- A x / ||A x||_2 on the device; returns (lambda, ms_total)."""
         lam, ms = C.c_double(0), C.c_float(0)

@@ -1,0 +1,299 @@
+"""GPU: Y = A X for k vectors per pass (spmv_hip_csr_spmm*), column by column against the reference's goldens and
+the oracle.  Column j of A X is A X[:, j]; fp64 gate 1e-10 (assert_parity), fp32 norm-wise against the
+fp64-accumulated oracle."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import sparsematrixvectormultiplication_amd as sp
+from _util import FP32_NORMWISE_RTOL, assert_parity, banded_csr, random_csr
+from conftest import GOLDEN_CASES, golden_path, load_golden
+
+pytestmark = pytest.mark.gpu
+
+K_F64 = (1, 2, 3, 4, 7, 8, 9, 16, 33, 64)
+K_F32 = (1, 2, 4, 5, 8, 33)
+
+
+class tuned:
+    """set_tuning for the duration of a with-block (back to the defaults after)."""
+    DEFAULTS = {"local_patterns": -1, "stream_tile": -1}
+
+    def __init__(self, **kv):
+        self.kv = kv
+
+    def __enter__(self):
+        for k, v in self.kv.items():
+            sp.set_tuning(k, v)
+
+    def __exit__(self, *exc):
+        for k in self.kv:
+            sp.set_tuning(k, self.DEFAULTS[k])
+
+
+def check_columns(oracle, Y, X, rp, col, val, what, rows=None):
+    """Every column of Y against the oracle on the same column of X (rows: the handle's row range)."""
+    lo, hi = rows if rows is not None else (0, len(rp) - 1)
+    for j in range(X.shape[1]):
+        x = X[:, j]
+        if val.dtype == np.float32:
+            ref = oracle.csr_f32_accum64(rp, col, val, x)[lo:hi]
+            y = Y[lo:hi, j].astype(np.float64)
+            scale = max(np.max(np.abs(ref)), 1e-30) if ref.size else 1.0
+            assert ref.size == 0 or np.max(np.abs(y - ref)) <= FP32_NORMWISE_RTOL * scale, f"{what} column {j}"
+        else:
+            ref = oracle.csr_serial(rp, col, val, x)
+            assert_parity(Y[lo:hi, j], ref[lo:hi], rp[lo:hi + 1] - rp[lo], col[rp[lo]:rp[hi]], val[rp[lo]:rp[hi]], x,
+                          what=f"{what} column {j}")
+
+
+def with_long_rows(rng, rp, col, val, N, where, lengths):
+    """The CSR with rows `where` replaced by rows of `lengths` distinct sorted columns."""
+    lens = np.diff(rp).astype(np.int64)
+    rows = [col[rp[r]:rp[r + 1]] for r in range(len(lens))]
+    vals = [val[rp[r]:rp[r + 1]] for r in range(len(lens))]
+    for r, n in zip(where, lengths):
+        rows[r] = np.sort(rng.choice(N, n, replace=False)).astype(np.int32)
+        vals[r] = rng.uniform(-1, 1, n).astype(val.dtype)
+        lens[r] = n
+    rp2 = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    return rp2, np.concatenate(rows).astype(np.int32), np.concatenate(vals)
+
+
+def hip_runtime():
+    """The HIP runtime the product library runs on (already loaded by it): for a stream of the caller's own."""
+    hip = C.CDLL("libamdhip64.so.7")
+    hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
+    hip.hipStreamSynchronize.argtypes = [C.c_void_p]
+    hip.hipStreamDestroy.argtypes = [C.c_void_p]
+    return hip
+
+
+# ------------------------------------------------------------------ goldens
+@pytest.mark.parametrize("name", GOLDEN_CASES)
+def test_spmm_matches_reference_golden(gpu, oracle, name):
+    """X = [ones, x_rand, 2 x_rand - 1]: columns 0 and 1 are the compiled reference's y_ones / y_rand."""
+    g = load_golden(name)
+    csr = sp.convert_in_csr(sp.read_matrix_market(golden_path(name)))
+    xr = np.asarray(g["x_rand"], dtype=np.float64)
+    X = np.column_stack([np.ones(csr.N), xr, 2.0 * xr - 1.0])
+    with sp.CsrDevice.from_host(csr) as dev:
+        Y = dev.spmm(X)
+    assert Y.shape == (csr.M, 3)
+    for j, key in ((0, "y_ones"), (1, "y_rand")):
+        assert_parity(Y[:, j], g[key], csr.row_ptr, csr.col_idx, csr.values, X[:, j], what=f"{name}/{key}")
+    check_columns(oracle, Y, X, np.asarray(csr.row_ptr), np.asarray(csr.col_idx), np.asarray(csr.values), name)
+
+
+# ------------------------------------------------------------------ seeded matrices
+def _seeded_cases(dtype):
+    rng = np.random.default_rng(31)
+    M, N = 3000, 30000
+    rp, col, val = random_csr(rng, M, N, 14, 60, 0.05, dtype=dtype)
+    # rows longer than the stage (2048) and than one piece (8192): the pieces path
+    rp, col, val = with_long_rows(rng, rp, col, val, N, [5, 1700, 2999], [2500, 9000, 20000])
+    yield "random", M, N, rp, col, val
+    M = N = 8000
+    rp, col, val = banded_csr(rng, M, N, 20, 150, empty_frac=0.1, dtype=dtype, far_frac=0.05)
+    rp, col, val = with_long_rows(rng, rp, col, val, N, [0, 4000], [2100, 7999])
+    yield "banded", M, N, rp, col, val
+
+
+@pytest.mark.parametrize("dtype,ks", [(np.float64, K_F64), (np.float32, K_F32)])
+def test_spmm_seeded_matrices_every_k(gpu, oracle, dtype, ks):
+    rng = np.random.default_rng(7)
+    for what, M, N, rp, col, val in _seeded_cases(dtype):
+        with sp.CsrDevice(M, N, rp, col, val) as dev:
+            assert dev.info()["long_rows"] >= 2
+            for k in ks:
+                X = rng.uniform(-1, 1, (N, k)).astype(dtype)
+                check_columns(oracle, dev.spmm(X), X, rp, col, val, f"{what} {np.dtype(dtype).name} k={k}")
+
+
+# ------------------------------------------------------------------ every plan kind of a handle
+def _plan_cases():
+    from sparsematrixvectormultiplication_amd import synth
+    rng = np.random.default_rng(17)
+    rp, col, val = banded_csr(rng, 20000, 20000, 22, 150)
+    yield "x-window", 20000, 20000, rp, col, val, {}, lambda i: i["local_blocks"] > 0 and i["pattern_slots"] == 0
+    M, rp, col, val = synth.kkt_like((24, 24, 25), 5)
+    yield "pattern", M, M, rp, col, val, {"local_patterns": 1}, lambda i: i["local_blocks"] > 0 and i["pattern_slots"] > 0
+    M, N = 7001, 2_000_003
+    lens = rng.poisson(18, M).astype(np.int64)
+    rows = np.repeat(np.arange(M), lens)
+    c = rng.integers(0, N, int(lens.sum()))
+    order = np.lexsort((c, rows))
+    rp = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    yield ("tile", M, N, rp, c[order].astype(np.int32), rng.uniform(-1, 1, rp[-1]), {"stream_tile": 1},
+           lambda i: i["tile_blocks"] > 0 and i["local_blocks"] == 0)
+    M = N = 40_000
+    lens = np.minimum(rng.poisson(9, M), 14).astype(np.int64)
+    rows = np.repeat(np.arange(M), lens)
+    c = rng.integers(0, N, int(lens.sum()))
+    order = np.lexsort((c, rows))
+    rp = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    yield ("gather", M, N, rp, c[order].astype(np.int32), rng.uniform(-1, 1, rp[-1]), {},
+           lambda i: i["local_blocks"] == 0 and i["tile_blocks"] == 0)
+
+
+def test_spmm_on_handles_with_every_plan_kind(gpu, oracle):
+    rng = np.random.default_rng(3)
+    for what, M, N, rp, col, val, knobs, has_plan in _plan_cases():
+        with tuned(**knobs):
+            dev = sp.CsrDevice(M, N, rp, col, val)
+        with dev:
+            info = dev.info()
+            assert has_plan(info), (what, {k: info[k] for k in ("local_blocks", "pattern_slots", "tile_blocks")})
+            for k in (1, 3, 8, 40):
+                X = rng.uniform(-1, 1, (N, k))
+                Y = dev.spmm(X)
+                check_columns(oracle, Y, X, rp, col, val, f"{what} k={k}")
+            x = X[:, 0].copy()
+            assert dev.spmm(x).ravel().tobytes() == dev.spmv(x, sp.CSR_AUTO).tobytes(), what
+
+
+# ------------------------------------------------------------------ k = 1, determinism, caller buffers
+def test_spmm_k1_is_spmv_and_results_are_reproducible(gpu, oracle):
+    rng = np.random.default_rng(21)
+    M, N = 5000, 5200
+    rp, col, val = random_csr(rng, M, N, 25, 80, 0.02)
+    rp, col, val = with_long_rows(rng, rp, col, val, N, [100], [5000])
+    lib = sp.lib()
+    hip = hip_runtime()
+    with sp.CsrDevice(M, N, rp, col, val) as dev:
+        x = rng.uniform(-1, 1, N)
+        assert dev.spmm(x).shape == (M, 1)
+        assert dev.spmm(x).ravel().tobytes() == dev.spmv(x, sp.CSR_AUTO).tobytes()
+        assert dev.spmm(x[:, None]).ravel().tobytes() == dev.spmv(x, sp.CSR_AUTO).tobytes()
+        for k in (3, 8, 33):
+            X = rng.uniform(-1, 1, (N, k))
+            Y = dev.spmm(X)
+            assert dev.spmm(X).tobytes() == Y.tobytes(), f"k={k}: result changed between calls"
+            # Fortran-ordered input: converted to C order first
+            assert dev.spmm(np.asfortranarray(X)).tobytes() == Y.tobytes()
+            # caller buffers and a stream of the caller's == the host entry point
+            dx, dy = C.c_void_p(), C.c_void_p()
+            assert lib.spmv_hip_malloc(C.byref(dx), N * k * 8) == 0 and lib.spmv_hip_malloc(C.byref(dy), M * k * 8) == 0
+            stream = C.c_void_p()
+            try:
+                assert lib.spmv_hip_memcpy_h2d(dx, X.ctypes.data_as(C.c_void_p), N * k * 8) == 0
+                assert lib.spmv_hip_memset(dy, 0xFF, M * k * 8) == 0  # NaN everywhere
+                assert hip.hipStreamCreate(C.byref(stream)) == 0
+                dev.spmm_on(dx.value, dy.value, k, stream=stream.value)
+                assert hip.hipStreamSynchronize(stream) == 0
+                out = np.empty((M, k))
+                assert lib.spmv_hip_memcpy_d2h(out.ctypes.data_as(C.c_void_p), dy, M * k * 8) == 0
+                assert out.tobytes() == Y.tobytes(), f"k={k}: spmm_on on a caller stream"
+                dev.spmm_on(dx.value, dy.value, k)  # the library's stream
+                assert lib.spmv_hip_memcpy_d2h(out.ctypes.data_as(C.c_void_p), dy, M * k * 8) == 0
+                assert out.tobytes() == Y.tobytes(), f"k={k}: spmm_on on the library stream"
+            finally:
+                if stream.value:
+                    hip.hipStreamDestroy(stream)
+                lib.spmv_hip_free(dx)
+                lib.spmv_hip_free(dy)
+        ms = dev.time_spmm(8, warmup=2, iters=5)
+        assert ms.shape == (5,) and np.all(ms > 0) and np.all(ms < 1e3)
+
+
+# ------------------------------------------------------------------ row blocks
+def test_spmm_row_block_handles_fill_one_shared_y(gpu, oracle):
+    rng = np.random.default_rng(8)
+    M, N, k = 6000, 6000, 5
+    rp, col, val = random_csr(rng, M, N, 20, 50, 0.05)
+    rp, col, val = with_long_rows(rng, rp, col, val, N, [10, 3333], [3000, 4500])
+    X = rng.uniform(-1, 1, (N, k))
+    with sp.CsrDevice(M, N, rp, col, val) as whole:
+        Y_ref = whole.spmm(X)
+    bounds = sp.partition_rows(rp, 8)
+    lib = sp.lib()
+    dx, dy = C.c_void_p(), C.c_void_p()
+    assert lib.spmv_hip_malloc(C.byref(dx), N * k * 8) == 0 and lib.spmv_hip_malloc(C.byref(dy), M * k * 8) == 0
+
+    def download():
+        out = np.empty((M, k))
+        assert lib.spmv_hip_memcpy_d2h(out.ctypes.data_as(C.c_void_p), dy, M * k * 8) == 0
+        return out
+
+    try:
+        assert lib.spmv_hip_memcpy_h2d(dx, X.ctypes.data_as(C.c_void_p), N * k * 8) == 0
+        assert lib.spmv_hip_memset(dy, 0xFF, M * k * 8) == 0  # NaN everywhere
+        for p in range(8):
+            lo, hi = int(bounds[p]), int(bounds[p + 1])
+            with sp.CsrDevice(M, N, rp, col, val, lo, hi) as dev:
+                before = download()
+                dev.spmm_on(dx.value, dy.value, k)
+                sp.hip_sync()
+                after = download()
+                outside = np.ones(M, bool)
+                outside[lo:hi] = False
+                assert after[outside].tobytes() == before[outside].tobytes(), f"block {p} wrote outside its rows"
+                assert np.all(np.isnan(after[hi:])) and np.all(np.isfinite(after[lo:hi]))  # later blocks' rows: untouched
+                # the host entry point writes only the handle's rows of Y_host
+                Yh = dev.spmm(X)
+                assert np.all(Yh[outside] == 0)
+                assert Yh[lo:hi].tobytes() == after[lo:hi].tobytes()
+        Y = download()
+    finally:
+        lib.spmv_hip_free(dx)
+        lib.spmv_hip_free(dy)
+    assert np.all(np.isfinite(Y))
+    for j in range(k):
+        assert_parity(Y[:, j], Y_ref[:, j], rp, col, val, X[:, j], what=f"row blocks column {j}")
+    check_columns(oracle, Y, X, rp, col, val, "row blocks")
+
+
+# ------------------------------------------------------------------ full size
+def test_spmm_full_size_nlpkkt_like(gpu, oracle):
+    from sparsematrixvectormultiplication_amd import synth
+    M, rp, col, val = synth.kkt_like()
+    rng = np.random.default_rng(4)
+    with sp.CsrDevice(M, M, rp, col, val) as dev:
+        for k in (8, 33):
+            X = rng.uniform(-1, 1, (M, k))
+            Y = dev.spmm(X)
+            cols = range(k) if k == 8 else (0, 16, 32)
+            for j in cols:
+                y = dev.spmv(np.ascontiguousarray(X[:, j]))
+                scale = np.max(np.abs(y))
+                assert np.max(np.abs(Y[:, j] - y)) <= 1e-12 * scale, f"k={k} column {j} vs spmv"
+            if k == 8:
+                for lo in (0, M // 2 - 5000, M - 10000):
+                    hi = lo + 10000
+                    e0, e1 = rp[lo], rp[hi]
+                    srp = (rp[lo:hi + 1] - e0).astype(np.int32)
+                    for j in range(k):
+                        ref = oracle.csr_serial(srp, col[e0:e1], val[e0:e1], X[:, j])
+                        assert_parity(Y[lo:hi, j], ref, srp, col[e0:e1], val[e0:e1], X[:, j],
+                                      what=f"rows {lo}..{hi} column {j}")
+
+
+# ------------------------------------------------------------------ errors
+def test_spmm_errors_leave_the_handle_usable(gpu, oracle):
+    rng = np.random.default_rng(2)
+    M, N = 2000, 2100
+    rp, col, val = random_csr(rng, M, N, 12, 40, 0.0)
+    x = rng.uniform(-1, 1, N)
+    y_ref = oracle.csr_serial(rp, col, val, x)
+    lib = sp.lib()
+    with sp.CsrDevice(M, N, rp, col, val) as dev:
+        dx, dy = C.c_void_p(), C.c_void_p()
+        assert lib.spmv_hip_malloc(C.byref(dx), N * 8 * 4 + 64) == 0 and lib.spmv_hip_malloc(C.byref(dy), M * 8 * 4 + 64) == 0
+        try:
+            with pytest.raises(sp.SpmvHipError, match="k = 0"):
+                dev.spmm_on(dx.value, dy.value, 0)
+            with pytest.raises(sp.SpmvHipError, match="aligned"):
+                dev.spmm_on(dx.value + 4, dy.value, 4)
+            with pytest.raises(sp.SpmvHipError, match="aligned"):
+                dev.spmm_on(dx.value, dy.value + 2, 4)
+            with pytest.raises(sp.SpmvHipError, match="NULL"):
+                dev.spmm_on(0, dy.value, 4)
+            with pytest.raises(sp.SpmvHipError):
+                dev.time_spmm(0)
+        finally:
+            lib.spmv_hip_free(dx)
+            lib.spmv_hip_free(dy)
+        assert_parity(dev.spmv(x), y_ref, rp, col, val, x, what="SpMV after the refused calls")
+        X = rng.uniform(-1, 1, (N, 4))
+        check_columns(oracle, dev.spmm(X), X, rp, col, val, "SpMM after the refused calls")
