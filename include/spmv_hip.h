@@ -340,6 +340,19 @@ int spmv_hip_hll_run_on(spmv_hll_dev *m, int variant, const void *d_x, void *d_y
 int spmv_hip_hll_time(spmv_hll_dev *m, int variant, int warmup, int iters, int zero_y,
                       float *ms_each);
 
+/* ---- HLL: several vectors per pass over the slab (SpMM) ------------------- */
+/* Y = A X for k vectors at once, fp64.  X: N x k, Y: M_total x k, both row-major (element (i, j) at i * k + j).  The
+ * handle writes rows [row0, row0 + M_local) of Y and no other row (hack-range handles and device-built slabs alike).
+ * Each slot of the slab is read from HBM once per call, whatever k is; padding slots are multiplied like real ones, as
+ * in every HLL SpMV kernel.  k = 1 is exactly spmv_hip_hll_run_on(m, SPMV_HLL_AUTO, ...) (same bits).  Results are a
+ * fixed sequence of adds that depends on the slab and k only (no atomics; 16-byte and element loads of X / Y add in
+ * the same order).  -1 for k < 1, NULL arguments or X / Y not aligned to 8 bytes (the HIP error state stays clean). */
+int spmv_hip_hll_spmm_on(spmv_hll_dev *m, int k, const void *d_X, void *d_Y, void *stream); /* NULL stream = library's */
+/* host arrays; syncs; copies back only the handle's rows of Y_host */
+int spmv_hip_hll_spmm(spmv_hll_dev *m, int k, const double *X_host, double *Y_host);
+/* the reference timing protocol of spmv_hip_hll_time, for the k-vector product on library-owned scratch X / Y */
+int spmv_hip_hll_spmm_time(spmv_hll_dev *m, int k, int warmup, int iters, float *ms_each);
+
 /* ---- multi-GPU: one process per GPU, rows split by nnz ------------------ */
 /* Contiguous nnz-balanced row split for `parts` GPUs: the reference's greedy
  * (prepare_thread_distribution, src/csr_matrix.c:167-266) with fixed-size

@@ -199,6 +199,9 @@ _PROTOTYPES = {
     "spmv_hip_hll_get_y": (C.c_int, [C.c_void_p, c_double_p]),
     "spmv_hip_hll_run_on": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spmv_hip_hll_time": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p]),
+    "spmv_hip_hll_spmm_on": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spmv_hip_hll_spmm": (C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p]),
+    "spmv_hip_hll_spmm_time": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_float_p]),
     "spmv_hip_partition_rows": (C.c_int, [C.c_int, c_int_p, C.c_int, c_int_p]),
     "spmv_hip_comm_scatter_staged": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int,
                                                C.c_void_p]),

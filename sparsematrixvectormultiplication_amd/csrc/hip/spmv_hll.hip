@@ -187,18 +187,24 @@ int hll_finish_handle(spmv_hll_dev *m, int total_rows, int N, const std::vector<
     // what hll_lds gets: .y = rows | slots of the window (from its even base) << 16 -- the kernel then knows how much to
     // stage without first asking the hack tables (0 in the upper half: a single row of more than 65535 slots, which has
     // its own path in the kernel)
+    m->stage_slots = (int)std::min<long long>(kHllCap, (widest + kStreamUnit - 1) / kStreamUnit * kStreamUnit);
+    std::vector<int> long_windows;  // one-row windows longer than the stage: SpMM's hll_spmm_row (spmv_hll_spmm.hip)
     for (int4 &d : hdesc) {
         const int last = d.x + d.y - 1;
         const long long s0 = (((long long)d.w << 32) | (unsigned)d.z) & ~1LL;
         const long long span = off[(size_t)(last / kHack)] + (long long)(last % kHack) * mz[(size_t)(last / kHack)] + mz[(size_t)(last / kHack)] - s0;
+        if (d.y == 1 && span > m->stage_slots) long_windows.push_back((int)(&d - hdesc.data()));
         d.y |= span <= 0xffff ? (int)span << 16 : 0;
     }
     m->num_blocks = (int)hdesc.size();
-    m->stage_slots = (int)std::min<long long>(kHllCap, (widest + kStreamUnit - 1) / kStreamUnit * kStreamUnit);
     int rc = 0;
     if (!m->hack_off) rc |= upload_array(&m->hack_off, off.data(), off.size(), 0);
     if (!rc && upload_maxnz) rc |= upload_array(&m->maxnz, mz.data(), mz.size(), 1);
     if (!rc) rc |= upload_array(&m->hdesc, hdesc.data(), hdesc.size(), 1);
+    if (!rc && !long_windows.empty()) {
+        rc |= upload_array(&m->long_windows, long_windows.data(), long_windows.size(), 0);
+        if (!rc) m->num_long_windows = (int)long_windows.size();
+    }
     if (!rc) {
         const size_t x_bytes = std::max<size_t>((size_t)N, 1) * sizeof(double) + kLineBytes;  // whole-line reads
         hipError_t e = hipMalloc((void **)&m->x, x_bytes);
@@ -208,7 +214,7 @@ int hll_finish_handle(spmv_hll_dev *m, int total_rows, int N, const std::vector<
         if (e != hipSuccess) rc = fail("hipMalloc(x/y) failed: %s", hipGetErrorString(e));
     }
     m->device_bytes = off.size() * 8 + mz.size() * 4 + ((size_t)off[H] + kPad) * 12 + hdesc.size() * 16 +
-                      ((size_t)N + (size_t)total_rows) * 8;
+                      long_windows.size() * 4 + ((size_t)N + (size_t)total_rows) * 8;
     // the x-window kernel: windows of 2048 slots, 16-bit local JA (needs the slab on the host)
     if (!rc && ja_host && g_stream_local && true_slots > 0) {
         std::vector<int4> plain;
@@ -811,6 +817,7 @@ extern "C" void spmv_hip_hll_free(spmv_hll_dev *m) {
     (void)hipFree(m->JA);
     (void)hipFree(m->AS);
     (void)hipFree(m->hdesc);
+    (void)hipFree(m->long_windows);
     (void)hipFree(m->ldesc4);
     (void)hipFree(m->ldesc);
     (void)hipFree(m->lines);

@@ -286,6 +286,8 @@ struct spmv_hll_dev {
     int4 *hdesc = nullptr;  // [num_blocks] {first row, rows, first slot lo, first slot hi}
     int num_blocks = 0;
     int stage_slots = kHllCap;  // LDS stage of hll_lds: the largest workgroup, <= kHllCap
+    int *long_windows = nullptr;  // [num_long_windows] hdesc windows of one row longer than the stage (SpMM: hll_spmm_row)
+    int num_long_windows = 0;
     // hll_lds_local (x window in LDS): own windows, 16-bit local JA
     int4 *ldesc4 = nullptr;
     int4 *ldesc = nullptr;  // {first line, lines, slots of the window from its even base, 0}

@@ -483,3 +483,32 @@ class HllDevice(_Handle):
                                            int(bool(zero_y)), ms.ctypes.data_as(nat.c_float_p)),
                "hll_time")
         return ms
+
+    def spmm(self, X):
+        """Y = A X for the k columns of X (N x k float64, or a vector of N: k = 1) in one pass over the slab
+        (spmv_hip_hll_spmm).  Returns an (M_total, k) array; rows outside the handle's are zero."""
+        X = np.asarray(X)
+        if X.dtype != np.float64:
+            raise ValueError(f"X has dtype {X.dtype}, HLL handles hold float64")
+        if X.ndim == 1:
+            X = X.reshape(-1, 1)
+        if X.ndim != 2 or X.shape[0] != self.N or X.shape[1] < 1:
+            raise ValueError(f"X must be {self.N} x k with k >= 1, got shape {X.shape}")
+        X = np.ascontiguousarray(X)
+        Y = np.zeros((self.M, X.shape[1]), dtype=np.float64)
+        _check(nat.lib().spmv_hip_hll_spmm(self.h, int(X.shape[1]), X.ctypes.data_as(nat.c_double_p),
+                                           Y.ctypes.data_as(nat.c_double_p)), "spmv_hip_hll_spmm")
+        return Y
+
+    def spmm_on(self, d_X: int, d_Y: int, k: int, stream: int = 0):
+        """Y = A X on device buffers (row-major N x k and M_total x k float64, e.g. spmv_hip_malloc or a torch
+        tensor's data_ptr()), asynchronous on `stream` (0 = the library's)."""
+        _check(nat.lib().spmv_hip_hll_spmm_on(self.h, int(k), C.c_void_p(d_X), C.c_void_p(d_Y), C.c_void_p(stream)),
+               "spmv_hip_hll_spmm_on")
+
+    def time_spmm(self, k, warmup=5, iters=95):
+        """Per-launch milliseconds of the k-vector product on library-owned X / Y (spmv_hip_hll_spmm_time)."""
+        ms = np.zeros(iters, dtype=np.float32)
+        _check(nat.lib().spmv_hip_hll_spmm_time(self.h, int(k), int(warmup), int(iters),
+                                                ms.ctypes.data_as(nat.c_float_p)), "hll_spmm_time")
+        return ms
