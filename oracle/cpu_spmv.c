@@ -160,4 +160,24 @@ void oracle_csr_row_abs_sums(const int num_row, const int *row_ptr, const int *c
     }
 }
 
+/* the same for fp32 data (products exact in double); returns the smallest
+ * nonzero |a_ij * x_j| of the whole matrix, 0 when every product is 0 -- the
+ * fp32 row gate is rigorous only while no fp32 product is subnormal */
+double oracle_csr_f32_row_abs_sums(const int num_row, const int *row_ptr, const int *col_idx,
+                                   const float *values, const float *x, double *out) {
+    double smallest = 0.0;
+    for (int r = 0; r < num_row; ++r) {
+        double acc = 0.0;
+        const int stop = row_ptr[r + 1];
+        for (int e = row_ptr[r]; e < stop; ++e) {
+            double p = (double)values[e] * (double)x[col_idx[e]];
+            p = p < 0 ? -p : p;
+            acc += p;
+            if (p > 0 && (smallest == 0.0 || p < smallest)) smallest = p;
+        }
+        out[r] = acc;
+    }
+    return smallest;
+}
+
 int oracle_max_threads(void) { return omp_get_max_threads(); }

@@ -60,6 +60,8 @@ class Oracle:
             L.oracle_csr_row_abs_sums.argtypes = [C.c_int, _ip, _ip, _dp, _dp, _dp]
             L.oracle_csr_row_abs_sums.restype = None
             L.oracle_max_threads.restype = C.c_int
+            L.oracle_csr_f32_row_abs_sums.argtypes = [C.c_int, _ip, _ip, nat.c_float_p, nat.c_float_p, _dp]
+            L.oracle_csr_f32_row_abs_sums.restype = C.c_double
 
     # K1 -- the oracle proper
     def csr_serial(self, row_ptr, col_idx, values, x):
@@ -118,6 +120,18 @@ class Oracle:
                                        col_idx.ctypes.data_as(_ip), values.ctypes.data_as(_dp),
                                        x.ctypes.data_as(_dp), out.ctypes.data_as(_dp))
         return out
+
+    def f32_row_abs_sums(self, row_ptr, col_idx, values_f32, x_f32):
+        """(per-row sum of |a_ij x_j|, smallest nonzero |a_ij x_j| or 0) of fp32 data, products in double."""
+        row_ptr, col_idx = _arr(row_ptr, np.int32), _arr(col_idx, np.int32)
+        values_f32, x_f32 = _arr(values_f32, np.float32), _arr(x_f32, np.float32)
+        out = np.zeros(len(row_ptr) - 1, dtype=np.float64)
+        smallest = self.L.oracle_csr_f32_row_abs_sums(len(out), row_ptr.ctypes.data_as(_ip),
+                                                      col_idx.ctypes.data_as(_ip),
+                                                      values_f32.ctypes.data_as(nat.c_float_p),
+                                                      x_f32.ctypes.data_as(nat.c_float_p),
+                                                      out.ctypes.data_as(_dp))
+        return out, float(smallest)
 
     def max_threads(self):
         return self.L.oracle_max_threads()

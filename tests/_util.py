@@ -45,6 +45,141 @@ def assert_parity(y, y_ref, row_ptr, col_idx, values, x, rtol=FP64_RTOL, what=""
                            f"{bad[0]}: |d| = {d[bad[0]]:.3e}, bound = {bound[bad[0]]:.3e}")
 
 
+# ---- the exact fp32 row gate.  fp32 x fp32 products are exact in fp64, so the oracle (csr_f32_accum64) is the exact
+# row sum up to its own fp64 summation error.  A kernel's fp32 result -- any summation tree, with or without FMA,
+# partial sums added later -- holds the standard order-independent bound (Higham, Accuracy and Stability of Numerical
+# Algorithms, 2nd ed., section 4.2):
+#   |y_i - ref_i| <= (gamma32(n_i) + gamma64(n_i)) * sum_j |a_ij x_j|,  gamma(n) = n u / (1 - n u)
+# with n_i the entries of row i, u32 = 2^-24, u64 = 2^-53.  Rigorous while no product underflows and nothing
+# overflows; the helper asserts that of its inputs.  An empty row (or one whose products are all 0) must be exactly 0.
+U32, U64 = 2.0 ** -24, 2.0 ** -53
+F32_MIN_NORMAL = float(np.finfo(np.float32).tiny)   # 2^-126
+F32_MAX = float(np.finfo(np.float32).max)
+
+
+def gamma(n, u):
+    n = np.asarray(n, dtype=np.float64)
+    return n * u / (1.0 - n * u)
+
+
+def f32_row_bound(row_ptr, col_idx, values, x):
+    """Per-row bound of the fp32 gate (the inputs checked: finite, no subnormal fp32 product, no overflow)."""
+    values = np.asarray(values)
+    x = np.asarray(x)
+    assert values.dtype == np.float32 and x.dtype == np.float32, "the fp32 gate takes fp32 data"
+    assert np.all(np.isfinite(values)) and np.all(np.isfinite(x)), "fp32 gate: non-finite input"
+    from oracle.oracle import Oracle
+    sums, smallest = _oracle(Oracle).f32_row_abs_sums(row_ptr, col_idx, values, x)
+    assert smallest == 0.0 or smallest >= F32_MIN_NORMAL, \
+        f"fp32 gate: a product |a_ij x_j| = {smallest:.3e} is subnormal in fp32; the bound does not hold"
+    assert sums.size == 0 or sums.max() * (1.0 + 2.0 ** -10) < F32_MAX, "fp32 gate: a row sum overflows fp32"
+    n = np.diff(np.asarray(row_ptr, dtype=np.int64))
+    # (sums is itself an fp64 sum of n terms and |y - ref| is rounded once more: the last factor covers both)
+    return (gamma(n, U32) + gamma(n, U64)) * sums * (1.0 + 4.0 * gamma(n + 2, U64))
+
+
+_ORACLE = []
+
+
+def _oracle(cls):
+    if not _ORACLE:
+        _ORACLE.append(cls())
+    return _ORACLE[0]
+
+
+def assert_parity_f32(y, y_ref, row_ptr, col_idx, values, x, what=""):
+    """Every row of an fp32 result against the fp64-accumulated oracle (y_ref = oracle.csr_f32_accum64), within the
+    rigorous fp32 summation bound above; results finite."""
+    y = np.asarray(y)
+    y_ref = np.asarray(y_ref, dtype=np.float64)
+    assert y.shape == y_ref.shape, f"{what}: shape {y.shape} vs {y_ref.shape}"
+    assert len(row_ptr) == y.size + 1, f"{what}: row_ptr has {len(row_ptr)} entries for {y.size} rows"
+    if y.size == 0:
+        return
+    assert np.all(np.isfinite(y)), f"{what}: non-finite result in row {np.flatnonzero(~np.isfinite(y))[0]}"
+    bound = f32_row_bound(row_ptr, col_idx, values, x)
+    d = np.abs(y.astype(np.float64) - y_ref)
+    bad = np.flatnonzero(d > bound)
+    assert bad.size == 0, (f"{what}: {bad.size} rows beyond the fp32 summation bound; first row {bad[0]} "
+                           f"({int(row_ptr[bad[0] + 1]) - int(row_ptr[bad[0]])} entries): y = {float(y[bad[0]])!r}, "
+                           f"ref = {y_ref[bad[0]]!r}, |d| = {d[bad[0]]:.3e}, bound = {bound[bad[0]]:.3e}")
+
+
+# ---- wide-range data and power-of-two scaling.  Every kernel's result is a fixed sequence of adds that depends on the
+# matrix structure only, so with D_r, D_c diagonal matrices of +-2^e (exact in IEEE arithmetic while nothing under- or
+# overflows, whatever the order of the adds and whether they are fused):  y(D_r A D_c^-1, D_c x) == D_r y(A, x), bit
+# for bit.  A term from the wrong row or the wrong column breaks that however small it is.
+WIDE_EXP = {np.dtype(np.float32): 40, np.dtype(np.float64): 300}
+
+
+CHUNK = 1 << 24   # (entries per step: the full-size matrices hold 2.6e8)
+
+
+def wide_range(rng, n, dtype):
+    """n values with random signs and magnitudes spread over [2^-8, 1]."""
+    out = np.empty(n, dtype=dtype)
+    for s in range(0, n, CHUNK):
+        m = min(CHUNK, n - s)
+        mag = np.exp2(-8.0 * rng.random(m))
+        out[s:s + m] = np.where(rng.random(m) < 0.5, -mag, mag)
+    return out
+
+
+def scaling(rng, M, N, dtype):
+    """(d_r, d_c): random +-2^e for every row and column, e within WIDE_EXP of the dtype."""
+    e = WIDE_EXP[np.dtype(dtype)]
+    dr = np.ldexp(np.where(rng.random(M) < 0.5, -1.0, 1.0), rng.integers(-e, e + 1, M))
+    dc = np.ldexp(np.where(rng.random(N) < 0.5, -1.0, 1.0), rng.integers(-e, e + 1, N))
+    return dr, dc
+
+
+def scaled_copy(row_ptr, col_idx, values, x, dr, dc):
+    """(D_r A D_c^-1 values, D_c x) in the data's dtype; asserts every entry stays a normal number (which makes the
+    scaling exact) and that the scaling is undone exactly."""
+    values = np.asarray(values)
+    dtype = values.dtype
+    tiny, big = np.finfo(dtype).tiny, np.finfo(dtype).max / 2.0 ** 20
+    row_ptr = np.asarray(row_ptr, dtype=np.int64)
+    v = np.empty_like(values)
+    r0 = 0
+    while r0 < len(row_ptr) - 1:          # whole rows, about CHUNK entries at a time
+        r1 = max(r0 + 1, int(np.searchsorted(row_ptr, row_ptr[r0] + CHUNK, side="right")) - 1)
+        r1 = min(r1, len(row_ptr) - 1)
+        e0, e1 = int(row_ptr[r0]), int(row_ptr[r1])
+        f = dr[np.repeat(np.arange(r0, r1), np.diff(row_ptr[r0:r1 + 1]))] / dc[col_idx[e0:e1]]
+        a = values[e0:e1].astype(np.float64)
+        out = (a * f).astype(dtype)
+        m = np.abs(out)
+        assert np.all(np.isfinite(out)) and np.all((m >= tiny) & (m <= big)), "scaled values leave the normal range"
+        assert np.array_equal(out.astype(np.float64) / f, a), "the scaling of the values is not exact"
+        v[e0:e1] = out
+        r0 = r1
+    xs = (np.asarray(x, dtype=np.float64) * dc).astype(dtype)
+    m = np.abs(xs)
+    assert np.all(np.isfinite(xs)) and np.all((m >= tiny) & (m <= big)), "scaled x leaves the normal range"
+    assert np.array_equal(xs.astype(np.float64) / dc, np.asarray(x, dtype=np.float64)), "the scaling of x is not exact"
+    return v, xs
+
+
+def scale_rows(y, dr):
+    """D_r y in y's dtype (exact: power-of-two factors, asserted to stay within the normal range or exactly 0)."""
+    y = np.asarray(y)
+    out = (y.astype(np.float64) * dr.reshape((-1,) + (1,) * (y.ndim - 1))).astype(y.dtype)
+    m = np.abs(out)
+    assert np.all(np.isfinite(out)) and np.all((m == 0) | (m >= np.finfo(y.dtype).tiny)), "D_r y leaves the normal range"
+    return out
+
+
+def assert_same_numbers(a, b, what=""):
+    """a == b element by element (+0 equals -0), no NaN anywhere."""
+    a, b = np.asarray(a), np.asarray(b)
+    assert a.shape == b.shape and a.dtype == b.dtype, f"{what}: {a.shape} {a.dtype} vs {b.shape} {b.dtype}"
+    assert not np.isnan(a).any() and not np.isnan(b).any(), f"{what}: NaN"
+    bad = np.flatnonzero((a != b).reshape(-1))
+    assert bad.size == 0, (f"{what}: {bad.size} of {a.size} elements differ; first at flat index {bad[0]}: "
+                           f"{a.reshape(-1)[bad[0]]!r} vs {b.reshape(-1)[bad[0]]!r}")
+
+
 def random_csr(rng, M, N, mean_row, max_row=None, empty_frac=0.0, dtype=np.float64):
     """Random CSR with sorted, distinct columns per row."""
     max_row = min(N, max_row or max(1, 4 * mean_row))

@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 import sparsematrixvectormultiplication_amd as sp
-from _util import FP32_NORMWISE_RTOL, assert_parity, coo_from_csr, random_csr
+from _util import FP32_NORMWISE_RTOL, assert_parity, assert_parity_f32, coo_from_csr, random_csr
 from conftest import GOLDEN_CASES, golden_path, load_golden
 
 pytestmark = pytest.mark.gpu
@@ -111,6 +111,7 @@ def test_stream_kernel_block_shapes_repeatable(gpu, oracle, mean, dtype):
                         else:
                             err = np.max(np.abs(y.astype(np.float64) - y_ref)) / np.max(np.abs(y_ref))
                             assert err <= FP32_NORMWISE_RTOL, f"cap={cap} kind={walk}: {err:.3e}"
+                            assert_parity_f32(y, y_ref, row_ptr, col, val, x, what=f"cap={cap} kind={walk} rep={rep}")
                         if first is None:
                             first = y
                         assert y.tobytes() == first.tobytes(), "result changed between launches"
@@ -209,9 +210,11 @@ def test_csr_fp32_matches_f64_accumulated_oracle(gpu, oracle):
     with sp.CsrDevice(M, N, row_ptr, col, val) as dev:
         assert dev.info()["value_bytes"] == 4
         for vname, variant in CSR_V:
-            y = dev.spmv(x, variant).astype(np.float64)
+            y32 = dev.spmv(x, variant)
+            y = y32.astype(np.float64)
             err = np.max(np.abs(y - y_ref)) / np.max(np.abs(y_ref))
             assert err <= FP32_NORMWISE_RTOL, f"fp32 {vname}: {err:.3e}"
+            assert_parity_f32(y32, y_ref, row_ptr, col, val, x, what=f"fp32 {vname}")
 
 
 # ----------------------------------------------------- API / protocol
@@ -344,6 +347,8 @@ def test_full_size_properties_nlpkkt_like(gpu, oracle):
             rp = (row_ptr[lo:hi + 1] - e0).astype(np.int32)
             ref = oracle.csr_serial(rp, col[e0:e1], val[e0:e1], x1)
             assert_parity(y1[lo:hi], ref, rp, col[e0:e1], val[e0:e1], x1, what=f"rows {lo}..{hi}")
+        # ... and on every row
+        assert_parity(y1, oracle.csr_serial(row_ptr, col, val, x1), row_ptr, col, val, x1, what="every row")
 
 
 def test_powerlaw_fp32_with_many_long_rows(gpu, oracle):
@@ -362,8 +367,10 @@ def test_powerlaw_fp32_with_many_long_rows(gpu, oracle):
         info = dev.info()
         assert info["long_rows"] > 0
         for vname, variant in (("stream", sp.CSR_STREAM), ("subwave", sp.CSR_SUBWAVE)):
-            y = dev.spmv(x, variant).astype(np.float64)
+            y32 = dev.spmv(x, variant)
+            y = y32.astype(np.float64)
             assert np.max(np.abs(y - y_ref)) <= FP32_NORMWISE_RTOL * scale, vname
+            assert_parity_f32(y32, y_ref, row_ptr, col, val, x, what=f"powerlaw {vname}")
         again = dev.spmv(x, sp.CSR_STREAM)
         assert again.tobytes() == dev.spmv(x, sp.CSR_STREAM).tobytes()  # no atomics: reproducible
 
@@ -521,6 +528,7 @@ def test_x_window_stream_kernel_matches_oracle_and_gather_kernel(gpu, oracle, dt
             else:
                 err = np.max(np.abs(y.astype(np.float64) - y_ref)) / np.max(np.abs(y_ref))
                 assert err <= FP32_NORMWISE_RTOL
+                assert_parity_f32(y, y_ref, row_ptr, col, val, x, what=f"x-window mean={mean}")
     finally:
         set_tuning("local_cap", 0)
         set_tuning("stream_kind", -1)
@@ -583,6 +591,7 @@ def test_x_window_plan_keeps_going_past_a_few_scattered_rows(gpu, oracle):
                 else:
                     ref = oracle.csr_f32_accum64(rp, c2, v2, x)
                     assert np.max(np.abs(y.astype(np.float64) - ref)) / np.max(np.abs(ref)) <= FP32_NORMWISE_RTOL
+                    assert_parity_f32(y, ref, rp, c2, v2, x, what=f"scattered rows {vname}")
 
 
 def test_auto_picks_lane_groups_for_mid_size_scattered_matrices_in_both_formats(gpu, oracle):

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import sparsematrixvectormultiplication_amd as sp
-from _util import FP32_NORMWISE_RTOL, assert_parity, banded_csr, random_csr
+from _util import FP32_NORMWISE_RTOL, assert_parity, assert_parity_f32, banded_csr, random_csr
 from conftest import GOLDEN_CASES, golden_path, load_golden
 
 pytestmark = pytest.mark.gpu
@@ -42,6 +42,8 @@ def check_columns(oracle, Y, X, rp, col, val, what, rows=None):
             y = Y[lo:hi, j].astype(np.float64)
             scale = max(np.max(np.abs(ref)), 1e-30) if ref.size else 1.0
             assert ref.size == 0 or np.max(np.abs(y - ref)) <= FP32_NORMWISE_RTOL * scale, f"{what} column {j}"
+            assert_parity_f32(Y[lo:hi, j], ref, rp[lo:hi + 1] - rp[lo], col[rp[lo]:rp[hi]], val[rp[lo]:rp[hi]], x,
+                              what=f"{what} column {j}")
         else:
             ref = oracle.csr_serial(rp, col, val, x)
             assert_parity(Y[lo:hi, j], ref[lo:hi], rp[lo:hi + 1] - rp[lo], col[rp[lo]:rp[hi]], val[rp[lo]:rp[hi]], x,
@@ -267,6 +269,10 @@ def test_spmm_full_size_nlpkkt_like(gpu, oracle):
                         ref = oracle.csr_serial(srp, col[e0:e1], val[e0:e1], X[:, j])
                         assert_parity(Y[lo:hi, j], ref, srp, col[e0:e1], val[e0:e1], X[:, j],
                                       what=f"rows {lo}..{hi} column {j}")
+                # ... and every row of every column
+                for j in range(k):
+                    x = np.ascontiguousarray(X[:, j])
+                    assert_parity(Y[:, j], oracle.csr_serial(rp, col, val, x), rp, col, val, x, what=f"every row, column {j}")
 
 
 # ------------------------------------------------------------------ errors

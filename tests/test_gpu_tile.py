@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import sparsematrixvectormultiplication_amd as sp
-from _util import FP32_NORMWISE_RTOL, assert_parity
+from _util import FP32_NORMWISE_RTOL, assert_parity, assert_parity_f32
 from conftest import GOLDEN_CASES, golden_path, load_golden
 from sparsematrixvectormultiplication_amd.device import set_tuning
 
@@ -58,6 +58,7 @@ def check(dev, x, y_ref, rp, col, val, dtype, what):
             assert np.all(np.isfinite(y))
             err = np.max(np.abs(y.astype(np.float64) - y_ref)) / max(np.max(np.abs(y_ref)), 1e-300)
             assert err <= FP32_NORMWISE_RTOL, f"{what}: {err:.3e}"
+            assert_parity_f32(y, y_ref, rp, col, val, x, what=f"{what} rep={rep}")
         first = y if first is None else first
         assert y.tobytes() == first.tobytes(), f"{what}: result changed between launches"
     return first
