@@ -112,9 +112,14 @@ typedef struct {
                                         writes every entry's x value in entry order, csr_tile streams it: "tile_expand") */
     long long pattern_slots; /* CSR: slots held by the pattern tables of an x-window plan (0: the kernel reads the 16-bit slot of
                                 every entry) -- where most rows of a block are their predecessor shifted by a constant the
-                                kernel rebuilds the slots from one table per block and 4 bytes per row ("local_patterns") */
+                                kernel rebuilds the slots from one segment per block: its pattern table and 6 bytes per row
+                                ("local_patterns"); the slots counted are the tables' */
     float pattern_with_us;    /* (auto) what upload measured for its kernel with the pattern plan ... */
     float pattern_without_us; /* ... and without (0 / 0: no plan was built); the plan stays where it is at least 2 % faster */
+    int pattern_segment_max;  /* CSR: bytes of the widest segment kept: the LDS the kernel adds per workgroup */
+    int pattern_segment_cap;  /* CSR: ... and the widest the LDS budget allowed (7 resident workgroups per CU) */
+    long long pattern_table_rows; /* CSR: rows of the blocks whose segment was wider: they rebuild their slots from their
+                                     pattern table (rinfo, row_ptr and the table in memory) */
 } spmv_dev_info;
 
 /* ---- device ------------------------------------------------------------ */
@@ -268,6 +273,10 @@ int spmv_hip_csr_addresses(const spmv_csr_dev *m, unsigned long long *out);
  * `warm` ordinary launches: stamps[3 * b + {0, 1, 2}] = start, end (ticks of the constant 100 MHz clock), dispatch id << 8
  * | XCD of block b; stamps has 3 * local_blocks entries. */
 int spmv_hip_csr_stamp_blocks(spmv_csr_dev *m, int warm, unsigned long long *stamps);
+/* The widest pattern-plan segment (bytes) upload lets an x-window plan keep: its LDS copy beside the stage of
+   max(local_cap * value_bytes, stage_lines * 128) bytes and the (local_cap + 8) 16-bit slots must not cost a resident
+   workgroup of csr_stream_local per CU (at most the 7 its registers allow).  -1 on bad arguments.  No device needed. */
+int spmv_hip_csr_pattern_segment_cap(int value_bytes, int local_cap, int stage_lines);
 /* Move one array of the handle (same numbering) to an address of the form (multiple of `align`) + offset; align a
  * power of two >= 256, offset a multiple of 256 below it.  Round 3 found the x-window kernel's time on the headline
  * matrix to depend on where its arrays lie (profiles/r3_placement_*.txt); this is the tool that study used. */

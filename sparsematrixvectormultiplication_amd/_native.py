@@ -58,7 +58,8 @@ class DevInfo(C.Structure):
                 ("tile_mid_rows", C.c_int), ("tile_mid_items", C.c_int), ("tile_mid_entries", C.c_longlong),
                 ("place_tries", C.c_int), ("place_first_us", C.c_float), ("place_best_us", C.c_float),
                 ("val_address", C.c_ulonglong), ("tile_expanded_entries", C.c_longlong),
-                ("pattern_slots", C.c_longlong), ("pattern_with_us", C.c_float), ("pattern_without_us", C.c_float)]
+                ("pattern_slots", C.c_longlong), ("pattern_with_us", C.c_float), ("pattern_without_us", C.c_float),
+                ("pattern_segment_max", C.c_int), ("pattern_segment_cap", C.c_int), ("pattern_table_rows", C.c_longlong)]
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
@@ -157,6 +158,7 @@ _PROTOTYPES = {
     "spmv_hip_hll_tile_digest": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "spmv_hip_csr_addresses": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "spmv_hip_csr_stamp_blocks": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_ulonglong)]),
+    "spmv_hip_csr_pattern_segment_cap": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "spmv_hip_csr_relocate": (C.c_int, [C.c_void_p, C.c_int, C.c_ulonglong, C.c_ulonglong]),
     "spmv_hip_csr_relocate_vmm": (C.c_int, [C.c_void_p, C.c_int, C.c_ulonglong, C.c_ulonglong]),
     "spmv_hip_set_tuning": (C.c_int, [C.c_char_p, C.c_int]),

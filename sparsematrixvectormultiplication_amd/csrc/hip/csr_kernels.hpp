@@ -464,7 +464,8 @@ __device__ __forceinline__ void local_stage_full(T *stage, const int *__restrict
 // its pattern starts in that table and its shift: 4 bytes per row instead of 2 per entry.  Every lane group fetches its
 // row's pattern (16-byte groups of 8 slots; neighbouring rows share them: cache hits) and writes the row's slots --
 // pattern + shift -- into an LDS array, from which the products read their slot pairs instead of from memory: the same
-// slots, the same products, the same bits.
+// slots, the same products, the same bits.  hll_lds_local uses these tables; csr_stream_local uses them only for blocks
+// whose segment (below) is wider than the LDS budget.
 struct pat_ctx {
     unsigned short *slots;          // LDS [CAP + 8]: the block's slots, entry order, from `base` on
     const uint4 *ptab8;             // the block's pattern table in memory, groups of 8 slots (a row's pattern starts at a group)
@@ -618,10 +619,156 @@ __device__ __forceinline__ void local_stage_full_pat(T *stage, const int *__rest
     for (int u = 0; u < kUnits; ++u) *reinterpret_cast<V2 *>(&stage[u * kUnit + 2 * t]) = v[u];
 }
 
+// ---- pattern SEGMENTS: the CSR kernel's pattern plan (round 4).  The tables above cost the kernel two dependent global
+// round trips (row extents and rinfo, then the pattern groups whose address comes from rinfo) and, in blocks of short
+// rows, a serial loop of them per pass of rows.  A segment holds everything one block needs, back to back and 16-byte
+// aligned, so that every lane fetches its share with ONE independent 16-byte load issued beside the line list, ahead of
+// the value stream:
+//   unsigned info[nrows]     first group of the row's pattern (counted from the segment's first group) | shift << 16
+//   u16 lo[nrows + 1]        the rows' first entries relative to the block's base; lo[nrows] = the block's end
+//   (zeros to 16 bytes) uint4 groups[]   the block's pattern groups of 8 slots
+// 6 bytes per row instead of row_ptr + rinfo (8).  The segment is copied into LDS behind the slots' array; the slots
+// and the row sums of every pass of rows are then taken from LDS only.  pdesc[b] = {first uint4 of the segment, uint4s};
+// {0, 0}: the block's segment did not fit the LDS budget upload gave the handle, and the block reads its slot stream.
+typedef __attribute__((address_space(3))) void seg_lds_void;
+typedef const __attribute__((address_space(1))) void seg_glb_void;
+__host__ __device__ __forceinline__ int seg_groups_at(int nrows) { return (4 * nrows + 2 * (nrows + 1) + 15) >> 4; }  // uint4s
+
+// zeros for the halves of the lanes' pairs outside the block (in front of its first entry, behind its last) ...
+template <int BLOCK, int CAP>
+__device__ __forceinline__ void seg_zero_outside(unsigned short *slots, int first_rel, int end_rel) {
+    const int t = threadIdx.x;
+    constexpr int kUnit = 2 * BLOCK;
+#pragma unroll
+    for (int u = 0; u < CAP / kUnit; ++u) {
+        const int e = u * kUnit + 2 * t;
+        if (e < first_rel || e >= end_rel) slots[e] = 0;
+        if (e + 1 < first_rel || e + 1 >= end_rel) slots[e + 1] = 0;
+    }
+}
+// slots q[0 .. min(left, 8)) = the pattern group + shift, with as few LDS stores as the row's end allows: one 16-byte
+// store for a whole group, at most three (8, 4, 2 bytes) for the row's last.  The stores are as aligned as the row's
+// start happens to be (2 bytes at least): gfx950 takes unaligned LDS accesses, and the compiler emits them as such.
+__device__ __forceinline__ void seg_write_group(unsigned short *q, int left, const uint4 p, int shift) {
+    const unsigned shift2 = ((unsigned)shift & 0xffffu) * 0x10001u;
+    unsigned a = pat_shifted(p.x, shift2), b = pat_shifted(p.y, shift2), c = pat_shifted(p.z, shift2), d = pat_shifted(p.w, shift2);
+    if (left >= 8) {
+        const uint4 w = make_uint4(a, b, c, d);
+        __builtin_memcpy(q, &w, 16);
+        return;
+    }
+    if (left & 4) {
+        const uint2 w = make_uint2(a, b);
+        __builtin_memcpy(q, &w, 8);
+        q += 4;
+        a = c;
+        b = d;
+    }
+    if (left & 2) {
+        __builtin_memcpy(q, &a, 4);
+        q += 2;
+        a = b;
+    }
+    if (left & 1) *q = (unsigned short)a;
+}
+// ... and the block's slots out of the LDS copy of its segment
+template <int BLOCK>
+__device__ __forceinline__ void seg_expand_slots(unsigned short *slots, const uint4 *seg, int nrows, int lanes) {
+    const int t = threadIdx.x;
+    const int my_row = t / lanes, my_lane = t % lanes, rows_per_pass = BLOCK / lanes;
+    const unsigned *info = reinterpret_cast<const unsigned *>(seg);
+    const unsigned short *lo = reinterpret_cast<const unsigned short *>(info + nrows);
+    const uint4 *grp = seg + seg_groups_at(nrows);
+    for (int row = my_row; row < nrows; row += rows_per_pass) {
+        const int a = lo[row], len = lo[row + 1] - a;
+        const unsigned ri = info[row];
+        const int off = (int)(ri & 0xffffu), shift = (int)(short)(ri >> 16);
+        for (int g = my_lane; g * 8 < len; g += lanes) seg_write_group(slots + a + g * 8, len - g * 8, grp[off + g], shift);
+    }
+}
+
+// A workgroup barrier for LDS only: this wave's LDS writes are done, its global loads (the value stream) may still be in
+// flight.  (__syncthreads carries a fence the compiler also applies to the loads in flight.)
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// the rows of the block out of the staged products, every pass's extents from the LDS copy of the segment
+template <typename T, int BLOCK>
+__device__ __forceinline__ void seg_sum_rows(const T *prod, const uint4 *seg, T *__restrict__ y, int r0, int nrows,
+                                             int lanes) {
+    const int t = threadIdx.x;
+    const int rows_per_pass = BLOCK / lanes;
+    const int my_row = t / lanes, my_lane = t % lanes;
+    const unsigned short *lo = reinterpret_cast<const unsigned short *>(reinterpret_cast<const unsigned *>(seg) + nrows);
+    for (int first = 0; first < nrows; first += rows_per_pass) {  // all lanes stay in the loop
+        const int row = first + my_row;
+        int a = 0, z = 0;
+        if (row < nrows) {
+            a = lo[row];
+            z = lo[row + 1];
+        }
+        T acc = lds_strided_sum(prod, a, z, my_lane, lanes);
+        acc = group_sum_rt(acc, lanes);
+        if (my_lane == 0 && row < nrows) y[r0 + row] = acc;
+    }
+}
+
+template <typename T, bool NT, int CAP, int ROUNDS>
+__device__ __forceinline__ void local_stage_full_seg(T *stage, const int *__restrict__ my_lines, int last_line,
+                                                     const T *__restrict__ val, const T *__restrict__ x, int e_first,
+                                                     unsigned short *slots, uint4 *seg_lds, const uint4 *__restrict__ seg,
+                                                     int seg_len, int nrows, int lanes, int first_rel, int end_rel) {
+    using V2 = typename vec2<T>::type;
+    constexpr int kUnit = 2 * kBlock, kUnits = CAP / kUnit;
+    const int t = threadIdx.x;
+    int line[ROUNDS];
+#pragma unroll
+    for (int k = 0; k < ROUNDS; ++k) {
+        const int at = k * kLocalLineQuantum + (t >> 3);
+        line[k] = stream_load<NT>(my_lines + (k == ROUNDS - 1 ? min(at, last_line) : at));
+    }
+    // the segment beside the line list: both come back ahead of the value stream
+    uint4 sg = make_uint4(0, 0, 0, 0);
+    if (t < seg_len) sg = seg[t];
+    V2 v[kUnits];
+#pragma unroll
+    for (int u = 0; u < kUnits; ++u) v[u] = stream_load<NT>(reinterpret_cast<const V2 *>(val + e_first + u * kUnit));
+    __builtin_amdgcn_sched_barrier(0);
+    // the x lines straight into the stage (LDS-DMA: lane l of a wave lands at the wave's base + 16 l, the stage's layout),
+    // as soon as the line list is back: they hold no registers, so nothing has to live across the barrier below
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    unsigned off[ROUNDS];
+#pragma unroll
+    for (int k = 0; k < ROUNDS; ++k) off[k] = (unsigned)line[k] * (unsigned)kLineBytes + (unsigned)(t & 7) * 16u;
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int k = 0; k < ROUNDS; ++k)
+        __builtin_amdgcn_global_load_lds((seg_glb_void *)(reinterpret_cast<const char *>(x) + off[k]),
+                                         (seg_lds_void *)(reinterpret_cast<char *>(stage) + (k * kBlock + wave * 64) * 16), 16, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    // while the stream is in flight: the segment into LDS, the slots out of it
+    seg_zero_outside<kBlock, CAP>(slots, first_rel, end_rel);
+    if (t < seg_len) seg_lds[t] = sg;
+    lds_barrier();
+    seg_expand_slots<kBlock>(slots, seg_lds, nrows, lanes);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the values and this wave's x lines are in
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < kUnits; ++u) {
+        const unsigned c = *reinterpret_cast<const unsigned *>(slots + u * kUnit + 2 * t);
+        v[u].x *= stage[c & 0xffffu];
+        v[u].y *= stage[c >> 16];
+    }
+    __syncthreads();  // the products take the place of the staged lines
+#pragma unroll
+    for (int u = 0; u < kUnits; ++u) *reinterpret_cast<V2 *>(&stage[u * kUnit + 2 * t]) = v[u];
+}
+
 // STAMP (measurement only, spmv_hip_csr_stamp_blocks): every workgroup leaves {start, end} of the constant 100 MHz
 // clock and the XCD it ran on in stamps[3 * block ..]; the product instantiation (STAMP = false) has no trace of it.
-// PAT: a pattern plan (above) -- lcol is not read; pdesc[b] = {first element of block b's pattern table in ptab (a
-// multiple of 8), elements in it}, rinfo per row, stage_bytes = where the LDS array of the slots begins.
+// PAT: a pattern plan (above) -- lcol is not read.  sdesc[b] = {first uint4 of block b's segment in pseg, uint4s}; {0, 0}
+// (or no sdesc): the block's segment is wider than the LDS budget and the block takes its slots from its pattern table:
+// pdesc[b] = {first element of block b's table in ptab (a multiple of 8), elements}, rinfo per row.  stage_bytes = where
+// the LDS array of the slots begins; the segment's copy lies behind it.
 template <typename T, bool NT, int CAP, bool STAMP = false, bool PAT = false>
 __global__ __launch_bounds__(kBlock) void csr_stream_local(int num_blocks, int xcd_chunk,
                                                            const int *__restrict__ ids,
@@ -635,7 +782,9 @@ __global__ __launch_bounds__(kBlock) void csr_stream_local(int num_blocks, int x
                                                            unsigned long long *__restrict__ stamps = nullptr, int probe = 0,
                                                            const int2 *__restrict__ pdesc = nullptr,
                                                            const unsigned *__restrict__ rinfo = nullptr,
-                                                           const unsigned short *__restrict__ ptab = nullptr, int stage_bytes = 0) {
+                                                           const unsigned short *__restrict__ ptab = nullptr, int stage_bytes = 0,
+                                                           const int2 *__restrict__ sdesc = nullptr,
+                                                           const uint4 *__restrict__ pseg = nullptr) {
         using V2 = typename vec2<T>::type;
     const bool no_slots = STAMP && (probe & 1);  // (measurement only; constant false in the product instantiation)
     unsigned long long t_start = 0;
@@ -655,12 +804,15 @@ __global__ __launch_bounds__(kBlock) void csr_stream_local(int num_blocks, int x
     const int2 ld = ldesc[b];
     const int r0 = d.x, nrows = d.z;
     const int base = d.y & kBaseMask;
+    int2 sd = make_int2(0, 0);
+    if (PAT && sdesc) sd = sdesc[b];
+    const bool seg = PAT && sd.y > 0;  // wave-uniform
 
     const int lanes = lanes_for_rows<kBlock>(nrows);
     // (only the first pass's row extents are loaded up front: keeping all passes in registers, as
-    // csr_stream_short does, costs 12 VGPRs = one resident workgroup per CU here)
+    // csr_stream_short does, costs 12 VGPRs = one resident workgroup per CU here; a segment brings them all)
     int seg_lo = 0, seg_hi = 0;
-    if (t / lanes < nrows) {
+    if (!seg && t / lanes < nrows) {
         seg_lo = row_ptr[r0 + t / lanes];
         seg_hi = row_ptr[r0 + t / lanes + 1];
     }
@@ -669,10 +821,60 @@ __global__ __launch_bounds__(kBlock) void csr_stream_local(int num_blocks, int x
     const int units = (d.w - base + kUnit - 1) / kUnit;                       // wave-uniform
     const int rounds = (ld.y + kLocalLineQuantum - 1) / kLocalLineQuantum;    // wave-uniform, 1..8
     const int *my_lines = lines + ld.x;
-    if constexpr (PAT) {
+    unsigned short *slots = reinterpret_cast<unsigned short *>(local_smem + stage_bytes);
+    uint4 *seg_lds = reinterpret_cast<uint4 *>(local_smem + stage_bytes + (CAP + 8) * sizeof(unsigned short));
+    if (seg) {
+        const uint4 *sp = pseg + sd.x;
+        const int first_rel = d.y - base, end_rel = d.w - base;
+        if (units == kUnits) {
+#define SPMV_SEG(R) local_stage_full_seg<T, NT, CAP, R>(stage, my_lines, ld.y - 1, val, x, e_first, slots, seg_lds, sp, sd.y, \
+                                                        nrows, lanes, first_rel, end_rel)
+            switch (rounds) {
+                case 1: SPMV_SEG(1); break;
+                case 2: SPMV_SEG(2); break;
+                case 3: SPMV_SEG(3); break;
+                case 4: SPMV_SEG(4); break;
+                case 5: SPMV_SEG(5); break;
+                case 6: SPMV_SEG(6); break;
+                case 7: SPMV_SEG(7); break;
+                default: SPMV_SEG(8); break;
+            }
+#undef SPMV_SEG
+        } else {
+            // a block cut short: plain loops
+            uint4 sg = make_uint4(0, 0, 0, 0);
+            if (t < sd.y) sg = sp[t];
+            for (int k = 0; k < rounds; ++k) {
+                const int line = my_lines[min(k * kLocalLineQuantum + (t >> 3), ld.y - 1)];
+                const unsigned off = (unsigned)line * (unsigned)kLineBytes + (unsigned)(t & 7) * 16u;
+                *reinterpret_cast<uint4 *>(reinterpret_cast<char *>(stage) + (k * kBlock + t) * 16) =
+                    *reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(x) + off);
+            }
+            seg_zero_outside<kBlock, CAP>(slots, first_rel, end_rel);
+            if (t < sd.y) seg_lds[t] = sg;
+            __syncthreads();
+            seg_expand_slots<kBlock>(slots, seg_lds, nrows, lanes);
+            __syncthreads();
+            V2 p[kUnits];
+#pragma unroll
+            for (int u = 0; u < kUnits; ++u) {
+                if (u < units) {
+                    const unsigned c = *reinterpret_cast<const unsigned *>(slots + u * kUnit + 2 * t);
+                    p[u] = stream_load<NT>(reinterpret_cast<const V2 *>(val + e_first + u * kUnit));
+                    p[u].x *= stage[c & 0xffffu];
+                    p[u].y *= stage[c >> 16];
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int u = 0; u < kUnits; ++u)
+                if (u < units) *reinterpret_cast<V2 *>(&stage[u * kUnit + 2 * t]) = p[u];
+        }
+    } else if constexpr (PAT) {
+        // a block whose segment is wider than the LDS budget: its pattern table (pat_ctx above)
         const int2 pd = pdesc[b];
         pat_ctx pc;
-        pc.slots = reinterpret_cast<unsigned short *>(local_smem + stage_bytes);
+        pc.slots = slots;
         pc.ptab8 = reinterpret_cast<const uint4 *>(ptab + pd.x);
         pc.rinfo = rinfo;
         pc.row_ptr = row_ptr;
@@ -760,7 +962,8 @@ __global__ __launch_bounds__(kBlock) void csr_stream_local(int num_blocks, int x
             if (u < units) *reinterpret_cast<V2 *>(&stage[u * kUnit + 2 * t]) = p[u];
     }
     __syncthreads();
-    sum_rows_from_lds<T, kBlock>(stage, row_ptr, y, r0, nrows, base, lanes, seg_lo - base, seg_hi - base);
+    if (seg) seg_sum_rows<T, kBlock>(stage, seg_lds, y, r0, nrows, lanes);
+    else sum_rows_from_lds<T, kBlock>(stage, row_ptr, y, r0, nrows, base, lanes, seg_lo - base, seg_hi - base);
     if constexpr (STAMP) {
         __syncthreads();
         if (threadIdx.x == 0) {

@@ -227,4 +227,28 @@ __global__ __launch_bounds__(BLOCK) void pat_fill(int blocks, const int4 *__rest
     }
 }
 
+// pat_segment (CSR): block b's segment (csr_kernels.hpp, pattern SEGMENTS) out of the tables pat_fill wrote -- rinfo of
+// its rows, its rows' first entries relative to the block's base, its pattern groups.  sdesc[b] = {first uint4 in seg,
+// uint4s}, set by the host; {0, 0}: the block keeps reading its slot stream.  seg is zeroed beforehand.
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void pat_segment(int blocks, const int4 *__restrict__ desc, const int *__restrict__ row_ptr,
+                                                     const unsigned *__restrict__ rinfo, const unsigned short *__restrict__ ptab,
+                                                     const int2 *__restrict__ tdesc, const int2 *__restrict__ sdesc,
+                                                     uint4 *__restrict__ seg) {
+    const int b = blockIdx.x, t = threadIdx.x;
+    if (b >= blocks) return;
+    const int2 sd = sdesc[b];
+    if (sd.y <= 0) return;
+    const int4 d = desc[b];
+    const int r0 = d.x, nrows = d.z, base = d.y & kBaseMask;
+    unsigned *info = reinterpret_cast<unsigned *>(seg + sd.x);
+    unsigned short *lo = reinterpret_cast<unsigned short *>(info + nrows);
+    uint4 *grp = seg + sd.x + seg_groups_at(nrows);
+    for (int i = t; i < nrows; i += BLOCK) info[i] = rinfo[r0 + i];
+    for (int i = t; i <= nrows; i += BLOCK) lo[i] = (unsigned short)(row_ptr[r0 + i] - base);
+    const int2 td = tdesc[b];
+    const uint4 *tab = reinterpret_cast<const uint4 *>(ptab + td.x);
+    for (int g = t; g < td.y / 8; g += BLOCK) grp[g] = tab[g];
+}
+
 }  // namespace spmv

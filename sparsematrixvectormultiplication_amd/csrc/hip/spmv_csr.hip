@@ -795,7 +795,8 @@ int csr_tune_placement(spmv_csr_dev *m) {
 }
 
 // The pattern plan of a handle's x-window plan (csr_kernels.hpp, PAT; plan_kernels.hpp): built on the device from the
-// plan's own arrays, whichever builder made them.  auto: kept when the tables hold at most a quarter of the slots.
+// plan's own arrays, whichever builder made them -- the tables (pat_mark, pat_fill), then one segment per block out of
+// them where it fits the LDS budget (pat_segment).  auto: kept when the tables hold at most a quarter of the slots.
 // Where it pays (same handle, same placement, the two instantiations alternately: profiles/r3_ab_patterns.txt): the
 // nlpkkt-like matrix 190 -> 178 us (bench.py over 4 uploads each; 204 -> 185 on a slow placement), a 27-point stencil
 // 197 -> 190; neutral on the FEM-shaped matrix (75 per row: 155 / 157) and on nlpkkt80-size (59 / 60); a loss where the
@@ -807,6 +808,30 @@ int csr_tune_placement(spmv_csr_dev *m) {
 // of at least 12 entries per row whose tables hold at most a quarter of the slots get a plan BUILT, and upload then
 // times its own kernel with and without it and keeps the plan only if it is at least 2 % faster on this handle
 // (csr_tune_patterns, beside the placement search).
+// The widest segment (uint4s, at most one per lane) whose LDS copy keeps as many workgroups of csr_stream_local<.., PAT>
+// resident per CU as its stage and slots alone would, up to the 7 its VGPRs allow.  LDS is counted in 512-byte granules
+// (no finer than the hardware's), of the 160 KiB of a gfx950 CU.
+constexpr size_t kLdsPerCu = 160 * 1024, kLdsGranule = 512;
+constexpr int kLocalWgsPerCu = 7;
+static int pattern_segment_cap(int value_bytes, int local_cap, int stage_lines) {
+    const size_t stage = std::max((size_t)local_cap * (size_t)value_bytes, (size_t)stage_lines * kLineBytes);
+    const size_t fixed = stage + ((size_t)local_cap + 8) * sizeof(unsigned short);
+    auto per_cu = [](size_t bytes) { return kLdsPerCu / ((bytes + kLdsGranule - 1) / kLdsGranule * kLdsGranule); };
+    const size_t want = std::min((size_t)kLocalWgsPerCu, per_cu(fixed));
+    int cap = 0;
+    while (cap < kBlock && per_cu(fixed + (size_t)(cap + 1) * sizeof(uint4)) >= want) ++cap;
+    return cap;
+}
+int csr_pattern_segment_cap(const spmv_csr_dev *m) {
+    return pattern_segment_cap(m->value_bytes, m->local_cap, m->local_stage_lines);
+}
+extern "C" int spmv_hip_csr_pattern_segment_cap(int value_bytes, int local_cap, int stage_lines) {
+    if ((value_bytes != 4 && value_bytes != 8) || local_cap <= 0 || local_cap > kStreamCapMax || stage_lines < 0 ||
+        stage_lines > kLocalLinesMax)
+        return fail("csr_pattern_segment_cap: bad arguments (%d, %d, %d)", value_bytes, local_cap, stage_lines);
+    return 16 * pattern_segment_cap(value_bytes, local_cap, stage_lines);
+}
+
 int csr_build_patterns(spmv_csr_dev *m) {
     if (g_local_patterns == 0 || m->local_blocks <= 0 || !m->lcol || !m->ldesc4 || !m->row_ptr || m->M_local <= 0) return 0;
     if (g_local_patterns < 0 && (m->nz * (m->value_bytes + 2LL) <= (128LL << 20) || m->nz < 12LL * m->M_local)) return 0;
@@ -850,6 +875,19 @@ int csr_build_patterns(spmv_csr_dev *m) {
         drop_tmp();
         return 0;
     }
+    // the tables first (pat_fill), then one segment per block out of them (pat_segment) where it fits the LDS budget
+    auto drop_plan = [&] {
+        (void)hipFree(m->ptab);
+        (void)hipFree(m->rinfo);
+        (void)hipFree(m->pdesc);
+        (void)hipFree(m->pseg);
+        (void)hipFree(m->sdesc);
+        m->ptab = nullptr;
+        m->rinfo = nullptr;
+        m->pdesc = nullptr;
+        m->pseg = nullptr;
+        m->sdesc = nullptr;
+    };
     e = hipMalloc((void **)&m->ptab, ((size_t)total + 1024) * sizeof(unsigned short));
     if (e == hipSuccess) e = hipMalloc((void **)&m->rinfo, (size_t)m->M_local * sizeof(unsigned));
     if (e == hipSuccess) e = hipMalloc((void **)&m->pdesc, (size_t)B * sizeof(int2));
@@ -861,21 +899,63 @@ int csr_build_patterns(spmv_csr_dev *m) {
                            m->ptab, m->pdesc);
         e = hipGetLastError();
     }
+    // the blocks' row counts: the size of their segments
+    std::vector<int4> h_desc((size_t)B);
+    if (e == hipSuccess) e = hipMemcpyAsync(h_desc.data(), m->ldesc4, (size_t)B * sizeof(int4), hipMemcpyDeviceToHost, g_stream);
     if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
     drop_tmp();
     if (e != hipSuccess) {
-        (void)hipFree(m->ptab);
-        (void)hipFree(m->rinfo);
-        (void)hipFree(m->pdesc);
-        m->ptab = nullptr;
-        m->rinfo = nullptr;
-        m->pdesc = nullptr;
+        drop_plan();
         return fail("pattern plan: building the tables failed: %s", hipGetErrorString(e));
+    }
+    trace.mark("tables");
+    // The LDS budget of a segment: the kernel's stage and slots take stage + (cap + 8) * 2 bytes; the segment's copy may
+    // not cost a resident workgroup per CU (at most the 7 the kernel's VGPRs allow).  A block whose segment is wider
+    // keeps its table.
+    const int cap16 = csr_pattern_segment_cap(m);
+    std::vector<int2> h_sdesc((size_t)B, make_int2(0, 0));
+    long long seg_total = 0, table_rows = 0;
+    int seg_max = 0;
+    for (int b = 0; b < B; ++b) {
+        const int4 d = h_desc[(size_t)b];
+        const int len = seg_groups_at(d.z) + h_count[(size_t)b] / 8;
+        if (len <= cap16) {
+            h_sdesc[(size_t)b] = make_int2((int)seg_total, len);
+            seg_total += len;
+            seg_max = std::max(seg_max, len);
+        } else {
+            table_rows += d.z;
+        }
+    }
+    if (seg_max > 0 && seg_total <= 0x7fffffffLL) {
+        e = hipMalloc((void **)&m->pseg, (size_t)seg_total * sizeof(uint4));
+        if (e == hipSuccess) e = hipMalloc((void **)&m->sdesc, (size_t)B * sizeof(int2));
+        if (e == hipSuccess) e = hipMemsetAsync(m->pseg, 0, (size_t)seg_total * sizeof(uint4), g_stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(m->sdesc, h_sdesc.data(), (size_t)B * sizeof(int2), hipMemcpyHostToDevice, g_stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL((pat_segment<256>), dim3(B), dim3(256), 0, g_stream, B, m->ldesc4, m->row_ptr, m->rinfo, m->ptab,
+                               m->pdesc, m->sdesc, m->pseg);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
+        if (e != hipSuccess) {
+            drop_plan();
+            return fail("pattern plan: building the segments failed: %s", hipGetErrorString(e));
+        }
+    } else {
+        seg_total = 0;
+        seg_max = 0;
+        table_rows = m->M_local;
     }
     m->pat_slots = total;
     m->pat_max = widest;
+    m->pat_seg_total = seg_total;
+    m->pat_seg_max = seg_max;
+    m->pat_seg_cap = cap16;
+    m->pat_table_rows = table_rows;
     m->device_bytes += ((size_t)total + 1024) * 2 + (size_t)m->M_local * 4 + (size_t)B * 8;
-    trace.mark("tables");
+    if (m->pseg) m->device_bytes += (size_t)seg_total * sizeof(uint4) + (size_t)B * sizeof(int2);
+    trace.mark("segments");
     return 0;
 }
 
@@ -916,14 +996,22 @@ int csr_tune_patterns(spmv_csr_dev *m) {
     m->pat_with_us = with_us;
     m->pat_without_us = without_us;
     if (!ok || with_us > 0.98f * without_us) {  // not faster here: the slot stream stays
+        m->device_bytes -= std::min(m->device_bytes, ((size_t)m->pat_slots + 1024) * 2 + (size_t)m->M_local * 4 + (size_t)m->local_blocks * 8 +
+                                                          (m->pseg ? (size_t)m->pat_seg_total * sizeof(uint4) + (size_t)m->local_blocks * sizeof(int2) : 0));
         (void)hipFree(m->ptab);
         (void)hipFree(m->rinfo);
         (void)hipFree(m->pdesc);
+        (void)hipFree(m->pseg);
+        (void)hipFree(m->sdesc);
         m->ptab = nullptr;
         m->rinfo = nullptr;
         m->pdesc = nullptr;
-        m->device_bytes -= std::min(m->device_bytes, ((size_t)m->pat_slots + 1024) * 2 + (size_t)m->M_local * 4 + (size_t)m->local_blocks * 8);
+        m->pseg = nullptr;
+        m->sdesc = nullptr;
         m->pat_slots = 0;
+        m->pat_seg_total = 0;
+        m->pat_seg_max = 0;
+        m->pat_table_rows = 0;
     }
     return 0;
 }
@@ -1641,6 +1729,8 @@ extern "C" void spmv_hip_csr_free(spmv_csr_dev *m) {
     (void)hipFree(m->ptab);
     (void)hipFree(m->rinfo);
     (void)hipFree(m->pdesc);
+    (void)hipFree(m->pseg);
+    (void)hipFree(m->sdesc);
     for (spmv_csr_dev::long_tiles *tier : {&m->mt}) {
         (void)hipFree(tier->block_row);
         (void)hipFree(tier->block_pass);
@@ -1918,12 +2008,19 @@ extern "C" int spmv_hip_csr_info(const spmv_csr_dev *m, spmv_dev_info *out) {
     out->pattern_slots = m->ptab ? m->pat_slots : 0;
     out->pattern_with_us = m->pat_with_us;
     out->pattern_without_us = m->pat_without_us;
+    out->pattern_segment_max = m->ptab ? 16 * m->pat_seg_max : 0;
+    out->pattern_segment_cap = 16 * m->pat_seg_cap;
+    out->pattern_table_rows = m->ptab ? m->pat_table_rows : 0;
     out->stream_kernel = m->local_blocks > 0 ? 1 : m->tile_blocks > 0 ? 3
                          : ((m->stream_cap == 4096 || m->stream_cap == 2048) && m->M_local > 0 &&
                             m->nz < (long long)m->M_local * (m->stream_cap / kBlock)) ? 2 : 0;
     if (m->local_blocks > 0)  // (a pattern plan: the tables and 4 bytes per row instead of 2 bytes per entry)
-        out->stream_bytes = m->nz * vb + (m->ptab ? 2 * m->pat_slots + 4LL * m->M_local + 8LL * m->local_blocks : 2 * m->nz) +
-                            4 * m->local_lines + 24LL * m->local_blocks + 4LL * (m->M_local + 1) + vb * m->M_local + vb * m->N;
+        // (a pattern plan: the segments instead of the slots; a block whose segment did not fit reads its table, rinfo
+        // and row_ptr -- counted as its share of the tables)
+        out->stream_bytes = m->nz * vb + (m->ptab ? 16 * m->pat_seg_total + 8LL * m->local_blocks +
+                                                        (2 * m->pat_slots + 8LL * m->M_local) * m->pat_table_rows / std::max(1, m->M_local)
+                                                  : 2 * m->nz + 4LL * (m->M_local + 1)) +
+                            4 * m->local_lines + 24LL * m->local_blocks + vb * m->M_local + vb * m->N;
     else if (m->tile_blocks > 0) {  // tiles: 4-byte column + 2-byte key + value per (padded) entry; rows beyond the limit as CSR
         out->stream_bytes = m->tile_padded * (vb + 6) - (m->tile_packed ? 2 : 0) * m->tile_staged + 16LL * m->tile_passes +
                             4LL * m->tile_blocks +
@@ -2120,13 +2217,13 @@ int csr_launch(const spmv_csr_dev *m, int variant, const T *x, T *y_full, hipStr
                     // a pattern plan: the slots are rebuilt in LDS (behind the stage) from the block's pattern table, not read
                     // entry by entry
                     const bool patterns = m->ptab && m->rinfo && m->pdesc && g_local_patterns != 0;
-                    const size_t pat_lds = lds + ((size_t)m->local_cap + 8) * sizeof(unsigned short);
+                    const size_t pat_lds = lds + ((size_t)m->local_cap + 8) * sizeof(unsigned short) + (size_t)m->pat_seg_max * sizeof(uint4);
 #define SPMV_LOCAL(NT, CAP)                                                                                   \
     do {                                                                                                      \
         if (patterns)                                                                                         \
             hipLaunchKernelGGL((csr_stream_local<T, NT, CAP, false, true>), dim3(lgrid), dim3(kBlock), pat_lds, s, lcount, lchunk, \
                                lids, m->ldesc4, m->ldesc, m->lines, m->row_ptr, m->lcol, (const T *)m->val, x, y, \
-                               (unsigned long long *)nullptr, 0, m->pdesc, m->rinfo, m->ptab, (int)lds);       \
+                               (unsigned long long *)nullptr, 0, m->pdesc, m->rinfo, m->ptab, (int)lds, m->sdesc, (const uint4 *)m->pseg); \
         else                                                                                                  \
             hipLaunchKernelGGL((csr_stream_local<T, NT, CAP>), dim3(lgrid), dim3(kBlock), lds, s, lcount, lchunk, lids, \
                                m->ldesc4, m->ldesc, m->lines, m->row_ptr, m->lcol, (const T *)m->val, x, y);   \

@@ -196,13 +196,20 @@ struct spmv_csr_dev {
     int2 *ldesc = nullptr;            // [local_blocks] {first line in `lines`, line count}
     int *lines = nullptr;             // x line ids, block after block, ascending inside a block
     unsigned short *lcol = nullptr;   // [nz + pad] slot of each entry in its block's staged lines
-    // the pattern plan (round 3; csr_kernels.hpp, PAT): where most rows of the blocks are their predecessor shifted by a
-    // constant, the kernel rebuilds the slots from a table per block and 4 bytes per row instead of reading lcol
+    // the pattern plan (csr_kernels.hpp, PAT): where most rows of the blocks are their predecessor shifted by a constant,
+    // the kernel rebuilds the slots instead of reading lcol -- from one segment per block (its rows' records and its
+    // pattern groups, copied into LDS), or, for a block whose segment is wider than the LDS budget, from its table
     unsigned short *ptab = nullptr;   // [pat_slots + pad] the blocks' pattern tables
     unsigned *rinfo = nullptr;        // [M_local] start of the row's pattern in its block's table | shift << 16
     int2 *pdesc = nullptr;            // [local_blocks] {first element in ptab (even), elements}
+    uint4 *pseg = nullptr;            // [pat_seg_total] the segments, 16-byte units (nullptr: no block's fits)
+    int2 *sdesc = nullptr;            // [local_blocks] {first uint4 of the block's segment, uint4s}; {0, 0}: the table
     long long pat_slots = 0;          // elements of all tables
     int pat_max = 0;                  // the largest table (elements)
+    long long pat_seg_total = 0;      // uint4s of all segments
+    int pat_seg_max = 0;              // the widest segment kept (uint4s): the LDS the kernel adds behind the slots
+    int pat_seg_cap = 0;              // the widest segment the LDS budget allowed (uint4s)
+    long long pat_table_rows = 0;     // rows of the blocks whose segment did not fit (they read rinfo, row_ptr and ptab)
     float pat_with_us = 0, pat_without_us = 0;  // (auto) the kernel with / without the plan, timed at upload (csr_tune_patterns)
     int local_blocks = 0;             // 0: no plan (not profitable / not possible)
     int local_stage_lines = 0;        // LDS stage: most lines any block lists, in steps of 32

@@ -1,0 +1,183 @@
+"""The pattern plan's segments (csr_stream_local<.., PAT>): one 16-byte-aligned segment per block -- its rows' records
+and its pattern groups -- copied into LDS, the slots and every pass's row extents taken from there.  The same slots, the
+same products, the same summation order: y must be the bits of the kernel that reads the 16-bit slot stream
+("local_patterns" 0 at launch, the same handle)."""
+import numpy as np
+import pytest
+
+import sparsematrixvectormultiplication_amd as sp
+from sparsematrixvectormultiplication_amd import synth
+from sparsematrixvectormultiplication_amd.device import set_tuning
+
+pytestmark = pytest.mark.gpu
+
+LDS_PER_CU, GRANULE = 160 * 1024, 512
+
+
+def stencil_1d(n, offsets, rng, dtype):
+    """Row i holds columns i + o (o in offsets, inside [0, n)): every row its predecessor shifted by one."""
+    offs = np.array(sorted(offsets))
+    rows = np.repeat(np.arange(n), len(offs))
+    cols = rows + np.tile(offs, n)
+    keep = (cols >= 0) & (cols < n)
+    rows, cols = rows[keep], cols[keep]
+    rp = np.zeros(n + 1, dtype=np.int32)
+    np.add.at(rp, rows + 1, 1)
+    rp = np.cumsum(rp).astype(np.int32)
+    return n, rp, cols.astype(np.int32), rng.uniform(-1, 1, len(cols)).astype(dtype)
+
+
+def concat(parts):
+    """Block-diagonal stack of (n, rp, col, val) matrices."""
+    n = sum(p[0] for p in parts)
+    rps, cols, vals, r_off, c_off, e_off = [np.zeros(1, np.int32)], [], [], 0, 0, 0
+    for m, rp, col, val in parts:
+        rps.append(rp[1:] + e_off)
+        cols.append(col + c_off)
+        vals.append(val)
+        c_off += m
+        e_off += int(rp[-1])
+    return n, np.concatenate(rps).astype(np.int32), np.concatenate(cols).astype(np.int32), np.concatenate(vals)
+
+
+def both(dev, x, run=None):
+    """y of the segment kernel and of the slot-stream kernel on the same handle."""
+    out = []
+    for p in (1, 0):
+        set_tuning("local_patterns", p)
+        sp.lib().spmv_hip_memset(dev.y_ptr, 0xFF, dev.M * x.itemsize)
+        if run is None:
+            out.append(dev.spmv(x, sp.CSR_STREAM).copy())
+        else:
+            dev.set_x(x)
+            run(dev)
+            sp.hip_sync()
+            out.append(dev.get_y().copy())
+    set_tuning("local_patterns", 1)
+    return out
+
+
+def check_budget(info, dtype):
+    """The widest segment kept fits the cap upload computed for this handle (the library's cap function at its stage), and
+    the cap keeps 7 workgroups per CU.  (The tests run at local_cap 2048: the `forced` fixture sets it.)"""
+    assert 0 < info["pattern_segment_max"] <= info["pattern_segment_cap"]
+    assert info["pattern_segment_cap"] == sp.lib().spmv_hip_csr_pattern_segment_cap(np.dtype(dtype).itemsize, 2048,
+                                                                                      info["local_stage_lines"])
+    stage = max(2048 * np.dtype(dtype).itemsize, info["local_stage_lines"] * 128)
+    lds = stage + (2048 + 8) * 2 + info["pattern_segment_cap"]
+    assert LDS_PER_CU // (-(-lds // GRANULE) * GRANULE) >= min(7, LDS_PER_CU // (-(-(stage + 4112) // GRANULE) * GRANULE))
+
+
+@pytest.fixture
+def forced():
+    set_tuning("local_patterns", 1)
+    set_tuning("local_cap", 2048)
+    yield
+    set_tuning("local_patterns", -1)
+    set_tuning("local_cap", 0)
+    set_tuning("stream_xcd", 0)
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("case", ["kkt", "rows129", "rows300", "odd", "cut"])
+def test_segment_bits_equal_the_slot_stream(gpu, oracle, forced, dtype, case):
+    rng = np.random.default_rng(2027)
+    if case == "kkt":        # the headline shape, small: ~74 rows per block, two lanes per row
+        M, rp, col, val = synth.kkt_like((24, 24, 25), 5)
+        val = val.astype(dtype)
+    elif case == "rows129":  # 12 per row: ~170 rows per block, one lane per row, one pass
+        M, rp, col, val = stencil_1d(20000, range(-6, 6), rng, dtype)
+    elif case == "rows300":  # 7 per row: ~290 rows per block, two passes of rows
+        M, rp, col, val = stencil_1d(30000, (-40, -3, -1, 0, 1, 3, 40), rng, dtype)
+    elif case == "odd":      # 9 per row: rows start at odd entries, pairs straddle rows
+        M, rp, col, val = stencil_1d(25001, range(-4, 5), rng, dtype)
+    else:                    # a short last block and a row block of a bigger matrix (blocks cut short at both ends)
+        M, rp, col, val = stencil_1d(9001, range(-13, 14), rng, dtype)
+    x = rng.uniform(-1, 1, M).astype(dtype)
+    ref = (oracle.csr_serial if dtype == np.float64 else oracle.csr_f32_accum64)(rp, col, val, x)
+    ranges = [(0, M)] + ([(M // 3 + 1, 2 * M // 3 + 7)] if case == "cut" else [])
+    for lo, hi in ranges:
+        with sp.CsrDevice(M, M, rp, col, val, row0=lo, row1=hi) as dev:
+            info = dev.info()
+            assert info["local_blocks"] > 0 and info["pattern_slots"] > 0, info
+            check_budget(info, dtype)
+            y, y0 = both(dev, x)
+            tol = 1e-10 if dtype == np.float64 else 1e-5
+            assert np.max(np.abs(y[lo:hi].astype(np.float64) - ref[lo:hi])) <= tol * max(np.max(np.abs(ref)), 1e-300)
+            assert y[lo:hi].tobytes() == y0[lo:hi].tobytes()
+
+
+@pytest.mark.parametrize("xcd", [-1, 1, 3, 64])
+def test_segment_under_stream_xcd(gpu, forced, xcd):
+    rng = np.random.default_rng(2028)
+    M, rp, col, val = stencil_1d(40000, range(-9, 10), rng, np.float64)
+    x = rng.uniform(-1, 1, M)
+    with sp.CsrDevice(M, M, rp, col, val) as dev:
+        assert dev.info()["pattern_slots"] > 0
+        set_tuning("stream_xcd", 0)
+        base, _ = both(dev, x)
+        set_tuning("stream_xcd", xcd)
+        y, y0 = both(dev, x)
+        assert y.tobytes() == y0.tobytes() == base.tobytes()
+
+
+def test_segment_on_the_block_sub_lists(gpu, forced):
+    """ids: the interior / boundary blocks (run_part) and the column split (run_split) of a row block."""
+    rng = np.random.default_rng(2029)
+    n = 30000
+    M, rp, col, val = stencil_1d(n, (-300, -2, -1, 0, 1, 2, 300), rng, np.float64)
+    lo, hi = n // 3, 2 * n // 3
+    x = rng.uniform(-1, 1, n)
+    with sp.CsrDevice(M, M, rp, col, val, lo, hi) as dev:
+        assert dev.info()["pattern_slots"] > 0
+        set_tuning("local_patterns", 1)
+        whole = dev.spmv(x, sp.CSR_STREAM)[lo:hi].copy()
+        counts = dev.split_interior()
+        assert counts["interior_blocks"] > 0 and counts["boundary_blocks"] > 0
+        dev.split_columns(lo, hi)
+        for parts in (lambda d: (d.run_part(0), d.run_part(1)), lambda d: (d.run_split(0), d.run_split(1))):
+            y, y0 = both(dev, x, parts)
+            assert y[lo:hi].tobytes() == y0[lo:hi].tobytes()
+        y, _ = both(dev, x, lambda d: (d.run_part(0), d.run_part(1)))
+        assert y[lo:hi].tobytes() == whole.tobytes()
+
+
+def test_segment_lds_budget_falls_back_per_block(gpu, oracle, forced):
+    """Blocks of very short rows (2 per row: ~1000 rows, 6 KB of records) do not fit the LDS budget: those blocks rebuild
+    their slots from their pattern table, the others from their segments -- one handle, both kinds of blocks, the slot
+    stream's bits.  A matrix of such blocks only keeps the tables alone."""
+    rng = np.random.default_rng(2030)
+    short = stencil_1d(60000, (0, 1), rng, np.float64)
+    wide = stencil_1d(30000, range(-13, 14), rng, np.float64)
+    for parts, mixed in (([wide, short, wide], True), ([short], False)):
+        M, rp, col, val = concat(parts)
+        x = rng.uniform(-1, 1, M)
+        with sp.CsrDevice(M, M, rp, col, val) as dev:
+            info = dev.info()
+            assert info["local_blocks"] > 0 and info["pattern_slots"] > 0, info
+            if mixed:
+                assert 0 < info["pattern_table_rows"] < M, info
+                check_budget(info, np.float64)
+            else:
+                assert info["pattern_segment_max"] == 0 and info["pattern_table_rows"] == M, info
+            y, y0 = both(dev, x)
+            assert y.tobytes() == y0.tobytes()
+            ref = oracle.csr_serial(rp, col, val, x)
+            assert np.max(np.abs(y - ref)) <= 1e-10 * np.max(np.abs(ref))
+
+
+def test_hll_patterns_unchanged(gpu, oracle, forced):
+    """hll_lds_local keeps its table layout: a forced plan still gives the slot stream's bits."""
+    rng = np.random.default_rng(2031)
+    M, rp, col, val = synth.kkt_like((24, 24, 25), 5)
+    x = rng.uniform(-1, 1, M)
+    hll = sp.convert_to_hll(sp.PreMatrix.from_arrays(M, M, np.repeat(np.arange(M, dtype=np.int32), np.diff(rp)), col, val))
+    with sp.HllDevice(hll) as dev:
+        assert dev.info()["local_blocks"] > 0 and dev.info()["pattern_slots"] > 0
+        y = dev.spmv(x, sp.HLL_LDS).copy()
+        set_tuning("local_patterns", 0)
+        y0 = dev.spmv(x, sp.HLL_LDS).copy()
+        set_tuning("local_patterns", 1)
+        assert y.tobytes() == y0.tobytes()
+        ref = oracle.csr_serial(rp, col, val, x)
+        assert np.max(np.abs(y - ref)) <= 1e-10 * np.max(np.abs(ref))

@@ -1,0 +1,65 @@
+"""The x-window kernel's pattern-plan instantiations (csr_stream_local<.., PAT = true>: slots rebuilt from one segment
+per block), checked on the code hipcc generates for gfx950 (no GPU needed): no scratch, no more VGPRs than the table
+layout they replaced used (72: seven resident workgroups per CU), and only dynamic LDS -- whose size upload caps so that
+the headline plan's stage, slots and widest segment still leave seven workgroups per CU (the library's own cap)."""
+import os
+import re
+import shutil
+import subprocess
+import tempfile
+
+import pytest
+
+import sparsematrixvectormultiplication_amd as sp
+from conftest import ROOT
+
+HIPCC = "/opt/rocm/bin/hipcc"
+SRC = os.path.join(ROOT, "sparsematrixvectormultiplication_amd", "csrc", "hip")
+LDS_PER_CU, GRANULE = 160 * 1024, 512
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+def test_pattern_segment_kernels_fit_seven_workgroups_per_cu():
+    tmp = tempfile.mkdtemp(prefix="spmv_seg_regs_")
+    try:
+        proc = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
+                               "-I" + SRC, "-c", os.path.join(SRC, "spmv_csr.hip"), "-o", os.path.join(tmp, "o.o"),
+                               "-save-temps=obj"], capture_output=True, text=True, timeout=600, cwd=tmp)
+        assert proc.returncode == 0, proc.stderr[-2000:]
+        asm = [f for f in os.listdir(tmp) if f.endswith("gfx950.s")]
+        assert asm, os.listdir(tmp)
+        text = open(os.path.join(tmp, asm[0])).read()
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    kernels = {}
+    for m in re.finditer(r"\.group_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.name:\s+(\S+)\n(?:.*\n)*?"
+                         r"\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)", text):
+        kernels[m.group(2)] = (int(m.group(1)), int(m.group(3)), int(m.group(4)))
+    # csr_stream_local<T, NT, CAP, STAMP = false, PAT = true>: {fp64, fp32} x {nt} x stages {1024, 2048, 3072}
+    pat = {k: v for k, v in kernels.items() if re.search(r"csr_stream_localI[df]Lb[01]ELi\d+ELb0ELb1EE", k)}
+    assert len(pat) == 12, sorted(k for k in kernels if "csr_stream_local" in k)
+    for name, (static_lds, scratch, vgprs) in pat.items():
+        assert scratch == 0, f"{name} spills {scratch} bytes of scratch ({vgprs} VGPRs)"
+        assert static_lds == 0, f"{name}: {static_lds} bytes of static LDS (the stage, slots and segment are dynamic)"
+        if "Li2048" in name:
+            assert vgprs <= 72, f"{name}: {vgprs} VGPRs: seven workgroups per CU no longer fit"
+
+
+def test_pattern_segment_cap_keeps_seven_workgroups_per_cu():
+    """The cap upload applies (the library's own function, as the launch sizes its LDS: stage + slots + widest segment
+    kept <= cap) keeps seven csr_stream_local workgroups per CU on the headline plan, is the widest that does, and holds
+    a block of 128 rows with 64 pattern groups."""
+    lib = sp.lib()
+
+    def per_cu(b):
+        return LDS_PER_CU // (-(-b // GRANULE) * GRANULE)
+
+    for value_bytes, stage_lines in ((8, 128), (8, 64), (4, 96)):
+        cap = lib.spmv_hip_csr_pattern_segment_cap(value_bytes, 2048, stage_lines)
+        stage = max(2048 * value_bytes, stage_lines * 128)
+        fixed = stage + (2048 + 8) * 2
+        assert cap > 0 and cap % 16 == 0, cap
+        assert per_cu(fixed + cap) >= min(7, per_cu(fixed)), (value_bytes, stage_lines, cap)
+        assert cap == 16 * 256 or per_cu(fixed + cap + 16) < min(7, per_cu(fixed)), (value_bytes, stage_lines, cap)
+    assert lib.spmv_hip_csr_pattern_segment_cap(8, 2048, 128) >= 8 * 128 + 64 * 16
+    assert lib.spmv_hip_csr_pattern_segment_cap(3, 2048, 128) == -1
