@@ -449,6 +449,23 @@ int spmv_hip_csr_power_iterate(spmv_csr_dev *m, int variant, int iters, const in
  * norm r.r before the first step and after every step; *ms_total device time of the loop. */
 int spmv_hip_csr_cg(spmv_csr_dev *m, int variant, int iters, const int *bounds, int use_halo, const void *b_host,
                     void *x_host, double *rr_hist, float *ms_total);
+/* k independent CG recurrences for a symmetric positive definite A, x0 = 0, sharing one SpMM per step (the loop of
+ * spmv_hip_csr_cg with one alpha and one beta per column: not block CG).  The product is spmv_hip_csr_spmm_on on
+ * library-owned P (N x k) and Q (M_total x k); k = 1 is the handle's AUTO SpMV and gives spmv_hip_csr_cg's bits
+ * (variant SPMV_CSR_AUTO).  Column j's dot products add in an order that does not depend on j: permuting the columns
+ * of B permutes the results bit for bit.  With a communicator every rank keeps its rows of X and R, P is all-gathered
+ * with the row bounds scaled by k and the k dot products are all-gathered and added in rank order; there is no halo
+ * exchange variant.
+ * B_host: M_total x k row-major, values of the handle's dtype (a rank reads its own rows).
+ * tol: column j freezes at the first step t with rs_j(t) <= tol^2 * rs_j(0) (tol = 0: only when rs_j = 0 exactly).
+ *   A frozen column's x, r, p no longer change and its history repeats its last value.  It still rides in the SpMM.
+ * tol = 0: exactly `iters` steps, no host synchronisation inside the loop.
+ * tol > 0: the host reads one device word every 16 steps and stops once every column is frozen.
+ * Out: X_host (optional) M_total x k; rr_hist (optional) (iters + 1) x k, r.r per column before step 1 and
+ * after every step; iters_done (optional) [k] steps each column took; *ms_total device time of the loop.
+ * -1: k < 1 or k > 64, non-square, tiles-only handle, n*k beyond int range, a communicator without bounds. */
+int spmv_hip_csr_cg_multi(spmv_csr_dev *m, int k, int iters, double tol, const int *bounds,
+                          const void *B_host, void *X_host, double *rr_hist, int *iters_done, float *ms_total);
 int spmv_hip_csr_split_interior(spmv_csr_dev *m, long long *counts);
 /* N4 overlap below block granularity (round 3).  On a KKT-coupled cut every block also lists lines of the coupling block,
  * which another rank owns: no interior BLOCKS -- but 13 of a row's 28 entries have their column in the rank's own range.

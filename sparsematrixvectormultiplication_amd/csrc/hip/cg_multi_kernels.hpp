@@ -1,0 +1,293 @@
+// cg_multi_kernels.hpp -- the vector kernels of spmv_hip_csr_cg_multi: k independent CG recurrences that share one
+// SpMM per step (gfx950).
+//
+// Every vector is a row-major n x k array (element (i, j) at i * k + j, the layout of the SpMM).  A lane owns V
+// consecutive columns of one row: V = 16 / sizeof(T) when a row is a whole number of 16-byte pieces (one wide load
+// per array), else V = 1.  The CL = 2^cl column lanes that cover a row sit in the LOW lane bits, so the lanes of a
+// wave read one contiguous run of rows; the 64 / CL rows of a wave sit in the high bits.  Lanes whose columns lie
+// past k (k / V not a power of two) idle.  A workgroup takes kBlock / CL rows per pass and strides over the grid:
+//
+//   mcg_dot_partial   the k column dot products a[:, j] . b[:, j]          -> part[g * k + j] of workgroup g
+//   mcg_update_x_r    x_j += alpha_j p_j, r_j -= alpha_j q_j, and r_j . r_j -> part[g * k + j]
+//   mcg_update_p      p_j = r_j + beta_j p_j
+//   mcg_fold          one workgroup per column folds part[] in workgroup order (fold_partials, k wide)
+//   mcg_start / mcg_set_alpha / mcg_set_beta   one workgroup: the k columns' scalars, the freeze rule, the history
+//
+// Reduction order.  Products are accumulated in double, for fp32 and fp64 data alike.  A lane adds its rows in
+// grid-stride order, the rows of one column in a wave are added by an xor butterfly over the high lane bits, the
+// waves of a workgroup in wave order, the workgroups by mcg_fold in workgroup order.  None of it depends on j, so
+// permuting the columns of B permutes the results bit for bit; no atomics, so every run gives the same bits.  With
+// k = 1 (CL = 1, V = 1) the lanes, the butterfly (group_sum<64>) and the wave sums are those of dot_partial /
+// cg_update_x_r / fold_partials in spmv_comm.hip, and the host keeps their grid cap: k = 1 is csr_cg bit for bit.
+//
+// Frozen columns (act[j] == 0) keep x, r and p: the update kernels write back what they read.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "csr_kernels.hpp"
+#include "wave_ops.hpp"
+
+namespace spmv {
+
+constexpr int kMcgMaxK = 64;      // widest k: one scalar lane per column in one wavefront
+constexpr int kMcgBlocks = 2048;  // grid cap of the vector kernels for k > 1 (k = 1 keeps csr_cg's cap)
+
+// the scalar slots, kMcgMaxK doubles each
+constexpr int kMcgRs = 0, kMcgPq = 1, kMcgRsNew = 2, kMcgAlpha = 3, kMcgBeta = 4, kMcgRs0 = 5, kMcgLocal = 6,
+              kMcgSlots = 7;
+// the int words: act[kMcgMaxK] (1 = still iterating), done[kMcgMaxK] (steps taken), then the count of active columns
+constexpr int kMcgAct = 0, kMcgDone = kMcgMaxK, kMcgActive = 2 * kMcgMaxK, kMcgFlagWords = 2 * kMcgMaxK + 1;
+
+typedef float v4f_mcg __attribute__((ext_vector_type(4)));
+
+template <typename T, int V>
+__device__ __forceinline__ void mcg_load(const T *__restrict__ p, T (&v)[V]) {
+    static_assert(V == 1 || V * sizeof(T) == 16, "one element or one 16-byte piece");
+    if constexpr (V == 1) {
+        v[0] = p[0];
+    } else if constexpr (sizeof(T) == 8) {
+        const v2d a = *reinterpret_cast<const v2d *>(p);
+        v[0] = a.x, v[1] = a.y;
+    } else {
+        const v4f_mcg a = *reinterpret_cast<const v4f_mcg *>(p);
+        v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w;
+    }
+}
+
+template <typename T, int V>
+__device__ __forceinline__ void mcg_store(T *__restrict__ p, const T (&v)[V]) {
+    if constexpr (V == 1) {
+        p[0] = v[0];
+    } else if constexpr (sizeof(T) == 8) {
+        *reinterpret_cast<v2d *>(p) = v2d{v[0], v[1]};
+    } else {
+        *reinterpret_cast<v4f_mcg *>(p) = v4f_mcg{v[0], v[1], v[2], v[3]};
+    }
+}
+
+// the value of lane ^ STEP (a true xor: the column lanes below STEP must not be mixed)
+template <int STEP>
+__device__ __forceinline__ double mcg_xor_partner(double v) {
+    if constexpr (STEP <= 2) {
+        return partner<STEP>(v);  // quad_perm xor
+    } else if constexpr (STEP < 32) {
+        constexpr int kSwz = 0x1F | (STEP << 10);  // ds_swizzle bit mode: and 0x1f, or 0, xor STEP
+        const int lo = __builtin_amdgcn_ds_swizzle(__double2loint(v), kSwz);
+        const int hi = __builtin_amdgcn_ds_swizzle(__double2hiint(v), kSwz);
+        return __hiloint2double(hi, lo);
+    } else {
+        return partner<32>(v);
+    }
+}
+
+// sum over the lanes of a wave with the same lane % 2^cl (the rows of one column); every lane gets its sum.  cl = 0
+// is group_sum<64>, the tree of dot_partial.
+__device__ __forceinline__ double mcg_rows_sum(double v, int cl) {
+    if (cl == 0) return group_sum<64>(v);
+    if (cl <= 1) v += mcg_xor_partner<2>(v);
+    if (cl <= 2) v += mcg_xor_partner<4>(v);
+    if (cl <= 3) v += mcg_xor_partner<8>(v);
+    if (cl <= 4) v += mcg_xor_partner<16>(v);
+    if (cl <= 5) v += mcg_xor_partner<32>(v);
+    return v;
+}
+
+// the lane's first row, its row stride and its first column (j0 >= k: an idle lane)
+struct McgLane {
+    long long row, stride;
+    int j0;
+    __device__ __forceinline__ McgLane(int cl, int V) {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        const long long rows_per_block = kBlock >> cl;
+        row = (long long)blockIdx.x * rows_per_block + ((long long)wave << (6 - cl)) + (lane >> cl);
+        stride = (long long)gridDim.x * rows_per_block;
+        j0 = (lane & ((1 << cl) - 1)) * V;
+    }
+};
+
+// the lane's V column sums -> the workgroup's partials part[blockIdx.x * k + j], waves added in order
+template <int V>
+__device__ __forceinline__ void mcg_block_partials(double (&acc)[V], int k, int cl, int j0, double *__restrict__ part) {
+    __shared__ double wave_sum[kBlock / 64][kMcgMaxK];
+#pragma unroll
+    for (int v = 0; v < V; ++v) acc[v] = mcg_rows_sum(acc[v], cl);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if ((lane >> cl) == 0) {
+#pragma unroll
+        for (int v = 0; v < V; ++v)
+            if (j0 + v < k) wave_sum[wave][j0 + v] = acc[v];
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < k) {
+        const int j = threadIdx.x;
+        double s = wave_sum[0][j];
+        for (int w = 1; w < kBlock / 64; ++w) s += wave_sum[w][j];
+        part[(long long)blockIdx.x * k + j] = s;
+    }
+}
+
+template <typename T, int V>
+__global__ __launch_bounds__(kBlock) void mcg_dot_partial(const T *__restrict__ a, const T *__restrict__ b, long long n,
+                                                          int k, int cl, double *__restrict__ part) {
+    const McgLane l(cl, V);
+    double acc[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) acc[v] = 0;
+    if (l.j0 < k) {
+        for (long long i = l.row; i < n; i += l.stride) {
+            T av[V], bv[V];
+            mcg_load<T, V>(a + i * k + l.j0, av);
+            mcg_load<T, V>(b + i * k + l.j0, bv);
+#pragma unroll
+            for (int v = 0; v < V; ++v) acc[v] += (double)av[v] * (double)bv[v];
+        }
+    }
+    mcg_block_partials<V>(acc, k, cl, l.j0, part);
+}
+
+// x += alpha p, r -= alpha q on this rank's rows (active columns), and the workgroup's partials of the new r.r
+template <typename T, int V>
+__global__ __launch_bounds__(kBlock) void mcg_update_x_r(long long n, int k, int cl, const double *__restrict__ s,
+                                                         const int *__restrict__ flags, const T *__restrict__ p,
+                                                         const T *__restrict__ q, T *__restrict__ x, T *__restrict__ r,
+                                                         double *__restrict__ part) {
+    const McgLane l(cl, V);
+    double acc[V], alpha[V];
+    bool live[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        acc[v] = 0;
+        live[v] = l.j0 + v < k && flags[kMcgAct + l.j0 + v] != 0;
+        alpha[v] = l.j0 + v < k ? s[kMcgAlpha * kMcgMaxK + l.j0 + v] : 0.0;
+    }
+    if (l.j0 < k) {
+        for (long long i = l.row; i < n; i += l.stride) {
+            const long long o = i * k + l.j0;
+            T pv[V], qv[V], xv[V], rv[V];
+            mcg_load<T, V>(p + o, pv);
+            mcg_load<T, V>(q + o, qv);
+            mcg_load<T, V>(x + o, xv);
+            mcg_load<T, V>(r + o, rv);
+#pragma unroll
+            for (int v = 0; v < V; ++v) {
+                const T xn = (T)((double)xv[v] + alpha[v] * (double)pv[v]);
+                const T rn = (T)((double)rv[v] - alpha[v] * (double)qv[v]);
+                xv[v] = live[v] ? xn : xv[v];
+                rv[v] = live[v] ? rn : rv[v];
+                acc[v] += (double)rv[v] * (double)rv[v];
+            }
+            mcg_store<T, V>(x + o, xv);
+            mcg_store<T, V>(r + o, rv);
+        }
+    }
+    mcg_block_partials<V>(acc, k, cl, l.j0, part);
+}
+
+template <typename T, int V>
+__global__ __launch_bounds__(kBlock) void mcg_update_p(long long n, int k, int cl, const double *__restrict__ s,
+                                                       const int *__restrict__ flags, const T *__restrict__ r,
+                                                       T *__restrict__ p) {
+    const McgLane l(cl, V);
+    if (l.j0 >= k) return;
+    double beta[V];
+    bool live[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        live[v] = l.j0 + v < k && flags[kMcgAct + l.j0 + v] != 0;
+        beta[v] = l.j0 + v < k ? s[kMcgBeta * kMcgMaxK + l.j0 + v] : 0.0;
+    }
+    for (long long i = l.row; i < n; i += l.stride) {
+        const long long o = i * k + l.j0;
+        T rv[V], pv[V];
+        mcg_load<T, V>(r + o, rv);
+        mcg_load<T, V>(p + o, pv);
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const T pn = (T)((double)rv[v] + beta[v] * (double)pv[v]);
+            pv[v] = live[v] ? pn : pv[v];
+        }
+        mcg_store<T, V>(p + o, pv);
+    }
+}
+
+// grid k: workgroup j folds part[g * k + j], g = 0 .. nparts, into out[j] in the order of fold_partials
+__global__ __launch_bounds__(kBlock) void mcg_fold(const double *__restrict__ part, int nparts, int k,
+                                                   double *__restrict__ out) {
+    __shared__ double wave_sum[kBlock / 64];
+    const int j = blockIdx.x;
+    double acc = 0;
+    for (int g = threadIdx.x; g < nparts; g += kBlock) acc += part[(long long)g * k + j];
+    acc = group_sum<64>(acc);
+    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = wave_sum[0];
+        for (int w = 1; w < kBlock / 64; ++w) s += wave_sum[w];
+        out[j] = s;
+    }
+}
+
+// the ranks' k sums (gathered[r * k + j]) in rank order -> out[j]; one wavefront
+__global__ __launch_bounds__(64) void mcg_rank_sum(const double *__restrict__ gathered, int ranks, int k,
+                                                   double *__restrict__ out) {
+    const int j = threadIdx.x;
+    if (j >= k) return;
+    double t = 0;
+    for (int r = 0; r < ranks; ++r) t += gathered[r * k + j];
+    out[j] = t;
+}
+
+// the scalar kernels: one wavefront, lane j = column j
+__device__ __forceinline__ void mcg_count_active(int *__restrict__ flags, bool live) {
+    const unsigned long long m = __ballot(live);
+    if (threadIdx.x == 0) flags[kMcgActive] = __popcll(m);
+}
+
+// after r.r of r = b: rs0 = rs, history row 0; a column with rs0 <= tol2 * rs0 (rs0 = 0 when tol < 1) is frozen at 0
+__global__ __launch_bounds__(64) void mcg_start(double *__restrict__ s, int *__restrict__ flags, double *__restrict__ hist,
+                                                int k, int iters, double tol2) {
+    const int j = threadIdx.x;
+    bool live = false;
+    if (j < k) {
+        const double rs = s[kMcgRs * kMcgMaxK + j];
+        s[kMcgRs0 * kMcgMaxK + j] = rs;
+        live = !(rs <= tol2 * rs);
+        flags[kMcgAct + j] = live;
+        flags[kMcgDone + j] = live ? iters : 0;
+        hist[j] = rs;
+    }
+    mcg_count_active(flags, live);
+}
+
+// alpha = rs / p.q (0 when p.q = 0), as cg_set_alpha
+__global__ __launch_bounds__(64) void mcg_set_alpha(double *__restrict__ s, int k) {
+    const int j = threadIdx.x;
+    if (j >= k) return;
+    const double pq = s[kMcgPq * kMcgMaxK + j];
+    s[kMcgAlpha * kMcgMaxK + j] = pq != 0.0 ? s[kMcgRs * kMcgMaxK + j] / pq : 0.0;
+}
+
+// after step t: beta = rs' / rs (0 when rs = 0), rs = rs', as cg_set_beta; then the freeze rule rs' <= tol2 * rs0, and
+// history row t (a frozen column repeats its last value)
+__global__ __launch_bounds__(64) void mcg_set_beta(double *__restrict__ s, int *__restrict__ flags,
+                                                   double *__restrict__ hist_row, int k, int t, double tol2) {
+    const int j = threadIdx.x;
+    bool live = false;
+    if (j < k) {
+        live = flags[kMcgAct + j] != 0;
+        if (live) {
+            const double rs = s[kMcgRs * kMcgMaxK + j], rs_new = s[kMcgRsNew * kMcgMaxK + j];
+            s[kMcgBeta * kMcgMaxK + j] = rs != 0.0 ? rs_new / rs : 0.0;
+            s[kMcgRs * kMcgMaxK + j] = rs_new;
+            if (rs_new <= tol2 * s[kMcgRs0 * kMcgMaxK + j]) {
+                live = false;
+                flags[kMcgAct + j] = 0;
+                flags[kMcgDone + j] = t;
+            }
+        }
+        hist_row[j] = s[kMcgRs * kMcgMaxK + j];
+    }
+    mcg_count_active(flags, live);
+}
+
+}  // namespace spmv

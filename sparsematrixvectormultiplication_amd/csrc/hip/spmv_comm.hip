@@ -3,6 +3,8 @@
 // its two implementations with the on-node autotune, and the timed step (kernel + exchange).
 #include "spmv_internal.hpp"
 
+#include "cg_multi_kernels.hpp"
+
 // ------------------------------------------------------------- multi-GPU
 // Hack ranges for `parts` ranks by the reference's HLL partitioner (K8: greedy over hacks,
 // weight = padded slots; src/hll_matrix.c:410-540).  bounds[p] .. bounds[p + 1] are HACK indices.
@@ -1051,5 +1053,192 @@ extern "C" int spmv_hip_csr_cg(spmv_csr_dev *m, int variant, int iters, const in
     return guarded("csr_cg", [&] {
         return m->value_bytes == 8 ? cg_body<double>(m, variant, iters, bounds, use_halo, b_host, x_host, rr_hist, ms_total)
                                    : cg_body<float>(m, variant, iters, bounds, use_halo, b_host, x_host, rr_hist, ms_total);
+    });
+}
+
+// ------------------------------------------------------------- k right-hand sides
+// spmv_hip_csr_cg_multi: k independent CG recurrences (one alpha, beta per column; not block CG) that share one SpMM
+// per step, so the matrix streams from HBM once per step for all k.  The loop of csr_cg, k wide: P (N x k, the SpMM
+// input), Q = A P (M_total x k), X and R (this rank's rows) are row-major; the vector kernels and the scalar kernels
+// are in cg_multi_kernels.hpp.  With a communicator P is all-gathered with the row bounds scaled by k (a row of P is
+// k contiguous values) and the k dot products travel as in cg_reduce: all-gathered, added in rank order.
+namespace {
+
+// part[0 .. grid) x k of this rank -> the k global sums in slot `slot` of d_s on every rank
+int mcg_reduce(const double *d_part, int grid, int k, double *d_s, double *d_gath, int slot) {
+    double *out = d_s + (size_t)slot * kMcgMaxK;
+    if (!g_comm) {
+        hipLaunchKernelGGL(mcg_fold, dim3(k), dim3(kBlock), 0, g_stream, d_part, grid, k, out);
+        return 0;
+    }
+    double *local = d_s + (size_t)kMcgLocal * kMcgMaxK;
+    hipLaunchKernelGGL(mcg_fold, dim3(k), dim3(kBlock), 0, g_stream, d_part, grid, k, local);
+    const ncclResult_t n = ncclAllGather(local, d_gath, (size_t)k, ncclDouble, g_comm, g_stream);
+    if (n != ncclSuccess) return fail("csr_cg_multi: ncclAllGather failed: %s", ncclGetErrorString(n));
+    hipLaunchKernelGGL(mcg_rank_sum, dim3(1), dim3(64), 0, g_stream, d_gath, g_comm_size, k, out);
+    return 0;
+}
+
+struct McgBuffers {
+    void *P = nullptr, *Q = nullptr, *X = nullptr, *R = nullptr;
+    double *s = nullptr, *part = nullptr, *gath = nullptr, *hist = nullptr;
+    int *flags = nullptr;
+};
+
+// the loop; V = values of T per lane (16-byte pieces or single elements).  *steps = the steps run (< iters when tol > 0
+// and every column froze).
+template <typename T, int V>
+int mcg_run(spmv_csr_dev *m, int k, int iters, double tol, const int *kbounds, const McgBuffers &b, int *steps) {
+    const long long n = m->M_local, kk = k;
+    int cl = 0;
+    while ((1 << cl) * V < k) ++cl;  // column lanes: the next power of two >= k / V
+    const long long rows_per_block = kBlock >> cl;
+    const int cap = k == 1 ? kNormBlocks : kMcgBlocks;  // k = 1: csr_cg's workgroups, csr_cg's bits
+    const int grid = (int)std::max<long long>(1, std::min<long long>(cap, (n + rows_per_block - 1) / rows_per_block));
+    const double tol2 = tol * tol;
+    T *P = (T *)b.P, *p_own = P + m->row0 * kk, *q_own = (T *)b.Q + m->row0 * kk, *x_own = (T *)b.X + m->row0 * kk;
+    T *R = (T *)b.R;
+    const dim3 g(grid), blk(kBlock);
+    hipLaunchKernelGGL((mcg_dot_partial<T, V>), g, blk, 0, g_stream, (const T *)R, (const T *)R, n, k, cl, b.part);
+    if (mcg_reduce(b.part, grid, k, b.s, b.gath, kMcgRs)) return -1;
+    hipLaunchKernelGGL(mcg_start, dim3(1), dim3(64), 0, g_stream, b.s, b.flags, b.hist, k, iters, tol2);
+    if (g_comm && spmv_hip_comm_allgatherv(P, kbounds, m->value_bytes, g_stream)) return -1;
+    *steps = iters;
+    for (int t = 1; t <= iters; ++t) {
+        if (spmv_hip_csr_spmm_on(m, k, P, b.Q, g_stream)) return -1;  // Q = A P on this rank's rows
+        hipLaunchKernelGGL((mcg_dot_partial<T, V>), g, blk, 0, g_stream, (const T *)p_own, (const T *)q_own, n, k, cl,
+                           b.part);
+        if (mcg_reduce(b.part, grid, k, b.s, b.gath, kMcgPq)) return -1;
+        hipLaunchKernelGGL(mcg_set_alpha, dim3(1), dim3(64), 0, g_stream, b.s, k);
+        hipLaunchKernelGGL((mcg_update_x_r<T, V>), g, blk, 0, g_stream, n, k, cl, (const double *)b.s,
+                           (const int *)b.flags, (const T *)p_own, (const T *)q_own, x_own, R, b.part);
+        if (mcg_reduce(b.part, grid, k, b.s, b.gath, kMcgRsNew)) return -1;
+        hipLaunchKernelGGL(mcg_set_beta, dim3(1), dim3(64), 0, g_stream, b.s, b.flags, b.hist + (size_t)t * kk, k, t,
+                           tol2);
+        hipLaunchKernelGGL((mcg_update_p<T, V>), g, blk, 0, g_stream, n, k, cl, (const double *)b.s,
+                           (const int *)b.flags, (const T *)R, p_own);
+        if (g_comm && spmv_hip_comm_allgatherv(P, kbounds, m->value_bytes, g_stream)) return -1;
+        if (tol > 0 && t % 16 == 0 && t < iters) {
+            // every rank holds the same bits, so every rank stops at the same step
+            int active = 0;
+            HIP_TRY(hipMemcpyAsync(&active, b.flags + kMcgActive, sizeof(int), hipMemcpyDeviceToHost, g_stream));
+            HIP_TRY(hipStreamSynchronize(g_stream));
+            if (active == 0) {
+                *steps = t;
+                break;
+            }
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+template <typename T>
+int mcg_body(spmv_csr_dev *m, int k, int iters, double tol, const int *bounds, const void *B_host, void *X_host,
+             double *rr_hist, int *iters_done, float *ms_total) {
+    const size_t kk = (size_t)k, vb = sizeof(T);
+    const size_t n_all = (size_t)m->M_total, n_own = (size_t)m->M_local, ncols = (size_t)m->N;
+    const size_t hist_len = ((size_t)iters + 1) * kk;
+    std::vector<int> kbounds;
+    if (g_comm) {
+        kbounds.resize((size_t)g_comm_size + 1);
+        for (int r = 0; r <= g_comm_size; ++r) kbounds[r] = bounds[r] * k;
+    }
+    McgBuffers b;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    int rc = 0, steps = 0;
+    do {
+        // P: read in whole 128-byte lines by the x-window SpMV kernels (k = 1), as the handle's x
+        const size_t p_bytes = std::max<size_t>(ncols * kk * vb, 16) + kLineBytes;
+        const size_t q_bytes = std::max<size_t>(n_all * kk * vb, 16);
+        hipError_t e = hipMalloc(&b.P, p_bytes);
+        if (e == hipSuccess) e = hipMalloc(&b.Q, q_bytes);
+        if (e == hipSuccess) e = hipMalloc(&b.X, q_bytes);
+        if (e == hipSuccess) e = hipMalloc(&b.R, std::max<size_t>(n_own * kk * vb, 16));
+        if (e == hipSuccess) e = hipMalloc((void **)&b.s, kMcgSlots * kMcgMaxK * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc((void **)&b.part, (size_t)kMcgBlocks * kMcgMaxK * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc((void **)&b.gath, (size_t)kMaxRanks * kMcgMaxK * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc((void **)&b.hist, hist_len * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc((void **)&b.flags, kMcgFlagWords * sizeof(int));
+        if (e == hipSuccess) e = hipEventCreate(&e0);
+        if (e == hipSuccess) e = hipEventCreate(&e1);
+        if (e == hipSuccess) e = hipMemsetAsync(b.P, 0, p_bytes, g_stream);
+        if (e == hipSuccess) e = hipMemsetAsync(b.Q, 0, q_bytes, g_stream);
+        if (e == hipSuccess) e = hipMemsetAsync(b.X, 0, q_bytes, g_stream);
+        if (e == hipSuccess) e = hipMemsetAsync(b.s, 0, kMcgSlots * kMcgMaxK * sizeof(double), g_stream);
+        if (e == hipSuccess) e = hipMemsetAsync(b.hist, 0, hist_len * sizeof(double), g_stream);
+        // r = b on this rank's rows; p = b: its own range of P (the rest arrives by the all-gatherv)
+        const size_t own_off = (size_t)m->row0 * kk * vb, own_bytes = n_own * kk * vb;
+        if (e == hipSuccess && n_own)
+            e = hipMemcpyAsync(b.R, (const char *)B_host + own_off, own_bytes, hipMemcpyHostToDevice, g_stream);
+        if (e == hipSuccess && n_own)
+            e = hipMemcpyAsync((char *)b.P + own_off, b.R, own_bytes, hipMemcpyDeviceToDevice, g_stream);
+        if (e == hipSuccess) e = hipEventRecord(e0, g_stream);
+        if (e != hipSuccess) { rc = fail("csr_cg_multi: setup failed: %s", hipGetErrorString(e)); break; }
+        const bool wide = kk * vb % 16 == 0;
+        rc = wide ? mcg_run<T, 16 / sizeof(T)>(m, k, iters, tol, kbounds.data(), b, &steps)
+                  : mcg_run<T, 1>(m, k, iters, tol, kbounds.data(), b, &steps);
+        if (rc) {
+            (void)hipStreamSynchronize(g_stream);
+            break;
+        }
+        e = hipEventRecord(e1, g_stream);
+        // the solution: every rank holds its rows; with a communicator all rows everywhere
+        if (e == hipSuccess && g_comm && X_host) {
+            if (spmv_hip_comm_allgatherv(b.X, kbounds.data(), m->value_bytes, g_stream)) {
+                (void)hipStreamSynchronize(g_stream);
+                rc = -1;
+                break;
+            }
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
+        float ms = 0;
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+        if (e == hipSuccess && X_host) e = hipMemcpy(X_host, b.X, n_all * kk * vb, hipMemcpyDeviceToHost);
+        const size_t run_len = ((size_t)steps + 1) * kk;
+        if (e == hipSuccess && rr_hist) e = hipMemcpy(rr_hist, b.hist, run_len * sizeof(double), hipMemcpyDeviceToHost);
+        int flags[kMcgFlagWords];
+        if (e == hipSuccess && iters_done) e = hipMemcpy(flags, b.flags, sizeof flags, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { rc = fail("csr_cg_multi: run failed: %s", hipGetErrorString(e)); break; }
+        // stopped early: every column is frozen, its history repeats its last value
+        if (rr_hist)
+            for (size_t i = run_len; i < hist_len; ++i) rr_hist[i] = rr_hist[i - kk];
+        if (iters_done) std::memcpy(iters_done, flags + kMcgDone, kk * sizeof(int));
+        if (ms_total) *ms_total = ms;
+    } while (0);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    (void)hipFree(b.P);
+    (void)hipFree(b.Q);
+    (void)hipFree(b.X);
+    (void)hipFree(b.R);
+    (void)hipFree(b.s);
+    (void)hipFree(b.part);
+    (void)hipFree(b.gath);
+    (void)hipFree(b.hist);
+    (void)hipFree(b.flags);
+    (void)hipGetLastError();  // a failed allocation above is reported by rc, not by the next launch
+    return rc;
+}
+
+}  // namespace
+
+extern "C" int spmv_hip_csr_cg_multi(spmv_csr_dev *m, int k, int iters, double tol, const int *bounds,
+                                     const void *B_host, void *X_host, double *rr_hist, int *iters_done,
+                                     float *ms_total) {
+    if (need_device()) return -1;
+    int rc = 0;
+    if (!m || iters < 0 || !B_host || !(tol >= 0)) rc = fail("csr_cg_multi: bad arguments");
+    else if (k < 1 || k > kMcgMaxK) rc = fail("csr_cg_multi: k = %d, must be in [1, %d]", k, kMcgMaxK);
+    else if (m->M_total != m->N) rc = fail("csr_cg_multi: needs a square matrix (%d x %d)", m->M_total, m->N);
+    else if (m->tiles_only) rc = fail("csr_cg_multi: a tiles-only handle has no SpMM kernels");
+    else if ((long long)m->M_total * k > 0x7fffffffLL)
+        rc = fail("csr_cg_multi: n * k = %lld values is beyond int range", (long long)m->M_total * k);
+    else if (g_comm && !bounds) rc = fail("csr_cg_multi: a communicator exists, the row bounds are required");
+    else if (g_comm_size > kMaxRanks) rc = fail("csr_cg_multi: more than %d ranks", kMaxRanks);
+    if (rc) return rc;
+    return guarded("csr_cg_multi", [&] {
+        return m->value_bytes == 8 ? mcg_body<double>(m, k, iters, tol, bounds, B_host, X_host, rr_hist, iters_done, ms_total)
+                                   : mcg_body<float>(m, k, iters, tol, bounds, B_host, X_host, rr_hist, iters_done, ms_total);
     });
 }

@@ -343,6 +343,36 @@ class CsrDevice(_Handle):
                                          hist.ctypes.data_as(nat.c_double_p), C.byref(ms)), "spmv_hip_csr_cg")
         return x, hist, float(ms.value)
 
+    def cg_multi(self, B, iters, tol=0.0, bounds=None):
+        """k independent CG recurrences from x0 = 0 that share one SpMM per step (spmv_hip_csr_cg_multi), for the k
+        columns of B (M x k, or a vector of M: k = 1).  Column j freezes once its r.r <= tol^2 times its initial r.r
+        (tol = 0: only at r.r = 0; tol > 0 also ends the loop early once every column is frozen).  Returns
+        (X (M, k), r.r history (iters + 1, k), steps each column took [k], ms)."""
+        B = np.asarray(B)
+        if B.dtype != self.dtype:
+            raise ValueError(f"B has dtype {B.dtype}, the handle holds {np.dtype(self.dtype)}")
+        if B.ndim == 1:
+            B = B.reshape(-1, 1)
+        if B.ndim != 2 or B.shape[0] != self.M or not 1 <= B.shape[1] <= 64:
+            raise ValueError(f"B must be {self.M} x k with 1 <= k <= 64, got shape {B.shape}")
+        if int(iters) < 0:
+            raise ValueError(f"iters must be >= 0, got {iters}")
+        if not float(tol) >= 0.0:
+            raise ValueError(f"tol must be >= 0, got {tol}")
+        B = np.ascontiguousarray(B)
+        k = B.shape[1]
+        X = np.zeros((self.M, k), dtype=self.dtype)
+        hist = np.zeros((int(iters) + 1, k))
+        done = np.zeros(k, dtype=np.int32)
+        ms = C.c_float(0)
+        bb = None if bounds is None else np.ascontiguousarray(bounds, dtype=np.int32)
+        _check(nat.lib().spmv_hip_csr_cg_multi(self.h, int(k), int(iters), float(tol),
+                                               None if bb is None else bb.ctypes.data_as(nat.c_int_p),
+                                               B.ctypes.data_as(C.c_void_p), X.ctypes.data_as(C.c_void_p),
+                                               hist.ctypes.data_as(nat.c_double_p), done.ctypes.data_as(nat.c_int_p),
+                                               C.byref(ms)), "spmv_hip_csr_cg_multi")
+        return X, hist, done, float(ms.value)
+
     def split_interior(self) -> dict:
         """Split the x-window blocks into interior (own range of x only) and boundary ones
         (spmv_hip_csr_split_interior); returns the block and entry counts."""
