@@ -466,6 +466,27 @@ int spmv_hip_csr_cg(spmv_csr_dev *m, int variant, int iters, const int *bounds, 
  * -1: k < 1 or k > 64, non-square, tiles-only handle, n*k beyond int range, a communicator without bounds. */
 int spmv_hip_csr_cg_multi(spmv_csr_dev *m, int k, int iters, double tol, const int *bounds,
                           const void *B_host, void *X_host, double *rr_hist, int *iters_done, float *ms_total);
+/* BiCGSTAB (van der Vorst 1992) for a square, possibly nonsymmetric A: x0 = 0, shadow residual r^ = r0 = b.  Two
+ * SpMVs per step (v = A p, t = A s) through the handle's launch for `variant` (SPMV_CSR_AUTO: whatever plan upload
+ * picked), on library-owned p and s; fixed-order device reductions in double, fp64 scalars that stay on the device.
+ * With a communicator every rank keeps its rows of x, r, r^, s, p all-gathered with `bounds` (two exchanges per step),
+ * the partial sums all-gathered and added in rank order: every rank holds the same bits and stops at the same step.
+ * There is no halo exchange variant.
+ * Stops: s.s <= tol^2 rr0 (a half step: x += alpha p, r = s), r.r <= tol^2 rr0 (tol = 0: only at exactly 0),
+ *   r^.v = 0 or r^.r' = 0 (BREAKDOWN_RHO), t.s = 0 or t.t = 0 (BREAKDOWN_OMEGA), a non-finite value counting as
+ *   a breakdown.  A breakdown leaves x at the last full iterate.  After a stop x and r no longer change and the
+ *   history repeats its last value.
+ * tol = 0: exactly `iters` steps are launched, no host synchronisation inside the loop.
+ * tol > 0: the host reads one device word every 16 steps and ends the loop once the solve has stopped.
+ * b_host: M_total values of the handle's dtype (a rank reads its own rows).  Out: x_host (optional) M_total values;
+ * rr_hist (optional) [iters + 1] r.r before step 1 and after every step (s.s at a converged half step);
+ * info (optional) [3]: steps taken (a converged half step counts, a step that broke down before its update does
+ * not), the status (SPMV_BICG_*), 1 when the solve stopped at a half step; *ms_total device time of the loop.
+ * -1: non-square, iters < 0, tol < 0 or not finite, a communicator without bounds, a row-range handle without a
+ * communicator, more ranks than the library supports. */
+enum { SPMV_BICG_RAN_ALL = 0, SPMV_BICG_CONVERGED = 1, SPMV_BICG_BREAKDOWN_RHO = 2, SPMV_BICG_BREAKDOWN_OMEGA = 3 };
+int spmv_hip_csr_bicgstab(spmv_csr_dev *m, int variant, int iters, double tol, const int *bounds,
+                          const void *b_host, void *x_host, double *rr_hist, int *info, float *ms_total);
 int spmv_hip_csr_split_interior(spmv_csr_dev *m, long long *counts);
 /* N4 overlap below block granularity (round 3).  On a KKT-coupled cut every block also lists lines of the coupling block,
  * which another rank owns: no interior BLOCKS -- but 13 of a row's 28 entries have their column in the rank's own range.

@@ -222,6 +222,8 @@ _PROTOTYPES = {
                                   c_float_p]),
     "spmv_hip_csr_cg_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, c_int_p, C.c_void_p, C.c_void_p,
                                         c_double_p, c_int_p, c_float_p]),
+    "spmv_hip_csr_bicgstab": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, c_int_p, C.c_void_p, C.c_void_p,
+                                        c_double_p, c_int_p, c_float_p]),
     "spmv_hip_csr_needed_ranges": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_int_p]),
     "spmv_hip_csr_split_interior": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
     "spmv_hip_csr_split_columns": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_longlong)]),

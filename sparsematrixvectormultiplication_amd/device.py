@@ -15,6 +15,8 @@ from .host import CsrHost, HllHost
 
 CSR_AUTO, CSR_THREAD_ROW, CSR_WAVE_ROW, CSR_SUBWAVE, CSR_STREAM = 0, 1, 2, 3, 4
 HLL_AUTO, HLL_THREAD_ROW, HLL_SUBWAVE, HLL_LDS = 0, 1, 2, 3
+# CsrDevice.bicgstab: info["status"] (SPMV_BICG_* of include/spmv_hip.h)
+BICG_RAN_ALL, BICG_CONVERGED, BICG_BREAKDOWN_RHO, BICG_BREAKDOWN_OMEGA = 0, 1, 2, 3
 CSR_STREAM_KERNELS = ("csr_stream", "csr_stream_local", "csr_stream_short", "csr_tile")
 HLL_LDS_KERNELS = ("hll_lds", "hll_lds_local", "csr_tile (HLL slab rows)")
 CSR_VARIANTS = {"thread_row": CSR_THREAD_ROW, "wave_row": CSR_WAVE_ROW, "subwave": CSR_SUBWAVE,
@@ -372,6 +374,33 @@ class CsrDevice(_Handle):
                                                hist.ctypes.data_as(nat.c_double_p), done.ctypes.data_as(nat.c_int_p),
                                                C.byref(ms)), "spmv_hip_csr_cg_multi")
         return X, hist, done, float(ms.value)
+
+    def bicgstab(self, b, iters, tol=0.0, variant=CSR_AUTO, bounds=None):
+        """BiCGSTAB from x0 = 0 with shadow residual r^ = b (spmv_hip_csr_bicgstab), for a square, possibly
+        nonsymmetric A.  Stops once r.r (or s.s at a half step) <= tol^2 times the initial r.r (tol = 0: only at
+        exactly 0; tol > 0 also ends the loop early), or at a breakdown.  Returns (x, r.r history (iters + 1),
+        info {"steps", "status" (BICG_*), "half_step"}, ms)."""
+        b = np.asarray(b)
+        if b.dtype != self.dtype:
+            raise ValueError(f"b has dtype {b.dtype}, the handle holds {np.dtype(self.dtype)}")
+        if b.ndim != 1 or b.shape[0] != self.M:
+            raise ValueError(f"b must be a vector of {self.M} values, got shape {b.shape}")
+        if int(iters) < 0:
+            raise ValueError(f"iters must be >= 0, got {iters}")
+        if not float(tol) >= 0.0 or not np.isfinite(float(tol)):
+            raise ValueError(f"tol must be finite and >= 0, got {tol}")
+        b = np.ascontiguousarray(b)
+        x = np.zeros(self.M, dtype=self.dtype)
+        hist = np.zeros(int(iters) + 1)
+        info = np.zeros(3, dtype=np.int32)
+        ms = C.c_float(0)
+        bb = None if bounds is None else np.ascontiguousarray(bounds, dtype=np.int32)
+        _check(nat.lib().spmv_hip_csr_bicgstab(self.h, int(variant), int(iters), float(tol),
+                                               None if bb is None else bb.ctypes.data_as(nat.c_int_p),
+                                               b.ctypes.data_as(C.c_void_p), x.ctypes.data_as(C.c_void_p),
+                                               hist.ctypes.data_as(nat.c_double_p), info.ctypes.data_as(nat.c_int_p),
+                                               C.byref(ms)), "spmv_hip_csr_bicgstab")
+        return x, hist, {"steps": int(info[0]), "status": int(info[1]), "half_step": int(info[2])}, float(ms.value)
 
     def split_interior(self) -> dict:
         """Split the x-window blocks into interior (own range of x only) and boundary ones

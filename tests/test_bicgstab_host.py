@@ -1,0 +1,104 @@
+"""BiCGSTAB on a CSR handle without a GPU: the C-ABI is exported and bound, CsrDevice.bicgstab checks its input before
+any device call, the entry point refuses a NULL handle, and the new kernels compile for gfx950 without scratch."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+import sparsematrixvectormultiplication_amd as sp
+from conftest import ROOT
+
+HIPCC = "/opt/rocm/bin/hipcc"
+SRC = os.path.join(ROOT, "sparsematrixvectormultiplication_amd", "csrc", "hip")
+VGPR_BOUND = 64  # the vector kernels stream; the cg_multi kernels sit under this too
+
+
+def test_bicgstab_symbol_is_exported_and_bound():
+    out = subprocess.run(["nm", "-D", "--defined-only", sp.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
+    assert "spmv_hip_csr_bicgstab" in exported
+    assert "spmv_hip_csr_bicgstab" in sp.EXPORTED_SYMBOLS
+    fn = sp.lib().spmv_hip_csr_bicgstab
+    assert fn.restype is C.c_int
+    assert len(fn.argtypes) == 10
+    assert fn.argtypes[1] is C.c_int and fn.argtypes[2] is C.c_int   # variant, iters
+    assert fn.argtypes[3] is C.c_double                               # tol
+    assert fn.argtypes[8] is C.POINTER(C.c_int)                       # info
+    assert (sp.BICG_RAN_ALL, sp.BICG_CONVERGED, sp.BICG_BREAKDOWN_RHO, sp.BICG_BREAKDOWN_OMEGA) == (0, 1, 2, 3)
+
+
+def test_bicgstab_status_values_match_the_header():
+    text = open(os.path.join(ROOT, "include", "spmv_hip.h")).read()
+    for name, value in (("RAN_ALL", 0), ("CONVERGED", 1), ("BREAKDOWN_RHO", 2), ("BREAKDOWN_OMEGA", 3)):
+        assert re.search(rf"SPMV_BICG_{name}\s*=\s*{value}\b", text), name
+
+
+def _handle_without_device(M=5, N=5, dtype=np.float64):
+    dev = sp.CsrDevice.__new__(sp.CsrDevice)
+    sp.device._Handle.__init__(dev)  # a NULL handle: any device call would fail, not raise ValueError
+    dev.M, dev.N, dev.dtype = M, N, dtype
+    return dev
+
+
+@pytest.mark.parametrize("b", [np.zeros(4), np.zeros(6), np.zeros((5, 1)), np.zeros(5, dtype=np.float32),
+                               np.zeros(5, dtype=np.int64)],
+                         ids=["short", "long", "2d", "fp32", "int"])
+def test_bicgstab_rejects_wrong_length_or_dtype_before_any_device_call(b):
+    dev = _handle_without_device()
+    with pytest.raises(ValueError):
+        dev.bicgstab(b, 3)
+
+
+def test_bicgstab_rejects_fp64_input_on_an_fp32_handle_and_bad_scalars():
+    dev32 = _handle_without_device(dtype=np.float32)
+    with pytest.raises(ValueError):
+        dev32.bicgstab(np.zeros(5), 3)
+    dev = _handle_without_device()
+    with pytest.raises(ValueError):
+        dev.bicgstab(np.zeros(5), -1)
+    for tol in (-1e-3, float("nan"), float("inf")):
+        with pytest.raises(ValueError):
+            dev.bicgstab(np.zeros(5), 3, tol=tol)
+
+
+def test_bicgstab_refuses_a_null_handle():
+    if sp.device_count() > 0:
+        pytest.skip("a HIP device is present; the no-device behaviour is checked on CPU hosts")
+    buf = (C.c_double * 8)()
+    hist = (C.c_double * 8)()
+    info = (C.c_int * 3)()
+    ms = C.c_float(0)
+    assert sp.lib().spmv_hip_csr_bicgstab(None, 0, 3, 0.0, None, buf, buf, hist, info, C.byref(ms)) == -1
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+def test_bicgstab_kernels_compile_for_gfx950_without_scratch():
+    tmp = tempfile.mkdtemp(prefix="spmv_bcg_")
+    try:
+        proc = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
+                               "-I" + SRC, "-c", os.path.join(SRC, "spmv_bicgstab.hip"), "-o", os.path.join(tmp, "o.o"),
+                               "-save-temps=obj"], capture_output=True, text=True, timeout=600, cwd=tmp)
+        assert proc.returncode == 0, proc.stderr[-2000:]
+        asm = [f for f in os.listdir(tmp) if f.endswith("gfx950.s")]
+        assert asm, os.listdir(tmp)
+        text = open(os.path.join(tmp, asm[0])).read()
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    kernels = {}
+    for m in re.finditer(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)", text):
+        kernels[m.group(1)] = (int(m.group(2)), int(m.group(3)))
+    bcg = {k: v for k, v in kernels.items() if "bcg_" in k}
+    # the five vector kernels x {fp64 in 16-byte pieces of 2, fp32 in pieces of 4}
+    vector = [k for k in bcg if re.search(r"bcg_(dot|dot2|update_s|update_x_r|update_p)I(dLi2|fLi4)E", k)]
+    assert len(vector) == 10, sorted(bcg)
+    for name in ("bcg_fold", "bcg_rank_sum", "bcg_start", "bcg_set_alpha", "bcg_check_s", "bcg_set_omega",
+                 "bcg_set_beta"):
+        assert any(name in k for k in bcg), (name, sorted(bcg))
+    for name, (scratch, vgprs) in bcg.items():
+        assert scratch == 0, f"{name} spills {scratch} bytes of scratch ({vgprs} VGPRs)"
+        assert vgprs <= VGPR_BOUND, f"{name}: {vgprs} VGPRs > {VGPR_BOUND}"
