@@ -262,6 +262,16 @@ int spmv_hip_csr_from_coo(int M, int N, long long nz, const int *I, const int *J
 /* the handle's CSR arrays back to the host: row_ptr[M_local + 1] rebased to 0, col[nz], val[nz] (handle's
  * dtype); any pointer may be NULL */
 int spmv_hip_csr_download(const spmv_csr_dev *m, int *row_ptr, int *col, void *val);
+/* A^T of a whole CSR handle, built on the device, as a new handle of N rows and M columns with the same dtype.
+ * Row j of the result holds the entries of column j of A in ascending row order.  Entries that repeat a (row, column)
+ * pair keep their order in A.  Values are moved, never combined, so the arrays are a permutation of A's: bit-exact.
+ * The build is one stable radix sort of the entries by column on the device; only the N + 1 row pointers of A^T cross
+ * to the host.  The result is an ordinary handle: upload's plans and searches apply to it, and it owns its arrays
+ * (freeing either handle leaves the other usable).
+ * -1: NULL argument, a row-range handle (row0 != 0 or M_local != M_total), a handle without its CSR arrays
+ * (tiles-only), M * value_bytes (the transpose's x) beyond the kernels' 32-bit gather range.  *out stays NULL on
+ * failure. */
+int spmv_hip_csr_transpose(const spmv_csr_dev *m, spmv_csr_dev **out);
 /* convenience over the kept struct */
 int spmv_hip_csr_upload_matrix(const CSRMatrix *csr, spmv_csr_dev **out);
 void spmv_hip_csr_free(spmv_csr_dev *m);
@@ -487,6 +497,27 @@ int spmv_hip_csr_cg_multi(spmv_csr_dev *m, int k, int iters, double tol, const i
 enum { SPMV_BICG_RAN_ALL = 0, SPMV_BICG_CONVERGED = 1, SPMV_BICG_BREAKDOWN_RHO = 2, SPMV_BICG_BREAKDOWN_OMEGA = 3 };
 int spmv_hip_csr_bicgstab(spmv_csr_dev *m, int variant, int iters, double tol, const int *bounds,
                           const void *b_host, void *x_host, double *rr_hist, int *info, float *ms_total);
+/* CGLS (conjugate gradients on the normal equations, the stable form of Bjorck, Elfving and Strakos 1998) for
+ * min ||A x - b||_2^2 + damp^2 ||x||_2^2, A of any shape (M x N), x0 = 0.  mt must be a transpose of m
+ * (spmv_hip_csr_transpose): same dtype, N x M, the same nz.  Only those properties are checked.
+ *   r = b, s = A^T r, p = s, gamma = s.s
+ *   each step: q = A p (m's AUTO launch), delta = q.q + damp^2 p.p, alpha = gamma / delta,
+ *              x += alpha p, r -= alpha q, s = A^T r - damp^2 x (mt's AUTO launch), gamma' = s.s,
+ *              stop if gamma' <= tol^2 gamma0, beta = gamma' / gamma, p = s + beta p
+ * From x0 = 0 it converges to the minimum-norm least-squares solution when damp = 0.
+ * Scalars are fp64 on the device.  Dots are accumulated in double in a fixed order: two calls give the same bits.
+ * tol = 0: exactly `iters` steps, no host synchronisation.  tol > 0: one device word is read every 16 steps.
+ * Breakdown: delta == 0 while gamma > 0, or any non-finite scalar.  It stops with x at the last full iterate and
+ * never writes a NaN into x.  gamma0 == 0 (A^T b = 0): converged at step 0, x = 0.
+ * After a stop x and r no longer change and both histories repeat their last value.
+ * Single device: no communicator, no row bounds.
+ * b_host: M values of the handle's dtype.  Out (all optional): x_host N values; ss_hist [iters + 1] s.s;
+ * rr_hist [iters + 1] r.r (the recurrence's ||b - A x||^2); info[2] = {steps, status}; *ms_total device time.
+ * -1: NULL m / mt / b_host, mt not N x M or nz / dtype differ, a row-range or tiles-only handle, iters < 0,
+ * tol or damp negative or not finite. */
+enum { SPMV_CGLS_RAN_ALL = 0, SPMV_CGLS_CONVERGED = 1, SPMV_CGLS_BREAKDOWN = 2 };
+int spmv_hip_csr_cgls(spmv_csr_dev *m, spmv_csr_dev *mt, int iters, double tol, double damp, const void *b_host,
+                      void *x_host, double *ss_hist, double *rr_hist, int *info, float *ms_total);
 int spmv_hip_csr_split_interior(spmv_csr_dev *m, long long *counts);
 /* N4 overlap below block granularity (round 3).  On a KKT-coupled cut every block also lists lines of the coupling block,
  * which another rank owns: no interior BLOCKS -- but 13 of a row's 28 entries have their column in the rank's own range.

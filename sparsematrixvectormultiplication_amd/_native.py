@@ -224,6 +224,9 @@ _PROTOTYPES = {
                                         c_double_p, c_int_p, c_float_p]),
     "spmv_hip_csr_bicgstab": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, c_int_p, C.c_void_p, C.c_void_p,
                                         c_double_p, c_int_p, c_float_p]),
+    "spmv_hip_csr_transpose": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "spmv_hip_csr_cgls": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                    c_double_p, c_double_p, c_int_p, c_float_p]),
     "spmv_hip_csr_needed_ranges": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_int_p]),
     "spmv_hip_csr_split_interior": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
     "spmv_hip_csr_split_columns": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_longlong)]),

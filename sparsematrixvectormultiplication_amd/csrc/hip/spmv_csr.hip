@@ -1633,6 +1633,10 @@ extern "C" int spmv_hip_csr_tile_auto_plan(int M, int N, const int *row_ptr, con
 int csr_adopt_f64(int M, int N, const int *row_ptr_host, int *d_col, double *d_val, spmv_csr_dev **out) {
     return guarded("csr_adopt", [&] { return csr_upload_impl<double>(M, N, row_ptr_host, nullptr, nullptr, 0, M, out, d_col, d_val); });
 }
+// ... and its fp32 twin (spmv_transpose.hip)
+int csr_adopt_f32(int M, int N, const int *row_ptr_host, int *d_col, float *d_val, spmv_csr_dev **out) {
+    return guarded("csr_adopt", [&] { return csr_upload_impl<float>(M, N, row_ptr_host, nullptr, nullptr, 0, M, out, d_col, d_val); });
+}
 
 // A handle that carries NOTHING but tile plans, for rows given as (first entry, length) pairs over host arrays:
 // how an HLL slab whose columns are too scattered for the x-window plan gets csr_tile (spmv_hll.hip).  The rows

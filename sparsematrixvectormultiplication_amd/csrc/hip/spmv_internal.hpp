@@ -338,6 +338,7 @@ struct LocalPlan {
 // spmv_csr.hip: a handle around device arrays that already hold the matrix (ownership passes to the handle
 // on success only); col / val carry kPad zeroed entries behind the last one
 int csr_adopt_f64(int M, int N, const int *row_ptr_host, int *d_col, double *d_val, spmv_csr_dev **out);
+int csr_adopt_f32(int M, int N, const int *row_ptr_host, int *d_col, float *d_val, spmv_csr_dev **out);
 // spmv_csr.hip: tile plans alone for rows given as (first entry, length) over host arrays (an HLL slab's rows);
 // *out = NULL when the rows get no plan
 // (col / val: host copies of the rows' arrays, or NULL when d_col / d_val -- the same arrays on the device -- are given

@@ -1,0 +1,143 @@
+// spmv_transpose.hip -- spmv_hip_csr_transpose: A^T of a whole CSR handle, built on the device (include/spmv_hip.h).
+//
+//   tr_make_pairs   one wavefront per row: payload[e] = row << 32 | e for the row's entries (no per-entry search)
+//   radix sort      (column, payload) pairs, stable, on the ceil(log2 N) bits a column can use (rocPRIM, as
+//                   spmv_coo.hip): CSR entries are in row order, so each column's entries come out in ascending row
+//                   order and entries that repeat a (row, column) pair keep their order in A
+//   tr_gather       colT[k] = row, valT[k] = val[e] at every sorted position: values are moved, never combined
+//   tr_row_ptr      row_ptr of A^T from the sorted columns (columns without entries included)
+//
+// The columns of A are the sort's key input as they are; only the N + 1 row pointers of A^T cross to the host, and
+// the arrays go to csr_upload_impl through the adopt path, so A^T gets every plan and search an upload gives.
+#include "spmv_internal.hpp"
+
+#include <rocprim/rocprim.hpp>
+
+namespace {
+
+constexpr int kTrWaves = kBlock / 64;
+constexpr int kTrMaxGrid = 1 << 20;  // grid cap of the row kernel (rows stride over the waves beyond it)
+
+__global__ __launch_bounds__(kBlock) void tr_make_pairs(int M, const int *__restrict__ row_ptr,
+                                                        unsigned long long *__restrict__ payload) {
+    const int lane = threadIdx.x & 63;
+    const long long waves = (long long)gridDim.x * kTrWaves;
+    for (long long r = (long long)blockIdx.x * kTrWaves + (threadIdx.x >> 6); r < M; r += waves) {
+        const int e0 = row_ptr[r], e1 = row_ptr[r + 1];
+        const unsigned long long hi = (unsigned long long)r << 32;
+        for (int e = e0 + lane; e < e1; e += 64) payload[e] = hi | (unsigned)e;
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void tr_gather(long long nz, const unsigned long long *__restrict__ payload,
+                                                    const T *__restrict__ val, int *__restrict__ colT,
+                                                    T *__restrict__ valT) {
+    const long long k = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (k >= nz) return;
+    const unsigned long long p = payload[k];
+    colT[k] = (int)(p >> 32);
+    valT[k] = val[(unsigned)p];
+}
+
+// sorted columns -> row_ptr of A^T, N + 1 entries (columns without entries included)
+__global__ __launch_bounds__(kBlock) void tr_row_ptr(long long nz, int N, const unsigned *__restrict__ key,
+                                                     int *__restrict__ row_ptr) {
+    const long long e = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (e > nz) return;
+    if (e == nz) {  // columns behind the last entry's column (all of them when nz == 0)
+        const int last = nz ? (int)key[nz - 1] : -1;
+        for (int c = last + 1; c <= N; ++c) row_ptr[c] = (int)nz;
+        return;
+    }
+    const int c = (int)key[e];
+    const int prev = e ? (int)key[e - 1] : -1;
+    for (int q = prev + 1; q <= c; ++q) row_ptr[q] = (int)e;  // usually zero or one iteration
+}
+
+template <typename T>
+int csr_adopt(int M, int N, const int *row_ptr_host, int *d_col, T *d_val, spmv_csr_dev **out) {
+    if constexpr (sizeof(T) == 8) return csr_adopt_f64(M, N, row_ptr_host, d_col, d_val, out);
+    else return csr_adopt_f32(M, N, row_ptr_host, d_col, d_val, out);
+}
+
+template <typename T>
+int transpose_body(const spmv_csr_dev *m, spmv_csr_dev **out) {
+    const int M = m->M_total, N = m->N;
+    const long long nz = m->nz;
+    const size_t n = (size_t)nz, n1 = std::max<size_t>(n, 1);
+    unsigned long long *d_pin = nullptr, *d_pout = nullptr;
+    unsigned *d_kout = nullptr;
+    int *d_colT = nullptr, *d_rpT = nullptr;
+    T *d_valT = nullptr;
+    void *d_tmp = nullptr;
+    std::vector<int> rp((size_t)N + 1, 0);
+    UploadTrace trace("csr_transpose");  // SPMV_TRACE_UPLOAD=1: the build here, then upload's own phases
+    int rc = -1;
+    do {
+        hipError_t e = hipMalloc((void **)&d_pin, n1 * sizeof(unsigned long long));
+        if (e == hipSuccess) e = hipMalloc((void **)&d_pout, n1 * sizeof(unsigned long long));
+        if (e == hipSuccess) e = hipMalloc((void **)&d_kout, n1 * sizeof(unsigned));
+        if (e == hipSuccess) e = hipMalloc((void **)&d_colT, (n + kPad) * sizeof(int));
+        if (e == hipSuccess) e = hipMalloc((void **)&d_valT, (n + kPad) * sizeof(T));
+        if (e == hipSuccess) e = hipMalloc((void **)&d_rpT, ((size_t)N + 1) * sizeof(int));
+        if (e == hipSuccess) e = hipMemsetAsync(d_colT + n, 0, kPad * sizeof(int), g_stream);
+        if (e == hipSuccess) e = hipMemsetAsync(d_valT + n, 0, kPad * sizeof(T), g_stream);
+        if (e != hipSuccess) { fail("csr_transpose: allocation failed: %s", hipGetErrorString(e)); break; }
+        if (n) {
+            const int rgrid = (int)std::min<long long>(kTrMaxGrid, ((long long)M + kTrWaves - 1) / kTrWaves);
+            hipLaunchKernelGGL(tr_make_pairs, dim3(rgrid), dim3(kBlock), 0, g_stream, M, m->row_ptr, d_pin);
+            // only the bits a column index can use (a matrix of one column: a single bit, every key 0)
+            unsigned col_bits = 1;
+            while (col_bits < 32 && (1ull << col_bits) < (unsigned long long)N) ++col_bits;
+            const unsigned *keys = reinterpret_cast<const unsigned *>(m->col);  // columns are in [0, N)
+            size_t tmp_bytes = 0;
+            e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys, d_kout, d_pin, d_pout, n, 0u, col_bits, g_stream);
+            if (e == hipSuccess) e = hipMalloc(&d_tmp, std::max<size_t>(tmp_bytes, 16));
+            if (e == hipSuccess)
+                e = rocprim::radix_sort_pairs(d_tmp, tmp_bytes, keys, d_kout, d_pin, d_pout, n, 0u, col_bits, g_stream);
+            if (e != hipSuccess) { fail("csr_transpose: sort failed: %s", hipGetErrorString(e)); break; }
+            const int egrid = (int)((nz + kBlock - 1) / kBlock);
+            hipLaunchKernelGGL((tr_gather<T>), dim3(egrid), dim3(kBlock), 0, g_stream, nz, d_pout, (const T *)m->val,
+                               d_colT, d_valT);
+        }
+        const int pgrid = (int)((nz + kBlock) / kBlock);  // covers e == nz as well
+        hipLaunchKernelGGL(tr_row_ptr, dim3(pgrid), dim3(kBlock), 0, g_stream, nz, N, d_kout, d_rpT);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(rp.data(), d_rpT, rp.size() * sizeof(int), hipMemcpyDeviceToHost, g_stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
+        if (e != hipSuccess) { fail("csr_transpose: build failed: %s", hipGetErrorString(e)); break; }
+        trace.mark("device build");
+        rc = csr_adopt<T>(N, M, rp.data(), d_colT, d_valT, out);
+        if (rc == 0) d_colT = nullptr, d_valT = nullptr;  // the handle owns them now
+    } while (0);
+    (void)hipFree(d_pin);
+    (void)hipFree(d_pout);
+    (void)hipFree(d_kout);
+    (void)hipFree(d_rpT);
+    (void)hipFree(d_tmp);
+    (void)hipFree(d_colT);
+    (void)hipFree(d_valT);
+    (void)hipGetLastError();  // a failed allocation above is reported by rc, not by the next launch
+    return rc;
+}
+
+}  // namespace
+
+extern "C" int spmv_hip_csr_transpose(const spmv_csr_dev *m, spmv_csr_dev **out) {
+    if (need_device()) return -1;
+    if (!out) return fail("csr_transpose: out is NULL");
+    *out = nullptr;
+    if (!m) return fail("csr_transpose: NULL handle");
+    if (m->row0 != 0 || m->M_local != m->M_total)
+        return fail("csr_transpose: a handle of rows [%d, %d) of %d; only whole matrices transpose", m->row0,
+                    m->row0 + m->M_local, m->M_total);
+    if (m->tiles_only || !m->row_ptr || (m->nz > 0 && (!m->col || !m->val)))
+        return fail("csr_transpose: the handle does not hold its CSR arrays");
+    if ((unsigned long long)m->M_total * (unsigned long long)m->value_bytes >= (1ull << 32))
+        return fail("csr_transpose: M = %d: the transpose's x exceeds the 32-bit gather offset range of the kernels",
+                    m->M_total);
+    return guarded("csr_transpose", [&] {
+        return m->value_bytes == 8 ? transpose_body<double>(m, out) : transpose_body<float>(m, out);
+    });
+}

@@ -17,6 +17,8 @@ CSR_AUTO, CSR_THREAD_ROW, CSR_WAVE_ROW, CSR_SUBWAVE, CSR_STREAM = 0, 1, 2, 3, 4
 HLL_AUTO, HLL_THREAD_ROW, HLL_SUBWAVE, HLL_LDS = 0, 1, 2, 3
 # CsrDevice.bicgstab: info["status"] (SPMV_BICG_* of include/spmv_hip.h)
 BICG_RAN_ALL, BICG_CONVERGED, BICG_BREAKDOWN_RHO, BICG_BREAKDOWN_OMEGA = 0, 1, 2, 3
+# CsrDevice.cgls: info["status"] (SPMV_CGLS_* of include/spmv_hip.h)
+CGLS_RAN_ALL, CGLS_CONVERGED, CGLS_BREAKDOWN = 0, 1, 2
 CSR_STREAM_KERNELS = ("csr_stream", "csr_stream_local", "csr_stream_short", "csr_tile")
 HLL_LDS_KERNELS = ("hll_lds", "hll_lds_local", "csr_tile (HLL slab rows)")
 CSR_VARIANTS = {"thread_row": CSR_THREAD_ROW, "wave_row": CSR_WAVE_ROW, "subwave": CSR_SUBWAVE,
@@ -203,6 +205,15 @@ class CsrDevice(_Handle):
                                                C.byref(self.h)), "spmv_hip_csr_from_coo")
         self.M, self.N, self.dtype = int(M), int(N), np.float64
         return self
+
+    def transpose(self) -> "CsrDevice":
+        """A^T as a new handle (spmv_hip_csr_transpose): built on the device from this handle's arrays, N x M, the same
+        dtype, bit-exact values; it gets the plans an upload of A^T would get and owns its arrays."""
+        out = CsrDevice.__new__(CsrDevice)
+        _Handle.__init__(out)
+        _check(nat.lib().spmv_hip_csr_transpose(self.h, C.byref(out.h)), "spmv_hip_csr_transpose")
+        out.M, out.N, out.dtype = self.N, self.M, self.dtype
+        return out
 
     def download(self):
         """(row_ptr, col_idx, values) of the handle's rows, from the device."""
@@ -401,6 +412,43 @@ class CsrDevice(_Handle):
                                                hist.ctypes.data_as(nat.c_double_p), info.ctypes.data_as(nat.c_int_p),
                                                C.byref(ms)), "spmv_hip_csr_bicgstab")
         return x, hist, {"steps": int(info[0]), "status": int(info[1]), "half_step": int(info[2])}, float(ms.value)
+
+    def cgls(self, b, iters, tol=0.0, damp=0.0, at=None):
+        """CGLS from x0 = 0 for min ||A x - b||^2 + damp^2 ||x||^2, A of any shape (spmv_hip_csr_cgls).  at: a
+        transpose of this handle (CsrDevice.transpose); None: one is built for the call and freed after it (its build
+        is not part of ms).  Stops once s.s <= tol^2 times the initial s.s (tol = 0: only at exactly 0; tol > 0 also
+        ends the loop early), or at a breakdown.  Returns (x (N), s.s history (iters + 1), r.r history (iters + 1),
+        info {"steps", "status" (CGLS_*)}, ms)."""
+        b = np.asarray(b)
+        if b.dtype != self.dtype:
+            raise ValueError(f"b has dtype {b.dtype}, the handle holds {np.dtype(self.dtype)}")
+        if b.ndim != 1 or b.shape[0] != self.M:
+            raise ValueError(f"b must be a vector of {self.M} values, got shape {b.shape}")
+        if int(iters) < 0:
+            raise ValueError(f"iters must be >= 0, got {iters}")
+        for name, v in (("tol", tol), ("damp", damp)):
+            if not float(v) >= 0.0 or not np.isfinite(float(v)):
+                raise ValueError(f"{name} must be finite and >= 0, got {v}")
+        if at is not None and not isinstance(at, CsrDevice):
+            raise ValueError("at must be a CsrDevice holding the transpose")
+        b = np.ascontiguousarray(b)
+        own = at is None
+        if own:
+            at = self.transpose()
+        try:
+            x = np.zeros(self.N, dtype=self.dtype)
+            ss = np.zeros(int(iters) + 1)
+            rr = np.zeros(int(iters) + 1)
+            info = np.zeros(2, dtype=np.int32)
+            ms = C.c_float(0)
+            _check(nat.lib().spmv_hip_csr_cgls(self.h, at.h, int(iters), float(tol), float(damp),
+                                               b.ctypes.data_as(C.c_void_p), x.ctypes.data_as(C.c_void_p),
+                                               ss.ctypes.data_as(nat.c_double_p), rr.ctypes.data_as(nat.c_double_p),
+                                               info.ctypes.data_as(nat.c_int_p), C.byref(ms)), "spmv_hip_csr_cgls")
+        finally:
+            if own:
+                at.close()
+        return x, ss, rr, {"steps": int(info[0]), "status": int(info[1])}, float(ms.value)
 
     def split_interior(self) -> dict:
         """Split the x-window blocks into interior (own range of x only) and boundary ones
