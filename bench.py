@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- SpMV throughput on MI355X, the reference's protocol, one JSON line.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload nlpkkt|cant|cant_hll|powerlaw] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload nlpkkt|cant|cant_hll|powerlaw] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one SpMV y = A x over the whole matrix (x = 1, the reference's input,
@@ -16,7 +16,13 @@ for.  SuiteSparse files are not available offline, so unless --mtx points at the
 real file a seeded, shape-matched stand-in is generated (M = 3 542 400 like
 nlpkkt120, ~98 M nnz, <= 28 per row; include/synth_matrix.h) and labelled as such.
 configs[1]/[2] (cant CSR / HLL: 49 MB, Infinity-Cache resident, ~6 us at the
-roofline, i.e. launch-bound) are reported in the same line under "also".
+roofline, i.e. launch-bound) are reported in the same line under "also" with --full.
+
+A plain run does what the headline needs and no more: set up, settle, warm up, time
+the K steps, dump y if asked, print the line.  --full adds, after the timed steps,
+what takes runs of its own: the box record (sysfs state, a 1 GiB stream probe), the
+CPU baseline with the reference's thread sweep and the parity gate against it (N = 1,
+fp64), and the side measurements under "also" (N = 1, default workload).
 
 Timing: W untimed steps, then exactly K steps between (barrier +
 torch.cuda.synchronize()) pairs, max over ranks.  Every timed launch is also
@@ -126,15 +132,19 @@ def parse_args():
     p.add_argument("--exchange", default="rccl", choices=["rccl", "torch", "gloo-host"],
                    help="gloo-host: debug transport through host memory (several ranks may share one GPU)")
     p.add_argument("--check", action="store_true", help="every rank checks the gathered y against the oracle")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-cpu-sweep", action="store_true", help="skip the reference's thread sweep (main.c:18)")
-    p.add_argument("--no-also", action="store_true", help="skip the cant CSR/HLL side measurements")
-    p.add_argument("--cpu-iters", type=int, default=0, help="0 = size for ~10 s")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also record the box, run the CPU baseline (with its thread sweep and the "
+                        "parity gate against it) and the side measurements under \"also\"; the --no-* options below "
+                        "drop parts of that")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and its parity gate")
+    p.add_argument("--no-cpu-sweep", action="store_true", help="with --full: skip the reference's thread sweep (main.c:18)")
+    p.add_argument("--no-also", action="store_true", help="with --full: skip the side measurements")
+    p.add_argument("--cpu-iters", type=int, default=0, help="with --full: 0 = size for ~10 s")
     p.add_argument("--dist-timeout", type=int, default=int(os.environ.get("SPMV_DIST_TIMEOUT", "300")),
                    help="seconds a rank waits in a torch.distributed collective before it gives up (N > 1)")
     p.add_argument("--fail-rank", type=int, default=-1,
                    help="TEST ONLY: this rank raises before the timed region (the job must end non-zero, not hang)")
-    p.add_argument("--no-box-state", action="store_true", help="skip the sysfs / stream-probe record of the box")
+    p.add_argument("--no-box-state", action="store_true", help="with --full: skip the sysfs / stream-probe record of the box")
     p.add_argument("--dump-outputs", metavar="DIR", default=None,
                    help="after the timed steps, write what the last one computed (the gathered y) to DIR/y.npy; "
                         "a y over the size limit is written as DIR/y_sample.npy, a fixed seeded sample of its rows")
@@ -861,7 +871,7 @@ def main():
                          "kernel_ms_mean": round(k_ms, 5),
                          "kernel_ms_min": round(float(np.min(ms_kernel)), 5) if slow == 0 else None},
         }
-        if not args.no_box_state:
+        if args.full and not args.no_box_state:
             # what distinguishes this box from the next one of the pool (the same code runs the headline kernel in
             # 180-187 or 199-204 us depending on it): HIP attributes, sysfs state of the card, a read-only stream probe
             try:
@@ -881,8 +891,8 @@ def main():
             result["config"]["allgatherv_autotune_ms"] = autotune_ms
             result["config"]["rows_per_rank"] = [int(bounds[r + 1] - bounds[r]) for r in range(world)]
 
-    # CPU baseline + oracle check: rank 0, N = 1 only (bounded, ~10 s)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and vb == 8:
+    # --full: CPU baseline + oracle check, rank 0, N = 1 only (bounded, ~10 s)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and vb == 8:
         wl["col_full"], wl["val_full"] = wl["col"], wl["val"]
         cb, y_cpu = cpu_baseline_hll(wl, args.cpu_iters) if hll_mode else cpu_baseline(wl, args.cpu_iters)
         if not args.no_cpu_sweep:
@@ -900,7 +910,7 @@ def main():
             result["value"] = None
             result["invalid"] = "parity gate failed"
             parity_failed = True
-    if rank == 0 and world == 1 and not args.no_also and args.workload == "nlpkkt":
+    if args.full and rank == 0 and world == 1 and not args.no_also and args.workload == "nlpkkt":
         dev.close()
         result["also"] = []
         for which in ("cant_csr", "cant_hll", "fem_large_csr", "powerlaw_f32", "road_like", "wide_band", "dense_band"):

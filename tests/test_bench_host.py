@@ -80,3 +80,14 @@ def test_dump_outputs_whole_or_a_seeded_sample(tmp_path, monkeypatch):
     assert s1.dtype == np.float64 and s1.nbytes <= 800 and len(s1) == 50
     assert np.all(np.diff(s1) > 0) and np.all(np.isin(s1, y64))
     assert s1.tobytes() == s2.tobytes()
+
+
+def test_plain_run_leaves_the_extra_measurements_to_full(monkeypatch):
+    """`bench.py --gpus 1 --steps N --warmup W` is a plain run; the box record, CPU baseline and side measurements
+    need --full, and the --no-* options only drop parts of a --full run."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2"])
+    args = bench.parse_args()
+    assert not args.full and (args.steps, args.warmup) == (4, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-also"])
+    args = bench.parse_args()
+    assert args.full and args.no_also and not args.no_cpu_baseline and not args.no_box_state

@@ -143,6 +143,28 @@ def test_bench_powerlaw_two_ranks_checked_against_the_oracle(gpu):
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_times_the_headline_and_full_adds_the_rest(gpu):
+    """A plain run prints the headline with no box record, CPU baseline, parity gate or side measurements; --full
+    adds the box record and the CPU baseline with its parity gate (`also` belongs to the default workload only)."""
+    import json
+    import sys
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+            "--workload", "cant", "--grid", "5,5,40", "--settle-ms", "0"]
+    outs = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-cpu-sweep", "--cpu-iters", "5"])):
+        proc = subprocess.run(base + extra, capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert proc.returncode == 0, proc.stderr[-3000:]
+        outs[mode] = json.loads([ln for ln in proc.stdout.splitlines() if ln.startswith("{")][-1])
+    plain, full = outs["plain"], outs["full"]
+    for out in (plain, full):
+        assert out["value"] > 0 and out["unit"] == "GFLOP/s" and out["dtype"] == "f64" and out["ms_per_step"] > 0
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["roofline"]["kernel_ms_mean"] > 0
+    assert not {"box", "cpu_baseline", "parity_vs_cpu_reference", "also"} & set(plain)
+    assert "box" in full and full["cpu_baseline"]["value"] > 0 and "thread_sweep" not in full["cpu_baseline"]
+    assert full["parity_vs_cpu_reference"]["parity_ok"]
+
+
+@pytest.mark.gpu
 def test_bench_dumps_what_the_last_timed_step_computed(tmp_path, gpu, oracle):
     """--dump-outputs DIR: after the --steps timed steps, the y of the last one lands in DIR/y.npy in the workload's
     dtype and equals the oracle's; the result line reports the steps asked for and the time of one of them."""

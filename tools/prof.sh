@@ -14,7 +14,7 @@ export TMPDIR=/tmp
 # (the same for upload's with / without timing of the pattern plan: here the plan is simply kept -- what the un-profiled
 # bench decides for this workload on every box seen, config.pattern_plan in its line)
 export SPMV_TUNING="${SPMV_TUNING:+$SPMV_TUNING,}place_tries=0,local_patterns=1"
-BENCH="python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-also $*"
+BENCH="python3 bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-also $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $BENCH > $OUT/trace.log 2>&1
 # counters in their own passes (TCC has 4 slots: FETCH_SIZE takes 3, WRITE_SIZE 2)
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- $BENCH > $OUT/pmc_fetch.log 2>&1

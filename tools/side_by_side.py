@@ -9,7 +9,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 rows = []
 for workload in ("cant", "cant_hll", "nlpkkt"):
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--no-also"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--full", "--no-also"],
                        capture_output=True, text=True, cwd=ROOT)
     if p.returncode:
         print(p.stderr[-2000:])
