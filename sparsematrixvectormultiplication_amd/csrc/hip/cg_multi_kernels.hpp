@@ -10,22 +10,18 @@
 //   mcg_dot_partial   the k column dot products a[:, j] . b[:, j]          -> part[g * k + j] of workgroup g
 //   mcg_update_x_r    x_j += alpha_j p_j, r_j -= alpha_j q_j, and r_j . r_j -> part[g * k + j]
 //   mcg_update_p      p_j = r_j + beta_j p_j
-//   mcg_fold          one workgroup per column folds part[] in workgroup order (fold_partials, k wide)
 //   mcg_start / mcg_set_alpha / mcg_set_beta   one workgroup: the k columns' scalars, the freeze rule, the history
 //
 // Reduction order.  Products are accumulated in double, for fp32 and fp64 data alike.  A lane adds its rows in
 // grid-stride order, the rows of one column in a wave are added by an xor butterfly over the high lane bits, the
-// waves of a workgroup in wave order, the workgroups by mcg_fold in workgroup order.  None of it depends on j, so
-// permuting the columns of B permutes the results bit for bit; no atomics, so every run gives the same bits.  With
-// k = 1 (CL = 1, V = 1) the lanes, the butterfly (group_sum<64>) and the wave sums are those of dot_partial /
-// cg_update_x_r / fold_partials in spmv_comm.hip, and the host keeps their grid cap: k = 1 is csr_cg bit for bit.
+// waves of a workgroup in wave order, the workgroups by solver_fold (one workgroup per column) in workgroup order.  None
+// of it depends on j, so permuting the columns of B permutes the results bit for bit; no atomics, so every run gives
+// the same bits.  With k = 1 (CL = 1, V = 1) the lanes, the butterfly (group_sum<64>) and the wave sums are those of
+// dot_partial / cg_update_x_r in spmv_cg.hip, and the host keeps their grid cap: k = 1 is csr_cg bit for bit.
 //
 // Frozen columns (act[j] == 0) keep x, r and p: the update kernels write back what they read.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include "csr_kernels.hpp"
-#include "wave_ops.hpp"
+#include "solver_ops.hpp"
 
 namespace spmv {
 
@@ -37,33 +33,6 @@ constexpr int kMcgRs = 0, kMcgPq = 1, kMcgRsNew = 2, kMcgAlpha = 3, kMcgBeta = 4
               kMcgSlots = 7;
 // the int words: act[kMcgMaxK] (1 = still iterating), done[kMcgMaxK] (steps taken), then the count of active columns
 constexpr int kMcgAct = 0, kMcgDone = kMcgMaxK, kMcgActive = 2 * kMcgMaxK, kMcgFlagWords = 2 * kMcgMaxK + 1;
-
-typedef float v4f_mcg __attribute__((ext_vector_type(4)));
-
-template <typename T, int V>
-__device__ __forceinline__ void mcg_load(const T *__restrict__ p, T (&v)[V]) {
-    static_assert(V == 1 || V * sizeof(T) == 16, "one element or one 16-byte piece");
-    if constexpr (V == 1) {
-        v[0] = p[0];
-    } else if constexpr (sizeof(T) == 8) {
-        const v2d a = *reinterpret_cast<const v2d *>(p);
-        v[0] = a.x, v[1] = a.y;
-    } else {
-        const v4f_mcg a = *reinterpret_cast<const v4f_mcg *>(p);
-        v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w;
-    }
-}
-
-template <typename T, int V>
-__device__ __forceinline__ void mcg_store(T *__restrict__ p, const T (&v)[V]) {
-    if constexpr (V == 1) {
-        p[0] = v[0];
-    } else if constexpr (sizeof(T) == 8) {
-        *reinterpret_cast<v2d *>(p) = v2d{v[0], v[1]};
-    } else {
-        *reinterpret_cast<v4f_mcg *>(p) = v4f_mcg{v[0], v[1], v[2], v[3]};
-    }
-}
 
 // the value of lane ^ STEP (a true xor: the column lanes below STEP must not be mixed)
 template <int STEP>
@@ -136,8 +105,8 @@ __global__ __launch_bounds__(kBlock) void mcg_dot_partial(const T *__restrict__ 
     if (l.j0 < k) {
         for (long long i = l.row; i < n; i += l.stride) {
             T av[V], bv[V];
-            mcg_load<T, V>(a + i * k + l.j0, av);
-            mcg_load<T, V>(b + i * k + l.j0, bv);
+            piece_load<T, V>(a + i * k + l.j0, av);
+            piece_load<T, V>(b + i * k + l.j0, bv);
 #pragma unroll
             for (int v = 0; v < V; ++v) acc[v] += (double)av[v] * (double)bv[v];
         }
@@ -164,10 +133,10 @@ __global__ __launch_bounds__(kBlock) void mcg_update_x_r(long long n, int k, int
         for (long long i = l.row; i < n; i += l.stride) {
             const long long o = i * k + l.j0;
             T pv[V], qv[V], xv[V], rv[V];
-            mcg_load<T, V>(p + o, pv);
-            mcg_load<T, V>(q + o, qv);
-            mcg_load<T, V>(x + o, xv);
-            mcg_load<T, V>(r + o, rv);
+            piece_load<T, V>(p + o, pv);
+            piece_load<T, V>(q + o, qv);
+            piece_load<T, V>(x + o, xv);
+            piece_load<T, V>(r + o, rv);
 #pragma unroll
             for (int v = 0; v < V; ++v) {
                 const T xn = (T)((double)xv[v] + alpha[v] * (double)pv[v]);
@@ -176,8 +145,8 @@ __global__ __launch_bounds__(kBlock) void mcg_update_x_r(long long n, int k, int
                 rv[v] = live[v] ? rn : rv[v];
                 acc[v] += (double)rv[v] * (double)rv[v];
             }
-            mcg_store<T, V>(x + o, xv);
-            mcg_store<T, V>(r + o, rv);
+            piece_store<T, V>(x + o, xv);
+            piece_store<T, V>(r + o, rv);
         }
     }
     mcg_block_partials<V>(acc, k, cl, l.j0, part);
@@ -199,42 +168,15 @@ __global__ __launch_bounds__(kBlock) void mcg_update_p(long long n, int k, int c
     for (long long i = l.row; i < n; i += l.stride) {
         const long long o = i * k + l.j0;
         T rv[V], pv[V];
-        mcg_load<T, V>(r + o, rv);
-        mcg_load<T, V>(p + o, pv);
+        piece_load<T, V>(r + o, rv);
+        piece_load<T, V>(p + o, pv);
 #pragma unroll
         for (int v = 0; v < V; ++v) {
             const T pn = (T)((double)rv[v] + beta[v] * (double)pv[v]);
             pv[v] = live[v] ? pn : pv[v];
         }
-        mcg_store<T, V>(p + o, pv);
+        piece_store<T, V>(p + o, pv);
     }
-}
-
-// grid k: workgroup j folds part[g * k + j], g = 0 .. nparts, into out[j] in the order of fold_partials
-__global__ __launch_bounds__(kBlock) void mcg_fold(const double *__restrict__ part, int nparts, int k,
-                                                   double *__restrict__ out) {
-    __shared__ double wave_sum[kBlock / 64];
-    const int j = blockIdx.x;
-    double acc = 0;
-    for (int g = threadIdx.x; g < nparts; g += kBlock) acc += part[(long long)g * k + j];
-    acc = group_sum<64>(acc);
-    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = wave_sum[0];
-        for (int w = 1; w < kBlock / 64; ++w) s += wave_sum[w];
-        out[j] = s;
-    }
-}
-
-// the ranks' k sums (gathered[r * k + j]) in rank order -> out[j]; one wavefront
-__global__ __launch_bounds__(64) void mcg_rank_sum(const double *__restrict__ gathered, int ranks, int k,
-                                                   double *__restrict__ out) {
-    const int j = threadIdx.x;
-    if (j >= k) return;
-    double t = 0;
-    for (int r = 0; r < ranks; ++r) t += gathered[r * k + j];
-    out[j] = t;
 }
 
 // the scalar kernels: one wavefront, lane j = column j

@@ -17,28 +17,11 @@
 
 namespace {
 
-constexpr int kBcgMaxRanks = 64;  // as the all-gatherv
-constexpr int kBcgPoll = 16;      // tol > 0: steps between reads of the device state word
-
 struct BcgBuffers {
-    void *p = nullptr, *s = nullptr, *v = nullptr, *t = nullptr, *x = nullptr, *r = nullptr, *rhat = nullptr;
-    double *sc = nullptr, *part = nullptr, *gath = nullptr, *hist = nullptr;
-    int *flags = nullptr;
+    void *p, *s, *v, *t, *x, *r, *rhat;
+    double *sc, *part, *gath, *hist;
+    int *flags;
 };
-
-// part[0 .. grid) x nv of this rank -> the nv global sums in sc[slot ..] on every rank
-int bcg_reduce(const double *part, int grid, int nv, double *sc, double *gath, int slot) {
-    if (!g_comm) {
-        hipLaunchKernelGGL(bcg_fold, dim3(1), dim3(kBlock), 0, g_stream, part, grid, nv, sc + slot);
-        return 0;
-    }
-    double *local = sc + kBcgLocal;
-    hipLaunchKernelGGL(bcg_fold, dim3(1), dim3(kBlock), 0, g_stream, part, grid, nv, local);
-    const ncclResult_t n = ncclAllGather(local, gath, (size_t)nv, ncclDouble, g_comm, g_stream);
-    if (n != ncclSuccess) return fail("csr_bicgstab: ncclAllGather failed: %s", ncclGetErrorString(n));
-    hipLaunchKernelGGL(bcg_rank_sum, dim3(1), dim3(1), 0, g_stream, gath, g_comm_size, nv, sc + slot);
-    return 0;
-}
 
 // the loop; *steps_run = the steps launched (< iters when tol > 0 and the solve stopped)
 template <typename T>
@@ -52,42 +35,42 @@ int bcg_run(spmv_csr_dev *m, int variant, int iters, double tol, const int *boun
     T *p = (T *)b.p, *s = (T *)b.s, *v = (T *)b.v, *t = (T *)b.t, *x = (T *)b.x, *r = (T *)b.r, *rhat = (T *)b.rhat;
     const int *fl = b.flags;
     const dim3 g(grid), blk(kBlock);
+    // part[0 .. grid) x nv of this rank -> the nv global sums in sc[slot ..] on every rank
+    auto reduce = [&](int nv, int slot) {
+        return solver_reduce(b.part, grid, nv, b.sc + slot, b.sc + kBcgLocal, b.gath, "csr_bicgstab");
+    };
     // rho = r.r^, rr0 = r.r with r = r^ = b
     hipLaunchKernelGGL((bcg_dot2<T, V>), g, blk, 0, g_stream, lo, hi, fl, (const T *)r, (const T *)rhat, b.part);
-    if (bcg_reduce(b.part, grid, 2, b.sc, b.gath, kBcgRho)) return -1;
+    if (reduce(2, kBcgRho)) return -1;
     hipLaunchKernelGGL(bcg_start, dim3(1), dim3(1), 0, g_stream, b.sc, b.flags, b.hist, iters);
     if (g_comm && spmv_hip_comm_allgatherv(p, bounds, m->value_bytes, g_stream)) return -1;
     *steps_run = iters;
     for (int k = 1; k <= iters; ++k) {
         if (csr_launch_any(m, variant, p, v, g_stream)) return -1;  // v = A p on this rank's rows
         hipLaunchKernelGGL((bcg_dot<T, V>), g, blk, 0, g_stream, lo, hi, fl, (const T *)rhat, (const T *)v, b.part);
-        if (bcg_reduce(b.part, grid, 1, b.sc, b.gath, kBcgRv)) return -1;
+        if (reduce(1, kBcgRv)) return -1;
         hipLaunchKernelGGL(bcg_set_alpha, dim3(1), dim3(1), 0, g_stream, b.sc, b.flags, k);
         hipLaunchKernelGGL((bcg_update_s<T, V>), g, blk, 0, g_stream, lo, hi, fl, (const double *)b.sc, (const T *)r,
                            (const T *)v, s, b.part);
-        if (bcg_reduce(b.part, grid, 1, b.sc, b.gath, kBcgSs)) return -1;
+        if (reduce(1, kBcgSs)) return -1;
         hipLaunchKernelGGL(bcg_check_s, dim3(1), dim3(1), 0, g_stream, b.sc, b.flags, k, tol2);
         if (g_comm && spmv_hip_comm_allgatherv(s, bounds, m->value_bytes, g_stream)) return -1;
         if (csr_launch_any(m, variant, s, t, g_stream)) return -1;  // t = A s
         hipLaunchKernelGGL((bcg_dot2<T, V>), g, blk, 0, g_stream, lo, hi, fl, (const T *)t, (const T *)s, b.part);
-        if (bcg_reduce(b.part, grid, 2, b.sc, b.gath, kBcgTs)) return -1;
+        if (reduce(2, kBcgTs)) return -1;
         hipLaunchKernelGGL(bcg_set_omega, dim3(1), dim3(1), 0, g_stream, b.sc, b.flags, k);
         hipLaunchKernelGGL((bcg_update_x_r<T, V>), g, blk, 0, g_stream, lo, hi, fl, (const double *)b.sc,
                            (const T *)rhat, (const T *)p, (const T *)s, (const T *)t, x, r, b.part);
-        if (bcg_reduce(b.part, grid, 2, b.sc, b.gath, kBcgRhoNew)) return -1;
+        if (reduce(2, kBcgRhoNew)) return -1;
         hipLaunchKernelGGL(bcg_set_beta, dim3(1), dim3(1), 0, g_stream, b.sc, b.flags, b.hist, k, tol2);
         hipLaunchKernelGGL((bcg_update_p<T, V>), g, blk, 0, g_stream, lo, hi, fl, (const double *)b.sc, (const T *)r,
                            (const T *)v, p);
         if (g_comm && spmv_hip_comm_allgatherv(p, bounds, m->value_bytes, g_stream)) return -1;
-        if (tol > 0 && k % kBcgPoll == 0 && k < iters) {
-            // every rank holds the same bits, so every rank stops at the same step
-            int state = kBcgRun;
-            HIP_TRY(hipMemcpyAsync(&state, b.flags + kBcgState, sizeof(int), hipMemcpyDeviceToHost, g_stream));
-            HIP_TRY(hipStreamSynchronize(g_stream));
-            if (state == kBcgStop) {
-                *steps_run = k;
-                break;
-            }
+        bool stop = false;
+        if (solver_poll(k, iters, tol, b.flags + kBcgState, kBcgStop, &stop)) return -1;
+        if (stop) {
+            *steps_run = k;
+            break;
         }
     }
     HIP_TRY(hipGetLastError());
@@ -98,98 +81,55 @@ template <typename T>
 int bcg_body(spmv_csr_dev *m, int variant, int iters, double tol, const int *bounds, const void *b_host, void *x_host,
              double *rr_hist, int *info, float *ms_total) {
     const size_t vb = sizeof(T), n_all = (size_t)m->M_total, n_own = (size_t)m->M_local;
-    const size_t hist_len = (size_t)iters + 1;
+    SolverScope scope;
+    // p, s: SpMV inputs, read in whole 128-byte lines by the x-window kernels; the rest: whole 16-byte pieces
+    const size_t in_bytes = ((size_t)m->N * vb + 15) / 16 * 16 + kLineBytes;
+    const size_t vec_bytes = std::max<size_t>((n_all * vb + 15) / 16 * 16, 16);
     BcgBuffers b;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = 0, steps_run = 0;
-    do {
-        // p, s: SpMV inputs, read in whole 128-byte lines by the x-window kernels; the rest: whole 16-byte pieces
-        const size_t in_bytes = ((size_t)m->N * vb + 15) / 16 * 16 + kLineBytes;
-        const size_t vec_bytes = std::max<size_t>((n_all * vb + 15) / 16 * 16, 16);
-        hipError_t e = hipMalloc(&b.p, in_bytes);
-        if (e == hipSuccess) e = hipMalloc(&b.s, in_bytes);
-        if (e == hipSuccess) e = hipMalloc(&b.v, vec_bytes);
-        if (e == hipSuccess) e = hipMalloc(&b.t, vec_bytes);
-        if (e == hipSuccess) e = hipMalloc(&b.x, vec_bytes);
-        if (e == hipSuccess) e = hipMalloc(&b.r, vec_bytes);
-        if (e == hipSuccess) e = hipMalloc(&b.rhat, vec_bytes);
-        if (e == hipSuccess) e = hipMalloc((void **)&b.sc, kBcgSlots * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void **)&b.part, (size_t)kBcgBlocks * 2 * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void **)&b.gath, (size_t)kBcgMaxRanks * 2 * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void **)&b.hist, hist_len * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void **)&b.flags, kBcgFlagWords * sizeof(int));
-        if (e == hipSuccess) e = hipEventCreate(&e0);
-        if (e == hipSuccess) e = hipEventCreate(&e1);
-        if (e == hipSuccess) e = hipMemsetAsync(b.p, 0, in_bytes, g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(b.s, 0, in_bytes, g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(b.v, 0, vec_bytes, g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(b.t, 0, vec_bytes, g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(b.x, 0, vec_bytes, g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(b.sc, 0, kBcgSlots * sizeof(double), g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(b.hist, 0, hist_len * sizeof(double), g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(b.flags, 0, kBcgFlagWords * sizeof(int), g_stream);
-        // r = r^ = p = b on this rank's rows (the rest of p arrives by the all-gatherv)
-        const size_t own_off = (size_t)m->row0 * vb, own_bytes = n_own * vb;
-        if (e == hipSuccess && n_own)
-            e = hipMemcpyAsync((char *)b.r + own_off, (const char *)b_host + own_off, own_bytes, hipMemcpyHostToDevice,
-                               g_stream);
-        if (e == hipSuccess && n_own)
-            e = hipMemcpyAsync((char *)b.rhat + own_off, (char *)b.r + own_off, own_bytes, hipMemcpyDeviceToDevice,
-                               g_stream);
-        if (e == hipSuccess && n_own)
-            e = hipMemcpyAsync((char *)b.p + own_off, (char *)b.r + own_off, own_bytes, hipMemcpyDeviceToDevice,
-                               g_stream);
-        if (e == hipSuccess) e = hipEventRecord(e0, g_stream);
-        if (e != hipSuccess) { rc = fail("csr_bicgstab: setup failed: %s", hipGetErrorString(e)); break; }
-        rc = bcg_run<T>(m, variant, iters, tol, bounds, b, &steps_run);
-        if (rc) {
-            (void)hipStreamSynchronize(g_stream);
-            break;
-        }
-        e = hipEventRecord(e1, g_stream);
-        // the solution: every rank holds its rows; with a communicator all rows everywhere
-        if (e == hipSuccess && g_comm && x_host) {
-            if (spmv_hip_comm_allgatherv(b.x, bounds, m->value_bytes, g_stream)) {
-                (void)hipStreamSynchronize(g_stream);
-                rc = -1;
-                break;
-            }
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-        float ms = 0;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        if (e == hipSuccess && x_host) e = hipMemcpy(x_host, b.x, n_all * vb, hipMemcpyDeviceToHost);
-        const size_t run_len = (size_t)steps_run + 1;
-        if (e == hipSuccess && rr_hist) e = hipMemcpy(rr_hist, b.hist, run_len * sizeof(double), hipMemcpyDeviceToHost);
-        int flags[kBcgFlagWords] = {0, 0, 0, 0};
-        if (e == hipSuccess) e = hipMemcpy(flags, b.flags, sizeof flags, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { rc = fail("csr_bicgstab: run failed: %s", hipGetErrorString(e)); break; }
-        // stopped early: the history repeats its last value
-        if (rr_hist)
-            for (size_t i = run_len; i < hist_len; ++i) rr_hist[i] = rr_hist[i - 1];
-        if (info) {
-            info[0] = flags[kBcgSteps];
-            info[1] = flags[kBcgStatus];
-            info[2] = flags[kBcgHalf];
-        }
-        if (ms_total) *ms_total = ms;
-    } while (0);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(b.p);
-    (void)hipFree(b.s);
-    (void)hipFree(b.v);
-    (void)hipFree(b.t);
-    (void)hipFree(b.x);
-    (void)hipFree(b.r);
-    (void)hipFree(b.rhat);
-    (void)hipFree(b.sc);
-    (void)hipFree(b.part);
-    (void)hipFree(b.gath);
-    (void)hipFree(b.hist);
-    (void)hipFree(b.flags);
-    (void)hipGetLastError();  // a failed allocation above is reported by rc, not by the next launch
-    return rc;
+    b.p = scope.alloc(in_bytes);
+    b.s = scope.alloc(in_bytes);
+    b.v = scope.alloc(vec_bytes);
+    b.t = scope.alloc(vec_bytes);
+    b.x = scope.alloc(vec_bytes);
+    b.r = scope.alloc(vec_bytes);
+    b.rhat = scope.alloc(vec_bytes);
+    b.sc = scope.alloc<double>(kBcgSlots * sizeof(double));
+    b.part = scope.alloc<double>((size_t)kBcgBlocks * 2 * sizeof(double));
+    b.gath = scope.alloc<double>((size_t)kMaxRanks * 2 * sizeof(double));
+    b.hist = scope.alloc<double>(((size_t)iters + 1) * sizeof(double));
+    b.flags = scope.alloc<int>(kBcgFlagWords * sizeof(int));
+    // r = r^ = p = b on this rank's rows (the rest of p arrives by the all-gatherv)
+    const size_t own_off = (size_t)m->row0 * vb, own_bytes = n_own * vb;
+    hipError_t e = scope.err;
+    if (e == hipSuccess && n_own)
+        e = hipMemcpyAsync((char *)b.r + own_off, (const char *)b_host + own_off, own_bytes, hipMemcpyHostToDevice,
+                           g_stream);
+    if (e == hipSuccess && n_own)
+        e = hipMemcpyAsync((char *)b.rhat + own_off, (char *)b.r + own_off, own_bytes, hipMemcpyDeviceToDevice, g_stream);
+    if (e == hipSuccess && n_own)
+        e = hipMemcpyAsync((char *)b.p + own_off, (char *)b.r + own_off, own_bytes, hipMemcpyDeviceToDevice, g_stream);
+    if (e == hipSuccess) e = hipEventRecord(scope.e0, g_stream);
+    if (e != hipSuccess) return fail("csr_bicgstab: setup failed: %s", hipGetErrorString(e));
+    int steps_run = 0;
+    if (bcg_run<T>(m, variant, iters, tol, bounds, b, &steps_run)) return -1;
+    e = hipEventRecord(scope.e1, g_stream);
+    // the solution: every rank holds its rows; with a communicator all rows everywhere
+    if (e == hipSuccess && g_comm && x_host && spmv_hip_comm_allgatherv(b.x, bounds, m->value_bytes, g_stream)) return -1;
+    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
+    float ms = 0;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, scope.e0, scope.e1);
+    if (e == hipSuccess && x_host) e = hipMemcpy(x_host, b.x, n_all * vb, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = copy_history(rr_hist, b.hist, steps_run, iters, 1);
+    int flags[kBcgFlagWords] = {0, 0, 0, 0};
+    if (e == hipSuccess) e = hipMemcpy(flags, b.flags, sizeof flags, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail("csr_bicgstab: run failed: %s", hipGetErrorString(e));
+    if (info) {
+        info[0] = flags[kBcgSteps];
+        info[1] = flags[kBcgStatus];
+        info[2] = flags[kBcgHalf];
+    }
+    if (ms_total) *ms_total = ms;
+    return 0;
 }
 
 }  // namespace
@@ -205,7 +145,7 @@ extern "C" int spmv_hip_csr_bicgstab(spmv_csr_dev *m, int variant, int iters, do
     else if (g_comm && !bounds) rc = fail("csr_bicgstab: a communicator exists, the row bounds are required");
     else if (!g_comm && (m->row0 != 0 || m->M_local != m->M_total))
         rc = fail("csr_bicgstab: a handle of rows [%d, %d) needs a communicator", m->row0, m->row0 + m->M_local);
-    else if (g_comm_size > kBcgMaxRanks) rc = fail("csr_bicgstab: more than %d ranks", kBcgMaxRanks);
+    else if (g_comm_size > kMaxRanks) rc = fail("csr_bicgstab: more than %d ranks", kMaxRanks);
     if (rc) return rc;
     return guarded("csr_bicgstab", [&] {
         return m->value_bytes == 8 ? bcg_body<double>(m, variant, iters, tol, bounds, b_host, x_host, rr_hist, info, ms_total)

@@ -15,23 +15,16 @@
 
 namespace {
 
-constexpr int kCglsPoll = 16;  // tol > 0: steps between reads of the device state word
-
 struct CglsBuffers {
-    void *p = nullptr, *q = nullptr, *r = nullptr, *s = nullptr, *x = nullptr;
-    double *sc = nullptr, *part = nullptr, *ss_hist = nullptr, *rr_hist = nullptr;
-    int *flags = nullptr;
+    void *p, *q, *r, *s, *x;
+    double *sc, *part, *ss_hist, *rr_hist;
+    int *flags;
 };
 
 // the vector kernels' grid over n rows in pieces of V
 int cgls_grid(long long n, int V) {
     const long long pieces = (n + V - 1) / V;
     return (int)std::max<long long>(1, std::min<long long>(kCglsBlocks, (pieces + kBlock - 1) / kBlock));
-}
-
-void cgls_fold_into(const CglsBuffers &b, int grid, int slot) {
-    hipLaunchKernelGGL(cgls_fold, dim3(1), dim3(kBlock), 0, g_stream, (const int *)b.flags, (const double *)b.part,
-                       grid, b.sc + slot);
 }
 
 // the loop; *steps_run = the steps launched (< iters when tol > 0 and the solve stopped)
@@ -45,42 +38,44 @@ int cgls_run(spmv_csr_dev *m, spmv_csr_dev *mt, int iters, double tol, double da
     T *p = (T *)b.p, *q = (T *)b.q, *r = (T *)b.r, *s = (T *)b.s, *x = (T *)b.x;
     const int *fl = b.flags;
     const dim3 blk(kBlock);
+    // the grid's partials -> sc[slot].  This rank's sums only: the handles hold whole matrices, so there is nothing to
+    // add over ranks even when a communicator exists.
+    auto fold = [&](int grid, int slot) {
+        hipLaunchKernelGGL(solver_fold, dim3(1), blk, 0, g_stream, (const double *)b.part, grid, 1, b.sc + slot);
+    };
     // rr0 = r.r with r = b; s = A^T r, gamma0 = s.s; p = s
     hipLaunchKernelGGL((cgls_norm2<T, V>), dim3(gM), blk, 0, g_stream, M, fl, (const T *)r, b.part);
-    cgls_fold_into(b, gM, kCglsRr);
+    fold(gM, kCglsRr);
     if (csr_launch_any(mt, SPMV_CSR_AUTO, r, s, g_stream)) return -1;
     hipLaunchKernelGGL((cgls_norm2<T, V>), dim3(gN), blk, 0, g_stream, N, fl, (const T *)s, b.part);
-    cgls_fold_into(b, gN, kCglsSs);
+    fold(gN, kCglsSs);
     if (N) HIP_TRY(hipMemcpyAsync(p, s, (size_t)N * sizeof(T), hipMemcpyDeviceToDevice, g_stream));
     hipLaunchKernelGGL(cgls_start, dim3(1), dim3(1), 0, g_stream, b.sc, b.flags, b.ss_hist, b.rr_hist, iters);
     *steps_run = iters;
     for (int k = 1; k <= iters; ++k) {
         if (csr_launch_any(m, SPMV_CSR_AUTO, p, q, g_stream)) return -1;  // q = A p
         hipLaunchKernelGGL((cgls_norm2<T, V>), dim3(gM), blk, 0, g_stream, M, fl, (const T *)q, b.part);
-        cgls_fold_into(b, gM, kCglsQq);
+        fold(gM, kCglsQq);
         hipLaunchKernelGGL(cgls_set_alpha, dim3(1), dim3(1), 0, g_stream, b.sc, b.flags, k, damp2);
         hipLaunchKernelGGL((cgls_update_x_r<T, V>), dim3(gMN), blk, 0, g_stream, N, M, fl, (const double *)b.sc,
                            (const T *)p, (const T *)q, x, r, b.part);
-        cgls_fold_into(b, gMN, kCglsRr);
+        fold(gMN, kCglsRr);
         if (csr_launch_any(mt, SPMV_CSR_AUTO, r, s, g_stream)) return -1;  // s = A^T r
         if (damp > 0)
             hipLaunchKernelGGL((cgls_update_s<T, V>), dim3(gN), blk, 0, g_stream, N, fl, damp2, (const T *)x, s, b.part);
         else
             hipLaunchKernelGGL((cgls_norm2<T, V>), dim3(gN), blk, 0, g_stream, N, fl, (const T *)s, b.part);
-        cgls_fold_into(b, gN, kCglsSs);
+        fold(gN, kCglsSs);
         hipLaunchKernelGGL(cgls_set_beta, dim3(1), dim3(1), 0, g_stream, b.sc, b.flags, b.ss_hist, b.rr_hist, k, tol2);
         // p.p feeds the next step's delta only when damp > 0
         hipLaunchKernelGGL((cgls_update_p<T, V>), dim3(gN), blk, 0, g_stream, N, fl, (const double *)b.sc,
                            (const T *)s, p, damp > 0 ? b.part : nullptr);
-        if (damp > 0) cgls_fold_into(b, gN, kCglsPp);
-        if (tol > 0 && k % kCglsPoll == 0 && k < iters) {
-            int state = kCglsRun;
-            HIP_TRY(hipMemcpyAsync(&state, b.flags + kCglsState, sizeof(int), hipMemcpyDeviceToHost, g_stream));
-            HIP_TRY(hipStreamSynchronize(g_stream));
-            if (state == kCglsStop) {
-                *steps_run = k;
-                break;
-            }
+        if (damp > 0) fold(gN, kCglsPp);
+        bool stop = false;
+        if (solver_poll(k, iters, tol, b.flags + kCglsState, kCglsStop, &stop)) return -1;
+        if (stop) {
+            *steps_run = k;
+            break;
         }
     }
     HIP_TRY(hipGetLastError());
@@ -91,81 +86,44 @@ template <typename T>
 int cgls_body(spmv_csr_dev *m, spmv_csr_dev *mt, int iters, double tol, double damp, const void *b_host,
               void *x_host, double *ss_hist, double *rr_hist, int *info, float *ms_total) {
     const size_t vb = sizeof(T), M = (size_t)m->M_total, N = (size_t)m->N;
-    const size_t hist_len = (size_t)iters + 1;
+    const size_t hist_bytes = ((size_t)iters + 1) * sizeof(double);
+    SolverScope scope;
+    // p (m's x), r (mt's x): read in whole 128-byte lines by the x-window kernels; q, s, x: whole 16-byte pieces
+    const size_t p_bytes = (N * vb + 15) / 16 * 16 + kLineBytes, r_bytes = (M * vb + 15) / 16 * 16 + kLineBytes;
+    const size_t vecM = std::max<size_t>((M * vb + 15) / 16 * 16, 16), vecN = std::max<size_t>((N * vb + 15) / 16 * 16, 16);
     CglsBuffers b;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = 0, steps_run = 0;
-    do {
-        // p (m's x), r (mt's x): read in whole 128-byte lines by the x-window kernels; q, s, x: whole 16-byte pieces
-        const size_t p_bytes = (N * vb + 15) / 16 * 16 + kLineBytes, r_bytes = (M * vb + 15) / 16 * 16 + kLineBytes;
-        const size_t vecM = std::max<size_t>((M * vb + 15) / 16 * 16, 16), vecN = std::max<size_t>((N * vb + 15) / 16 * 16, 16);
-        hipError_t e = hipMalloc(&b.p, p_bytes);
-        if (e == hipSuccess) e = hipMalloc(&b.r, r_bytes);
-        if (e == hipSuccess) e = hipMalloc(&b.q, vecM);
-        if (e == hipSuccess) e = hipMalloc(&b.s, vecN);
-        if (e == hipSuccess) e = hipMalloc(&b.x, vecN);
-        if (e == hipSuccess) e = hipMalloc((void **)&b.sc, kCglsSlots * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void **)&b.part, (size_t)kCglsBlocks * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void **)&b.ss_hist, hist_len * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void **)&b.rr_hist, hist_len * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void **)&b.flags, kCglsFlagWords * sizeof(int));
-        if (e == hipSuccess) e = hipEventCreate(&e0);
-        if (e == hipSuccess) e = hipEventCreate(&e1);
-        if (e == hipSuccess) e = hipMemsetAsync(b.p, 0, p_bytes, g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(b.r, 0, r_bytes, g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(b.q, 0, vecM, g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(b.s, 0, vecN, g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(b.x, 0, vecN, g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(b.sc, 0, kCglsSlots * sizeof(double), g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(b.ss_hist, 0, hist_len * sizeof(double), g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(b.rr_hist, 0, hist_len * sizeof(double), g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(b.flags, 0, kCglsFlagWords * sizeof(int), g_stream);
-        if (e == hipSuccess && M) e = hipMemcpyAsync(b.r, b_host, M * vb, hipMemcpyHostToDevice, g_stream);
-        if (e == hipSuccess) e = hipEventRecord(e0, g_stream);
-        if (e != hipSuccess) { rc = fail("csr_cgls: setup failed: %s", hipGetErrorString(e)); break; }
-        rc = cgls_run<T>(m, mt, iters, tol, damp, b, &steps_run);
-        if (rc) {
-            (void)hipStreamSynchronize(g_stream);
-            break;
-        }
-        e = hipEventRecord(e1, g_stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-        float ms = 0;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        if (e == hipSuccess && x_host && N) e = hipMemcpy(x_host, b.x, N * vb, hipMemcpyDeviceToHost);
-        const size_t run_len = (size_t)steps_run + 1;
-        if (e == hipSuccess && ss_hist)
-            e = hipMemcpy(ss_hist, b.ss_hist, run_len * sizeof(double), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && rr_hist)
-            e = hipMemcpy(rr_hist, b.rr_hist, run_len * sizeof(double), hipMemcpyDeviceToHost);
-        int flags[kCglsFlagWords] = {0, 0, 0, 0};
-        if (e == hipSuccess) e = hipMemcpy(flags, b.flags, sizeof flags, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { rc = fail("csr_cgls: run failed: %s", hipGetErrorString(e)); break; }
-        // stopped early: the histories repeat their last values
-        for (size_t i = run_len; i < hist_len; ++i) {
-            if (ss_hist) ss_hist[i] = ss_hist[i - 1];
-            if (rr_hist) rr_hist[i] = rr_hist[i - 1];
-        }
-        if (info) {
-            info[0] = flags[kCglsSteps];
-            info[1] = flags[kCglsStatus];
-        }
-        if (ms_total) *ms_total = ms;
-    } while (0);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(b.p);
-    (void)hipFree(b.q);
-    (void)hipFree(b.r);
-    (void)hipFree(b.s);
-    (void)hipFree(b.x);
-    (void)hipFree(b.sc);
-    (void)hipFree(b.part);
-    (void)hipFree(b.ss_hist);
-    (void)hipFree(b.rr_hist);
-    (void)hipFree(b.flags);
-    (void)hipGetLastError();  // a failed allocation above is reported by rc, not by the next launch
-    return rc;
+    b.p = scope.alloc(p_bytes);
+    b.r = scope.alloc(r_bytes);
+    b.q = scope.alloc(vecM);
+    b.s = scope.alloc(vecN);
+    b.x = scope.alloc(vecN);
+    b.sc = scope.alloc<double>(kCglsSlots * sizeof(double));
+    b.part = scope.alloc<double>((size_t)kCglsBlocks * sizeof(double));
+    b.ss_hist = scope.alloc<double>(hist_bytes);
+    b.rr_hist = scope.alloc<double>(hist_bytes);
+    b.flags = scope.alloc<int>(kCglsFlagWords * sizeof(int));
+    hipError_t e = scope.err;
+    if (e == hipSuccess && M) e = hipMemcpyAsync(b.r, b_host, M * vb, hipMemcpyHostToDevice, g_stream);
+    if (e == hipSuccess) e = hipEventRecord(scope.e0, g_stream);
+    if (e != hipSuccess) return fail("csr_cgls: setup failed: %s", hipGetErrorString(e));
+    int steps_run = 0;
+    if (cgls_run<T>(m, mt, iters, tol, damp, b, &steps_run)) return -1;
+    e = hipEventRecord(scope.e1, g_stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
+    float ms = 0;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, scope.e0, scope.e1);
+    if (e == hipSuccess && x_host && N) e = hipMemcpy(x_host, b.x, N * vb, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = copy_history(ss_hist, b.ss_hist, steps_run, iters, 1);
+    if (e == hipSuccess) e = copy_history(rr_hist, b.rr_hist, steps_run, iters, 1);
+    int flags[kCglsFlagWords] = {0, 0, 0, 0};
+    if (e == hipSuccess) e = hipMemcpy(flags, b.flags, sizeof flags, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail("csr_cgls: run failed: %s", hipGetErrorString(e));
+    if (info) {
+        info[0] = flags[kCglsSteps];
+        info[1] = flags[kCglsStatus];
+    }
+    if (ms_total) *ms_total = ms;
+    return 0;
 }
 
 // a handle CGLS can launch by itself: the whole matrix, with its CSR arrays

@@ -3,7 +3,7 @@
 // its two implementations with the on-node autotune, and the timed step (kernel + exchange).
 #include "spmv_internal.hpp"
 
-#include "cg_multi_kernels.hpp"
+#include "solver_ops.hpp"
 
 // ------------------------------------------------------------- multi-GPU
 // Hack ranges for `parts` ranks by the reference's HLL partitioner (K8: greedy over hacks,
@@ -87,7 +87,6 @@ extern "C" int spmv_hip_comm_destroy(void) {
 
 namespace {
 
-constexpr int kMaxRanks = 64;
 struct gather_bounds {
     int b[kMaxRanks + 1];
 };
@@ -391,37 +390,20 @@ extern "C" int spmv_hip_hll_step_time(spmv_hll_dev *m, int variant, const int *b
 // captured into a hipGraph.
 namespace {
 
-constexpr int kNormBlocks = 512;
-
 template <typename T>
 __global__ __launch_bounds__(kBlock) void norm2_partial(const T *__restrict__ y, long long n, double *__restrict__ part) {
-    __shared__ double wave_sum[kBlock / 64];
-    double acc = 0;
-    for (long long k = (long long)blockIdx.x * kBlock + threadIdx.x; k < n; k += (long long)gridDim.x * kBlock) {
-        const double v = (double)y[k];
-        acc += v * v;
+    double acc[1] = {0.0};
+    for (PieceLane l(0, n, 1); l.q < l.end; l.q += l.stride) {
+        const double v = (double)y[l.q];
+        acc[0] += v * v;
     }
-    acc = group_sum<64>(acc);
-    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = wave_sum[0];
-        for (int w = 1; w < kBlock / 64; ++w) s += wave_sum[w];
-        part[blockIdx.x] = s;
-    }
+    block_partials<1>(acc, part);
 }
 
 // one workgroup: partial sums in fixed order -> norm[0] = ||y||_2, norm[1] = 1 / ||y||_2 (0 if y = 0)
 __global__ __launch_bounds__(kBlock) void norm2_finish(const double *__restrict__ part, int nparts, double *__restrict__ norm) {
-    __shared__ double wave_sum[kBlock / 64];
-    double acc = 0;
-    for (int k = threadIdx.x; k < nparts; k += kBlock) acc += part[k];
-    acc = group_sum<64>(acc);
-    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = acc;
-    __syncthreads();
+    const double s = fold_partials(part, nparts, 1, 0);
     if (threadIdx.x == 0) {
-        double s = wave_sum[0];
-        for (int w = 1; w < kBlock / 64; ++w) s += wave_sum[w];
         const double nrm = sqrt(s);
         norm[0] = nrm;
         norm[1] = nrm > 0 ? 1.0 / nrm : 0.0;
@@ -432,8 +414,7 @@ template <typename T>
 __global__ __launch_bounds__(kBlock) void scale_into(const T *__restrict__ y, long long n, const double *__restrict__ norm,
                                                      T *__restrict__ x) {
     const double inv = norm[1];
-    for (long long k = (long long)blockIdx.x * kBlock + threadIdx.x; k < n; k += (long long)gridDim.x * kBlock)
-        x[k] = (T)((double)y[k] * inv);
+    for (PieceLane l(0, n, 1); l.q < l.end; l.q += l.stride) x[l.q] = (T)((double)y[l.q] * inv);
 }
 
 template <typename T>
@@ -464,17 +445,15 @@ extern "C" int spmv_hip_csr_power_iterate(spmv_csr_dev *m, int variant, int iter
     if (!m || iters <= 0) return fail("power_iterate: bad arguments");
     if (m->M_total != m->N) return fail("power_iterate: needs a square matrix (%d x %d)", m->M_total, m->N);
     if (g_comm && !bounds) return fail("power_iterate: a communicator exists, the row bounds are required");
-    double *d_part = nullptr, *d_norm = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    SolverScope scope;
+    double *d_part = scope.alloc<double>(kNormBlocks * sizeof(double));
+    double *d_norm = scope.alloc<double>(2 * sizeof(double));
+    if (scope.err != hipSuccess) return fail("power_iterate: setup failed: %s", hipGetErrorString(scope.err));
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     int rc = 0;
     do {
-        hipError_t e = hipMalloc((void **)&d_part, kNormBlocks * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void **)&d_norm, 2 * sizeof(double));
-        if (e == hipSuccess) e = hipEventCreate(&e0);
-        if (e == hipSuccess) e = hipEventCreate(&e1);
-        if (e != hipSuccess) { rc = fail("power_iterate: setup failed: %s", hipGetErrorString(e)); break; }
+        hipError_t e = hipSuccess;
         auto loop = [&]() {
             return m->value_bytes == 8 ? power_iterations<double>(m, variant, iters, bounds, d_part, d_norm)
                                        : power_iterations<float>(m, variant, iters, bounds, d_part, d_norm);
@@ -488,17 +467,17 @@ extern "C" int spmv_hip_csr_power_iterate(spmv_csr_dev *m, int variant, int iter
             if (!rc && (e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0)) != hipSuccess)
                 rc = fail("power_iterate: hipGraphInstantiate failed: %s", hipGetErrorString(e));
             if (rc) break;
-            e = hipEventRecord(e0, g_stream);
+            e = hipEventRecord(scope.e0, g_stream);
             if (e == hipSuccess) e = hipGraphLaunch(exec, g_stream);
         } else {
-            e = hipEventRecord(e0, g_stream);
+            e = hipEventRecord(scope.e0, g_stream);
             if (e == hipSuccess) rc = loop();
             if (rc) break;
         }
-        if (e == hipSuccess) e = hipEventRecord(e1, g_stream);
+        if (e == hipSuccess) e = hipEventRecord(scope.e1, g_stream);
         if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
         float ms = 0;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, scope.e0, scope.e1);
         double nrm[2] = {0, 0};
         if (e == hipSuccess) e = hipMemcpy(nrm, d_norm, sizeof nrm, hipMemcpyDeviceToHost);
         if (e != hipSuccess) { rc = fail("power_iterate: run failed: %s", hipGetErrorString(e)); break; }
@@ -507,10 +486,6 @@ extern "C" int spmv_hip_csr_power_iterate(spmv_csr_dev *m, int variant, int iter
     } while (0);
     if (exec) (void)hipGraphExecDestroy(exec);
     if (graph) (void)hipGraphDestroy(graph);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(d_part);
-    (void)hipFree(d_norm);
     return rc;
 }
 
@@ -527,7 +502,6 @@ struct halo_segment {
     int peer, lo, hi;  // vector entries [lo, hi) to / from `peer`
 };
 std::vector<halo_segment> g_halo_send, g_halo_recv;
-bool g_halo_ready = false;
 
 
 // merge sorted, possibly touching ranges; then close the smallest gaps until at most max_ranges remain
@@ -548,6 +522,8 @@ void squeeze_ranges(std::vector<std::pair<int, int>> &r, int max_ranges) {
 }
 
 }  // namespace
+
+bool g_halo_ready = false;
 
 // The entries of x the handle's rows touch, as at most max_ranges ascending ranges [lo, hi) (128-byte line
 // granularity; small gaps are closed when there are more).  From the x-window plan's line lists; a handle
@@ -733,21 +709,6 @@ extern "C" int spmv_hip_comm_halo_exchange(void *d_vec, int value_bytes, void *s
 
 namespace {
 
-// own rows only: sum of squares -> part[], then one workgroup folds them into sum[0]
-__global__ __launch_bounds__(kBlock) void fold_partials(const double *__restrict__ part, int nparts, double *__restrict__ sum) {
-    __shared__ double wave_sum[kBlock / 64];
-    double acc = 0;
-    for (int k = threadIdx.x; k < nparts; k += kBlock) acc += part[k];
-    acc = group_sum<64>(acc);
-    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = wave_sum[0];
-        for (int w = 1; w < kBlock / 64; ++w) s += wave_sum[w];
-        sum[0] = s;
-    }
-}
-
 __global__ void norm_from_sum(const double *__restrict__ sum, double *__restrict__ norm) {
     const double nrm = sqrt(sum[0]);
     norm[0] = nrm;
@@ -785,7 +746,7 @@ int power_iterations_halo(spmv_csr_dev *m, int variant, int iters, double *d_par
             if (csr_launch_any(m, variant, m->x, m->y, g_stream)) return -1;
         }
         hipLaunchKernelGGL((norm2_partial<T>), dim3(grid), dim3(kBlock), 0, g_stream, (const T *)y_own, n, d_part);
-        hipLaunchKernelGGL(fold_partials, dim3(1), dim3(kBlock), 0, g_stream, d_part, grid, d_sum);
+        hipLaunchKernelGGL(solver_fold, dim3(1), dim3(kBlock), 0, g_stream, d_part, grid, 1, d_sum);  // own rows only
         if (g_comm) {
             const ncclResult_t nr = ncclAllReduce(d_sum, d_sum, 1, ncclDouble, ncclSum, g_comm, g_stream);
             if (nr != ncclSuccess) return fail("power_iterate_halo: ncclAllReduce failed: %s", ncclGetErrorString(nr));
@@ -819,426 +780,36 @@ extern "C" int spmv_hip_csr_power_iterate_halo(spmv_csr_dev *m, int variant, int
     if (!m || iters <= 0) return fail("power_iterate_halo: bad arguments");
     if (m->M_total != m->N) return fail("power_iterate_halo: needs a square matrix (%d x %d)", m->M_total, m->N);
     if (g_comm && !g_halo_ready) return fail("power_iterate_halo: call spmv_hip_comm_halo_setup first");
-    double *d_part = nullptr, *d_sum = nullptr, *d_norm = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr, scaled = nullptr, arrived = nullptr;
+    SolverScope scope;
+    double *d_part = scope.alloc<double>(kNormBlocks * sizeof(double));
+    double *d_sum = scope.alloc<double>(sizeof(double));
+    double *d_norm = scope.alloc<double>(2 * sizeof(double));
+    hipEvent_t scaled = nullptr, arrived = nullptr;
     int rc = 0;
     do {
-        hipError_t e = hipMalloc((void **)&d_part, kNormBlocks * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void **)&d_sum, sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void **)&d_norm, 2 * sizeof(double));
-        if (e == hipSuccess) e = hipEventCreate(&e0);
-        if (e == hipSuccess) e = hipEventCreate(&e1);
+        hipError_t e = scope.err;
         if (e == hipSuccess) e = hipEventCreateWithFlags(&scaled, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&arrived, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventRecord(e0, g_stream);
+        if (e == hipSuccess) e = hipEventRecord(scope.e0, g_stream);
         if (e != hipSuccess) { rc = fail("power_iterate_halo: setup failed: %s", hipGetErrorString(e)); break; }
         rc = m->value_bytes == 8 ? power_iterations_halo<double>(m, variant, iters, d_part, d_sum, d_norm, scaled, arrived)
                                  : power_iterations_halo<float>(m, variant, iters, d_part, d_sum, d_norm, scaled, arrived);
         if (rc) {
             (void)hipStreamSynchronize(g_stream2);  // nothing of the loop may outlive its events
-            (void)hipStreamSynchronize(g_stream);
             break;
         }
-        e = hipEventRecord(e1, g_stream);
+        e = hipEventRecord(scope.e1, g_stream);
         if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
         float ms = 0;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, scope.e0, scope.e1);
         double nrm[2] = {0, 0};
         if (e == hipSuccess) e = hipMemcpy(nrm, d_norm, sizeof nrm, hipMemcpyDeviceToHost);
         if (e != hipSuccess) { rc = fail("power_iterate_halo: run failed: %s", hipGetErrorString(e)); break; }
         if (lambda) *lambda = nrm[0];
         if (ms_total) *ms_total = ms;
     } while (0);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
+    (void)hipStreamSynchronize(g_stream);
     if (scaled) (void)hipEventDestroy(scaled);
     if (arrived) (void)hipEventDestroy(arrived);
-    (void)hipFree(d_part);
-    (void)hipFree(d_sum);
-    (void)hipFree(d_norm);
     return rc;
-}
-
-// ------------------------------------------------------------- conjugate gradients
-// SURVEY.md 8(f) N4, the second iterated skeleton (the reference multiplies by a fixed x; a Krylov method is what
-// an SpMV engine is for).  Plain CG for a symmetric positive definite A, x0 = 0:
-//     r = b, p = b, rs = r.r;   repeat:  q = A p;  alpha = rs / p.q;  x += alpha p;  r -= alpha q;
-//                                        rs' = r.r;  beta = rs' / rs;  p = r + beta p;  rs = rs'
-// p is the handle's x (the SpMV input, full length on every rank), q its y (this rank's rows).  Every rank keeps
-// its own rows of x, r; the SpMV's exchange is the same as in the power iteration -- all-gatherv of p, or the
-// halo exchange when spmv_hip_comm_halo_setup has run and use_halo is set.  Dot products are fixed-order device
-// reductions (grid-stride partial sums per workgroup, folded by one workgroup); across ranks the partial sums are
-// ALL-GATHERED and added in rank order by every rank, so all ranks hold the same bits whatever reduction tree the
-// collective library would pick for an all-reduce.  Scalars stay on the device: no host synchronisation in the loop.
-namespace {
-
-constexpr int kCgRs = 0, kCgPq = 1, kCgRsNew = 2, kCgAlpha = 3, kCgBeta = 4, kCgLocal = 5, kCgScalars = 8;
-
-template <typename T>
-__global__ __launch_bounds__(kBlock) void dot_partial(const T *__restrict__ a, const T *__restrict__ b, long long n,
-                                                      double *__restrict__ part) {
-    __shared__ double wave_sum[kBlock / 64];
-    double acc = 0;
-    for (long long k = (long long)blockIdx.x * kBlock + threadIdx.x; k < n; k += (long long)gridDim.x * kBlock)
-        acc += (double)a[k] * (double)b[k];
-    acc = group_sum<64>(acc);
-    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = wave_sum[0];
-        for (int w = 1; w < kBlock / 64; ++w) s += wave_sum[w];
-        part[blockIdx.x] = s;
-    }
-}
-
-// x += alpha p, r -= alpha q on this rank's rows, and the workgroup's partial of the new r.r
-template <typename T>
-__global__ __launch_bounds__(kBlock) void cg_update_x_r(long long n, const double *__restrict__ s, const T *__restrict__ p,
-                                                        const T *__restrict__ q, T *__restrict__ x, T *__restrict__ r,
-                                                        double *__restrict__ part) {
-    __shared__ double wave_sum[kBlock / 64];
-    const double alpha = s[kCgAlpha];
-    double acc = 0;
-    for (long long k = (long long)blockIdx.x * kBlock + threadIdx.x; k < n; k += (long long)gridDim.x * kBlock) {
-        x[k] = (T)((double)x[k] + alpha * (double)p[k]);
-        const T rk = (T)((double)r[k] - alpha * (double)q[k]);
-        r[k] = rk;
-        acc += (double)rk * (double)rk;
-    }
-    acc = group_sum<64>(acc);
-    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = wave_sum[0];
-        for (int w = 1; w < kBlock / 64; ++w) t += wave_sum[w];
-        part[blockIdx.x] = t;
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(kBlock) void cg_update_p(long long n, const double *__restrict__ s, const T *__restrict__ r,
-                                                      T *__restrict__ p) {
-    const double beta = s[kCgBeta];
-    for (long long k = (long long)blockIdx.x * kBlock + threadIdx.x; k < n; k += (long long)gridDim.x * kBlock)
-        p[k] = (T)((double)r[k] + beta * (double)p[k]);
-}
-
-// the ranks' partial sums in rank order -> s[slot]
-__global__ void cg_rank_sum(const double *__restrict__ gathered, int ranks, double *__restrict__ s, int slot) {
-    double t = 0;
-    for (int k = 0; k < ranks; ++k) t += gathered[k];
-    s[slot] = t;
-}
-__global__ void cg_set_alpha(double *__restrict__ s) { s[kCgAlpha] = s[kCgPq] != 0.0 ? s[kCgRs] / s[kCgPq] : 0.0; }
-__global__ void cg_set_beta(double *__restrict__ s, double *__restrict__ hist, int k) {
-    s[kCgBeta] = s[kCgRs] != 0.0 ? s[kCgRsNew] / s[kCgRs] : 0.0;
-    s[kCgRs] = s[kCgRsNew];
-    if (hist) hist[k] = s[kCgRsNew];
-}
-__global__ void cg_record(const double *__restrict__ s, double *__restrict__ hist) { hist[0] = s[kCgRs]; }
-
-// part[0 .. grid) of this rank -> the global sum in s[slot] on every rank
-int cg_reduce(double *d_part, int grid, double *d_s, double *d_gath, int slot) {
-    if (!g_comm) {
-        hipLaunchKernelGGL(fold_partials, dim3(1), dim3(kBlock), 0, g_stream, d_part, grid, d_s + slot);
-        return 0;
-    }
-    hipLaunchKernelGGL(fold_partials, dim3(1), dim3(kBlock), 0, g_stream, d_part, grid, d_s + kCgLocal);
-    const ncclResult_t n = ncclAllGather(d_s + kCgLocal, d_gath, 1, ncclDouble, g_comm, g_stream);
-    if (n != ncclSuccess) return fail("csr_cg: ncclAllGather failed: %s", ncclGetErrorString(n));
-    hipLaunchKernelGGL(cg_rank_sum, dim3(1), dim3(1), 0, g_stream, d_gath, g_comm_size, d_s, slot);
-    return 0;
-}
-
-int cg_exchange_p(spmv_csr_dev *m, const int *bounds, int use_halo) {
-    if (!g_comm) return 0;
-    if (use_halo) return spmv_hip_comm_halo_exchange(m->x, m->value_bytes, g_stream);
-    return spmv_hip_comm_allgatherv(m->x, bounds, m->value_bytes, g_stream);
-}
-
-template <typename T>
-int cg_run(spmv_csr_dev *m, int variant, int iters, const int *bounds, int use_halo, T *d_xs, T *d_r, double *d_s,
-           double *d_part, double *d_gath, double *d_hist) {
-    const long long n = m->M_local;
-    const int grid = (int)std::max<long long>(1, std::min<long long>(kNormBlocks, (n + kBlock - 1) / kBlock));
-    T *p_own = (T *)m->x + m->row0, *q_own = (T *)m->y + m->row0, *x_own = d_xs + m->row0;
-    // rs = r.r with r = b (already in d_r and in p's own range); every rank gets the whole p
-    hipLaunchKernelGGL((dot_partial<T>), dim3(grid), dim3(kBlock), 0, g_stream, (const T *)d_r, (const T *)d_r, n, d_part);
-    if (cg_reduce(d_part, grid, d_s, d_gath, kCgRs)) return -1;
-    hipLaunchKernelGGL(cg_record, dim3(1), dim3(1), 0, g_stream, d_s, d_hist);
-    if (cg_exchange_p(m, bounds, use_halo)) return -1;
-    for (int k = 0; k < iters; ++k) {
-        if (csr_launch_any(m, variant, m->x, m->y, g_stream)) return -1;  // q = A p on this rank's rows
-        hipLaunchKernelGGL((dot_partial<T>), dim3(grid), dim3(kBlock), 0, g_stream, (const T *)p_own, (const T *)q_own, n, d_part);
-        if (cg_reduce(d_part, grid, d_s, d_gath, kCgPq)) return -1;
-        hipLaunchKernelGGL(cg_set_alpha, dim3(1), dim3(1), 0, g_stream, d_s);
-        hipLaunchKernelGGL((cg_update_x_r<T>), dim3(grid), dim3(kBlock), 0, g_stream, n, d_s, (const T *)p_own,
-                           (const T *)q_own, x_own, d_r, d_part);
-        if (cg_reduce(d_part, grid, d_s, d_gath, kCgRsNew)) return -1;
-        hipLaunchKernelGGL(cg_set_beta, dim3(1), dim3(1), 0, g_stream, d_s, d_hist, k + 1);
-        hipLaunchKernelGGL((cg_update_p<T>), dim3(grid), dim3(kBlock), 0, g_stream, n, d_s, (const T *)d_r, p_own);
-        if (cg_exchange_p(m, bounds, use_halo)) return -1;
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-template <typename T>
-int cg_body(spmv_csr_dev *m, int variant, int iters, const int *bounds, int use_halo, const void *b_host, void *x_host,
-            double *rr_hist, float *ms_total) {
-    const size_t n_all = (size_t)m->M_total, n_own = (size_t)m->M_local;
-    T *d_xs = nullptr, *d_r = nullptr;
-    double *d_s = nullptr, *d_part = nullptr, *d_gath = nullptr, *d_hist = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = 0;
-    do {
-        hipError_t e = hipMalloc((void **)&d_xs, std::max<size_t>(n_all, 1) * sizeof(T));
-        if (e == hipSuccess) e = hipMalloc((void **)&d_r, std::max<size_t>(n_own, 1) * sizeof(T));
-        if (e == hipSuccess) e = hipMalloc((void **)&d_s, kCgScalars * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void **)&d_part, kNormBlocks * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void **)&d_gath, kMaxRanks * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void **)&d_hist, ((size_t)iters + 1) * sizeof(double));
-        if (e == hipSuccess) e = hipEventCreate(&e0);
-        if (e == hipSuccess) e = hipEventCreate(&e1);
-        if (e == hipSuccess) e = hipMemsetAsync(d_xs, 0, std::max<size_t>(n_all, 1) * sizeof(T), g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_s, 0, kCgScalars * sizeof(double), g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_hist, 0, ((size_t)iters + 1) * sizeof(double), g_stream);
-        // r = b on this rank's rows; p = b: the own range of the handle's x (the rest arrives by the exchange)
-        if (e == hipSuccess && n_own)
-            e = hipMemcpyAsync(d_r, (const T *)b_host + m->row0, n_own * sizeof(T), hipMemcpyHostToDevice, g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(m->x, 0, (size_t)m->N * sizeof(T), g_stream);
-        if (e == hipSuccess && n_own)
-            e = hipMemcpyAsync((T *)m->x + m->row0, d_r, n_own * sizeof(T), hipMemcpyDeviceToDevice, g_stream);
-        if (e == hipSuccess) e = hipEventRecord(e0, g_stream);
-        if (e != hipSuccess) { rc = fail("csr_cg: setup failed: %s", hipGetErrorString(e)); break; }
-        rc = cg_run<T>(m, variant, iters, bounds, use_halo, d_xs, d_r, d_s, d_part, d_gath, d_hist);
-        if (rc) {
-            (void)hipStreamSynchronize(g_stream);
-            break;
-        }
-        e = hipEventRecord(e1, g_stream);
-        // the solution: every rank holds its rows; with a communicator all rows everywhere
-        if (e == hipSuccess && g_comm && x_host) {
-            if (spmv_hip_comm_allgatherv(d_xs, bounds, m->value_bytes, g_stream)) { rc = -1; break; }
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-        float ms = 0;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        if (e == hipSuccess && x_host) e = hipMemcpy(x_host, d_xs, n_all * sizeof(T), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && rr_hist) e = hipMemcpy(rr_hist, d_hist, ((size_t)iters + 1) * sizeof(double), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { rc = fail("csr_cg: run failed: %s", hipGetErrorString(e)); break; }
-        if (ms_total) *ms_total = ms;
-    } while (0);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(d_xs);
-    (void)hipFree(d_r);
-    (void)hipFree(d_s);
-    (void)hipFree(d_part);
-    (void)hipFree(d_gath);
-    (void)hipFree(d_hist);
-    return rc;
-}
-
-}  // namespace
-
-extern "C" int spmv_hip_csr_cg(spmv_csr_dev *m, int variant, int iters, const int *bounds, int use_halo,
-                               const void *b_host, void *x_host, double *rr_hist, float *ms_total) {
-    if (need_device()) return -1;
-    if (!m || iters < 0 || !b_host) return fail("csr_cg: bad arguments");
-    if (m->M_total != m->N) return fail("csr_cg: needs a square matrix (%d x %d)", m->M_total, m->N);
-    if (g_comm && !bounds) return fail("csr_cg: a communicator exists, the row bounds are required");
-    if (g_comm && use_halo && !g_halo_ready) return fail("csr_cg: call spmv_hip_comm_halo_setup first");
-    if (g_comm_size > kMaxRanks) return fail("csr_cg: more than %d ranks", kMaxRanks);
-    return guarded("csr_cg", [&] {
-        return m->value_bytes == 8 ? cg_body<double>(m, variant, iters, bounds, use_halo, b_host, x_host, rr_hist, ms_total)
-                                   : cg_body<float>(m, variant, iters, bounds, use_halo, b_host, x_host, rr_hist, ms_total);
-    });
-}
-
-// ------------------------------------------------------------- k right-hand sides
-// spmv_hip_csr_cg_multi: k independent CG recurrences (one alpha, beta per column; not block CG) that share one SpMM
-// per step, so the matrix streams from HBM once per step for all k.  The loop of csr_cg, k wide: P (N x k, the SpMM
-// input), Q = A P (M_total x k), X and R (this rank's rows) are row-major; the vector kernels and the scalar kernels
-// are in cg_multi_kernels.hpp.  With a communicator P is all-gathered with the row bounds scaled by k (a row of P is
-// k contiguous values) and the k dot products travel as in cg_reduce: all-gathered, added in rank order.
-namespace {
-
-// part[0 .. grid) x k of this rank -> the k global sums in slot `slot` of d_s on every rank
-int mcg_reduce(const double *d_part, int grid, int k, double *d_s, double *d_gath, int slot) {
-    double *out = d_s + (size_t)slot * kMcgMaxK;
-    if (!g_comm) {
-        hipLaunchKernelGGL(mcg_fold, dim3(k), dim3(kBlock), 0, g_stream, d_part, grid, k, out);
-        return 0;
-    }
-    double *local = d_s + (size_t)kMcgLocal * kMcgMaxK;
-    hipLaunchKernelGGL(mcg_fold, dim3(k), dim3(kBlock), 0, g_stream, d_part, grid, k, local);
-    const ncclResult_t n = ncclAllGather(local, d_gath, (size_t)k, ncclDouble, g_comm, g_stream);
-    if (n != ncclSuccess) return fail("csr_cg_multi: ncclAllGather failed: %s", ncclGetErrorString(n));
-    hipLaunchKernelGGL(mcg_rank_sum, dim3(1), dim3(64), 0, g_stream, d_gath, g_comm_size, k, out);
-    return 0;
-}
-
-struct McgBuffers {
-    void *P = nullptr, *Q = nullptr, *X = nullptr, *R = nullptr;
-    double *s = nullptr, *part = nullptr, *gath = nullptr, *hist = nullptr;
-    int *flags = nullptr;
-};
-
-// the loop; V = values of T per lane (16-byte pieces or single elements).  *steps = the steps run (< iters when tol > 0
-// and every column froze).
-template <typename T, int V>
-int mcg_run(spmv_csr_dev *m, int k, int iters, double tol, const int *kbounds, const McgBuffers &b, int *steps) {
-    const long long n = m->M_local, kk = k;
-    int cl = 0;
-    while ((1 << cl) * V < k) ++cl;  // column lanes: the next power of two >= k / V
-    const long long rows_per_block = kBlock >> cl;
-    const int cap = k == 1 ? kNormBlocks : kMcgBlocks;  // k = 1: csr_cg's workgroups, csr_cg's bits
-    const int grid = (int)std::max<long long>(1, std::min<long long>(cap, (n + rows_per_block - 1) / rows_per_block));
-    const double tol2 = tol * tol;
-    T *P = (T *)b.P, *p_own = P + m->row0 * kk, *q_own = (T *)b.Q + m->row0 * kk, *x_own = (T *)b.X + m->row0 * kk;
-    T *R = (T *)b.R;
-    const dim3 g(grid), blk(kBlock);
-    hipLaunchKernelGGL((mcg_dot_partial<T, V>), g, blk, 0, g_stream, (const T *)R, (const T *)R, n, k, cl, b.part);
-    if (mcg_reduce(b.part, grid, k, b.s, b.gath, kMcgRs)) return -1;
-    hipLaunchKernelGGL(mcg_start, dim3(1), dim3(64), 0, g_stream, b.s, b.flags, b.hist, k, iters, tol2);
-    if (g_comm && spmv_hip_comm_allgatherv(P, kbounds, m->value_bytes, g_stream)) return -1;
-    *steps = iters;
-    for (int t = 1; t <= iters; ++t) {
-        if (spmv_hip_csr_spmm_on(m, k, P, b.Q, g_stream)) return -1;  // Q = A P on this rank's rows
-        hipLaunchKernelGGL((mcg_dot_partial<T, V>), g, blk, 0, g_stream, (const T *)p_own, (const T *)q_own, n, k, cl,
-                           b.part);
-        if (mcg_reduce(b.part, grid, k, b.s, b.gath, kMcgPq)) return -1;
-        hipLaunchKernelGGL(mcg_set_alpha, dim3(1), dim3(64), 0, g_stream, b.s, k);
-        hipLaunchKernelGGL((mcg_update_x_r<T, V>), g, blk, 0, g_stream, n, k, cl, (const double *)b.s,
-                           (const int *)b.flags, (const T *)p_own, (const T *)q_own, x_own, R, b.part);
-        if (mcg_reduce(b.part, grid, k, b.s, b.gath, kMcgRsNew)) return -1;
-        hipLaunchKernelGGL(mcg_set_beta, dim3(1), dim3(64), 0, g_stream, b.s, b.flags, b.hist + (size_t)t * kk, k, t,
-                           tol2);
-        hipLaunchKernelGGL((mcg_update_p<T, V>), g, blk, 0, g_stream, n, k, cl, (const double *)b.s,
-                           (const int *)b.flags, (const T *)R, p_own);
-        if (g_comm && spmv_hip_comm_allgatherv(P, kbounds, m->value_bytes, g_stream)) return -1;
-        if (tol > 0 && t % 16 == 0 && t < iters) {
-            // every rank holds the same bits, so every rank stops at the same step
-            int active = 0;
-            HIP_TRY(hipMemcpyAsync(&active, b.flags + kMcgActive, sizeof(int), hipMemcpyDeviceToHost, g_stream));
-            HIP_TRY(hipStreamSynchronize(g_stream));
-            if (active == 0) {
-                *steps = t;
-                break;
-            }
-        }
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-template <typename T>
-int mcg_body(spmv_csr_dev *m, int k, int iters, double tol, const int *bounds, const void *B_host, void *X_host,
-             double *rr_hist, int *iters_done, float *ms_total) {
-    const size_t kk = (size_t)k, vb = sizeof(T);
-    const size_t n_all = (size_t)m->M_total, n_own = (size_t)m->M_local, ncols = (size_t)m->N;
-    const size_t hist_len = ((size_t)iters + 1) * kk;
-    std::vector<int> kbounds;
-    if (g_comm) {
-        kbounds.resize((size_t)g_comm_size + 1);
-        for (int r = 0; r <= g_comm_size; ++r) kbounds[r] = bounds[r] * k;
-    }
-    McgBuffers b;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = 0, steps = 0;
-    do {
-        // P: read in whole 128-byte lines by the x-window SpMV kernels (k = 1), as the handle's x
-        const size_t p_bytes = std::max<size_t>(ncols * kk * vb, 16) + kLineBytes;
-        const size_t q_bytes = std::max<size_t>(n_all * kk * vb, 16);
-        hipError_t e = hipMalloc(&b.P, p_bytes);
-        if (e == hipSuccess) e = hipMalloc(&b.Q, q_bytes);
-        if (e == hipSuccess) e = hipMalloc(&b.X, q_bytes);
-        if (e == hipSuccess) e = hipMalloc(&b.R, std::max<size_t>(n_own * kk * vb, 16));
-        if (e == hipSuccess) e = hipMalloc((void **)&b.s, kMcgSlots * kMcgMaxK * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void **)&b.part, (size_t)kMcgBlocks * kMcgMaxK * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void **)&b.gath, (size_t)kMaxRanks * kMcgMaxK * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void **)&b.hist, hist_len * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void **)&b.flags, kMcgFlagWords * sizeof(int));
-        if (e == hipSuccess) e = hipEventCreate(&e0);
-        if (e == hipSuccess) e = hipEventCreate(&e1);
-        if (e == hipSuccess) e = hipMemsetAsync(b.P, 0, p_bytes, g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(b.Q, 0, q_bytes, g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(b.X, 0, q_bytes, g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(b.s, 0, kMcgSlots * kMcgMaxK * sizeof(double), g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(b.hist, 0, hist_len * sizeof(double), g_stream);
-        // r = b on this rank's rows; p = b: its own range of P (the rest arrives by the all-gatherv)
-        const size_t own_off = (size_t)m->row0 * kk * vb, own_bytes = n_own * kk * vb;
-        if (e == hipSuccess && n_own)
-            e = hipMemcpyAsync(b.R, (const char *)B_host + own_off, own_bytes, hipMemcpyHostToDevice, g_stream);
-        if (e == hipSuccess && n_own)
-            e = hipMemcpyAsync((char *)b.P + own_off, b.R, own_bytes, hipMemcpyDeviceToDevice, g_stream);
-        if (e == hipSuccess) e = hipEventRecord(e0, g_stream);
-        if (e != hipSuccess) { rc = fail("csr_cg_multi: setup failed: %s", hipGetErrorString(e)); break; }
-        const bool wide = kk * vb % 16 == 0;
-        rc = wide ? mcg_run<T, 16 / sizeof(T)>(m, k, iters, tol, kbounds.data(), b, &steps)
-                  : mcg_run<T, 1>(m, k, iters, tol, kbounds.data(), b, &steps);
-        if (rc) {
-            (void)hipStreamSynchronize(g_stream);
-            break;
-        }
-        e = hipEventRecord(e1, g_stream);
-        // the solution: every rank holds its rows; with a communicator all rows everywhere
-        if (e == hipSuccess && g_comm && X_host) {
-            if (spmv_hip_comm_allgatherv(b.X, kbounds.data(), m->value_bytes, g_stream)) {
-                (void)hipStreamSynchronize(g_stream);
-                rc = -1;
-                break;
-            }
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-        float ms = 0;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        if (e == hipSuccess && X_host) e = hipMemcpy(X_host, b.X, n_all * kk * vb, hipMemcpyDeviceToHost);
-        const size_t run_len = ((size_t)steps + 1) * kk;
-        if (e == hipSuccess && rr_hist) e = hipMemcpy(rr_hist, b.hist, run_len * sizeof(double), hipMemcpyDeviceToHost);
-        int flags[kMcgFlagWords];
-        if (e == hipSuccess && iters_done) e = hipMemcpy(flags, b.flags, sizeof flags, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { rc = fail("csr_cg_multi: run failed: %s", hipGetErrorString(e)); break; }
-        // stopped early: every column is frozen, its history repeats its last value
-        if (rr_hist)
-            for (size_t i = run_len; i < hist_len; ++i) rr_hist[i] = rr_hist[i - kk];
-        if (iters_done) std::memcpy(iters_done, flags + kMcgDone, kk * sizeof(int));
-        if (ms_total) *ms_total = ms;
-    } while (0);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(b.P);
-    (void)hipFree(b.Q);
-    (void)hipFree(b.X);
-    (void)hipFree(b.R);
-    (void)hipFree(b.s);
-    (void)hipFree(b.part);
-    (void)hipFree(b.gath);
-    (void)hipFree(b.hist);
-    (void)hipFree(b.flags);
-    (void)hipGetLastError();  // a failed allocation above is reported by rc, not by the next launch
-    return rc;
-}
-
-}  // namespace
-
-extern "C" int spmv_hip_csr_cg_multi(spmv_csr_dev *m, int k, int iters, double tol, const int *bounds,
-                                     const void *B_host, void *X_host, double *rr_hist, int *iters_done,
-                                     float *ms_total) {
-    if (need_device()) return -1;
-    int rc = 0;
-    if (!m || iters < 0 || !B_host || !(tol >= 0)) rc = fail("csr_cg_multi: bad arguments");
-    else if (k < 1 || k > kMcgMaxK) rc = fail("csr_cg_multi: k = %d, must be in [1, %d]", k, kMcgMaxK);
-    else if (m->M_total != m->N) rc = fail("csr_cg_multi: needs a square matrix (%d x %d)", m->M_total, m->N);
-    else if (m->tiles_only) rc = fail("csr_cg_multi: a tiles-only handle has no SpMM kernels");
-    else if ((long long)m->M_total * k > 0x7fffffffLL)
-        rc = fail("csr_cg_multi: n * k = %lld values is beyond int range", (long long)m->M_total * k);
-    else if (g_comm && !bounds) rc = fail("csr_cg_multi: a communicator exists, the row bounds are required");
-    else if (g_comm_size > kMaxRanks) rc = fail("csr_cg_multi: more than %d ranks", kMaxRanks);
-    if (rc) return rc;
-    return guarded("csr_cg_multi", [&] {
-        return m->value_bytes == 8 ? mcg_body<double>(m, k, iters, tol, bounds, B_host, X_host, rr_hist, iters_done, ms_total)
-                                   : mcg_body<float>(m, k, iters, tol, bounds, B_host, X_host, rr_hist, iters_done, ms_total);
-    });
 }

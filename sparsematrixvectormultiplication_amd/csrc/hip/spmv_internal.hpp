@@ -31,6 +31,7 @@ extern hipStream_t g_stream;
 extern hipStream_t g_stream2;  // second stream: the halo exchange that runs beside the interior blocks
 extern ncclComm_t g_comm;
 extern int g_comm_rank, g_comm_size;
+constexpr int kMaxRanks = 64;  // widest communicator: the all-gatherv's bounds, the solvers' gathered sums
 
 // kernel tuning knobs (spmv_hip_set_tuning); defaults are the measured best
 extern int g_stream_cap;      // nnz staged per stream workgroup (fixed at upload); 0 = by matrix size
@@ -39,6 +40,7 @@ extern int g_stream_nt;       // non-temporal loads for col/val in the gather st
 extern int g_local_nt;        // same for the x-window kernels: -1 = auto (off while the matrix fits the Infinity Cache)
 extern int g_stream_xcd;      // blocks per XCD run (xcd_chunked); 0 = default, -1 = one contiguous eighth per XCD
 extern int g_halo_split;      // halo setup splits the handle by columns (1) or by blocks only (0)
+extern bool g_halo_ready;     // spmv_hip_comm_halo_setup has made this rank's send / receive segments
 extern int g_halo_overlap;    // power iteration with halo: exchange beside the interior blocks (1) or strictly in order (0)
 extern int g_gather_mode;     // all-gatherv: 0 = one ncclBroadcast per owner in a group, 1 = padded ncclAllGather + scatter
 extern int g_local_cap;       // stage of the x-window plan: 0 = auto, 1024 or 2048

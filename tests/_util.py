@@ -1,7 +1,12 @@
 """Shared helpers for the parity tests."""
+import collections
 import hashlib
 import json
 import os
+import re
+import shutil
+import subprocess
+import tempfile
 
 import numpy as np
 
@@ -330,3 +335,32 @@ def write_parser_case(path, field, symmetry, ragged):
 
 def parser_case_key(field, symmetry, ragged):
     return f"{field}-{symmetry}{'-ragged' if ragged else ''}"
+
+
+# ---- what the compiler made of a translation unit: every kernel's static LDS, scratch and VGPRs from the code
+# object's metadata (the gfx950 assembly that -save-temps keeps)
+HIPCC = "/opt/rocm/bin/hipcc"
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIP_SRC = os.path.join(_ROOT, "sparsematrixvectormultiplication_amd", "csrc", "hip")
+Kernel = collections.namedtuple("Kernel", "lds scratch vgprs")
+
+
+def compile_kernels(source, timeout=600):
+    """{mangled kernel name: Kernel(lds, scratch, vgprs)} of csrc/hip/<source> compiled for gfx950."""
+    tmp = tempfile.mkdtemp(prefix="spmv_isa_")
+    try:
+        proc = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950",
+                               "-I" + os.path.join(_ROOT, "include"),
+                               "-I" + HIP_SRC, "-c", os.path.join(HIP_SRC, source), "-o", os.path.join(tmp, "o.o"),
+                               "-save-temps=obj"], capture_output=True, text=True, timeout=timeout, cwd=tmp)
+        assert proc.returncode == 0, proc.stderr[-2000:]
+        asm = [f for f in os.listdir(tmp) if f.endswith("gfx950.s")]
+        assert asm, os.listdir(tmp)
+        text = open(os.path.join(tmp, asm[0])).read()
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    kernels = {}
+    for m in re.finditer(r"\.group_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.name:\s+(\S+)\n(?:.*\n)*?"
+                         r"\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)", text):
+        kernels[m.group(2)] = Kernel(int(m.group(1)), int(m.group(3)), int(m.group(4)))
+    return kernels

@@ -3,18 +3,15 @@ any device call, the entry point refuses a NULL handle, and the new kernels comp
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import sparsematrixvectormultiplication_amd as sp
+from _util import HIPCC, compile_kernels
 from conftest import ROOT
 
-HIPCC = "/opt/rocm/bin/hipcc"
-SRC = os.path.join(ROOT, "sparsematrixvectormultiplication_amd", "csrc", "hip")
 VGPR_BOUND = 64  # the vector kernels stream; the cg_multi kernels sit under this too
 
 
@@ -77,26 +74,14 @@ def test_bicgstab_refuses_a_null_handle():
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_bicgstab_kernels_compile_for_gfx950_without_scratch():
-    tmp = tempfile.mkdtemp(prefix="spmv_bcg_")
-    try:
-        proc = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
-                               "-I" + SRC, "-c", os.path.join(SRC, "spmv_bicgstab.hip"), "-o", os.path.join(tmp, "o.o"),
-                               "-save-temps=obj"], capture_output=True, text=True, timeout=600, cwd=tmp)
-        assert proc.returncode == 0, proc.stderr[-2000:]
-        asm = [f for f in os.listdir(tmp) if f.endswith("gfx950.s")]
-        assert asm, os.listdir(tmp)
-        text = open(os.path.join(tmp, asm[0])).read()
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
-    kernels = {}
-    for m in re.finditer(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)", text):
-        kernels[m.group(1)] = (int(m.group(2)), int(m.group(3)))
-    bcg = {k: v for k, v in kernels.items() if "bcg_" in k}
+def test_bicgstab_and_shared_solver_kernels_compile_for_gfx950_without_scratch():
+    kernels = {k: (v.scratch, v.vgprs) for k, v in compile_kernels("spmv_bicgstab.hip").items()}
+    # with the shared fold and rank-sum kernels of solver_ops.hpp
+    bcg = {k: v for k, v in kernels.items() if "bcg_" in k or "solver_" in k}
     # the five vector kernels x {fp64 in 16-byte pieces of 2, fp32 in pieces of 4}
     vector = [k for k in bcg if re.search(r"bcg_(dot|dot2|update_s|update_x_r|update_p)I(dLi2|fLi4)E", k)]
     assert len(vector) == 10, sorted(bcg)
-    for name in ("bcg_fold", "bcg_rank_sum", "bcg_start", "bcg_set_alpha", "bcg_check_s", "bcg_set_omega",
+    for name in ("solver_fold", "solver_rank_sum", "bcg_start", "bcg_set_alpha", "bcg_check_s", "bcg_set_omega",
                  "bcg_set_beta"):
         assert any(name in k for k in bcg), (name, sorted(bcg))
     for name, (scratch, vgprs) in bcg.items():

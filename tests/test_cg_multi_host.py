@@ -4,18 +4,13 @@ kernels compile for gfx950 without scratch."""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import sparsematrixvectormultiplication_amd as sp
-from conftest import ROOT
-
-HIPCC = "/opt/rocm/bin/hipcc"
-SRC = os.path.join(ROOT, "sparsematrixvectormultiplication_amd", "csrc", "hip")
+from _util import HIPCC, compile_kernels
 
 
 def test_cg_multi_symbol_is_exported_and_bound():
@@ -67,27 +62,14 @@ def test_cg_multi_refuses_a_null_handle():
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_cg_multi_kernels_compile_for_gfx950_without_scratch():
-    tmp = tempfile.mkdtemp(prefix="spmv_mcg_")
-    try:
-        proc = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
-                               "-I" + SRC, "-c", os.path.join(SRC, "spmv_comm.hip"), "-o", os.path.join(tmp, "o.o"),
-                               "-save-temps=obj"], capture_output=True, text=True, timeout=600, cwd=tmp)
-        assert proc.returncode == 0, proc.stderr[-2000:]
-        asm = [f for f in os.listdir(tmp) if f.endswith("gfx950.s")]
-        assert asm, os.listdir(tmp)
-        text = open(os.path.join(tmp, asm[0])).read()
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
-    kernels = {}
-    for m in re.finditer(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)", text):
-        kernels[m.group(1)] = (int(m.group(2)), int(m.group(3)))
-    mcg = {k: v for k, v in kernels.items() if "mcg_" in k}
-    # {dot_partial, update_x_r, update_p} x {fp64 element, fp64 16-byte, fp32 element, fp32 16-byte}, fold, rank sum,
-    # and the three scalar kernels
+def test_cg_and_shared_solver_kernels_compile_for_gfx950_without_scratch():
+    kernels = {k: (v.scratch, v.vgprs) for k, v in compile_kernels("spmv_cg.hip").items()}
+    mcg = {k: v for k, v in kernels.items() if "mcg_" in k or "solver_" in k}
+    # {dot_partial, update_x_r, update_p} x {fp64 element, fp64 16-byte, fp32 element, fp32 16-byte}, the three scalar
+    # kernels, and the shared fold and rank sum of solver_ops.hpp
     vector = [k for k in mcg if re.search(r"mcg_(dot_partial|update_x_r|update_p)I[df]Li[124]E", k)]
     assert len(vector) == 12, sorted(mcg)
-    for name in ("mcg_fold", "mcg_rank_sum", "mcg_start", "mcg_set_alpha", "mcg_set_beta"):
+    for name in ("solver_fold", "solver_rank_sum", "mcg_start", "mcg_set_alpha", "mcg_set_beta"):
         assert any(name in k for k in mcg), (name, sorted(mcg))
     for name, (scratch, vgprs) in mcg.items():
         assert scratch == 0, f"{name} spills {scratch} bytes of scratch ({vgprs} VGPRs)"

@@ -4,18 +4,15 @@ kernels compile for gfx950 without scratch."""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import sparsematrixvectormultiplication_amd as sp
+from _util import HIPCC, compile_kernels
 from conftest import ROOT
 
-HIPCC = "/opt/rocm/bin/hipcc"
-SRC = os.path.join(ROOT, "sparsematrixvectormultiplication_amd", "csrc", "hip")
 VGPR_BOUND = 64  # as test_bicgstab_host.py: the vector kernels stream
 
 
@@ -93,44 +90,28 @@ def test_transpose_and_cgls_refuse_null_handles():
     assert L.spmv_hip_csr_cgls(None, None, 3, 0.0, 0.0, buf, buf, hist, hist, info, C.byref(ms)) == -1
 
 
-def compile_kernels(source):
-    tmp = tempfile.mkdtemp(prefix="spmv_cgls_")
-    try:
-        proc = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
-                               "-I" + SRC, "-c", os.path.join(SRC, source), "-o", os.path.join(tmp, "o.o"),
-                               "-save-temps=obj"], capture_output=True, text=True, timeout=900, cwd=tmp)
-        assert proc.returncode == 0, proc.stderr[-2000:]
-        asm = [f for f in os.listdir(tmp) if f.endswith("gfx950.s")]
-        assert asm, os.listdir(tmp)
-        text = open(os.path.join(tmp, asm[0])).read()
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
-    kernels = {}
-    for m in re.finditer(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)", text):
-        kernels[m.group(1)] = (int(m.group(2)), int(m.group(3)))
-    return kernels
-
-
 def assert_no_scratch(kernels):
-    for name, (scratch, vgprs) in kernels.items():
+    for name, k in kernels.items():
+        scratch, vgprs = k.scratch, k.vgprs
         assert scratch == 0, f"{name} spills {scratch} bytes of scratch ({vgprs} VGPRs)"
         assert vgprs <= VGPR_BOUND, f"{name}: {vgprs} VGPRs > {VGPR_BOUND}"
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_cgls_kernels_compile_for_gfx950_without_scratch():
-    cgls = {k: v for k, v in compile_kernels("spmv_cgls.hip").items() if "cgls_" in k}
+def test_cgls_and_shared_solver_kernels_compile_for_gfx950_without_scratch():
+    # with the shared fold (and rank sum) of solver_ops.hpp
+    cgls = {k: v for k, v in compile_kernels("spmv_cgls.hip", timeout=900).items() if "cgls_" in k or "solver_" in k}
     # the four vector kernels x {fp64 in 16-byte pieces of 2, fp32 in pieces of 4}
     vector = [k for k in cgls if re.search(r"cgls_(norm2|update_x_r|update_s|update_p)I(dLi2|fLi4)E", k)]
     assert len(vector) == 8, sorted(cgls)
-    for name in ("cgls_fold", "cgls_start", "cgls_set_alpha", "cgls_set_beta"):
+    for name in ("solver_fold", "cgls_start", "cgls_set_alpha", "cgls_set_beta"):
         assert any(name in k for k in cgls), (name, sorted(cgls))
     assert_no_scratch(cgls)
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_transpose_kernels_compile_for_gfx950_without_scratch():
-    tr = {k: v for k, v in compile_kernels("spmv_transpose.hip").items() if re.search(r"tr_(make_pairs|gather|row_ptr)", k)}
+    tr = {k: v for k, v in compile_kernels("spmv_transpose.hip", timeout=900).items() if re.search(r"tr_(make_pairs|gather|row_ptr)", k)}
     assert any("tr_make_pairs" in k for k in tr) and any("tr_row_ptr" in k for k in tr), sorted(tr)
     assert sum("tr_gather" in k for k in tr) == 2, sorted(tr)   # fp64 and fp32
     assert_no_scratch(tr)

@@ -3,20 +3,15 @@ HllDevice.spmm checks its input before any device call, the entry points refuse 
 compile for gfx950 in their own translation unit without scratch."""
 import ctypes as C
 import os
-import re
-import shutil
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import sparsematrixvectormultiplication_amd as sp
-from conftest import ROOT
+from _util import HIPCC, compile_kernels
 
 HLL_SPMM_SYMBOLS = ("spmv_hip_hll_spmm", "spmv_hip_hll_spmm_on", "spmv_hip_hll_spmm_time")
-HIPCC = "/opt/rocm/bin/hipcc"
-SRC = os.path.join(ROOT, "sparsematrixvectormultiplication_amd", "csrc", "hip")
 
 
 def test_hll_spmm_symbols_are_exported_and_bound():
@@ -59,20 +54,7 @@ def test_hll_spmm_entry_points_refuse_a_null_handle():
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_hll_spmm_kernels_compile_for_gfx950_without_scratch():
-    tmp = tempfile.mkdtemp(prefix="spmv_hll_spmm_regs_")
-    try:
-        proc = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
-                               "-I" + SRC, "-c", os.path.join(SRC, "spmv_hll_spmm.hip"), "-o", os.path.join(tmp, "o.o"),
-                               "-save-temps=obj"], capture_output=True, text=True, timeout=600, cwd=tmp)
-        assert proc.returncode == 0, proc.stderr[-2000:]
-        asm = [f for f in os.listdir(tmp) if f.endswith("gfx950.s")]
-        assert asm, os.listdir(tmp)
-        text = open(os.path.join(tmp, asm[0])).read()
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
-    kernels = {}
-    for m in re.finditer(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)", text):
-        kernels[m.group(1)] = (int(m.group(2)), int(m.group(3)))
+    kernels = {k: (v.scratch, v.vgprs) for k, v in compile_kernels("spmv_hll_spmm.hip").items()}
     # 4 column-tile widths x {16-byte, element} loads, for the window and the long-row kernels (fp64 only)
     assert len([k for k in kernels if "hll_spmm_block" in k]) == 8, sorted(kernels)
     assert len([k for k in kernels if "hll_spmm_row" in k]) == 8, sorted(kernels)

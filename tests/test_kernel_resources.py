@@ -5,35 +5,15 @@ its register allocation into scratch before (private_segment_fixed_size > 0: 167
 A spill there, or in the x-window kernels, is a performance bug that no parity test sees."""
 import os
 import re
-import shutil
-import subprocess
-import tempfile
 
 import pytest
 
-from conftest import ROOT
-
-HIPCC = "/opt/rocm/bin/hipcc"
-SRC = os.path.join(ROOT, "sparsematrixvectormultiplication_amd", "csrc", "hip")
+from _util import HIPCC, compile_kernels
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_hot_kernels_do_not_spill_and_keep_their_occupancy():
-    tmp = tempfile.mkdtemp(prefix="spmv_regs_")
-    try:
-        proc = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
-                               "-I" + SRC, "-c", os.path.join(SRC, "spmv_csr.hip"), "-o", os.path.join(tmp, "o.o"),
-                               "-save-temps=obj"], capture_output=True, text=True, timeout=600, cwd=tmp)
-        assert proc.returncode == 0, proc.stderr[-2000:]
-        asm = [f for f in os.listdir(tmp) if f.endswith("gfx950.s")]
-        assert asm, os.listdir(tmp)
-        text = open(os.path.join(tmp, asm[0])).read()
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
-    # the kernel descriptors' metadata: name, scratch bytes, VGPRs
-    kernels = {}
-    for m in re.finditer(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)", text):
-        kernels[m.group(1)] = (int(m.group(2)), int(m.group(3)))
+    kernels = {k: (v.scratch, v.vgprs) for k, v in compile_kernels("spmv_csr.hip").items()}
     # csr_tile<T, NT, 2048, 4, PACK, GA>: the GA (gather ahead) instantiations are an experiment that did not pay and is off
     # by default (profiles/r3_ab_gather_ahead.txt); the product's eight are the ones held to the budget
     all_tile = {k: v for k, v in kernels.items() if "csr_tile" in k}

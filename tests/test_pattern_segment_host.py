@@ -4,37 +4,18 @@ layout they replaced used (72: seven resident workgroups per CU), and only dynam
 the headline plan's stage, slots and widest segment still leave seven workgroups per CU (the library's own cap)."""
 import os
 import re
-import shutil
-import subprocess
-import tempfile
 
 import pytest
 
 import sparsematrixvectormultiplication_amd as sp
-from conftest import ROOT
+from _util import HIPCC, compile_kernels
 
-HIPCC = "/opt/rocm/bin/hipcc"
-SRC = os.path.join(ROOT, "sparsematrixvectormultiplication_amd", "csrc", "hip")
 LDS_PER_CU, GRANULE = 160 * 1024, 512
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_pattern_segment_kernels_fit_seven_workgroups_per_cu():
-    tmp = tempfile.mkdtemp(prefix="spmv_seg_regs_")
-    try:
-        proc = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
-                               "-I" + SRC, "-c", os.path.join(SRC, "spmv_csr.hip"), "-o", os.path.join(tmp, "o.o"),
-                               "-save-temps=obj"], capture_output=True, text=True, timeout=600, cwd=tmp)
-        assert proc.returncode == 0, proc.stderr[-2000:]
-        asm = [f for f in os.listdir(tmp) if f.endswith("gfx950.s")]
-        assert asm, os.listdir(tmp)
-        text = open(os.path.join(tmp, asm[0])).read()
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
-    kernels = {}
-    for m in re.finditer(r"\.group_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.name:\s+(\S+)\n(?:.*\n)*?"
-                         r"\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)", text):
-        kernels[m.group(2)] = (int(m.group(1)), int(m.group(3)), int(m.group(4)))
+    kernels = {k: (v.lds, v.scratch, v.vgprs) for k, v in compile_kernels("spmv_csr.hip").items()}
     # csr_stream_local<T, NT, CAP, STAMP = false, PAT = true>: {fp64, fp32} x {nt} x stages {1024, 2048, 3072}
     pat = {k: v for k, v in kernels.items() if re.search(r"csr_stream_localI[df]Lb[01]ELi\d+ELb0ELb1EE", k)}
     assert len(pat) == 12, sorted(k for k in kernels if "csr_stream_local" in k)

@@ -4,19 +4,15 @@ scratch."""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import sparsematrixvectormultiplication_amd as sp
-from conftest import ROOT
+from _util import HIPCC, compile_kernels
 
 SPMM_SYMBOLS = ("spmv_hip_csr_spmm", "spmv_hip_csr_spmm_on", "spmv_hip_csr_spmm_time")
-HIPCC = "/opt/rocm/bin/hipcc"
-SRC = os.path.join(ROOT, "sparsematrixvectormultiplication_amd", "csrc", "hip")
 
 
 def test_spmm_symbols_are_exported_and_bound():
@@ -64,20 +60,7 @@ def test_spmm_entry_points_refuse_a_null_handle():
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_spmm_kernels_compile_for_gfx950_without_scratch():
-    tmp = tempfile.mkdtemp(prefix="spmv_spmm_regs_")
-    try:
-        proc = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
-                               "-I" + SRC, "-c", os.path.join(SRC, "spmv_spmm.hip"), "-o", os.path.join(tmp, "o.o"),
-                               "-save-temps=obj"], capture_output=True, text=True, timeout=600, cwd=tmp)
-        assert proc.returncode == 0, proc.stderr[-2000:]
-        asm = [f for f in os.listdir(tmp) if f.endswith("gfx950.s")]
-        assert asm, os.listdir(tmp)
-        text = open(os.path.join(tmp, asm[0])).read()
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
-    kernels = {}
-    for m in re.finditer(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)", text):
-        kernels[m.group(1)] = (int(m.group(2)), int(m.group(3)))
+    kernels = {k: (v.scratch, v.vgprs) for k, v in compile_kernels("spmv_spmm.hip").items()}
     spmm = {k: v for k, v in kernels.items() if "csr_spmm" in k}
     # {fp64, fp32} x 4 column-tile widths x {16-byte, element} loads, for the block and piece kernels; 2 finish kernels
     assert len([k for k in spmm if "csr_spmm_block" in k]) == 16, sorted(spmm)

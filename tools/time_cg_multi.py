@@ -131,7 +131,7 @@ def trace_report(args):
         if hit is not None:
             g = "vector"
             vec_bytes += calls * hit * n * k * vb
-        elif "mcg_" in name:
+        elif "mcg_" in name or "solver_fold" in name or "solver_rank_sum" in name:   # (the shared fold / rank sum)
             g = "small"
         elif "spmm" in name or k == 1:
             g = "spmm"
