@@ -4,8 +4,7 @@
 // :285-317, :682-685).
 #include "spmv_internal.hpp"
 
-#include "plan_kernels.hpp"
-#include <chrono>
+#include "upload_ops.hpp"
 
 #include "tile_plan.hpp"
 #include "tile_plan_device.hpp"
@@ -638,165 +637,36 @@ bool csr_build_local(int M, int N, const int *rp, const int *col, long long nz, 
     return true;
 }
 
-// The x-window plan of the blocks `desc` (cut by entries and rows only) built on the device from the
-// uploaded column indices (plan_kernels.hpp).  1: the handle carries the plan; 0: some block lists
-// more than kLocalLinesMax lines, the host builder (which may cut blocks by lines or split rows)
-// has to decide; 2: so many blocks list so many lines that the host builder would refuse too; -1: HIP error.
+// The x-window plan of the blocks `desc` (cut by entries and rows only) built on the device from the uploaded column
+// indices (upload_ops.hpp).  1: the handle carries the plan; 0: some block lists more than kLocalLinesMax lines, the
+// host builder (which may cut blocks by lines or split rows) has to decide; 2: so many blocks list so many lines that
+// the host builder would refuse too; -1: HIP error.
 template <int SHIFT>
 int csr_plan_on_device(spmv_csr_dev *m, const std::vector<int4> &desc, long long nz) {
     const int W = (int)desc.size();
-    if (W == 0) return 0;
-    std::vector<long long> seg_begin((size_t)W);
-    std::vector<int> seg_len((size_t)W);
+    std::vector<long long> begin((size_t)W);
+    std::vector<int> len((size_t)W), nl;
     for (int w = 0; w < W; ++w) {
-        seg_begin[w] = desc[w].y;
-        seg_len[w] = desc[w].w - desc[w].y;
-        if (seg_len[w] > kPlanCap) return 0;
+        begin[w] = desc[w].y;
+        len[w] = desc[w].w - desc[w].y;
+        if (len[w] > kPlanCap) return 0;
     }
-    long long *d_begin = nullptr;
-    int *d_len = nullptr, *d_n = nullptr, *d_off = nullptr;
-    int result = -1;
-    do {
-        if (upload_array(&d_begin, seg_begin.data(), seg_begin.size(), 0)) break;
-        if (upload_array(&d_len, seg_len.data(), seg_len.size(), 0)) break;
-        hipError_t e = hipMalloc((void **)&d_n, (size_t)W * sizeof(int));
-        if (e != hipSuccess) { fail("csr plan: hipMalloc failed: %s", hipGetErrorString(e)); break; }
-        hipLaunchKernelGGL((plan_count<SHIFT>), dim3(W), dim3(kBlock), 0, g_stream, W, d_begin, d_len, m->col, d_n);
-        std::vector<int> nl((size_t)W);
-        e = hipMemcpyAsync(nl.data(), d_n, (size_t)W * sizeof(int), hipMemcpyDeviceToHost, g_stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-        if (e != hipSuccess) { fail("csr plan: count pass failed: %s", hipGetErrorString(e)); break; }
-        std::vector<int> line_off((size_t)W);
-        std::vector<int2> ldesc((size_t)W);
-        long long total = 0;
-        int widest = 0;
-        bool fits = true;
-        for (int w = 0; w < W && fits; ++w) {
-            const int n = std::max(nl[w], 1);  // a block of empty rows still stages one line
-            fits = nl[w] <= kLocalLinesMax && total + n < (1LL << 31);
-            line_off[w] = (int)total;
-            ldesc[w] = int2{(int)total, n};
-            total += n;
-            widest = std::max(widest, n);
-        }
-        if (!fits) {
-            // Some block lists too many lines.  The host builder may still find a plan (blocks cut by lines, a few rows
-            // split) -- unless the matrix is plainly scattered: a block with n lines needs at least n / 256 line-limited
-            // blocks, a line-limited block can overlap two of ours, and the host refuses a plan with more than 1.2 x
-            // our block count.  2 = refused here (the host builder would spend ~0.2 s at 2.6e8 entries to say the same).
-            long long need = 0;
-            for (int w = 0; w < W; ++w) need += std::max(1, (nl[w] + kLocalLinesMax - 1) / kLocalLinesMax);
-            result = (need + 1) / 2 > (long long)W + W / 5 + 1 ? 2 : 0;
-            break;
-        }
-        if (upload_array(&d_off, line_off.data(), line_off.size(), 0)) break;
-        e = hipMalloc((void **)&m->lines, ((size_t)total + kLocalLinesMax) * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void **)&m->lcol, ((size_t)nz + kPad) * sizeof(unsigned short));
-        if (e == hipSuccess) e = hipMemsetAsync(m->lines, 0, ((size_t)total + kLocalLinesMax) * sizeof(int), g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(m->lcol, 0, ((size_t)nz + kPad) * sizeof(unsigned short), g_stream);
-        if (e != hipSuccess) { fail("csr plan: allocation failed: %s", hipGetErrorString(e)); break; }
-        hipLaunchKernelGGL((plan_fill<SHIFT>), dim3(W), dim3(kBlock), 0, g_stream, W, d_begin, d_len, m->col, d_off,
-                           m->lines, m->lcol);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-        if (e != hipSuccess) { fail("csr plan: fill pass failed: %s", hipGetErrorString(e)); break; }
-        if (upload_array(&m->ldesc4, desc.data(), desc.size(), 1)) break;
-        if (upload_array(&m->ldesc, ldesc.data(), ldesc.size(), 1)) break;
-        m->local_blocks = W;
-        m->local_lines = total;
-        m->local_stage_lines = std::max(kLocalLineQuantum,
-                                        (widest + kLocalLineQuantum - 1) / kLocalLineQuantum * kLocalLineQuantum);
-        result = 1;
-    } while (0);
-    (void)hipFree(d_begin);
-    (void)hipFree(d_len);
-    (void)hipFree(d_n);
-    (void)hipFree(d_off);
-    if (result != 1) {
-        (void)hipFree(m->lines);
-        (void)hipFree(m->lcol);
-        (void)hipFree(m->ldesc4);
-        (void)hipFree(m->ldesc);
-        m->lines = nullptr;
-        m->lcol = nullptr;
-        m->ldesc4 = nullptr;
-        m->ldesc = nullptr;
-        m->local_blocks = 0;
-    }
-    return result;
-}
-
-// Where the value array lies decides -- for as long as the allocation lives, by a mechanism the counters at hand do not
-// name (profiles/r3_placement_*.txt: not the XCD mapping, not the TLB, not one slow XCD; every block of one HALF of
-// the matrix is a little slower) -- whether the x-window kernel runs the headline matrix in 182-187 or in 199-205 us.
-// So a handle that streams enough values for it to matter times its own kernel on a few placements and keeps the best:
-// up to g_place_tries fresh allocations of the value array (earlier candidates stay allocated meanwhile, so every one
-// is a different place), 2 + 6 launches each.  ~2 ms per candidate at 100 M entries; upload itself takes 50-100.
-// Three levels exist -- both halves of the array fast (180-182 us on the headline matrix), one (186-194), none
-// (199-205); fresh allocations land on them roughly 2 : 5 : 5 (profiles/r3_placement_*.txt) -- so the search goes on
-// until a candidate is 8.5 % faster than the slowest seen (= the top level reached) or the tries are used up.
-template <typename T>
-int csr_tune_placement(spmv_csr_dev *m) {
-    const size_t bytes = ((size_t)m->nz + kPad) * sizeof(T);
-    if (g_place_tries <= 0 || (size_t)m->nz * sizeof(T) < ((size_t)128 << 20) || m->tiles_only || !m->val) return 0;
-    if (m->local_blocks == 0 && m->tile_blocks > 0) return 0;  // csr_tile streams its own re-ordered copy, not m->val
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
-        if (e0) (void)hipEventDestroy(e0);
-        return 0;
-    }
-    auto measure = [&](float &us) {
-        for (int i = 0; i < 2; ++i)
-            if (csr_launch_any(m, SPMV_CSR_AUTO, m->x, m->y, g_stream)) return -1;
-        hipError_t e = hipEventRecord(e0, g_stream);
-        for (int i = 0; i < 6 && e == hipSuccess; ++i)
-            if (csr_launch_any(m, SPMV_CSR_AUTO, m->x, m->y, g_stream)) return -1;
-        if (e == hipSuccess) e = hipEventRecord(e1, g_stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-        float ms = 0;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        if (e != hipSuccess) return fail("placement tuning: timing failed: %s", hipGetErrorString(e));
-        us = ms * 1e3f / 6.0f;
-        return 0;
-    };
-    int rc = 0;
-    void *first = m->val, *best = m->val;
-    float best_us = 0;
-    std::vector<void *> others;
-    rc = measure(best_us);
-    m->place_first_us = best_us;
-    m->place_tries = 1;
-    float worst_us = best_us;
-    for (int t = 0; t < g_place_tries && !rc; ++t) {
-        void *p = nullptr;
-        if (hipMalloc(&p, bytes) != hipSuccess) break;  // (out of memory for another copy: keep what we have)
-        others.push_back(p);
-        if (hipMemcpy(p, first, bytes, hipMemcpyDeviceToDevice) != hipSuccess) break;
-        m->val = p;
-        float us = 0;
-        rc = measure(us);
-        if (rc) break;
-        ++m->place_tries;
-        if (us < best_us * 0.985f) {  // (1.5 %: above the run-to-run noise of 6 launches)
-            best = p;
-            best_us = us;
-        }
-        worst_us = std::max(worst_us, us);
-        if (best_us < worst_us * 0.915f) break;  // both halves of the array at their fast level (see above): nothing better to find
-    }
-    m->val = best;
-    m->place_best_us = best_us;
-    if (best != first) (void)hipFree(first);
-    for (void *p : others)
-        if (p != best) (void)hipFree(p);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return rc;
+    const int rc = plan_on_device<SHIFT>(m, m->col, (size_t)nz, desc, begin, len, m->lcol, m->ldesc,
+                                         [](int, int first, int n) { return int2{first, n}; }, nl);
+    if (rc != 0 || nl.empty()) return rc;
+    // Some block lists too many lines.  The host builder may still find a plan (blocks cut by lines, a few rows split) --
+    // unless the matrix is plainly scattered: a block with n lines needs at least n / 256 line-limited blocks, a
+    // line-limited block can overlap two of ours, and the host refuses a plan with more than 1.2 x our block count.
+    // 2 = refused here (the host builder would spend ~0.2 s at 2.6e8 entries to say the same).
+    long long need = 0;
+    for (int n : nl) need += std::max(1, (n + kLocalLinesMax - 1) / kLocalLinesMax);
+    return (need + 1) / 2 > (long long)W + W / 5 + 1 ? 2 : 0;
 }
 
 // The pattern plan of a handle's x-window plan (csr_kernels.hpp, PAT; plan_kernels.hpp): built on the device from the
-// plan's own arrays, whichever builder made them -- the tables (pat_mark, pat_fill), then one segment per block out of
-// them where it fits the LDS budget (pat_segment).  auto: kept when the tables hold at most a quarter of the slots.
+// plan's own arrays, whichever builder made them -- the tables (build_pattern_tables, upload_ops.hpp), then one segment
+// per block out of them where it fits the LDS budget (csr_pattern_segments).  auto: kept when the tables hold at most a
+// quarter of the slots.
 // Where it pays (same handle, same placement, the two instantiations alternately: profiles/r3_ab_patterns.txt): the
 // nlpkkt-like matrix 190 -> 178 us (bench.py over 4 uploads each; 204 -> 185 on a slow placement), a 27-point stencil
 // 197 -> 190; neutral on the FEM-shaped matrix (75 per row: 155 / 157) and on nlpkkt80-size (59 / 60); a loss where the
@@ -807,7 +677,7 @@ int csr_tune_placement(spmv_csr_dev *m) {
 // (27-point stencil: 204 -> 195 on one box, 177 -> 183 on another).  Hence auto: streamed matrices (the `nt` threshold)
 // of at least 12 entries per row whose tables hold at most a quarter of the slots get a plan BUILT, and upload then
 // times its own kernel with and without it and keeps the plan only if it is at least 2 % faster on this handle
-// (csr_tune_patterns, beside the placement search).
+// (tune_pattern_plan, beside the placement search).
 // The widest segment (uint4s, at most one per lane) whose LDS copy keeps as many workgroups of csr_stream_local<.., PAT>
 // resident per CU as its stage and slots alone would, up to the 7 its VGPRs allow.  LDS is counted in 512-byte granules
 // (no finer than the hardware's), of the 160 KiB of a gfx950 CU.
@@ -832,93 +702,25 @@ extern "C" int spmv_hip_csr_pattern_segment_cap(int value_bytes, int local_cap, 
     return 16 * pattern_segment_cap(value_bytes, local_cap, stage_lines);
 }
 
-int csr_build_patterns(spmv_csr_dev *m) {
-    if (g_local_patterns == 0 || m->local_blocks <= 0 || !m->lcol || !m->ldesc4 || !m->row_ptr || m->M_local <= 0) return 0;
-    if (g_local_patterns < 0 && (m->nz * (m->value_bytes + 2LL) <= (128LL << 20) || m->nz < 12LL * m->M_local)) return 0;
-    UploadTrace trace("csr_build_patterns");
+// The segments of a pattern plan whose tables are built (count[b]: elements of block b's table).  The LDS budget of a
+// segment: the kernel's stage and slots take stage + (cap + 8) * 2 bytes; the segment's copy may not cost a resident
+// workgroup per CU (at most the 7 the kernel's VGPRs allow).  A block whose segment is wider keeps its table.  A
+// failure drops the whole plan (and clears the last HIP error).
+void csr_pattern_segments(spmv_csr_dev *m, const std::vector<int> &count) {
+    PatternPlan &pat = m->pat;
+    if (!pat.ptab) return;
+    UploadTrace trace("csr_pattern_segments");
     const int B = m->local_blocks;
-    int *rowflag = nullptr, *pcount = nullptr;
-    long long *pbase = nullptr;
-    auto drop_tmp = [&] {
-        (void)hipFree(rowflag);
-        (void)hipFree(pcount);
-        (void)hipFree(pbase);
-    };
-    hipError_t e = hipMalloc((void **)&rowflag, (size_t)m->M_local * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&pcount, (size_t)B * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&pbase, (size_t)B * sizeof(long long));
-    if (e == hipSuccess) e = hipMemsetAsync(rowflag, 0, (size_t)m->M_local * sizeof(int), g_stream);
-    if (e != hipSuccess) {
-        drop_tmp();
-        return fail("pattern plan: allocation failed: %s", hipGetErrorString(e));
-    }
-    hipLaunchKernelGGL((pat_mark<256>), dim3(B), dim3(256), 0, g_stream, B, m->ldesc4, m->row_ptr, m->lcol, rowflag, pcount);
-    std::vector<int> h_count((size_t)B);
-    e = hipMemcpyAsync(h_count.data(), pcount, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, g_stream);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-    if (e != hipSuccess) {
-        drop_tmp();
-        return fail("pattern plan: marking the rows failed: %s", hipGetErrorString(e));
-    }
-    std::vector<long long> h_base((size_t)B);
-    long long total = 0;
-    int widest = 0;
-    for (int b = 0; b < B; ++b) {
-        h_base[(size_t)b] = total;
-        total += h_count[(size_t)b];
-        widest = std::max(widest, h_count[(size_t)b]);
-    }
-    trace.mark("rows marked");
-    // (auto) a plan whose tables hold more than a quarter of the slots keeps reading the slot stream
-    if ((g_local_patterns < 0 && total * 4 > m->nz) || total > 0x7ffffff0LL) {
-        drop_tmp();
-        return 0;
-    }
-    // the tables first (pat_fill), then one segment per block out of them (pat_segment) where it fits the LDS budget
-    auto drop_plan = [&] {
-        (void)hipFree(m->ptab);
-        (void)hipFree(m->rinfo);
-        (void)hipFree(m->pdesc);
-        (void)hipFree(m->pseg);
-        (void)hipFree(m->sdesc);
-        m->ptab = nullptr;
-        m->rinfo = nullptr;
-        m->pdesc = nullptr;
-        m->pseg = nullptr;
-        m->sdesc = nullptr;
-    };
-    e = hipMalloc((void **)&m->ptab, ((size_t)total + 1024) * sizeof(unsigned short));
-    if (e == hipSuccess) e = hipMalloc((void **)&m->rinfo, (size_t)m->M_local * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMalloc((void **)&m->pdesc, (size_t)B * sizeof(int2));
-    if (e == hipSuccess) e = hipMemsetAsync(m->ptab, 0, ((size_t)total + 1024) * sizeof(unsigned short), g_stream);
-    if (e == hipSuccess) e = hipMemsetAsync(m->rinfo, 0, (size_t)m->M_local * sizeof(unsigned), g_stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(pbase, h_base.data(), (size_t)B * sizeof(long long), hipMemcpyHostToDevice, g_stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL((pat_fill<256>), dim3(B), dim3(256), 0, g_stream, B, m->ldesc4, m->row_ptr, m->lcol, rowflag, pbase, m->rinfo,
-                           m->ptab, m->pdesc);
-        e = hipGetLastError();
-    }
-    // the blocks' row counts: the size of their segments
-    std::vector<int4> h_desc((size_t)B);
-    if (e == hipSuccess) e = hipMemcpyAsync(h_desc.data(), m->ldesc4, (size_t)B * sizeof(int4), hipMemcpyDeviceToHost, g_stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-    drop_tmp();
-    if (e != hipSuccess) {
-        drop_plan();
-        return fail("pattern plan: building the tables failed: %s", hipGetErrorString(e));
-    }
-    trace.mark("tables");
-    // The LDS budget of a segment: the kernel's stage and slots take stage + (cap + 8) * 2 bytes; the segment's copy may
-    // not cost a resident workgroup per CU (at most the 7 the kernel's VGPRs allow).  A block whose segment is wider
-    // keeps its table.
     const int cap16 = csr_pattern_segment_cap(m);
+    std::vector<int4> h_desc((size_t)B);  // the blocks' row counts: the size of their segments
+    hipError_t e = hipMemcpyAsync(h_desc.data(), m->ldesc4, (size_t)B * sizeof(int4), hipMemcpyDeviceToHost, g_stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
     std::vector<int2> h_sdesc((size_t)B, make_int2(0, 0));
     long long seg_total = 0, table_rows = 0;
     int seg_max = 0;
-    for (int b = 0; b < B; ++b) {
+    for (int b = 0; b < B && e == hipSuccess; ++b) {
         const int4 d = h_desc[(size_t)b];
-        const int len = seg_groups_at(d.z) + h_count[(size_t)b] / 8;
+        const int len = seg_groups_at(d.z) + count[(size_t)b] / 8;
         if (len <= cap16) {
             h_sdesc[(size_t)b] = make_int2((int)seg_total, len);
             seg_total += len;
@@ -928,92 +730,31 @@ int csr_build_patterns(spmv_csr_dev *m) {
         }
     }
     if (seg_max > 0 && seg_total <= 0x7fffffffLL) {
-        e = hipMalloc((void **)&m->pseg, (size_t)seg_total * sizeof(uint4));
-        if (e == hipSuccess) e = hipMalloc((void **)&m->sdesc, (size_t)B * sizeof(int2));
-        if (e == hipSuccess) e = hipMemsetAsync(m->pseg, 0, (size_t)seg_total * sizeof(uint4), g_stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(m->sdesc, h_sdesc.data(), (size_t)B * sizeof(int2), hipMemcpyHostToDevice, g_stream);
+        e = hipMalloc((void **)&pat.pseg, (size_t)seg_total * sizeof(uint4));
+        if (e == hipSuccess) e = hipMalloc((void **)&pat.sdesc, (size_t)B * sizeof(int2));
+        if (e == hipSuccess) e = hipMemsetAsync(pat.pseg, 0, (size_t)seg_total * sizeof(uint4), g_stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(pat.sdesc, h_sdesc.data(), (size_t)B * sizeof(int2), hipMemcpyHostToDevice, g_stream);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL((pat_segment<256>), dim3(B), dim3(256), 0, g_stream, B, m->ldesc4, m->row_ptr, m->rinfo, m->ptab,
-                               m->pdesc, m->sdesc, m->pseg);
+            hipLaunchKernelGGL((pat_segment<256>), dim3(B), dim3(256), 0, g_stream, B, m->ldesc4, m->row_ptr, pat.rinfo,
+                               pat.ptab, pat.pdesc, pat.sdesc, pat.pseg);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-        if (e != hipSuccess) {
-            drop_plan();
-            return fail("pattern plan: building the segments failed: %s", hipGetErrorString(e));
-        }
     } else {
         seg_total = 0;
         seg_max = 0;
         table_rows = m->M_local;
     }
-    m->pat_slots = total;
-    m->pat_max = widest;
-    m->pat_seg_total = seg_total;
-    m->pat_seg_max = seg_max;
-    m->pat_seg_cap = cap16;
-    m->pat_table_rows = table_rows;
-    m->device_bytes += ((size_t)total + 1024) * 2 + (size_t)m->M_local * 4 + (size_t)B * 8;
-    if (m->pseg) m->device_bytes += (size_t)seg_total * sizeof(uint4) + (size_t)B * sizeof(int2);
+    if (e != hipSuccess) {
+        pat.release();
+        (void)hipGetLastError();
+        return;
+    }
+    pat.seg_total = seg_total;
+    pat.seg_max = seg_max;
+    pat.seg_cap = cap16;
+    pat.table_rows = table_rows;
     trace.mark("segments");
-    return 0;
-}
-
-// (auto) the handle's kernel with and without its pattern plan, alternately, two rounds of 2 + 6 launches each: the plan
-// stays if it is at least 2 % faster here.  Never a reason to lose the handle.
-int csr_tune_patterns(spmv_csr_dev *m) {
-    if (g_local_patterns >= 0 || !m->ptab || !m->x || !m->y) return 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
-        if (e0) (void)hipEventDestroy(e0);
-        return 0;
-    }
-    auto measure = [&](int patterns, float &us) {
-        const int keep = g_local_patterns;
-        g_local_patterns = patterns;
-        int rc = 0;
-        for (int i = 0; i < 2 && !rc; ++i) rc = csr_launch_any(m, SPMV_CSR_AUTO, m->x, m->y, g_stream);
-        hipError_t e = rc ? hipErrorUnknown : hipEventRecord(e0, g_stream);
-        for (int i = 0; i < 6 && e == hipSuccess && !rc; ++i) rc = csr_launch_any(m, SPMV_CSR_AUTO, m->x, m->y, g_stream);
-        if (e == hipSuccess && !rc) e = hipEventRecord(e1, g_stream);
-        if (e == hipSuccess && !rc) e = hipStreamSynchronize(g_stream);
-        float ms = 0;
-        if (e == hipSuccess && !rc) e = hipEventElapsedTime(&ms, e0, e1);
-        g_local_patterns = keep;
-        us = ms * 1e3f / 6.0f;
-        return (e == hipSuccess && !rc) ? 0 : -1;
-    };
-    float with_us = 0, without_us = 0;
-    bool ok = true;
-    for (int round = 0; round < 2 && ok; ++round) {
-        float a = 0, b = 0;
-        ok = measure(1, a) == 0 && measure(0, b) == 0;
-        with_us = round ? std::min(with_us, a) : a;
-        without_us = round ? std::min(without_us, b) : b;
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    m->pat_with_us = with_us;
-    m->pat_without_us = without_us;
-    if (!ok || with_us > 0.98f * without_us) {  // not faster here: the slot stream stays
-        m->device_bytes -= std::min(m->device_bytes, ((size_t)m->pat_slots + 1024) * 2 + (size_t)m->M_local * 4 + (size_t)m->local_blocks * 8 +
-                                                          (m->pseg ? (size_t)m->pat_seg_total * sizeof(uint4) + (size_t)m->local_blocks * sizeof(int2) : 0));
-        (void)hipFree(m->ptab);
-        (void)hipFree(m->rinfo);
-        (void)hipFree(m->pdesc);
-        (void)hipFree(m->pseg);
-        (void)hipFree(m->sdesc);
-        m->ptab = nullptr;
-        m->rinfo = nullptr;
-        m->pdesc = nullptr;
-        m->pseg = nullptr;
-        m->sdesc = nullptr;
-        m->pat_slots = 0;
-        m->pat_seg_total = 0;
-        m->pat_seg_max = 0;
-        m->pat_table_rows = 0;
-    }
-    return 0;
 }
 
 template <typename T>
@@ -1227,7 +968,11 @@ int csr_upload_impl(int M, int N, const int *row_ptr, const int *col_idx, const 
             m->local_lines = (long long)local.lines.size() - kLocalLinesMax;
         }
     }
-    if (!rc && m->local_blocks > 0) rc |= csr_build_patterns(m);
+    // the pattern plan (optional: one that cannot be built is simply not there); here, ahead of the value array, whose
+    // first placement goes with the allocations before it
+    if (!rc)
+        csr_pattern_segments(m, build_pattern_tables<false>(m->pat, m->local_blocks, m->M_local, nz, m->value_bytes,
+                                                            m->ldesc4, m->row_ptr, nullptr, m->lcol));
     if (!rc && !m->col) rc |= upload_array(&m->col, col_idx ? col_idx + e0 : nullptr, (size_t)nz, kPad);
     if (!rc && !m->val) rc |= upload_array((T **)&m->val, values ? values + e0 : nullptr, (size_t)nz, kPad);
     if (!rc) rc |= upload_array(&m->desc, desc.data(), desc.size(), 1);
@@ -1260,7 +1005,7 @@ int csr_upload_impl(int M, int N, const int *row_ptr, const int *col_idx, const 
     if (have_local)
         m->device_bytes += (size_t)m->local_blocks * 24 + ((size_t)m->local_lines + kLocalLinesMax) * 4 +
                            ((size_t)nz + kPad) * 2;
-    m->device_bytes += tile_bytes;
+    m->device_bytes += m->pat.bytes(Ml, m->local_blocks) + tile_bytes;
 
     // lanes per row for the SUBWAVE kernel: about half the mean row length,
     // rounded to a power of two, so that a typical row takes 1-2 passes
@@ -1275,19 +1020,11 @@ int csr_upload_impl(int M, int N, const int *row_ptr, const int *col_idx, const 
     if (!have_local && !tb.have_tiles && nz < (20LL << 20) && max_row <= std::max(64.0, 8.0 * mean))
         m->auto_variant = SPMV_CSR_SUBWAVE;
     trace.mark("blocks, remaining uploads, vectors");
-    // Both searches below compare launch times: they begin in the card's steady state -- after an idle stretch (this
-    // upload) the same launch costs 178, then 208, then, from about the 60th on, 175 us (profiles/r3_launch_time_series.txt),
-    // a drift as large as what the searches look for.  ~15 ms of the handle's own kernel first.
-    if ((m->ptab && g_local_patterns < 0) || (g_place_tries > 0 && (size_t)m->nz * sizeof(T) >= ((size_t)128 << 20) && m->val && !m->tiles_only)) {
-        const auto t_settle = std::chrono::steady_clock::now();
-        while (std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_settle).count() < 15.0) {
-            bool bad = false;
-            for (int i = 0; i < 16 && !bad; ++i) bad = csr_launch_any(m, SPMV_CSR_AUTO, m->x, m->y, g_stream) != 0;
-            if (bad || hipStreamSynchronize(g_stream) != hipSuccess) break;
-        }
-    }
-    (void)csr_tune_patterns(m);      // (auto) the pattern plan stays only where it measures faster on this handle
-    (void)csr_tune_placement<T>(m);  // (never a reason to lose the handle: whatever went wrong in there, it holds a valid array)
+    // the searches (upload_ops.hpp); the placement of m->val where it is large and streamed by the handle's kernel (a
+    // tile plan without an x-window plan streams its own re-ordered copy)
+    const bool place = (size_t)nz * sizeof(T) >= kPlaceMinBytes && !m->tiles_only && (m->local_blocks > 0 || m->tile_blocks == 0);
+    upload_searches(m, Ml, place ? &m->val : nullptr, ((size_t)nz + kPad) * sizeof(T),
+                    [m] { return csr_launch_any(m, SPMV_CSR_AUTO, m->x, m->y, g_stream); });
     trace.mark("placement tuning");
     *out = m;
     return 0;
@@ -1730,11 +1467,7 @@ extern "C" void spmv_hip_csr_free(spmv_csr_dev *m) {
     (void)hipFree(m->ldesc);
     (void)hipFree(m->lines);
     (void)hipFree(m->lcol);
-    (void)hipFree(m->ptab);
-    (void)hipFree(m->rinfo);
-    (void)hipFree(m->pdesc);
-    (void)hipFree(m->pseg);
-    (void)hipFree(m->sdesc);
+    m->pat.release();
     for (spmv_csr_dev::long_tiles *tier : {&m->mt}) {
         (void)hipFree(tier->block_row);
         (void)hipFree(tier->block_pass);
@@ -2009,20 +1742,20 @@ extern "C" int spmv_hip_csr_info(const spmv_csr_dev *m, spmv_dev_info *out) {
     out->place_best_us = m->place_best_us;
     out->val_address = (unsigned long long)(uintptr_t)m->val;
     out->tile_expanded_entries = m->xe && m->expansion ? (long long)m->expansion->entries : 0;
-    out->pattern_slots = m->ptab ? m->pat_slots : 0;
-    out->pattern_with_us = m->pat_with_us;
-    out->pattern_without_us = m->pat_without_us;
-    out->pattern_segment_max = m->ptab ? 16 * m->pat_seg_max : 0;
-    out->pattern_segment_cap = 16 * m->pat_seg_cap;
-    out->pattern_table_rows = m->ptab ? m->pat_table_rows : 0;
+    out->pattern_slots = m->pat.ptab ? m->pat.slots : 0;
+    out->pattern_with_us = m->pat.with_us;
+    out->pattern_without_us = m->pat.without_us;
+    out->pattern_segment_max = m->pat.ptab ? 16 * m->pat.seg_max : 0;
+    out->pattern_segment_cap = 16 * m->pat.seg_cap;
+    out->pattern_table_rows = m->pat.ptab ? m->pat.table_rows : 0;
     out->stream_kernel = m->local_blocks > 0 ? 1 : m->tile_blocks > 0 ? 3
                          : ((m->stream_cap == 4096 || m->stream_cap == 2048) && m->M_local > 0 &&
                             m->nz < (long long)m->M_local * (m->stream_cap / kBlock)) ? 2 : 0;
     if (m->local_blocks > 0)  // (a pattern plan: the tables and 4 bytes per row instead of 2 bytes per entry)
         // (a pattern plan: the segments instead of the slots; a block whose segment did not fit reads its table, rinfo
         // and row_ptr -- counted as its share of the tables)
-        out->stream_bytes = m->nz * vb + (m->ptab ? 16 * m->pat_seg_total + 8LL * m->local_blocks +
-                                                        (2 * m->pat_slots + 8LL * m->M_local) * m->pat_table_rows / std::max(1, m->M_local)
+        out->stream_bytes = m->nz * vb + (m->pat.ptab ? 16 * m->pat.seg_total + 8LL * m->local_blocks +
+                                                            (2 * m->pat.slots + 8LL * m->M_local) * m->pat.table_rows / std::max(1, m->M_local)
                                                   : 2 * m->nz + 4LL * (m->M_local + 1)) +
                             4 * m->local_lines + 24LL * m->local_blocks + vb * m->M_local + vb * m->N;
     else if (m->tile_blocks > 0) {  // tiles: 4-byte column + 2-byte key + value per (padded) entry; rows beyond the limit as CSR
@@ -2220,14 +1953,14 @@ int csr_launch(const spmv_csr_dev *m, int variant, const T *x, T *y_full, hipStr
                     const size_t lds = std::max((size_t)m->local_cap * sizeof(T), (size_t)m->local_stage_lines * kLineBytes);
                     // a pattern plan: the slots are rebuilt in LDS (behind the stage) from the block's pattern table, not read
                     // entry by entry
-                    const bool patterns = m->ptab && m->rinfo && m->pdesc && g_local_patterns != 0;
-                    const size_t pat_lds = lds + ((size_t)m->local_cap + 8) * sizeof(unsigned short) + (size_t)m->pat_seg_max * sizeof(uint4);
+                    const bool patterns = m->pat.ptab && g_local_patterns != 0;
+                    const size_t pat_lds = lds + ((size_t)m->local_cap + 8) * sizeof(unsigned short) + (size_t)m->pat.seg_max * sizeof(uint4);
 #define SPMV_LOCAL(NT, CAP)                                                                                   \
     do {                                                                                                      \
         if (patterns)                                                                                         \
             hipLaunchKernelGGL((csr_stream_local<T, NT, CAP, false, true>), dim3(lgrid), dim3(kBlock), pat_lds, s, lcount, lchunk, \
                                lids, m->ldesc4, m->ldesc, m->lines, m->row_ptr, m->lcol, (const T *)m->val, x, y, \
-                               (unsigned long long *)nullptr, 0, m->pdesc, m->rinfo, m->ptab, (int)lds, m->sdesc, (const uint4 *)m->pseg); \
+                               (unsigned long long *)nullptr, 0, m->pat.pdesc, m->pat.rinfo, m->pat.ptab, (int)lds, m->pat.sdesc, (const uint4 *)m->pat.pseg); \
         else                                                                                                  \
             hipLaunchKernelGGL((csr_stream_local<T, NT, CAP>), dim3(lgrid), dim3(kBlock), lds, s, lcount, lchunk, lids, \
                                m->ldesc4, m->ldesc, m->lines, m->row_ptr, m->lcol, (const T *)m->val, x, y);   \

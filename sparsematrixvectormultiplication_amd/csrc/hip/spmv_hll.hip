@@ -1,10 +1,9 @@
 // spmv_hll.hip -- HLL side of the C-ABI: the flat slab, its workgroup windows and x-window plan,
 // the device builder from a resident CSR matrix, launchers, timing.  Replaces the per-hack
 // allocations and launches of /root/reference/main_cuda.cu:369-455, :545-568, :613-637, :731-744.
-#include <chrono>
 #include "spmv_internal.hpp"
 
-#include "plan_kernels.hpp"
+#include "upload_ops.hpp"
 
 namespace {
 
@@ -273,192 +272,19 @@ int hll_finish_handle(spmv_hll_dev *m, int total_rows, int N, const std::vector<
 
 }  // namespace
 
-// The HLL twins of csr_build_patterns / csr_tune_patterns (spmv_csr.hip): the windows' pattern plan, built on the device
-// from the plan's own arrays for streamed slabs of at least 12 slots per row whose tables hold at most a quarter of the
-// slots, and kept only where upload times its own kernel at least 2 % faster with it.
-static int hll_build_patterns(spmv_hll_dev *m) {
-    if (g_local_patterns == 0 || m->local_blocks <= 0 || !m->lja || !m->ldesc4 || !m->row_seg || m->M <= 0) return 0;
-    if (g_local_patterns < 0 && (m->slots * 10LL <= (128LL << 20) || m->slots < 12LL * m->M)) return 0;
-    const int B = m->local_blocks;
-    int *rowflag = nullptr, *pcount = nullptr;
-    long long *pbase = nullptr;
-    auto drop_tmp = [&] {
-        (void)hipFree(rowflag);
-        (void)hipFree(pcount);
-        (void)hipFree(pbase);
-    };
-    hipError_t e = hipMalloc((void **)&rowflag, (size_t)m->M * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&pcount, (size_t)B * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&pbase, (size_t)B * sizeof(long long));
-    if (e == hipSuccess) e = hipMemsetAsync(rowflag, 0, (size_t)m->M * sizeof(int), g_stream);
-    if (e != hipSuccess) {
-        drop_tmp();
-        return fail("pattern plan: allocation failed: %s", hipGetErrorString(e));
-    }
-    hipLaunchKernelGGL((pat_mark<256, true>), dim3(B), dim3(256), 0, g_stream, B, m->ldesc4, (const int *)nullptr, m->lja, rowflag,
-                       pcount, m->row_seg);
-    std::vector<int> h_count((size_t)B);
-    e = hipMemcpyAsync(h_count.data(), pcount, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, g_stream);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-    if (e != hipSuccess) {
-        drop_tmp();
-        return fail("pattern plan: marking the rows failed: %s", hipGetErrorString(e));
-    }
-    std::vector<long long> h_base((size_t)B);
-    long long total = 0;
-    for (int b = 0; b < B; ++b) {
-        h_base[(size_t)b] = total;
-        total += h_count[(size_t)b];
-    }
-    if ((g_local_patterns < 0 && total * 4 > m->slots) || total > 0x7ffffff0LL) {
-        drop_tmp();
-        return 0;
-    }
-    e = hipMalloc((void **)&m->ptab, ((size_t)total + 1024) * sizeof(unsigned short));
-    if (e == hipSuccess) e = hipMalloc((void **)&m->rinfo, (size_t)m->M * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMalloc((void **)&m->pdesc, (size_t)B * sizeof(int2));
-    if (e == hipSuccess) e = hipMemsetAsync(m->ptab, 0, ((size_t)total + 1024) * sizeof(unsigned short), g_stream);
-    if (e == hipSuccess) e = hipMemsetAsync(m->rinfo, 0, (size_t)m->M * sizeof(unsigned), g_stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(pbase, h_base.data(), (size_t)B * sizeof(long long), hipMemcpyHostToDevice, g_stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL((pat_fill<256, true>), dim3(B), dim3(256), 0, g_stream, B, m->ldesc4, (const int *)nullptr, m->lja, rowflag,
-                           pbase, m->rinfo, m->ptab, m->pdesc, m->row_seg);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-    drop_tmp();
-    if (e != hipSuccess) {
-        (void)hipFree(m->ptab);
-        (void)hipFree(m->rinfo);
-        (void)hipFree(m->pdesc);
-        m->ptab = nullptr;
-        m->rinfo = nullptr;
-        m->pdesc = nullptr;
-        return fail("pattern plan: building the tables failed: %s", hipGetErrorString(e));
-    }
-    m->pat_slots = total;
-    m->device_bytes += ((size_t)total + 1024) * 2 + (size_t)m->M * 4 + (size_t)B * 8;
-    return 0;
-}
-
-// ~15 ms of the handle's own kernel ahead of the two searches (see csr_upload_impl: after an idle stretch a launch's time
-// drifts by as much as the searches look for)
-static void hll_settle(spmv_hll_dev *m) {
-    const bool will_search = (m->ptab && g_local_patterns < 0) ||
-                             (g_place_tries > 0 && (size_t)m->slots * sizeof(double) >= ((size_t)128 << 20) && m->AS);
-    if (!will_search || !m->x || !m->y) return;
-    const auto t0 = std::chrono::steady_clock::now();
-    while (std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() < 15.0) {
-        bool bad = false;
-        for (int i = 0; i < 16 && !bad; ++i) bad = hll_launch(m, SPMV_HLL_AUTO, m->x, m->y, g_stream) != 0;
-        if (bad || hipStreamSynchronize(g_stream) != hipSuccess) break;
-    }
-}
-
-static void hll_tune_patterns(spmv_hll_dev *m) {
-    if (g_local_patterns >= 0 || !m->ptab || !m->x || !m->y) return;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
-        if (e0) (void)hipEventDestroy(e0);
-        return;
-    }
-    auto measure = [&](int patterns, float &us) {
-        const int keep = g_local_patterns;
-        g_local_patterns = patterns;
-        int rc = 0;
-        for (int i = 0; i < 2 && !rc; ++i) rc = hll_launch(m, SPMV_HLL_AUTO, m->x, m->y, g_stream);
-        hipError_t e = rc ? hipErrorUnknown : hipEventRecord(e0, g_stream);
-        for (int i = 0; i < 6 && e == hipSuccess && !rc; ++i) rc = hll_launch(m, SPMV_HLL_AUTO, m->x, m->y, g_stream);
-        if (e == hipSuccess && !rc) e = hipEventRecord(e1, g_stream);
-        if (e == hipSuccess && !rc) e = hipStreamSynchronize(g_stream);
-        float ms = 0;
-        if (e == hipSuccess && !rc) e = hipEventElapsedTime(&ms, e0, e1);
-        g_local_patterns = keep;
-        us = ms * 1e3f / 6.0f;
-        return (e == hipSuccess && !rc) ? 0 : -1;
-    };
-    float with_us = 0, without_us = 0;
-    bool ok = true;
-    for (int round = 0; round < 2 && ok; ++round) {
-        float a = 0, b = 0;
-        ok = measure(1, a) == 0 && measure(0, b) == 0;
-        with_us = round ? std::min(with_us, a) : a;
-        without_us = round ? std::min(without_us, b) : b;
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    m->pat_with_us = with_us;
-    m->pat_without_us = without_us;
-    if (!ok || with_us > 0.98f * without_us) {
-        (void)hipFree(m->ptab);
-        (void)hipFree(m->rinfo);
-        (void)hipFree(m->pdesc);
-        m->ptab = nullptr;
-        m->rinfo = nullptr;
-        m->pdesc = nullptr;
-        m->device_bytes -= std::min(m->device_bytes, ((size_t)m->pat_slots + 1024) * 2 + (size_t)m->M * 4 + (size_t)m->local_blocks * 8);
-        m->pat_slots = 0;
-    }
-}
-
-// The HLL twin of csr_tune_placement (spmv_csr.hip): a slab whose AS array is large enough for its placement to
-// matter times its own kernel on a few fresh allocations of AS and keeps the fastest.
-static void hll_tune_placement(spmv_hll_dev *m) {
+// The pattern plan (tables only) and the searches of a finished handle (upload_ops.hpp).  The placement of AS where it is
+// large and streamed by the slab's own kernels (csr_tile over the slab's rows streams its own re-ordered copy).
+static void hll_upload_searches(spmv_hll_dev *m) {
+    (void)build_pattern_tables<true>(m->pat, m->local_blocks, m->M, m->slots, 8, m->ldesc4, nullptr, m->row_seg, m->lja);
+    m->device_bytes += m->pat.bytes(m->M, m->local_blocks);
     size_t bytes = 0;
-    if (g_place_tries <= 0 || (size_t)m->slots * sizeof(double) < ((size_t)128 << 20) || !m->AS) return;
-    if (hipMemPtrGetInfo(m->AS, &bytes) != hipSuccess || bytes < (size_t)m->slots * sizeof(double)) return;
-    if (m->local_blocks == 0 && m->tiles) return;  // csr_tile over the slab's rows streams its own re-ordered copy
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
-        if (e0) (void)hipEventDestroy(e0);
-        return;
+    bool place = m->AS && (size_t)m->slots * sizeof(double) >= kPlaceMinBytes && (m->local_blocks > 0 || !m->tiles);
+    if (place && (hipMemPtrGetInfo(m->AS, &bytes) != hipSuccess || bytes < (size_t)m->slots * sizeof(double))) {
+        (void)hipGetLastError();
+        place = false;
     }
-    auto measure = [&](float &us) {
-        for (int i = 0; i < 2; ++i)
-            if (hll_launch(m, SPMV_HLL_AUTO, m->x, m->y, g_stream)) return -1;
-        hipError_t e = hipEventRecord(e0, g_stream);
-        for (int i = 0; i < 6 && e == hipSuccess; ++i)
-            if (hll_launch(m, SPMV_HLL_AUTO, m->x, m->y, g_stream)) return -1;
-        if (e == hipSuccess) e = hipEventRecord(e1, g_stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-        float ms = 0;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        if (e != hipSuccess) return -1;
-        us = ms * 1e3f / 6.0f;
-        return 0;
-    };
-    double *first = m->AS, *best = m->AS;
-    float best_us = 0;
-    std::vector<double *> others;
-    int rc = measure(best_us);
-    m->place_first_us = best_us;
-    m->place_tries = 1;
-    float worst_us = best_us;
-    for (int t = 0; t < g_place_tries && !rc; ++t) {
-        double *p = nullptr;
-        if (hipMalloc((void **)&p, bytes) != hipSuccess) break;
-        others.push_back(p);
-        if (hipMemcpy(p, first, bytes, hipMemcpyDeviceToDevice) != hipSuccess) break;
-        m->AS = p;
-        float us = 0;
-        rc = measure(us);
-        if (rc) break;
-        ++m->place_tries;
-        if (us < best_us * 0.985f) {
-            best = p;
-            best_us = us;
-        }
-        worst_us = std::max(worst_us, us);
-        if (best_us < worst_us * 0.915f) break;  // both halves at their fast level: nothing better to find
-    }
-    m->AS = best;
-    m->place_best_us = best_us;
-    if (best != first) (void)hipFree(first);
-    for (double *p : others)
-        if (p != best) (void)hipFree(p);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    upload_searches(m, m->M, place ? &m->AS : nullptr, bytes,
+                    [m] { return hll_launch(m, SPMV_HLL_AUTO, m->x, m->y, g_stream); });
 }
 
 // Host-only self-check of what HLL upload precomputes (flat slab offsets, workgroup windows, the
@@ -536,89 +362,26 @@ extern "C" int spmv_hip_hll_plan_check(const HLLMatrix *hll, int total_rows, int
 
 namespace {
 
-// x-window plan of a device-resident slab, built by plan_count / plan_fill.  Returns 1 when the handle
-// now carries the plan, 0 when some window lists more than kLocalLinesMax lines (caller falls back to
+// x-window plan of a device-resident slab (upload_ops.hpp): the windows of hll_build_blocks at kPlanCap slots.  Returns 1
+// when the handle now carries the plan, 0 when some window lists more than kLocalLinesMax lines (caller falls back to
 // the host builder), -1 on a HIP error.
 int hll_plan_on_device(spmv_hll_dev *m, int total_rows, const std::vector<long long> &off, const std::vector<int> &mz) {
-    const int H = (int)mz.size();
     std::vector<int4> win;
-    hll_build_blocks(total_rows, H, off.data(), mz.data(), kPlanCap, win);
+    hll_build_blocks(total_rows, (int)mz.size(), off.data(), mz.data(), kPlanCap, win);
     const int W = (int)win.size();
-    if (W == 0) return 0;
     auto start_of = [&](int r) { return off[r / kHack] + (long long)(r % kHack) * mz[r / kHack]; };
-    std::vector<long long> seg_begin((size_t)W);
-    std::vector<int> seg_len((size_t)W), count((size_t)W);
+    std::vector<long long> begin((size_t)W);
+    std::vector<int> len((size_t)W), count((size_t)W), nl;
     for (int w = 0; w < W; ++w) {
         const int r0 = win[w].x, r1 = r0 + win[w].y - 1;
         const long long s0 = start_of(r0), end = start_of(r1) + mz[r1 / kHack];
         if (end - (s0 & ~1LL) > kPlanCap) return 0;  // a row that alone exceeds the stage: no plan
-        seg_begin[w] = s0;
-        seg_len[w] = (int)(end - s0);
+        begin[w] = s0;
+        len[w] = (int)(end - s0);
         count[w] = (int)(end - (s0 & ~1LL));
     }
-    long long *d_begin = nullptr;
-    int *d_len = nullptr, *d_n = nullptr, *d_off = nullptr;
-    int result = -1;
-    do {
-        if (upload_array(&d_begin, seg_begin.data(), seg_begin.size(), 0)) break;
-        if (upload_array(&d_len, seg_len.data(), seg_len.size(), 0)) break;
-        hipError_t e = hipMalloc((void **)&d_n, (size_t)W * sizeof(int));
-        if (e != hipSuccess) { fail("hll plan: hipMalloc failed: %s", hipGetErrorString(e)); break; }
-        hipLaunchKernelGGL((plan_count<4>), dim3(W), dim3(kBlock), 0, g_stream, W, d_begin, d_len, m->JA, d_n);
-        std::vector<int> nl((size_t)W);
-        e = hipMemcpyAsync(nl.data(), d_n, (size_t)W * sizeof(int), hipMemcpyDeviceToHost, g_stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-        if (e != hipSuccess) { fail("hll plan: count pass failed: %s", hipGetErrorString(e)); break; }
-        std::vector<int> line_off((size_t)W);
-        std::vector<int4> ldesc((size_t)W);
-        long long total = 0;
-        int widest = 0;
-        bool fits = true;
-        for (int w = 0; w < W && fits; ++w) {
-            const int n = std::max(nl[w], 1);  // a window of empty rows still stages one line
-            fits = nl[w] <= kLocalLinesMax && total + n < (1LL << 31);
-            line_off[w] = (int)total;
-            ldesc[w] = int4{(int)total, n, count[w], 0};
-            total += n;
-            widest = std::max(widest, n);
-        }
-        if (!fits) { result = 0; break; }
-        if (upload_array(&d_off, line_off.data(), line_off.size(), 0)) break;
-        const size_t S = (size_t)off[H];
-        e = hipMalloc((void **)&m->lines, ((size_t)total + kLocalLinesMax) * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void **)&m->lja, (S + kPad) * sizeof(unsigned short));
-        if (e == hipSuccess) e = hipMemsetAsync(m->lines, 0, ((size_t)total + kLocalLinesMax) * sizeof(int), g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(m->lja, 0, (S + kPad) * sizeof(unsigned short), g_stream);
-        if (e != hipSuccess) { fail("hll plan: allocation failed: %s", hipGetErrorString(e)); break; }
-        hipLaunchKernelGGL((plan_fill<4>), dim3(W), dim3(kBlock), 0, g_stream, W, d_begin, d_len, m->JA, d_off,
-                           m->lines, m->lja);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-        if (e != hipSuccess) { fail("hll plan: fill pass failed: %s", hipGetErrorString(e)); break; }
-        if (upload_array(&m->ldesc4, win.data(), win.size(), 1)) break;
-        if (upload_array(&m->ldesc, ldesc.data(), ldesc.size(), 1)) break;
-        m->local_blocks = W;
-        m->local_lines = total;
-        m->local_stage_lines = std::max(kLocalLineQuantum,
-                                        (widest + kLocalLineQuantum - 1) / kLocalLineQuantum * kLocalLineQuantum);
-        result = 1;
-    } while (0);
-    (void)hipFree(d_begin);
-    (void)hipFree(d_len);
-    (void)hipFree(d_n);
-    (void)hipFree(d_off);
-    if (result != 1) {  // leave no half-built plan behind
-        (void)hipFree(m->lines);
-        (void)hipFree(m->lja);
-        (void)hipFree(m->ldesc4);
-        (void)hipFree(m->ldesc);
-        m->lines = nullptr;
-        m->lja = nullptr;
-        m->ldesc4 = nullptr;
-        m->ldesc = nullptr;
-        m->local_blocks = 0;
-    }
-    return result;
+    return plan_on_device<4>(m, m->JA, (size_t)off.back(), win, begin, len, m->lja, m->ldesc,
+                             [&](int w, int first, int n) { return int4{first, n, count[w], 0}; }, nl);
 }
 
 }  // namespace
@@ -688,10 +451,7 @@ static int spmv_hip_hll_upload_part_body(const HLLMatrix *hll, int total_rows, i
         spmv_hip_hll_free(m);
         return -1;
     }
-    (void)hll_build_patterns(m);
-    hll_settle(m);  // (the searches below compare launch times: the card's steady state first)
-    hll_tune_patterns(m);  // (never a reason to lose the handle)
-    hll_tune_placement(m);
+    hll_upload_searches(m);
     *out = m;
     return 0;
 }
@@ -782,10 +542,7 @@ static int spmv_hip_hll_from_csr_body(const spmv_csr_dev *csr, spmv_hll_dev **ou
         spmv_hip_hll_free(m);
         return -1;
     }
-    (void)hll_build_patterns(m);
-    hll_settle(m);  // (the searches below compare launch times: the card's steady state first)
-    hll_tune_patterns(m);  // (never a reason to lose the handle)
-    hll_tune_placement(m);
+    hll_upload_searches(m);
     *out = m;
     return 0;
 }
@@ -823,9 +580,7 @@ extern "C" void spmv_hip_hll_free(spmv_hll_dev *m) {
     (void)hipFree(m->lines);
     (void)hipFree(m->lja);
     (void)hipFree(m->row_seg);
-    (void)hipFree(m->ptab);
-    (void)hipFree(m->rinfo);
-    (void)hipFree(m->pdesc);
+    m->pat.release();
     spmv_hip_csr_free(m->tiles);
     (void)hipFree(m->x);
     (void)hipFree(m->y);
@@ -863,9 +618,9 @@ extern "C" int spmv_hip_hll_info(const spmv_hll_dev *m, spmv_dev_info *out) {
     out->place_first_us = m->place_first_us;
     out->place_best_us = m->place_best_us;
     out->val_address = (unsigned long long)(uintptr_t)m->AS;
-    out->pattern_slots = m->ptab ? m->pat_slots : 0;
-    out->pattern_with_us = m->pat_with_us;
-    out->pattern_without_us = m->pat_without_us;
+    out->pattern_slots = m->pat.ptab ? m->pat.slots : 0;
+    out->pattern_with_us = m->pat.with_us;
+    out->pattern_without_us = m->pat.without_us;
     out->stream_kernel = m->local_blocks > 0 ? 1 : m->tiles ? 2 : 0;
     if (m->tiles) {
         spmv_dev_info t;
@@ -885,7 +640,7 @@ extern "C" int spmv_hip_hll_info(const spmv_hll_dev *m, spmv_dev_info *out) {
     out->local_stage_lines = m->local_stage_lines;
     out->local_lines = m->local_lines;
     if (m->local_blocks > 0)  // (a pattern plan: the tables and 4 bytes per row instead of 2 bytes per slot)
-        out->stream_bytes = m->slots * 8 + (m->ptab ? 2 * m->pat_slots + 4LL * m->M + 8LL * m->local_blocks : 2 * m->slots) +
+        out->stream_bytes = m->slots * 8 + (m->pat.ptab ? 2 * m->pat.slots + 4LL * m->M + 8LL * m->local_blocks : 2 * m->slots) +
                             4 * m->local_lines + 32LL * m->local_blocks + 12LL * m->hacks + 8LL * ((long long)m->M + m->N);
     return 0;
 }
@@ -946,16 +701,16 @@ int hll_launch(const spmv_hll_dev *m, int variant, const double *x, double *y_fu
                 const size_t llds = std::max((size_t)2048 * sizeof(double), (size_t)m->local_stage_lines * kLineBytes);
                 const bool lnt = g_local_nt < 0 ? m->slots * 10 > (128LL << 20) : g_local_nt != 0;
                 // a pattern plan: the windows' slots are rebuilt in LDS (behind the stage), lja is not read
-                const bool patterns = m->ptab && m->rinfo && m->pdesc && g_local_patterns != 0;
+                const bool patterns = m->pat.ptab && g_local_patterns != 0;
                 const size_t pat_lds = llds + ((size_t)2048 + 8) * sizeof(unsigned short);
                 if (patterns && lnt)
                     hipLaunchKernelGGL((hll_lds_local<double, true, 2048, true>), dim3(lgrid), dim3(kBlock), pat_lds, s,
                                        m->local_blocks, lchunk, m->ldesc4, m->ldesc, m->lines, m->row_seg,
-                                       m->lja, m->AS, x, y, m->pdesc, m->rinfo, m->ptab, (int)llds);
+                                       m->lja, m->AS, x, y, m->pat.pdesc, m->pat.rinfo, m->pat.ptab, (int)llds);
                 else if (patterns)
                     hipLaunchKernelGGL((hll_lds_local<double, false, 2048, true>), dim3(lgrid), dim3(kBlock), pat_lds, s,
                                        m->local_blocks, lchunk, m->ldesc4, m->ldesc, m->lines, m->row_seg,
-                                       m->lja, m->AS, x, y, m->pdesc, m->rinfo, m->ptab, (int)llds);
+                                       m->lja, m->AS, x, y, m->pat.pdesc, m->pat.rinfo, m->pat.ptab, (int)llds);
                 else if (lnt)
                     hipLaunchKernelGGL((hll_lds_local<double, true, 2048>), dim3(lgrid), dim3(kBlock), llds, s,
                                        m->local_blocks, lchunk, m->ldesc4, m->ldesc, m->lines, m->row_seg,

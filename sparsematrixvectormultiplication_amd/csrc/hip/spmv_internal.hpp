@@ -172,6 +172,43 @@ inline bool skew_cut(int nrows, int maxlen, int len) {
 namespace spmv {
 struct TileExpansion;  // tile_plan_device.hpp
 }
+// The pattern plan of an x-window plan (csr_kernels.hpp, PAT; hll_lds_local<.., PAT>): where most rows of the blocks are
+// their predecessor shifted by a constant, the kernel rebuilds the slots instead of reading the 16-bit slot stream -- from
+// one segment per block (its rows' records and its pattern groups, copied into LDS), or, for a block whose segment is
+// wider than the LDS budget, from its table.  Built and timed at upload (upload_ops.hpp); HLL has the tables only.
+struct PatternPlan {
+    unsigned short *ptab = nullptr;   // [slots + pad] the blocks' pattern tables
+    unsigned *rinfo = nullptr;        // [rows] start of the row's pattern in its block's table | shift << 16
+    int2 *pdesc = nullptr;            // [blocks] {first element in ptab (even), elements}
+    uint4 *pseg = nullptr;            // [seg_total] the segments, 16-byte units (nullptr: no block's fits)
+    int2 *sdesc = nullptr;            // [blocks] {first uint4 of the block's segment, uint4s}; {0, 0}: the table
+    long long slots = 0;              // elements of all tables
+    int widest = 0;                   // the largest table (elements)
+    long long seg_total = 0;          // uint4s of all segments
+    int seg_max = 0;                  // the widest segment kept (uint4s): the LDS the kernel adds behind the slots
+    int seg_cap = 0;                  // the widest segment the LDS budget allowed (uint4s)
+    long long table_rows = 0;         // rows of the blocks whose segment did not fit (they read rinfo, row_ptr and ptab)
+    float with_us = 0, without_us = 0;  // (auto) the kernel with / without the plan, timed at upload (tune_pattern_plan)
+
+    size_t bytes(long long rows, long long blocks) const {
+        if (!ptab) return 0;
+        return ((size_t)slots + 1024) * 2 + (size_t)rows * 4 + (size_t)blocks * 8 +
+               (pseg ? (size_t)seg_total * sizeof(uint4) + (size_t)blocks * sizeof(int2) : 0);
+    }
+    // the arrays and what describes them; seg_cap and the timings stay for info()
+    void release() {
+        for (void *p : {(void *)ptab, (void *)rinfo, (void *)pdesc, (void *)pseg, (void *)sdesc}) (void)hipFree(p);
+        ptab = nullptr;
+        rinfo = nullptr;
+        pdesc = nullptr;
+        pseg = nullptr;
+        sdesc = nullptr;
+        slots = 0;
+        seg_total = 0;
+        seg_max = 0;
+        table_rows = 0;
+    }
+};
 struct spmv_csr_dev {
     int value_bytes = 8;
     int M_local = 0, M_total = 0, N = 0, row0 = 0;
@@ -198,22 +235,8 @@ struct spmv_csr_dev {
     int2 *ldesc = nullptr;            // [local_blocks] {first line in `lines`, line count}
     int *lines = nullptr;             // x line ids, block after block, ascending inside a block
     unsigned short *lcol = nullptr;   // [nz + pad] slot of each entry in its block's staged lines
-    // the pattern plan (csr_kernels.hpp, PAT): where most rows of the blocks are their predecessor shifted by a constant,
-    // the kernel rebuilds the slots instead of reading lcol -- from one segment per block (its rows' records and its
-    // pattern groups, copied into LDS), or, for a block whose segment is wider than the LDS budget, from its table
-    unsigned short *ptab = nullptr;   // [pat_slots + pad] the blocks' pattern tables
-    unsigned *rinfo = nullptr;        // [M_local] start of the row's pattern in its block's table | shift << 16
-    int2 *pdesc = nullptr;            // [local_blocks] {first element in ptab (even), elements}
-    uint4 *pseg = nullptr;            // [pat_seg_total] the segments, 16-byte units (nullptr: no block's fits)
-    int2 *sdesc = nullptr;            // [local_blocks] {first uint4 of the block's segment, uint4s}; {0, 0}: the table
-    long long pat_slots = 0;          // elements of all tables
-    int pat_max = 0;                  // the largest table (elements)
-    long long pat_seg_total = 0;      // uint4s of all segments
-    int pat_seg_max = 0;              // the widest segment kept (uint4s): the LDS the kernel adds behind the slots
-    int pat_seg_cap = 0;              // the widest segment the LDS budget allowed (uint4s)
-    long long pat_table_rows = 0;     // rows of the blocks whose segment did not fit (they read rinfo, row_ptr and ptab)
-    float pat_with_us = 0, pat_without_us = 0;  // (auto) the kernel with / without the plan, timed at upload (csr_tune_patterns)
-    int local_blocks = 0;             // 0: no plan (not profitable / not possible)
+    PatternPlan pat;                  // the pattern plan of the blocks (the kernel then does not read lcol)
+    int local_blocks = 0;            // 0: no plan (not profitable / not possible)
     int local_stage_lines = 0;        // LDS stage: most lines any block lists, in steps of 32
     int local_cap = 2048;
     long long local_lines = 0;
@@ -275,7 +298,7 @@ struct spmv_csr_dev {
     int auto_variant = SPMV_CSR_STREAM;
     int max_row = 0;
     size_t device_bytes = 0;
-    int place_tries = 0;  // placement tuning at upload (csr_tune_placement): placements timed, first / kept time
+    int place_tries = 0;  // placement tuning at upload (tune_placement): placements timed, first / kept time
     float place_first_us = 0, place_best_us = 0;
     // arrays moved to a chosen address (spmv_hip_csr_relocate): the field points INTO `raw`, which is what gets freed
     // (vmm: the memory came from hipMemCreate + hipMemAddressReserve + hipMemMap, `raw` is the reserved range)
@@ -303,12 +326,7 @@ struct spmv_hll_dev {
     int *lines = nullptr;
     unsigned short *lja = nullptr;
     unsigned *row_seg = nullptr;   // [M] a row's (first slot in its window | slots << 16)
-    // the pattern plan of the windows (round 3; see spmv_csr_dev): hll_lds_local<.., PAT> does not read lja
-    unsigned short *ptab = nullptr;
-    unsigned *rinfo = nullptr;
-    int2 *pdesc = nullptr;
-    long long pat_slots = 0;
-    float pat_with_us = 0, pat_without_us = 0;
+    PatternPlan pat;               // the pattern plan of the windows (tables only): hll_lds_local<.., PAT> does not read lja
     spmv_csr_dev *tiles = nullptr; // csr_tile over the slab's rows (padding slots included), when the slab gets no x-window plan
     int local_blocks = 0, local_stage_lines = 0;
     long long local_lines = 0;
@@ -317,7 +335,7 @@ struct spmv_hll_dev {
     int lanes_per_row = 8;
     int auto_variant = SPMV_HLL_LDS;
     size_t device_bytes = 0;
-    int place_tries = 0;  // placement tuning at upload (hll_tune_placement)
+    int place_tries = 0;  // placement tuning at upload (tune_placement)
     float place_first_us = 0, place_best_us = 0;
 };
 

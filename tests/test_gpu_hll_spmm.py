@@ -346,6 +346,10 @@ def test_hll_spmm_full_size_nlpkkt_like(gpu, oracle):
     X = rng.uniform(-1, 1, (M, 8))
     with sp.CsrDevice(M, M, rp, col, val) as cdev:
         with sp.HllDevice.from_csr_device(cdev) as dev:
+            # the slab's AS is above 128 MiB: upload searched its placement, and the handle runs after the search
+            info = dev.info()
+            assert info["place_tries"] >= 1 and 0 < info["place_best_us"] <= info["place_first_us"], info
+            dev.run()
             Y = dev.spmm(X)
     check_columns(oracle, Y, X, rp, col, val, "nlpkkt-like k=8")
 

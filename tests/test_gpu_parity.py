@@ -331,6 +331,10 @@ def test_full_size_properties_nlpkkt_like(gpu, oracle):
     rng = np.random.default_rng(4)
     x1, x2 = rng.uniform(-1, 1, M), rng.uniform(-1, 1, M)
     with sp.CsrDevice(M, M, row_ptr, col, val) as dev:
+        # the value array is above 128 MiB: upload searched its placement, and the handle runs after the search
+        info = dev.info()
+        assert info["place_tries"] >= 1 and 0 < info["place_best_us"] <= info["place_first_us"], info
+        dev.run()
         y1 = dev.spmv(x1, sp.CSR_STREAM)
         y2 = dev.spmv(x2, sp.CSR_STREAM)
         y12 = dev.spmv(2.0 * x1 - 3.0 * x2, sp.CSR_STREAM)

@@ -181,3 +181,29 @@ def test_hll_patterns_unchanged(gpu, oracle, forced):
         assert y.tobytes() == y0.tobytes()
         ref = oracle.csr_serial(rp, col, val, x)
         assert np.max(np.abs(y - ref)) <= 1e-10 * np.max(np.abs(ref))
+
+
+def test_device_bytes_count_the_pattern_plan(gpu, forced):
+    """device_bytes of an upload with a pattern plan against the same upload without one: HLL grows by exactly the tables,
+    rinfo and pdesc; CSR by at least that (its segments come on top)."""
+    rng = np.random.default_rng(2032)
+    M, rp, col, val = stencil_1d(40000, range(-9, 10), rng, np.float64)
+    hll = sp.convert_to_hll(sp.PreMatrix.from_arrays(M, M, np.repeat(np.arange(M, dtype=np.int32), np.diff(rp)), col, val))
+    uploads = {"csr fp64": lambda: sp.CsrDevice(M, M, rp, col, val),
+               "csr fp32": lambda: sp.CsrDevice(M, M, rp, col, val.astype(np.float32)),
+               "hll": lambda: sp.HllDevice(hll)}
+    for name, upload in uploads.items():
+        infos = []
+        for p in (1, 0):
+            set_tuning("local_patterns", p)
+            with upload() as dev:
+                infos.append(dev.info())
+        set_tuning("local_patterns", 1)
+        with_plan, without = infos
+        assert with_plan["local_blocks"] > 0 and with_plan["pattern_slots"] > 0 and without["pattern_slots"] == 0, name
+        tables = 2 * (with_plan["pattern_slots"] + 1024) + 4 * M + 8 * with_plan["local_blocks"]
+        grew = with_plan["device_bytes"] - without["device_bytes"]
+        if name == "hll":
+            assert grew == tables, (name, grew, tables)
+        else:
+            assert grew >= tables, (name, grew, tables)
