@@ -518,6 +518,53 @@ int spmv_hip_csr_bicgstab(spmv_csr_dev *m, int variant, int iters, double tol, c
 enum { SPMV_CGLS_RAN_ALL = 0, SPMV_CGLS_CONVERGED = 1, SPMV_CGLS_BREAKDOWN = 2 };
 int spmv_hip_csr_cgls(spmv_csr_dev *m, spmv_csr_dev *mt, int iters, double tol, double damp, const void *b_host,
                       void *x_host, double *ss_hist, double *rr_hist, int *info, float *ms_total);
+/* Preconditioners of a square CSR handle, built on the device: M = the diagonal (JACOBI, block = 1) or the block
+ * diagonal of `block` x `block` blocks (BLOCK_JACOBI, block in [1, 32]) of the handle's own rows [row0, row0 + M_local).
+ * Blocks start at row0; the last one may be shorter.  Entries that repeat a (row, column) pair are added in entry order
+ * (block = 1: the diagonal is their left-to-right fp64 sum).  Each block is inverted in fp64 (Gauss-Jordan with partial
+ * pivoting, the first largest |pivot| wins; JACOBI: 1.0 / d, correctly rounded) and stored once rounded to the
+ * handle's dtype.  BLOCK_JACOBI with block = 1 gives JACOBI's bytes.  P owns its arrays: P and the handle may be freed
+ * in either order.  Two builds give the same bytes.
+ * -1 (*out stays NULL, the HIP error state stays clean): a missing, zero or non-finite diagonal, a zero or non-finite
+ * pivot or inverse (the message names the first bad row or block), a bad kind or block, a non-square matrix, a
+ * tiles-only handle.
+ *   spmv_hip_precond_info      info[5] = kind, block, rows, row0, value_bytes
+ *   spmv_hip_precond_apply     z = M^-1 r on P's rows: r_host, z_host hold `rows` values (element i = row row0 + i); syncs
+ *   spmv_hip_precond_apply_on  the same on device vectors, asynchronous on `stream` (NULL = the library's)
+ * The apply accumulates each row's sum in double and rounds it once. */
+typedef struct spmv_precond spmv_precond;
+enum { SPMV_PRECOND_JACOBI = 1, SPMV_PRECOND_BLOCK_JACOBI = 2 };
+int spmv_hip_csr_precond_build(const spmv_csr_dev *m, int kind, int block, spmv_precond **out);
+void spmv_hip_precond_free(spmv_precond *P);
+int spmv_hip_precond_info(const spmv_precond *P, int *info);
+int spmv_hip_precond_apply(const spmv_precond *P, const void *r_host, void *z_host);
+int spmv_hip_precond_apply_on(const spmv_precond *P, const void *d_r, void *d_z, void *stream);
+/* Preconditioned CG for a symmetric positive definite A and M, x0 = 0 (P = NULL: M = I, z is r itself):
+ *   r = b, z = M^-1 r, p = z, rz = r.z, rr0 = r.r
+ *   each step: q = A p, alpha = rz / p.q, x += alpha p, r -= alpha q, z = M^-1 r, rz' = r.z, rr = r.r,
+ *              stop (CONVERGED) if rr <= tol^2 rr0, beta = rz' / rz, p = z + beta p
+ * The product, the communicator, the bounds and the all-gatherv of p are those of spmv_hip_csr_cg (no halo variant).
+ * Jacobi is fused into the x / r update with both dots; a block-Jacobi apply is a pass of its own that makes the dots.
+ * P = NULL, or Jacobi on a matrix whose diagonal is exactly 1, with tol = 0 and no breakdown gives spmv_hip_csr_cg's
+ * x and rr_hist bit for bit.
+ * Breakdown: p.q <= 0, rz' <= 0 while rr > 0, or any non-finite scalar (A or M not SPD); x stays at the last full
+ * iterate, no NaN is written into it.  rr0 = 0: converged at step 0 with x = 0.  After a stop x no longer changes and
+ * both histories repeat their last value.  tol = 0: exactly `iters` steps, no host synchronisation; tol > 0: the host
+ * reads one device word every 16 steps.
+ * Out (all optional): x_host M_total values; rr_hist, rz_hist [iters + 1] r.r and r.z before step 1 and after every
+ * step; info[2] = {steps, status (SPMV_PCG_*)}; *ms_total device time of the loop.
+ * -1: as spmv_hip_csr_bicgstab, and a P whose rows, row0 or dtype differ from the handle's. */
+enum { SPMV_PCG_RAN_ALL = 0, SPMV_PCG_CONVERGED = 1, SPMV_PCG_BREAKDOWN = 2 };
+int spmv_hip_csr_pcg(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, double tol, const int *bounds,
+                     const void *b_host, void *x_host, double *rr_hist, double *rz_hist, int *info, float *ms_total);
+/* Right-preconditioned BiCGSTAB: the loop of spmv_hip_csr_bicgstab on A M^-1 with x = M^-1 y, so r stays the true
+ * residual and tol, the half step, the breakdown rules, rr_hist and info mean what they mean there:
+ *   p^ = M^-1 p, v = A p^, ..., s^ = M^-1 s, t = A s^, x += alpha p^ + omega s^ (a half step: x += alpha p^)
+ * With a communicator p^ and s^ (the products' inputs) are all-gathered.  Jacobi is fused into the s and p updates.
+ * P = NULL gives spmv_hip_csr_bicgstab's bits.  -1: as spmv_hip_csr_bicgstab, and a P that does not fit the handle. */
+int spmv_hip_csr_pbicgstab(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, double tol,
+                           const int *bounds, const void *b_host, void *x_host, double *rr_hist, int *info,
+                           float *ms_total);
 int spmv_hip_csr_split_interior(spmv_csr_dev *m, long long *counts);
 /* N4 overlap below block granularity (round 3).  On a KKT-coupled cut every block also lists lines of the coupling block,
  * which another rank owns: no interior BLOCKS -- but 13 of a row's 28 entries have their column in the rank's own range.

@@ -14,6 +14,8 @@ from .host import (HACK_SIZE, ITERATION_SKIP, CsrHost, HllHost, PreMatrix,  # no
                    read_matrix_market, csr_plan_check, csr_tile_plan_check, csr_tile_auto_plan, hll_plan_check, partition_hacks, hack_bounds_to_rows, save_csr_binary, load_csr_binary, load_csr_cached)
 from .device import (BICG_BREAKDOWN_OMEGA, BICG_BREAKDOWN_RHO, BICG_CONVERGED, BICG_RAN_ALL,  # noqa: F401
                      CGLS_BREAKDOWN, CGLS_CONVERGED, CGLS_RAN_ALL,  # noqa: F401
+                     PCG_BREAKDOWN, PCG_CONVERGED, PCG_RAN_ALL, PRECOND_BLOCK_JACOBI, PRECOND_JACOBI,  # noqa: F401
+                     Preconditioner,  # noqa: F401
                      CSR_AUTO, CSR_STREAM, CSR_SUBWAVE, CSR_THREAD_ROW, CSR_VARIANTS,  # noqa: F401
                      CSR_WAVE_ROW, HLL_AUTO, HLL_LDS, HLL_SUBWAVE, HLL_THREAD_ROW, HLL_VARIANTS,
                      CsrDevice, HllDevice, SpmvHipError, device_count, device_name, flush_cache,

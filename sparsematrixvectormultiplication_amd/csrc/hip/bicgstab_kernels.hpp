@@ -11,6 +11,9 @@
 //   bcg_start / bcg_set_alpha / bcg_check_s / bcg_set_omega / bcg_set_beta   one thread: the scalars, the stop and
 //                    breakdown rules and the history
 //
+// Right preconditioning (spmv_hip_csr_pbicgstab) swaps three of them: bcg_jac_update_s (also s^ = D^-1 s; 5 values
+// per row), bcg_pre_update_x_r (x moves along p^ and s^; 8) and bcg_jac_update_p (also p^ = D^-1 p; 6).
+//
 // Every vector is indexed by global row; a kernel covers the rows [lo, hi) of this rank in pieces of V = 16 / sizeof(T)
 // rows (piece_load / piece_store, PieceLane: solver_ops.hpp); the rows outside [lo, hi) are neither read nor written.
 // The partials are folded and added over the ranks by solver_reduce, in the order of solver_ops.hpp.  The grid
@@ -162,6 +165,113 @@ __global__ __launch_bounds__(kBlock) void bcg_update_p(long long lo, long long h
 #pragma unroll
         for (int j = 0; j < V; ++j) pv[j] = (T)((double)rv[j] + beta * ((double)pv[j] - omega * (double)vv[j]));
         piece_store<T, V>(p, i0, lo, hi, pv);
+    }
+}
+
+// ---- right preconditioning (spmv_hip_csr_pbicgstab): the products' inputs are p^ = M^-1 p and s^ = M^-1 s, and x
+// moves along them.  Jacobi (dinv = D^-1 by global row) is fused into the s and p updates: one more array read and
+// the hat vector written beside.  A block-Jacobi apply is a pc_apply pass after bcg_update_s / bcg_update_p.
+
+// s = r - alpha v, s^ = D^-1 s on [lo, hi), partials of s.s
+template <typename T, int V>
+__global__ __launch_bounds__(kBlock) void bcg_jac_update_s(long long lo, long long hi, const int *__restrict__ flags,
+                                                           const double *__restrict__ sc, const T *__restrict__ r,
+                                                           const T *__restrict__ v, const T *__restrict__ dinv,
+                                                           T *__restrict__ s, T *__restrict__ sh,
+                                                           double *__restrict__ part) {
+    if (flags[kBcgState] != kBcgRun) return;
+    const double alpha = sc[kBcgAlpha];
+    double acc[1] = {0.0};
+    for (PieceLane l(lo, hi, V); l.q < l.end; l.q += l.stride) {
+        const long long i0 = l.q * V;
+        T rv[V], vv[V], dv[V], sv[V], hv[V];
+        piece_load<T, V>(r, i0, lo, hi, rv);
+        piece_load<T, V>(v, i0, lo, hi, vv);
+        piece_load<T, V>(dinv, i0, lo, hi, dv);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            sv[j] = (T)((double)rv[j] - alpha * (double)vv[j]);
+            hv[j] = (T)((double)dv[j] * (double)sv[j]);
+            acc[0] += (double)sv[j] * (double)sv[j];
+        }
+        piece_store<T, V>(s, i0, lo, hi, sv);
+        piece_store<T, V>(sh, i0, lo, hi, hv);
+    }
+    block_partials<1>(acc, part);
+}
+
+// RUN: x += alpha p^ + omega s^, r = s - omega t on [lo, hi), partials of r^.r and r.r.  HALF: x += alpha p^, r = s.
+template <typename T, int V>
+__global__ __launch_bounds__(kBlock) void bcg_pre_update_x_r(long long lo, long long hi, const int *__restrict__ flags,
+                                                             const double *__restrict__ sc, const T *__restrict__ rhat,
+                                                             const T *__restrict__ ph, const T *__restrict__ sh,
+                                                             const T *__restrict__ s, const T *__restrict__ t,
+                                                             T *__restrict__ x, T *__restrict__ r,
+                                                             double *__restrict__ part) {
+    const int state = flags[kBcgState];
+    if (state == kBcgStop) return;
+    const double alpha = sc[kBcgAlpha];
+    double acc[2] = {0.0, 0.0};
+    if (state == kBcgHalfStep) {
+        for (PieceLane l(lo, hi, V); l.q < l.end; l.q += l.stride) {
+            const long long i0 = l.q * V;
+            T xv[V], pv[V], sv[V];
+            piece_load<T, V>(x, i0, lo, hi, xv);
+            piece_load<T, V>(ph, i0, lo, hi, pv);
+            piece_load<T, V>(s, i0, lo, hi, sv);
+#pragma unroll
+            for (int j = 0; j < V; ++j) xv[j] = (T)((double)xv[j] + alpha * (double)pv[j]);
+            piece_store<T, V>(x, i0, lo, hi, xv);
+            piece_store<T, V>(r, i0, lo, hi, sv);
+        }
+    } else {
+        const double omega = sc[kBcgOmega];
+        for (PieceLane l(lo, hi, V); l.q < l.end; l.q += l.stride) {
+            const long long i0 = l.q * V;
+            T xv[V], pv[V], shv[V], sv[V], tv[V], hv[V];
+            piece_load<T, V>(x, i0, lo, hi, xv);
+            piece_load<T, V>(ph, i0, lo, hi, pv);
+            piece_load<T, V>(sh, i0, lo, hi, shv);
+            piece_load<T, V>(s, i0, lo, hi, sv);
+            piece_load<T, V>(t, i0, lo, hi, tv);
+            piece_load<T, V>(rhat, i0, lo, hi, hv);
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                xv[j] = (T)((double)xv[j] + (alpha * (double)pv[j] + omega * (double)shv[j]));
+                const T rn = (T)((double)sv[j] - omega * (double)tv[j]);
+                sv[j] = rn;  // the new r
+                acc[0] += (double)hv[j] * (double)rn;
+                acc[1] += (double)rn * (double)rn;
+            }
+            piece_store<T, V>(x, i0, lo, hi, xv);
+            piece_store<T, V>(r, i0, lo, hi, sv);
+        }
+    }
+    block_partials<2>(acc, part);
+}
+
+// p = r + beta (p - omega v), p^ = D^-1 p on [lo, hi)
+template <typename T, int V>
+__global__ __launch_bounds__(kBlock) void bcg_jac_update_p(long long lo, long long hi, const int *__restrict__ flags,
+                                                           const double *__restrict__ sc, const T *__restrict__ r,
+                                                           const T *__restrict__ v, const T *__restrict__ dinv,
+                                                           T *__restrict__ p, T *__restrict__ ph) {
+    if (flags[kBcgState] != kBcgRun) return;
+    const double beta = sc[kBcgBeta], omega = sc[kBcgOmega];
+    for (PieceLane l(lo, hi, V); l.q < l.end; l.q += l.stride) {
+        const long long i0 = l.q * V;
+        T rv[V], vv[V], pv[V], dv[V], hv[V];
+        piece_load<T, V>(r, i0, lo, hi, rv);
+        piece_load<T, V>(v, i0, lo, hi, vv);
+        piece_load<T, V>(p, i0, lo, hi, pv);
+        piece_load<T, V>(dinv, i0, lo, hi, dv);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            pv[j] = (T)((double)rv[j] + beta * ((double)pv[j] - omega * (double)vv[j]));
+            hv[j] = (T)((double)dv[j] * (double)pv[j]);
+        }
+        piece_store<T, V>(p, i0, lo, hi, pv);
+        piece_store<T, V>(ph, i0, lo, hi, hv);
     }
 }
 

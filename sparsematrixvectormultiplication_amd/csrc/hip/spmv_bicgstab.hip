@@ -11,22 +11,30 @@
 // state never leave the device.  With a communicator s and p are all-gathered with the row bounds after they are made
 // (two exchanges per step) and every reduction is all-gathered and added in rank order, as csr_cg does: every rank
 // holds the same bits and stops at the same step.
+//
+// spmv_hip_csr_pbicgstab runs the same loop right-preconditioned: p^ = M^-1 p and s^ = M^-1 s are the products' inputs
+// (library-owned, all-gathered in place of p and s), x moves along them, and r stays the true residual.  Jacobi is
+// fused into the s and p updates (bcg_jac_update_s / _p, with D^-1 copied to global row indexing so the 16-byte pieces
+// line up); a block-Jacobi apply is a pc_apply pass after bcg_update_s / bcg_update_p.  P = NULL takes the
+// unpreconditioned path: exactly csr_bicgstab's launches.
 #include "spmv_internal.hpp"
 
 #include "bicgstab_kernels.hpp"
+#include "precond_kernels.hpp"
 
 namespace {
 
 struct BcgBuffers {
     void *p, *s, *v, *t, *x, *r, *rhat;
+    void *ph, *sh, *dinv;  // with a preconditioner: M^-1 p, M^-1 s (the products' inputs), Jacobi's D^-1 by global row
     double *sc, *part, *gath, *hist;
     int *flags;
 };
 
 // the loop; *steps_run = the steps launched (< iters when tol > 0 and the solve stopped)
 template <typename T>
-int bcg_run(spmv_csr_dev *m, int variant, int iters, double tol, const int *bounds, const BcgBuffers &b,
-            int *steps_run) {
+int bcg_run(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, double tol, const int *bounds,
+            const BcgBuffers &b, int *steps_run) {
     constexpr int V = 16 / sizeof(T);
     const long long lo = m->row0, hi = (long long)m->row0 + m->M_local;
     const long long pieces = (hi + V - 1) / V - lo / V;
@@ -43,29 +51,51 @@ int bcg_run(spmv_csr_dev *m, int variant, int iters, double tol, const int *boun
     hipLaunchKernelGGL((bcg_dot2<T, V>), g, blk, 0, g_stream, lo, hi, fl, (const T *)r, (const T *)rhat, b.part);
     if (reduce(2, kBcgRho)) return -1;
     hipLaunchKernelGGL(bcg_start, dim3(1), dim3(1), 0, g_stream, b.sc, b.flags, b.hist, iters);
-    if (g_comm && spmv_hip_comm_allgatherv(p, bounds, m->value_bytes, g_stream)) return -1;
+    // with P: the products read p^ and s^; Jacobi fuses into the updates, a block apply follows them
+    const bool jac = P && P->block == 1, blockwise = P && P->block > 1;
+    T *ph = P ? (T *)b.ph : p, *sh = P ? (T *)b.sh : s;
+    const T *dinv = (const T *)b.dinv;
+    const long long own = lo;  // P's local row 0 in the global vectors
+    if (P) precond_launch<T, false>(P, p + own, ph + own, fl, nullptr, 0, g_stream);  // p^ = M^-1 b
+    if (g_comm && spmv_hip_comm_allgatherv(ph, bounds, m->value_bytes, g_stream)) return -1;
     *steps_run = iters;
     for (int k = 1; k <= iters; ++k) {
-        if (csr_launch_any(m, variant, p, v, g_stream)) return -1;  // v = A p on this rank's rows
+        if (csr_launch_any(m, variant, ph, v, g_stream)) return -1;  // v = A p (A p^) on this rank's rows
         hipLaunchKernelGGL((bcg_dot<T, V>), g, blk, 0, g_stream, lo, hi, fl, (const T *)rhat, (const T *)v, b.part);
         if (reduce(1, kBcgRv)) return -1;
         hipLaunchKernelGGL(bcg_set_alpha, dim3(1), dim3(1), 0, g_stream, b.sc, b.flags, k);
-        hipLaunchKernelGGL((bcg_update_s<T, V>), g, blk, 0, g_stream, lo, hi, fl, (const double *)b.sc, (const T *)r,
-                           (const T *)v, s, b.part);
+        if (jac) {
+            hipLaunchKernelGGL((bcg_jac_update_s<T, V>), g, blk, 0, g_stream, lo, hi, fl, (const double *)b.sc,
+                               (const T *)r, (const T *)v, dinv, s, sh, b.part);
+        } else {
+            hipLaunchKernelGGL((bcg_update_s<T, V>), g, blk, 0, g_stream, lo, hi, fl, (const double *)b.sc,
+                               (const T *)r, (const T *)v, s, b.part);
+            if (blockwise) precond_launch<T, false>(P, s + own, sh + own, fl, nullptr, 0, g_stream);
+        }
         if (reduce(1, kBcgSs)) return -1;
         hipLaunchKernelGGL(bcg_check_s, dim3(1), dim3(1), 0, g_stream, b.sc, b.flags, k, tol2);
-        if (g_comm && spmv_hip_comm_allgatherv(s, bounds, m->value_bytes, g_stream)) return -1;
-        if (csr_launch_any(m, variant, s, t, g_stream)) return -1;  // t = A s
+        if (g_comm && spmv_hip_comm_allgatherv(sh, bounds, m->value_bytes, g_stream)) return -1;
+        if (csr_launch_any(m, variant, sh, t, g_stream)) return -1;  // t = A s (A s^)
         hipLaunchKernelGGL((bcg_dot2<T, V>), g, blk, 0, g_stream, lo, hi, fl, (const T *)t, (const T *)s, b.part);
         if (reduce(2, kBcgTs)) return -1;
         hipLaunchKernelGGL(bcg_set_omega, dim3(1), dim3(1), 0, g_stream, b.sc, b.flags, k);
-        hipLaunchKernelGGL((bcg_update_x_r<T, V>), g, blk, 0, g_stream, lo, hi, fl, (const double *)b.sc,
-                           (const T *)rhat, (const T *)p, (const T *)s, (const T *)t, x, r, b.part);
+        if (P)
+            hipLaunchKernelGGL((bcg_pre_update_x_r<T, V>), g, blk, 0, g_stream, lo, hi, fl, (const double *)b.sc,
+                               (const T *)rhat, (const T *)ph, (const T *)sh, (const T *)s, (const T *)t, x, r, b.part);
+        else
+            hipLaunchKernelGGL((bcg_update_x_r<T, V>), g, blk, 0, g_stream, lo, hi, fl, (const double *)b.sc,
+                               (const T *)rhat, (const T *)p, (const T *)s, (const T *)t, x, r, b.part);
         if (reduce(2, kBcgRhoNew)) return -1;
         hipLaunchKernelGGL(bcg_set_beta, dim3(1), dim3(1), 0, g_stream, b.sc, b.flags, b.hist, k, tol2);
-        hipLaunchKernelGGL((bcg_update_p<T, V>), g, blk, 0, g_stream, lo, hi, fl, (const double *)b.sc, (const T *)r,
-                           (const T *)v, p);
-        if (g_comm && spmv_hip_comm_allgatherv(p, bounds, m->value_bytes, g_stream)) return -1;
+        if (jac) {
+            hipLaunchKernelGGL((bcg_jac_update_p<T, V>), g, blk, 0, g_stream, lo, hi, fl, (const double *)b.sc,
+                               (const T *)r, (const T *)v, dinv, p, ph);
+        } else {
+            hipLaunchKernelGGL((bcg_update_p<T, V>), g, blk, 0, g_stream, lo, hi, fl, (const double *)b.sc,
+                               (const T *)r, (const T *)v, p);
+            if (blockwise) precond_launch<T, false>(P, p + own, ph + own, fl, nullptr, 0, g_stream);
+        }
+        if (g_comm && spmv_hip_comm_allgatherv(ph, bounds, m->value_bytes, g_stream)) return -1;
         bool stop = false;
         if (solver_poll(k, iters, tol, b.flags + kBcgState, kBcgStop, &stop)) return -1;
         if (stop) {
@@ -78,8 +108,8 @@ int bcg_run(spmv_csr_dev *m, int variant, int iters, double tol, const int *boun
 }
 
 template <typename T>
-int bcg_body(spmv_csr_dev *m, int variant, int iters, double tol, const int *bounds, const void *b_host, void *x_host,
-             double *rr_hist, int *info, float *ms_total) {
+int bcg_body(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, double tol, const int *bounds,
+             const void *b_host, void *x_host, double *rr_hist, int *info, float *ms_total) {
     const size_t vb = sizeof(T), n_all = (size_t)m->M_total, n_own = (size_t)m->M_local;
     SolverScope scope;
     // p, s: SpMV inputs, read in whole 128-byte lines by the x-window kernels; the rest: whole 16-byte pieces
@@ -98,9 +128,17 @@ int bcg_body(spmv_csr_dev *m, int variant, int iters, double tol, const int *bou
     b.gath = scope.alloc<double>((size_t)kMaxRanks * 2 * sizeof(double));
     b.hist = scope.alloc<double>(((size_t)iters + 1) * sizeof(double));
     b.flags = scope.alloc<int>(kBcgFlagWords * sizeof(int));
+    b.ph = b.sh = b.dinv = nullptr;
+    if (P) {
+        b.ph = scope.alloc(in_bytes);
+        b.sh = scope.alloc(in_bytes);
+        if (P->block == 1) b.dinv = scope.alloc(vec_bytes);
+    }
     // r = r^ = p = b on this rank's rows (the rest of p arrives by the all-gatherv)
     const size_t own_off = (size_t)m->row0 * vb, own_bytes = n_own * vb;
     hipError_t e = scope.err;
+    if (e == hipSuccess && b.dinv && n_own)  // D^-1 by global row
+        e = hipMemcpyAsync((char *)b.dinv + own_off, P->inv, own_bytes, hipMemcpyDeviceToDevice, g_stream);
     if (e == hipSuccess && n_own)
         e = hipMemcpyAsync((char *)b.r + own_off, (const char *)b_host + own_off, own_bytes, hipMemcpyHostToDevice,
                            g_stream);
@@ -111,7 +149,7 @@ int bcg_body(spmv_csr_dev *m, int variant, int iters, double tol, const int *bou
     if (e == hipSuccess) e = hipEventRecord(scope.e0, g_stream);
     if (e != hipSuccess) return fail("csr_bicgstab: setup failed: %s", hipGetErrorString(e));
     int steps_run = 0;
-    if (bcg_run<T>(m, variant, iters, tol, bounds, b, &steps_run)) return -1;
+    if (bcg_run<T>(m, P, variant, iters, tol, bounds, b, &steps_run)) return -1;
     e = hipEventRecord(scope.e1, g_stream);
     // the solution: every rank holds its rows; with a communicator all rows everywhere
     if (e == hipSuccess && g_comm && x_host && spmv_hip_comm_allgatherv(b.x, bounds, m->value_bytes, g_stream)) return -1;
@@ -132,23 +170,36 @@ int bcg_body(spmv_csr_dev *m, int variant, int iters, double tol, const int *bou
     return 0;
 }
 
+int bcg_entry(const char *what, spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, double tol,
+              const int *bounds, const void *b_host, void *x_host, double *rr_hist, int *info, float *ms_total) {
+    if (need_device()) return -1;
+    int rc = 0;
+    if (!m || !b_host) rc = fail("%s: bad arguments", what);
+    else if (iters < 0) rc = fail("%s: iters = %d, must be >= 0", what, iters);
+    else if (!(tol >= 0) || !std::isfinite(tol)) rc = fail("%s: tol = %g, must be finite and >= 0", what, tol);
+    else if (m->M_total != m->N) rc = fail("%s: needs a square matrix (%d x %d)", what, m->M_total, m->N);
+    else if (g_comm && !bounds) rc = fail("%s: a communicator exists, the row bounds are required", what);
+    else if (!g_comm && (m->row0 != 0 || m->M_local != m->M_total))
+        rc = fail("%s: a handle of rows [%d, %d) needs a communicator", what, m->row0, m->row0 + m->M_local);
+    else if (g_comm_size > kMaxRanks) rc = fail("%s: more than %d ranks", what, kMaxRanks);
+    else if (P) rc = precond_matches(m, P, what);
+    if (rc) return rc;
+    return guarded(what, [&] {
+        return m->value_bytes == 8
+                   ? bcg_body<double>(m, P, variant, iters, tol, bounds, b_host, x_host, rr_hist, info, ms_total)
+                   : bcg_body<float>(m, P, variant, iters, tol, bounds, b_host, x_host, rr_hist, info, ms_total);
+    });
+}
+
 }  // namespace
 
 extern "C" int spmv_hip_csr_bicgstab(spmv_csr_dev *m, int variant, int iters, double tol, const int *bounds,
                                      const void *b_host, void *x_host, double *rr_hist, int *info, float *ms_total) {
-    if (need_device()) return -1;
-    int rc = 0;
-    if (!m || !b_host) rc = fail("csr_bicgstab: bad arguments");
-    else if (iters < 0) rc = fail("csr_bicgstab: iters = %d, must be >= 0", iters);
-    else if (!(tol >= 0) || !std::isfinite(tol)) rc = fail("csr_bicgstab: tol = %g, must be finite and >= 0", tol);
-    else if (m->M_total != m->N) rc = fail("csr_bicgstab: needs a square matrix (%d x %d)", m->M_total, m->N);
-    else if (g_comm && !bounds) rc = fail("csr_bicgstab: a communicator exists, the row bounds are required");
-    else if (!g_comm && (m->row0 != 0 || m->M_local != m->M_total))
-        rc = fail("csr_bicgstab: a handle of rows [%d, %d) needs a communicator", m->row0, m->row0 + m->M_local);
-    else if (g_comm_size > kMaxRanks) rc = fail("csr_bicgstab: more than %d ranks", kMaxRanks);
-    if (rc) return rc;
-    return guarded("csr_bicgstab", [&] {
-        return m->value_bytes == 8 ? bcg_body<double>(m, variant, iters, tol, bounds, b_host, x_host, rr_hist, info, ms_total)
-                                   : bcg_body<float>(m, variant, iters, tol, bounds, b_host, x_host, rr_hist, info, ms_total);
-    });
+    return bcg_entry("csr_bicgstab", m, nullptr, variant, iters, tol, bounds, b_host, x_host, rr_hist, info, ms_total);
+}
+
+extern "C" int spmv_hip_csr_pbicgstab(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, double tol,
+                                      const int *bounds, const void *b_host, void *x_host, double *rr_hist, int *info,
+                                      float *ms_total) {
+    return bcg_entry("csr_pbicgstab", m, P, variant, iters, tol, bounds, b_host, x_host, rr_hist, info, ms_total);
 }

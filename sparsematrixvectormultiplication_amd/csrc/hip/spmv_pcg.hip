@@ -1,0 +1,304 @@
+// spmv_pcg.hip -- spmv_hip_csr_pcg: preconditioned conjugate gradients on a CSR handle, entirely on the device
+// (include/spmv_hip.h).
+//
+//     r = b; z = M^-1 r; p = z; rz = r.z; rr0 = r.r
+//     per step:  q = A p; alpha = rz / p.q; x += alpha p; r -= alpha q; z = M^-1 r; rz' = r.z; rr = r.r
+//                (rr <= tol^2 rr0: stop); beta = rz' / rz; p = z + beta p
+//
+// The layout and the walk are csr_cg's: p is the handle's x (all-gathered with the bounds when a communicator exists),
+// q its y, x / r / z hold this rank's rows at local index, the lanes walk single rows (PieceLane with V = 1) on
+// csr_cg's grid, and the dots fold as csr_cg's do.  That is what makes P = NULL (z is r) and Jacobi with a unit
+// diagonal give csr_cg's bits.  The modes of the x / r update:
+//
+//   NONE    x += alpha p, r -= alpha q, partials of r.r twice (z is r)                    6 values moved per row
+//   JACOBI  the same and z = D^-1 r (one more read, one more write), partials of r.r, r.z  8
+//   BLOCK   x += alpha p, r -= alpha q (6), then pc_apply: z = M^-1 r with r.r and r.z    b + 2 more (L2 serves r's
+//           repeats inside a block)
+//
+// pcg_dot (p.q, 2 values) and pcg_update_p (p = z + beta p, 3) complete the step: fp64 Jacobi PCG moves 13 values =
+// 104 B per row against csr_cg's 11 (88 B).  The scalars and the stop state never leave the device; after a stop the
+// vector kernels return before they write, so a stopped solve can go on being launched with x untouched (tol = 0).
+#include "spmv_internal.hpp"
+
+#include "precond_kernels.hpp"
+
+namespace {
+
+// the scalar slots (doubles); two-value reductions land in adjacent slots: (Rr, Rz), (RrNew, RzNew)
+constexpr int kPcgRr = 0, kPcgRz = 1, kPcgPq = 2, kPcgRrNew = 3, kPcgRzNew = 4, kPcgAlpha = 5, kPcgBeta = 6,
+              kPcgRr0 = 7, kPcgLastRr = 8, kPcgLastRz = 9, kPcgLocal = 10, kPcgSlots = 16;
+// the int words; the state word is word 0 (pc_apply reads it there) and RUN is 0
+constexpr int kPcgState = 0, kPcgSteps = 1, kPcgStatus = 2, kPcgFlagWords = 4;
+constexpr int kPcgRun = 0, kPcgStop = 1;
+constexpr int kModeNone = 0, kModeJacobi = 1, kModeBlock = 2;
+
+// partials of a.b on [0, n): dot_partial of spmv_cg.hip with the stop check
+template <typename T>
+__global__ __launch_bounds__(kBlock) void pcg_dot(long long n, const int *__restrict__ flags, const T *__restrict__ a,
+                                                  const T *__restrict__ b, double *__restrict__ part) {
+    if (flags[kPcgState] != kPcgRun) return;
+    double acc[1] = {0.0};
+    for (PieceLane l(0, n, 1); l.q < l.end; l.q += l.stride) acc[0] += (double)a[l.q] * (double)b[l.q];
+    block_partials<1>(acc, part);
+}
+
+// at the start: partials of r.r and r.z; JAC: z = D^-1 r first (else z is r)
+template <typename T, bool JAC>
+__global__ __launch_bounds__(kBlock) void pcg_start_dots(long long n, const T *__restrict__ dinv,
+                                                         const T *__restrict__ r, T *__restrict__ z,
+                                                         double *__restrict__ part) {
+    double acc[2] = {0.0, 0.0};
+    for (PieceLane l(0, n, 1); l.q < l.end; l.q += l.stride) {
+        const long long k = l.q;
+        const T rk = r[k];
+        T zk = rk;
+        if constexpr (JAC) {
+            zk = (T)((double)dinv[k] * (double)rk);
+            z[k] = zk;
+        }
+        acc[0] += (double)rk * (double)rk;
+        acc[1] += (double)rk * (double)zk;
+    }
+    block_partials<2>(acc, part);
+}
+
+// x += alpha p, r -= alpha q on this rank's rows; NONE: partials of r.r (twice), JACOBI: z = D^-1 r and partials of
+// r.r, r.z, BLOCK: no partials (pc_apply makes them)
+template <typename T, int MODE>
+__global__ __launch_bounds__(kBlock) void pcg_update_x_r(long long n, const int *__restrict__ flags,
+                                                         const double *__restrict__ s, const T *__restrict__ p,
+                                                         const T *__restrict__ q, const T *__restrict__ dinv,
+                                                         T *__restrict__ x, T *__restrict__ r, T *__restrict__ z,
+                                                         double *__restrict__ part) {
+    if (flags[kPcgState] != kPcgRun) return;
+    const double alpha = s[kPcgAlpha];
+    double acc[2] = {0.0, 0.0};
+    for (PieceLane l(0, n, 1); l.q < l.end; l.q += l.stride) {
+        const long long k = l.q;
+        x[k] = (T)((double)x[k] + alpha * (double)p[k]);
+        const T rk = (T)((double)r[k] - alpha * (double)q[k]);
+        r[k] = rk;
+        if constexpr (MODE == kModeNone) {
+            acc[0] += (double)rk * (double)rk;
+            acc[1] = acc[0];
+        } else if constexpr (MODE == kModeJacobi) {
+            const T zk = (T)((double)dinv[k] * (double)rk);
+            z[k] = zk;
+            acc[0] += (double)rk * (double)rk;
+            acc[1] += (double)rk * (double)zk;
+        }
+    }
+    if constexpr (MODE != kModeBlock) block_partials<2>(acc, part);
+}
+
+// p = z + beta p on this rank's rows
+template <typename T>
+__global__ __launch_bounds__(kBlock) void pcg_update_p(long long n, const int *__restrict__ flags,
+                                                       const double *__restrict__ s, const T *__restrict__ z,
+                                                       T *__restrict__ p) {
+    if (flags[kPcgState] != kPcgRun) return;
+    const double beta = s[kPcgBeta];
+    for (PieceLane l(0, n, 1); l.q < l.end; l.q += l.stride) p[l.q] = (T)((double)z[l.q] + beta * (double)p[l.q]);
+}
+
+// ---- the scalar kernels: one thread each.  A stop writes the status and the steps taken and never touches x.
+__device__ __forceinline__ void pcg_stop(int *__restrict__ flags, int status, int steps) {
+    flags[kPcgState] = kPcgStop;
+    flags[kPcgStatus] = status;
+    flags[kPcgSteps] = steps;
+}
+
+// rr0 = r.r, rz = r.z, history row 0; rr0 = 0 converges at step 0; rz <= 0 or anything not finite breaks down there
+__global__ void pcg_start(double *__restrict__ s, int *__restrict__ flags, double *__restrict__ hrr,
+                          double *__restrict__ hrz, int iters) {
+    const double rr0 = s[kPcgRr], rz = s[kPcgRz];
+    s[kPcgRr0] = rr0;
+    s[kPcgLastRr] = rr0;
+    s[kPcgLastRz] = rz;
+    hrr[0] = rr0;
+    hrz[0] = rz;
+    flags[kPcgState] = kPcgRun;
+    flags[kPcgSteps] = iters;
+    flags[kPcgStatus] = SPMV_PCG_RAN_ALL;
+    if (rr0 == 0.0) pcg_stop(flags, SPMV_PCG_CONVERGED, 0);
+    else if (!(rz > 0.0) || !isfinite(rz) || !isfinite(rr0)) pcg_stop(flags, SPMV_PCG_BREAKDOWN, 0);
+}
+
+// step t: alpha = rz / p.q; p.q <= 0 or anything not finite breaks down (step t not taken)
+__global__ void pcg_set_alpha(double *__restrict__ s, int *__restrict__ flags, int t) {
+    if (flags[kPcgState] != kPcgRun) return;
+    const double pq = s[kPcgPq], alpha = s[kPcgRz] / pq;
+    if (!(pq > 0.0) || !isfinite(pq) || !isfinite(alpha)) {
+        pcg_stop(flags, SPMV_PCG_BREAKDOWN, t - 1);
+        return;
+    }
+    s[kPcgAlpha] = alpha;
+}
+
+// end of step t: history row t; a non-finite rr or rz' breaks down, rr <= tol2 rr0 converges, rz' <= 0 breaks down
+// (x is the iterate of step t); else beta = rz' / rz, rz = rz'
+__global__ void pcg_set_beta(double *__restrict__ s, int *__restrict__ flags, double *__restrict__ hrr,
+                             double *__restrict__ hrz, int t, double tol2) {
+    if (flags[kPcgState] != kPcgRun) {
+        hrr[t] = s[kPcgLastRr];
+        hrz[t] = s[kPcgLastRz];
+        return;
+    }
+    const double rr = s[kPcgRrNew], rz = s[kPcgRzNew];
+    s[kPcgLastRr] = rr;
+    s[kPcgLastRz] = rz;
+    hrr[t] = rr;
+    hrz[t] = rz;
+    if (!isfinite(rr) || !isfinite(rz)) {
+        pcg_stop(flags, SPMV_PCG_BREAKDOWN, t);
+        return;
+    }
+    if (rr <= tol2 * s[kPcgRr0]) {
+        pcg_stop(flags, SPMV_PCG_CONVERGED, t);
+        return;
+    }
+    if (!(rz > 0.0)) {
+        pcg_stop(flags, SPMV_PCG_BREAKDOWN, t);
+        return;
+    }
+    s[kPcgBeta] = rz / s[kPcgRz];
+    s[kPcgRz] = rz;
+}
+
+struct PcgBuffers {
+    void *x, *r, *z;  // x: M_total values (the all-gatherv's), r, z: this rank's rows (z is r without P)
+    double *sc, *part, *gath, *hrr, *hrz;
+    int *flags;
+};
+
+int pcg_exchange_p(spmv_csr_dev *m, const int *bounds) {
+    if (!g_comm) return 0;
+    return spmv_hip_comm_allgatherv(m->x, bounds, m->value_bytes, g_stream);
+}
+
+// the loop; *steps_run = the steps launched (< iters when tol > 0 and the solve stopped)
+template <typename T>
+int pcg_run(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, double tol, const int *bounds,
+            const PcgBuffers &b, int *steps_run) {
+    const long long n = m->M_local;
+    const int grid = (int)std::max<long long>(1, std::min<long long>(kNormBlocks, (n + kBlock - 1) / kBlock));
+    const int mode = !P ? kModeNone : P->block == 1 ? kModeJacobi : kModeBlock;
+    const double tol2 = tol * tol;
+    T *p_own = (T *)m->x + m->row0, *q_own = (T *)m->y + m->row0, *x_own = (T *)b.x + m->row0;
+    T *r = (T *)b.r, *z = (T *)b.z;
+    const T *dinv = P ? (const T *)P->inv : nullptr;
+    const int *fl = b.flags;
+    const dim3 g(grid), blk(kBlock);
+    auto reduce = [&](int nv, int slot) {
+        return solver_reduce(b.part, grid, nv, b.sc + slot, b.sc + kPcgLocal, b.gath, "csr_pcg");
+    };
+    // z = M^-1 r, rr0 = r.r, rz = r.z with r = b; p = z (the own range of the handle's x; the rest by the exchange)
+    if (mode == kModeNone)
+        hipLaunchKernelGGL((pcg_start_dots<T, false>), g, blk, 0, g_stream, n, dinv, (const T *)r, z, b.part);
+    else if (mode == kModeJacobi)
+        hipLaunchKernelGGL((pcg_start_dots<T, true>), g, blk, 0, g_stream, n, dinv, (const T *)r, z, b.part);
+    else
+        precond_launch<T, true>(P, r, z, nullptr, b.part, grid, g_stream);
+    if (reduce(2, kPcgRr)) return -1;
+    hipLaunchKernelGGL(pcg_start, dim3(1), dim3(1), 0, g_stream, b.sc, b.flags, b.hrr, b.hrz, iters);
+    if (n) HIP_TRY(hipMemcpyAsync(p_own, z, (size_t)n * sizeof(T), hipMemcpyDeviceToDevice, g_stream));
+    if (pcg_exchange_p(m, bounds)) return -1;
+    *steps_run = iters;
+    for (int t = 1; t <= iters; ++t) {
+        if (csr_launch_any(m, variant, m->x, m->y, g_stream)) return -1;  // q = A p on this rank's rows
+        hipLaunchKernelGGL((pcg_dot<T>), g, blk, 0, g_stream, n, fl, (const T *)p_own, (const T *)q_own, b.part);
+        if (reduce(1, kPcgPq)) return -1;
+        hipLaunchKernelGGL(pcg_set_alpha, dim3(1), dim3(1), 0, g_stream, b.sc, b.flags, t);
+        if (mode == kModeNone) {
+            hipLaunchKernelGGL((pcg_update_x_r<T, kModeNone>), g, blk, 0, g_stream, n, fl, (const double *)b.sc,
+                               (const T *)p_own, (const T *)q_own, dinv, x_own, r, z, b.part);
+        } else if (mode == kModeJacobi) {
+            hipLaunchKernelGGL((pcg_update_x_r<T, kModeJacobi>), g, blk, 0, g_stream, n, fl, (const double *)b.sc,
+                               (const T *)p_own, (const T *)q_own, dinv, x_own, r, z, b.part);
+        } else {
+            hipLaunchKernelGGL((pcg_update_x_r<T, kModeBlock>), g, blk, 0, g_stream, n, fl, (const double *)b.sc,
+                               (const T *)p_own, (const T *)q_own, dinv, x_own, r, z, b.part);
+            precond_launch<T, true>(P, r, z, fl, b.part, grid, g_stream);
+        }
+        if (reduce(2, kPcgRrNew)) return -1;
+        hipLaunchKernelGGL(pcg_set_beta, dim3(1), dim3(1), 0, g_stream, b.sc, b.flags, b.hrr, b.hrz, t, tol2);
+        hipLaunchKernelGGL((pcg_update_p<T>), g, blk, 0, g_stream, n, fl, (const double *)b.sc, (const T *)z, p_own);
+        if (pcg_exchange_p(m, bounds)) return -1;
+        bool stop = false;
+        if (solver_poll(t, iters, tol, b.flags + kPcgState, kPcgStop, &stop)) return -1;
+        if (stop) {
+            *steps_run = t;
+            break;
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+template <typename T>
+int pcg_body(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, double tol, const int *bounds,
+             const void *b_host, void *x_host, double *rr_hist, double *rz_hist, int *info, float *ms_total) {
+    const size_t n_all = (size_t)m->M_total, n_own = (size_t)m->M_local, vb = sizeof(T);
+    SolverScope scope;
+    PcgBuffers b;
+    b.x = scope.alloc(std::max<size_t>(n_all, 1) * vb);
+    b.r = scope.alloc(std::max<size_t>(n_own, 1) * vb);
+    b.z = P ? scope.alloc(std::max<size_t>(n_own, 1) * vb) : b.r;
+    b.sc = scope.alloc<double>(kPcgSlots * sizeof(double));
+    b.part = scope.alloc<double>((size_t)kNormBlocks * 2 * sizeof(double));
+    b.gath = scope.alloc<double>((size_t)kMaxRanks * 2 * sizeof(double));
+    b.hrr = scope.alloc<double>(((size_t)iters + 1) * sizeof(double));
+    b.hrz = scope.alloc<double>(((size_t)iters + 1) * sizeof(double));
+    b.flags = scope.alloc<int>(kPcgFlagWords * sizeof(int));
+    // r = b on this rank's rows; the handle's x (p) starts at 0 (its own range is set to z by the loop)
+    hipError_t e = scope.err;
+    if (e == hipSuccess && n_own)
+        e = hipMemcpyAsync(b.r, (const T *)b_host + m->row0, n_own * vb, hipMemcpyHostToDevice, g_stream);
+    if (e == hipSuccess) e = hipMemsetAsync(m->x, 0, (size_t)m->N * vb, g_stream);
+    if (e == hipSuccess) e = hipEventRecord(scope.e0, g_stream);
+    if (e != hipSuccess) return fail("csr_pcg: setup failed: %s", hipGetErrorString(e));
+    int steps_run = 0;
+    if (pcg_run<T>(m, P, variant, iters, tol, bounds, b, &steps_run)) return -1;
+    e = hipEventRecord(scope.e1, g_stream);
+    // the solution: every rank holds its rows; with a communicator all rows everywhere
+    if (e == hipSuccess && g_comm && x_host && spmv_hip_comm_allgatherv(b.x, bounds, m->value_bytes, g_stream)) return -1;
+    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
+    float ms = 0;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, scope.e0, scope.e1);
+    if (e == hipSuccess && x_host) e = hipMemcpy(x_host, b.x, n_all * vb, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = copy_history(rr_hist, b.hrr, steps_run, iters, 1);
+    if (e == hipSuccess) e = copy_history(rz_hist, b.hrz, steps_run, iters, 1);
+    int flags[kPcgFlagWords] = {0, 0, 0, 0};
+    if (e == hipSuccess) e = hipMemcpy(flags, b.flags, sizeof flags, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail("csr_pcg: run failed: %s", hipGetErrorString(e));
+    if (info) {
+        info[0] = flags[kPcgSteps];
+        info[1] = flags[kPcgStatus];
+    }
+    if (ms_total) *ms_total = ms;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int spmv_hip_csr_pcg(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, double tol,
+                                const int *bounds, const void *b_host, void *x_host, double *rr_hist, double *rz_hist,
+                                int *info, float *ms_total) {
+    if (need_device()) return -1;
+    int rc = 0;
+    if (!m || !b_host) rc = fail("csr_pcg: bad arguments");
+    else if (iters < 0) rc = fail("csr_pcg: iters = %d, must be >= 0", iters);
+    else if (!(tol >= 0) || !std::isfinite(tol)) rc = fail("csr_pcg: tol = %g, must be finite and >= 0", tol);
+    else if (m->M_total != m->N) rc = fail("csr_pcg: needs a square matrix (%d x %d)", m->M_total, m->N);
+    else if (g_comm && !bounds) rc = fail("csr_pcg: a communicator exists, the row bounds are required");
+    else if (!g_comm && (m->row0 != 0 || m->M_local != m->M_total))
+        rc = fail("csr_pcg: a handle of rows [%d, %d) needs a communicator", m->row0, m->row0 + m->M_local);
+    else if (g_comm_size > kMaxRanks) rc = fail("csr_pcg: more than %d ranks", kMaxRanks);
+    else if (P) rc = precond_matches(m, P, "csr_pcg");
+    if (rc) return rc;
+    return guarded("csr_pcg", [&] {
+        return m->value_bytes == 8
+                   ? pcg_body<double>(m, P, variant, iters, tol, bounds, b_host, x_host, rr_hist, rz_hist, info, ms_total)
+                   : pcg_body<float>(m, P, variant, iters, tol, bounds, b_host, x_host, rr_hist, rz_hist, info, ms_total);
+    });
+}

@@ -1,0 +1,164 @@
+// spmv_precond.hip -- Jacobi and block-Jacobi preconditioners of CSR handles, built and applied on the device
+// (include/spmv_hip.h).
+//
+// The build: pc_extract gathers the diagonal (or each block's b x b diagonal block) in fp64 from the handle's CSR
+// arrays, pc_invert_diag / pc_invert_block invert it into P's own array (precond_kernels.hpp).  Only two ints cross to
+// the host: the first row without its diagonal entry and the first bad row or block.  The fp64 blocks are a temporary
+// of ceil(rows / b) b^2 doubles, freed on every path.
+#include "spmv_internal.hpp"
+
+#include <climits>
+
+#include "precond_kernels.hpp"
+
+namespace {
+
+constexpr int kPcMaxGrid = 1 << 20;  // grid cap of the build kernels (they stride beyond it)
+
+template <typename T>
+int precond_build(const spmv_csr_dev *m, int kind, int b, spmv_precond **out) {
+    const int n = m->M_local;
+    const long long nblocks = ((long long)n + b - 1) / b;
+    const size_t entries = std::max<size_t>((size_t)nblocks * b * b, 1);
+    const size_t inv_bytes = std::max<size_t>(entries * sizeof(T), 16);
+    double *D = nullptr;
+    int *bad = nullptr;
+    void *inv = nullptr;
+    int rc = -1;
+    do {
+        hipError_t e = hipMalloc((void **)&D, entries * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc(&inv, inv_bytes);
+        if (e == hipSuccess) e = hipMalloc((void **)&bad, 2 * sizeof(int));
+        if (e == hipSuccess) e = hipMemsetAsync(D, 0, entries * sizeof(double), g_stream);
+        if (e == hipSuccess) e = hipMemsetAsync(inv, 0, inv_bytes, g_stream);
+        const int none[2] = {INT_MAX, INT_MAX};
+        if (e == hipSuccess) e = hipMemcpy(bad, none, sizeof none, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            fail("csr_precond_build: allocation failed: %s", hipGetErrorString(e));
+            break;
+        }
+        if (n) {
+            const int rgrid = (int)std::min<long long>(kPcMaxGrid, ((long long)n + kPcWaves - 1) / kPcWaves);
+            hipLaunchKernelGGL((pc_extract<T>), dim3(rgrid), dim3(kBlock), 0, g_stream, n, m->row0, b, m->row_ptr,
+                               m->col, (const T *)m->val, D, bad);
+            if (b == 1) {
+                const int grid = (int)std::min<long long>(kPcMaxGrid, ((long long)n + kBlock - 1) / kBlock);
+                hipLaunchKernelGGL((pc_invert_diag<T>), dim3(grid), dim3(kBlock), 0, g_stream, n, (const double *)D,
+                                   (T *)inv, bad);
+            } else {
+                const int grid = (int)std::min<long long>(kPcMaxGrid, nblocks);
+                hipLaunchKernelGGL((pc_invert_block<T>), dim3(grid), dim3(64), 0, g_stream, n, b, (const double *)D,
+                                   (T *)inv, bad);
+            }
+        }
+        int h[2] = {INT_MAX, INT_MAX};
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(h, bad, sizeof h, hipMemcpyDeviceToHost, g_stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
+        if (e != hipSuccess) {
+            fail("csr_precond_build: build failed: %s", hipGetErrorString(e));
+            break;
+        }
+        if (h[0] != INT_MAX) {
+            fail("csr_precond_build: row %d (global row %d) has no diagonal entry", h[0], m->row0 + h[0]);
+            break;
+        }
+        if (h[1] != INT_MAX) {
+            if (b == 1)
+                fail("csr_precond_build: row %d (global row %d): the diagonal is zero or not finite, or so small that "
+                     "its inverse is not finite", h[1], m->row0 + h[1]);
+            else
+                fail("csr_precond_build: block %d (global rows [%d, %d)): a zero or non-finite pivot, or an inverse "
+                     "that is not finite", h[1], m->row0 + h[1] * b, m->row0 + (int)std::min<long long>(
+                                                                                    (long long)(h[1] + 1) * b, n));
+            break;
+        }
+        spmv_precond *P = new spmv_precond;
+        P->kind = kind;
+        P->block = b;
+        P->rows = n;
+        P->row0 = m->row0;
+        P->value_bytes = (int)sizeof(T);
+        P->inv = inv;
+        inv = nullptr;  // P owns it now
+        *out = P;
+        rc = 0;
+    } while (0);
+    (void)hipFree(D);
+    (void)hipFree(bad);
+    (void)hipFree(inv);
+    (void)hipGetLastError();  // a refused build or a failed allocation is reported by rc, not by the next launch
+    return rc;
+}
+
+int precond_apply_launch(const spmv_precond *P, const void *d_r, void *d_z, hipStream_t s) {
+    if (!P->rows) return 0;
+    if (P->value_bytes == 8) precond_launch<double, false>(P, d_r, d_z, nullptr, nullptr, 0, s);
+    else precond_launch<float, false>(P, d_r, d_z, nullptr, nullptr, 0, s);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int spmv_hip_csr_precond_build(const spmv_csr_dev *m, int kind, int block, spmv_precond **out) {
+    if (need_device()) return -1;
+    if (!out) return fail("csr_precond_build: out is NULL");
+    *out = nullptr;
+    if (!m) return fail("csr_precond_build: NULL handle");
+    if (kind != SPMV_PRECOND_JACOBI && kind != SPMV_PRECOND_BLOCK_JACOBI)
+        return fail("csr_precond_build: kind = %d, must be SPMV_PRECOND_JACOBI or SPMV_PRECOND_BLOCK_JACOBI", kind);
+    if (kind == SPMV_PRECOND_JACOBI && block != 1) return fail("csr_precond_build: JACOBI takes block = 1, not %d", block);
+    if (block < 1 || block > kPcMaxBlock)
+        return fail("csr_precond_build: block = %d, must be in [1, %d]", block, kPcMaxBlock);
+    if (m->M_total != m->N) return fail("csr_precond_build: needs a square matrix (%d x %d)", m->M_total, m->N);
+    if (m->tiles_only || !m->row_ptr || (m->nz > 0 && (!m->col || !m->val)))
+        return fail("csr_precond_build: the handle does not hold its CSR arrays");
+    return guarded("csr_precond_build", [&] {
+        return m->value_bytes == 8 ? precond_build<double>(m, kind, block, out)
+                                   : precond_build<float>(m, kind, block, out);
+    });
+}
+
+extern "C" void spmv_hip_precond_free(spmv_precond *P) {
+    if (!P) return;
+    (void)hipFree(P->inv);
+    delete P;
+}
+
+extern "C" int spmv_hip_precond_info(const spmv_precond *P, int *info) {
+    if (!P || !info) return fail("precond_info: bad arguments");
+    info[0] = P->kind;
+    info[1] = P->block;
+    info[2] = P->rows;
+    info[3] = P->row0;
+    info[4] = P->value_bytes;
+    return 0;
+}
+
+extern "C" int spmv_hip_precond_apply_on(const spmv_precond *P, const void *d_r, void *d_z, void *stream) {
+    if (need_device()) return -1;
+    if (!P || (P->rows && (!d_r || !d_z))) return fail("precond_apply_on: bad arguments");
+    if (((uintptr_t)d_r | (uintptr_t)d_z) % (uintptr_t)P->value_bytes)
+        return fail("precond_apply_on: r and z must be aligned to %d bytes", P->value_bytes);
+    return precond_apply_launch(P, d_r, d_z, stream ? (hipStream_t)stream : g_stream);
+}
+
+extern "C" int spmv_hip_precond_apply(const spmv_precond *P, const void *r_host, void *z_host) {
+    if (need_device()) return -1;
+    if (!P || (P->rows && (!r_host || !z_host))) return fail("precond_apply: bad arguments");
+    return guarded("precond_apply", [&] {
+        const size_t bytes = (size_t)P->rows * P->value_bytes;
+        SolverScope scope;
+        void *r = scope.alloc(std::max<size_t>(bytes, 16));
+        void *z = scope.alloc(std::max<size_t>(bytes, 16));
+        hipError_t e = scope.err;
+        if (e == hipSuccess && bytes) e = hipMemcpyAsync(r, r_host, bytes, hipMemcpyHostToDevice, g_stream);
+        if (e != hipSuccess) return fail("precond_apply: setup failed: %s", hipGetErrorString(e));
+        if (precond_apply_launch(P, r, z, g_stream)) return -1;
+        e = hipStreamSynchronize(g_stream);
+        if (e == hipSuccess && bytes) e = hipMemcpy(z_host, z, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return fail("precond_apply: run failed: %s", hipGetErrorString(e));
+        return 0;
+    });
+}

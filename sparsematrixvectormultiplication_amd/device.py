@@ -19,6 +19,10 @@ HLL_AUTO, HLL_THREAD_ROW, HLL_SUBWAVE, HLL_LDS = 0, 1, 2, 3
 BICG_RAN_ALL, BICG_CONVERGED, BICG_BREAKDOWN_RHO, BICG_BREAKDOWN_OMEGA = 0, 1, 2, 3
 # CsrDevice.cgls: info["status"] (SPMV_CGLS_* of include/spmv_hip.h)
 CGLS_RAN_ALL, CGLS_CONVERGED, CGLS_BREAKDOWN = 0, 1, 2
+# CsrDevice.pcg: info["status"] (SPMV_PCG_*); CsrDevice.preconditioner kinds (SPMV_PRECOND_*)
+PCG_RAN_ALL, PCG_CONVERGED, PCG_BREAKDOWN = 0, 1, 2
+PRECOND_JACOBI, PRECOND_BLOCK_JACOBI = 1, 2
+PRECOND_KINDS = {"jacobi": PRECOND_JACOBI, "block_jacobi": PRECOND_BLOCK_JACOBI}
 CSR_STREAM_KERNELS = ("csr_stream", "csr_stream_local", "csr_stream_short", "csr_tile")
 HLL_LDS_KERNELS = ("hll_lds", "hll_lds_local", "csr_tile (HLL slab rows)")
 CSR_VARIANTS = {"thread_row": CSR_THREAD_ROW, "wave_row": CSR_WAVE_ROW, "subwave": CSR_SUBWAVE,
@@ -191,6 +195,11 @@ class CsrDevice(_Handle):
                   col_idx.ctypes.data_as(nat.c_int_p), values.ctypes.data_as(vp), int(row0),
                   int(row1), C.byref(self.h)), "spmv_hip_csr_upload")
         self.M, self.N = int(M), int(N)
+        self.row0, self.row1 = int(row0), int(row1)
+
+    def _own_rows(self):
+        """(row0, row1): the rows this handle holds (the whole matrix unless uploaded as a row range)."""
+        return getattr(self, "row0", 0), getattr(self, "row1", self.M)
 
     @classmethod
     def from_coo(cls, M, N, I, J, val):
@@ -386,11 +395,7 @@ class CsrDevice(_Handle):
                                                C.byref(ms)), "spmv_hip_csr_cg_multi")
         return X, hist, done, float(ms.value)
 
-    def bicgstab(self, b, iters, tol=0.0, variant=CSR_AUTO, bounds=None):
-        """BiCGSTAB from x0 = 0 with shadow residual r^ = b (spmv_hip_csr_bicgstab), for a square, possibly
-        nonsymmetric A.  Stops once r.r (or s.s at a half step) <= tol^2 times the initial r.r (tol = 0: only at
-        exactly 0; tol > 0 also ends the loop early), or at a breakdown.  Returns (x, r.r history (iters + 1),
-        info {"steps", "status" (BICG_*), "half_step"}, ms)."""
+    def _check_solve_args(self, b, iters, tol, precond):
         b = np.asarray(b)
         if b.dtype != self.dtype:
             raise ValueError(f"b has dtype {b.dtype}, the handle holds {np.dtype(self.dtype)}")
@@ -400,17 +405,67 @@ class CsrDevice(_Handle):
             raise ValueError(f"iters must be >= 0, got {iters}")
         if not float(tol) >= 0.0 or not np.isfinite(float(tol)):
             raise ValueError(f"tol must be finite and >= 0, got {tol}")
-        b = np.ascontiguousarray(b)
+        if precond is not None:
+            if not isinstance(precond, Preconditioner):
+                raise ValueError("precond must be a Preconditioner (CsrDevice.preconditioner) or None")
+            if np.dtype(precond.dtype) != np.dtype(self.dtype):
+                raise ValueError(f"the preconditioner holds {np.dtype(precond.dtype)}, the handle "
+                                 f"{np.dtype(self.dtype)}")
+            row0, row1 = self._own_rows()
+            if (precond.row0, precond.row0 + precond.rows) != (row0, row1):
+                raise ValueError(f"the preconditioner covers rows [{precond.row0}, {precond.row0 + precond.rows}), "
+                                 f"the handle rows [{row0}, {row1})")
+        return np.ascontiguousarray(b)
+
+    def preconditioner(self, kind="jacobi", block=1) -> "Preconditioner":
+        """A Jacobi (kind "jacobi", block 1) or block-Jacobi (kind "block_jacobi", block in [1, 32]) preconditioner of
+        this handle's rows, built on the device (spmv_hip_csr_precond_build); it owns its arrays."""
+        if kind not in PRECOND_KINDS:
+            raise ValueError(f"kind must be one of {sorted(PRECOND_KINDS)}, got {kind!r}")
+        if isinstance(block, bool) or int(block) != block or not 1 <= int(block) <= 32:
+            raise ValueError(f"block must be an integer in [1, 32], got {block!r}")
+        if kind == "jacobi" and int(block) != 1:
+            raise ValueError(f"jacobi takes block = 1, got {block}")
+        return Preconditioner(self, PRECOND_KINDS[kind], int(block))
+
+    def pcg(self, b, iters, tol=0.0, precond=None, variant=CSR_AUTO, bounds=None):
+        """Preconditioned CG from x0 = 0 (spmv_hip_csr_pcg) for a symmetric positive definite A; precond: a
+        Preconditioner of this handle, or None (no preconditioning: csr_cg's bits).  Stops once r.r <= tol^2 times
+        the initial r.r (tol = 0: only at exactly 0; tol > 0 also ends the loop early), or at a breakdown.  Returns
+        (x, r.r history (iters + 1), r.z history (iters + 1), info {"steps", "status" (PCG_*)}, ms)."""
+        b = self._check_solve_args(b, iters, tol, precond)
+        x = np.zeros(self.M, dtype=self.dtype)
+        rr = np.zeros(int(iters) + 1)
+        rz = np.zeros(int(iters) + 1)
+        info = np.zeros(2, dtype=np.int32)
+        ms = C.c_float(0)
+        bb = None if bounds is None else np.ascontiguousarray(bounds, dtype=np.int32)
+        _check(nat.lib().spmv_hip_csr_pcg(self.h, None if precond is None else precond.h, int(variant), int(iters),
+                                          float(tol), None if bb is None else bb.ctypes.data_as(nat.c_int_p),
+                                          b.ctypes.data_as(C.c_void_p), x.ctypes.data_as(C.c_void_p),
+                                          rr.ctypes.data_as(nat.c_double_p), rz.ctypes.data_as(nat.c_double_p),
+                                          info.ctypes.data_as(nat.c_int_p), C.byref(ms)), "spmv_hip_csr_pcg")
+        return x, rr, rz, {"steps": int(info[0]), "status": int(info[1])}, float(ms.value)
+
+    def bicgstab(self, b, iters, tol=0.0, variant=CSR_AUTO, bounds=None, precond=None):
+        """BiCGSTAB from x0 = 0 with shadow residual r^ = b (spmv_hip_csr_bicgstab), for a square, possibly
+        nonsymmetric A.  Stops once r.r (or s.s at a half step) <= tol^2 times the initial r.r (tol = 0: only at
+        exactly 0; tol > 0 also ends the loop early), or at a breakdown.  precond: a Preconditioner of this handle
+        applied from the right (spmv_hip_csr_pbicgstab; r stays the true residual), or None.  Returns (x, r.r history
+        (iters + 1), info {"steps", "status" (BICG_*), "half_step"}, ms)."""
+        b = self._check_solve_args(b, iters, tol, precond)
         x = np.zeros(self.M, dtype=self.dtype)
         hist = np.zeros(int(iters) + 1)
         info = np.zeros(3, dtype=np.int32)
         ms = C.c_float(0)
         bb = None if bounds is None else np.ascontiguousarray(bounds, dtype=np.int32)
-        _check(nat.lib().spmv_hip_csr_bicgstab(self.h, int(variant), int(iters), float(tol),
-                                               None if bb is None else bb.ctypes.data_as(nat.c_int_p),
-                                               b.ctypes.data_as(C.c_void_p), x.ctypes.data_as(C.c_void_p),
-                                               hist.ctypes.data_as(nat.c_double_p), info.ctypes.data_as(nat.c_int_p),
-                                               C.byref(ms)), "spmv_hip_csr_bicgstab")
+        args = (int(variant), int(iters), float(tol), None if bb is None else bb.ctypes.data_as(nat.c_int_p),
+                b.ctypes.data_as(C.c_void_p), x.ctypes.data_as(C.c_void_p), hist.ctypes.data_as(nat.c_double_p),
+                info.ctypes.data_as(nat.c_int_p), C.byref(ms))
+        if precond is None:
+            _check(nat.lib().spmv_hip_csr_bicgstab(self.h, *args), "spmv_hip_csr_bicgstab")
+        else:
+            _check(nat.lib().spmv_hip_csr_pbicgstab(self.h, precond.h, *args), "spmv_hip_csr_pbicgstab")
         return x, hist, {"steps": int(info[0]), "status": int(info[1]), "half_step": int(info[2])}, float(ms.value)
 
     def cgls(self, b, iters, tol=0.0, damp=0.0, at=None):
@@ -495,6 +550,44 @@ class CsrDevice(_Handle):
                                                 mk.ctypes.data_as(nat.c_float_p),
                                                 mx.ctypes.data_as(nat.c_float_p)), "csr_step_time")
         return mk, mx
+
+
+class Preconditioner(_Handle):
+    """M^-1 of a Jacobi or block-Jacobi preconditioner of a CsrDevice's rows, resident in HBM (CsrDevice.preconditioner).
+    It owns its arrays: the handle it was built from may be freed first."""
+
+    _free = "spmv_hip_precond_free"
+
+    def __init__(self, dev: CsrDevice, kind: int, block: int):
+        super().__init__()
+        _check(nat.lib().spmv_hip_csr_precond_build(dev.h, int(kind), int(block), C.byref(self.h)),
+               "spmv_hip_csr_precond_build")
+        info = self.info()
+        self.kind, self.block, self.rows, self.row0 = info["kind"], info["block"], info["rows"], info["row0"]
+        self.dtype = np.float64 if info["value_bytes"] == 8 else np.float32
+
+    def info(self) -> dict:
+        out = (C.c_int * 5)()
+        _check(nat.lib().spmv_hip_precond_info(self.h, out), "spmv_hip_precond_info")
+        return dict(zip(("kind", "block", "rows", "row0", "value_bytes"), (int(v) for v in out)))
+
+    def apply(self, r):
+        """z = M^-1 r for r of `rows` values (element i = row row0 + i) of the handle's dtype."""
+        r = np.asarray(r)
+        if r.dtype != self.dtype:
+            raise ValueError(f"r has dtype {r.dtype}, the preconditioner holds {np.dtype(self.dtype)}")
+        if r.ndim != 1 or r.shape[0] != self.rows:
+            raise ValueError(f"r must be a vector of {self.rows} values, got shape {r.shape}")
+        r = np.ascontiguousarray(r)
+        z = np.zeros(self.rows, dtype=self.dtype)
+        _check(nat.lib().spmv_hip_precond_apply(self.h, r.ctypes.data_as(C.c_void_p), z.ctypes.data_as(C.c_void_p)),
+               "spmv_hip_precond_apply")
+        return z
+
+    def apply_on(self, d_r: int, d_z: int, stream: int = 0):
+        """z = M^-1 r on device vectors, asynchronous on `stream` (0 = the library's)."""
+        _check(nat.lib().spmv_hip_precond_apply_on(self.h, C.c_void_p(d_r), C.c_void_p(d_z), C.c_void_p(stream)),
+               "spmv_hip_precond_apply_on")
 
 
 class HllDevice(_Handle):
