@@ -539,12 +539,79 @@ void spmv_hip_precond_free(spmv_precond *P);
 int spmv_hip_precond_info(const spmv_precond *P, int *info);
 int spmv_hip_precond_apply(const spmv_precond *P, const void *r_host, void *z_host);
 int spmv_hip_precond_apply_on(const spmv_precond *P, const void *d_r, void *d_z, void *stream);
+/* Sparse triangular solves on a square CSR handle.  T is the lower (upper) triangle of the handle's own diagonal block
+ * A[row0:row1, row0:row1]: entries on the other side of the diagonal and entries in columns outside [row0, row1) are
+ * ignored, with SPMV_TRSV_UNIT the stored diagonal as well.  Rows may be unsorted and may repeat a (row, column) pair:
+ * repeats are added in entry order in fp64.  The solver owns a private copy of its triangle, stored in level order
+ * (row i's level = 1 + the largest level among the rows it reads) with the off-diagonal values rounded to the handle's
+ * dtype and the diagonal kept as its inverse (1.0 / d in fp64, rounded once); it never changes the handle and may
+ * outlive it.  A solve is one launch per wide level and one launch per run of consecutive narrow levels (one
+ * workgroup, a barrier between levels); no kernel waits for another workgroup.  Every row's sum is accumulated in
+ * double in a fixed order and rounded once: two solves, and two builds, give the same bits.
+ * ordering: SPMV_ORDER_NATURAL only (SPMV_ORDER_MULTICOLOR changes which matrix a preconditioner factors, below).
+ * -1 (*out stays NULL, the HIP error state stays clean, the handle still works): a missing, zero or non-finite diagonal
+ * with SPMV_TRSV_NONUNIT (the message names the first bad row), a bad uplo / diag / ordering, a non-square matrix, a
+ * tiles-only handle.
+ *   spmv_hip_trsv_solve     x with T x = b; b_host, x_host hold `rows` values (element i = row row0 + i); syncs
+ *   spmv_hip_trsv_solve_on  the same on device vectors (b and x must not overlap), asynchronous on `stream` (NULL =
+ *                           the library's), no host synchronisation
+ *   spmv_hip_trsv_info      info[SPMV_TRSV_INFO_WORDS] = rows, row0, value_bytes, off-diagonal entries, levels, launches,
+ *                           rows of the widest level, colours (0), rows of the median level, lanes per short row,
+ *                           microseconds of the analysis (download, canonical rows, levels) and of the upload */
+typedef struct spmv_trsv spmv_trsv;
+enum { SPMV_TRSV_LOWER = 0, SPMV_TRSV_UPPER = 1 };
+enum { SPMV_TRSV_NONUNIT = 0, SPMV_TRSV_UNIT = 1 };
+enum { SPMV_ORDER_NATURAL = 0, SPMV_ORDER_MULTICOLOR = 1 };
+enum { SPMV_TRSV_INFO_WORDS = 12, SPMV_PRECOND_TRI_INFO_WORDS = 14 };
+int spmv_hip_csr_trsv_build(const spmv_csr_dev *m, int uplo, int diag, int ordering, spmv_trsv **out);
+int spmv_hip_trsv_solve(const spmv_trsv *T, const void *b_host, void *x_host);
+int spmv_hip_trsv_solve_on(const spmv_trsv *T, const void *d_b, void *d_x, void *stream);
+int spmv_hip_trsv_info(const spmv_trsv *T, int *info);
+void spmv_hip_trsv_free(spmv_trsv *T);
+/* The host analysis behind them (no device needed), on an n x n CSR pattern with local columns; columns outside [0, n)
+ * are ignored, rows may be unsorted.
+ *   spmv_trsv_colour  greedy first-fit colouring in natural order over the pattern of A + A^T; colour[n], order[n] =
+ *                     the rows by (colour, row); returns the number of colours (-1: out of memory or bad arguments)
+ *   spmv_trsv_levels  the level schedule of the strict lower / upper triangle: level[n] (from 1), perm[n] = the rows
+ *                     level by level, inside a level first the rows with fewer than long_len entries on that side, then
+ *                     the others, each in ascending order; level_ptr[levels + 1], level_split[levels] (a level's first
+ *                     long row) index perm; plan[3 k] = {1, first, end} for a run of narrow levels (at most chain_rows
+ *                     rows and chain_entries entries each), {0, l, l + 1} for a wide one; counts[4] = levels, launches,
+ *                     widest level, entries.  The caller allocates level_ptr[n + 1], level_split[n], plan[3 n]. */
+int spmv_trsv_colour(int n, const int *row_ptr, const int *col, int *colour, int *order);
+int spmv_trsv_levels(int n, const int *row_ptr, const int *col, int uplo, int long_len, int chain_rows,
+                     int chain_entries, int *level, int *perm, int *level_ptr, int *level_split, int *plan,
+                     long long *counts);
+/* Preconditioners made of two triangular solves, of the handle's own diagonal block A = L + D + U (the same
+ * spmv_precond type: info (block = 1), apply, apply_on, free, spmv_hip_csr_pcg and spmv_hip_csr_pbicgstab take them):
+ *   SPMV_PRECOND_SSOR   M = w / (2 - w) (D/w + L) (D/w)^-1 (D/w + U), 0 < w = omega < 2; no factorisation; w = 1 is
+ *                       symmetric Gauss-Seidel.  M is symmetric when A is.
+ *   SPMV_PRECOND_ILU0   M = L U, L unit lower, U upper, both with A's pattern, (L U)_ij = a_ij on it (omega unused).
+ *                       Factored on the device level by level, one wavefront per row, a row's updates in ascending
+ *                       pivot order in fp64, the factors rounded once to the handle's dtype.  For SPD A, U = D L^T.
+ * SPMV_ORDER_MULTICOLOR builds them of Q A Q^T, Q ordering the rows by (colour, row) of spmv_trsv_colour; the apply
+ * reads r and writes z through Q inside its first and last kernel.  One P serves one stream at a time (the two
+ * solves share a vector of P's).  P keeps only the diagonal on the host; spmv_hip_precond_factors reads the rest back.
+ * -1 as spmv_hip_csr_precond_build, and for a zero or non-finite ILU(0) pivot (its row in the message).
+ *   spmv_hip_precond_tri_info  info[SPMV_PRECOND_TRI_INFO_WORDS] = forward solve: levels, launches, widest, median
+ *                              level; backward solve: the same four; colours (0: natural order); entries of L and of
+ *                              U (each with its diagonal); microseconds of analysis, factorisation, upload
+ *   spmv_hip_precond_factors   L (which = SPMV_FACTOR_L) or U in the handle's row numbering, columns ascending, values
+ *                              of the handle's dtype, both with their diagonal (ILU(0): L's is exactly 1; SSOR: the
+ *                              triangles of A).  With the multicolour order they are Q^T L Q and Q^T U Q.  First call:
+ *                              col = val = NULL fills row_ptr[rows + 1]; second call: all three. */
+enum { SPMV_PRECOND_SSOR = 3, SPMV_PRECOND_ILU0 = 4 };
+enum { SPMV_FACTOR_L = 0, SPMV_FACTOR_U = 1 };
+int spmv_hip_csr_precond_build_tri(const spmv_csr_dev *m, int kind, int ordering, double omega, spmv_precond **out);
+int spmv_hip_precond_tri_info(const spmv_precond *P, int *info);
+int spmv_hip_precond_factors(const spmv_precond *P, int which, int *row_ptr, int *col, void *val);
 /* Preconditioned CG for a symmetric positive definite A and M, x0 = 0 (P = NULL: M = I, z is r itself):
  *   r = b, z = M^-1 r, p = z, rz = r.z, rr0 = r.r
  *   each step: q = A p, alpha = rz / p.q, x += alpha p, r -= alpha q, z = M^-1 r, rz' = r.z, rr = r.r,
  *              stop (CONVERGED) if rr <= tol^2 rr0, beta = rz' / rz, p = z + beta p
  * The product, the communicator, the bounds and the all-gatherv of p are those of spmv_hip_csr_cg (no halo variant).
- * Jacobi is fused into the x / r update with both dots; a block-Jacobi apply is a pass of its own that makes the dots.
+ * Jacobi is fused into the x / r update with both dots; a block-Jacobi apply is a pass of its own that makes the dots;
+ * an SSOR or ILU(0) apply is its two solves, then one pass for the two dots.
  * P = NULL, or Jacobi on a matrix whose diagonal is exactly 1, with tol = 0 and no breakdown gives spmv_hip_csr_cg's
  * x and rr_hist bit for bit.
  * Breakdown: p.q <= 0, rz' <= 0 while rr > 0, or any non-finite scalar (A or M not SPD); x stays at the last full
@@ -560,7 +627,8 @@ int spmv_hip_csr_pcg(spmv_csr_dev *m, const spmv_precond *P, int variant, int it
 /* Right-preconditioned BiCGSTAB: the loop of spmv_hip_csr_bicgstab on A M^-1 with x = M^-1 y, so r stays the true
  * residual and tol, the half step, the breakdown rules, rr_hist and info mean what they mean there:
  *   p^ = M^-1 p, v = A p^, ..., s^ = M^-1 s, t = A s^, x += alpha p^ + omega s^ (a half step: x += alpha p^)
- * With a communicator p^ and s^ (the products' inputs) are all-gathered.  Jacobi is fused into the s and p updates.
+ * With a communicator p^ and s^ (the products' inputs) are all-gathered.  Jacobi is fused into the s and p updates;
+ * block-Jacobi, SSOR and ILU(0) are applied after them.
  * P = NULL gives spmv_hip_csr_bicgstab's bits.  -1: as spmv_hip_csr_bicgstab, and a P that does not fit the handle. */
 int spmv_hip_csr_pbicgstab(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, double tol,
                            const int *bounds, const void *b_host, void *x_host, double *rr_hist, int *info,

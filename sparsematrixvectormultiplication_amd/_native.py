@@ -230,6 +230,17 @@ _PROTOTYPES = {
     "spmv_hip_precond_info": (C.c_int, [C.c_void_p, c_int_p]),
     "spmv_hip_precond_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "spmv_hip_precond_apply_on": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spmv_hip_csr_trsv_build": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "spmv_hip_trsv_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spmv_hip_trsv_solve_on": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spmv_hip_trsv_info": (C.c_int, [C.c_void_p, c_int_p]),
+    "spmv_hip_trsv_free": (None, [C.c_void_p]),
+    "spmv_trsv_colour": (C.c_int, [C.c_int, c_int_p, c_int_p, c_int_p, c_int_p]),
+    "spmv_trsv_levels": (C.c_int, [C.c_int, c_int_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p,
+                                   c_int_p, c_int_p, c_int_p, C.POINTER(C.c_longlong)]),
+    "spmv_hip_csr_precond_build_tri": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_void_p)]),
+    "spmv_hip_precond_tri_info": (C.c_int, [C.c_void_p, c_int_p]),
+    "spmv_hip_precond_factors": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_int_p, C.c_void_p]),
     "spmv_hip_csr_pcg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, c_int_p, C.c_void_p,
                                    C.c_void_p, c_double_p, c_double_p, c_int_p, c_float_p]),
     "spmv_hip_csr_pbicgstab": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, c_int_p, C.c_void_p,

@@ -182,7 +182,14 @@ struct spmv_precond {
     int rows = 0, row0 = 0;   // the handle's own rows [row0, row0 + rows)
     int value_bytes = 8;      // the handle's dtype
     void *inv = nullptr;      // ceil(rows / block) * block^2 values of that dtype (layout above); owned
+    struct spmv_tri_precond *tri = nullptr;  // SSOR / ILU0: the two triangular solves (spmv_trsv.hip); owned, inv is NULL
 };
+
+// SSOR and ILU(0) take a path of their own wherever Jacobi / block-Jacobi are told apart by P->block
+inline bool precond_is_tri(const spmv_precond *P) { return P && P->tri != nullptr; }
+// spmv_trsv.hip: z = M^-1 r by P's two solves on stream s (flags as pc_apply: a stopped solver's launches return)
+int precond_tri_apply(const spmv_precond *P, const void *r, void *z, const int *flags, hipStream_t s);
+void precond_tri_free(struct spmv_tri_precond *tp);
 
 // z = M^-1 r on P's rows (r, z at local row 0) on stream s; flags / part as pc_apply; grid 0: by the row count
 template <typename T, bool DOTS>

@@ -14,6 +14,9 @@
 //   JACOBI  the same and z = D^-1 r (one more read, one more write), partials of r.r, r.z  8
 //   BLOCK   x += alpha p, r -= alpha q (6), then pc_apply: z = M^-1 r with r.r and r.z    b + 2 more (L2 serves r's
 //           repeats inside a block)
+//   TRI     x += alpha p, r -= alpha q (6), then SSOR's / ILU(0)'s two solves (spmv_trsv.hip), then pcg_dots: r.r and
+//           r.z by the walk and the fold of the other modes (2 more reads); the solves' last kernel is a level of a few
+//           rows, so the dots are a pass of their own rather than fused into it
 //
 // pcg_dot (p.q, 2 values) and pcg_update_p (p = z + beta p, 3) complete the step: fp64 Jacobi PCG moves 13 values =
 // 104 B per row against csr_cg's 11 (88 B).  The scalars and the stop state never leave the device; after a stop the
@@ -30,7 +33,7 @@ constexpr int kPcgRr = 0, kPcgRz = 1, kPcgPq = 2, kPcgRrNew = 3, kPcgRzNew = 4, 
 // the int words; the state word is word 0 (pc_apply reads it there) and RUN is 0
 constexpr int kPcgState = 0, kPcgSteps = 1, kPcgStatus = 2, kPcgFlagWords = 4;
 constexpr int kPcgRun = 0, kPcgStop = 1;
-constexpr int kModeNone = 0, kModeJacobi = 1, kModeBlock = 2;
+constexpr int kModeNone = 0, kModeJacobi = 1, kModeBlock = 2, kModeTri = 3;
 
 // partials of a.b on [0, n): dot_partial of spmv_cg.hip with the stop check
 template <typename T>
@@ -40,6 +43,20 @@ __global__ __launch_bounds__(kBlock) void pcg_dot(long long n, const int *__rest
     double acc[1] = {0.0};
     for (PieceLane l(0, n, 1); l.q < l.end; l.q += l.stride) acc[0] += (double)a[l.q] * (double)b[l.q];
     block_partials<1>(acc, part);
+}
+
+// partials of r.r and r.z after an apply that made none (flags NULL: at the start)
+template <typename T>
+__global__ __launch_bounds__(kBlock) void pcg_dots(long long n, const int *__restrict__ flags, const T *__restrict__ r,
+                                                   const T *__restrict__ z, double *__restrict__ part) {
+    if (flags && flags[kPcgState] != kPcgRun) return;
+    double acc[2] = {0.0, 0.0};
+    for (PieceLane l(0, n, 1); l.q < l.end; l.q += l.stride) {
+        const double rk = (double)r[l.q];
+        acc[0] += rk * rk;
+        acc[1] += rk * (double)z[l.q];
+    }
+    block_partials<2>(acc, part);
 }
 
 // at the start: partials of r.r and r.z; JAC: z = D^-1 r first (else z is r)
@@ -182,7 +199,7 @@ int pcg_run(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, doub
             const PcgBuffers &b, int *steps_run) {
     const long long n = m->M_local;
     const int grid = (int)std::max<long long>(1, std::min<long long>(kNormBlocks, (n + kBlock - 1) / kBlock));
-    const int mode = !P ? kModeNone : P->block == 1 ? kModeJacobi : kModeBlock;
+    const int mode = !P ? kModeNone : precond_is_tri(P) ? kModeTri : P->block == 1 ? kModeJacobi : kModeBlock;
     const double tol2 = tol * tol;
     T *p_own = (T *)m->x + m->row0, *q_own = (T *)m->y + m->row0, *x_own = (T *)b.x + m->row0;
     T *r = (T *)b.r, *z = (T *)b.z;
@@ -197,8 +214,12 @@ int pcg_run(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, doub
         hipLaunchKernelGGL((pcg_start_dots<T, false>), g, blk, 0, g_stream, n, dinv, (const T *)r, z, b.part);
     else if (mode == kModeJacobi)
         hipLaunchKernelGGL((pcg_start_dots<T, true>), g, blk, 0, g_stream, n, dinv, (const T *)r, z, b.part);
-    else
+    else if (mode == kModeBlock)
         precond_launch<T, true>(P, r, z, nullptr, b.part, grid, g_stream);
+    else {
+        if (precond_tri_apply(P, r, z, nullptr, g_stream)) return -1;
+        hipLaunchKernelGGL((pcg_dots<T>), g, blk, 0, g_stream, n, (const int *)nullptr, (const T *)r, (const T *)z, b.part);
+    }
     if (reduce(2, kPcgRr)) return -1;
     hipLaunchKernelGGL(pcg_start, dim3(1), dim3(1), 0, g_stream, b.sc, b.flags, b.hrr, b.hrz, iters);
     if (n) HIP_TRY(hipMemcpyAsync(p_own, z, (size_t)n * sizeof(T), hipMemcpyDeviceToDevice, g_stream));
@@ -218,7 +239,12 @@ int pcg_run(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, doub
         } else {
             hipLaunchKernelGGL((pcg_update_x_r<T, kModeBlock>), g, blk, 0, g_stream, n, fl, (const double *)b.sc,
                                (const T *)p_own, (const T *)q_own, dinv, x_own, r, z, b.part);
-            precond_launch<T, true>(P, r, z, fl, b.part, grid, g_stream);
+            if (mode == kModeBlock) {
+                precond_launch<T, true>(P, r, z, fl, b.part, grid, g_stream);
+            } else {
+                if (precond_tri_apply(P, r, z, fl, g_stream)) return -1;
+                hipLaunchKernelGGL((pcg_dots<T>), g, blk, 0, g_stream, n, fl, (const T *)r, (const T *)z, b.part);
+            }
         }
         if (reduce(2, kPcgRrNew)) return -1;
         hipLaunchKernelGGL(pcg_set_beta, dim3(1), dim3(1), 0, g_stream, b.sc, b.flags, b.hrr, b.hrz, t, tol2);

@@ -5,6 +5,9 @@
 // arrays, pc_invert_diag / pc_invert_block invert it into P's own array (precond_kernels.hpp).  Only two ints cross to
 // the host: the first row without its diagonal entry and the first bad row or block.  The fp64 blocks are a temporary
 // of ceil(rows / b) b^2 doubles, freed on every path.
+//
+// SSOR and ILU(0) (spmv_hip_csr_precond_build_tri) are the same spmv_precond with P->tri set: spmv_trsv.hip builds and
+// applies them, free / info / apply / apply_on here hand them on.
 #include "spmv_internal.hpp"
 
 #include <climits>
@@ -93,6 +96,7 @@ int precond_build(const spmv_csr_dev *m, int kind, int b, spmv_precond **out) {
 
 int precond_apply_launch(const spmv_precond *P, const void *d_r, void *d_z, hipStream_t s) {
     if (!P->rows) return 0;
+    if (precond_is_tri(P)) return precond_tri_apply(P, d_r, d_z, nullptr, s);
     if (P->value_bytes == 8) precond_launch<double, false>(P, d_r, d_z, nullptr, nullptr, 0, s);
     else precond_launch<float, false>(P, d_r, d_z, nullptr, nullptr, 0, s);
     HIP_TRY(hipGetLastError());
@@ -123,6 +127,7 @@ extern "C" int spmv_hip_csr_precond_build(const spmv_csr_dev *m, int kind, int b
 extern "C" void spmv_hip_precond_free(spmv_precond *P) {
     if (!P) return;
     (void)hipFree(P->inv);
+    precond_tri_free(P->tri);
     delete P;
 }
 

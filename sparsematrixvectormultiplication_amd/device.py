@@ -21,8 +21,18 @@ BICG_RAN_ALL, BICG_CONVERGED, BICG_BREAKDOWN_RHO, BICG_BREAKDOWN_OMEGA = 0, 1, 2
 CGLS_RAN_ALL, CGLS_CONVERGED, CGLS_BREAKDOWN = 0, 1, 2
 # CsrDevice.pcg: info["status"] (SPMV_PCG_*); CsrDevice.preconditioner kinds (SPMV_PRECOND_*)
 PCG_RAN_ALL, PCG_CONVERGED, PCG_BREAKDOWN = 0, 1, 2
-PRECOND_JACOBI, PRECOND_BLOCK_JACOBI = 1, 2
-PRECOND_KINDS = {"jacobi": PRECOND_JACOBI, "block_jacobi": PRECOND_BLOCK_JACOBI}
+PRECOND_JACOBI, PRECOND_BLOCK_JACOBI, PRECOND_SSOR, PRECOND_ILU0 = 1, 2, 3, 4
+PRECOND_KINDS = {"jacobi": PRECOND_JACOBI, "block_jacobi": PRECOND_BLOCK_JACOBI, "ssor": PRECOND_SSOR,
+                 "ilu0": PRECOND_ILU0}
+# CsrDevice.triangular / the SSOR and ILU(0) preconditioners (SPMV_TRSV_*, SPMV_ORDER_*)
+TRSV_LOWER, TRSV_UPPER, TRSV_NONUNIT, TRSV_UNIT = 0, 1, 0, 1
+ORDER_NATURAL, ORDER_MULTICOLOR = 0, 1
+ORDERINGS = {"natural": ORDER_NATURAL, "multicolor": ORDER_MULTICOLOR}
+TRSV_INFO = ("rows", "row0", "value_bytes", "entries", "levels", "launches", "widest", "colours", "median",
+             "lanes_per_row", "analysis_us", "upload_us")
+PRECOND_TRI_INFO = ("forward_levels", "forward_launches", "forward_widest", "forward_median", "backward_levels",
+                    "backward_launches", "backward_widest", "backward_median", "colours", "entries_l", "entries_u",
+                    "analysis_us", "factor_us", "upload_us")
 CSR_STREAM_KERNELS = ("csr_stream", "csr_stream_local", "csr_stream_short", "csr_tile")
 HLL_LDS_KERNELS = ("hll_lds", "hll_lds_local", "csr_tile (HLL slab rows)")
 CSR_VARIANTS = {"thread_row": CSR_THREAD_ROW, "wave_row": CSR_WAVE_ROW, "subwave": CSR_SUBWAVE,
@@ -417,16 +427,37 @@ class CsrDevice(_Handle):
                                  f"the handle rows [{row0}, {row1})")
         return np.ascontiguousarray(b)
 
-    def preconditioner(self, kind="jacobi", block=1) -> "Preconditioner":
-        """A Jacobi (kind "jacobi", block 1) or block-Jacobi (kind "block_jacobi", block in [1, 32]) preconditioner of
-        this handle's rows, built on the device (spmv_hip_csr_precond_build); it owns its arrays."""
+    def preconditioner(self, kind="jacobi", block=1, omega=1.0, ordering="natural") -> "Preconditioner":
+        """A preconditioner of this handle's rows; it owns its arrays.  kind "jacobi" (block 1) or "block_jacobi"
+        (block in [1, 32]): built on the device (spmv_hip_csr_precond_build).  kind "ssor" (0 < omega < 2; 1 is
+        symmetric Gauss-Seidel) or "ilu0": two sparse triangular solves (spmv_hip_csr_precond_build_tri), block 1;
+        ordering "natural", or "multicolor": of the rows reordered by a greedy colouring (few dependency levels, more
+        steps)."""
         if kind not in PRECOND_KINDS:
             raise ValueError(f"kind must be one of {sorted(PRECOND_KINDS)}, got {kind!r}")
         if isinstance(block, bool) or int(block) != block or not 1 <= int(block) <= 32:
             raise ValueError(f"block must be an integer in [1, 32], got {block!r}")
-        if kind == "jacobi" and int(block) != 1:
-            raise ValueError(f"jacobi takes block = 1, got {block}")
+        if kind != "block_jacobi" and int(block) != 1:
+            raise ValueError(f"{kind} takes block = 1, got {block}")
+        if ordering not in ORDERINGS:
+            raise ValueError(f"ordering must be one of {sorted(ORDERINGS)}, got {ordering!r}")
+        if kind in ("ssor", "ilu0"):
+            if not np.isfinite(float(omega)) or not 0.0 < float(omega) < 2.0:
+                raise ValueError(f"omega must lie in (0, 2), got {omega!r}")
+            return Preconditioner(self, PRECOND_KINDS[kind], 1, float(omega), ORDERINGS[ordering])
+        if ordering != "natural":
+            raise ValueError(f"{kind} takes ordering = 'natural', got {ordering!r}")
         return Preconditioner(self, PRECOND_KINDS[kind], int(block))
+
+    def triangular(self, lower=True, unit_diagonal=False, ordering="natural") -> "TriangularSolver":
+        """The lower (upper) triangle of this handle's diagonal block as a solver of T x = b on the device
+        (spmv_hip_csr_trsv_build); it owns a copy of the triangle.  ordering: "natural" only."""
+        if ordering not in ORDERINGS:
+            raise ValueError(f"ordering must be one of {sorted(ORDERINGS)}, got {ordering!r}")
+        if ordering != "natural":
+            raise ValueError("a bare triangular solve takes ordering = 'natural': the multicolour order changes which "
+                             "matrix a preconditioner factors")
+        return TriangularSolver(self, bool(lower), bool(unit_diagonal))
 
     def pcg(self, b, iters, tol=0.0, precond=None, variant=CSR_AUTO, bounds=None):
         """Preconditioned CG from x0 = 0 (spmv_hip_csr_pcg) for a symmetric positive definite A; precond: a
@@ -552,16 +583,63 @@ class CsrDevice(_Handle):
         return mk, mx
 
 
+def _check_vector(v, rows, dtype, name, owner):
+    v = np.asarray(v)
+    if v.dtype != dtype:
+        raise ValueError(f"{name} has dtype {v.dtype}, the {owner} holds {np.dtype(dtype)}")
+    if v.ndim != 1 or v.shape[0] != rows:
+        raise ValueError(f"{name} must be a vector of {rows} values, got shape {v.shape}")
+    return np.ascontiguousarray(v)
+
+
+class TriangularSolver(_Handle):
+    """x with T x = b for a triangle of a CsrDevice's diagonal block, resident in HBM in level order
+    (CsrDevice.triangular).  It owns its arrays: the handle it was built from may be freed first."""
+
+    _free = "spmv_hip_trsv_free"
+
+    def __init__(self, dev: CsrDevice, lower: bool, unit_diagonal: bool):
+        super().__init__()
+        _check(nat.lib().spmv_hip_csr_trsv_build(dev.h, TRSV_LOWER if lower else TRSV_UPPER,
+                                                 TRSV_UNIT if unit_diagonal else TRSV_NONUNIT, ORDER_NATURAL,
+                                                 C.byref(self.h)), "spmv_hip_csr_trsv_build")
+        info = self.info()
+        self.rows, self.row0 = info["rows"], info["row0"]
+        self.dtype = np.float64 if info["value_bytes"] == 8 else np.float32
+
+    def info(self) -> dict:
+        out = (C.c_int * len(TRSV_INFO))()
+        _check(nat.lib().spmv_hip_trsv_info(self.h, out), "spmv_hip_trsv_info")
+        return dict(zip(TRSV_INFO, (int(v) for v in out)))
+
+    def solve(self, b):
+        """x with T x = b for b of `rows` values (element i = row row0 + i) of the handle's dtype."""
+        b = _check_vector(b, self.rows, self.dtype, "b", "solver")
+        x = np.zeros(self.rows, dtype=self.dtype)
+        _check(nat.lib().spmv_hip_trsv_solve(self.h, b.ctypes.data_as(C.c_void_p), x.ctypes.data_as(C.c_void_p)),
+               "spmv_hip_trsv_solve")
+        return x
+
+    def solve_on(self, d_b: int, d_x: int, stream: int = 0):
+        """The same on device vectors (b and x must not overlap), asynchronous on `stream` (0 = the library's)."""
+        _check(nat.lib().spmv_hip_trsv_solve_on(self.h, C.c_void_p(d_b), C.c_void_p(d_x), C.c_void_p(stream)),
+               "spmv_hip_trsv_solve_on")
+
+
 class Preconditioner(_Handle):
-    """M^-1 of a Jacobi or block-Jacobi preconditioner of a CsrDevice's rows, resident in HBM (CsrDevice.preconditioner).
-    It owns its arrays: the handle it was built from may be freed first."""
+    """M^-1 of a Jacobi, block-Jacobi, SSOR or ILU(0) preconditioner of a CsrDevice's rows, resident in HBM
+    (CsrDevice.preconditioner).  It owns its arrays: the handle it was built from may be freed first."""
 
     _free = "spmv_hip_precond_free"
 
-    def __init__(self, dev: CsrDevice, kind: int, block: int):
+    def __init__(self, dev: CsrDevice, kind: int, block: int, omega: float = 1.0, ordering: int = ORDER_NATURAL):
         super().__init__()
-        _check(nat.lib().spmv_hip_csr_precond_build(dev.h, int(kind), int(block), C.byref(self.h)),
-               "spmv_hip_csr_precond_build")
+        if kind in (PRECOND_SSOR, PRECOND_ILU0):
+            _check(nat.lib().spmv_hip_csr_precond_build_tri(dev.h, int(kind), int(ordering), float(omega),
+                                                            C.byref(self.h)), "spmv_hip_csr_precond_build_tri")
+        else:
+            _check(nat.lib().spmv_hip_csr_precond_build(dev.h, int(kind), int(block), C.byref(self.h)),
+                   "spmv_hip_csr_precond_build")
         info = self.info()
         self.kind, self.block, self.rows, self.row0 = info["kind"], info["block"], info["rows"], info["row0"]
         self.dtype = np.float64 if info["value_bytes"] == 8 else np.float32
@@ -583,6 +661,29 @@ class Preconditioner(_Handle):
         _check(nat.lib().spmv_hip_precond_apply(self.h, r.ctypes.data_as(C.c_void_p), z.ctypes.data_as(C.c_void_p)),
                "spmv_hip_precond_apply")
         return z
+
+    def tri_info(self) -> dict:
+        """SSOR / ILU(0): levels, launches, widest and median level of the forward and the backward solve, colours
+        (0: natural order), entries of L and of U, microseconds of analysis, factorisation and upload."""
+        out = (C.c_int * len(PRECOND_TRI_INFO))()
+        _check(nat.lib().spmv_hip_precond_tri_info(self.h, out), "spmv_hip_precond_tri_info")
+        return dict(zip(PRECOND_TRI_INFO, (int(v) for v in out)))
+
+    def factors(self):
+        """SSOR / ILU(0): (L, U), each a (row_ptr, col, val) triple in the handle's row numbering with ascending
+        columns, both with their diagonal (ILU(0): L's is exactly 1; SSOR: the triangles of A).  With the multicolour
+        order they are Q^T L Q and Q^T U Q, triangular after the rows are put in (colour, row) order."""
+        out = []
+        for which in (0, 1):
+            rp = np.zeros(self.rows + 1, dtype=np.int32)
+            fn = nat.lib().spmv_hip_precond_factors
+            _check(fn(self.h, which, rp.ctypes.data_as(nat.c_int_p), None, None), "spmv_hip_precond_factors")
+            col = np.zeros(max(int(rp[-1]), 1), dtype=np.int32)
+            val = np.zeros(max(int(rp[-1]), 1), dtype=self.dtype)
+            _check(fn(self.h, which, rp.ctypes.data_as(nat.c_int_p), col.ctypes.data_as(nat.c_int_p),
+                      val.ctypes.data_as(C.c_void_p)), "spmv_hip_precond_factors")
+            out.append((rp, col[:rp[-1]], val[:rp[-1]]))
+        return tuple(out)
 
     def apply_on(self, d_r: int, d_z: int, stream: int = 0):
         """z = M^-1 r on device vectors, asynchronous on `stream` (0 = the library's)."""

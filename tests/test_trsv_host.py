@@ -1,0 +1,264 @@
+"""Sparse triangular solves and the SSOR / ILU(0) preconditioners without a GPU: the entry points are exported, declared
+and bound, the enums match the header, the Python methods check their input before any device call, the host analysis
+(colouring, levels, launch plan) matches a Python restatement, and the new kernels compile for gfx950 without scratch."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import sparsematrixvectormultiplication_amd as sp
+from sparsematrixvectormultiplication_amd import _native as nat
+from _util import HIPCC, compile_kernels
+from conftest import ROOT, golden_path
+
+VGPR_BOUND = 64  # the bound the solver kernels sit under (test_bicgstab_host.py)
+LONG_LEN, CHAIN_ROWS, CHAIN_ENTRIES = 128, 256, 4096  # kTrsvLong, kTrsvChainRows, kTrsvChainEntries
+NEW = {"spmv_hip_csr_trsv_build": 5, "spmv_hip_trsv_solve": 3, "spmv_hip_trsv_solve_on": 4, "spmv_hip_trsv_info": 2,
+       "spmv_hip_trsv_free": 1, "spmv_trsv_colour": 5, "spmv_trsv_levels": 13, "spmv_hip_csr_precond_build_tri": 5,
+       "spmv_hip_precond_tri_info": 2, "spmv_hip_precond_factors": 5}
+
+
+# ---------------------------------------------------------------- Python restatements (test_gpu_trsv.py uses them too)
+def canonical(rp, col, val, row0=0, n=None):
+    """the diagonal block A[row0:row0 + n, row0:row0 + n] as sorted scipy CSR, repeated entries added in entry order in
+    fp64 (np.add.at walks the entries in order)"""
+    import scipy.sparse as sps
+    n = len(rp) - 1 if n is None else n
+    rows = np.repeat(np.arange(len(rp) - 1), np.diff(rp)) - row0
+    cols = np.asarray(col, np.int64) - row0
+    keep = (rows >= 0) & (rows < n) & (cols >= 0) & (cols < n)
+    key, inverse = np.unique(rows[keep] * max(n, 1) + cols[keep], return_inverse=True)
+    sums = np.zeros(len(key))
+    np.add.at(sums, inverse, np.asarray(val, np.float64)[keep])
+    a = sps.csr_matrix((sums, (key // max(n, 1), key % max(n, 1))), shape=(n, n))
+    a.sort_indices()
+    return a
+
+
+def levels_ref(a, lower):
+    """level[i] = 1 + the largest level among the rows i reads on its side of the diagonal"""
+    n = a.shape[0]
+    level = np.zeros(n, np.int64)
+    for i in (range(n) if lower else range(n - 1, -1, -1)):
+        c = a.indices[a.indptr[i]:a.indptr[i + 1]]
+        c = c[c < i] if lower else c[c > i]
+        level[i] = 1 + (level[c].max() if len(c) else 0)
+    return level
+
+
+def plan_ref(t, level):
+    """the launches of a strict triangle t: runs of narrow levels are one launch, every wide level one"""
+    plan = []
+    rows, entries = np.bincount(level)[1:], np.bincount(level, weights=np.diff(t.indptr))[1:]
+    for l, narrow in enumerate((rows <= CHAIN_ROWS) & (entries <= CHAIN_ENTRIES)):
+        if narrow and plan and plan[-1][0] == 1:
+            plan[-1][2] = l + 1
+        else:
+            plan.append([int(narrow), l, l + 1])
+    return plan
+
+
+def colour_ref(a):
+    """greedy first fit in natural order over A + A^T; (colour, the rows by (colour, row))"""
+    s = (a + a.T).tocsr()
+    colour = np.full(a.shape[0], -1)
+    for i in range(a.shape[0]):
+        c = s.indices[s.indptr[i]:s.indptr[i + 1]]
+        used = set(colour[c[c < i]].tolist())
+        colour[i] = next(k for k in range(len(used) + 1) if k not in used)
+    return colour, np.lexsort((np.arange(a.shape[0]), colour))
+
+
+def grid5(g, shift=0.0):
+    import scipy.sparse as sps
+    t = sps.diags([-np.ones(g - 1), np.full(g, 2.0 + shift / 2), -np.ones(g - 1)], [-1, 0, 1])
+    return (sps.kron(sps.eye(g), t) + sps.kron(t, sps.eye(g))).tocsr()
+
+
+def ip(a):
+    return np.ascontiguousarray(a, np.int32).ctypes.data_as(nat.c_int_p)
+
+
+def host_levels(a, lower):
+    n = a.shape[0]
+    rp, col = np.ascontiguousarray(a.indptr, np.int32), np.ascontiguousarray(a.indices, np.int32)
+    level, perm, lptr = np.zeros(n + 1, np.int32), np.zeros(n + 1, np.int32), np.zeros(n + 1, np.int32)
+    split, plan, counts = np.zeros(n + 1, np.int32), np.zeros(3 * n + 3, np.int32), (C.c_longlong * 4)()
+    rc = sp.lib().spmv_trsv_levels(n, ip(rp), ip(col), sp.TRSV_LOWER if lower else sp.TRSV_UPPER, LONG_LEN, CHAIN_ROWS,
+                                   CHAIN_ENTRIES, level.ctypes.data_as(nat.c_int_p), perm.ctypes.data_as(nat.c_int_p),
+                                   lptr.ctypes.data_as(nat.c_int_p), split.ctypes.data_as(nat.c_int_p),
+                                   plan.ctypes.data_as(nat.c_int_p), counts)
+    assert rc == 0
+    levels, launches = int(counts[0]), int(counts[1])
+    return dict(level=level[:n], perm=perm[:n], level_ptr=lptr[:levels + 1], split=split[:levels],
+                plan=plan[:3 * launches].reshape(-1, 3).tolist(), levels=levels, launches=launches,
+                widest=int(counts[2]), entries=int(counts[3]))
+
+
+def host_colour(a):
+    n = a.shape[0]
+    colour, order = np.zeros(n + 1, np.int32), np.zeros(n + 1, np.int32)
+    k = sp.lib().spmv_trsv_colour(n, ip(a.indptr), ip(a.indices), colour.ctypes.data_as(nat.c_int_p),
+                                  order.ctypes.data_as(nat.c_int_p))
+    return k, colour[:n], order[:n]
+
+
+def analysis_cases():
+    import scipy.sparse as sps
+    rng = np.random.default_rng(0)
+    for name in ("dup_entries", "sym_empty_rows", "sym_pattern", "banded_scaled", "general_matrix", "one_by_one"):
+        h = sp.convert_in_csr(sp.read_matrix_market(golden_path(name)))
+        if h.M == h.N:
+            yield name, canonical(np.array(h.row_ptr), np.array(h.col_idx), np.array(h.values))
+    yield "tridiagonal", sps.diags([np.ones(999), np.ones(1000), np.ones(999)], [-1, 0, 1]).tocsr()
+    yield "grid", grid5(24)
+    arrow = sps.lil_matrix((700, 700))
+    arrow.setdiag(1.0)
+    arrow[0, :], arrow[:, 0], arrow[699, :], arrow[:, 699] = 1.0, 1.0, 1.0, 1.0
+    yield "arrow", arrow.tocsr()
+    yield "random", (sps.random(900, 900, density=0.01, random_state=rng) + sps.eye(900)).tocsr()
+
+
+# ---------------------------------------------------------------- exported, declared, bound
+def test_new_symbols_are_exported_declared_and_bound():
+    out = subprocess.run(["nm", "-D", "--defined-only", sp.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
+    header = open(os.path.join(ROOT, "include", "spmv_hip.h")).read()
+    L = sp.lib()
+    for name, nargs in NEW.items():
+        assert name in exported and name in sp.EXPORTED_SYMBOLS, name
+        assert re.search(rf"\b{name}\s*\(", header), name
+        assert len(getattr(L, name).argtypes) == nargs, name
+    assert L.spmv_hip_trsv_free.restype is None
+    assert L.spmv_hip_csr_precond_build_tri.argtypes[3] is C.c_double
+    assert len(L.spmv_hip_csr_precond_build.argtypes) == 4   # the two old kinds keep their entry point
+
+
+def test_enum_values_match_the_header():
+    text = open(os.path.join(ROOT, "include", "spmv_hip.h")).read()
+    for name, value in (("PRECOND_SSOR", 3), ("PRECOND_ILU0", 4), ("ORDER_NATURAL", 0), ("ORDER_MULTICOLOR", 1),
+                        ("TRSV_LOWER", 0), ("TRSV_UPPER", 1), ("TRSV_NONUNIT", 0), ("TRSV_UNIT", 1)):
+        assert re.search(rf"SPMV_{name}\s*=\s*{value}\b", text), name
+        assert getattr(sp, name) == value
+    assert re.search(rf"SPMV_TRSV_INFO_WORDS\s*=\s*{len(sp.device.TRSV_INFO)}\b", text)
+    assert re.search(rf"SPMV_PRECOND_TRI_INFO_WORDS\s*=\s*{len(sp.device.PRECOND_TRI_INFO)}\b", text)
+    src = open(os.path.join(ROOT, "sparsematrixvectormultiplication_amd", "csrc", "hip", "trsv_kernels.hpp")).read()
+    for name, value in (("kTrsvLong", LONG_LEN), ("kTrsvChainRows", CHAIN_ROWS), ("kTrsvChainEntries", CHAIN_ENTRIES)):
+        assert re.search(rf"{name}\s*=\s*{value}\b", src), name
+
+
+# ---------------------------------------------------------------- refused before any device call
+def _handle_without_device(M=6, N=6, dtype=np.float64):
+    dev = sp.CsrDevice.__new__(sp.CsrDevice)
+    sp.device._Handle.__init__(dev)  # a NULL handle: any device call would fail, not raise ValueError
+    dev.M, dev.N, dev.dtype = M, N, dtype
+    return dev
+
+
+@pytest.mark.parametrize("kwargs", [dict(kind="ssor", omega=0.0), dict(kind="ssor", omega=2.0),
+                                    dict(kind="ssor", omega=-0.5), dict(kind="ssor", omega=float("nan")),
+                                    dict(kind="ssor", omega=float("inf")), dict(kind="ilu0", ordering="rcm"),
+                                    dict(kind="ssor", ordering="colour"), dict(kind="ilu0", block=2),
+                                    dict(kind="ssor", block=3), dict(kind="ilu"), dict(kind="ic0"),
+                                    dict(kind="jacobi", ordering="multicolor")])
+def test_preconditioner_rejects_bad_arguments(kwargs):
+    with pytest.raises(ValueError):
+        _handle_without_device().preconditioner(**kwargs)
+
+
+def test_triangular_rejects_orderings_and_bad_vectors():
+    dev = _handle_without_device()
+    for ordering in ("multicolor", "rcm"):
+        with pytest.raises(ValueError):
+            dev.triangular(ordering=ordering)
+    T = sp.TriangularSolver.__new__(sp.TriangularSolver)
+    sp.device._Handle.__init__(T)
+    T.rows, T.row0, T.dtype = 6, 0, np.float64
+    for b in (np.zeros(5), np.zeros(7), np.zeros((6, 1)), np.zeros(6, np.float32), np.zeros(6, np.int64)):
+        with pytest.raises(ValueError):
+            T.solve(b)
+
+
+def test_entry_points_refuse_null_arguments():
+    if sp.device_count() > 0:
+        pytest.skip("a HIP device is present; the no-device behaviour is checked on CPU hosts")
+    L = sp.lib()
+    out = C.c_void_p()
+    buf, info = (C.c_double * 8)(), (C.c_int * 16)()
+    assert L.spmv_hip_csr_trsv_build(None, 0, 0, 0, C.byref(out)) == -1 and not out
+    assert L.spmv_hip_csr_precond_build_tri(None, sp.PRECOND_ILU0, 0, 1.0, C.byref(out)) == -1 and not out
+    assert L.spmv_hip_trsv_solve(None, buf, buf) == -1 and L.spmv_hip_trsv_solve_on(None, buf, buf, None) == -1
+    assert L.spmv_hip_trsv_info(None, info) == -1 and L.spmv_hip_precond_tri_info(None, info) == -1
+    assert L.spmv_hip_precond_factors(None, 0, info, None, None) == -1
+    L.spmv_hip_trsv_free(None)   # a no-op
+
+
+def test_host_analysis_refuses_null_arguments():
+    L = sp.lib()                 # host functions: with or without a device
+    assert L.spmv_trsv_colour(3, None, None, None, None) == -1
+    assert L.spmv_trsv_levels(3, None, None, 0, 1, 1, 1, None, None, None, None, None, None) == -1
+
+
+# ---------------------------------------------------------------- the host analysis
+@pytest.mark.parametrize("name,a", list(analysis_cases()), ids=lambda v: v if isinstance(v, str) else "")
+def test_levels_permutation_and_plan_match_the_restatement(name, a):
+    import scipy.sparse as sps
+    n = a.shape[0]
+    for lower in (True, False):
+        got = host_levels(a, lower)
+        t = (sps.tril(a, -1) if lower else sps.triu(a, 1)).tocsr()
+        level = levels_ref(a, lower)
+        length = np.diff(t.indptr)
+        assert np.array_equal(got["level"], level), name
+        assert got["levels"] == (level.max() if n else 0) and got["entries"] == t.nnz
+        assert np.array_equal(got["perm"], np.lexsort((np.arange(n), length >= LONG_LEN, level))), name
+        assert np.array_equal(got["level_ptr"], np.concatenate([[0], np.cumsum(np.bincount(level)[1:])])), name
+        first_long = [p0 + int(np.sum(length[got["perm"][p0:p1]] < LONG_LEN))
+                      for p0, p1 in zip(got["level_ptr"][:-1], got["level_ptr"][1:])]
+        assert got["split"].tolist() == first_long, name
+        assert got["plan"] == plan_ref(t, level) and got["widest"] == np.bincount(level)[1:].max(), name
+    if name == "tridiagonal":
+        assert got["levels"] == n and got["launches"] == 1
+    if name == "arrow":
+        assert np.max(length) >= LONG_LEN      # the long-row side of the split is exercised
+
+
+@pytest.mark.parametrize("g", [7, 64])
+def test_grid_levels_and_colours(g):
+    a = grid5(g)
+    assert host_levels(a, True)["levels"] == host_levels(a, False)["levels"] == 2 * g - 1
+    k, colour, order = host_colour(a)
+    ref_colour, ref_order = colour_ref(a)
+    assert k == 2 and np.array_equal(colour, ref_colour) and np.array_equal(order, ref_order)
+    p = a[order][:, order].tocsr()
+    assert host_levels(p, True)["levels"] == host_levels(p, False)["levels"] == 2
+    assert host_levels(p, True)["launches"] == (2 if g * g // 2 > CHAIN_ROWS else 1)   # wide levels: one launch each
+
+
+@pytest.mark.parametrize("name,a", list(analysis_cases()), ids=lambda v: v if isinstance(v, str) else "")
+def test_colouring_matches_the_restatement(name, a):
+    k, colour, order = host_colour(a)
+    ref_colour, ref_order = colour_ref(a)
+    assert np.array_equal(colour, ref_colour) and np.array_equal(order, ref_order)
+    assert k == (ref_colour.max() + 1 if a.shape[0] else 0)
+    s = (a + a.T).tocoo()
+    off = s.row != s.col
+    assert np.all(colour[s.row[off]] != colour[s.col[off]])
+
+
+# ---------------------------------------------------------------- the kernels
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+def test_trsv_kernels_compile_for_gfx950_without_scratch():
+    kernels = {k: v for k, v in compile_kernels("spmv_trsv.hip").items() if "trsv_" in k or "ilu0_" in k}
+    for n in ("trsv_levelIdLb0E", "trsv_levelIdLb1E", "trsv_levelIfLb0E", "trsv_levelIfLb1E", "trsv_chainIdLb0E",
+              "trsv_chainIdLb1E", "trsv_chainIfLb0E", "trsv_chainIfLb1E", "ilu0_level", "ilu0_chain"):
+        assert any(n in k for k in kernels), (n, sorted(kernels))
+    for name, v in kernels.items():
+        assert v.scratch == 0, f"{name} spills {v.scratch} bytes of scratch ({v.vgprs} VGPRs)"
+        assert v.vgprs <= VGPR_BOUND, f"{name}: {v.vgprs} VGPRs > {VGPR_BOUND}"
+        assert v.lds == 0, f"{name}: {v.lds} bytes of LDS, the header says none"   # trsv_kernels.hpp: 0 bytes
+    pcg = {k: v for k, v in compile_kernels("spmv_pcg.hip").items() if "pcg_dots" in k}
+    assert len(pcg) == 2 and all(v.scratch == 0 and v.vgprs <= VGPR_BOUND for v in pcg.values()), pcg
