@@ -1009,7 +1009,9 @@ __global__ __launch_bounds__(kBlock) void csr_long_pieces(int count, const int4 
             xv[2 * u] = gather(x, c[u].x);
             xv[2 * u + 1] = gather(x, c[u].y);
         }
-        if (e0 < n0) v[0].x = T(0);  // only lane 0 of the first trip of an odd-start piece
+        // only lane 0 of the first trip of an odd-start piece: the entry before it is another row's, and its x may be
+        // NaN or infinite (0 * x is no 0 then), so the x goes as well as the value
+        if (e0 < n0) v[0].x = xv[0] = T(0);
 #pragma unroll
         for (int u = 0; u < kUnits; ++u) {
             a0 += v[u].x * xv[2 * u];

@@ -185,6 +185,76 @@ def assert_same_numbers(a, b, what=""):
                            f"{a.reshape(-1)[bad[0]]!r} vs {b.reshape(-1)[bad[0]]!r}")
 
 
+# ---- poison: what 0 x something hides.  A NaN or an infinity in x (or in a stored value) must reach exactly the rows
+# that store an entry reading it, and change no bit of any other row: no kernel has atomics and no launch decision
+# reads values, so a row's sequence of adds is fixed by the structure.  Judged against the structure and the serial
+# oracle only.
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
+
+
+def _same_bits(y_clean, y_poisoned, rows, what):
+    bad = rows[_bits(y_clean)[rows] != _bits(y_poisoned)[rows]]
+    assert bad.size == 0, (f"{what}: {bad.size} rows that read nothing poisoned changed bits; first row {bad[0]}: "
+                           f"{y_clean[bad[0]]!r} -> {y_poisoned[bad[0]]!r}")
+
+
+def rows_reading(row_ptr, col, columns_mask):
+    """Mask of the rows that store an entry in a column of columns_mask."""
+    row_ptr = np.asarray(row_ptr, dtype=np.int64)
+    hit = np.concatenate([[0], np.cumsum(columns_mask[np.asarray(col)], dtype=np.int64)])
+    return hit[row_ptr[1:]] > hit[row_ptr[:-1]]
+
+
+def assert_poison_x(y_clean, y_poisoned, row_ptr, col, val, x_poisoned, oracle_y, what=""):
+    """y_poisoned = A x_poisoned against y_clean (the same handle and variant on the same x with finite values in the
+    poisoned places) and oracle_y (the serial fp64 oracle on x_poisoned).  A row that stores no entry in a non-finite
+    column keeps y_clean's bits; a row that stores one has the oracle's class (NaN, +Inf or -Inf), which does not
+    depend on the order of the adds while finite partial sums cannot overflow: values and finite x within [-1, 1]."""
+    y_clean, y_poisoned, oracle_y = np.asarray(y_clean), np.asarray(y_poisoned), np.asarray(oracle_y, dtype=np.float64)
+    val, x_poisoned = np.asarray(val), np.asarray(x_poisoned)
+    M = len(row_ptr) - 1
+    assert y_clean.shape == y_poisoned.shape == oracle_y.shape == (M,), f"{what}: shapes"
+    assert y_clean.dtype == y_poisoned.dtype, f"{what}: {y_clean.dtype} vs {y_poisoned.dtype}"
+    poisoned = ~np.isfinite(x_poisoned)
+    assert np.all(np.isfinite(val)) and (val.size == 0 or np.abs(val).max() <= 1), f"{what}: values beyond [-1, 1]"
+    assert np.abs(x_poisoned[~poisoned]).max(initial=0) <= 1, f"{what}: finite x beyond [-1, 1]"
+    touched = rows_reading(row_ptr, col, poisoned)
+    assert not np.isfinite(oracle_y[touched]).any() and np.isfinite(oracle_y[~touched]).all(), \
+        f"{what}: the oracle disagrees with the structure about which rows read a poisoned column"
+    _same_bits(y_clean, y_poisoned, np.flatnonzero(~touched), what)
+    y = y_poisoned.astype(np.float64)
+    for name, want, got in (("NaN", np.isnan(oracle_y), np.isnan(y)), ("+Inf", oracle_y == np.inf, y == np.inf),
+                            ("-Inf", oracle_y == -np.inf, y == -np.inf)):
+        bad = np.flatnonzero(touched & (want != got))
+        assert bad.size == 0, (f"{what}: {bad.size} rows that read a poisoned column are not {name} where the oracle "
+                               f"is (or are where it is not); first row {bad[0]}: {y_poisoned[bad[0]]!r}, oracle "
+                               f"{oracle_y[bad[0]]!r}")
+
+
+def assert_poison_values(y_clean, y_poisoned, poisoned_rows, what=""):
+    """Exactly the rows holding a NaN stored value are NaN; every other row keeps the clean handle's bits."""
+    y_clean, y_poisoned = np.asarray(y_clean), np.asarray(y_poisoned)
+    assert y_clean.shape == y_poisoned.shape and y_clean.dtype == y_poisoned.dtype, f"{what}: shapes"
+    mask = np.zeros(len(y_clean), dtype=bool)
+    mask[np.asarray(poisoned_rows, dtype=np.int64)] = True
+    bad = np.flatnonzero(mask & ~np.isnan(y_poisoned))
+    assert bad.size == 0, f"{what}: row {bad[0]} holds a NaN value and is {y_poisoned[bad[0]]!r}"
+    assert np.isfinite(y_clean).all(), f"{what}: the clean result is not finite"
+    _same_bits(y_clean, y_poisoned, np.flatnonzero(~mask), what)
+
+
+def assert_guard_bands(buffer_bytes_before, buffer_bytes_after, what=""):
+    """The bytes around a caller's y are what they were."""
+    a = np.frombuffer(bytes(buffer_bytes_before), dtype=np.uint8)
+    b = np.frombuffer(bytes(buffer_bytes_after), dtype=np.uint8)
+    assert a.size == b.size and a.size > 0, f"{what}: guard bands of {a.size} and {b.size} bytes"
+    bad = np.flatnonzero(a != b)
+    assert bad.size == 0, (f"{what}: {bad.size} guard bytes changed; first at byte {bad[0]}: "
+                           f"{a[bad[0]]:#04x} -> {b[bad[0]]:#04x}")
+
+
 def random_csr(rng, M, N, mean_row, max_row=None, empty_frac=0.0, dtype=np.float64):
     """Random CSR with sorted, distinct columns per row."""
     max_row = min(N, max_row or max(1, 4 * mean_row))

@@ -1,11 +1,13 @@
 """Host-only: the fp32 row gate (assert_parity_f32) is sound -- fp32 sums of seeded rows in any of the orders the
 kernels use pass it -- and sharp -- one dropped entry fails it where the norm-wise check passes; the wide-range
-generator stays in the normal range and the oracle obeys the power-of-two scaling identity bit for bit."""
+generator stays in the normal range and the oracle obeys the power-of-two scaling identity bit for bit; the poison helpers (assert_poison_x, assert_poison_values,
+assert_guard_bands) reject a leaked or a missing NaN, a one-ulp change, an infinity of the wrong sign and one changed
+guard byte."""
 import numpy as np
 import pytest
 
-from _util import (FP32_NORMWISE_RTOL, WIDE_EXP, assert_parity, assert_parity_f32, assert_same_numbers, random_csr,
-                   scale_rows, scaled_copy, scaling, wide_range)
+from _util import (FP32_NORMWISE_RTOL, WIDE_EXP, assert_guard_bands, assert_parity, assert_parity_f32, assert_poison_values,
+                   assert_poison_x, assert_same_numbers, random_csr, scale_rows, scaled_copy, scaling, wide_range)
 
 
 def fp32_sequential(p):
@@ -137,3 +139,102 @@ def test_wide_range_generator_is_normal_and_the_oracle_obeys_the_identity(oracle
         # the fp32 sums of the scaled data are the scaled fp32 sums (what the GPU identity relies on)
         assert_same_numbers(simulate("lanes+xor", rp, col, vs, xs), scale_rows(simulate("lanes+xor", rp, col, val, x), dr),
                             "simulated fp32 sums")
+
+
+# ---- the poison helpers on a hand-made 3-row example: row 0 reads columns 0 and 2, row 1 column 1, row 2 is empty
+POISON_RP = np.array([0, 2, 3, 3], dtype=np.int32)
+POISON_COL = np.array([0, 2, 1], dtype=np.int32)
+
+
+def poison_example(oracle, dtype, poison):
+    val = np.array([0.5, -0.25, 0.75], dtype=dtype)
+    x = np.array([0.5, -1.0, 0.25], dtype=dtype)
+    xp = x.copy()
+    xp[2] = poison                                                       # read by row 0 only
+    ref = oracle.csr_serial if dtype == np.float64 else oracle.csr_f32_accum64
+    y_clean = ref(POISON_RP, POISON_COL, val, x).astype(dtype)
+    y_poisoned = ref(POISON_RP, POISON_COL, val, xp).astype(dtype)
+    return val, xp, y_clean, y_poisoned, ref(POISON_RP, POISON_COL, val, xp)
+
+
+def one_ulp(v):
+    return np.nextafter(v, np.asarray(2, dtype=v.dtype))
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_poison_x_helper_accepts_the_oracle_and_rejects_every_kind_of_leak(oracle, dtype):
+    val, xp, y_clean, y, ref = poison_example(oracle, dtype, np.nan)
+    assert np.isnan(y[0]) and y[1] == y_clean[1] == -0.75 and y[2] == 0
+    args = (POISON_RP, POISON_COL, val, xp, ref)
+    assert_poison_x(y_clean, y, *args)
+    for row in (1, 2):                                                   # a leaked NaN in an untouched row
+        bad = y.copy()
+        bad[row] = np.nan
+        with pytest.raises(AssertionError, match="changed bits"):
+            assert_poison_x(y_clean, bad, *args)
+    bad = y.copy()
+    bad[0] = y_clean[0]                                                  # a missing NaN in a touched row
+    with pytest.raises(AssertionError, match="not NaN"):
+        assert_poison_x(y_clean, bad, *args)
+    bad = y.copy()
+    bad[1] = one_ulp(bad[1])                                             # one ulp in an untouched row
+    assert bad[1] != y[1] and abs(float(bad[1]) - float(y[1])) <= 1e-7
+    with pytest.raises(AssertionError, match="changed bits"):
+        assert_poison_x(y_clean, bad, *args)
+    bad = y.copy()
+    bad[2] = -0.0                                                        # -0 for +0: the same number, other bits
+    with pytest.raises(AssertionError, match="changed bits"):
+        assert_poison_x(y_clean, bad, *args)
+    with pytest.raises(AssertionError, match=r"beyond \[-1, 1\]"):      # the class argument needs the bound
+        assert_poison_x(y_clean, y, POISON_RP, POISON_COL, val * 4, xp, ref)
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_poison_x_helper_tells_the_infinities_apart(oracle, dtype):
+    val, xp, y_clean, y, ref = poison_example(oracle, dtype, np.inf)
+    assert ref[0] == -np.inf                                             # -0.25 * +Inf
+    args = (POISON_RP, POISON_COL, val, xp, ref)
+    assert_poison_x(y_clean, y, *args)
+    for wrong in (np.inf, np.nan, y_clean[0]):                           # +Inf where the oracle has -Inf, NaN, finite
+        bad = y.copy()
+        bad[0] = wrong
+        with pytest.raises(AssertionError, match="oracle"):
+            assert_poison_x(y_clean, bad, *args)
+    xp2 = xp.copy()
+    xp2[0] = np.inf                                                      # +Inf - Inf in row 0: NaN, and only NaN
+    ref2 = (oracle.csr_serial if dtype == np.float64 else oracle.csr_f32_accum64)(POISON_RP, POISON_COL, val, xp2)
+    assert np.isnan(ref2[0])
+    y2 = ref2.astype(dtype)
+    assert_poison_x(y_clean, y2, POISON_RP, POISON_COL, val, xp2, ref2)
+    with pytest.raises(AssertionError, match="not NaN"):
+        assert_poison_x(y_clean, y, POISON_RP, POISON_COL, val, xp2, ref2)
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_poison_values_helper_rejects_leaked_missing_and_one_ulp(oracle, dtype):
+    _, _, y_clean, y, _ = poison_example(oracle, dtype, np.nan)          # (row 0 NaN: as if its stored value were)
+    assert_poison_values(y_clean, y, [0])
+    bad = y.copy()
+    bad[2] = np.nan
+    with pytest.raises(AssertionError, match="changed bits"):            # a leaked NaN
+        assert_poison_values(y_clean, bad, [0])
+    with pytest.raises(AssertionError, match="holds a NaN value"):       # a missing NaN
+        assert_poison_values(y_clean, y, [0, 1])
+    with pytest.raises(AssertionError, match="holds a NaN value"):       # an infinity is not the NaN a NaN value gives
+        assert_poison_values(y_clean, np.where(np.isnan(y), np.inf, y).astype(dtype), [0])
+    bad = y.copy()
+    bad[1] = one_ulp(bad[1])
+    with pytest.raises(AssertionError, match="changed bits"):            # one ulp
+        assert_poison_values(y_clean, bad, [0])
+
+
+def test_guard_band_helper_rejects_one_changed_byte():
+    before = bytes([0xA5]) * 512
+    assert_guard_bands(before, bytes(before))
+    for at in (0, 255, 256, 511):
+        after = bytearray(before)
+        after[at] ^= 1
+        with pytest.raises(AssertionError, match=f"first at byte {at}"):
+            assert_guard_bands(before, after)
+    with pytest.raises(AssertionError, match="guard bands of"):
+        assert_guard_bands(before, before[:-1])
