@@ -605,13 +605,60 @@ enum { SPMV_FACTOR_L = 0, SPMV_FACTOR_U = 1 };
 int spmv_hip_csr_precond_build_tri(const spmv_csr_dev *m, int kind, int ordering, double omega, spmv_precond **out);
 int spmv_hip_precond_tri_info(const spmv_precond *P, int *info);
 int spmv_hip_precond_factors(const spmv_precond *P, int which, int *row_ptr, int *col, void *val);
+/* FSAI, a factorised sparse approximate inverse (Kolotilina and Yeremin) of the handle's own diagonal block (the same
+ * spmv_precond type: info (block = 1), apply, apply_on, free, spmv_hip_csr_pcg and spmv_hip_csr_pbicgstab take it): a
+ * sparse lower-triangular G with G^T G ~ A^-1, applied as z = G^T (G r), two SpMVs and no triangular solve.
+ * The block is made canonical as for the triangular solves (local columns, sorted rows, repeats added in entry order in
+ * fp64) and only its lower triangle is read: A~ is the symmetric matrix with that lower triangle (A itself when A is
+ * symmetric; for a nonsymmetric A the preconditioner is the FSAI of A~, still a valid right preconditioner).
+ * Row i of G has the pattern S_i = {i} and the stored columns j < i of row i; with more than cap - 1 of those the
+ * cap - 1 of largest |a_ij| stay, ties to the larger column (cap in [1, 32]; an explicit zero is a stored column).  With
+ * S_i ascending, i last, row i of G solves C^T g = e_last, C C^T = A~[S_i, S_i] the Cholesky factorisation (an entry
+ * A~[a, b], a >= b, is read from canonical row a and is 0 when the row does not store it): diag(G A~ G^T) = 1 and
+ * (G A~)_ij = 0 for j in S_i, j != i.  cap = 1 gives G = diag(a_ii^-1/2).  G^T G is symmetric positive definite
+ * whatever A is.  No powers of A enlarge the pattern and G is not filtered afterwards.
+ * The rows are built on the device, each by the smallest power of two >= |S_i| (at least 4) of lanes, in fp64 in a
+ * fixed order without atomics, and rounded once to the handle's dtype: two builds give the same bytes.  G is an
+ * ordinary whole rows x rows CSR handle with whatever plan upload picks, G^T is spmv_hip_csr_transpose of it (the
+ * bit-exact transpose of the rounded G).  P owns both and the vector between the products: it may outlive the handle
+ * it was built from, and one P serves one stream at a time.  On a row-range handle this is FSAI of the diagonal block:
+ * across ranks, block-Jacobi of FSAI.  CSR handles only, one right-hand side.
+ * The apply runs the two handles' own launches; r and z hold `rows` values at local row 0 and must not overlap (an r
+ * or z that is not 128-byte aligned takes the gather kernels; an aligned r is read as spmv_hip_csr_run_on reads its x,
+ * in whole 128-byte lines, so up to the end of the line that holds its last value).  Its rounding is that of the SpMV kernels, twice: the
+ * sentence "accumulated in double, rounded once" of the other kinds does not describe this one -- t = G r is rounded to
+ * the handle's dtype before G^T multiplies it.  The launches do not look at a solver's stop state: after a stop they
+ * rewrite z with the bits it holds.
+ * -1 (*out stays NULL, the HIP error state stays clean, the handle still works): a row without a diagonal entry (named),
+ * a Cholesky pivot that is not positive or not finite (A~[S_i, S_i] is not positive definite; the first such row is
+ * named), an entry of G that is not finite in the handle's dtype, a cap outside [1, 32], a non-square matrix, a
+ * tiles-only handle.
+ *   spmv_hip_precond_fsai_info  info[SPMV_PRECOND_FSAI_INFO_WORDS] = cap, entries of G, rows that lost entries to the
+ *                               cap, the largest |S_i|, the plan of G and of G^T (0 gather kernels, 1 x-window, 2
+ *                               x-window with a pattern plan, 3 csr_tile), microseconds of analysis (download,
+ *                               canonical rows, patterns), of the device build, and of the two uploads with the
+ *                               transpose
+ *   spmv_hip_precond_factors    G for SPMV_FACTOR_L, G^T for SPMV_FACTOR_U, as their handles hold them
+ *   spmv_fsai_plan              the host pass (no device needed) on an n x n CSR matrix with local columns (columns
+ *                               outside [0, n) are ignored; rows may be unsorted and repeat a column, repeats are added
+ *                               in entry order): g_ptr[n + 1] and g_col (room for min(n cap, row_ptr[n] + n) entries)
+ *                               = the patterns S_i; width_ptr[5] and width_rows[n] = the rows of 4 << k lanes are
+ *                               width_rows[width_ptr[k] .. width_ptr[k + 1]), ascending; counts[4] = entries of G,
+ *                               rows that lost entries to the cap, the largest |S_i|, the first row that stores no
+ *                               diagonal entry (-1: none).  -1: bad arguments or out of memory. */
+enum { SPMV_PRECOND_FSAI = 5 };
+enum { SPMV_PRECOND_FSAI_INFO_WORDS = 9 };
+int spmv_hip_csr_precond_build_fsai(const spmv_csr_dev *m, int cap, spmv_precond **out);
+int spmv_hip_precond_fsai_info(const spmv_precond *P, int *info);
+int spmv_fsai_plan(int n, const int *row_ptr, const int *col, const double *val, int cap, int *g_ptr, int *g_col,
+                   int *width_ptr, int *width_rows, long long *counts);
 /* Preconditioned CG for a symmetric positive definite A and M, x0 = 0 (P = NULL: M = I, z is r itself):
  *   r = b, z = M^-1 r, p = z, rz = r.z, rr0 = r.r
  *   each step: q = A p, alpha = rz / p.q, x += alpha p, r -= alpha q, z = M^-1 r, rz' = r.z, rr = r.r,
  *              stop (CONVERGED) if rr <= tol^2 rr0, beta = rz' / rz, p = z + beta p
  * The product, the communicator, the bounds and the all-gatherv of p are those of spmv_hip_csr_cg (no halo variant).
  * Jacobi is fused into the x / r update with both dots; a block-Jacobi apply is a pass of its own that makes the dots;
- * an SSOR or ILU(0) apply is its two solves, then one pass for the two dots.
+ * an SSOR or ILU(0) apply is its two solves, an FSAI apply its two SpMVs, then one pass for the two dots.
  * P = NULL, or Jacobi on a matrix whose diagonal is exactly 1, with tol = 0 and no breakdown gives spmv_hip_csr_cg's
  * x and rr_hist bit for bit.
  * Breakdown: p.q <= 0, rz' <= 0 while rr > 0, or any non-finite scalar (A or M not SPD); x stays at the last full
@@ -628,7 +675,7 @@ int spmv_hip_csr_pcg(spmv_csr_dev *m, const spmv_precond *P, int variant, int it
  * residual and tol, the half step, the breakdown rules, rr_hist and info mean what they mean there:
  *   p^ = M^-1 p, v = A p^, ..., s^ = M^-1 s, t = A s^, x += alpha p^ + omega s^ (a half step: x += alpha p^)
  * With a communicator p^ and s^ (the products' inputs) are all-gathered.  Jacobi is fused into the s and p updates;
- * block-Jacobi, SSOR and ILU(0) are applied after them.
+ * block-Jacobi, SSOR, ILU(0) and FSAI are applied after them.
  * P = NULL gives spmv_hip_csr_bicgstab's bits.  -1: as spmv_hip_csr_bicgstab, and a P that does not fit the handle. */
 int spmv_hip_csr_pbicgstab(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, double tol,
                            const int *bounds, const void *b_host, void *x_host, double *rr_hist, int *info,

@@ -241,6 +241,10 @@ _PROTOTYPES = {
     "spmv_hip_csr_precond_build_tri": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_void_p)]),
     "spmv_hip_precond_tri_info": (C.c_int, [C.c_void_p, c_int_p]),
     "spmv_hip_precond_factors": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_int_p, C.c_void_p]),
+    "spmv_hip_csr_precond_build_fsai": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "spmv_hip_precond_fsai_info": (C.c_int, [C.c_void_p, c_int_p]),
+    "spmv_fsai_plan": (C.c_int, [C.c_int, c_int_p, c_int_p, c_double_p, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p,
+                                 C.POINTER(C.c_longlong)]),
     "spmv_hip_csr_pcg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, c_int_p, C.c_void_p,
                                    C.c_void_p, c_double_p, c_double_p, c_int_p, c_float_p]),
     "spmv_hip_csr_pbicgstab": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, c_int_p, C.c_void_p,

@@ -183,13 +183,24 @@ struct spmv_precond {
     int value_bytes = 8;      // the handle's dtype
     void *inv = nullptr;      // ceil(rows / block) * block^2 values of that dtype (layout above); owned
     struct spmv_tri_precond *tri = nullptr;  // SSOR / ILU0: the two triangular solves (spmv_trsv.hip); owned, inv is NULL
+    struct spmv_fsai_precond *fsai = nullptr;  // FSAI: the handles of G and G^T (spmv_fsai.hip); owned, inv is NULL
 };
 
-// SSOR and ILU(0) take a path of their own wherever Jacobi / block-Jacobi are told apart by P->block
-inline bool precond_is_tri(const spmv_precond *P) { return P && P->tri != nullptr; }
 // spmv_trsv.hip: z = M^-1 r by P's two solves on stream s (flags as pc_apply: a stopped solver's launches return)
 int precond_tri_apply(const spmv_precond *P, const void *r, void *z, const int *flags, hipStream_t s);
 void precond_tri_free(struct spmv_tri_precond *tp);
+// spmv_fsai.hip: z = G^T (G r) by the two handles' own launches on stream s (they do not look at a solver's flags: after
+// a stop r no longer changes, so z is rewritten with the bits it holds)
+int precond_fsai_apply(const spmv_precond *P, const void *r, void *z, hipStream_t s);
+void precond_fsai_free(struct spmv_fsai_precond *fp);
+int precond_fsai_factors(const spmv_precond *P, int which, int *row_ptr, int *col, void *val);
+
+// SSOR, ILU(0) and FSAI take a path of their own wherever Jacobi / block-Jacobi are told apart by P->block: an apply
+// through P's own launches (precond_own_apply), then one pass for whatever dots the solver needs
+inline bool precond_has_own_apply(const spmv_precond *P) { return P && (P->tri != nullptr || P->fsai != nullptr); }
+inline int precond_own_apply(const spmv_precond *P, const void *r, void *z, const int *flags, hipStream_t s) {
+    return P->fsai ? precond_fsai_apply(P, r, z, s) : precond_tri_apply(P, r, z, flags, s);
+}
 
 // z = M^-1 r on P's rows (r, z at local row 0) on stream s; flags / part as pc_apply; grid 0: by the row count
 template <typename T, bool DOTS>

@@ -16,7 +16,8 @@
 //           repeats inside a block)
 //   TRI     x += alpha p, r -= alpha q (6), then SSOR's / ILU(0)'s two solves (spmv_trsv.hip), then pcg_dots: r.r and
 //           r.z by the walk and the fold of the other modes (2 more reads); the solves' last kernel is a level of a few
-//           rows, so the dots are a pass of their own rather than fused into it
+//           rows, so the dots are a pass of their own rather than fused into it; FSAI's two SpMVs (spmv_fsai.hip) take
+//           the same path: its launches are the handles' own, which make no dots
 //
 // pcg_dot (p.q, 2 values) and pcg_update_p (p = z + beta p, 3) complete the step: fp64 Jacobi PCG moves 13 values =
 // 104 B per row against csr_cg's 11 (88 B).  The scalars and the stop state never leave the device; after a stop the
@@ -199,7 +200,7 @@ int pcg_run(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, doub
             const PcgBuffers &b, int *steps_run) {
     const long long n = m->M_local;
     const int grid = (int)std::max<long long>(1, std::min<long long>(kNormBlocks, (n + kBlock - 1) / kBlock));
-    const int mode = !P ? kModeNone : precond_is_tri(P) ? kModeTri : P->block == 1 ? kModeJacobi : kModeBlock;
+    const int mode = !P ? kModeNone : precond_has_own_apply(P) ? kModeTri : P->block == 1 ? kModeJacobi : kModeBlock;
     const double tol2 = tol * tol;
     T *p_own = (T *)m->x + m->row0, *q_own = (T *)m->y + m->row0, *x_own = (T *)b.x + m->row0;
     T *r = (T *)b.r, *z = (T *)b.z;
@@ -217,7 +218,7 @@ int pcg_run(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, doub
     else if (mode == kModeBlock)
         precond_launch<T, true>(P, r, z, nullptr, b.part, grid, g_stream);
     else {
-        if (precond_tri_apply(P, r, z, nullptr, g_stream)) return -1;
+        if (precond_own_apply(P, r, z, nullptr, g_stream)) return -1;
         hipLaunchKernelGGL((pcg_dots<T>), g, blk, 0, g_stream, n, (const int *)nullptr, (const T *)r, (const T *)z, b.part);
     }
     if (reduce(2, kPcgRr)) return -1;
@@ -242,7 +243,7 @@ int pcg_run(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, doub
             if (mode == kModeBlock) {
                 precond_launch<T, true>(P, r, z, fl, b.part, grid, g_stream);
             } else {
-                if (precond_tri_apply(P, r, z, fl, g_stream)) return -1;
+                if (precond_own_apply(P, r, z, fl, g_stream)) return -1;
                 hipLaunchKernelGGL((pcg_dots<T>), g, blk, 0, g_stream, n, fl, (const T *)r, (const T *)z, b.part);
             }
         }

@@ -7,7 +7,8 @@
 // of ceil(rows / b) b^2 doubles, freed on every path.
 //
 // SSOR and ILU(0) (spmv_hip_csr_precond_build_tri) are the same spmv_precond with P->tri set: spmv_trsv.hip builds and
-// applies them, free / info / apply / apply_on here hand them on.
+// applies them, free / info / apply / apply_on here hand them on.  FSAI (spmv_hip_csr_precond_build_fsai) likewise, with
+// P->fsai set: spmv_fsai.hip.
 #include "spmv_internal.hpp"
 
 #include <climits>
@@ -96,7 +97,7 @@ int precond_build(const spmv_csr_dev *m, int kind, int b, spmv_precond **out) {
 
 int precond_apply_launch(const spmv_precond *P, const void *d_r, void *d_z, hipStream_t s) {
     if (!P->rows) return 0;
-    if (precond_is_tri(P)) return precond_tri_apply(P, d_r, d_z, nullptr, s);
+    if (precond_has_own_apply(P)) return precond_own_apply(P, d_r, d_z, nullptr, s);
     if (P->value_bytes == 8) precond_launch<double, false>(P, d_r, d_z, nullptr, nullptr, 0, s);
     else precond_launch<float, false>(P, d_r, d_z, nullptr, nullptr, 0, s);
     HIP_TRY(hipGetLastError());
@@ -128,6 +129,7 @@ extern "C" void spmv_hip_precond_free(spmv_precond *P) {
     if (!P) return;
     (void)hipFree(P->inv);
     precond_tri_free(P->tri);
+    precond_fsai_free(P->fsai);
     delete P;
 }
 

@@ -2,8 +2,9 @@
 // (include/spmv_hip.h; the kernels are in trsv_kernels.hpp, the level analysis and the colouring in host/trsv_plan.c).
 //
 // The build, once per object, on the host except for the factorisation:
-//   1. the handle's CSR arrays are downloaded and the diagonal block A[row0:row1, row0:row1] is made canonical: local
-//      columns, every row sorted by column (a stable sort), entries that repeat a column added in entry order in fp64;
+//   1. the handle's CSR arrays are downloaded and the diagonal block A[row0:row1, row0:row1] is made canonical
+//      (canon_rows.hpp, shared with spmv_fsai.hip): local columns, every row sorted by column (a stable sort), entries
+//      that repeat a column added in entry order in fp64;
 //   2. ordering MULTICOLOR: spmv_trsv_colour, the rows ordered by (colour, row), the canonical matrix permuted;
 //   3. spmv_trsv_levels on each triangle: levels, the level order, the launch plan;
 //   4. ILU(0) only: the canonical matrix goes to the device in fp64 and ilu0_level / ilu0_chain factor it in place with
@@ -19,22 +20,15 @@
 // (its columns are stored in the caller's numbering), so no kernel exists only to permute.
 #include "spmv_internal.hpp"
 
-#include <algorithm>
 #include <climits>
 #include <cmath>
 #include <memory>
 
+#include "canon_rows.hpp"
 #include "precond_kernels.hpp"
 #include "trsv_kernels.hpp"
 
 namespace {
-
-// the canonical diagonal block: sorted rows without repeats, local columns; diag[i] = the place of (i, i) or -1
-struct Canon {
-    int n = 0;
-    std::vector<int> rp, col, diag;
-    std::vector<double> val;
-};
 
 struct TriPlan {
     std::vector<int> perm, level_ptr, level_split, plan;  // plan: {kind, first level, end level} per launch
@@ -58,45 +52,6 @@ struct TriDev {  // one triangle on the device
     }
     spmv::TrsvView view() const { return {rp, col, brow, xrow, level_ptr, level_split, val, dinv}; }
 };
-
-double now_ms() { return UploadTrace::now() * 1e3; }
-
-template <typename T>
-int canon_download(const spmv_csr_dev *m, Canon &A) {
-    const int n = m->M_local;
-    const size_t nz = (size_t)m->nz;
-    std::vector<int> rp((size_t)n + 1, 0), col(nz);
-    std::vector<T> val(nz);
-    HIP_TRY(hipMemcpy(rp.data(), m->row_ptr, ((size_t)n + 1) * sizeof(int), hipMemcpyDeviceToHost));
-    if (nz) HIP_TRY(hipMemcpy(col.data(), m->col, nz * sizeof(int), hipMemcpyDeviceToHost));
-    if (nz) HIP_TRY(hipMemcpy(val.data(), m->val, nz * sizeof(T), hipMemcpyDeviceToHost));
-    A.n = n;
-    A.rp.assign((size_t)n + 1, 0);
-    A.diag.assign((size_t)n, -1);
-    A.col.clear();
-    A.val.clear();
-    A.col.reserve(nz);
-    A.val.reserve(nz);
-    std::vector<int> idx;
-    for (int i = 0; i < n; ++i) {
-        idx.clear();
-        for (int e = rp[i]; e < rp[i + 1]; ++e)
-            if (col[e] >= m->row0 && col[e] < m->row0 + n) idx.push_back(e);
-        std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return col[a] < col[b]; });
-        for (size_t k = 0; k < idx.size(); ++k) {
-            const int c = col[idx[k]] - m->row0;
-            if (k && c == A.col.back()) {
-                A.val.back() += (double)val[idx[k]];
-                continue;
-            }
-            if (c == i) A.diag[i] = (int)A.col.size();
-            A.col.push_back(c);
-            A.val.push_back((double)val[idx[k]]);
-        }
-        A.rp[i + 1] = (int)A.col.size();
-    }
-    return 0;
-}
 
 // B = Q A Q^T with row k of B = row order[k] of A
 void canon_permute(const Canon &A, const std::vector<int> &order, Canon &B) {
@@ -148,11 +103,6 @@ int tri_analyse(const Canon &B, int uplo, TriPlan &p) {
     std::sort(width.begin(), width.end());
     p.median = p.levels ? width[(size_t)p.levels / 2] : 0;
     return 0;
-}
-
-template <typename V>
-int to_device(V **d, const std::vector<V> &h) {
-    return upload_array(d, h.data(), h.size(), h.empty() ? 4 : 0);
 }
 
 // the triangle of B on side uplo in level order.  dinv: by row of B (NULL: unit diagonal).  bmap / xmap (NULL: the
@@ -214,20 +164,6 @@ void tri_launch(const TriDev &t, double scale, const int *flags, const T *b, T *
             hipLaunchKernelGGL((spmv::trsv_level<T, SCALED>), dim3(t.plan[k + 3]), dim3(kBlock), 0, s, v, t.plan[k + 1],
                                t.G, scale, flags, b, x);
     }
-}
-
-// the first row (B's numbering) whose diagonal is missing / zero or not finite; -1: none
-int first_missing_diag(const Canon &B) {
-    for (int i = 0; i < B.n; ++i)
-        if (B.diag[i] < 0) return i;
-    return -1;
-}
-
-int handle_ok(const spmv_csr_dev *m, const char *what) {
-    if (m->M_total != m->N) return fail("%s: needs a square matrix (%d x %d)", what, m->M_total, m->N);
-    if (m->tiles_only || !m->row_ptr || (m->nz > 0 && (!m->col || !m->val)))
-        return fail("%s: the handle does not hold its CSR arrays", what);
-    return 0;
 }
 
 }  // namespace
@@ -572,8 +508,9 @@ static int factors_body(const spmv_precond *P, bool lower, int *row_ptr, int *co
 extern "C" int spmv_hip_precond_factors(const spmv_precond *P, int which, int *row_ptr, int *col, void *val) {
     if (need_device()) return -1;
     if (!P || !row_ptr || (!col) != (!val)) return fail("precond_factors: bad arguments");
-    if (!P->tri) return fail("precond_factors: kind %d has no factors", P->kind);
+    if (!P->tri && !P->fsai) return fail("precond_factors: kind %d has no factors", P->kind);
     if (which != SPMV_FACTOR_L && which != SPMV_FACTOR_U) return fail("precond_factors: which = %d", which);
+    if (P->fsai) return guarded("precond_factors", [&] { return precond_fsai_factors(P, which, row_ptr, col, val); });
     return guarded("precond_factors", [&] {
         return P->value_bytes == 8 ? factors_body<double>(P, which == SPMV_FACTOR_L, row_ptr, col, (double *)val)
                                    : factors_body<float>(P, which == SPMV_FACTOR_L, row_ptr, col, (float *)val);

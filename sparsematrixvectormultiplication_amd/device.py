@@ -21,9 +21,9 @@ BICG_RAN_ALL, BICG_CONVERGED, BICG_BREAKDOWN_RHO, BICG_BREAKDOWN_OMEGA = 0, 1, 2
 CGLS_RAN_ALL, CGLS_CONVERGED, CGLS_BREAKDOWN = 0, 1, 2
 # CsrDevice.pcg: info["status"] (SPMV_PCG_*); CsrDevice.preconditioner kinds (SPMV_PRECOND_*)
 PCG_RAN_ALL, PCG_CONVERGED, PCG_BREAKDOWN = 0, 1, 2
-PRECOND_JACOBI, PRECOND_BLOCK_JACOBI, PRECOND_SSOR, PRECOND_ILU0 = 1, 2, 3, 4
+PRECOND_JACOBI, PRECOND_BLOCK_JACOBI, PRECOND_SSOR, PRECOND_ILU0, PRECOND_FSAI = 1, 2, 3, 4, 5
 PRECOND_KINDS = {"jacobi": PRECOND_JACOBI, "block_jacobi": PRECOND_BLOCK_JACOBI, "ssor": PRECOND_SSOR,
-                 "ilu0": PRECOND_ILU0}
+                 "ilu0": PRECOND_ILU0, "fsai": PRECOND_FSAI}
 # CsrDevice.triangular / the SSOR and ILU(0) preconditioners (SPMV_TRSV_*, SPMV_ORDER_*)
 TRSV_LOWER, TRSV_UPPER, TRSV_NONUNIT, TRSV_UNIT = 0, 1, 0, 1
 ORDER_NATURAL, ORDER_MULTICOLOR = 0, 1
@@ -33,6 +33,9 @@ TRSV_INFO = ("rows", "row0", "value_bytes", "entries", "levels", "launches", "wi
 PRECOND_TRI_INFO = ("forward_levels", "forward_launches", "forward_widest", "forward_median", "backward_levels",
                     "backward_launches", "backward_widest", "backward_median", "colours", "entries_l", "entries_u",
                     "analysis_us", "factor_us", "upload_us")
+PRECOND_FSAI_INFO = ("cap", "entries", "truncated_rows", "widest", "plan_g", "plan_gt", "analysis_us", "build_us",
+                     "upload_us")
+FSAI_PLANS = ("gather", "x_window", "x_window_pattern", "csr_tile")  # fsai_info()["plan_g"], ["plan_gt"]
 CSR_STREAM_KERNELS = ("csr_stream", "csr_stream_local", "csr_stream_short", "csr_tile")
 HLL_LDS_KERNELS = ("hll_lds", "hll_lds_local", "csr_tile (HLL slab rows)")
 CSR_VARIANTS = {"thread_row": CSR_THREAD_ROW, "wave_row": CSR_WAVE_ROW, "subwave": CSR_SUBWAVE,
@@ -427,12 +430,14 @@ class CsrDevice(_Handle):
                                  f"the handle rows [{row0}, {row1})")
         return np.ascontiguousarray(b)
 
-    def preconditioner(self, kind="jacobi", block=1, omega=1.0, ordering="natural") -> "Preconditioner":
+    def preconditioner(self, kind="jacobi", block=1, omega=1.0, ordering="natural", cap=32) -> "Preconditioner":
         """A preconditioner of this handle's rows; it owns its arrays.  kind "jacobi" (block 1) or "block_jacobi"
         (block in [1, 32]): built on the device (spmv_hip_csr_precond_build).  kind "ssor" (0 < omega < 2; 1 is
         symmetric Gauss-Seidel) or "ilu0": two sparse triangular solves (spmv_hip_csr_precond_build_tri), block 1;
         ordering "natural", or "multicolor": of the rows reordered by a greedy colouring (few dependency levels, more
-        steps)."""
+        steps).  kind "fsai": a sparse lower-triangular G with G^T G ~ A^-1 on the pattern of the lower triangle, at
+        most cap (in [1, 32]) entries per row, applied as two SpMVs (spmv_hip_csr_precond_build_fsai); block 1,
+        ordering "natural"."""
         if kind not in PRECOND_KINDS:
             raise ValueError(f"kind must be one of {sorted(PRECOND_KINDS)}, got {kind!r}")
         if isinstance(block, bool) or int(block) != block or not 1 <= int(block) <= 32:
@@ -447,6 +452,10 @@ class CsrDevice(_Handle):
             return Preconditioner(self, PRECOND_KINDS[kind], 1, float(omega), ORDERINGS[ordering])
         if ordering != "natural":
             raise ValueError(f"{kind} takes ordering = 'natural', got {ordering!r}")
+        if kind == "fsai":
+            if isinstance(cap, bool) or int(cap) != cap or not 1 <= int(cap) <= 32:
+                raise ValueError(f"cap must be an integer in [1, 32], got {cap!r}")
+            return Preconditioner(self, PRECOND_FSAI, 1, cap=int(cap))
         return Preconditioner(self, PRECOND_KINDS[kind], int(block))
 
     def triangular(self, lower=True, unit_diagonal=False, ordering="natural") -> "TriangularSolver":
@@ -627,14 +636,18 @@ class TriangularSolver(_Handle):
 
 
 class Preconditioner(_Handle):
-    """M^-1 of a Jacobi, block-Jacobi, SSOR or ILU(0) preconditioner of a CsrDevice's rows, resident in HBM
+    """M^-1 of a Jacobi, block-Jacobi, SSOR, ILU(0) or FSAI preconditioner of a CsrDevice's rows, resident in HBM
     (CsrDevice.preconditioner).  It owns its arrays: the handle it was built from may be freed first."""
 
     _free = "spmv_hip_precond_free"
 
-    def __init__(self, dev: CsrDevice, kind: int, block: int, omega: float = 1.0, ordering: int = ORDER_NATURAL):
+    def __init__(self, dev: CsrDevice, kind: int, block: int, omega: float = 1.0, ordering: int = ORDER_NATURAL,
+                 cap: int = 32):
         super().__init__()
-        if kind in (PRECOND_SSOR, PRECOND_ILU0):
+        if kind == PRECOND_FSAI:
+            _check(nat.lib().spmv_hip_csr_precond_build_fsai(dev.h, int(cap), C.byref(self.h)),
+                   "spmv_hip_csr_precond_build_fsai")
+        elif kind in (PRECOND_SSOR, PRECOND_ILU0):
             _check(nat.lib().spmv_hip_csr_precond_build_tri(dev.h, int(kind), int(ordering), float(omega),
                                                             C.byref(self.h)), "spmv_hip_csr_precond_build_tri")
         else:
@@ -669,10 +682,19 @@ class Preconditioner(_Handle):
         _check(nat.lib().spmv_hip_precond_tri_info(self.h, out), "spmv_hip_precond_tri_info")
         return dict(zip(PRECOND_TRI_INFO, (int(v) for v in out)))
 
+    def fsai_info(self) -> dict:
+        """FSAI: the cap, the entries of G, the rows that lost entries to the cap, the largest pattern, the plans of
+        the handles of G and G^T (an index into FSAI_PLANS), microseconds of analysis, device build, and the two
+        uploads with the transpose."""
+        out = (C.c_int * len(PRECOND_FSAI_INFO))()
+        _check(nat.lib().spmv_hip_precond_fsai_info(self.h, out), "spmv_hip_precond_fsai_info")
+        return dict(zip(PRECOND_FSAI_INFO, (int(v) for v in out)))
+
     def factors(self):
         """SSOR / ILU(0): (L, U), each a (row_ptr, col, val) triple in the handle's row numbering with ascending
         columns, both with their diagonal (ILU(0): L's is exactly 1; SSOR: the triangles of A).  With the multicolour
-        order they are Q^T L Q and Q^T U Q, triangular after the rows are put in (colour, row) order."""
+        order they are Q^T L Q and Q^T U Q, triangular after the rows are put in (colour, row) order.  FSAI: (G, G^T),
+        M^-1 = G^T G."""
         out = []
         for which in (0, 1):
             rp = np.zeros(self.rows + 1, dtype=np.int32)
