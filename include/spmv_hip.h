@@ -671,6 +671,45 @@ int spmv_fsai_plan(int n, const int *row_ptr, const int *col, const double *val,
 enum { SPMV_PCG_RAN_ALL = 0, SPMV_PCG_CONVERGED = 1, SPMV_PCG_BREAKDOWN = 2 };
 int spmv_hip_csr_pcg(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, double tol, const int *bounds,
                      const void *b_host, void *x_host, double *rr_hist, double *rz_hist, int *info, float *ms_total);
+/* k independent preconditioned CG recurrences for a symmetric positive definite A and M, x0 = 0, sharing one SpMM per
+ * step: the loop of spmv_hip_csr_pcg with one alpha, one beta, one stop state and one status per column (not block CG),
+ * in the layout of spmv_hip_csr_cg_multi.  B, X and every loop vector are row-major n x k; the product is
+ * spmv_hip_csr_spmm_on on library-owned P (N x k) and Q (M_total x k).  The communicator, the bounds scaled by k, the
+ * all-gatherv of P and the dot products added in rank order are those of spmv_hip_csr_cg_multi.
+ * P: NULL, JACOBI, BLOCK_JACOBI or FSAI.  Jacobi is fused into the x / r update with both dots; a block-Jacobi apply is
+ * a pass of its own that makes the dots; an FSAI apply is Z = G^T (G R), two SpMMs through P's handles, then one pass for
+ * the dots.  SSOR and ILU0 are refused: their triangular solves take one right-hand side.
+ * Column j's sums add in an order that does not depend on j: permuting the columns of B permutes X, both histories,
+ * steps and status bit for bit, and two calls give the same bits.  k = 1 gives spmv_hip_csr_pcg's bits (variant
+ * SPMV_CSR_AUTO); P = NULL gives spmv_hip_csr_cg_multi's X and history while no column breaks down.
+ * Per column, the rules of spmv_hip_csr_pcg: rr0 = 0 converges at step 0 with x = 0; before step t's update p.q <= 0 or a
+ * non-finite scalar is a breakdown with steps = t - 1; after it a non-finite rr or rz is a breakdown, then rr <= tol^2 rr0
+ * converges, then rz <= 0 is a breakdown.  A stopped column keeps its x, r, z and p, its histories repeat their last
+ * value, it still rides in the SpMM and it never receives a NaN in X, whatever the other columns hold.
+ * tol = 0: exactly `iters` steps, no host synchronisation; tol > 0: the host reads one device word every 16 steps and
+ * ends the loop once no column is active.
+ * Out (all optional): X_host M_total x k; rr_hist, rz_hist (iters + 1) x k, r.r and r.z per column before step 1 and
+ * after every step; steps[k]; status[k] (SPMV_PCG_*); *ms_total device time of the loop.
+ * -1 (the HIP error state stays clean, the handle still works): k < 1 or k > 64, a non-square matrix, a tiles-only
+ * handle, n*k beyond int range, iters < 0, tol < 0 or not finite, a communicator without bounds, a row-range handle
+ * without a communicator, a P whose rows, row0 or dtype differ from the handle's, a P of kind SSOR or ILU0.
+ *   spmv_hip_precond_apply_multi_on  Z = M^-1 R for row-major rows x k device arrays (element (i, j) at i k + j, row i =
+ *                                    row row0 + i), asynchronous on `stream` (NULL = the library's).  Jacobi and
+ *                                    block-Jacobi ignore d_work; a row's sum is pc_apply's: in double, the block's
+ *                                    columns ascending, rounded once.  FSAI needs d_work, rows x k values plus one
+ *                                    128-byte line: work = G R, then Z = G^T work, by spmv_hip_csr_spmm_on on P's two
+ *                                    handles (R, with the same tail, is read as that call reads its X); P's own vector
+ *                                    is not touched.  The Jacobi and block-Jacobi kernels move 16-byte pieces of a
+ *                                    row when k values are whole pieces AND d_R and d_Z are 16-byte aligned; else they
+ *                                    move single elements (the same bits, more instructions).  -1: k outside [1, 64],
+ *                                    arrays not aligned to the element size, FSAI without d_work, SSOR or ILU0.
+ *   spmv_hip_precond_apply_multi     the same on host arrays of rows x k values: allocates, copies, syncs */
+int spmv_hip_csr_pcg_multi(spmv_csr_dev *m, const spmv_precond *P, int k, int iters, double tol, const int *bounds,
+                           const void *B_host, void *X_host, double *rr_hist, double *rz_hist, int *steps, int *status,
+                           float *ms_total);
+int spmv_hip_precond_apply_multi_on(const spmv_precond *P, int k, const void *d_R, void *d_Z, void *d_work,
+                                    void *stream);
+int spmv_hip_precond_apply_multi(const spmv_precond *P, int k, const void *R_host, void *Z_host);
 /* Right-preconditioned BiCGSTAB: the loop of spmv_hip_csr_bicgstab on A M^-1 with x = M^-1 y, so r stays the true
  * residual and tol, the half step, the breakdown rules, rr_hist and info mean what they mean there:
  *   p^ = M^-1 p, v = A p^, ..., s^ = M^-1 s, t = A s^, x += alpha p^ + omega s^ (a half step: x += alpha p^)

@@ -247,6 +247,11 @@ _PROTOTYPES = {
                                  C.POINTER(C.c_longlong)]),
     "spmv_hip_csr_pcg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, c_int_p, C.c_void_p,
                                    C.c_void_p, c_double_p, c_double_p, c_int_p, c_float_p]),
+    "spmv_hip_csr_pcg_multi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, c_int_p, C.c_void_p,
+                                         C.c_void_p, c_double_p, c_double_p, c_int_p, c_int_p, c_float_p]),
+    "spmv_hip_precond_apply_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "spmv_hip_precond_apply_multi_on": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]),
     "spmv_hip_csr_pbicgstab": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, c_int_p, C.c_void_p,
                                          C.c_void_p, c_double_p, c_int_p, c_float_p]),
     "spmv_hip_csr_cgls": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p,

@@ -11,6 +11,7 @@
 //   mcg_update_x_r    x_j += alpha_j p_j, r_j -= alpha_j q_j, and r_j . r_j -> part[g * k + j]
 //   mcg_update_p      p_j = r_j + beta_j p_j
 //   mcg_start / mcg_set_alpha / mcg_set_beta   one workgroup: the k columns' scalars, the freeze rule, the history
+//                     (in spmv_cg.hip: spmv_pcg_multi.hip builds on this header with scalar kernels of its own)
 //
 // Reduction order.  Products are accumulated in double, for fp32 and fp64 data alike.  A lane adds its rows in
 // grid-stride order, the rows of one column in a wave are added by an xor butterfly over the high lane bits, the
@@ -179,57 +180,10 @@ __global__ __launch_bounds__(kBlock) void mcg_update_p(long long n, int k, int c
     }
 }
 
-// the scalar kernels: one wavefront, lane j = column j
+// the scalar kernels (one wavefront, lane j = column j) count the columns still iterating
 __device__ __forceinline__ void mcg_count_active(int *__restrict__ flags, bool live) {
     const unsigned long long m = __ballot(live);
     if (threadIdx.x == 0) flags[kMcgActive] = __popcll(m);
-}
-
-// after r.r of r = b: rs0 = rs, history row 0; a column with rs0 <= tol2 * rs0 (rs0 = 0 when tol < 1) is frozen at 0
-__global__ __launch_bounds__(64) void mcg_start(double *__restrict__ s, int *__restrict__ flags, double *__restrict__ hist,
-                                                int k, int iters, double tol2) {
-    const int j = threadIdx.x;
-    bool live = false;
-    if (j < k) {
-        const double rs = s[kMcgRs * kMcgMaxK + j];
-        s[kMcgRs0 * kMcgMaxK + j] = rs;
-        live = !(rs <= tol2 * rs);
-        flags[kMcgAct + j] = live;
-        flags[kMcgDone + j] = live ? iters : 0;
-        hist[j] = rs;
-    }
-    mcg_count_active(flags, live);
-}
-
-// alpha = rs / p.q (0 when p.q = 0), as cg_set_alpha
-__global__ __launch_bounds__(64) void mcg_set_alpha(double *__restrict__ s, int k) {
-    const int j = threadIdx.x;
-    if (j >= k) return;
-    const double pq = s[kMcgPq * kMcgMaxK + j];
-    s[kMcgAlpha * kMcgMaxK + j] = pq != 0.0 ? s[kMcgRs * kMcgMaxK + j] / pq : 0.0;
-}
-
-// after step t: beta = rs' / rs (0 when rs = 0), rs = rs', as cg_set_beta; then the freeze rule rs' <= tol2 * rs0, and
-// history row t (a frozen column repeats its last value)
-__global__ __launch_bounds__(64) void mcg_set_beta(double *__restrict__ s, int *__restrict__ flags,
-                                                   double *__restrict__ hist_row, int k, int t, double tol2) {
-    const int j = threadIdx.x;
-    bool live = false;
-    if (j < k) {
-        live = flags[kMcgAct + j] != 0;
-        if (live) {
-            const double rs = s[kMcgRs * kMcgMaxK + j], rs_new = s[kMcgRsNew * kMcgMaxK + j];
-            s[kMcgBeta * kMcgMaxK + j] = rs != 0.0 ? rs_new / rs : 0.0;
-            s[kMcgRs * kMcgMaxK + j] = rs_new;
-            if (rs_new <= tol2 * s[kMcgRs0 * kMcgMaxK + j]) {
-                live = false;
-                flags[kMcgAct + j] = 0;
-                flags[kMcgDone + j] = t;
-            }
-        }
-        hist_row[j] = s[kMcgRs * kMcgMaxK + j];
-    }
-    mcg_count_active(flags, live);
 }
 
 }  // namespace spmv

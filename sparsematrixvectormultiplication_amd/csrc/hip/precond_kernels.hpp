@@ -192,6 +192,8 @@ void precond_tri_free(struct spmv_tri_precond *tp);
 // spmv_fsai.hip: z = G^T (G r) by the two handles' own launches on stream s (they do not look at a solver's flags: after
 // a stop r no longer changes, so z is rewritten with the bits it holds)
 int precond_fsai_apply(const spmv_precond *P, const void *r, void *z, hipStream_t s);
+// the same for rows x k row-major R and Z: two SpMMs; work: rows x k values and one 128-byte line, P's t is not used
+int precond_fsai_apply_multi(const spmv_precond *P, int k, const void *R, void *Z, void *work, hipStream_t s);
 void precond_fsai_free(struct spmv_fsai_precond *fp);
 int precond_fsai_factors(const spmv_precond *P, int which, int *row_ptr, int *col, void *val);
 

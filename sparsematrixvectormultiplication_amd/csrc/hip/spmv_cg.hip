@@ -154,6 +154,54 @@ extern "C" int spmv_hip_csr_cg(spmv_csr_dev *m, int variant, int iters, const in
 // k contiguous values) and the k dot products travel as in csr_cg: all-gathered, added in rank order (solver_reduce).
 namespace {
 
+// ---- the scalar kernels: one wavefront, lane j = column j (mcg_count_active and the slots: cg_multi_kernels.hpp)
+// after r.r of r = b: rs0 = rs, history row 0; a column with rs0 <= tol2 * rs0 (rs0 = 0 when tol < 1) is frozen at 0
+__global__ __launch_bounds__(64) void mcg_start(double *__restrict__ s, int *__restrict__ flags, double *__restrict__ hist,
+                                                int k, int iters, double tol2) {
+    const int j = threadIdx.x;
+    bool live = false;
+    if (j < k) {
+        const double rs = s[kMcgRs * kMcgMaxK + j];
+        s[kMcgRs0 * kMcgMaxK + j] = rs;
+        live = !(rs <= tol2 * rs);
+        flags[kMcgAct + j] = live;
+        flags[kMcgDone + j] = live ? iters : 0;
+        hist[j] = rs;
+    }
+    mcg_count_active(flags, live);
+}
+
+// alpha = rs / p.q (0 when p.q = 0), as cg_set_alpha
+__global__ __launch_bounds__(64) void mcg_set_alpha(double *__restrict__ s, int k) {
+    const int j = threadIdx.x;
+    if (j >= k) return;
+    const double pq = s[kMcgPq * kMcgMaxK + j];
+    s[kMcgAlpha * kMcgMaxK + j] = pq != 0.0 ? s[kMcgRs * kMcgMaxK + j] / pq : 0.0;
+}
+
+// after step t: beta = rs' / rs (0 when rs = 0), rs = rs', as cg_set_beta; then the freeze rule rs' <= tol2 * rs0, and
+// history row t (a frozen column repeats its last value)
+__global__ __launch_bounds__(64) void mcg_set_beta(double *__restrict__ s, int *__restrict__ flags,
+                                                   double *__restrict__ hist_row, int k, int t, double tol2) {
+    const int j = threadIdx.x;
+    bool live = false;
+    if (j < k) {
+        live = flags[kMcgAct + j] != 0;
+        if (live) {
+            const double rs = s[kMcgRs * kMcgMaxK + j], rs_new = s[kMcgRsNew * kMcgMaxK + j];
+            s[kMcgBeta * kMcgMaxK + j] = rs != 0.0 ? rs_new / rs : 0.0;
+            s[kMcgRs * kMcgMaxK + j] = rs_new;
+            if (rs_new <= tol2 * s[kMcgRs0 * kMcgMaxK + j]) {
+                live = false;
+                flags[kMcgAct + j] = 0;
+                flags[kMcgDone + j] = t;
+            }
+        }
+        hist_row[j] = s[kMcgRs * kMcgMaxK + j];
+    }
+    mcg_count_active(flags, live);
+}
+
 struct McgBuffers {
     void *P, *Q, *X, *R;
     double *s, *part, *gath, *hist;

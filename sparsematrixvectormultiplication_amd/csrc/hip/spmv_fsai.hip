@@ -186,6 +186,15 @@ int precond_fsai_apply(const spmv_precond *P, const void *r, void *z, hipStream_
     return csr_launch_any(fp->Gt, SPMV_CSR_AUTO, fp->t, z, s);
 }
 
+// Z = G^T (G R) for rows x k row-major R: two SpMMs through the same two handles (k = 1: their AUTO launches, the bits
+// of precond_fsai_apply).  work (rows x k values and a line tail) stands in for P's own t, which is not touched.
+int precond_fsai_apply_multi(const spmv_precond *P, int k, const void *R, void *Z, void *work, hipStream_t s) {
+    const spmv_fsai_precond *fp = P->fsai;
+    if (!P->rows) return 0;
+    if (spmv_hip_csr_spmm_on(fp->G, k, R, work, s)) return -1;
+    return spmv_hip_csr_spmm_on(fp->Gt, k, work, Z, s);
+}
+
 // G (which = SPMV_FACTOR_L) or G^T as their handles hold them: columns ascending, values of the handle's dtype
 int precond_fsai_factors(const spmv_precond *P, int which, int *row_ptr, int *col, void *val) {
     const spmv_csr_dev *h = which == SPMV_FACTOR_L ? P->fsai->G : P->fsai->Gt;

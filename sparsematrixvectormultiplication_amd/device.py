@@ -419,16 +419,19 @@ class CsrDevice(_Handle):
         if not float(tol) >= 0.0 or not np.isfinite(float(tol)):
             raise ValueError(f"tol must be finite and >= 0, got {tol}")
         if precond is not None:
-            if not isinstance(precond, Preconditioner):
-                raise ValueError("precond must be a Preconditioner (CsrDevice.preconditioner) or None")
-            if np.dtype(precond.dtype) != np.dtype(self.dtype):
-                raise ValueError(f"the preconditioner holds {np.dtype(precond.dtype)}, the handle "
-                                 f"{np.dtype(self.dtype)}")
-            row0, row1 = self._own_rows()
-            if (precond.row0, precond.row0 + precond.rows) != (row0, row1):
-                raise ValueError(f"the preconditioner covers rows [{precond.row0}, {precond.row0 + precond.rows}), "
-                                 f"the handle rows [{row0}, {row1})")
+            self._check_precond(precond)
         return np.ascontiguousarray(b)
+
+    def _check_precond(self, precond):
+        if not isinstance(precond, Preconditioner):
+            raise ValueError("precond must be a Preconditioner (CsrDevice.preconditioner) or None")
+        if np.dtype(precond.dtype) != np.dtype(self.dtype):
+            raise ValueError(f"the preconditioner holds {np.dtype(precond.dtype)}, the handle "
+                             f"{np.dtype(self.dtype)}")
+        row0, row1 = self._own_rows()
+        if (precond.row0, precond.row0 + precond.rows) != (row0, row1):
+            raise ValueError(f"the preconditioner covers rows [{precond.row0}, {precond.row0 + precond.rows}), "
+                             f"the handle rows [{row0}, {row1})")
 
     def preconditioner(self, kind="jacobi", block=1, omega=1.0, ordering="natural", cap=32) -> "Preconditioner":
         """A preconditioner of this handle's rows; it owns its arrays.  kind "jacobi" (block 1) or "block_jacobi"
@@ -486,6 +489,36 @@ class CsrDevice(_Handle):
                                           rr.ctypes.data_as(nat.c_double_p), rz.ctypes.data_as(nat.c_double_p),
                                           info.ctypes.data_as(nat.c_int_p), C.byref(ms)), "spmv_hip_csr_pcg")
         return x, rr, rz, {"steps": int(info[0]), "status": int(info[1])}, float(ms.value)
+
+    def pcg_multi(self, B, iters, tol=0.0, precond=None, bounds=None):
+        """k independent preconditioned CG recurrences from x0 = 0 that share one SpMM per step
+        (spmv_hip_csr_pcg_multi), for the k columns of a C-contiguous B (M x k, 1 <= k <= 64) of the handle's dtype.
+        precond: a Jacobi, block-Jacobi or FSAI Preconditioner of this handle, or None (cg_multi's bits); SSOR and
+        ILU(0) take one right-hand side and are refused.  Every column stops on its own, by the rules of pcg; tol > 0
+        also ends the loop early once every column has stopped.  Returns (X (M, k), r.r history (iters + 1, k), r.z
+        history (iters + 1, k), info {"steps": int array [k], "status": int array [k] (PCG_*)}, ms)."""
+        B = _check_columns(B, self.M, self.dtype, "B", "handle")
+        if int(iters) < 0:
+            raise ValueError(f"iters must be >= 0, got {iters}")
+        if not float(tol) >= 0.0 or not np.isfinite(float(tol)):
+            raise ValueError(f"tol must be finite and >= 0, got {tol}")
+        if precond is not None:
+            self._check_precond(precond)
+        k = B.shape[1]
+        X = np.zeros((self.M, k), dtype=self.dtype)
+        rr = np.zeros((int(iters) + 1, k))
+        rz = np.zeros((int(iters) + 1, k))
+        steps = np.zeros(k, dtype=np.int32)
+        status = np.zeros(k, dtype=np.int32)
+        ms = C.c_float(0)
+        bb = None if bounds is None else np.ascontiguousarray(bounds, dtype=np.int32)
+        _check(nat.lib().spmv_hip_csr_pcg_multi(self.h, None if precond is None else precond.h, int(k), int(iters),
+                                                float(tol), None if bb is None else bb.ctypes.data_as(nat.c_int_p),
+                                                B.ctypes.data_as(C.c_void_p), X.ctypes.data_as(C.c_void_p),
+                                                rr.ctypes.data_as(nat.c_double_p), rz.ctypes.data_as(nat.c_double_p),
+                                                steps.ctypes.data_as(nat.c_int_p), status.ctypes.data_as(nat.c_int_p),
+                                                C.byref(ms)), "spmv_hip_csr_pcg_multi")
+        return X, rr, rz, {"steps": steps, "status": status}, float(ms.value)
 
     def bicgstab(self, b, iters, tol=0.0, variant=CSR_AUTO, bounds=None, precond=None):
         """BiCGSTAB from x0 = 0 with shadow residual r^ = b (spmv_hip_csr_bicgstab), for a square, possibly
@@ -601,6 +634,18 @@ def _check_vector(v, rows, dtype, name, owner):
     return np.ascontiguousarray(v)
 
 
+def _check_columns(A, rows, dtype, name, owner):
+    """A as it is when it is a C-contiguous rows x k array of dtype with 1 <= k <= 64; else ValueError"""
+    A = np.asarray(A)
+    if A.dtype != dtype:
+        raise ValueError(f"{name} has dtype {A.dtype}, the {owner} holds {np.dtype(dtype)}")
+    if A.ndim != 2 or A.shape[0] != rows or not 1 <= A.shape[1] <= 64:
+        raise ValueError(f"{name} must be {rows} x k with 1 <= k <= 64, got shape {A.shape}")
+    if not A.flags.c_contiguous:
+        raise ValueError(f"{name} must be C-contiguous (row-major {rows} x k)")
+    return A
+
+
 class TriangularSolver(_Handle):
     """x with T x = b for a triangle of a CsrDevice's diagonal block, resident in HBM in level order
     (CsrDevice.triangular).  It owns its arrays: the handle it was built from may be freed first."""
@@ -674,6 +719,26 @@ class Preconditioner(_Handle):
         _check(nat.lib().spmv_hip_precond_apply(self.h, r.ctypes.data_as(C.c_void_p), z.ctypes.data_as(C.c_void_p)),
                "spmv_hip_precond_apply")
         return z
+
+    def apply_multi(self, R):
+        """Z = M^-1 R for the k columns of a C-contiguous R (rows x k, 1 <= k <= 64) of the handle's dtype
+        (spmv_hip_precond_apply_multi); Jacobi, block-Jacobi and FSAI."""
+        R = _check_columns(R, self.rows, self.dtype, "R", "preconditioner")
+        Z = np.zeros(R.shape, dtype=self.dtype)
+        _check(nat.lib().spmv_hip_precond_apply_multi(self.h, int(R.shape[1]), R.ctypes.data_as(C.c_void_p),
+                                                      Z.ctypes.data_as(C.c_void_p)), "spmv_hip_precond_apply_multi")
+        return Z
+
+    def apply_multi_on(self, d_R: int, d_Z: int, k: int, d_work: int = 0, stream: int = 0):
+        """The same on row-major rows x k device arrays, asynchronous on `stream` (0 = the library's).  FSAI needs
+        d_work, rows x k values and one 128-byte line; the other kinds ignore it.  Jacobi and block-Jacobi move 16-byte
+        pieces when a row of k values is whole pieces and d_R, d_Z are 16-byte aligned, single elements otherwise (the
+        same bits)."""
+        if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= 64:
+            raise ValueError(f"k must be an integer in [1, 64], got {k!r}")
+        _check(nat.lib().spmv_hip_precond_apply_multi_on(self.h, int(k), C.c_void_p(d_R), C.c_void_p(d_Z),
+                                                         C.c_void_p(d_work), C.c_void_p(stream)),
+               "spmv_hip_precond_apply_multi_on")
 
     def tri_info(self) -> dict:
         """SSOR / ILU(0): levels, launches, widest and median level of the forward and the backward solve, colours
