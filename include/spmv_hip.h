@@ -719,6 +719,43 @@ int spmv_hip_precond_apply_multi(const spmv_precond *P, int k, const void *R_hos
 int spmv_hip_csr_pbicgstab(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, double tol,
                            const int *bounds, const void *b_host, void *x_host, double *rr_hist, int *info,
                            float *ms_total);
+/* MINRES (Paige and Saunders 1975) for (A - shift I) x = b with a symmetric, possibly indefinite A and an optional
+ * symmetric positive definite preconditioner M (P = NULL: y is r2 itself), x0 = 0.  One SpMV per step through the
+ * handle's launch for `variant` on library-owned v, short recurrences, fixed-order device reductions in double, fp64
+ * scalars that stay on the device.  The shift goes to A alone; M is used as built.
+ *   r1 = r2 = b;  y = M^-1 r2;  bb0 = r2.y;  beta = sqrt(bb0);  phibar = beta
+ *   oldb = dbar = epsln = 0;  cs = -1;  sn = 0;  w = w2 = 0;  hist[0] = bb0
+ *   step k:  v = y / beta
+ *            t = A v - shift v;  if k >= 2: t -= (beta / oldb) r1
+ *            alfa = v.t;  t -= (alfa / beta) r2
+ *            r1 = r2;  r2 = t;  y = M^-1 r2;  oldb = beta;  bb = r2.y;  beta = sqrt(bb)
+ *            oldeps = epsln;  delta = cs dbar + sn alfa;  gbar = sn dbar - cs alfa;  epsln = sn beta;  dbar = -cs beta
+ *            gamma = sqrt(gbar^2 + beta^2);  cs = gbar / gamma;  sn = beta / gamma;  phi = cs phibar;  phibar = sn phibar
+ *            w1 = w2;  w2 = w;  w = (v - oldeps w1 - delta w2) / gamma;  x += phi w
+ *            hist[k] = phibar^2;  converged when phibar^2 <= tol^2 bb0
+ * (cs, sn, dbar, phibar on the right-hand sides of one line are the values before the step.)  hist[k] is the
+ * recurrence's r.r of (A - shift I) x_k = b; with M it is r.M^-1 r.  It never grows.
+ * Converged: bb0 == 0 at step 0 with x = 0; else the first step with phibar^2 <= tol^2 bb0 (tol = 0: only at exactly
+ *   0), which still does its x += phi w.
+ * Breakdown (x stays at the last full iterate, no NaN is written into it; the step is not counted): at the start bb0
+ *   < 0 or not finite (steps = 0); in step k alfa or alfa / beta not finite; bb < 0 (M is not positive definite);
+ *   gamma == 0; or bb, delta, epsln, dbar, gamma, phi, phibar, the new beta / oldb or phibar^2 not finite.
+ * After a stop x no longer changes and the history repeats its last value.
+ * tol = 0: exactly `iters` steps are launched, no host synchronisation inside the loop.
+ * tol > 0: the host reads one device word every 16 steps and ends the loop once the solve has stopped.
+ * With a communicator every rank keeps its rows; the next v is all-gathered with `bounds` (one exchange per step), the
+ * partial sums are all-gathered and added in rank order: every rank holds the same bits and stops at the same step.
+ * There is no halo exchange variant.  With P the apply follows the Lanczos update as launches of its own (a pass for
+ * Jacobi and block-Jacobi, two triangular solves for SSOR and ILU(0), two SpMVs for FSAI), then one pass for r2.y.
+ * b_host: M_total values of the handle's dtype (a rank reads its own rows).  Out (all optional): x_host M_total
+ * values; rr_hist [iters + 1]; info[2] = {steps, status (SPMV_MINRES_*)}; *ms_total device time of the loop.
+ * -1: NULL m or b_host, a non-square or tiles-only handle, iters < 0, tol < 0 or not finite, shift not finite, a
+ * communicator without bounds, a row-range handle without a communicator, more ranks than the library supports, a P
+ * whose rows, row0 or dtype differ from the handle's. */
+enum { SPMV_MINRES_RAN_ALL = 0, SPMV_MINRES_CONVERGED = 1, SPMV_MINRES_BREAKDOWN = 2 };
+int spmv_hip_csr_minres(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, double tol, double shift,
+                        const int *bounds, const void *b_host, void *x_host, double *rr_hist, int *info,
+                        float *ms_total);
 int spmv_hip_csr_split_interior(spmv_csr_dev *m, long long *counts);
 /* N4 overlap below block granularity (round 3).  On a KKT-coupled cut every block also lists lines of the coupling block,
  * which another rank owns: no interior BLOCKS -- but 13 of a row's 28 entries have their column in the rank's own range.

@@ -21,6 +21,8 @@ BICG_RAN_ALL, BICG_CONVERGED, BICG_BREAKDOWN_RHO, BICG_BREAKDOWN_OMEGA = 0, 1, 2
 CGLS_RAN_ALL, CGLS_CONVERGED, CGLS_BREAKDOWN = 0, 1, 2
 # CsrDevice.pcg: info["status"] (SPMV_PCG_*); CsrDevice.preconditioner kinds (SPMV_PRECOND_*)
 PCG_RAN_ALL, PCG_CONVERGED, PCG_BREAKDOWN = 0, 1, 2
+# CsrDevice.minres: info["status"] (SPMV_MINRES_* of include/spmv_hip.h)
+MINRES_RAN_ALL, MINRES_CONVERGED, MINRES_BREAKDOWN = 0, 1, 2
 PRECOND_JACOBI, PRECOND_BLOCK_JACOBI, PRECOND_SSOR, PRECOND_ILU0, PRECOND_FSAI = 1, 2, 3, 4, 5
 PRECOND_KINDS = {"jacobi": PRECOND_JACOBI, "block_jacobi": PRECOND_BLOCK_JACOBI, "ssor": PRECOND_SSOR,
                  "ilu0": PRECOND_ILU0, "fsai": PRECOND_FSAI}
@@ -540,6 +542,29 @@ class CsrDevice(_Handle):
         else:
             _check(nat.lib().spmv_hip_csr_pbicgstab(self.h, precond.h, *args), "spmv_hip_csr_pbicgstab")
         return x, hist, {"steps": int(info[0]), "status": int(info[1]), "half_step": int(info[2])}, float(ms.value)
+
+    def minres(self, b, iters, tol=0.0, shift=0.0, precond=None, variant=CSR_AUTO, bounds=None):
+        """MINRES from x0 = 0 (spmv_hip_csr_minres) for (A - shift I) x = b with a symmetric, possibly indefinite A:
+        one SpMV per step, a residual norm that never grows.  precond: a Preconditioner of this handle that is
+        symmetric positive definite (it is used as built, the shift goes to A alone), or None.  Stops once the
+        recurrence's r.r (r.M^-1 r with a preconditioner) <= tol^2 times its initial value (tol = 0: only at exactly
+        0; tol > 0 also ends the loop early), or at a breakdown.  Returns (x, that r.r history (iters + 1), info
+        {"steps", "status" (MINRES_*)}, ms)."""
+        if not np.isfinite(float(shift)):
+            raise ValueError(f"shift must be finite, got {shift}")
+        b = self._check_solve_args(b, iters, tol, precond)
+        x = np.zeros(self.M, dtype=self.dtype)
+        hist = np.zeros(int(iters) + 1)
+        info = np.zeros(2, dtype=np.int32)
+        ms = C.c_float(0)
+        bb = None if bounds is None else np.ascontiguousarray(bounds, dtype=np.int32)
+        _check(nat.lib().spmv_hip_csr_minres(self.h, None if precond is None else precond.h, int(variant), int(iters),
+                                             float(tol), float(shift),
+                                             None if bb is None else bb.ctypes.data_as(nat.c_int_p),
+                                             b.ctypes.data_as(C.c_void_p), x.ctypes.data_as(C.c_void_p),
+                                             hist.ctypes.data_as(nat.c_double_p), info.ctypes.data_as(nat.c_int_p),
+                                             C.byref(ms)), "spmv_hip_csr_minres")
+        return x, hist, {"steps": int(info[0]), "status": int(info[1])}, float(ms.value)
 
     def cgls(self, b, iters, tol=0.0, damp=0.0, at=None):
         """CGLS from x0 = 0 for min ||A x - b||^2 + damp^2 ||x||^2, A of any shape (spmv_hip_csr_cgls).  at: a
