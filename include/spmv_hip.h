@@ -120,6 +120,10 @@ typedef struct {
     int pattern_segment_cap;  /* CSR: ... and the widest the LDS budget allowed (7 resident workgroups per CU) */
     long long pattern_table_rows; /* CSR: rows of the blocks whose segment was wider: they rebuild their slots from their
                                      pattern table (rinfo, row_ptr and the table in memory) */
+    long long pattern_segments_stored; /* CSR: segments held in memory: equal segments are stored once and shared by their
+                                          blocks ("local_share"; 0: no segments) */
+    long long local_lists_stored;   /* CSR: line lists held in memory: lists that are equal relative to their first line are
+                                       stored once, each block adds its own first line (0: every block holds absolute ids) */
 } spmv_dev_info;
 
 /* ---- device ------------------------------------------------------------ */
@@ -179,6 +183,10 @@ int spmv_hip_gather_probe(int value_bytes, size_t table_bytes, int waves_per_cu,
  *                         slots from a pattern table instead of reading them -- auto: built for streamed matrices of at least
  *                         12 entries per row whose tables hold at most a quarter of the slots, then kept only if upload
  *                         measures its kernel at least 2 % faster with it on this handle; 0 never; 1 always
+ *                     "local_share" -1 | 0 | 1 | 2 (read at upload) x-window plans of CSR handles: every distinct pattern segment
+ *                         and every distinct line list (relative to its first line) is stored once and shared by the blocks
+ *                         that repeat it -- auto: on; 0 off (every block its own copy); 1 on; 2 on, with a hash of the
+ *                         span's length alone, so that every group has to be told apart word by word (tests)
  *                     "tile_mid_items" (0 = three rounds of the CUs) work items of the middle tier
  *                     "tile_expand" -1 | 0 | 1 (read at upload and at launch) a tile plan with gather passes runs on an
  *                         expanded x -- auto: from 2^22 entries on when under a tenth of them are staged, fp32 always, fp64

@@ -407,11 +407,18 @@ constexpr int kLineBytes = 128;
 constexpr int kLocalLinesMax = 256;  // lines per block: rank fits the 16-bit slot for fp64 and fp32
 constexpr int kLocalLineQuantum = kBlock / 8;  // lines one pass of the workgroup stages (16 B per lane)
 
+// A line id of a block's list.  A list of the block's own is streamed once; shared lists ("local_share": equal lists
+// stored once, many blocks read one copy) stay in the caches, so they are loaded without the streamed-once hint.
+template <bool NT>
+__device__ __forceinline__ int local_line_load(const int *p, bool shared) {
+    return shared ? *p : stream_load<NT>(p);
+}
+
 template <typename T, bool NT, int CAP, int ROUNDS>
 __device__ __forceinline__ void local_stage_full(T *stage, const int *__restrict__ my_lines, int last_line,
                                                  const unsigned short *__restrict__ lcol,
                                                  const T *__restrict__ val, const T *__restrict__ x,
-                                                 int e_first, bool no_slots = false) {
+                                                 int e_first, bool no_slots = false, bool shared_lists = false) {
     using V2 = typename vec2<T>::type;
     constexpr int kUnit = 2 * kBlock, kUnits = CAP / kUnit;
     const int t = threadIdx.x;
@@ -422,7 +429,7 @@ __device__ __forceinline__ void local_stage_full(T *stage, const int *__restrict
         // lanes behind the end of the list repeat its last line: one more hit on a line that is
         // being fetched anyway instead of up to 31 extra lines
         const int at = k * kLocalLineQuantum + (t >> 3);
-        line[k] = stream_load<NT>(my_lines + (k == ROUNDS - 1 ? min(at, last_line) : at));
+        line[k] = local_line_load<NT>(my_lines + (k == ROUNDS - 1 ? min(at, last_line) : at), shared_lists);
     }
     unsigned c[kUnits];
     V2 v[kUnits];
@@ -578,7 +585,7 @@ __device__ __forceinline__ void pat_expand_slots(const pat_ctx c, const uint4 (&
 template <typename T, bool NT, int CAP, int ROUNDS, bool HLL = false>
 __device__ __forceinline__ void local_stage_full_pat(T *stage, const int *__restrict__ my_lines, int last_line,
                                                      const T *__restrict__ val, const T *__restrict__ x, int e_first,
-                                                     const pat_ctx pc) {
+                                                     const pat_ctx pc, bool shared_lists = false) {
     using V2 = typename vec2<T>::type;
     constexpr int kUnit = 2 * kBlock, kUnits = CAP / kUnit;
     const int t = threadIdx.x;
@@ -586,7 +593,7 @@ __device__ __forceinline__ void local_stage_full_pat(T *stage, const int *__rest
 #pragma unroll
     for (int k = 0; k < ROUNDS; ++k) {
         const int at = k * kLocalLineQuantum + (t >> 3);
-        line[k] = stream_load<NT>(my_lines + (k == ROUNDS - 1 ? min(at, last_line) : at));
+        line[k] = local_line_load<NT>(my_lines + (k == ROUNDS - 1 ? min(at, last_line) : at), shared_lists);
     }
     V2 v[kUnits];
 #pragma unroll
@@ -716,7 +723,8 @@ template <typename T, bool NT, int CAP, int ROUNDS>
 __device__ __forceinline__ void local_stage_full_seg(T *stage, const int *__restrict__ my_lines, int last_line,
                                                      const T *__restrict__ val, const T *__restrict__ x, int e_first,
                                                      unsigned short *slots, uint4 *seg_lds, const uint4 *__restrict__ seg,
-                                                     int seg_len, int nrows, int lanes, int first_rel, int end_rel) {
+                                                     int seg_len, int nrows, int lanes, int first_rel, int end_rel,
+                                                     bool shared_lists = false) {
     using V2 = typename vec2<T>::type;
     constexpr int kUnit = 2 * kBlock, kUnits = CAP / kUnit;
     const int t = threadIdx.x;
@@ -724,7 +732,7 @@ __device__ __forceinline__ void local_stage_full_seg(T *stage, const int *__rest
 #pragma unroll
     for (int k = 0; k < ROUNDS; ++k) {
         const int at = k * kLocalLineQuantum + (t >> 3);
-        line[k] = stream_load<NT>(my_lines + (k == ROUNDS - 1 ? min(at, last_line) : at));
+        line[k] = local_line_load<NT>(my_lines + (k == ROUNDS - 1 ? min(at, last_line) : at), shared_lists);
     }
     // the segment beside the line list: both come back ahead of the value stream
     uint4 sg = make_uint4(0, 0, 0, 0);
@@ -769,6 +777,8 @@ __device__ __forceinline__ void local_stage_full_seg(T *stage, const int *__rest
 // (or no sdesc): the block's segment is wider than the LDS budget and the block takes its slots from its pattern table:
 // pdesc[b] = {first element of block b's table in ptab (a multiple of 8), elements}, rinfo per row.  stage_bytes = where
 // the LDS array of the slots begins; the segment's copy lies behind it.
+// lbase (optional): shared line lists -- block b's list holds ids relative to line lbase[b], and equal lists are one
+// copy in `lines` (so are equal segments in pseg: sdesc points where it likes).
 template <typename T, bool NT, int CAP, bool STAMP = false, bool PAT = false>
 __global__ __launch_bounds__(kBlock) void csr_stream_local(int num_blocks, int xcd_chunk,
                                                            const int *__restrict__ ids,
@@ -784,7 +794,8 @@ __global__ __launch_bounds__(kBlock) void csr_stream_local(int num_blocks, int x
                                                            const unsigned *__restrict__ rinfo = nullptr,
                                                            const unsigned short *__restrict__ ptab = nullptr, int stage_bytes = 0,
                                                            const int2 *__restrict__ sdesc = nullptr,
-                                                           const uint4 *__restrict__ pseg = nullptr) {
+                                                           const uint4 *__restrict__ pseg = nullptr,
+                                                           const int *__restrict__ lbase = nullptr) {
         using V2 = typename vec2<T>::type;
     const bool no_slots = STAMP && (probe & 1);  // (measurement only; constant false in the product instantiation)
     unsigned long long t_start = 0;
@@ -821,6 +832,9 @@ __global__ __launch_bounds__(kBlock) void csr_stream_local(int num_blocks, int x
     const int units = (d.w - base + kUnit - 1) / kUnit;                       // wave-uniform
     const int rounds = (ld.y + kLocalLineQuantum - 1) / kLocalLineQuantum;    // wave-uniform, 1..8
     const int *my_lines = lines + ld.x;
+    // shared line lists: the list counts from the block's first line, so x is taken from that line on (wave-uniform)
+    const bool shared_lists = lbase != nullptr;
+    if (shared_lists) x = reinterpret_cast<const T *>(reinterpret_cast<const char *>(x) + (size_t)lbase[b] * kLineBytes);
     unsigned short *slots = reinterpret_cast<unsigned short *>(local_smem + stage_bytes);
     uint4 *seg_lds = reinterpret_cast<uint4 *>(local_smem + stage_bytes + (CAP + 8) * sizeof(unsigned short));
     if (seg) {
@@ -828,7 +842,7 @@ __global__ __launch_bounds__(kBlock) void csr_stream_local(int num_blocks, int x
         const int first_rel = d.y - base, end_rel = d.w - base;
         if (units == kUnits) {
 #define SPMV_SEG(R) local_stage_full_seg<T, NT, CAP, R>(stage, my_lines, ld.y - 1, val, x, e_first, slots, seg_lds, sp, sd.y, \
-                                                        nrows, lanes, first_rel, end_rel)
+                                                        nrows, lanes, first_rel, end_rel, shared_lists)
             switch (rounds) {
                 case 1: SPMV_SEG(1); break;
                 case 2: SPMV_SEG(2); break;
@@ -890,14 +904,14 @@ __global__ __launch_bounds__(kBlock) void csr_stream_local(int num_blocks, int x
         pc.ri = t / lanes < nrows ? rinfo[r0 + t / lanes] : 0u;
         if (units == kUnits) {
             switch (rounds) {
-                case 1: local_stage_full_pat<T, NT, CAP, 1>(stage, my_lines, ld.y - 1, val, x, e_first, pc); break;
-                case 2: local_stage_full_pat<T, NT, CAP, 2>(stage, my_lines, ld.y - 1, val, x, e_first, pc); break;
-                case 3: local_stage_full_pat<T, NT, CAP, 3>(stage, my_lines, ld.y - 1, val, x, e_first, pc); break;
-                case 4: local_stage_full_pat<T, NT, CAP, 4>(stage, my_lines, ld.y - 1, val, x, e_first, pc); break;
-                case 5: local_stage_full_pat<T, NT, CAP, 5>(stage, my_lines, ld.y - 1, val, x, e_first, pc); break;
-                case 6: local_stage_full_pat<T, NT, CAP, 6>(stage, my_lines, ld.y - 1, val, x, e_first, pc); break;
-                case 7: local_stage_full_pat<T, NT, CAP, 7>(stage, my_lines, ld.y - 1, val, x, e_first, pc); break;
-                default: local_stage_full_pat<T, NT, CAP, 8>(stage, my_lines, ld.y - 1, val, x, e_first, pc); break;
+                case 1: local_stage_full_pat<T, NT, CAP, 1>(stage, my_lines, ld.y - 1, val, x, e_first, pc, shared_lists); break;
+                case 2: local_stage_full_pat<T, NT, CAP, 2>(stage, my_lines, ld.y - 1, val, x, e_first, pc, shared_lists); break;
+                case 3: local_stage_full_pat<T, NT, CAP, 3>(stage, my_lines, ld.y - 1, val, x, e_first, pc, shared_lists); break;
+                case 4: local_stage_full_pat<T, NT, CAP, 4>(stage, my_lines, ld.y - 1, val, x, e_first, pc, shared_lists); break;
+                case 5: local_stage_full_pat<T, NT, CAP, 5>(stage, my_lines, ld.y - 1, val, x, e_first, pc, shared_lists); break;
+                case 6: local_stage_full_pat<T, NT, CAP, 6>(stage, my_lines, ld.y - 1, val, x, e_first, pc, shared_lists); break;
+                case 7: local_stage_full_pat<T, NT, CAP, 7>(stage, my_lines, ld.y - 1, val, x, e_first, pc, shared_lists); break;
+                default: local_stage_full_pat<T, NT, CAP, 8>(stage, my_lines, ld.y - 1, val, x, e_first, pc, shared_lists); break;
             }
         } else {
             // a block cut short: plain loops
@@ -928,14 +942,14 @@ __global__ __launch_bounds__(kBlock) void csr_stream_local(int num_blocks, int x
         }
     } else if (units == kUnits) {
         switch (rounds) {
-            case 1: local_stage_full<T, NT, CAP, 1>(stage, my_lines, ld.y - 1, lcol, val, x, e_first, no_slots); break;
-            case 2: local_stage_full<T, NT, CAP, 2>(stage, my_lines, ld.y - 1, lcol, val, x, e_first, no_slots); break;
-            case 3: local_stage_full<T, NT, CAP, 3>(stage, my_lines, ld.y - 1, lcol, val, x, e_first, no_slots); break;
-            case 4: local_stage_full<T, NT, CAP, 4>(stage, my_lines, ld.y - 1, lcol, val, x, e_first, no_slots); break;
-            case 5: local_stage_full<T, NT, CAP, 5>(stage, my_lines, ld.y - 1, lcol, val, x, e_first, no_slots); break;
-            case 6: local_stage_full<T, NT, CAP, 6>(stage, my_lines, ld.y - 1, lcol, val, x, e_first, no_slots); break;
-            case 7: local_stage_full<T, NT, CAP, 7>(stage, my_lines, ld.y - 1, lcol, val, x, e_first, no_slots); break;
-            default: local_stage_full<T, NT, CAP, 8>(stage, my_lines, ld.y - 1, lcol, val, x, e_first, no_slots); break;
+            case 1: local_stage_full<T, NT, CAP, 1>(stage, my_lines, ld.y - 1, lcol, val, x, e_first, no_slots, shared_lists); break;
+            case 2: local_stage_full<T, NT, CAP, 2>(stage, my_lines, ld.y - 1, lcol, val, x, e_first, no_slots, shared_lists); break;
+            case 3: local_stage_full<T, NT, CAP, 3>(stage, my_lines, ld.y - 1, lcol, val, x, e_first, no_slots, shared_lists); break;
+            case 4: local_stage_full<T, NT, CAP, 4>(stage, my_lines, ld.y - 1, lcol, val, x, e_first, no_slots, shared_lists); break;
+            case 5: local_stage_full<T, NT, CAP, 5>(stage, my_lines, ld.y - 1, lcol, val, x, e_first, no_slots, shared_lists); break;
+            case 6: local_stage_full<T, NT, CAP, 6>(stage, my_lines, ld.y - 1, lcol, val, x, e_first, no_slots, shared_lists); break;
+            case 7: local_stage_full<T, NT, CAP, 7>(stage, my_lines, ld.y - 1, lcol, val, x, e_first, no_slots, shared_lists); break;
+            default: local_stage_full<T, NT, CAP, 8>(stage, my_lines, ld.y - 1, lcol, val, x, e_first, no_slots, shared_lists); break;
         }
     } else {
         // a block cut short (row cap, line cap, end of the matrix): plain loops

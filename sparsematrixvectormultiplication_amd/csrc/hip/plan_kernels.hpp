@@ -251,4 +251,76 @@ __global__ __launch_bounds__(BLOCK) void pat_segment(int blocks, const int4 *__r
     for (int g = t; g < td.y / 8; g += BLOCK) grp[g] = tab[g];
 }
 
+// ---- shared spans (share_spans, upload_ops.hpp): the blocks of a stencil repeat -- the same segment, the same line list
+// relative to its first line -- and every distinct one is stored once.  A span is desc[b] = {first element, elements} of
+// `data`, an element `words` 32-bit words; rel != 0: the span counts from its first word (line lists), which goes to
+// base[b].  One workgroup per block throughout.
+__device__ __forceinline__ unsigned long long share_mix(unsigned long long z) {  // (splitmix64's finaliser)
+    z += 0x9e3779b97f4a7c15ull;
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+// share_hash: hash[b] over the span's words and their positions (a sum: the order of the lanes does not matter); weak:
+// the span's length alone (tests: every group then has to be told apart by share_verify)
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void share_hash(int blocks, const int2 *__restrict__ desc, const unsigned *__restrict__ data,
+                                                    int words, int rel, int weak, unsigned long long *__restrict__ hash,
+                                                    int *__restrict__ base) {
+    __shared__ unsigned long long part[BLOCK];
+    const int b = blockIdx.x, t = threadIdx.x;
+    if (b >= blocks) return;
+    const int2 d = desc[b];
+    const int n = d.y * words;
+    const unsigned *w = data + (size_t)d.x * words;
+    const unsigned first = rel && n > 0 ? w[0] : 0u;
+    unsigned long long h = 0;
+    for (int i = t; i < n; i += BLOCK) h += share_mix(((unsigned long long)i << 32) | (unsigned)(w[i] - first));
+    part[t] = h;
+    __syncthreads();
+    for (int s = BLOCK / 2; s > 0; s >>= 1) {
+        if (t < s) part[t] += part[t + s];
+        __syncthreads();
+    }
+    if (t == 0) {
+        hash[b] = weak ? (unsigned long long)n : share_mix(part[0] + (unsigned long long)n);
+        if (base) base[b] = (int)first;
+    }
+}
+// share_verify: differs[b] = 1 (zeroed beforehand) when block b's span is not, word for word, that of block canon[b]
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void share_verify(int blocks, const int2 *__restrict__ desc, const unsigned *__restrict__ data,
+                                                      int words, int rel, const int *__restrict__ canon,
+                                                      int *__restrict__ differs) {
+    const int b = blockIdx.x, t = threadIdx.x;
+    if (b >= blocks) return;
+    const int c = canon[b];
+    if (c == b || c < 0) return;
+    const int2 d = desc[b], dc = desc[c];
+    if (d.y != dc.y) {
+        if (t == 0) differs[b] = 1;
+        return;
+    }
+    const int n = d.y * words;
+    const unsigned *w = data + (size_t)d.x * words, *wc = data + (size_t)dc.x * words;
+    const unsigned first = rel && n > 0 ? w[0] : 0u, first_c = rel && n > 0 ? wc[0] : 0u;
+    bool bad = false;
+    for (int i = t; i < n; i += BLOCK) bad |= (w[i] - first) != (wc[i] - first_c);
+    if (bad) differs[b] = 1;
+}
+// share_gather: kept span k = {block, first element in `out`} copied to its new home
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void share_gather(int kept, const int2 *__restrict__ keep, const int2 *__restrict__ desc,
+                                                      const unsigned *__restrict__ data, int words, int rel,
+                                                      unsigned *__restrict__ out) {
+    const int k = blockIdx.x, t = threadIdx.x;
+    if (k >= kept) return;
+    const int2 d = desc[keep[k].x];
+    const int n = d.y * words;
+    const unsigned *w = data + (size_t)d.x * words;
+    unsigned *o = out + (size_t)keep[k].y * words;
+    const unsigned first = rel && n > 0 ? w[0] : 0u;
+    for (int i = t; i < n; i += BLOCK) o[i] = w[i] - first;
+}
+
 }  // namespace spmv

@@ -535,10 +535,12 @@ static int spmv_hip_csr_needed_ranges_body(const spmv_csr_dev *m, int max_ranges
     if (m->local_blocks <= 0 || m->num_long > 0) {
         r.emplace_back(0, m->N);  // no plan, or rows outside it: everything
     } else {
-        std::vector<int> lines((size_t)m->local_lines);
-        HIP_TRY(hipStreamSynchronize(g_stream));
-        if (!lines.empty())
-            HIP_TRY(hipMemcpy(lines.data(), m->lines, lines.size() * sizeof(int), hipMemcpyDeviceToHost));
+        std::vector<int2> ld;
+        std::vector<int> stored, lbase, lines;
+        if (csr_lines_to_host(m, ld, stored, lbase)) return -1;
+        lines.reserve((size_t)m->local_lines);
+        for (size_t b = 0; b < ld.size(); ++b)
+            for (int k = 0; k < ld[b].y; ++k) lines.push_back(stored[(size_t)ld[b].x + k] + lbase[b]);
         std::sort(lines.begin(), lines.end());
         lines.erase(std::unique(lines.begin(), lines.end()), lines.end());
         const int per_line = kLineBytes / m->value_bytes;

@@ -716,7 +716,7 @@ void csr_pattern_segments(spmv_csr_dev *m, const std::vector<int> &count) {
     hipError_t e = hipMemcpyAsync(h_desc.data(), m->ldesc4, (size_t)B * sizeof(int4), hipMemcpyDeviceToHost, g_stream);
     if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
     std::vector<int2> h_sdesc((size_t)B, make_int2(0, 0));
-    long long seg_total = 0, table_rows = 0;
+    long long seg_total = 0, table_rows = 0, segments = 0;
     int seg_max = 0;
     for (int b = 0; b < B && e == hipSuccess; ++b) {
         const int4 d = h_desc[(size_t)b];
@@ -725,6 +725,7 @@ void csr_pattern_segments(spmv_csr_dev *m, const std::vector<int> &count) {
             h_sdesc[(size_t)b] = make_int2((int)seg_total, len);
             seg_total += len;
             seg_max = std::max(seg_max, len);
+            ++segments;
         } else {
             table_rows += d.z;
         }
@@ -743,6 +744,7 @@ void csr_pattern_segments(spmv_csr_dev *m, const std::vector<int> &count) {
     } else {
         seg_total = 0;
         seg_max = 0;
+        segments = 0;
         table_rows = m->M_local;
     }
     if (e != hipSuccess) {
@@ -751,10 +753,39 @@ void csr_pattern_segments(spmv_csr_dev *m, const std::vector<int> &count) {
         return;
     }
     pat.seg_total = seg_total;
+    pat.seg_distinct = segments;
     pat.seg_max = seg_max;
     pat.seg_cap = cap16;
     pat.table_rows = table_rows;
     trace.mark("segments");
+}
+
+// Shared plans ("local_share"; share_spans, upload_ops.hpp).  The blocks of a stencil repeat with the period of (row start
+// mod 16, position in the grid line): on the nlpkkt-like matrix 48 069 blocks hold 1 173 distinct segments and 361
+// distinct line lists relative to their first line, and every block streamed its own copy from HBM in every
+// launch.  One pass over whichever plan was built (device or host builder) stores each distinct segment once -- a segment
+// is position-independent, sdesc[b] points anywhere in pseg -- and each distinct relative line list once, the block's
+// first line in lbase[b]; the kernel then reads them from the caches.  A rule, not a measurement: only a span that is not
+// its group's canonical word for word keeps its own copy.  A failure leaves the plan unshared.  What it buys on that
+// matrix: 51 MB of 893 MB per launch, and no time (profiles/plan_sharing_bench_ab.txt).
+void csr_share_plan(spmv_csr_dev *m) {
+    if (g_local_share == 0 || m->local_blocks <= 0 || !m->lines || !m->ldesc) return;
+    UploadTrace trace("csr_share_plan");
+    const bool weak = g_local_share == 2;
+    PatternPlan &pat = m->pat;
+    if (pat.pseg && pat.sdesc) {
+        long long stored = 0, distinct = 0;
+        if (share_spans(pat.pseg, pat.sdesc, m->local_blocks, 0, false, weak, nullptr, stored, distinct)) {
+            pat.seg_total = stored;
+            pat.seg_distinct = distinct;
+        }
+    }
+    long long stored = 0, distinct = 0;
+    if (share_spans(m->lines, m->ldesc, m->local_blocks, (size_t)kLocalLinesMax, true, weak, &m->lbase, stored, distinct)) {
+        m->lines_stored = stored;
+        m->lists_distinct = distinct;
+    }
+    trace.mark("shared segments and line lists");
 }
 
 template <typename T>
@@ -973,6 +1004,8 @@ int csr_upload_impl(int M, int N, const int *row_ptr, const int *col_idx, const 
     if (!rc)
         csr_pattern_segments(m, build_pattern_tables<false>(m->pat, m->local_blocks, m->M_local, nz, m->value_bytes,
                                                             m->ldesc4, m->row_ptr, nullptr, m->lcol));
+    // equal segments and line lists once: before the searches below, which time the plan the handle keeps
+    if (!rc) csr_share_plan(m);
     if (!rc && !m->col) rc |= upload_array(&m->col, col_idx ? col_idx + e0 : nullptr, (size_t)nz, kPad);
     if (!rc && !m->val) rc |= upload_array((T **)&m->val, values ? values + e0 : nullptr, (size_t)nz, kPad);
     if (!rc) rc |= upload_array(&m->desc, desc.data(), desc.size(), 1);
@@ -1003,8 +1036,8 @@ int csr_upload_impl(int M, int N, const int *row_ptr, const int *col_idx, const 
                       long_rows.size() * 16 + pieces.size() * 16 + (size_t)num_partial * sizeof(T) +
                       ((size_t)N + (size_t)M) * sizeof(T);
     if (have_local)
-        m->device_bytes += (size_t)m->local_blocks * 24 + ((size_t)m->local_lines + kLocalLinesMax) * 4 +
-                           ((size_t)nz + kPad) * 2;
+        m->device_bytes += (size_t)m->local_blocks * 24 + (m->lbase ? (size_t)m->local_blocks * 4 : 0) +
+                           ((size_t)(m->lbase ? m->lines_stored : m->local_lines) + kLocalLinesMax) * 4 + ((size_t)nz + kPad) * 2;
     m->device_bytes += m->pat.bytes(Ml, m->local_blocks) + tile_bytes;
 
     // lanes per row for the SUBWAVE kernel: about half the mean row length,
@@ -1466,6 +1499,7 @@ extern "C" void spmv_hip_csr_free(spmv_csr_dev *m) {
     (void)hipFree(m->ldesc4);
     (void)hipFree(m->ldesc);
     (void)hipFree(m->lines);
+    (void)hipFree(m->lbase);
     (void)hipFree(m->lcol);
     m->pat.release();
     for (spmv_csr_dev::long_tiles *tier : {&m->mt}) {
@@ -1628,11 +1662,13 @@ extern "C" int spmv_hip_csr_stamp_blocks(spmv_csr_dev *m, int warm, unsigned lon
         if (lnt)
             hipLaunchKernelGGL((csr_stream_local<double, true, 2048, true>), dim3(lgrid), dim3(kBlock), lds, g_stream, lcount, lchunk,
                                (const int *)nullptr, m->ldesc4, m->ldesc, m->lines, m->row_ptr, m->lcol, (const double *)m->val,
-                               (const double *)m->x, y, d, probe);
+                               (const double *)m->x, y, d, probe, (const int2 *)nullptr, (const unsigned *)nullptr,
+                               (const unsigned short *)nullptr, 0, (const int2 *)nullptr, (const uint4 *)nullptr, m->lbase);
         else
             hipLaunchKernelGGL((csr_stream_local<double, false, 2048, true>), dim3(lgrid), dim3(kBlock), lds, g_stream, lcount, lchunk,
                                (const int *)nullptr, m->ldesc4, m->ldesc, m->lines, m->row_ptr, m->lcol, (const double *)m->val,
-                               (const double *)m->x, y, d, probe);
+                               (const double *)m->x, y, d, probe, (const int2 *)nullptr, (const unsigned *)nullptr,
+                               (const unsigned short *)nullptr, 0, (const int2 *)nullptr, (const uint4 *)nullptr, m->lbase);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
         if (e == hipSuccess) e = hipMemcpy(stamps_host, d, bytes, hipMemcpyDeviceToHost);
@@ -1748,6 +1784,8 @@ extern "C" int spmv_hip_csr_info(const spmv_csr_dev *m, spmv_dev_info *out) {
     out->pattern_segment_max = m->pat.ptab ? 16 * m->pat.seg_max : 0;
     out->pattern_segment_cap = 16 * m->pat.seg_cap;
     out->pattern_table_rows = m->pat.ptab ? m->pat.table_rows : 0;
+    out->pattern_segments_stored = m->pat.ptab && m->pat.pseg ? m->pat.seg_distinct : 0;
+    out->local_lists_stored = m->lbase ? m->lists_distinct : 0;
     out->stream_kernel = m->local_blocks > 0 ? 1 : m->tile_blocks > 0 ? 3
                          : ((m->stream_cap == 4096 || m->stream_cap == 2048) && m->M_local > 0 &&
                             m->nz < (long long)m->M_local * (m->stream_cap / kBlock)) ? 2 : 0;
@@ -1757,7 +1795,8 @@ extern "C" int spmv_hip_csr_info(const spmv_csr_dev *m, spmv_dev_info *out) {
         out->stream_bytes = m->nz * vb + (m->pat.ptab ? 16 * m->pat.seg_total + 8LL * m->local_blocks +
                                                             (2 * m->pat.slots + 8LL * m->M_local) * m->pat.table_rows / std::max(1, m->M_local)
                                                   : 2 * m->nz + 4LL * (m->M_local + 1)) +
-                            4 * m->local_lines + 24LL * m->local_blocks + vb * m->M_local + vb * m->N;
+                            (m->lbase ? 4 * m->lines_stored + 4LL * m->local_blocks : 4 * m->local_lines) +
+                            24LL * m->local_blocks + vb * m->M_local + vb * m->N;
     else if (m->tile_blocks > 0) {  // tiles: 4-byte column + 2-byte key + value per (padded) entry; rows beyond the limit as CSR
         out->stream_bytes = m->tile_padded * (vb + 6) - (m->tile_packed ? 2 : 0) * m->tile_staged + 16LL * m->tile_passes +
                             4LL * m->tile_blocks +
@@ -1960,10 +1999,12 @@ int csr_launch(const spmv_csr_dev *m, int variant, const T *x, T *y_full, hipStr
         if (patterns)                                                                                         \
             hipLaunchKernelGGL((csr_stream_local<T, NT, CAP, false, true>), dim3(lgrid), dim3(kBlock), pat_lds, s, lcount, lchunk, \
                                lids, m->ldesc4, m->ldesc, m->lines, m->row_ptr, m->lcol, (const T *)m->val, x, y, \
-                               (unsigned long long *)nullptr, 0, m->pat.pdesc, m->pat.rinfo, m->pat.ptab, (int)lds, m->pat.sdesc, (const uint4 *)m->pat.pseg); \
+                               (unsigned long long *)nullptr, 0, m->pat.pdesc, m->pat.rinfo, m->pat.ptab, (int)lds, m->pat.sdesc, (const uint4 *)m->pat.pseg, m->lbase); \
         else                                                                                                  \
             hipLaunchKernelGGL((csr_stream_local<T, NT, CAP>), dim3(lgrid), dim3(kBlock), lds, s, lcount, lchunk, lids, \
-                               m->ldesc4, m->ldesc, m->lines, m->row_ptr, m->lcol, (const T *)m->val, x, y);   \
+                               m->ldesc4, m->ldesc, m->lines, m->row_ptr, m->lcol, (const T *)m->val, x, y,    \
+                               (unsigned long long *)nullptr, 0, (const int2 *)nullptr, (const unsigned *)nullptr, \
+                               (const unsigned short *)nullptr, 0, (const int2 *)nullptr, (const uint4 *)nullptr, m->lbase); \
     } while (0)
                     // streamed-once hint only when the matrix cannot live in the 256 MiB Infinity Cache anyway
                     // (cant-like, 53 MB: 10.9 us without it, 11.7 us with; fem-large: 160 vs 151 us)
@@ -2077,6 +2118,20 @@ int csr_launch_part(const spmv_csr_dev *m, int part, const void *x, void *y, hip
     return csr_launch<float>(m, SPMV_CSR_STREAM, (const float *)x, (float *)y, s, part);
 }
 
+// The handle's line lists on the host, whichever way they are stored: ld[b] = {first id in `lines`, ids}, base[b] = what
+// block b adds to its ids (0 where the lists hold absolute ids).
+int csr_lines_to_host(const spmv_csr_dev *m, std::vector<int2> &ld, std::vector<int> &lines, std::vector<int> &base) {
+    const size_t B = (size_t)m->local_blocks;
+    ld.resize(B);
+    base.assign(B, 0);
+    lines.resize((size_t)(m->lbase ? m->lines_stored : m->local_lines));
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    if (B) HIP_TRY(hipMemcpy(ld.data(), m->ldesc, B * sizeof(int2), hipMemcpyDeviceToHost));
+    if (B && m->lbase) HIP_TRY(hipMemcpy(base.data(), m->lbase, B * sizeof(int), hipMemcpyDeviceToHost));
+    if (!lines.empty()) HIP_TRY(hipMemcpy(lines.data(), m->lines, lines.size() * sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // Which x-window blocks of the handle are interior: every x line they list lies inside the handle's own rows'
 // range of x (square matrix, x owned like y: entries [row0, row0 + M_local)).  Computed from the plan's line
 // lists (ascending inside a block: first and last line decide).  counts (optional, 4 values): interior blocks,
@@ -2093,19 +2148,17 @@ static int csr_split_interior_body(spmv_csr_dev *m, long long *counts) {
     long long e_in = 0, e_out = m->nz;
     if (m->local_blocks > 0) {
         const int B = m->local_blocks;
-        std::vector<int2> ld((size_t)B);
+        std::vector<int2> ld;
         std::vector<int4> d4((size_t)B);
-        std::vector<int> lines((size_t)m->local_lines);
-        HIP_TRY(hipStreamSynchronize(g_stream));
-        HIP_TRY(hipMemcpy(ld.data(), m->ldesc, ld.size() * sizeof(int2), hipMemcpyDeviceToHost));
+        std::vector<int> lines, lbase;
+        if (csr_lines_to_host(m, ld, lines, lbase)) return -1;
         HIP_TRY(hipMemcpy(d4.data(), m->ldesc4, d4.size() * sizeof(int4), hipMemcpyDeviceToHost));
-        if (!lines.empty()) HIP_TRY(hipMemcpy(lines.data(), m->lines, lines.size() * sizeof(int), hipMemcpyDeviceToHost));
         const int per_line = kLineBytes / m->value_bytes;
         const long long own_lo = m->row0, own_hi = (long long)m->row0 + m->M_local;  // [lo, hi) of x
         std::vector<int> in_ids, out_ids;
         for (int b = 0; b < B; ++b) {
-            const long long first = (long long)lines[(size_t)ld[b].x] * per_line;
-            const long long last = ((long long)lines[(size_t)ld[b].x + ld[b].y - 1] + 1) * per_line;  // exclusive
+            const long long first = ((long long)lines[(size_t)ld[b].x] + lbase[b]) * per_line;
+            const long long last = ((long long)lines[(size_t)ld[b].x + ld[b].y - 1] + lbase[b] + 1) * per_line;  // exclusive
             // (a block of empty rows lists line 0 only to have something to stage: it reads nothing)
             const bool empty = d4[b].w == d4[b].y;
             if (empty || (first >= own_lo && std::min<long long>(last, m->N) <= own_hi)) {

@@ -68,6 +68,7 @@ extern int g_tile_long;       // 1: the rows beyond the tile limit get a tile pl
 extern int g_tile_pack;       // 1: passes that can be staged store head | row | column offset in one 32-bit word (no key read)
 extern int g_tile_density;    // a pass is staged when it holds at least one entry per this many columns of its window
 extern int g_tile_mid_lo;     // a scattered matrix's rows longer than this (up to tile_lmax) form the middle tier ("tile_mid_lo")
+extern int g_local_share;     // x-window plans: equal segments / relative line lists stored once: -1 auto (on), 0 off, 1 on, 2 on with a hash of the length only ("local_share")
 extern int g_local_patterns;  // x-window plans: -1 auto (a pattern plan where it holds a quarter of the slots at most), 0 never, 1 always ("local_patterns")
 extern int g_tile_expand;     // plans with gather passes: -1 auto, 0 never, 1 always: x expanded into entry order ahead of csr_tile ("tile_expand")
 extern int g_tile_gather_ahead;  // 1: plans with gather passes run the csr_tile instantiation that gathers one pass early
@@ -188,6 +189,7 @@ struct PatternPlan {
     int seg_max = 0;                  // the widest segment kept (uint4s): the LDS the kernel adds behind the slots
     int seg_cap = 0;                  // the widest segment the LDS budget allowed (uint4s)
     long long table_rows = 0;         // rows of the blocks whose segment did not fit (they read rinfo, row_ptr and ptab)
+    long long seg_distinct = 0;       // segments stored: equal ones are stored once (share_spans), sdesc points many blocks at one
     float with_us = 0, without_us = 0;  // (auto) the kernel with / without the plan, timed at upload (tune_pattern_plan)
 
     size_t bytes(long long rows, long long blocks) const {
@@ -207,6 +209,7 @@ struct PatternPlan {
         seg_total = 0;
         seg_max = 0;
         table_rows = 0;
+        seg_distinct = 0;
     }
 };
 struct spmv_csr_dev {
@@ -234,6 +237,10 @@ struct spmv_csr_dev {
     int4 *ldesc4 = nullptr;           // [local_blocks] like desc
     int2 *ldesc = nullptr;            // [local_blocks] {first line in `lines`, line count}
     int *lines = nullptr;             // x line ids, block after block, ascending inside a block
+    int *lbase = nullptr;             // [local_blocks] shared line lists ("local_share"): a block's list counts from its first
+                                      // line, lbase[b]; equal lists are stored once.  nullptr: the lists hold absolute ids
+    long long lines_stored = 0;       // ... then the line ids `lines` holds (local_lines: what the blocks list)
+    long long lists_distinct = 0;     // ... and the lists
     unsigned short *lcol = nullptr;   // [nz + pad] slot of each entry in its block's staged lines
     PatternPlan pat;                  // the pattern plan of the blocks (the kernel then does not read lcol)
     int local_blocks = 0;            // 0: no plan (not profitable / not possible)
@@ -367,6 +374,9 @@ int csr_tiles_from_rows_f64(int M_local, int M_total, int row0, int N, const int
                             long long entries, const int *col, const double *val, spmv_csr_dev **out,
                             const int *d_col = nullptr, const double *d_val = nullptr);
 
+// spmv_csr.hip: the line lists of the handle's x-window plan on the host: ld[b] = {first id in `lines`, ids}, base[b] =
+// what block b adds to its ids (shared lists count from the block's first line; 0 otherwise)
+int csr_lines_to_host(const spmv_csr_dev *m, std::vector<int2> &ld, std::vector<int> &lines, std::vector<int> &base);
 int csr_tile_digest(const spmv_csr_dev *m, unsigned long long *out);  // spmv_csr.hip: see spmv_hip_csr_tile_digest
 // launchers the timing / exchange code calls across translation units
 int csr_launch_any(const spmv_csr_dev *m, int variant, const void *x, void *y, hipStream_t s);

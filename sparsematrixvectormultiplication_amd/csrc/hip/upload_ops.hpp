@@ -146,6 +146,107 @@ std::vector<int> build_pattern_tables(PatternPlan &pat, int blocks, int rows, lo
     return count;
 }
 
+// Every distinct span of `data` stored once (plan_kernels.hpp, shared spans).  desc[b] = {first element, elements} of
+// block b's span ({.., 0}: none, left alone); relative: spans count from their first element, which goes to *base
+// ([blocks], allocated here).  The spans are hashed on the device, equal (length, hash) keys grouped on the host, the
+// first block of a group its canonical; a block whose span is not the canonical's word for word keeps its own copy.
+// `data` is replaced by the compacted array (`pad` zeroed elements behind it) and desc rewritten; stored / distinct:
+// its elements and its spans.  False: a HIP failure -- the plan is what it was and the last error is cleared.
+template <typename E>
+bool share_spans(E *&data, int2 *desc, int blocks, size_t pad, bool relative, bool weak, int **base, long long &stored,
+                 long long &distinct) {
+    static_assert(sizeof(E) % 4 == 0, "spans are compared in 32-bit words");
+    constexpr int words = (int)(sizeof(E) / 4);
+    const size_t B = (size_t)blocks;
+    std::vector<int2> h_desc(B), keep;
+    std::vector<unsigned long long> h_hash(B);
+    std::vector<int> canon(B, -1), differs(B, 0), order;
+    unsigned long long *d_hash = nullptr;
+    int *d_base = nullptr, *d_canon = nullptr, *d_differs = nullptr;
+    int2 *d_keep = nullptr;
+    E *fresh = nullptr;
+    long long total = 0;
+    const unsigned *words_in = reinterpret_cast<const unsigned *>(data);
+    hipError_t e = hipMalloc((void **)&d_hash, B * sizeof(unsigned long long));
+    if (e == hipSuccess && relative) e = hipMalloc((void **)&d_base, B * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_canon, B * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_differs, B * sizeof(int));
+    if (e == hipSuccess) e = hipMemsetAsync(d_differs, 0, B * sizeof(int), g_stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL((share_hash<256>), dim3(blocks), dim3(256), 0, g_stream, blocks, desc, words_in, words,
+                           relative ? 1 : 0, weak ? 1 : 0, d_hash, d_base);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(h_hash.data(), d_hash, B * sizeof(unsigned long long), hipMemcpyDeviceToHost, g_stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h_desc.data(), desc, B * sizeof(int2), hipMemcpyDeviceToHost, g_stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
+    if (e == hipSuccess) {
+        for (int b = 0; b < blocks; ++b)
+            if (h_desc[(size_t)b].y > 0) order.push_back(b);
+        std::sort(order.begin(), order.end(), [&](int a, int b) {
+            if (h_desc[(size_t)a].y != h_desc[(size_t)b].y) return h_desc[(size_t)a].y < h_desc[(size_t)b].y;
+            if (h_hash[(size_t)a] != h_hash[(size_t)b]) return h_hash[(size_t)a] < h_hash[(size_t)b];
+            return a < b;
+        });
+        for (size_t k = 0; k < order.size(); ++k) {
+            const int b = order[k], p = k ? order[k - 1] : -1;
+            const bool same = p >= 0 && h_desc[(size_t)p].y == h_desc[(size_t)b].y && h_hash[(size_t)p] == h_hash[(size_t)b];
+            canon[(size_t)b] = same ? canon[(size_t)p] : b;
+        }
+        e = hipMemcpyAsync(d_canon, canon.data(), B * sizeof(int), hipMemcpyHostToDevice, g_stream);
+    }
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL((share_verify<256>), dim3(blocks), dim3(256), 0, g_stream, blocks, desc, words_in, words,
+                           relative ? 1 : 0, d_canon, d_differs);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(differs.data(), d_differs, B * sizeof(int), hipMemcpyDeviceToHost, g_stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
+    if (e == hipSuccess) {
+        // the kept spans in block order (a canonical is the first block of its group: it comes before its sharers)
+        for (int b = 0; b < blocks; ++b) {
+            int2 &d = h_desc[(size_t)b];
+            if (d.y <= 0) continue;
+            if (canon[(size_t)b] == b || differs[(size_t)b]) {
+                canon[(size_t)b] = b;
+                keep.push_back(make_int2(b, (int)total));
+                total += d.y;
+            }
+        }
+        e = hipMalloc((void **)&fresh, ((size_t)total + pad) * sizeof(E));
+        if (e == hipSuccess && pad) e = hipMemsetAsync(fresh + total, 0, pad * sizeof(E), g_stream);
+        if (e == hipSuccess) e = hipMalloc((void **)&d_keep, std::max<size_t>(keep.size(), 1) * sizeof(int2));
+        if (e == hipSuccess && !keep.empty())
+            e = hipMemcpyAsync(d_keep, keep.data(), keep.size() * sizeof(int2), hipMemcpyHostToDevice, g_stream);
+    }
+    if (e == hipSuccess && !keep.empty()) {
+        hipLaunchKernelGGL((share_gather<256>), dim3((unsigned)keep.size()), dim3(256), 0, g_stream, (int)keep.size(), d_keep,
+                           desc, words_in, words, relative ? 1 : 0, reinterpret_cast<unsigned *>(fresh));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
+    if (e == hipSuccess) {
+        // (the descriptors last: until here the plan is untouched)
+        for (const int2 &k : keep) h_desc[(size_t)k.x].x = k.y;
+        for (int b = 0; b < blocks; ++b)
+            if (h_desc[(size_t)b].y > 0) h_desc[(size_t)b].x = h_desc[(size_t)canon[(size_t)b]].x;
+        e = hipMemcpy(desc, h_desc.data(), B * sizeof(int2), hipMemcpyHostToDevice);
+    }
+    for (void *p : {(void *)d_hash, (void *)d_canon, (void *)d_differs, (void *)d_keep}) (void)hipFree(p);
+    if (e != hipSuccess) {
+        (void)hipFree(fresh);
+        (void)hipFree(d_base);
+        (void)hipGetLastError();
+        return false;
+    }
+    (void)hipFree(data);
+    data = fresh;
+    if (base) *base = d_base;
+    stored = total;
+    distinct = (long long)keep.size();
+    return true;
+}
+
 // One pair of events for the searches.  time(): 2 untimed + 6 timed launches -> us per launch; false when a launch or
 // the timing failed.
 struct UploadTimer {

@@ -37,10 +37,17 @@ def bench_line(log):
     raise SystemExit(f"no bench JSON line in {log}")
 
 
-def per_product(sub, counter, products):
+def products_of(line):
+    """Products one profiled bench ran at N = 1: the untimed settle launches (--settle-ms: as many as fit the time, so
+    every pass has its own count), W warm-ups + 1, then the K timed steps."""
+    return int(line["steps"]) + int(line["warmup"]) + 1 + int(line["config"].get("settle_launches_before_warmup", 0))
+
+
+def per_product(sub, counter):
     """Counter value per SpMV: the sum over ALL dispatches of a kernel name divided by the number of products the
-    profiled bench ran (a kernel that is launched twice per product -- csr_tile: ordinary tiles + long rows' tiles --
-    must be added up, not averaged)."""
+    profiled bench of THIS pass ran (a kernel that is launched twice per product -- csr_tile: ordinary tiles + long
+    rows' tiles -- must be added up, not averaged)."""
+    products = products_of(bench_line(os.path.join(root, sub + ".log")))
     acc = defaultdict(float)
     files = sorted(glob.glob(os.path.join(root, sub, "**", "*counter_collection.csv"), recursive=True), key=os.path.getmtime)
     for f in files[-1:]:  # the newest pass only (a merged gpurun_out/ keeps earlier runs' files beside it)
@@ -53,9 +60,8 @@ def per_product(sub, counter, products):
 line = bench_line(os.path.join(root, "trace.log"))
 kernel = line["roofline"]["kernel"]
 workload = line["config"]["workload_key"]
-products = int(line["steps"]) + int(line["warmup"]) + 1   # bench.py at N = 1: W warm-ups + 1, then the K timed steps
-fetch = per_product("pmc_fetch", "FETCH_SIZE", products)
-write = per_product("pmc_write", "WRITE_SIZE", products)
+fetch = per_product("pmc_fetch", "FETCH_SIZE")
+write = per_product("pmc_write", "WRITE_SIZE")
 out_path = os.path.join(ROOT, "profiles", "traffic.json")
 table = json.load(open(out_path)) if os.path.exists(out_path) else {}
 table = {k: v for k, v in table.items() if isinstance(v, dict)}  # round-1 entries carried no stamp
