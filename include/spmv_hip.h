@@ -764,6 +764,62 @@ enum { SPMV_MINRES_RAN_ALL = 0, SPMV_MINRES_CONVERGED = 1, SPMV_MINRES_BREAKDOWN
 int spmv_hip_csr_minres(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, double tol, double shift,
                         const int *bounds, const void *b_host, void *x_host, double *rr_hist, int *info,
                         float *ms_total);
+/* LOBPCG (Knyazev 2001) for the k smallest (largest = 0) or largest eigenpairs of a symmetric A held by an fp64 CSR
+ * handle, with an optional symmetric positive definite preconditioner (Jacobi, block-Jacobi or FSAI; smallest only).
+ * Six row-major n x k arrays X, W, P, AX, AW, AP (element (i, j) at i k + j, the SpMM's layout).  Per step one SpMM
+ * (spmv_hip_csr_spmm_on), one k-wide apply (spmv_hip_precond_apply_multi_on), a Gram pass and an update pass over the
+ * basis S = [X | W | P], AS = [AX | AW | AP] (lobpcg_kernels.hpp), and a Rayleigh-Ritz step on the host.
+ *   anorm = ||A||_inf (row sums of |a| in entry order, then the maximum)
+ *   step 0:  X = X0;  AX = A X;  G_B = X^T X, G_A = X^T AX;  (theta, C) = rr(G_B, G_A);  X = X C;  AX = AX C
+ *   step t = 0, 1, ...:
+ *            W = AX - X diag(theta);  res_hist[t, j] = ||w_j||_2;  theta_hist[t, j] = theta_j
+ *            CONVERGED when tol > 0 and every ||w_j|| <= tol anorm;  RAN_ALL when t == iters
+ *            W = M^-1 W (with P);  AW = A W
+ *            G_B = S^T S, G_A = S^T AS  (nb = 2 blocks at t = 0, where there is no P yet, 3 afterwards)
+ *            (theta, C, Cp) = rr(G_B, G_A);  X = S C;  P = S Cp;  AX = AS C;  AP = AS Cp
+ *   after the loop:  AW = A X;  resid[j] = ||A x_j - theta_j x_j||_2;  w = theta
+ * rr is spmv_lobpcg_rr below.  There is no explicit projection of W on X and no locking: a converged column keeps
+ * riding.  The host reads the Gram matrices in every step: there is no sync-free mode, and tol = 0 means exactly
+ * `iters` steps.
+ * BREAKDOWN: at step 0 when a Gram entry is not finite or X0 has fewer than k independent columns (w and X are then
+ * zeros, steps = 0); in step t when a residual norm or a Gram entry is not finite or fewer than k basis directions
+ * are kept: X stays at the last full iterate.  After a stop both histories repeat their last row.
+ * Sums: a Gram entry adds its rows 4 at a time (one fp64 MFMA per 16 x 16 tile), a wave its row groups in grid-stride
+ * order, the waves of a workgroup in wave order, the workgroups in workgroup order; the residual norms as
+ * spmv_hip_csr_cg_multi's dots.  No atomics: two calls give the same bits.
+ * X0_host: n x k.  Out (all optional): w[k]; X_host n x k; theta_hist, res_hist (iters + 1) x k; resid[k]; *anorm;
+ * info[4] = {steps, status (SPMV_LOBPCG_*), restarts (steps that dropped P), the smallest basis size kept in any
+ * step}; *ms device time of the whole solve; *host_ms wall time inside spmv_lobpcg_rr.
+ * -1: NULL m or X0_host, an fp32 handle, a non-square, row-range or tiles-only handle, an active communicator, k
+ * outside [1, 16], n < 4 k, iters < 0, tol < 0 or not finite, a P of kind SSOR or ILU0 (no k-wide apply), a P whose
+ * rows, row0 or dtype differ from the handle's, any P together with largest.
+ *   spmv_lobpcg_rr          host only (csrc/host/lobpcg_rr.c).  GB = S^T S, GA = S^T AS, both m x m row-major, m = nb k,
+ *                           nb in [1, 3], k in [1, 16].  Both are symmetrised; D = diag(GB)^-1/2 (0 where the diagonal
+ *                           is <= 1e-290); D GB D = V L V^T; the directions with L_i > drop max L are kept.  When some
+ *                           were dropped and nb == 3 the same is done on the leading 2k x 2k blocks (*restarted = 1, the
+ *                           P rows of C are 0).  T = D V_keep L_keep^-1/2; T^T GA T = Z diag(ritz) Z^T; theta = the k
+ *                           smallest ascending (largest: the k largest descending); C = T Z_k (m x k row-major);
+ *                           Cp = C with its first k rows 0, each column scaled to Cp_j^T GB Cp_j = 1 (a zero column
+ *                           stays 0).  *kept = directions kept.  The eigenproblems are solved by Householder
+ *                           tridiagonalisation and implicit QL.  Returns 0; SPMV_LOBPCG_RR_BREAKDOWN when an entry is
+ *                           not finite or kept < k (theta, C, Cp are then not to be used); -1 for bad arguments.
+ *   spmv_hip_lobpcg_gram    the Gram pass alone on device arrays: d_S[nb], d_AS[nb] row-major n x k fp64 (entries from nb
+ *                           on are not read and may be NULL) -> GB_host, GA_host (m x m).  Synchronous.
+ *   spmv_hip_lobpcg_update  the update pass alone: X = S C, P = S Cp, AX = AS C, AP = AS Cp with C_host, Cp_host m x k;
+ *                           the outputs may be the S / AS blocks themselves (a row is read completely before it is
+ *                           written).  Synchronous.  Both: -1 for n < 0, k outside [1, 16], nb outside [1, 3], n k
+ *                           beyond int range, a NULL or misaligned array. */
+enum { SPMV_LOBPCG_RAN_ALL = 0, SPMV_LOBPCG_CONVERGED = 1, SPMV_LOBPCG_BREAKDOWN = 2 };
+enum { SPMV_LOBPCG_RR_BREAKDOWN = 1 };
+int spmv_hip_csr_lobpcg(spmv_csr_dev *m, const spmv_precond *P, int k, int iters, double tol, int largest,
+                        const double *X0_host, double *w, double *X_host, double *theta_hist, double *res_hist,
+                        double *resid, double *anorm, int *info, float *ms, float *host_ms);
+int spmv_lobpcg_rr(int nb, int k, const double *GB, const double *GA, int largest, double drop, double *theta,
+                   double *C, double *Cp, int *kept, int *restarted);
+int spmv_hip_lobpcg_gram(long long n, int k, int nb, const void *const *d_S, const void *const *d_AS,
+                         double *GB_host, double *GA_host);
+int spmv_hip_lobpcg_update(long long n, int k, int nb, const void *const *d_S, const void *const *d_AS,
+                           const double *C_host, const double *Cp_host, void *d_X, void *d_P, void *d_AX, void *d_AP);
 int spmv_hip_csr_split_interior(spmv_csr_dev *m, long long *counts);
 /* N4 overlap below block granularity (round 3).  On a KKT-coupled cut every block also lists lines of the coupling block,
  * which another rank owns: no interior BLOCKS -- but 13 of a row's 28 entries have their column in the rank's own range.

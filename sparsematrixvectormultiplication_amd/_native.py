@@ -257,6 +257,15 @@ _PROTOTYPES = {
                                          C.c_void_p, c_double_p, c_int_p, c_float_p]),
     "spmv_hip_csr_minres": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, c_int_p,
                                       C.c_void_p, C.c_void_p, c_double_p, c_int_p, c_float_p]),
+    "spmv_hip_csr_lobpcg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, c_double_p,
+                                      c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p,
+                                      c_float_p, c_float_p]),
+    "spmv_lobpcg_rr": (C.c_int, [C.c_int, C.c_int, c_double_p, c_double_p, C.c_int, C.c_double, c_double_p, c_double_p,
+                                 c_double_p, c_int_p, c_int_p]),
+    "spmv_hip_lobpcg_gram": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                       c_double_p, c_double_p]),
+    "spmv_hip_lobpcg_update": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                         c_double_p, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spmv_hip_csr_cgls": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                     c_double_p, c_double_p, c_int_p, c_float_p]),
     "spmv_hip_csr_needed_ranges": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_int_p]),

@@ -23,6 +23,9 @@ CGLS_RAN_ALL, CGLS_CONVERGED, CGLS_BREAKDOWN = 0, 1, 2
 PCG_RAN_ALL, PCG_CONVERGED, PCG_BREAKDOWN = 0, 1, 2
 # CsrDevice.minres: info["status"] (SPMV_MINRES_* of include/spmv_hip.h)
 MINRES_RAN_ALL, MINRES_CONVERGED, MINRES_BREAKDOWN = 0, 1, 2
+# CsrDevice.lobpcg: info["status"] (SPMV_LOBPCG_* of include/spmv_hip.h); its limits
+LOBPCG_RAN_ALL, LOBPCG_CONVERGED, LOBPCG_BREAKDOWN = 0, 1, 2
+LOBPCG_MAX_K, LOBPCG_DROP = 16, 1e-10
 PRECOND_JACOBI, PRECOND_BLOCK_JACOBI, PRECOND_SSOR, PRECOND_ILU0, PRECOND_FSAI = 1, 2, 3, 4, 5
 PRECOND_KINDS = {"jacobi": PRECOND_JACOBI, "block_jacobi": PRECOND_BLOCK_JACOBI, "ssor": PRECOND_SSOR,
                  "ilu0": PRECOND_ILU0, "fsai": PRECOND_FSAI}
@@ -566,6 +569,59 @@ class CsrDevice(_Handle):
                                              C.byref(ms)), "spmv_hip_csr_minres")
         return x, hist, {"steps": int(info[0]), "status": int(info[1])}, float(ms.value)
 
+    def lobpcg(self, k, iters, tol=0.0, precond=None, X0=None, largest=False, seed=0):
+        """LOBPCG (spmv_hip_csr_lobpcg) for the k smallest (largest=True: largest) eigenpairs of a symmetric fp64 A,
+        1 <= k <= 16, n >= 4 k.  precond: a Jacobi, block-Jacobi or FSAI Preconditioner of this handle (smallest only),
+        or None.  X0: n x k starting block (None: np.random.default_rng(seed).standard_normal((n, k))).  Stops as
+        converged once tol > 0 and every residual norm <= tol ||A||_inf; tol = 0 runs exactly `iters` steps (the host
+        reads the Gram matrices in every step either way).  Returns (w [k] ascending (largest: descending), X (n, k),
+        theta history (iters + 1, k), residual-norm history (iters + 1, k), info {"steps", "status" (LOBPCG_*),
+        "restarts", "min_basis", "resid" [k] (the true ||A x - w x||), "anorm", "host_ms"}, ms)."""
+        if np.dtype(self.dtype) != np.dtype(np.float64):
+            raise ValueError(f"lobpcg needs an fp64 handle, this one holds {np.dtype(self.dtype)}")
+        if self.M != self.N:
+            raise ValueError(f"lobpcg needs a square matrix, got {self.M} x {self.N}")
+        if self._own_rows() != (0, self.M):
+            raise ValueError(f"lobpcg needs the whole matrix, the handle holds rows {self._own_rows()}")
+        if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= LOBPCG_MAX_K:
+            raise ValueError(f"k must be an integer in [1, {LOBPCG_MAX_K}], got {k!r}")
+        k = int(k)
+        if self.M < 4 * k:
+            raise ValueError(f"lobpcg needs n >= 4 k = {4 * k}, got n = {self.M}")
+        if int(iters) < 0:
+            raise ValueError(f"iters must be >= 0, got {iters}")
+        if not float(tol) >= 0.0 or not np.isfinite(float(tol)):
+            raise ValueError(f"tol must be finite and >= 0, got {tol}")
+        if precond is not None:
+            self._check_precond(precond)
+            if precond.kind in (PRECOND_SSOR, PRECOND_ILU0):
+                raise ValueError("lobpcg: SSOR and ILU(0) take one right-hand side, they have no k-wide apply")
+            if largest:
+                raise ValueError("lobpcg: a preconditioner serves the smallest eigenvalues only")
+        from .distributed import NativeComm  # (distributed imports this module)
+        if NativeComm.active:
+            raise ValueError("lobpcg runs on one device, a communicator is active (NativeComm.close() first)")
+        if X0 is None:
+            X0 = np.random.default_rng(seed).standard_normal((self.M, k))
+        X0 = np.asarray(X0)
+        if X0.dtype != np.float64 or X0.shape != (self.M, k):
+            raise ValueError(f"X0 must be a float64 array of shape ({self.M}, {k}), got {X0.dtype} {X0.shape}")
+        X0 = np.ascontiguousarray(X0)
+        iters = int(iters)
+        w, X, resid = np.zeros(k), np.zeros((self.M, k)), np.zeros(k)
+        th, rh = np.zeros((iters + 1, k)), np.zeros((iters + 1, k))
+        words = np.zeros(4, dtype=np.int32)
+        anorm, ms, host_ms = C.c_double(0), C.c_float(0), C.c_float(0)
+        dp = nat.c_double_p
+        _check(nat.lib().spmv_hip_csr_lobpcg(self.h, None if precond is None else precond.h, k, iters, float(tol),
+                                             int(bool(largest)), X0.ctypes.data_as(dp), w.ctypes.data_as(dp),
+                                             X.ctypes.data_as(dp), th.ctypes.data_as(dp), rh.ctypes.data_as(dp),
+                                             resid.ctypes.data_as(dp), C.byref(anorm), words.ctypes.data_as(nat.c_int_p),
+                                             C.byref(ms), C.byref(host_ms)), "spmv_hip_csr_lobpcg")
+        info = {"steps": int(words[0]), "status": int(words[1]), "restarts": int(words[2]), "min_basis": int(words[3]),
+                "resid": resid, "anorm": float(anorm.value), "host_ms": float(host_ms.value)}
+        return w, X, th, rh, info, float(ms.value)
+
     def cgls(self, b, iters, tol=0.0, damp=0.0, at=None):
         """CGLS from x0 = 0 for min ||A x - b||^2 + damp^2 ||x||^2, A of any shape (spmv_hip_csr_cgls).  at: a
         transpose of this handle (CsrDevice.transpose); None: one is built for the call and freed after it (its build
@@ -648,6 +704,57 @@ class CsrDevice(_Handle):
                                                 mk.ctypes.data_as(nat.c_float_p),
                                                 mx.ctypes.data_as(nat.c_float_p)), "csr_step_time")
         return mk, mx
+
+
+def lobpcg_rr(GB, GA, nb, k, largest=False, drop=LOBPCG_DROP):
+    """The Rayleigh-Ritz step of lobpcg on the host (spmv_lobpcg_rr): GB = S^T S, GA = S^T AS, both (nb k) x (nb k).
+    Returns (rc (0, or 1: breakdown), theta [k], C (nb k, k), Cp (nb k, k), kept, restarted)."""
+    m = int(nb) * int(k)
+    GB = np.ascontiguousarray(GB, dtype=np.float64)
+    GA = np.ascontiguousarray(GA, dtype=np.float64)
+    if GB.shape != (m, m) or GA.shape != (m, m):
+        raise ValueError(f"GB and GA must be {m} x {m}, got {GB.shape} and {GA.shape}")
+    theta, Cm, Cp = np.zeros(int(k)), np.zeros((m, int(k))), np.zeros((m, int(k)))
+    kept, restarted = C.c_int(0), C.c_int(0)
+    dp = nat.c_double_p
+    rc = nat.lib().spmv_lobpcg_rr(int(nb), int(k), GB.ctypes.data_as(dp), GA.ctypes.data_as(dp), int(bool(largest)),
+                                  float(drop), theta.ctypes.data_as(dp), Cm.ctypes.data_as(dp), Cp.ctypes.data_as(dp),
+                                  C.byref(kept), C.byref(restarted))
+    if rc < 0:
+        raise ValueError(f"spmv_lobpcg_rr refused nb = {nb}, k = {k}, drop = {drop}")
+    return rc, theta, Cm, Cp, int(kept.value), int(restarted.value)
+
+
+def _block_pointers(blocks):
+    arr = (C.c_void_p * 3)()
+    for i, p in enumerate(blocks):
+        arr[i] = C.c_void_p(p) if p else None
+    return arr
+
+
+def lobpcg_gram(n, k, nb, d_S, d_AS):
+    """The Gram pass of lobpcg alone (spmv_hip_lobpcg_gram) on device arrays: d_S, d_AS are up to 3 device addresses
+    of row-major n x k fp64 blocks (those from nb on may be 0).  Returns (S^T S, S^T AS), each (nb k) x (nb k)."""
+    m = int(nb) * int(k)
+    GB, GA = np.zeros((m, m)), np.zeros((m, m))
+    _check(nat.lib().spmv_hip_lobpcg_gram(int(n), int(k), int(nb), _block_pointers(d_S), _block_pointers(d_AS),
+                                          GB.ctypes.data_as(nat.c_double_p), GA.ctypes.data_as(nat.c_double_p)),
+           "spmv_hip_lobpcg_gram")
+    return GB, GA
+
+
+def lobpcg_update(n, k, nb, d_S, d_AS, Cm, Cp, d_X, d_P, d_AX, d_AP):
+    """The update pass of lobpcg alone (spmv_hip_lobpcg_update): X = S C, P = S Cp, AX = AS C, AP = AS Cp on device
+    arrays; the outputs may be blocks of S / AS."""
+    m = int(nb) * int(k)
+    Cm = np.ascontiguousarray(Cm, dtype=np.float64)
+    Cp = np.ascontiguousarray(Cp, dtype=np.float64)
+    if Cm.shape != (m, int(k)) or Cp.shape != (m, int(k)):
+        raise ValueError(f"C and Cp must be {m} x {k}, got {Cm.shape} and {Cp.shape}")
+    _check(nat.lib().spmv_hip_lobpcg_update(int(n), int(k), int(nb), _block_pointers(d_S), _block_pointers(d_AS),
+                                            Cm.ctypes.data_as(nat.c_double_p), Cp.ctypes.data_as(nat.c_double_p),
+                                            C.c_void_p(d_X), C.c_void_p(d_P), C.c_void_p(d_AX), C.c_void_p(d_AP)),
+           "spmv_hip_lobpcg_update")
 
 
 def _check_vector(v, rows, dtype, name, owner):

@@ -106,7 +106,10 @@ def halo_plan(rank, bounds, all_ranges, max_segments=4096):
 
 
 class NativeComm:
-    """RCCL communicator owned by libspmv_amd.so (spmv_hip_comm_*)."""
+    """RCCL communicator owned by libspmv_amd.so (spmv_hip_comm_*).  The library holds one at a time; `active` is
+    True from a successful construction to close() (what the single-device methods, CsrDevice.lobpcg, look at)."""
+
+    active = False
 
     def __init__(self, rank, world, exchange_id):
         """exchange_id(bytes_or_None) -> bytes: hands rank 0's id to every rank."""
@@ -118,6 +121,7 @@ class NativeComm:
             raise SpmvHipError("communicator id has the wrong length")
         _check(nat.lib().spmv_hip_comm_init(ident, int(rank), int(world)), "spmv_hip_comm_init")
         self.rank, self.world = rank, world
+        NativeComm.active = True
 
     def allgatherv(self, d_y: int, bounds, value_bytes=8, stream: int = 0):
         b = np.ascontiguousarray(bounds, dtype=np.int32)
@@ -155,6 +159,7 @@ class NativeComm:
 
     def close(self):
         nat.lib().spmv_hip_comm_destroy()
+        NativeComm.active = False
 
 
 class RowPartitionedCsr:
