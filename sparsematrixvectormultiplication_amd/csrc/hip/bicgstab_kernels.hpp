@@ -33,16 +33,17 @@ constexpr int kBcgBlocks = 2048;  // grid cap of the vector kernels
 // the scalar slots (doubles).  Two-value reductions land in adjacent slots: (Rho, Rr0), (Ts, Tt), (RhoNew, Rr).
 constexpr int kBcgRho = 0, kBcgRr0 = 1, kBcgRv = 2, kBcgAlpha = 3, kBcgSs = 4, kBcgTs = 5, kBcgTt = 6, kBcgOmega = 7,
               kBcgRhoNew = 8, kBcgRr = 9, kBcgBeta = 10, kBcgLast = 11, kBcgLocal = 12, kBcgSlots = 16;
-// the int words
-constexpr int kBcgState = 0, kBcgSteps = 1, kBcgStatus = 2, kBcgHalf = 3, kBcgFlagWords = 4;
-constexpr int kBcgRun = 0, kBcgHalfStep = 1, kBcgStop = 2;
+// the int words: the stop flags of solver_ops.hpp, word 3 = the stop came at a half step; the state passes through
+// kBcgHalfStep (the x update of that step still runs) on its way to kBcgStop
+constexpr int kBcgHalf = 3;
+constexpr int kBcgHalfStep = 1, kBcgStop = 2;
 
 // partials of a.b on [lo, hi)
 template <typename T, int V>
 __global__ __launch_bounds__(kBlock) void bcg_dot(long long lo, long long hi, const int *__restrict__ flags,
                                                   const T *__restrict__ a, const T *__restrict__ b,
                                                   double *__restrict__ part) {
-    if (flags[kBcgState] != kBcgRun) return;
+    if (flags[kSolverState] != kSolverRun) return;
     double acc[1] = {0.0};
     for (PieceLane l(lo, hi, V); l.q < l.end; l.q += l.stride) {
         const long long i0 = l.q * V;
@@ -60,7 +61,7 @@ template <typename T, int V>
 __global__ __launch_bounds__(kBlock) void bcg_dot2(long long lo, long long hi, const int *__restrict__ flags,
                                                    const T *__restrict__ a, const T *__restrict__ b,
                                                    double *__restrict__ part) {
-    if (flags[kBcgState] != kBcgRun) return;
+    if (flags[kSolverState] != kSolverRun) return;
     double acc[2] = {0.0, 0.0};
     for (PieceLane l(lo, hi, V); l.q < l.end; l.q += l.stride) {
         const long long i0 = l.q * V;
@@ -83,7 +84,7 @@ __global__ __launch_bounds__(kBlock) void bcg_update_s(long long lo, long long h
                                                        const double *__restrict__ sc, const T *__restrict__ r,
                                                        const T *__restrict__ v, T *__restrict__ s,
                                                        double *__restrict__ part) {
-    if (flags[kBcgState] != kBcgRun) return;
+    if (flags[kSolverState] != kSolverRun) return;
     const double alpha = sc[kBcgAlpha];
     double acc[1] = {0.0};
     for (PieceLane l(lo, hi, V); l.q < l.end; l.q += l.stride) {
@@ -108,7 +109,7 @@ __global__ __launch_bounds__(kBlock) void bcg_update_x_r(long long lo, long long
                                                          const T *__restrict__ p, const T *__restrict__ s,
                                                          const T *__restrict__ t, T *__restrict__ x,
                                                          T *__restrict__ r, double *__restrict__ part) {
-    const int state = flags[kBcgState];
+    const int state = flags[kSolverState];
     if (state == kBcgStop) return;
     const double alpha = sc[kBcgAlpha];
     double acc[2] = {0.0, 0.0};
@@ -154,7 +155,7 @@ template <typename T, int V>
 __global__ __launch_bounds__(kBlock) void bcg_update_p(long long lo, long long hi, const int *__restrict__ flags,
                                                        const double *__restrict__ sc, const T *__restrict__ r,
                                                        const T *__restrict__ v, T *__restrict__ p) {
-    if (flags[kBcgState] != kBcgRun) return;
+    if (flags[kSolverState] != kSolverRun) return;
     const double beta = sc[kBcgBeta], omega = sc[kBcgOmega];
     for (PieceLane l(lo, hi, V); l.q < l.end; l.q += l.stride) {
         const long long i0 = l.q * V;
@@ -179,7 +180,7 @@ __global__ __launch_bounds__(kBlock) void bcg_jac_update_s(long long lo, long lo
                                                            const T *__restrict__ v, const T *__restrict__ dinv,
                                                            T *__restrict__ s, T *__restrict__ sh,
                                                            double *__restrict__ part) {
-    if (flags[kBcgState] != kBcgRun) return;
+    if (flags[kSolverState] != kSolverRun) return;
     const double alpha = sc[kBcgAlpha];
     double acc[1] = {0.0};
     for (PieceLane l(lo, hi, V); l.q < l.end; l.q += l.stride) {
@@ -208,7 +209,7 @@ __global__ __launch_bounds__(kBlock) void bcg_pre_update_x_r(long long lo, long 
                                                              const T *__restrict__ s, const T *__restrict__ t,
                                                              T *__restrict__ x, T *__restrict__ r,
                                                              double *__restrict__ part) {
-    const int state = flags[kBcgState];
+    const int state = flags[kSolverState];
     if (state == kBcgStop) return;
     const double alpha = sc[kBcgAlpha];
     double acc[2] = {0.0, 0.0};
@@ -256,7 +257,7 @@ __global__ __launch_bounds__(kBlock) void bcg_jac_update_p(long long lo, long lo
                                                            const double *__restrict__ sc, const T *__restrict__ r,
                                                            const T *__restrict__ v, const T *__restrict__ dinv,
                                                            T *__restrict__ p, T *__restrict__ ph) {
-    if (flags[kBcgState] != kBcgRun) return;
+    if (flags[kSolverState] != kSolverRun) return;
     const double beta = sc[kBcgBeta], omega = sc[kBcgOmega];
     for (PieceLane l(lo, hi, V); l.q < l.end; l.q += l.stride) {
         const long long i0 = l.q * V;
@@ -275,31 +276,27 @@ __global__ __launch_bounds__(kBlock) void bcg_jac_update_p(long long lo, long lo
     }
 }
 
-// ---- the scalar kernels: one thread each.  A stop writes the status and the steps taken and never touches x.
-__device__ __forceinline__ void bcg_stop(int *__restrict__ flags, int status, int steps) {
-    flags[kBcgState] = kBcgStop;
-    flags[kBcgStatus] = status;
-    flags[kBcgSteps] = steps;
-}
+// ---- the scalar kernels: one thread each.  A stop (solver_stop with state kBcgStop) writes the status and the steps
+// taken and never touches x.
 
 // rho = r^.r, rr0 = r.r (slots kBcgRho, kBcgRr0), history row 0; rr0 = 0 (b = 0) stops at step 0, converged
 __global__ void bcg_start(double *__restrict__ sc, int *__restrict__ flags, double *__restrict__ hist, int iters) {
     const double rr0 = sc[kBcgRr0];
     sc[kBcgLast] = rr0;
     hist[0] = rr0;
-    flags[kBcgState] = kBcgRun;
-    flags[kBcgSteps] = iters;
-    flags[kBcgStatus] = SPMV_BICG_RAN_ALL;
+    flags[kSolverState] = kSolverRun;
+    flags[kSolverSteps] = iters;
+    flags[kSolverStatus] = SPMV_BICG_RAN_ALL;
     flags[kBcgHalf] = 0;
-    if (rr0 == 0.0) bcg_stop(flags, SPMV_BICG_CONVERGED, 0);
+    if (rr0 == 0.0) solver_stop(flags, SPMV_BICG_CONVERGED, 0, kBcgStop);
 }
 
 // step t: alpha = rho / r^.v; r^.v = 0 or not finite breaks down (step t not taken)
 __global__ void bcg_set_alpha(double *__restrict__ sc, int *__restrict__ flags, int t) {
-    if (flags[kBcgState] != kBcgRun) return;
+    if (flags[kSolverState] != kSolverRun) return;
     const double rv = sc[kBcgRv];
     if (rv == 0.0 || !isfinite(rv)) {
-        bcg_stop(flags, SPMV_BICG_BREAKDOWN_RHO, t - 1);
+        solver_stop(flags, SPMV_BICG_BREAKDOWN_RHO, t - 1, kBcgStop);
         return;
     }
     sc[kBcgAlpha] = sc[kBcgRho] / rv;
@@ -307,12 +304,12 @@ __global__ void bcg_set_alpha(double *__restrict__ sc, int *__restrict__ flags, 
 
 // step t: s.s <= tol2 rr0 converges at the half step (x += alpha p, r = s are still to be applied: state HALF)
 __global__ void bcg_check_s(double *__restrict__ sc, int *__restrict__ flags, int t, double tol2) {
-    if (flags[kBcgState] != kBcgRun) return;
+    if (flags[kSolverState] != kSolverRun) return;
     const double ss = sc[kBcgSs];
     if (ss <= tol2 * sc[kBcgRr0]) {
-        flags[kBcgState] = kBcgHalfStep;
-        flags[kBcgStatus] = SPMV_BICG_CONVERGED;
-        flags[kBcgSteps] = t;
+        flags[kSolverState] = kBcgHalfStep;
+        flags[kSolverStatus] = SPMV_BICG_CONVERGED;
+        flags[kSolverSteps] = t;
         flags[kBcgHalf] = 1;
         sc[kBcgLast] = ss;
     }
@@ -320,10 +317,10 @@ __global__ void bcg_check_s(double *__restrict__ sc, int *__restrict__ flags, in
 
 // step t: omega = t.s / t.t; t.t = 0, t.s = 0 or anything not finite breaks down (step t not taken)
 __global__ void bcg_set_omega(double *__restrict__ sc, int *__restrict__ flags, int t) {
-    if (flags[kBcgState] != kBcgRun) return;
+    if (flags[kSolverState] != kSolverRun) return;
     const double ts = sc[kBcgTs], tt = sc[kBcgTt], omega = ts / tt;
     if (tt == 0.0 || ts == 0.0 || !isfinite(ts) || !isfinite(tt) || !isfinite(omega)) {
-        bcg_stop(flags, SPMV_BICG_BREAKDOWN_OMEGA, t - 1);
+        solver_stop(flags, SPMV_BICG_BREAKDOWN_OMEGA, t - 1, kBcgStop);
         return;
     }
     sc[kBcgOmega] = omega;
@@ -333,9 +330,9 @@ __global__ void bcg_set_omega(double *__restrict__ sc, int *__restrict__ flags, 
 // the iterate of step t); else beta = (rho' / rho) (alpha / omega), rho = rho'
 __global__ void bcg_set_beta(double *__restrict__ sc, int *__restrict__ flags, double *__restrict__ hist, int t,
                              double tol2) {
-    const int state = flags[kBcgState];
-    if (state != kBcgRun) {
-        if (state == kBcgHalfStep) flags[kBcgState] = kBcgStop;
+    const int state = flags[kSolverState];
+    if (state != kSolverRun) {
+        if (state == kBcgHalfStep) flags[kSolverState] = kBcgStop;
         hist[t] = sc[kBcgLast];
         return;
     }
@@ -343,11 +340,11 @@ __global__ void bcg_set_beta(double *__restrict__ sc, int *__restrict__ flags, d
     sc[kBcgLast] = rr;
     hist[t] = rr;
     if (rr <= tol2 * sc[kBcgRr0]) {
-        bcg_stop(flags, SPMV_BICG_CONVERGED, t);
+        solver_stop(flags, SPMV_BICG_CONVERGED, t, kBcgStop);
         return;
     }
     if (rho_new == 0.0 || !isfinite(rho_new)) {
-        bcg_stop(flags, SPMV_BICG_BREAKDOWN_RHO, t);
+        solver_stop(flags, SPMV_BICG_BREAKDOWN_RHO, t, kBcgStop);
         return;
     }
     sc[kBcgBeta] = (rho_new / sc[kBcgRho]) * (sc[kBcgAlpha] / sc[kBcgOmega]);

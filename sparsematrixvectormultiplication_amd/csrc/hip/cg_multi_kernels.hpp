@@ -35,6 +35,13 @@ constexpr int kMcgRs = 0, kMcgPq = 1, kMcgRsNew = 2, kMcgAlpha = 3, kMcgBeta = 4
 // the int words: act[kMcgMaxK] (1 = still iterating), done[kMcgMaxK] (steps taken), then the count of active columns
 constexpr int kMcgAct = 0, kMcgDone = kMcgMaxK, kMcgActive = 2 * kMcgMaxK, kMcgFlagWords = 2 * kMcgMaxK + 1;
 
+// host: cl with 2^cl column lanes, the next power of two >= k / V
+inline int mcg_column_lanes(int k, int V) {
+    int cl = 0;
+    while ((1 << cl) * V < k) ++cl;
+    return cl;
+}
+
 // the value of lane ^ STEP (a true xor: the column lanes below STEP must not be mixed)
 template <int STEP>
 __device__ __forceinline__ double mcg_xor_partner(double v) {

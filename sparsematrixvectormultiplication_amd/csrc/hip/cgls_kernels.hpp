@@ -26,15 +26,13 @@ constexpr int kCglsBlocks = 2048;  // grid cap of the vector kernels
 // the scalar slots (doubles)
 constexpr int kCglsGamma = 0, kCglsGamma0 = 1, kCglsQq = 2, kCglsPp = 3, kCglsAlpha = 4, kCglsRr = 5, kCglsSs = 6,
               kCglsBeta = 7, kCglsLastSs = 8, kCglsLastRr = 9, kCglsSlots = 16;
-// the int words
-constexpr int kCglsState = 0, kCglsSteps = 1, kCglsStatus = 2, kCglsFlagWords = 4;
-constexpr int kCglsRun = 0, kCglsStop = 1;
+// the int words: the stop flags of solver_ops.hpp
 
 // partials of a.a on [0, n)
 template <typename T, int V>
 __global__ __launch_bounds__(kBlock) void cgls_norm2(long long n, const int *__restrict__ flags,
                                                      const T *__restrict__ a, double *__restrict__ part) {
-    if (flags[kCglsState] != kCglsRun) return;
+    if (flags[kSolverState] != kSolverRun) return;
     double acc[1] = {0.0};
     for (PieceLane l(0, n, V); l.q < l.end; l.q += l.stride) {
         T av[V];
@@ -51,7 +49,7 @@ __global__ __launch_bounds__(kBlock) void cgls_update_x_r(long long N, long long
                                                           const double *__restrict__ sc, const T *__restrict__ p,
                                                           const T *__restrict__ q, T *__restrict__ x,
                                                           T *__restrict__ r, double *__restrict__ part) {
-    if (flags[kCglsState] != kCglsRun) return;
+    if (flags[kSolverState] != kSolverRun) return;
     const double alpha = sc[kCglsAlpha];
     double acc[1] = {0.0};
     for (PieceLane l(0, M > N ? M : N, V); l.q < l.end; l.q += l.stride) {
@@ -84,7 +82,7 @@ template <typename T, int V>
 __global__ __launch_bounds__(kBlock) void cgls_update_s(long long N, const int *__restrict__ flags, double damp2,
                                                         const T *__restrict__ x, T *__restrict__ s,
                                                         double *__restrict__ part) {
-    if (flags[kCglsState] != kCglsRun) return;
+    if (flags[kSolverState] != kSolverRun) return;
     double acc[1] = {0.0};
     for (PieceLane l(0, N, V); l.q < l.end; l.q += l.stride) {
         const long long i0 = l.q * V;
@@ -106,7 +104,7 @@ template <typename T, int V>
 __global__ __launch_bounds__(kBlock) void cgls_update_p(long long N, const int *__restrict__ flags,
                                                         const double *__restrict__ sc, const T *__restrict__ s,
                                                         T *__restrict__ p, double *__restrict__ part) {
-    if (flags[kCglsState] != kCglsRun) return;
+    if (flags[kSolverState] != kSolverRun) return;
     const double beta = sc[kCglsBeta];
     double acc[1] = {0.0};
     for (PieceLane l(0, N, V); l.q < l.end; l.q += l.stride) {
@@ -124,12 +122,8 @@ __global__ __launch_bounds__(kBlock) void cgls_update_p(long long N, const int *
     if (part) block_partials<1>(acc, part);
 }
 
-// ---- the scalar kernels: one thread each.  A stop writes the status and the steps taken and never touches x.
-__device__ __forceinline__ void cgls_stop(int *__restrict__ flags, int status, int steps) {
-    flags[kCglsState] = kCglsStop;
-    flags[kCglsStatus] = status;
-    flags[kCglsSteps] = steps;
-}
+// ---- the scalar kernels: one thread each.  A stop (solver_stop) writes the status and the steps taken and never
+// touches x.
 
 // gamma0 = s.s, rr0 = r.r (slots kCglsSs, kCglsRr) with s = A^T b, r = b; history row 0; p = s, so p.p = gamma0.
 // A non-finite gamma0 or rr0 breaks down at step 0; gamma0 = 0 (A^T b = 0) has converged at step 0.
@@ -143,21 +137,21 @@ __global__ void cgls_start(double *__restrict__ sc, int *__restrict__ flags, dou
     sc[kCglsLastRr] = rr0;
     ss_hist[0] = gamma0;
     rr_hist[0] = rr0;
-    flags[kCglsState] = kCglsRun;
-    flags[kCglsSteps] = iters;
-    flags[kCglsStatus] = SPMV_CGLS_RAN_ALL;
-    if (!isfinite(gamma0) || !isfinite(rr0)) cgls_stop(flags, SPMV_CGLS_BREAKDOWN, 0);
-    else if (gamma0 == 0.0) cgls_stop(flags, SPMV_CGLS_CONVERGED, 0);
+    flags[kSolverState] = kSolverRun;
+    flags[kSolverSteps] = iters;
+    flags[kSolverStatus] = SPMV_CGLS_RAN_ALL;
+    if (!isfinite(gamma0) || !isfinite(rr0)) solver_stop(flags, SPMV_CGLS_BREAKDOWN, 0);
+    else if (gamma0 == 0.0) solver_stop(flags, SPMV_CGLS_CONVERGED, 0);
 }
 
 // step t: delta = q.q + damp^2 p.p, alpha = gamma / delta; delta = 0 or anything not finite breaks down (step t not
 // taken: x and r stay the iterate of step t - 1)
 __global__ void cgls_set_alpha(double *__restrict__ sc, int *__restrict__ flags, int t, double damp2) {
-    if (flags[kCglsState] != kCglsRun) return;
+    if (flags[kSolverState] != kSolverRun) return;
     const double delta = sc[kCglsQq] + damp2 * sc[kCglsPp];
     const double alpha = sc[kCglsGamma] / delta;
     if (delta == 0.0 || !isfinite(delta) || !isfinite(alpha)) {
-        cgls_stop(flags, SPMV_CGLS_BREAKDOWN, t - 1);
+        solver_stop(flags, SPMV_CGLS_BREAKDOWN, t - 1);
         return;
     }
     sc[kCglsAlpha] = alpha;
@@ -167,7 +161,7 @@ __global__ void cgls_set_alpha(double *__restrict__ sc, int *__restrict__ flags,
 // converges; else beta = gamma' / gamma, gamma = gamma'
 __global__ void cgls_set_beta(double *__restrict__ sc, int *__restrict__ flags, double *__restrict__ ss_hist,
                               double *__restrict__ rr_hist, int t, double tol2) {
-    if (flags[kCglsState] != kCglsRun) {
+    if (flags[kSolverState] != kSolverRun) {
         ss_hist[t] = sc[kCglsLastSs];
         rr_hist[t] = sc[kCglsLastRr];
         return;
@@ -178,11 +172,11 @@ __global__ void cgls_set_beta(double *__restrict__ sc, int *__restrict__ flags, 
     ss_hist[t] = ss;
     rr_hist[t] = rr;
     if (!isfinite(ss) || !isfinite(rr)) {
-        cgls_stop(flags, SPMV_CGLS_BREAKDOWN, t);
+        solver_stop(flags, SPMV_CGLS_BREAKDOWN, t);
         return;
     }
     if (ss <= tol2 * sc[kCglsGamma0]) {
-        cgls_stop(flags, SPMV_CGLS_CONVERGED, t);
+        solver_stop(flags, SPMV_CGLS_CONVERGED, t);
         return;
     }
     sc[kCglsBeta] = ss / sc[kCglsGamma];

@@ -33,16 +33,15 @@ constexpr int kMrBlocks = 2048;  // grid cap of the vector kernels
 constexpr int kMrBb0 = 0, kMrBeta = 1, kMrOldb = 2, kMrAlfa = 3, kMrBb = 4, kMrDbar = 5, kMrEpsln = 6, kMrCs = 7,
               kMrSn = 8, kMrPhibar = 9, kMrC1 = 10, kMrC2 = 11, kMrOldeps = 12, kMrDelta = 13, kMrGamma = 14,
               kMrPhi = 15, kMrLast = 16, kMrLocal = 17, kMrSlots = 20;
-// the int words; the state comes first: the preconditioner applies look at word 0
-constexpr int kMrState = 0, kMrSteps = 1, kMrStatus = 2, kMrFinal = 3, kMrFlagWords = 4;
-constexpr int kMrRun = 0, kMrStop = 1;
+// the int words: the stop flags of solver_ops.hpp, word 3 = the step that converged (its mr_update still runs)
+constexpr int kMrFinal = 3;
 
 // partials of a.b on [lo, hi)
 template <typename T, int V>
 __global__ __launch_bounds__(kBlock) void mr_dot(long long lo, long long hi, const int *__restrict__ flags,
                                                  const T *__restrict__ a, const T *__restrict__ b,
                                                  double *__restrict__ part) {
-    if (flags[kMrState] != kMrRun) return;
+    if (flags[kSolverState] != kSolverRun) return;
     double acc[1] = {0.0};
     for (PieceLane l(lo, hi, V); l.q < l.end; l.q += l.stride) {
         const long long i0 = l.q * V;
@@ -61,7 +60,7 @@ __global__ __launch_bounds__(kBlock) void mr_lanczos_a(long long lo, long long h
                                                        const double *__restrict__ sc, int k, double shift,
                                                        const T *__restrict__ a, const T *__restrict__ v,
                                                        T *__restrict__ r1, double *__restrict__ part) {
-    if (flags[kMrState] != kMrRun) return;
+    if (flags[kSolverState] != kSolverRun) return;
     const bool three = k >= 2;
     const double c1 = three ? sc[kMrC1] : 0.0;
     double acc[1] = {0.0};
@@ -93,7 +92,7 @@ template <typename T, int V>
 __global__ __launch_bounds__(kBlock) void mr_lanczos_b(long long lo, long long hi, const int *__restrict__ flags,
                                                        const double *__restrict__ sc, const T *__restrict__ r2,
                                                        T *__restrict__ t, double *__restrict__ part) {
-    if (flags[kMrState] != kMrRun) return;
+    if (flags[kSolverState] != kSolverRun) return;
     const double c2 = sc[kMrC2];
     double acc[1] = {0.0};
     for (PieceLane l(lo, hi, V); l.q < l.end; l.q += l.stride) {
@@ -119,7 +118,7 @@ __global__ __launch_bounds__(kBlock) void mr_update(long long lo, long long hi, 
                                                     const double *__restrict__ sc, int k, const T *__restrict__ y,
                                                     const T *__restrict__ w2, T *__restrict__ w1, T *__restrict__ x,
                                                     T *__restrict__ v) {
-    const bool run = flags[kMrState] == kMrRun;
+    const bool run = flags[kSolverState] == kSolverRun;
     if (!run && !(k > 0 && flags[kMrFinal] == k)) return;
     const double beta = sc[kMrBeta];
     if (k == 0) {
@@ -159,11 +158,6 @@ __global__ __launch_bounds__(kBlock) void mr_update(long long lo, long long hi, 
 
 // ---- the scalar kernels: one thread each.  A stop writes the status and the steps taken; only a converged step's
 // mr_update still touches x.
-__device__ __forceinline__ void mr_stop(int *__restrict__ flags, int status, int steps) {
-    flags[kMrState] = kMrStop;
-    flags[kMrStatus] = status;
-    flags[kMrSteps] = steps;
-}
 
 // bb0 = r2.y (slot kMrBb) with r2 = b, y = M^-1 b or b: history row 0, beta = phibar = sqrt(bb0), cs = -1, the rest 0.
 // bb0 not finite or < 0 (M not positive definite) breaks down at step 0; bb0 = 0 (b = 0) has converged at step 0.
@@ -172,16 +166,16 @@ __global__ void mr_start(double *__restrict__ sc, int *__restrict__ flags, doubl
     sc[kMrBb0] = bb0;
     sc[kMrLast] = bb0;
     hist[0] = bb0;
-    flags[kMrState] = kMrRun;
-    flags[kMrSteps] = iters;
-    flags[kMrStatus] = SPMV_MINRES_RAN_ALL;
+    flags[kSolverState] = kSolverRun;
+    flags[kSolverSteps] = iters;
+    flags[kSolverStatus] = SPMV_MINRES_RAN_ALL;
     flags[kMrFinal] = -1;
     if (!isfinite(bb0) || bb0 < 0.0) {
-        mr_stop(flags, SPMV_MINRES_BREAKDOWN, 0);
+        solver_stop(flags, SPMV_MINRES_BREAKDOWN, 0);
         return;
     }
     if (bb0 == 0.0) {
-        mr_stop(flags, SPMV_MINRES_CONVERGED, 0);
+        solver_stop(flags, SPMV_MINRES_CONVERGED, 0);
         return;
     }
     const double beta = sqrt(bb0);
@@ -197,10 +191,10 @@ __global__ void mr_start(double *__restrict__ sc, int *__restrict__ flags, doubl
 
 // step k: alfa = v.t (slot kMrAlfa), c2 = alfa / beta; alfa not finite breaks down (step k not taken)
 __global__ void mr_set_alfa(double *__restrict__ sc, int *__restrict__ flags, int k) {
-    if (flags[kMrState] != kMrRun) return;
+    if (flags[kSolverState] != kSolverRun) return;
     const double alfa = sc[kMrAlfa], c2 = alfa / sc[kMrBeta];
     if (!isfinite(alfa) || !isfinite(c2)) {
-        mr_stop(flags, SPMV_MINRES_BREAKDOWN, k - 1);
+        solver_stop(flags, SPMV_MINRES_BREAKDOWN, k - 1);
         return;
     }
     sc[kMrC2] = c2;
@@ -212,7 +206,7 @@ __global__ void mr_set_alfa(double *__restrict__ sc, int *__restrict__ flags, in
 __global__ void mr_rotate(double *__restrict__ sc, int *__restrict__ flags, double *__restrict__ hist, int k,
                           double tol2) {
 #pragma clang fp contract(off)
-    if (flags[kMrState] != kMrRun) {
+    if (flags[kSolverState] != kSolverRun) {
         hist[k] = sc[kMrLast];
         return;
     }
@@ -232,7 +226,7 @@ __global__ void mr_rotate(double *__restrict__ sc, int *__restrict__ flags, doub
                         isfinite(phi) && isfinite(phibar) && isfinite(c1) && isfinite(rr);
     if (!(bb >= 0.0) || gamma == 0.0 || !finite) {
         hist[k] = sc[kMrLast];
-        mr_stop(flags, SPMV_MINRES_BREAKDOWN, k - 1);
+        solver_stop(flags, SPMV_MINRES_BREAKDOWN, k - 1);
         return;
     }
     sc[kMrOldb] = oldb;
@@ -250,7 +244,7 @@ __global__ void mr_rotate(double *__restrict__ sc, int *__restrict__ flags, doub
     sc[kMrLast] = rr;
     hist[k] = rr;
     if (rr <= tol2 * sc[kMrBb0]) {
-        mr_stop(flags, SPMV_MINRES_CONVERGED, k);
+        solver_stop(flags, SPMV_MINRES_CONVERGED, k);
         flags[kMrFinal] = k;
     }
 }

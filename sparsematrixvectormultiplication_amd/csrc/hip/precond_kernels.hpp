@@ -146,14 +146,14 @@ __global__ __launch_bounds__(64) void pc_invert_block(int n, int b, const double
     }
 }
 
-// z = M^-1 r on local rows [0, n) (r, z: element i = global row row0 + i).  flags (NULL: none): a solver's state word,
-// anything but 0 (RUN) returns before writing.  DOTS: the workgroup's partials of r.r and r.z in part[2 g],
-// part[2 g + 1].  Lanes walk single rows (PieceLane with V = 1).
+// z = M^-1 r on local rows [0, n) (r, z: element i = global row row0 + i).  flags (NULL: none): a solver's stop flags
+// (solver_ops.hpp), any state but kSolverRun returns before writing.  DOTS: the workgroup's partials of r.r and r.z in
+// part[2 g], part[2 g + 1].  Lanes walk single rows (PieceLane with V = 1).
 template <typename T, bool DOTS>
 __global__ __launch_bounds__(kBlock) void pc_apply(long long n, int b, const T *__restrict__ inv,
                                                    const T *__restrict__ r, T *__restrict__ z,
                                                    const int *__restrict__ flags, double *__restrict__ part) {
-    if (flags && flags[0] != 0) return;
+    if (flags && flags[kSolverState] != kSolverRun) return;
     double acc[2] = {0.0, 0.0};
     for (PieceLane l(0, n, 1); l.q < l.end; l.q += l.stride) {
         const long long i = l.q, k = i / b;
@@ -209,7 +209,7 @@ template <typename T, bool DOTS>
 void precond_launch(const spmv_precond *P, const void *r, void *z, const int *flags, double *part, int grid,
                     hipStream_t s) {
     const long long n = P->rows;
-    if (!grid) grid = (int)std::max<long long>(1, std::min<long long>(kPcBlocks, (n + kBlock - 1) / kBlock));
+    if (!grid) grid = solver_grid(kPcBlocks, n, kBlock);
     hipLaunchKernelGGL((pc_apply<T, DOTS>), dim3(grid), dim3(kBlock), 0, s, n, P->block, (const T *)P->inv,
                        (const T *)r, (T *)z, flags, part);
 }

@@ -1,6 +1,10 @@
-// solver_ops.hpp -- what the iterated methods on CSR handles share (csr_cg and csr_cg_multi in spmv_cg.hip,
-// csr_bicgstab in spmv_bicgstab.hip, csr_cgls in spmv_cgls.hip, the power iterations in spmv_comm.hip): the pieces a
-// vector kernel loads and stores, the lanes' walk over them, the fixed-order reductions, and the host side of a solve.
+// solver_ops.hpp -- what the iterated methods on CSR handles share: csr_cg and csr_cg_multi (spmv_cg.hip), csr_pcg
+// (spmv_pcg.hip), csr_pcg_multi (spmv_pcg_multi.hip), csr_bicgstab and csr_pbicgstab (spmv_bicgstab.hip), csr_minres
+// (spmv_minres.hip), csr_cgls (spmv_cgls.hip), csr_lobpcg (spmv_lobpcg.hip) and the power iterations (spmv_comm.hip).
+// For the device: the pieces a vector kernel loads and stores, the lanes' walk over them, the fixed-order reductions
+// and the stop flags.  For the host: the frame of a solve -- the refusals the entries share (solver_check_*), the
+// buffers and events (SolverScope), the start and the end of the timed part (solver_begin, solver_finish), the grid
+// clamp (solver_grid), the poll of the stop word (solver_poll) and the dtype dispatch (solver_dispatch).
 //
 // Reduction order.  Products are accumulated in double for fp32 and fp64 data alike.  A lane adds its pieces in stride
 // order (and a piece's rows in row order), group_sum<64> adds the lanes of a wave, the waves of a workgroup are added in
@@ -114,6 +118,21 @@ __device__ __forceinline__ double fold_partials(const double *__restrict__ part,
     return workgroup_sum<1>(acc);
 }
 
+// The stop flags of the solvers with one right-hand side: kSolverFlagWords ints, zeroed with the solve's buffers.  Word
+// kSolverState is kSolverRun (0) while the solve iterates; a vector kernel that finds anything else there returns
+// before it writes, and so do pc_apply and the triangular solves' kernels, which are handed the same words.  A stop
+// leaves the steps taken and the solver's status in words kSolverSteps and kSolverStatus; word 3 is the solver's own
+// (BiCGSTAB's half step, MINRES's final step), and so are state values past kSolverStop.
+constexpr int kSolverState = 0, kSolverSteps = 1, kSolverStatus = 2, kSolverFlagWords = 4;
+constexpr int kSolverRun = 0, kSolverStop = 1;
+
+// one thread: stop with `status` after `steps` steps
+__device__ __forceinline__ void solver_stop(int *__restrict__ flags, int status, int steps, int state = kSolverStop) {
+    flags[kSolverState] = state;
+    flags[kSolverStatus] = status;
+    flags[kSolverSteps] = steps;
+}
+
 // Kernels of more than one translation unit: internal linkage, one copy in each
 namespace {
 
@@ -138,6 +157,54 @@ __global__ __launch_bounds__(64) void solver_rank_sum(const double *__restrict__
 }  // namespace spmv
 
 // ---------------------------------------------------------------- the host side of a solve
+// workgroups for `items` items at `per_block` each: at least 1, at most cap
+inline int solver_grid(long long cap, long long items, long long per_block) {
+    return (int)std::max<long long>(1, std::min<long long>(cap, (items + per_block - 1) / per_block));
+}
+
+// The refusals the entries share, each -1 with a message naming `what`; an entry calls them in its own order, with its
+// own refusals in between.
+inline int solver_check_steps(const char *what, int iters, double tol) {
+    if (iters < 0) return fail("%s: iters = %d, must be >= 0", what, iters);
+    if (!(tol >= 0) || !std::isfinite(tol)) return fail("%s: tol = %g, must be finite and >= 0", what, tol);
+    return 0;
+}
+inline int solver_check_square(const char *what, const spmv_csr_dev *m) {
+    if (m->M_total != m->N) return fail("%s: needs a square matrix (%d x %d)", what, m->M_total, m->N);
+    return 0;
+}
+// the rows of a handle and the communicator fit together
+inline int solver_check_rows(const char *what, const spmv_csr_dev *m, const int *bounds) {
+    if (g_comm && !bounds) return fail("%s: a communicator exists, the row bounds are required", what);
+    if (!g_comm && (m->row0 != 0 || m->M_local != m->M_total))
+        return fail("%s: a handle of rows [%d, %d) needs a communicator", what, m->row0, m->row0 + m->M_local);
+    if (g_comm_size > kMaxRanks) return fail("%s: more than %d ranks", what, kMaxRanks);
+    return 0;
+}
+
+inline int solver_setup_failed(const char *what, hipError_t e) {
+    return fail("%s: setup failed: %s", what, hipGetErrorString(e));
+}
+inline int solver_run_failed(const char *what, hipError_t e) {
+    return fail("%s: run failed: %s", what, hipGetErrorString(e));
+}
+
+// the all-gatherv's row bounds for rows of k values (empty without a communicator)
+inline std::vector<int> solver_scaled_bounds(const int *bounds, int k) {
+    std::vector<int> kbounds;
+    if (g_comm) {
+        kbounds.resize((size_t)g_comm_size + 1);
+        for (int r = 0; r <= g_comm_size; ++r) kbounds[r] = bounds[r] * k;
+    }
+    return kbounds;
+}
+
+// body(T()) with T the handle's dtype, under guarded()
+template <typename F>
+int solver_dispatch(const char *what, int value_bytes, F body) {
+    return guarded(what, [&] { return value_bytes == 8 ? body(double()) : body(float()); });
+}
+
 namespace {
 
 // part[g * nv + j] of this rank's `grid` workgroups -> out[j], the sums over all ranks, on every rank.  Without a
@@ -197,6 +264,43 @@ inline hipError_t copy_history(double *host, const double *dev, int steps_run, i
     if (e == hipSuccess)
         for (size_t i = run; i < all; ++i) host[i] = host[i - row];
     return e;
+}
+
+// The start of a solve's timed part, after the allocations and the body's own copies of its input (e: their first
+// error, beginning with scope.err): records e0.
+inline int solver_begin(SolverScope &scope, hipError_t e, const char *what) {
+    if (e == hipSuccess) e = hipEventRecord(scope.e0, g_stream);
+    return e == hipSuccess ? 0 : solver_setup_failed(what, e);
+}
+
+struct SolverHistory {
+    double *host;  // iters + 1 rows (NULL: not wanted)
+    const double *dev;
+};
+
+// The end of a solve: records e1, all-gathers x_dev with `bounds` when a communicator exists and x is wanted (bounds
+// NULL: every rank holds all of x), waits, takes the time, and copies to the host x (x_bytes; nothing for 0 bytes or
+// a NULL x_host), the histories (rows of `row` doubles: 0 .. steps_run copied, the last one repeated up to iters) and
+// flag_words ints of flags_dev (flags_host NULL: not read).  *ms_total (NULL: not wanted) is set on success only.
+inline int solver_finish(SolverScope &scope, const char *what, int value_bytes, const int *bounds, void *x_dev,
+                         void *x_host, size_t x_bytes, std::initializer_list<SolverHistory> hists, int steps_run,
+                         int iters, size_t row, const int *flags_dev, int *flags_host, size_t flag_words,
+                         float *ms_total) {
+    hipError_t e = hipEventRecord(scope.e1, g_stream);
+    // the solution: every rank holds its rows; with a communicator all rows everywhere
+    if (e == hipSuccess && g_comm && x_host && bounds && spmv_hip_comm_allgatherv(x_dev, bounds, value_bytes, g_stream))
+        return -1;
+    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
+    float ms = 0;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, scope.e0, scope.e1);
+    if (e == hipSuccess && x_host && x_bytes) e = hipMemcpy(x_host, x_dev, x_bytes, hipMemcpyDeviceToHost);
+    for (const SolverHistory &h : hists)
+        if (e == hipSuccess) e = copy_history(h.host, h.dev, steps_run, iters, row);
+    if (e == hipSuccess && flags_host)
+        e = hipMemcpy(flags_host, flags_dev, flag_words * sizeof(int), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return solver_run_failed(what, e);
+    if (ms_total) *ms_total = ms;
+    return 0;
 }
 
 constexpr int kSolverPoll = 16;  // tol > 0: steps between reads of the device's stop word

@@ -38,8 +38,7 @@ int bcg_run(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, doub
             const BcgBuffers &b, int *steps_run) {
     constexpr int V = 16 / sizeof(T);
     const long long lo = m->row0, hi = (long long)m->row0 + m->M_local;
-    const long long pieces = (hi + V - 1) / V - lo / V;
-    const int grid = (int)std::max<long long>(1, std::min<long long>(kBcgBlocks, (pieces + kBlock - 1) / kBlock));
+    const int grid = solver_grid(kBcgBlocks, (hi + V - 1) / V - lo / V, kBlock);  // over the 16-byte pieces
     const double tol2 = tol * tol;
     T *p = (T *)b.p, *s = (T *)b.s, *v = (T *)b.v, *t = (T *)b.t, *x = (T *)b.x, *r = (T *)b.r, *rhat = (T *)b.rhat;
     const int *fl = b.flags;
@@ -107,7 +106,7 @@ int bcg_run(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, doub
         }
         if (g_comm && spmv_hip_comm_allgatherv(ph, bounds, m->value_bytes, g_stream)) return -1;
         bool stop = false;
-        if (solver_poll(k, iters, tol, b.flags + kBcgState, kBcgStop, &stop)) return -1;
+        if (solver_poll(k, iters, tol, b.flags + kSolverState, kBcgStop, &stop)) return -1;
         if (stop) {
             *steps_run = k;
             break;
@@ -137,7 +136,7 @@ int bcg_body(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, dou
     b.part = scope.alloc<double>((size_t)kBcgBlocks * 2 * sizeof(double));
     b.gath = scope.alloc<double>((size_t)kMaxRanks * 2 * sizeof(double));
     b.hist = scope.alloc<double>(((size_t)iters + 1) * sizeof(double));
-    b.flags = scope.alloc<int>(kBcgFlagWords * sizeof(int));
+    b.flags = scope.alloc<int>(kSolverFlagWords * sizeof(int));
     b.ph = b.sh = b.dinv = nullptr;
     if (P) {
         b.ph = scope.alloc(in_bytes);
@@ -156,48 +155,30 @@ int bcg_body(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, dou
         e = hipMemcpyAsync((char *)b.rhat + own_off, (char *)b.r + own_off, own_bytes, hipMemcpyDeviceToDevice, g_stream);
     if (e == hipSuccess && n_own)
         e = hipMemcpyAsync((char *)b.p + own_off, (char *)b.r + own_off, own_bytes, hipMemcpyDeviceToDevice, g_stream);
-    if (e == hipSuccess) e = hipEventRecord(scope.e0, g_stream);
-    if (e != hipSuccess) return fail("csr_bicgstab: setup failed: %s", hipGetErrorString(e));
+    if (solver_begin(scope, e, "csr_bicgstab")) return -1;
     int steps_run = 0;
     if (bcg_run<T>(m, P, variant, iters, tol, bounds, b, &steps_run)) return -1;
-    e = hipEventRecord(scope.e1, g_stream);
-    // the solution: every rank holds its rows; with a communicator all rows everywhere
-    if (e == hipSuccess && g_comm && x_host && spmv_hip_comm_allgatherv(b.x, bounds, m->value_bytes, g_stream)) return -1;
-    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-    float ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, scope.e0, scope.e1);
-    if (e == hipSuccess && x_host) e = hipMemcpy(x_host, b.x, n_all * vb, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = copy_history(rr_hist, b.hist, steps_run, iters, 1);
-    int flags[kBcgFlagWords] = {0, 0, 0, 0};
-    if (e == hipSuccess) e = hipMemcpy(flags, b.flags, sizeof flags, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail("csr_bicgstab: run failed: %s", hipGetErrorString(e));
+    int flags[kSolverFlagWords] = {0, 0, 0, 0};
+    if (solver_finish(scope, "csr_bicgstab", m->value_bytes, bounds, b.x, x_host, n_all * vb, {{rr_hist, b.hist}},
+                      steps_run, iters, 1, b.flags, flags, kSolverFlagWords, ms_total))
+        return -1;
     if (info) {
-        info[0] = flags[kBcgSteps];
-        info[1] = flags[kBcgStatus];
+        info[0] = flags[kSolverSteps];
+        info[1] = flags[kSolverStatus];
         info[2] = flags[kBcgHalf];
     }
-    if (ms_total) *ms_total = ms;
     return 0;
 }
 
 int bcg_entry(const char *what, spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, double tol,
               const int *bounds, const void *b_host, void *x_host, double *rr_hist, int *info, float *ms_total) {
     if (need_device()) return -1;
-    int rc = 0;
-    if (!m || !b_host) rc = fail("%s: bad arguments", what);
-    else if (iters < 0) rc = fail("%s: iters = %d, must be >= 0", what, iters);
-    else if (!(tol >= 0) || !std::isfinite(tol)) rc = fail("%s: tol = %g, must be finite and >= 0", what, tol);
-    else if (m->M_total != m->N) rc = fail("%s: needs a square matrix (%d x %d)", what, m->M_total, m->N);
-    else if (g_comm && !bounds) rc = fail("%s: a communicator exists, the row bounds are required", what);
-    else if (!g_comm && (m->row0 != 0 || m->M_local != m->M_total))
-        rc = fail("%s: a handle of rows [%d, %d) needs a communicator", what, m->row0, m->row0 + m->M_local);
-    else if (g_comm_size > kMaxRanks) rc = fail("%s: more than %d ranks", what, kMaxRanks);
-    else if (P) rc = precond_matches(m, P, what);
-    if (rc) return rc;
-    return guarded(what, [&] {
-        return m->value_bytes == 8
-                   ? bcg_body<double>(m, P, variant, iters, tol, bounds, b_host, x_host, rr_hist, info, ms_total)
-                   : bcg_body<float>(m, P, variant, iters, tol, bounds, b_host, x_host, rr_hist, info, ms_total);
+    if (!m || !b_host) return fail("%s: bad arguments", what);
+    if (solver_check_steps(what, iters, tol) || solver_check_square(what, m) || solver_check_rows(what, m, bounds))
+        return -1;
+    if (P && precond_matches(m, P, what)) return -1;
+    return solver_dispatch(what, m->value_bytes, [&](auto t) {
+        return bcg_body<decltype(t)>(m, P, variant, iters, tol, bounds, b_host, x_host, rr_hist, info, ms_total);
     });
 }
 

@@ -71,7 +71,7 @@ template <typename T>
 int cg_run(spmv_csr_dev *m, int variant, int iters, const int *bounds, int use_halo, T *d_xs, T *d_r, double *d_s,
            double *d_part, double *d_gath, double *d_hist) {
     const long long n = m->M_local;
-    const int grid = (int)std::max<long long>(1, std::min<long long>(kNormBlocks, (n + kBlock - 1) / kBlock));
+    const int grid = solver_grid(kNormBlocks, n, kBlock);
     T *p_own = (T *)m->x + m->row0, *q_own = (T *)m->y + m->row0, *x_own = d_xs + m->row0;
     // part[0 .. grid) of this rank -> the global sum in d_s[slot] on every rank
     auto reduce = [&](int slot) { return solver_reduce(d_part, grid, 1, d_s + slot, d_s + kCgLocal, d_gath, "csr_cg"); };
@@ -114,20 +114,10 @@ int cg_body(spmv_csr_dev *m, int variant, int iters, const int *bounds, int use_
     if (e == hipSuccess) e = hipMemsetAsync(m->x, 0, (size_t)m->N * sizeof(T), g_stream);
     if (e == hipSuccess && n_own)
         e = hipMemcpyAsync((T *)m->x + m->row0, d_r, n_own * sizeof(T), hipMemcpyDeviceToDevice, g_stream);
-    if (e == hipSuccess) e = hipEventRecord(scope.e0, g_stream);
-    if (e != hipSuccess) return fail("csr_cg: setup failed: %s", hipGetErrorString(e));
+    if (solver_begin(scope, e, "csr_cg")) return -1;
     if (cg_run<T>(m, variant, iters, bounds, use_halo, d_xs, d_r, d_s, d_part, d_gath, d_hist)) return -1;
-    e = hipEventRecord(scope.e1, g_stream);
-    // the solution: every rank holds its rows; with a communicator all rows everywhere
-    if (e == hipSuccess && g_comm && x_host && spmv_hip_comm_allgatherv(d_xs, bounds, m->value_bytes, g_stream)) return -1;
-    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-    float ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, scope.e0, scope.e1);
-    if (e == hipSuccess && x_host) e = hipMemcpy(x_host, d_xs, n_all * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = copy_history(rr_hist, d_hist, iters, iters, 1);
-    if (e != hipSuccess) return fail("csr_cg: run failed: %s", hipGetErrorString(e));
-    if (ms_total) *ms_total = ms;
-    return 0;
+    return solver_finish(scope, "csr_cg", m->value_bytes, bounds, d_xs, x_host, n_all * sizeof(T), {{rr_hist, d_hist}},
+                         iters, iters, 1, nullptr, nullptr, 0, ms_total);
 }
 
 }  // namespace
@@ -136,13 +126,13 @@ extern "C" int spmv_hip_csr_cg(spmv_csr_dev *m, int variant, int iters, const in
                                const void *b_host, void *x_host, double *rr_hist, float *ms_total) {
     if (need_device()) return -1;
     if (!m || iters < 0 || !b_host) return fail("csr_cg: bad arguments");
-    if (m->M_total != m->N) return fail("csr_cg: needs a square matrix (%d x %d)", m->M_total, m->N);
+    if (solver_check_square("csr_cg", m)) return -1;
+    // (its own lines from here: a partial handle is not refused, and the halo check sits between the shared two)
     if (g_comm && !bounds) return fail("csr_cg: a communicator exists, the row bounds are required");
     if (g_comm && use_halo && !g_halo_ready) return fail("csr_cg: call spmv_hip_comm_halo_setup first");
     if (g_comm_size > kMaxRanks) return fail("csr_cg: more than %d ranks", kMaxRanks);
-    return guarded("csr_cg", [&] {
-        return m->value_bytes == 8 ? cg_body<double>(m, variant, iters, bounds, use_halo, b_host, x_host, rr_hist, ms_total)
-                                   : cg_body<float>(m, variant, iters, bounds, use_halo, b_host, x_host, rr_hist, ms_total);
+    return solver_dispatch("csr_cg", m->value_bytes, [&](auto t) {
+        return cg_body<decltype(t)>(m, variant, iters, bounds, use_halo, b_host, x_host, rr_hist, ms_total);
     });
 }
 
@@ -213,11 +203,9 @@ struct McgBuffers {
 template <typename T, int V>
 int mcg_run(spmv_csr_dev *m, int k, int iters, double tol, const int *kbounds, const McgBuffers &b, int *steps) {
     const long long n = m->M_local, kk = k;
-    int cl = 0;
-    while ((1 << cl) * V < k) ++cl;  // column lanes: the next power of two >= k / V
-    const long long rows_per_block = kBlock >> cl;
+    const int cl = mcg_column_lanes(k, V);
     const int cap = k == 1 ? kNormBlocks : kMcgBlocks;  // k = 1: csr_cg's workgroups, csr_cg's bits
-    const int grid = (int)std::max<long long>(1, std::min<long long>(cap, (n + rows_per_block - 1) / rows_per_block));
+    const int grid = solver_grid(cap, n, kBlock >> cl);
     const double tol2 = tol * tol;
     T *P = (T *)b.P, *p_own = P + m->row0 * kk, *q_own = (T *)b.Q + m->row0 * kk, *x_own = (T *)b.X + m->row0 * kk;
     T *R = (T *)b.R;
@@ -262,11 +250,7 @@ int mcg_body(spmv_csr_dev *m, int k, int iters, double tol, const int *bounds, c
              double *rr_hist, int *iters_done, float *ms_total) {
     const size_t kk = (size_t)k, vb = sizeof(T);
     const size_t n_all = (size_t)m->M_total, n_own = (size_t)m->M_local, ncols = (size_t)m->N;
-    std::vector<int> kbounds;
-    if (g_comm) {
-        kbounds.resize((size_t)g_comm_size + 1);
-        for (int r = 0; r <= g_comm_size; ++r) kbounds[r] = bounds[r] * k;
-    }
+    const std::vector<int> kbounds = solver_scaled_bounds(bounds, k);
     SolverScope scope;
     // P: read in whole 128-byte lines by the x-window SpMV kernels (k = 1), as the handle's x
     const size_t p_bytes = std::max<size_t>(ncols * kk * vb, 16) + kLineBytes;
@@ -288,28 +272,18 @@ int mcg_body(spmv_csr_dev *m, int k, int iters, double tol, const int *bounds, c
         e = hipMemcpyAsync(b.R, (const char *)B_host + own_off, own_bytes, hipMemcpyHostToDevice, g_stream);
     if (e == hipSuccess && n_own)
         e = hipMemcpyAsync((char *)b.P + own_off, b.R, own_bytes, hipMemcpyDeviceToDevice, g_stream);
-    if (e == hipSuccess) e = hipEventRecord(scope.e0, g_stream);
-    if (e != hipSuccess) return fail("csr_cg_multi: setup failed: %s", hipGetErrorString(e));
+    if (solver_begin(scope, e, "csr_cg_multi")) return -1;
     int steps = 0;
     const bool wide = kk * vb % 16 == 0;
     if (wide ? mcg_run<T, 16 / sizeof(T)>(m, k, iters, tol, kbounds.data(), b, &steps)
              : mcg_run<T, 1>(m, k, iters, tol, kbounds.data(), b, &steps))
         return -1;
-    e = hipEventRecord(scope.e1, g_stream);
-    // the solution: every rank holds its rows; with a communicator all rows everywhere
-    if (e == hipSuccess && g_comm && X_host && spmv_hip_comm_allgatherv(b.X, kbounds.data(), m->value_bytes, g_stream))
-        return -1;
-    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-    float ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, scope.e0, scope.e1);
-    if (e == hipSuccess && X_host) e = hipMemcpy(X_host, b.X, n_all * kk * vb, hipMemcpyDeviceToHost);
-    // stopped early: every column is frozen, its history repeats its last value
-    if (e == hipSuccess) e = copy_history(rr_hist, b.hist, steps, iters, kk);
+    // stopped early: every column is frozen, its history repeats its last value; the flags are read only when asked for
     int flags[kMcgFlagWords];
-    if (e == hipSuccess && iters_done) e = hipMemcpy(flags, b.flags, sizeof flags, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail("csr_cg_multi: run failed: %s", hipGetErrorString(e));
+    if (solver_finish(scope, "csr_cg_multi", m->value_bytes, kbounds.data(), b.X, X_host, n_all * kk * vb,
+                      {{rr_hist, b.hist}}, steps, iters, kk, b.flags, iters_done ? flags : nullptr, kMcgFlagWords, ms_total))
+        return -1;
     if (iters_done) std::memcpy(iters_done, flags + kMcgDone, kk * sizeof(int));
-    if (ms_total) *ms_total = ms;
     return 0;
 }
 
@@ -322,15 +296,14 @@ extern "C" int spmv_hip_csr_cg_multi(spmv_csr_dev *m, int k, int iters, double t
     int rc = 0;
     if (!m || iters < 0 || !B_host || !(tol >= 0)) rc = fail("csr_cg_multi: bad arguments");
     else if (k < 1 || k > kMcgMaxK) rc = fail("csr_cg_multi: k = %d, must be in [1, %d]", k, kMcgMaxK);
-    else if (m->M_total != m->N) rc = fail("csr_cg_multi: needs a square matrix (%d x %d)", m->M_total, m->N);
+    else if (solver_check_square("csr_cg_multi", m)) rc = -1;
     else if (m->tiles_only) rc = fail("csr_cg_multi: a tiles-only handle has no SpMM kernels");
     else if ((long long)m->M_total * k > 0x7fffffffLL)
         rc = fail("csr_cg_multi: n * k = %lld values is beyond int range", (long long)m->M_total * k);
     else if (g_comm && !bounds) rc = fail("csr_cg_multi: a communicator exists, the row bounds are required");
     else if (g_comm_size > kMaxRanks) rc = fail("csr_cg_multi: more than %d ranks", kMaxRanks);
     if (rc) return rc;
-    return guarded("csr_cg_multi", [&] {
-        return m->value_bytes == 8 ? mcg_body<double>(m, k, iters, tol, bounds, B_host, X_host, rr_hist, iters_done, ms_total)
-                                   : mcg_body<float>(m, k, iters, tol, bounds, B_host, X_host, rr_hist, iters_done, ms_total);
+    return solver_dispatch("csr_cg_multi", m->value_bytes, [&](auto t) {
+        return mcg_body<decltype(t)>(m, k, iters, tol, bounds, B_host, X_host, rr_hist, iters_done, ms_total);
     });
 }

@@ -22,10 +22,7 @@ struct CglsBuffers {
 };
 
 // the vector kernels' grid over n rows in pieces of V
-int cgls_grid(long long n, int V) {
-    const long long pieces = (n + V - 1) / V;
-    return (int)std::max<long long>(1, std::min<long long>(kCglsBlocks, (pieces + kBlock - 1) / kBlock));
-}
+int cgls_grid(long long n, int V) { return solver_grid(kCglsBlocks, (n + V - 1) / V, kBlock); }
 
 // the loop; *steps_run = the steps launched (< iters when tol > 0 and the solve stopped)
 template <typename T>
@@ -72,7 +69,7 @@ int cgls_run(spmv_csr_dev *m, spmv_csr_dev *mt, int iters, double tol, double da
                            (const T *)s, p, damp > 0 ? b.part : nullptr);
         if (damp > 0) fold(gN, kCglsPp);
         bool stop = false;
-        if (solver_poll(k, iters, tol, b.flags + kCglsState, kCglsStop, &stop)) return -1;
+        if (solver_poll(k, iters, tol, b.flags + kSolverState, kSolverStop, &stop)) return -1;
         if (stop) {
             *steps_run = k;
             break;
@@ -101,28 +98,22 @@ int cgls_body(spmv_csr_dev *m, spmv_csr_dev *mt, int iters, double tol, double d
     b.part = scope.alloc<double>((size_t)kCglsBlocks * sizeof(double));
     b.ss_hist = scope.alloc<double>(hist_bytes);
     b.rr_hist = scope.alloc<double>(hist_bytes);
-    b.flags = scope.alloc<int>(kCglsFlagWords * sizeof(int));
+    b.flags = scope.alloc<int>(kSolverFlagWords * sizeof(int));
     hipError_t e = scope.err;
     if (e == hipSuccess && M) e = hipMemcpyAsync(b.r, b_host, M * vb, hipMemcpyHostToDevice, g_stream);
-    if (e == hipSuccess) e = hipEventRecord(scope.e0, g_stream);
-    if (e != hipSuccess) return fail("csr_cgls: setup failed: %s", hipGetErrorString(e));
+    if (solver_begin(scope, e, "csr_cgls")) return -1;
     int steps_run = 0;
     if (cgls_run<T>(m, mt, iters, tol, damp, b, &steps_run)) return -1;
-    e = hipEventRecord(scope.e1, g_stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-    float ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, scope.e0, scope.e1);
-    if (e == hipSuccess && x_host && N) e = hipMemcpy(x_host, b.x, N * vb, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = copy_history(ss_hist, b.ss_hist, steps_run, iters, 1);
-    if (e == hipSuccess) e = copy_history(rr_hist, b.rr_hist, steps_run, iters, 1);
-    int flags[kCglsFlagWords] = {0, 0, 0, 0};
-    if (e == hipSuccess) e = hipMemcpy(flags, b.flags, sizeof flags, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail("csr_cgls: run failed: %s", hipGetErrorString(e));
+    // no bounds: the handles hold whole matrices, x is whole on every rank
+    int flags[kSolverFlagWords] = {0, 0, 0, 0};
+    if (solver_finish(scope, "csr_cgls", m->value_bytes, nullptr, b.x, x_host, N * vb,
+                      {{ss_hist, b.ss_hist}, {rr_hist, b.rr_hist}}, steps_run, iters, 1, b.flags, flags, kSolverFlagWords,
+                      ms_total))
+        return -1;
     if (info) {
-        info[0] = flags[kCglsSteps];
-        info[1] = flags[kCglsStatus];
+        info[0] = flags[kSolverSteps];
+        info[1] = flags[kSolverStatus];
     }
-    if (ms_total) *ms_total = ms;
     return 0;
 }
 
@@ -143,8 +134,7 @@ extern "C" int spmv_hip_csr_cgls(spmv_csr_dev *m, spmv_csr_dev *mt, int iters, d
     if (need_device()) return -1;
     int rc = 0;
     if (!m || !mt || !b_host) rc = fail("csr_cgls: bad arguments");
-    else if (iters < 0) rc = fail("csr_cgls: iters = %d, must be >= 0", iters);
-    else if (!(tol >= 0) || !std::isfinite(tol)) rc = fail("csr_cgls: tol = %g, must be finite and >= 0", tol);
+    else if (solver_check_steps("csr_cgls", iters, tol)) rc = -1;
     else if (!(damp >= 0) || !std::isfinite(damp)) rc = fail("csr_cgls: damp = %g, must be finite and >= 0", damp);
     else if (cgls_whole(m, "A") || cgls_whole(mt, "A^T")) rc = -1;
     else if (mt->M_total != m->N || mt->N != m->M_total)
@@ -153,8 +143,7 @@ extern "C" int spmv_hip_csr_cgls(spmv_csr_dev *m, spmv_csr_dev *mt, int iters, d
     else if (mt->value_bytes != m->value_bytes)
         rc = fail("csr_cgls: A^T holds %d-byte values, A %d-byte: not its transpose", mt->value_bytes, m->value_bytes);
     if (rc) return rc;
-    return guarded("csr_cgls", [&] {
-        return m->value_bytes == 8 ? cgls_body<double>(m, mt, iters, tol, damp, b_host, x_host, ss_hist, rr_hist, info, ms_total)
-                                   : cgls_body<float>(m, mt, iters, tol, damp, b_host, x_host, ss_hist, rr_hist, info, ms_total);
+    return solver_dispatch("csr_cgls", m->value_bytes, [&](auto t) {
+        return cgls_body<decltype(t)>(m, mt, iters, tol, damp, b_host, x_host, ss_hist, rr_hist, info, ms_total);
     });
 }

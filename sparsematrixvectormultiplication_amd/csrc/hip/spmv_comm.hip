@@ -420,7 +420,7 @@ __global__ __launch_bounds__(kBlock) void scale_into(const T *__restrict__ y, lo
 template <typename T>
 int power_iterations(spmv_csr_dev *m, int variant, int iters, const int *bounds, double *d_part, double *d_norm) {
     const long long n = m->M_total;
-    const int grid = (int)std::max<long long>(1, std::min<long long>(kNormBlocks, (n + kBlock - 1) / kBlock));
+    const int grid = solver_grid(kNormBlocks, n, kBlock);
     for (int i = 0; i < iters; ++i) {
         if (csr_launch_any(m, variant, m->x, m->y, g_stream)) return -1;
         if (g_comm && bounds && spmv_hip_comm_allgatherv(m->y, bounds, m->value_bytes, g_stream)) return -1;
@@ -728,7 +728,7 @@ template <typename T>
 int power_iterations_halo(spmv_csr_dev *m, int variant, int iters, double *d_part, double *d_sum, double *d_norm,
                           hipEvent_t scaled, hipEvent_t arrived) {
     const long long n = m->M_local;
-    const int grid = (int)std::max<long long>(1, std::min<long long>(kNormBlocks, (n + kBlock - 1) / kBlock));
+    const int grid = solver_grid(kNormBlocks, n, kBlock);
     T *y_own = (T *)m->y + m->row0, *x_own = (T *)m->x + m->row0;
     const bool fast_path = variant == SPMV_CSR_AUTO || variant == SPMV_CSR_STREAM;
     // the column split (own_part / halo_part) replaces the block split where halo setup made one: the product is then

@@ -22,19 +22,11 @@ namespace {
 
 constexpr double kLobDrop = 1e-10;  // basis directions below drop * the largest are dropped (spmv_lobpcg_rr)
 
-// column lanes of the residual pass: the next power of two >= k / V
-int lob_column_lanes(int k, int V) {
-    int cl = 0;
-    while ((1 << cl) * V < k) ++cl;
-    return cl;
-}
-
 int lob_gram_tiles(int m) { return (m + 15) / 16; }
 
 // workgroups of the Gram pass over n rows
 int lob_gram_grid(long long n) {
-    const long long groups = (n + 3) / 4, waves = kBlock / 64;
-    return (int)std::max<long long>(1, std::min<long long>(kLobGramBlocks, (groups + waves - 1) / waves));
+    return solver_grid(kLobGramBlocks, (n + 3) / 4, kBlock / 64);  // a wave takes a group of 4 rows
 }
 
 // G_B and G_A of the first nb blocks -> out[0 .. 2 MP^2) on the device (MP = 16 tiles(m); the lower tiles of G_B stay 0);
@@ -65,7 +57,7 @@ void lob_gram_unpack(const double *folded, int m, double *GB, double *GA) {
 template <int NB, bool VEC>
 void lob_update_vec(long long n, int k, const double *const *S, const double *const *AS, const double *coef, double *X,
                     double *P, double *AX, double *AP) {
-    const int grid = (int)std::max<long long>(1, std::min<long long>(kLobUpdateBlocks, (n + kBlock - 1) / kBlock));
+    const int grid = solver_grid(kLobUpdateBlocks, n, kBlock);
     const double *s1 = NB > 1 ? S[1] : nullptr, *s2 = NB > 2 ? S[2] : nullptr;
     const double *a1 = NB > 1 ? AS[1] : nullptr, *a2 = NB > 2 ? AS[2] : nullptr;
     const dim3 g(grid), blk(kBlock);
@@ -129,9 +121,8 @@ int lob_run(spmv_csr_dev *m, const spmv_precond *pc, int k, int iters, double to
     const long long n = m->M_total;
     const size_t kk = (size_t)k;
     const bool wide = k % 2 == 0;
-    const int V = wide ? 2 : 1, cl = lob_column_lanes(k, V);
-    const long long rows_per_block = kBlock >> cl;
-    const int rgrid = (int)std::max<long long>(1, std::min<long long>(kMcgBlocks, (n + rows_per_block - 1) / rows_per_block));
+    const int V = wide ? 2 : 1, cl = mcg_column_lanes(k, V);  // the residual pass walks as cg_multi's kernels do
+    const int rgrid = solver_grid(kMcgBlocks, n, kBlock >> cl);
     std::vector<double> folded((size_t)2 * 48 * 48), GB((size_t)48 * 48), GA((size_t)48 * 48), C((size_t)48 * 16),
         Cp((size_t)48 * 16), coef, rsum(kk);
     // ||AX - X diag(theta)||_2 per column -> rsum (the host waits); R: where the residual goes (nullptr: nowhere)
@@ -254,12 +245,13 @@ int lob_body(spmv_csr_dev *m, const spmv_precond *pc, int k, int iters, double t
     b.gram_out = scope.alloc<double>((size_t)2 * mp_max * mp_max * sizeof(double));
     b.an_part = scope.alloc<double>((size_t)kNormBlocks * sizeof(double));
     b.an_out = scope.alloc<double>(sizeof(double));
+    // (not solver_begin: the timed part has always included the copy of X0)
     hipError_t e = scope.err;
     if (e == hipSuccess) e = hipEventRecord(scope.e0, g_stream);
     if (e == hipSuccess) e = hipMemcpyAsync(b.X, X0_host, n * kk * sizeof(double), hipMemcpyHostToDevice, g_stream);
-    if (e != hipSuccess) return fail("csr_lobpcg: setup failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return solver_setup_failed("csr_lobpcg", e);
     // anorm = ||A||_inf
-    const int agrid = (int)std::max<size_t>(1, std::min<size_t>(kNormBlocks, (n + kBlock - 1) / kBlock));
+    const int agrid = solver_grid(kNormBlocks, (long long)n, kBlock);
     hipLaunchKernelGGL(lob_row_abs_max, dim3(agrid), dim3(kBlock), 0, g_stream, (long long)n, m->row_ptr,
                        (const double *)m->val, b.an_part);
     hipLaunchKernelGGL(lob_max, dim3(1), dim3(kBlock), 0, g_stream, b.an_part, agrid, b.an_out);
@@ -269,16 +261,13 @@ int lob_body(spmv_csr_dev *m, const spmv_precond *pc, int k, int iters, double t
     LobResult res;
     std::vector<double> theta(kk, 0.0);
     if (lob_run(m, pc, k, iters, tol, largest, b, anorm, theta, theta_hist, res_hist, resid, res)) return -1;
-    e = hipEventRecord(scope.e1, g_stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-    float ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, scope.e0, scope.e1);
-    if (e == hipSuccess && X_host) e = hipMemcpy(X_host, b.X, n * kk * sizeof(double), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail("csr_lobpcg: run failed: %s", hipGetErrorString(e));
+    // X alone comes from the device here: the histories and the stop state are the host's
+    if (solver_finish(scope, "csr_lobpcg", 8, nullptr, b.X, X_host, n * kk * sizeof(double), {}, 0, 0, 0, nullptr, nullptr, 0,
+                      ms_out))
+        return -1;
     if (w) std::memcpy(w, theta.data(), kk * sizeof(double));
     if (anorm_out) *anorm_out = anorm;
     if (info) info[0] = res.steps, info[1] = res.status, info[2] = res.restarts, info[3] = res.min_basis;
-    if (ms_out) *ms_out = ms;
     if (host_ms) *host_ms = (float)res.host_ms;
     return 0;
 }
@@ -293,15 +282,14 @@ extern "C" int spmv_hip_csr_lobpcg(spmv_csr_dev *m, const spmv_precond *P, int k
     int rc = 0;
     if (!m || !X0_host) rc = fail("%s: bad arguments", what);
     else if (m->value_bytes != 8) rc = fail("%s: needs an fp64 handle", what);
-    else if (m->M_total != m->N) rc = fail("%s: needs a square matrix (%d x %d)", what, m->M_total, m->N);
+    else if (solver_check_square(what, m)) rc = -1;
     else if (m->tiles_only) rc = fail("%s: a tiles-only handle has no SpMM kernels", what);
     else if (m->row0 != 0 || m->M_local != m->M_total)
         rc = fail("%s: a handle of rows [%d, %d) is not the whole matrix", what, m->row0, m->row0 + m->M_local);
     else if (g_comm) rc = fail("%s: runs on one device, a communicator is active", what);
     else if (k < 1 || k > kLobMaxK) rc = fail("%s: k = %d, must be in [1, %d]", what, k, kLobMaxK);
     else if (m->M_total < 4 * k) rc = fail("%s: n = %d, must be >= 4 k = %d", what, m->M_total, 4 * k);
-    else if (iters < 0) rc = fail("%s: iters = %d, must be >= 0", what, iters);
-    else if (!(tol >= 0) || !std::isfinite(tol)) rc = fail("%s: tol = %g, must be finite and >= 0", what, tol);
+    else if (solver_check_steps(what, iters, tol)) rc = -1;
     else if ((long long)m->M_total * k > 0x7fffffffLL)
         rc = fail("%s: n * k = %lld values is beyond int range", what, (long long)m->M_total * k);
     else if (P && P->tri)
@@ -325,7 +313,7 @@ extern "C" int spmv_hip_lobpcg_gram(long long n, int k, int nb, const void *cons
         SolverScope scope;
         double *part = scope.alloc<double>((size_t)lob_gram_grid(n) * 2 * mp * mp * sizeof(double));
         double *out = scope.alloc<double>((size_t)2 * mp * mp * sizeof(double));
-        if (scope.err != hipSuccess) return fail("%s: setup failed: %s", what, hipGetErrorString(scope.err));
+        if (scope.err != hipSuccess) return solver_setup_failed(what, scope.err);
         if (lob_gram_launch(n, k, nb, (const double *const *)d_S, (const double *const *)d_AS, part, out)) return -1;
         std::vector<double> folded((size_t)2 * mp * mp);
         HIP_TRY(hipMemcpyAsync(folded.data(), out, folded.size() * sizeof(double), hipMemcpyDeviceToHost, g_stream));
@@ -350,7 +338,7 @@ extern "C" int spmv_hip_lobpcg_update(long long n, int k, int nb, const void *co
         lob_pack_coef(m, k, C_host, Cp_host, coef);
         SolverScope scope;
         double *d_coef = scope.alloc<double>(coef.size() * sizeof(double));
-        if (scope.err != hipSuccess) return fail("%s: setup failed: %s", what, hipGetErrorString(scope.err));
+        if (scope.err != hipSuccess) return solver_setup_failed(what, scope.err);
         HIP_TRY(hipMemcpyAsync(d_coef, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice, g_stream));
         if (lob_update_launch(n, k, nb, (const double *const *)d_S, (const double *const *)d_AS, d_coef, (double *)d_X,
                               (double *)d_P, (double *)d_AX, (double *)d_AP))

@@ -36,8 +36,7 @@ int mr_run(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, doubl
            const int *bounds, const MrBuffers &b, int *steps_run) {
     constexpr int V = 16 / sizeof(T);
     const long long lo = m->row0, hi = (long long)m->row0 + m->M_local;
-    const long long pieces = (hi + V - 1) / V - lo / V;
-    const int grid = (int)std::max<long long>(1, std::min<long long>(kMrBlocks, (pieces + kBlock - 1) / kBlock));
+    const int grid = solver_grid(kMrBlocks, (hi + V - 1) / V - lo / V, kBlock);  // over the 16-byte pieces
     const double tol2 = tol * tol;
     T *v = (T *)b.v, *a = (T *)b.a, *x = (T *)b.x, *yb = (T *)b.y;
     T *r1 = (T *)b.r[0], *r2 = (T *)b.r[1], *w1 = (T *)b.w[0], *w2 = (T *)b.w[1];
@@ -87,7 +86,7 @@ int mr_run(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, doubl
         std::swap(w1, w2);  // w1 = w2; w2 = w
         if (g_comm && spmv_hip_comm_allgatherv(v, bounds, m->value_bytes, g_stream)) return -1;
         bool stop = false;
-        if (solver_poll(k, iters, tol, b.flags + kMrState, kMrStop, &stop)) return -1;
+        if (solver_poll(k, iters, tol, b.flags + kSolverState, kSolverStop, &stop)) return -1;
         if (stop) {
             *steps_run = k;
             break;
@@ -118,33 +117,24 @@ int mr_body(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, doub
     b.part = scope.alloc<double>((size_t)kMrBlocks * sizeof(double));
     b.gath = scope.alloc<double>((size_t)kMaxRanks * sizeof(double));
     b.hist = scope.alloc<double>(((size_t)iters + 1) * sizeof(double));
-    b.flags = scope.alloc<int>(kMrFlagWords * sizeof(int));
+    b.flags = scope.alloc<int>(kSolverFlagWords * sizeof(int));
     // r2 = b on this rank's rows (r1 is first read at step 2, after step 1 made it r2)
     const size_t own_off = (size_t)m->row0 * vb, own_bytes = n_own * vb;
     hipError_t e = scope.err;
     if (e == hipSuccess && n_own)
         e = hipMemcpyAsync((char *)b.r[1] + own_off, (const char *)b_host + own_off, own_bytes, hipMemcpyHostToDevice,
                            g_stream);
-    if (e == hipSuccess) e = hipEventRecord(scope.e0, g_stream);
-    if (e != hipSuccess) return fail("csr_minres: setup failed: %s", hipGetErrorString(e));
+    if (solver_begin(scope, e, "csr_minres")) return -1;
     int steps_run = 0;
     if (mr_run<T>(m, P, variant, iters, tol, shift, bounds, b, &steps_run)) return -1;
-    e = hipEventRecord(scope.e1, g_stream);
-    // the solution: every rank holds its rows; with a communicator all rows everywhere
-    if (e == hipSuccess && g_comm && x_host && spmv_hip_comm_allgatherv(b.x, bounds, m->value_bytes, g_stream)) return -1;
-    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-    float ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, scope.e0, scope.e1);
-    if (e == hipSuccess && x_host) e = hipMemcpy(x_host, b.x, n_all * vb, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = copy_history(rr_hist, b.hist, steps_run, iters, 1);
-    int flags[kMrFlagWords] = {0, 0, 0, 0};
-    if (e == hipSuccess) e = hipMemcpy(flags, b.flags, sizeof flags, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail("csr_minres: run failed: %s", hipGetErrorString(e));
+    int flags[kSolverFlagWords] = {0, 0, 0, 0};
+    if (solver_finish(scope, "csr_minres", m->value_bytes, bounds, b.x, x_host, n_all * vb, {{rr_hist, b.hist}}, steps_run,
+                      iters, 1, b.flags, flags, kSolverFlagWords, ms_total))
+        return -1;
     if (info) {
-        info[0] = flags[kMrSteps];
-        info[1] = flags[kMrStatus];
+        info[0] = flags[kSolverSteps];
+        info[1] = flags[kSolverStatus];
     }
-    if (ms_total) *ms_total = ms;
     return 0;
 }
 
@@ -155,22 +145,14 @@ extern "C" int spmv_hip_csr_minres(spmv_csr_dev *m, const spmv_precond *P, int v
                                    int *info, float *ms_total) {
     const char *what = "csr_minres";
     if (need_device()) return -1;
-    int rc = 0;
-    if (!m || !b_host) rc = fail("%s: bad arguments", what);
-    else if (iters < 0) rc = fail("%s: iters = %d, must be >= 0", what, iters);
-    else if (!(tol >= 0) || !std::isfinite(tol)) rc = fail("%s: tol = %g, must be finite and >= 0", what, tol);
-    else if (!std::isfinite(shift)) rc = fail("%s: shift = %g, must be finite", what, shift);
-    else if (m->M_total != m->N) rc = fail("%s: needs a square matrix (%d x %d)", what, m->M_total, m->N);
-    else if (m->tiles_only) rc = fail("%s: a tiles-only handle runs the tile kernel only", what);
-    else if (g_comm && !bounds) rc = fail("%s: a communicator exists, the row bounds are required", what);
-    else if (!g_comm && (m->row0 != 0 || m->M_local != m->M_total))
-        rc = fail("%s: a handle of rows [%d, %d) needs a communicator", what, m->row0, m->row0 + m->M_local);
-    else if (g_comm_size > kMaxRanks) rc = fail("%s: more than %d ranks", what, kMaxRanks);
-    else if (P) rc = precond_matches(m, P, what);
-    if (rc) return rc;
-    return guarded(what, [&] {
-        return m->value_bytes == 8
-                   ? mr_body<double>(m, P, variant, iters, tol, shift, bounds, b_host, x_host, rr_hist, info, ms_total)
-                   : mr_body<float>(m, P, variant, iters, tol, shift, bounds, b_host, x_host, rr_hist, info, ms_total);
+    if (!m || !b_host) return fail("%s: bad arguments", what);
+    if (solver_check_steps(what, iters, tol)) return -1;
+    if (!std::isfinite(shift)) return fail("%s: shift = %g, must be finite", what, shift);
+    if (solver_check_square(what, m)) return -1;
+    if (m->tiles_only) return fail("%s: a tiles-only handle runs the tile kernel only", what);
+    if (solver_check_rows(what, m, bounds)) return -1;
+    if (P && precond_matches(m, P, what)) return -1;
+    return solver_dispatch(what, m->value_bytes, [&](auto t) {
+        return mr_body<decltype(t)>(m, P, variant, iters, tol, shift, bounds, b_host, x_host, rr_hist, info, ms_total);
     });
 }

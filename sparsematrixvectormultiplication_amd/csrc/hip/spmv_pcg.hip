@@ -31,16 +31,14 @@ namespace {
 // the scalar slots (doubles); two-value reductions land in adjacent slots: (Rr, Rz), (RrNew, RzNew)
 constexpr int kPcgRr = 0, kPcgRz = 1, kPcgPq = 2, kPcgRrNew = 3, kPcgRzNew = 4, kPcgAlpha = 5, kPcgBeta = 6,
               kPcgRr0 = 7, kPcgLastRr = 8, kPcgLastRz = 9, kPcgLocal = 10, kPcgSlots = 16;
-// the int words; the state word is word 0 (pc_apply reads it there) and RUN is 0
-constexpr int kPcgState = 0, kPcgSteps = 1, kPcgStatus = 2, kPcgFlagWords = 4;
-constexpr int kPcgRun = 0, kPcgStop = 1;
+// the int words: the stop flags of solver_ops.hpp
 constexpr int kModeNone = 0, kModeJacobi = 1, kModeBlock = 2, kModeTri = 3;
 
 // partials of a.b on [0, n): dot_partial of spmv_cg.hip with the stop check
 template <typename T>
 __global__ __launch_bounds__(kBlock) void pcg_dot(long long n, const int *__restrict__ flags, const T *__restrict__ a,
                                                   const T *__restrict__ b, double *__restrict__ part) {
-    if (flags[kPcgState] != kPcgRun) return;
+    if (flags[kSolverState] != kSolverRun) return;
     double acc[1] = {0.0};
     for (PieceLane l(0, n, 1); l.q < l.end; l.q += l.stride) acc[0] += (double)a[l.q] * (double)b[l.q];
     block_partials<1>(acc, part);
@@ -50,7 +48,7 @@ __global__ __launch_bounds__(kBlock) void pcg_dot(long long n, const int *__rest
 template <typename T>
 __global__ __launch_bounds__(kBlock) void pcg_dots(long long n, const int *__restrict__ flags, const T *__restrict__ r,
                                                    const T *__restrict__ z, double *__restrict__ part) {
-    if (flags && flags[kPcgState] != kPcgRun) return;
+    if (flags && flags[kSolverState] != kSolverRun) return;
     double acc[2] = {0.0, 0.0};
     for (PieceLane l(0, n, 1); l.q < l.end; l.q += l.stride) {
         const double rk = (double)r[l.q];
@@ -88,7 +86,7 @@ __global__ __launch_bounds__(kBlock) void pcg_update_x_r(long long n, const int 
                                                          const T *__restrict__ q, const T *__restrict__ dinv,
                                                          T *__restrict__ x, T *__restrict__ r, T *__restrict__ z,
                                                          double *__restrict__ part) {
-    if (flags[kPcgState] != kPcgRun) return;
+    if (flags[kSolverState] != kSolverRun) return;
     const double alpha = s[kPcgAlpha];
     double acc[2] = {0.0, 0.0};
     for (PieceLane l(0, n, 1); l.q < l.end; l.q += l.stride) {
@@ -114,18 +112,13 @@ template <typename T>
 __global__ __launch_bounds__(kBlock) void pcg_update_p(long long n, const int *__restrict__ flags,
                                                        const double *__restrict__ s, const T *__restrict__ z,
                                                        T *__restrict__ p) {
-    if (flags[kPcgState] != kPcgRun) return;
+    if (flags[kSolverState] != kSolverRun) return;
     const double beta = s[kPcgBeta];
     for (PieceLane l(0, n, 1); l.q < l.end; l.q += l.stride) p[l.q] = (T)((double)z[l.q] + beta * (double)p[l.q]);
 }
 
-// ---- the scalar kernels: one thread each.  A stop writes the status and the steps taken and never touches x.
-__device__ __forceinline__ void pcg_stop(int *__restrict__ flags, int status, int steps) {
-    flags[kPcgState] = kPcgStop;
-    flags[kPcgStatus] = status;
-    flags[kPcgSteps] = steps;
-}
-
+// ---- the scalar kernels: one thread each.  A stop (solver_stop) writes the status and the steps taken and never
+// touches x.
 // rr0 = r.r, rz = r.z, history row 0; rr0 = 0 converges at step 0; rz <= 0 or anything not finite breaks down there
 __global__ void pcg_start(double *__restrict__ s, int *__restrict__ flags, double *__restrict__ hrr,
                           double *__restrict__ hrz, int iters) {
@@ -135,19 +128,19 @@ __global__ void pcg_start(double *__restrict__ s, int *__restrict__ flags, doubl
     s[kPcgLastRz] = rz;
     hrr[0] = rr0;
     hrz[0] = rz;
-    flags[kPcgState] = kPcgRun;
-    flags[kPcgSteps] = iters;
-    flags[kPcgStatus] = SPMV_PCG_RAN_ALL;
-    if (rr0 == 0.0) pcg_stop(flags, SPMV_PCG_CONVERGED, 0);
-    else if (!(rz > 0.0) || !isfinite(rz) || !isfinite(rr0)) pcg_stop(flags, SPMV_PCG_BREAKDOWN, 0);
+    flags[kSolverState] = kSolverRun;
+    flags[kSolverSteps] = iters;
+    flags[kSolverStatus] = SPMV_PCG_RAN_ALL;
+    if (rr0 == 0.0) solver_stop(flags, SPMV_PCG_CONVERGED, 0);
+    else if (!(rz > 0.0) || !isfinite(rz) || !isfinite(rr0)) solver_stop(flags, SPMV_PCG_BREAKDOWN, 0);
 }
 
 // step t: alpha = rz / p.q; p.q <= 0 or anything not finite breaks down (step t not taken)
 __global__ void pcg_set_alpha(double *__restrict__ s, int *__restrict__ flags, int t) {
-    if (flags[kPcgState] != kPcgRun) return;
+    if (flags[kSolverState] != kSolverRun) return;
     const double pq = s[kPcgPq], alpha = s[kPcgRz] / pq;
     if (!(pq > 0.0) || !isfinite(pq) || !isfinite(alpha)) {
-        pcg_stop(flags, SPMV_PCG_BREAKDOWN, t - 1);
+        solver_stop(flags, SPMV_PCG_BREAKDOWN, t - 1);
         return;
     }
     s[kPcgAlpha] = alpha;
@@ -157,7 +150,7 @@ __global__ void pcg_set_alpha(double *__restrict__ s, int *__restrict__ flags, i
 // (x is the iterate of step t); else beta = rz' / rz, rz = rz'
 __global__ void pcg_set_beta(double *__restrict__ s, int *__restrict__ flags, double *__restrict__ hrr,
                              double *__restrict__ hrz, int t, double tol2) {
-    if (flags[kPcgState] != kPcgRun) {
+    if (flags[kSolverState] != kSolverRun) {
         hrr[t] = s[kPcgLastRr];
         hrz[t] = s[kPcgLastRz];
         return;
@@ -168,15 +161,15 @@ __global__ void pcg_set_beta(double *__restrict__ s, int *__restrict__ flags, do
     hrr[t] = rr;
     hrz[t] = rz;
     if (!isfinite(rr) || !isfinite(rz)) {
-        pcg_stop(flags, SPMV_PCG_BREAKDOWN, t);
+        solver_stop(flags, SPMV_PCG_BREAKDOWN, t);
         return;
     }
     if (rr <= tol2 * s[kPcgRr0]) {
-        pcg_stop(flags, SPMV_PCG_CONVERGED, t);
+        solver_stop(flags, SPMV_PCG_CONVERGED, t);
         return;
     }
     if (!(rz > 0.0)) {
-        pcg_stop(flags, SPMV_PCG_BREAKDOWN, t);
+        solver_stop(flags, SPMV_PCG_BREAKDOWN, t);
         return;
     }
     s[kPcgBeta] = rz / s[kPcgRz];
@@ -199,7 +192,7 @@ template <typename T>
 int pcg_run(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, double tol, const int *bounds,
             const PcgBuffers &b, int *steps_run) {
     const long long n = m->M_local;
-    const int grid = (int)std::max<long long>(1, std::min<long long>(kNormBlocks, (n + kBlock - 1) / kBlock));
+    const int grid = solver_grid(kNormBlocks, n, kBlock);
     const int mode = !P ? kModeNone : precond_has_own_apply(P) ? kModeTri : P->block == 1 ? kModeJacobi : kModeBlock;
     const double tol2 = tol * tol;
     T *p_own = (T *)m->x + m->row0, *q_own = (T *)m->y + m->row0, *x_own = (T *)b.x + m->row0;
@@ -252,7 +245,7 @@ int pcg_run(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, doub
         hipLaunchKernelGGL((pcg_update_p<T>), g, blk, 0, g_stream, n, fl, (const double *)b.sc, (const T *)z, p_own);
         if (pcg_exchange_p(m, bounds)) return -1;
         bool stop = false;
-        if (solver_poll(t, iters, tol, b.flags + kPcgState, kPcgStop, &stop)) return -1;
+        if (solver_poll(t, iters, tol, b.flags + kSolverState, kSolverStop, &stop)) return -1;
         if (stop) {
             *steps_run = t;
             break;
@@ -276,33 +269,23 @@ int pcg_body(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, dou
     b.gath = scope.alloc<double>((size_t)kMaxRanks * 2 * sizeof(double));
     b.hrr = scope.alloc<double>(((size_t)iters + 1) * sizeof(double));
     b.hrz = scope.alloc<double>(((size_t)iters + 1) * sizeof(double));
-    b.flags = scope.alloc<int>(kPcgFlagWords * sizeof(int));
+    b.flags = scope.alloc<int>(kSolverFlagWords * sizeof(int));
     // r = b on this rank's rows; the handle's x (p) starts at 0 (its own range is set to z by the loop)
     hipError_t e = scope.err;
     if (e == hipSuccess && n_own)
         e = hipMemcpyAsync(b.r, (const T *)b_host + m->row0, n_own * vb, hipMemcpyHostToDevice, g_stream);
     if (e == hipSuccess) e = hipMemsetAsync(m->x, 0, (size_t)m->N * vb, g_stream);
-    if (e == hipSuccess) e = hipEventRecord(scope.e0, g_stream);
-    if (e != hipSuccess) return fail("csr_pcg: setup failed: %s", hipGetErrorString(e));
+    if (solver_begin(scope, e, "csr_pcg")) return -1;
     int steps_run = 0;
     if (pcg_run<T>(m, P, variant, iters, tol, bounds, b, &steps_run)) return -1;
-    e = hipEventRecord(scope.e1, g_stream);
-    // the solution: every rank holds its rows; with a communicator all rows everywhere
-    if (e == hipSuccess && g_comm && x_host && spmv_hip_comm_allgatherv(b.x, bounds, m->value_bytes, g_stream)) return -1;
-    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-    float ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, scope.e0, scope.e1);
-    if (e == hipSuccess && x_host) e = hipMemcpy(x_host, b.x, n_all * vb, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = copy_history(rr_hist, b.hrr, steps_run, iters, 1);
-    if (e == hipSuccess) e = copy_history(rz_hist, b.hrz, steps_run, iters, 1);
-    int flags[kPcgFlagWords] = {0, 0, 0, 0};
-    if (e == hipSuccess) e = hipMemcpy(flags, b.flags, sizeof flags, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail("csr_pcg: run failed: %s", hipGetErrorString(e));
+    int flags[kSolverFlagWords] = {0, 0, 0, 0};
+    if (solver_finish(scope, "csr_pcg", m->value_bytes, bounds, b.x, x_host, n_all * vb,
+                      {{rr_hist, b.hrr}, {rz_hist, b.hrz}}, steps_run, iters, 1, b.flags, flags, kSolverFlagWords, ms_total))
+        return -1;
     if (info) {
-        info[0] = flags[kPcgSteps];
-        info[1] = flags[kPcgStatus];
+        info[0] = flags[kSolverSteps];
+        info[1] = flags[kSolverStatus];
     }
-    if (ms_total) *ms_total = ms;
     return 0;
 }
 
@@ -312,20 +295,12 @@ extern "C" int spmv_hip_csr_pcg(spmv_csr_dev *m, const spmv_precond *P, int vari
                                 const int *bounds, const void *b_host, void *x_host, double *rr_hist, double *rz_hist,
                                 int *info, float *ms_total) {
     if (need_device()) return -1;
-    int rc = 0;
-    if (!m || !b_host) rc = fail("csr_pcg: bad arguments");
-    else if (iters < 0) rc = fail("csr_pcg: iters = %d, must be >= 0", iters);
-    else if (!(tol >= 0) || !std::isfinite(tol)) rc = fail("csr_pcg: tol = %g, must be finite and >= 0", tol);
-    else if (m->M_total != m->N) rc = fail("csr_pcg: needs a square matrix (%d x %d)", m->M_total, m->N);
-    else if (g_comm && !bounds) rc = fail("csr_pcg: a communicator exists, the row bounds are required");
-    else if (!g_comm && (m->row0 != 0 || m->M_local != m->M_total))
-        rc = fail("csr_pcg: a handle of rows [%d, %d) needs a communicator", m->row0, m->row0 + m->M_local);
-    else if (g_comm_size > kMaxRanks) rc = fail("csr_pcg: more than %d ranks", kMaxRanks);
-    else if (P) rc = precond_matches(m, P, "csr_pcg");
-    if (rc) return rc;
-    return guarded("csr_pcg", [&] {
-        return m->value_bytes == 8
-                   ? pcg_body<double>(m, P, variant, iters, tol, bounds, b_host, x_host, rr_hist, rz_hist, info, ms_total)
-                   : pcg_body<float>(m, P, variant, iters, tol, bounds, b_host, x_host, rr_hist, rz_hist, info, ms_total);
+    const char *what = "csr_pcg";
+    if (!m || !b_host) return fail("%s: bad arguments", what);
+    if (solver_check_steps(what, iters, tol) || solver_check_square(what, m) || solver_check_rows(what, m, bounds))
+        return -1;
+    if (P && precond_matches(m, P, what)) return -1;
+    return solver_dispatch(what, m->value_bytes, [&](auto t) {
+        return pcg_body<decltype(t)>(m, P, variant, iters, tol, bounds, b_host, x_host, rr_hist, rz_hist, info, ms_total);
     });
 }

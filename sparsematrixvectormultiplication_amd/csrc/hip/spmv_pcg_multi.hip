@@ -23,9 +23,8 @@
 
 namespace {
 
-constexpr int kModeNone = 0, kModeJacobi = 1, kModeBlock = 2, kModeFsai = 3;
-
-int mpcg_mode(const spmv_precond *P) { return !P ? kModeNone : P->fsai ? kModeFsai : P->block == 1 ? kModeJacobi : kModeBlock; }
+// the mode of mpcg_update_x_r: block-Jacobi and FSAI apply after it
+int mpcg_mode(const spmv_precond *P) { return !P ? kMpcgNone : !P->fsai && P->block == 1 ? kMpcgJacobi : kMpcgApply; }
 
 // SSOR / ILU(0): -1 with a message naming `what`
 int mpcg_refuse_tri(const spmv_precond *P, const char *what) {
@@ -34,18 +33,11 @@ int mpcg_refuse_tri(const spmv_precond *P, const char *what) {
     return 0;
 }
 
-// column lanes: the next power of two >= k / V
-int mpcg_column_lanes(int k, int V) {
-    int cl = 0;
-    while ((1 << cl) * V < k) ++cl;
-    return cl;
-}
-
 // Z = M^-1 R for Jacobi / block-Jacobi on stream s, V values per lane; DOTS, flags and the partials as mpc_apply
 template <typename T, int V, bool DOTS>
 void mpc_launch(const spmv_precond *P, int k, const void *R, void *Z, const int *flags, double *part_rr, double *part_rz,
                 int grid, hipStream_t s) {
-    const int cl = mpcg_column_lanes(k, V);
+    const int cl = mcg_column_lanes(k, V);
     hipLaunchKernelGGL((mpc_apply<T, V, DOTS>), dim3(grid), dim3(kBlock), 0, s, (long long)P->rows, k, cl, P->block,
                        (const T *)P->inv, (const T *)R, (T *)Z, flags, part_rr, part_rz);
 }
@@ -57,8 +49,7 @@ int mpc_apply_on(const spmv_precond *P, int k, const void *R, void *Z, void *wor
     if (P->fsai) return precond_fsai_apply_multi(P, k, R, Z, work, s);
     constexpr int W = 16 / sizeof(T);
     const bool wide = (size_t)k * sizeof(T) % 16 == 0 && (((uintptr_t)R | (uintptr_t)Z) & 15) == 0;
-    const long long rows_per_block = kBlock >> mpcg_column_lanes(k, wide ? W : 1);
-    const int grid = (int)std::max<long long>(1, std::min<long long>(kMcgBlocks, (P->rows + rows_per_block - 1) / rows_per_block));
+    const int grid = solver_grid(kMcgBlocks, P->rows, kBlock >> mcg_column_lanes(k, wide ? W : 1));
     if (wide) mpc_launch<T, W, false>(P, k, R, Z, nullptr, nullptr, nullptr, grid, s);
     else mpc_launch<T, 1, false>(P, k, R, Z, nullptr, nullptr, nullptr, grid, s);
     HIP_TRY(hipGetLastError());
@@ -84,11 +75,10 @@ template <typename T, int V>
 int mpcg_run(spmv_csr_dev *m, const spmv_precond *pc, int k, int iters, double tol, const int *kbounds,
              const MpcgBuffers &b, int *steps) {
     const long long n = m->M_local, kk = k;
-    const int cl = mpcg_column_lanes(k, V);
-    const long long rows_per_block = kBlock >> cl;
+    const int cl = mcg_column_lanes(k, V);
     const int cap = k == 1 ? kNormBlocks : kMcgBlocks;  // k = 1: csr_pcg's workgroups, csr_pcg's bits
-    const int grid = (int)std::max<long long>(1, std::min<long long>(cap, (n + rows_per_block - 1) / rows_per_block));
-    const int mode = mpcg_mode(pc), z_is_r = mode == kModeNone;
+    const int grid = solver_grid(cap, n, kBlock >> cl);
+    const int mode = mpcg_mode(pc), z_is_r = mode == kMpcgNone;
     const double tol2 = tol * tol;
     T *P = (T *)b.P, *p_own = P + m->row0 * kk, *q_own = (T *)b.Q + m->row0 * kk, *x_own = (T *)b.X + m->row0 * kk;
     T *R = (T *)b.R, *Z = (T *)b.Z;
@@ -105,7 +95,7 @@ int mpcg_run(spmv_csr_dev *m, const spmv_precond *pc, int k, int iters, double t
     auto reduce_dots = [&] { return reduce(b.part_rr, kMpcgRrNew) || (!z_is_r && reduce(b.part_rz, kMpcgRzNew)); };
     // after the x / r update of the modes that do not fuse their apply: Z = M^-1 R and the two sets of partials
     auto apply_dots = [&](const int *flags) {
-        if (mode == kModeBlock) {
+        if (!pc->fsai) {
             mpc_launch<T, V, true>(pc, k, R, Z, flags, b.part_rr, b.part_rz, grid, g_stream);
             return 0;
         }
@@ -114,9 +104,9 @@ int mpcg_run(spmv_csr_dev *m, const spmv_precond *pc, int k, int iters, double t
         return 0;
     };
     // Z = M^-1 R, rr0 = r.r, rz = r.z with R = B; P = Z (its own range; the rest by the all-gatherv)
-    if (mode == kModeNone)
+    if (mode == kMpcgNone)
         hipLaunchKernelGGL((mpcg_start_dots<T, V, false>), g, blk, 0, g_stream, n, k, cl, dinv, (const T *)R, Z, b.part_rr, b.part_rz);
-    else if (mode == kModeJacobi)
+    else if (mode == kMpcgJacobi)
         hipLaunchKernelGGL((mpcg_start_dots<T, V, true>), g, blk, 0, g_stream, n, k, cl, dinv, (const T *)R, Z, b.part_rr, b.part_rz);
     else if (apply_dots(nullptr))
         return -1;
@@ -131,10 +121,10 @@ int mpcg_run(spmv_csr_dev *m, const spmv_precond *pc, int k, int iters, double t
                            b.part_rr);
         if (reduce(b.part_rr, kMcgPq)) return -1;
         hipLaunchKernelGGL(mpcg_set_alpha, dim3(1), dim3(64), 0, g_stream, b.s, b.flags, k, t);
-        if (mode == kModeNone) {
+        if (mode == kMpcgNone) {
             hipLaunchKernelGGL((mpcg_update_x_r<T, V, kMpcgNone>), g, blk, 0, g_stream, n, k, cl, sc, fl, (const T *)p_own,
                                (const T *)q_own, dinv, x_own, R, Z, b.part_rr, b.part_rz);
-        } else if (mode == kModeJacobi) {
+        } else if (mode == kMpcgJacobi) {
             hipLaunchKernelGGL((mpcg_update_x_r<T, V, kMpcgJacobi>), g, blk, 0, g_stream, n, k, cl, sc, fl, (const T *)p_own,
                                (const T *)q_own, dinv, x_own, R, Z, b.part_rr, b.part_rz);
         } else {
@@ -164,11 +154,7 @@ int mpcg_body(spmv_csr_dev *m, const spmv_precond *pc, int k, int iters, double 
               float *ms_total) {
     const size_t kk = (size_t)k, vb = sizeof(T);
     const size_t n_all = (size_t)m->M_total, n_own = (size_t)m->M_local, ncols = (size_t)m->N;
-    std::vector<int> kbounds;
-    if (g_comm) {
-        kbounds.resize((size_t)g_comm_size + 1);
-        for (int r = 0; r <= g_comm_size; ++r) kbounds[r] = bounds[r] * k;
-    }
+    const std::vector<int> kbounds = solver_scaled_bounds(bounds, k);
     SolverScope scope;
     // what feeds a product at k = 1 is read in whole 128-byte lines by the x-window SpMV kernels: P by A, and with
     // FSAI R by G and work by G^T
@@ -193,30 +179,19 @@ int mpcg_body(spmv_csr_dev *m, const spmv_precond *pc, int k, int iters, double 
     hipError_t e = scope.err;
     if (e == hipSuccess && n_own)
         e = hipMemcpyAsync(b.R, (const char *)B_host + (size_t)m->row0 * kk * vb, own_bytes, hipMemcpyHostToDevice, g_stream);
-    if (e == hipSuccess) e = hipEventRecord(scope.e0, g_stream);
-    if (e != hipSuccess) return fail("csr_pcg_multi: setup failed: %s", hipGetErrorString(e));
+    if (solver_begin(scope, e, "csr_pcg_multi")) return -1;
     int steps = 0;
     const bool wide = kk * vb % 16 == 0;
     if (wide ? mpcg_run<T, 16 / sizeof(T)>(m, pc, k, iters, tol, kbounds.data(), b, &steps)
              : mpcg_run<T, 1>(m, pc, k, iters, tol, kbounds.data(), b, &steps))
         return -1;
-    e = hipEventRecord(scope.e1, g_stream);
-    // the solution: every rank holds its rows; with a communicator all rows everywhere
-    if (e == hipSuccess && g_comm && X_host && spmv_hip_comm_allgatherv(b.X, kbounds.data(), m->value_bytes, g_stream))
-        return -1;
-    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-    float ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, scope.e0, scope.e1);
-    if (e == hipSuccess && X_host) e = hipMemcpy(X_host, b.X, n_all * kk * vb, hipMemcpyDeviceToHost);
     // stopped early: every column has stopped, its histories repeat their last value
-    if (e == hipSuccess) e = copy_history(rr_hist, b.hrr, steps, iters, kk);
-    if (e == hipSuccess) e = copy_history(rz_hist, b.hrz, steps, iters, kk);
     int flags[kMpcgFlagWords];
-    if (e == hipSuccess) e = hipMemcpy(flags, b.flags, sizeof flags, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail("csr_pcg_multi: run failed: %s", hipGetErrorString(e));
+    if (solver_finish(scope, "csr_pcg_multi", m->value_bytes, kbounds.data(), b.X, X_host, n_all * kk * vb,
+                      {{rr_hist, b.hrr}, {rz_hist, b.hrz}}, steps, iters, kk, b.flags, flags, kMpcgFlagWords, ms_total))
+        return -1;
     if (steps_out) std::memcpy(steps_out, flags + kMcgDone, kk * sizeof(int));
     if (status_out) std::memcpy(status_out, flags + kMpcgStatus, kk * sizeof(int));
-    if (ms_total) *ms_total = ms;
     return 0;
 }
 
@@ -226,27 +201,18 @@ extern "C" int spmv_hip_csr_pcg_multi(spmv_csr_dev *m, const spmv_precond *P, in
                                       const int *bounds, const void *B_host, void *X_host, double *rr_hist,
                                       double *rz_hist, int *steps, int *status, float *ms_total) {
     if (need_device()) return -1;
-    int rc = 0;
-    if (!m || !B_host) rc = fail("csr_pcg_multi: bad arguments");
-    else if (iters < 0) rc = fail("csr_pcg_multi: iters = %d, must be >= 0", iters);
-    else if (!(tol >= 0) || !std::isfinite(tol)) rc = fail("csr_pcg_multi: tol = %g, must be finite and >= 0", tol);
-    else if (k < 1 || k > kMcgMaxK) rc = fail("csr_pcg_multi: k = %d, must be in [1, %d]", k, kMcgMaxK);
-    else if (m->M_total != m->N) rc = fail("csr_pcg_multi: needs a square matrix (%d x %d)", m->M_total, m->N);
-    else if (m->tiles_only) rc = fail("csr_pcg_multi: a tiles-only handle has no SpMM kernels");
-    else if ((long long)m->M_total * k > 0x7fffffffLL)
-        rc = fail("csr_pcg_multi: n * k = %lld values is beyond int range", (long long)m->M_total * k);
-    else if (g_comm && !bounds) rc = fail("csr_pcg_multi: a communicator exists, the row bounds are required");
-    else if (!g_comm && (m->row0 != 0 || m->M_local != m->M_total))
-        rc = fail("csr_pcg_multi: a handle of rows [%d, %d) needs a communicator", m->row0, m->row0 + m->M_local);
-    else if (g_comm_size > kMaxRanks) rc = fail("csr_pcg_multi: more than %d ranks", kMaxRanks);
-    else if (P && mpcg_refuse_tri(P, "csr_pcg_multi")) rc = -1;
-    else if (P) rc = precond_matches(m, P, "csr_pcg_multi");
-    if (rc) return rc;
-    return guarded("csr_pcg_multi", [&] {
-        return m->value_bytes == 8 ? mpcg_body<double>(m, P, k, iters, tol, bounds, B_host, X_host, rr_hist, rz_hist, steps,
-                                                       status, ms_total)
-                                   : mpcg_body<float>(m, P, k, iters, tol, bounds, B_host, X_host, rr_hist, rz_hist, steps,
-                                                      status, ms_total);
+    const char *what = "csr_pcg_multi";
+    if (!m || !B_host) return fail("%s: bad arguments", what);
+    if (solver_check_steps(what, iters, tol)) return -1;
+    if (k < 1 || k > kMcgMaxK) return fail("%s: k = %d, must be in [1, %d]", what, k, kMcgMaxK);
+    if (solver_check_square(what, m)) return -1;
+    if (m->tiles_only) return fail("%s: a tiles-only handle has no SpMM kernels", what);
+    if ((long long)m->M_total * k > 0x7fffffffLL)
+        return fail("%s: n * k = %lld values is beyond int range", what, (long long)m->M_total * k);
+    if (solver_check_rows(what, m, bounds)) return -1;
+    if (P && (mpcg_refuse_tri(P, what) || precond_matches(m, P, what))) return -1;
+    return solver_dispatch(what, m->value_bytes, [&](auto t) {
+        return mpcg_body<decltype(t)>(m, P, k, iters, tol, bounds, B_host, X_host, rr_hist, rz_hist, steps, status, ms_total);
     });
 }
 
@@ -273,13 +239,13 @@ extern "C" int spmv_hip_precond_apply_multi(const spmv_precond *P, int k, const 
         void *work = P->fsai ? scope.alloc(padded) : nullptr;
         hipError_t e = scope.err;
         if (e == hipSuccess && bytes) e = hipMemcpyAsync(R, R_host, bytes, hipMemcpyHostToDevice, g_stream);
-        if (e != hipSuccess) return fail("precond_apply_multi: setup failed: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return solver_setup_failed("precond_apply_multi", e);
         if (P->value_bytes == 8 ? mpc_apply_on<double>(P, k, R, Z, work, g_stream)
                                 : mpc_apply_on<float>(P, k, R, Z, work, g_stream))
             return -1;
         e = hipStreamSynchronize(g_stream);
         if (e == hipSuccess && bytes) e = hipMemcpy(Z_host, Z, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return fail("precond_apply_multi: run failed: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return solver_run_failed("precond_apply_multi", e);
         return 0;
     });
 }

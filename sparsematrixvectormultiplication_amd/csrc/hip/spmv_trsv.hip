@@ -142,7 +142,7 @@ int tri_upload(const Canon &B, int uplo, const TriPlan &p, const T *dinv, const 
             const long long ns = p.level_split[l0] - p.level_ptr[l0], nl = p.level_ptr[l0 + 1] - p.level_split[l0];
             threads = std::max(ns * G, nl * 64);
         }
-        const int grid = (int)std::max<long long>(1, std::min<long long>(spmv::kTrsvBlocks, (threads + kBlock - 1) / kBlock));
+        const int grid = solver_grid(spmv::kTrsvBlocks, threads, kBlock);
         t.plan.insert(t.plan.end(), {kind, l0, l1, grid});
     }
     if (to_device(&t.rp, rp) || to_device(&t.col, col) || to_device(&t.brow, brow) || to_device(&t.xrow, xrow) ||

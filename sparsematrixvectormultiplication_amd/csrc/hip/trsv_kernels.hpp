@@ -77,7 +77,7 @@ __device__ __forceinline__ void trsv_rows(const TrsvView &t, int first, int coun
 template <typename T, bool SCALED>
 __global__ __launch_bounds__(kBlock) void trsv_level(TrsvView t, int level, int G, double scale,
                                                      const int *__restrict__ flags, const T *__restrict__ b, T *x) {
-    if (flags && flags[0] != 0) return;
+    if (flags && flags[kSolverState] != kSolverRun) return;
     const long long tid = (long long)blockIdx.x * kBlock + threadIdx.x, nthreads = (long long)gridDim.x * kBlock;
     const int p0 = t.level_ptr[level], ps = t.level_split[level], p1 = t.level_ptr[level + 1];
     trsv_rows<T, SCALED>(t, p0, ps - p0, G, tid, nthreads, scale, b, x);
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(kBlock) void trsv_level(TrsvView t, int level, int 
 template <typename T, bool SCALED>
 __global__ __launch_bounds__(kBlock) void trsv_chain(TrsvView t, int l0, int l1, int G, double scale,
                                                      const int *__restrict__ flags, const T *__restrict__ b, T *x) {
-    if (flags && flags[0] != 0) return;
+    if (flags && flags[kSolverState] != kSolverRun) return;
     for (int l = l0; l < l1; ++l) {
         const int p0 = t.level_ptr[l], ps = t.level_split[l], p1 = t.level_ptr[l + 1];
         trsv_rows<T, SCALED>(t, p0, ps - p0, G, threadIdx.x, kBlock, scale, b, x);

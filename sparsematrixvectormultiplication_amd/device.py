@@ -361,9 +361,7 @@ class CsrDevice(_Handle):
     def power_iterate(self, iters, variant=CSR_AUTO, bounds=None, use_graph=True):
         """iters steps of x <- A x / ||A x||_2 on the device; returns (lambda, ms_total)."""
         lam, ms = C.c_double(0), C.c_float(0)
-        b = None if bounds is None else np.ascontiguousarray(bounds, dtype=np.int32)
-        _check(nat.lib().spmv_hip_csr_power_iterate(self.h, int(variant), int(iters),
-                                                    None if b is None else b.ctypes.data_as(nat.c_int_p),
+        _check(nat.lib().spmv_hip_csr_power_iterate(self.h, int(variant), int(iters), _bounds_arg(bounds),
                                                     int(bool(use_graph)), C.byref(lam), C.byref(ms)),
                "csr_power_iterate")
         return float(lam.value), float(ms.value)
@@ -376,9 +374,7 @@ class CsrDevice(_Handle):
         x = np.zeros(self.M, dtype=self.dtype)
         hist = np.zeros(iters + 1)
         ms = C.c_float(0)
-        bb = None if bounds is None else np.ascontiguousarray(bounds, dtype=np.int32)
-        _check(nat.lib().spmv_hip_csr_cg(self.h, int(variant), int(iters),
-                                         None if bb is None else bb.ctypes.data_as(nat.c_int_p), int(bool(use_halo)),
+        _check(nat.lib().spmv_hip_csr_cg(self.h, int(variant), int(iters), _bounds_arg(bounds), int(bool(use_halo)),
                                          b.ctypes.data_as(C.c_void_p), x.ctypes.data_as(C.c_void_p),
                                          hist.ctypes.data_as(nat.c_double_p), C.byref(ms)), "spmv_hip_csr_cg")
         return x, hist, float(ms.value)
@@ -395,37 +391,25 @@ class CsrDevice(_Handle):
             B = B.reshape(-1, 1)
         if B.ndim != 2 or B.shape[0] != self.M or not 1 <= B.shape[1] <= 64:
             raise ValueError(f"B must be {self.M} x k with 1 <= k <= 64, got shape {B.shape}")
-        if int(iters) < 0:
-            raise ValueError(f"iters must be >= 0, got {iters}")
-        if not float(tol) >= 0.0:
-            raise ValueError(f"tol must be >= 0, got {tol}")
+        _check_iters_tol(iters, tol, finite=False)
         B = np.ascontiguousarray(B)
         k = B.shape[1]
         X = np.zeros((self.M, k), dtype=self.dtype)
         hist = np.zeros((int(iters) + 1, k))
         done = np.zeros(k, dtype=np.int32)
         ms = C.c_float(0)
-        bb = None if bounds is None else np.ascontiguousarray(bounds, dtype=np.int32)
-        _check(nat.lib().spmv_hip_csr_cg_multi(self.h, int(k), int(iters), float(tol),
-                                               None if bb is None else bb.ctypes.data_as(nat.c_int_p),
+        _check(nat.lib().spmv_hip_csr_cg_multi(self.h, int(k), int(iters), float(tol), _bounds_arg(bounds),
                                                B.ctypes.data_as(C.c_void_p), X.ctypes.data_as(C.c_void_p),
                                                hist.ctypes.data_as(nat.c_double_p), done.ctypes.data_as(nat.c_int_p),
                                                C.byref(ms)), "spmv_hip_csr_cg_multi")
         return X, hist, done, float(ms.value)
 
     def _check_solve_args(self, b, iters, tol, precond):
-        b = np.asarray(b)
-        if b.dtype != self.dtype:
-            raise ValueError(f"b has dtype {b.dtype}, the handle holds {np.dtype(self.dtype)}")
-        if b.ndim != 1 or b.shape[0] != self.M:
-            raise ValueError(f"b must be a vector of {self.M} values, got shape {b.shape}")
-        if int(iters) < 0:
-            raise ValueError(f"iters must be >= 0, got {iters}")
-        if not float(tol) >= 0.0 or not np.isfinite(float(tol)):
-            raise ValueError(f"tol must be finite and >= 0, got {tol}")
+        b = _check_vector(b, self.M, self.dtype, "b", "handle")
+        _check_iters_tol(iters, tol)
         if precond is not None:
             self._check_precond(precond)
-        return np.ascontiguousarray(b)
+        return b
 
     def _check_precond(self, precond):
         if not isinstance(precond, Preconditioner):
@@ -487,9 +471,8 @@ class CsrDevice(_Handle):
         rz = np.zeros(int(iters) + 1)
         info = np.zeros(2, dtype=np.int32)
         ms = C.c_float(0)
-        bb = None if bounds is None else np.ascontiguousarray(bounds, dtype=np.int32)
         _check(nat.lib().spmv_hip_csr_pcg(self.h, None if precond is None else precond.h, int(variant), int(iters),
-                                          float(tol), None if bb is None else bb.ctypes.data_as(nat.c_int_p),
+                                          float(tol), _bounds_arg(bounds),
                                           b.ctypes.data_as(C.c_void_p), x.ctypes.data_as(C.c_void_p),
                                           rr.ctypes.data_as(nat.c_double_p), rz.ctypes.data_as(nat.c_double_p),
                                           info.ctypes.data_as(nat.c_int_p), C.byref(ms)), "spmv_hip_csr_pcg")
@@ -503,10 +486,7 @@ class CsrDevice(_Handle):
         also ends the loop early once every column has stopped.  Returns (X (M, k), r.r history (iters + 1, k), r.z
         history (iters + 1, k), info {"steps": int array [k], "status": int array [k] (PCG_*)}, ms)."""
         B = _check_columns(B, self.M, self.dtype, "B", "handle")
-        if int(iters) < 0:
-            raise ValueError(f"iters must be >= 0, got {iters}")
-        if not float(tol) >= 0.0 or not np.isfinite(float(tol)):
-            raise ValueError(f"tol must be finite and >= 0, got {tol}")
+        _check_iters_tol(iters, tol)
         if precond is not None:
             self._check_precond(precond)
         k = B.shape[1]
@@ -516,9 +496,8 @@ class CsrDevice(_Handle):
         steps = np.zeros(k, dtype=np.int32)
         status = np.zeros(k, dtype=np.int32)
         ms = C.c_float(0)
-        bb = None if bounds is None else np.ascontiguousarray(bounds, dtype=np.int32)
         _check(nat.lib().spmv_hip_csr_pcg_multi(self.h, None if precond is None else precond.h, int(k), int(iters),
-                                                float(tol), None if bb is None else bb.ctypes.data_as(nat.c_int_p),
+                                                float(tol), _bounds_arg(bounds),
                                                 B.ctypes.data_as(C.c_void_p), X.ctypes.data_as(C.c_void_p),
                                                 rr.ctypes.data_as(nat.c_double_p), rz.ctypes.data_as(nat.c_double_p),
                                                 steps.ctypes.data_as(nat.c_int_p), status.ctypes.data_as(nat.c_int_p),
@@ -536,9 +515,8 @@ class CsrDevice(_Handle):
         hist = np.zeros(int(iters) + 1)
         info = np.zeros(3, dtype=np.int32)
         ms = C.c_float(0)
-        bb = None if bounds is None else np.ascontiguousarray(bounds, dtype=np.int32)
-        args = (int(variant), int(iters), float(tol), None if bb is None else bb.ctypes.data_as(nat.c_int_p),
-                b.ctypes.data_as(C.c_void_p), x.ctypes.data_as(C.c_void_p), hist.ctypes.data_as(nat.c_double_p),
+        args = (int(variant), int(iters), float(tol), _bounds_arg(bounds), b.ctypes.data_as(C.c_void_p),
+                x.ctypes.data_as(C.c_void_p), hist.ctypes.data_as(nat.c_double_p),
                 info.ctypes.data_as(nat.c_int_p), C.byref(ms))
         if precond is None:
             _check(nat.lib().spmv_hip_csr_bicgstab(self.h, *args), "spmv_hip_csr_bicgstab")
@@ -560,10 +538,8 @@ class CsrDevice(_Handle):
         hist = np.zeros(int(iters) + 1)
         info = np.zeros(2, dtype=np.int32)
         ms = C.c_float(0)
-        bb = None if bounds is None else np.ascontiguousarray(bounds, dtype=np.int32)
         _check(nat.lib().spmv_hip_csr_minres(self.h, None if precond is None else precond.h, int(variant), int(iters),
-                                             float(tol), float(shift),
-                                             None if bb is None else bb.ctypes.data_as(nat.c_int_p),
+                                             float(tol), float(shift), _bounds_arg(bounds),
                                              b.ctypes.data_as(C.c_void_p), x.ctypes.data_as(C.c_void_p),
                                              hist.ctypes.data_as(nat.c_double_p), info.ctypes.data_as(nat.c_int_p),
                                              C.byref(ms)), "spmv_hip_csr_minres")
@@ -588,10 +564,7 @@ class CsrDevice(_Handle):
         k = int(k)
         if self.M < 4 * k:
             raise ValueError(f"lobpcg needs n >= 4 k = {4 * k}, got n = {self.M}")
-        if int(iters) < 0:
-            raise ValueError(f"iters must be >= 0, got {iters}")
-        if not float(tol) >= 0.0 or not np.isfinite(float(tol)):
-            raise ValueError(f"tol must be finite and >= 0, got {tol}")
+        _check_iters_tol(iters, tol)
         if precond is not None:
             self._check_precond(precond)
             if precond.kind in (PRECOND_SSOR, PRECOND_ILU0):
@@ -628,19 +601,12 @@ class CsrDevice(_Handle):
         is not part of ms).  Stops once s.s <= tol^2 times the initial s.s (tol = 0: only at exactly 0; tol > 0 also
         ends the loop early), or at a breakdown.  Returns (x (N), s.s history (iters + 1), r.r history (iters + 1),
         info {"steps", "status" (CGLS_*)}, ms)."""
-        b = np.asarray(b)
-        if b.dtype != self.dtype:
-            raise ValueError(f"b has dtype {b.dtype}, the handle holds {np.dtype(self.dtype)}")
-        if b.ndim != 1 or b.shape[0] != self.M:
-            raise ValueError(f"b must be a vector of {self.M} values, got shape {b.shape}")
-        if int(iters) < 0:
-            raise ValueError(f"iters must be >= 0, got {iters}")
-        for name, v in (("tol", tol), ("damp", damp)):
-            if not float(v) >= 0.0 or not np.isfinite(float(v)):
-                raise ValueError(f"{name} must be finite and >= 0, got {v}")
+        b = _check_vector(b, self.M, self.dtype, "b", "handle")
+        _check_iters_tol(iters, tol)
+        if not float(damp) >= 0.0 or not np.isfinite(float(damp)):
+            raise ValueError(f"damp must be finite and >= 0, got {damp}")
         if at is not None and not isinstance(at, CsrDevice):
             raise ValueError("at must be a CsrDevice holding the transpose")
-        b = np.ascontiguousarray(b)
         own = at is None
         if own:
             at = self.transpose()
@@ -755,6 +721,20 @@ def lobpcg_update(n, k, nb, d_S, d_AS, Cm, Cp, d_X, d_P, d_AX, d_AP):
                                             Cm.ctypes.data_as(nat.c_double_p), Cp.ctypes.data_as(nat.c_double_p),
                                             C.c_void_p(d_X), C.c_void_p(d_P), C.c_void_p(d_AX), C.c_void_p(d_AP)),
            "spmv_hip_lobpcg_update")
+
+
+def _bounds_arg(bounds):
+    """The row bounds of the ranks as the int pointer a solver entry takes; None (no communicator) stays None"""
+    if bounds is None:
+        return None
+    return np.ascontiguousarray(bounds, dtype=np.int32).ctypes.data_as(nat.c_int_p)  # (the pointer keeps the array)
+
+
+def _check_iters_tol(iters, tol, finite=True):
+    if int(iters) < 0:
+        raise ValueError(f"iters must be >= 0, got {iters}")
+    if not float(tol) >= 0.0 or finite and not np.isfinite(float(tol)):
+        raise ValueError(f"tol must be {'finite and ' if finite else ''}>= 0, got {tol}")
 
 
 def _check_vector(v, rows, dtype, name, owner):
