@@ -1,6 +1,7 @@
 """Sparse triangular solves and the SSOR / ILU(0) preconditioners without a GPU: the entry points are exported, declared
 and bound, the enums match the header, the Python methods check their input before any device call, the host analysis
-(colouring, levels, launch plan) matches a Python restatement, and the new kernels compile for gfx950 without scratch."""
+(colouring, levels, launch plan) matches a Python restatement, also at the exact long-row length and chain limits, and
+the new kernels compile for gfx950 without scratch."""
 import ctypes as C
 import os
 import re
@@ -78,6 +79,61 @@ def grid5(g, shift=0.0):
     return (sps.kron(sps.eye(g), t) + sps.kron(t, sps.eye(g))).tocsr()
 
 
+def lanes_ref(t):
+    """tri_upload's rule for a strict triangle t: the lanes per short row, from the mean row shorter than kTrsvLong"""
+    k = np.diff(t.indptr)
+    k = k[k < LONG_LEN]
+    mean = float(k.sum()) / len(k) if len(k) else 0.0
+    G = 1
+    while G < 32 and 2 * G < mean:
+        G *= 2
+    return G
+
+
+def layered(lengths, rng):
+    """A strictly lower triangular 0 / 1 pattern built level by level (test_gpu_trsv_edges.py uses it too).  lengths[l]
+    holds the entries of each row of level l; the rows of a level are neighbours, level 0 comes first and its rows are
+    empty.  A row of k entries in level l >= 1 reads a run of k neighbouring earlier rows (cyclic over all of them) that
+    ends at a row of level l - 1 drawn by rng: its level, its length and every level's width are known by construction,
+    without a loop over the rows."""
+    import scipy.sparse as sps
+    start = np.concatenate([[0], np.cumsum([len(k) for k in lengths])]).astype(np.int64)
+    rows, cols = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)]
+    for l, k in enumerate(lengths):
+        k = np.asarray(k, np.int64)
+        if l == 0:
+            assert np.all(k == 0), "a row without entries is in the first level, and only there"
+            continue
+        assert np.all(k >= 1) and np.all(k <= start[l]), (l, int(k.min()), int(k.max()), int(start[l]))
+        last = rng.integers(start[l - 1], start[l], len(k))
+        j = np.arange(int(k.sum())) - np.repeat(np.cumsum(k) - k, k)
+        rows.append(np.repeat(np.arange(start[l], start[l + 1]), k))
+        cols.append((np.repeat(last, k) - j) % start[l])
+    rows, cols = np.concatenate(rows), np.concatenate(cols)
+    n = int(start[-1])
+    s = sps.csr_matrix((np.ones(len(rows)), (rows, cols)), shape=(n, n))
+    s.sort_indices()
+    assert s.nnz == len(rows)
+    return s
+
+
+def mirrored(s):
+    """s with rows and columns reversed: a strict lower triangle becomes a strict upper one of the same levels"""
+    import scipy.sparse as sps
+    c = s.tocoo()
+    n = s.shape[0]
+    m = sps.csr_matrix((c.data, (n - 1 - c.row, n - 1 - c.col)), shape=s.shape)
+    m.sort_indices()
+    return m
+
+
+def both_sides(lengths, rng):
+    """layered(lengths) below the diagonal, its mirror image above, ones on the diagonal"""
+    import scipy.sparse as sps
+    s = layered(lengths, rng)
+    return (s + mirrored(s) + sps.eye(s.shape[0])).tocsr()
+
+
 def ip(a):
     return np.ascontiguousarray(a, np.int32).ctypes.data_as(nat.c_int_p)
 
@@ -120,6 +176,25 @@ def analysis_cases():
     arrow[0, :], arrow[:, 0], arrow[699, :], arrow[:, 699] = 1.0, 1.0, 1.0, 1.0
     yield "arrow", arrow.tocsr()
     yield "random", (sps.random(900, 900, density=0.01, random_state=rng) + sps.eye(900)).tocsr()
+    yield "split edges", both_sides(SPLIT_EDGES, np.random.default_rng(1))
+    yield "chain edges", both_sides(CHAIN_EDGES, np.random.default_rng(2))
+
+
+def rows_of(*pairs):
+    """lengths of one level: (count, length), ... in this order"""
+    return np.concatenate([np.full(c, k) for c, k in pairs])
+
+
+# rows of LONG_LEN - 1 and LONG_LEN entries: mixed in one level (the split inside), a level of short rows only (the
+# split at its end), a level of long rows only (the split at its start)
+SPLIT_EDGES = [rows_of((300, 0)), rows_of((1, 128), (2, 127), (1, 129), (1, 1), (2, 128), (1, 127)), rows_of((5, 127)),
+               rows_of((4, 128)), rows_of((1, 127), (1, 128))]
+SPLIT_EDGES_FIRST_LONG = [300, 4, 5, 0, 1]     # short rows ahead of each level's first long row
+# levels of CHAIN_ROWS and CHAIN_ROWS + 1 rows, of CHAIN_ENTRIES and CHAIN_ENTRIES + 1 entries, and both limits at once
+CHAIN_EDGES = [rows_of((256, 0)), rows_of((257, 1)), rows_of((256, 16)), rows_of((255, 16), (1, 17)), rows_of((64, 64)),
+               rows_of((63, 64), (1, 65)), rows_of((32, 128)), rows_of((31, 128), (1, 129)), rows_of((3, 2)),
+               rows_of((256, 16))]
+CHAIN_EDGES_PLAN = [[1, 0, 1], [0, 1, 2], [1, 2, 3], [0, 3, 4], [1, 4, 5], [0, 5, 6], [1, 6, 7], [0, 7, 8], [1, 8, 10]]
 
 
 # ---------------------------------------------------------------- exported, declared, bound
@@ -224,6 +299,51 @@ def test_levels_permutation_and_plan_match_the_restatement(name, a):
         assert got["levels"] == n and got["launches"] == 1
     if name == "arrow":
         assert np.max(length) >= LONG_LEN      # the long-row side of the split is exercised
+
+
+@pytest.mark.parametrize("lower", [True, False])
+def test_long_row_split_at_the_exact_length(lower):
+    """rows of 127 entries are short, rows of 128 long; the split sits inside a level, at its end and at its start, and
+    the places of a level keep the row order on either side of it"""
+    import scipy.sparse as sps
+    a = both_sides(SPLIT_EDGES, np.random.default_rng(1))
+    got = host_levels(a, lower)
+    t = (sps.tril(a, -1) if lower else sps.triu(a, 1)).tocsr()
+    length = np.diff(t.indptr)
+    sizes = [len(k) for k in SPLIT_EDGES]
+    assert got["levels"] == len(SPLIT_EDGES) and np.diff(got["level_ptr"]).tolist() == sizes
+    assert (got["split"] - got["level_ptr"][:-1]).tolist() == SPLIT_EDGES_FIRST_LONG
+    for l, (p0, ps, p1) in enumerate(zip(got["level_ptr"][:-1], got["split"], got["level_ptr"][1:])):
+        assert np.all(length[got["perm"][p0:ps]] < LONG_LEN) and np.all(length[got["perm"][ps:p1]] >= LONG_LEN), l
+        assert np.all(np.diff(got["perm"][p0:ps]) > 0) and np.all(np.diff(got["perm"][ps:p1]) > 0), l
+        assert sorted(length[got["perm"][p0:p1]].tolist()) == sorted(SPLIT_EDGES[l].tolist()), l
+    assert np.array_equal(got["level"], levels_ref(a, lower)) and got["entries"] == t.nnz
+    assert lanes_ref(t) == 2    # 310 short rows, 1144 entries: a mean of 3.7 (the long rows do not count)
+
+
+@pytest.mark.parametrize("lower", [True, False])
+def test_chain_limits_at_the_exact_counts(lower):
+    """a level of 256 rows or 4096 entries is narrow, one of 257 rows or 4097 entries is wide, whatever its rows are
+    made of (32 long rows of 128 entries are a narrow level); narrow neighbours share a launch"""
+    import scipy.sparse as sps
+    a = both_sides(CHAIN_EDGES, np.random.default_rng(2))
+    got = host_levels(a, lower)
+    t = (sps.tril(a, -1) if lower else sps.triu(a, 1)).tocsr()
+    level = levels_ref(a, lower)
+    assert np.array_equal(got["level"], level)
+    assert np.bincount(level)[1:].tolist() == [len(k) for k in CHAIN_EDGES]
+    assert np.bincount(level, weights=np.diff(t.indptr))[1:].tolist() == [int(k.sum()) for k in CHAIN_EDGES]
+    assert got["plan"] == CHAIN_EDGES_PLAN == plan_ref(t, level) and got["launches"] == len(CHAIN_EDGES_PLAN)
+    assert got["widest"] == 257
+    assert (got["split"] - got["level_ptr"][:-1]).tolist() == [256, 257, 256, 256, 64, 64, 0, 0, 3, 256]
+
+
+@pytest.mark.parametrize("mean,expect", [(1.0, 1), (2.0, 1), (2.5, 2), (4.0, 2), (8.0, 4), (16.0, 8), (32.0, 16),
+                                         (32.5, 32), (63.5, 32)])
+def test_lanes_restatement(mean, expect):
+    """the restated rule on two-level patterns of a known mean: 128 empty rows and 128 of twice the mean"""
+    t = layered([np.zeros(128, int), np.full(128, int(2 * mean))], np.random.default_rng(0))
+    assert lanes_ref(t) == expect
 
 
 @pytest.mark.parametrize("g", [7, 64])
