@@ -660,6 +660,84 @@ int spmv_hip_csr_precond_build_fsai(const spmv_csr_dev *m, int cap, spmv_precond
 int spmv_hip_precond_fsai_info(const spmv_precond *P, int *info);
 int spmv_fsai_plan(int n, const int *row_ptr, const int *col, const double *val, int cap, int *g_ptr, int *g_col,
                    int *width_ptr, int *width_rows, long long *counts);
+/* Smoothed-aggregation algebraic multigrid (Vanek, Mandel and Brezina) of the handle's own diagonal block, one V(1,1)
+ * cycle per apply (the same spmv_precond type: info (block = 1), apply, apply_on, apply_multi, apply_multi_on, free;
+ * spmv_hip_csr_pcg, _pbicgstab, _minres, _pcg_multi and _lobpcg take it).  On a row-range handle this is the AMG of the
+ * diagonal block: across ranks, block-Jacobi of AMG.  fp64 and fp32 CSR handles.
+ * The setup runs on the host in fp64 on the canonical block (local columns, sorted rows, repeats added in entry order):
+ * level l holds A_l with n_l rows and d_i = a_ii, A_0 is the block.
+ *   1. every d_i must be present, finite and > 0 (else -1; level 0 names the row, deeper levels the level)
+ *   2. rho_l = max_i (sum_j |a_ij|) / d_i, the Gershgorin bound of D^-1 A, in stored order; w_l = 4 / (3 rho_l): the
+ *      damped Jacobi sweep x += w D^-1 (b - A x) converges for SPD A without an eigenvalue estimate
+ *   3. n_l <= coarse_rows: the DIRECT coarsest level, its dense inverse by Gauss-Jordan with partial pivoting in fp64
+ *      (a zero or non-finite pivot: -1 with the level)
+ *   4. l + 1 == max_levels: the SMOOTH coarsest level
+ *   5. an off-diagonal (i, j) is strong when a_ij != 0 and |a_ij| >= theta sqrt(d_i d_j); the strength graph has an
+ *      edge when either direction is strong; neighbours in ascending order
+ *   6. aggregation in three passes in row order: (a) a row with a neighbour, itself and all neighbours unaggregated,
+ *      starts an aggregate of itself and them; (b) a row still unaggregated joins the aggregate, as it stood after (a),
+ *      of its first neighbour that had one; (c) a row still unaggregated with a neighbour starts an aggregate and takes
+ *      its unaggregated neighbours along.  Rows without neighbours are in no aggregate: they are only smoothed.
+ *   7. na aggregates; na == 0 or 10 na > 9 n_l (a stall): the SMOOTH coarsest level
+ *   8. T (n_l x na) has T[i, agg(i)] = 1; P_l = T - diag(w_l / d_i) A_l T on the pattern of A_l T (entries that cancel
+ *      stay); R_l = P_l^T; A_{l+1} = R_l (A_l P_l); every sum in fp64 in ascending column order
+ * theta in [0, 1), coarse_rows in [1, 256], max_levels in [1, 16].
+ * The apply, with b the right-hand side of level l and g = w_l / d (d as the device holds it, g kept in fp64):
+ *   not coarsest:  x = g.b;  r = b - A x;  b' = R r;  e = cycle(l + 1, b');  x = x + P e;  x' = x + g.(b - A x)
+ *   DIRECT:        x = Ainv b
+ *   SMOOTH:        x = g.b;  x' = x + g.(b - A x)
+ * Every row's value is accumulated in double in a fixed order and rounded once to the handle's dtype on store; level
+ * vectors are of the handle's dtype; no atomics; the second sweep writes a second vector.  Two applies, and two builds,
+ * give the same bits.  M is symmetric positive definite for SPD A up to that rounding.
+ * On the device level 0 is P's own upload of the canonical block (an ordinary handle: A_0 x runs through its AUTO launch,
+ * for k vectors through spmv_hip_csr_spmm_on) plus three fused vector passes; every P_l, R_l, A_l (l > 0) and Ainv is a
+ * plain CSR array of P's, rounded once to the handle's dtype, run by one row kernel (amg_kernels.hpp: G lanes per row, G a
+ * power of two <= 32 from the operator's mean row).  With chain != 0 everything from the first level l > 0 with at most
+ * 256 rows and 4096 entries of A_l down to the coarsest and back is ONE launch of one workgroup (a single-level DIRECT
+ * hierarchy is that one launch); chain = 0 launches every pass on its own and gives the same bits.  No kernel waits for
+ * another workgroup.  P owns its level vectors for one right-hand side, so one P serves one stream at a time; it may
+ * outlive the handle.  r and z must not overlap.  The launches do not look at a solver's stop state: after a stop they
+ * rewrite z with the bits it holds.
+ * For k right-hand sides the same kernels walk row-major n_l x k arrays, a group keeping 4 columns in registers per
+ * walk of the row; column j's sums do not depend on j or k.  The level vectors then live in the caller's d_work:
+ *   spmv_hip_precond_work_bytes      *bytes = what spmv_hip_precond_apply_multi_on needs in d_work for k columns: 0 for
+ *                                    Jacobi and block-Jacobi, rows x k values (at least 16 bytes) and a 128-byte line
+ *                                    for FSAI, the sum of the level vectors for AMG (every vector n_l rounded up to 32 rows
+ *                                    plus 32 rows, times k values; the part behind a vector's values should be zero:
+ *                                    the x-window kernels read whole 128-byte lines); -1 for SSOR and ILU(0)
+ *   spmv_hip_csr_precond_build_amg   -1 (*out stays NULL, the HIP error state stays clean, the handle still works): the
+ *                                    refusals above, a parameter out of range, a non-square or tiles-only handle
+ *   spmv_hip_precond_amg_info        info[SPMV_PRECOND_AMG_INFO_WORDS] = levels, the first chained level (-1: none),
+ *                                    launches per apply, the coarsest kind (SPMV_AMG_DIRECT / _SMOOTH), operator
+ *                                    complexity x 1000 (sum of entries of A_l / entries of A_0), microseconds of
+ *                                    download with canonical rows, of the host setup, of the uploads, chain, then
+ *                                    rows[16] and entries of A_l[16] per level (0 beyond the last)
+ *   spmv_hip_precond_amg_level       what the device holds of level `level`: which = SPMV_AMG_A, _P, _R or _INV (the
+ *                                    dense inverse of a DIRECT level as n_l rows of n_l entries), values of the handle's
+ *                                    dtype; scalars[5] = w_l, rho_l, the kind (SPMV_AMG_NOT_COARSEST, _DIRECT, _SMOOTH),
+ *                                    n_l, the aggregates.  row_ptr = NULL: scalars alone; col = val = NULL: row_ptr
+ *                                    (n_l + 1 entries; R: aggregates + 1) and scalars; else all.
+ *   spmv_amg_plan_build / _levels / _level / _free / _error   the host setup alone (no device needed) on canonical rows
+ *                                    (ascending columns in [0, n) without repeats, else -1): the same reader in fp64,
+ *                                    with which = SPMV_AMG_T as well; _error is the message of this thread's last -1. */
+enum { SPMV_PRECOND_AMG = 6 };
+enum { SPMV_PRECOND_AMG_INFO_WORDS = 41 };
+enum { SPMV_AMG_A = 0, SPMV_AMG_P = 1, SPMV_AMG_R = 2, SPMV_AMG_INV = 3, SPMV_AMG_T = 4 };
+enum { SPMV_AMG_NOT_COARSEST = 0, SPMV_AMG_DIRECT = 1, SPMV_AMG_SMOOTH = 2 };
+typedef struct spmv_amg_plan spmv_amg_plan;
+int spmv_amg_plan_build(int n, const int *row_ptr, const int *col, const double *val, double theta, int coarse_rows,
+                        int max_levels, spmv_amg_plan **out);
+int spmv_amg_plan_levels(const spmv_amg_plan *plan);
+int spmv_amg_plan_level(const spmv_amg_plan *plan, int level, int which, int *row_ptr, int *col, double *val,
+                        double *scalars);
+void spmv_amg_plan_free(spmv_amg_plan *plan);
+const char *spmv_amg_plan_error(void);
+int spmv_hip_csr_precond_build_amg(const spmv_csr_dev *m, double theta, int coarse_rows, int max_levels, int chain,
+                                   spmv_precond **out);
+int spmv_hip_precond_amg_info(const spmv_precond *P, int *info);
+int spmv_hip_precond_amg_level(const spmv_precond *P, int level, int which, int *row_ptr, int *col, void *val,
+                               double *scalars);
+int spmv_hip_precond_work_bytes(const spmv_precond *P, int k, long long *bytes);
 /* Preconditioned CG for a symmetric positive definite A and M, x0 = 0 (P = NULL: M = I, z is r itself):
  *   r = b, z = M^-1 r, p = z, rz = r.z, rr0 = r.r
  *   each step: q = A p, alpha = rz / p.q, x += alpha p, r -= alpha q, z = M^-1 r, rz' = r.z, rr = r.r,
@@ -684,9 +762,9 @@ int spmv_hip_csr_pcg(spmv_csr_dev *m, const spmv_precond *P, int variant, int it
  * in the layout of spmv_hip_csr_cg_multi.  B, X and every loop vector are row-major n x k; the product is
  * spmv_hip_csr_spmm_on on library-owned P (N x k) and Q (M_total x k).  The communicator, the bounds scaled by k, the
  * all-gatherv of P and the dot products added in rank order are those of spmv_hip_csr_cg_multi.
- * P: NULL, JACOBI, BLOCK_JACOBI or FSAI.  Jacobi is fused into the x / r update with both dots; a block-Jacobi apply is
- * a pass of its own that makes the dots; an FSAI apply is Z = G^T (G R), two SpMMs through P's handles, then one pass for
- * the dots.  SSOR and ILU0 are refused: their triangular solves take one right-hand side.
+ * P: NULL, JACOBI, BLOCK_JACOBI, FSAI or AMG.  Jacobi is fused into the x / r update with both dots; a block-Jacobi apply is
+ * a pass of its own that makes the dots; an FSAI apply is Z = G^T (G R), two SpMMs through P's handles, an AMG apply its
+ * V-cycle on k columns, then one pass for the dots.  SSOR and ILU0 are refused: their triangular solves take one right-hand side.
  * Column j's sums add in an order that does not depend on j: permuting the columns of B permutes X, both histories,
  * steps and status bit for bit, and two calls give the same bits.  k = 1 gives spmv_hip_csr_pcg's bits (variant
  * SPMV_CSR_AUTO); P = NULL gives spmv_hip_csr_cg_multi's X and history while no column breaks down.
@@ -710,7 +788,7 @@ int spmv_hip_csr_pcg(spmv_csr_dev *m, const spmv_precond *P, int variant, int it
  *                                    is not touched.  The Jacobi and block-Jacobi kernels move 16-byte pieces of a
  *                                    row when k values are whole pieces AND d_R and d_Z are 16-byte aligned; else they
  *                                    move single elements (the same bits, more instructions).  -1: k outside [1, 64],
- *                                    arrays not aligned to the element size, FSAI without d_work, SSOR or ILU0.
+ *                                    arrays not aligned to the element size, FSAI or AMG without d_work, SSOR or ILU0.
  *   spmv_hip_precond_apply_multi     the same on host arrays of rows x k values: allocates, copies, syncs */
 int spmv_hip_csr_pcg_multi(spmv_csr_dev *m, const spmv_precond *P, int k, int iters, double tol, const int *bounds,
                            const void *B_host, void *X_host, double *rr_hist, double *rz_hist, int *steps, int *status,
@@ -765,7 +843,7 @@ int spmv_hip_csr_minres(spmv_csr_dev *m, const spmv_precond *P, int variant, int
                         const int *bounds, const void *b_host, void *x_host, double *rr_hist, int *info,
                         float *ms_total);
 /* LOBPCG (Knyazev 2001) for the k smallest (largest = 0) or largest eigenpairs of a symmetric A held by an fp64 CSR
- * handle, with an optional symmetric positive definite preconditioner (Jacobi, block-Jacobi or FSAI; smallest only).
+ * handle, with an optional symmetric positive definite preconditioner (Jacobi, block-Jacobi, FSAI or AMG; smallest only).
  * Six row-major n x k arrays X, W, P, AX, AW, AP (element (i, j) at i k + j, the SpMM's layout).  Per step one SpMM
  * (spmv_hip_csr_spmm_on), one k-wide apply (spmv_hip_precond_apply_multi_on), a Gram pass and an update pass over the
  * basis S = [X | W | P], AS = [AX | AW | AP] (lobpcg_kernels.hpp), and a Rayleigh-Ritz step on the host.

@@ -246,6 +246,17 @@ _PROTOTYPES = {
     "spmv_hip_precond_fsai_info": (C.c_int, [C.c_void_p, c_int_p]),
     "spmv_fsai_plan": (C.c_int, [C.c_int, c_int_p, c_int_p, c_double_p, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p,
                                  C.POINTER(C.c_longlong)]),
+    "spmv_amg_plan_build": (C.c_int, [C.c_int, c_int_p, c_int_p, c_double_p, C.c_double, C.c_int, C.c_int,
+                                      C.POINTER(C.c_void_p)]),
+    "spmv_amg_plan_levels": (C.c_int, [C.c_void_p]),
+    "spmv_amg_plan_level": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_int_p, c_double_p, c_double_p]),
+    "spmv_amg_plan_free": (None, [C.c_void_p]),
+    "spmv_amg_plan_error": (C.c_char_p, []),
+    "spmv_hip_csr_precond_build_amg": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int,
+                                                 C.POINTER(C.c_void_p)]),
+    "spmv_hip_precond_amg_info": (C.c_int, [C.c_void_p, c_int_p]),
+    "spmv_hip_precond_amg_level": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_int_p, C.c_void_p, c_double_p]),
+    "spmv_hip_precond_work_bytes": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_longlong)]),
     "spmv_hip_csr_pcg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, c_int_p, C.c_void_p,
                                    C.c_void_p, c_double_p, c_double_p, c_int_p, c_float_p]),
     "spmv_hip_csr_pcg_multi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, c_int_p, C.c_void_p,

@@ -184,6 +184,7 @@ struct spmv_precond {
     void *inv = nullptr;      // ceil(rows / block) * block^2 values of that dtype (layout above); owned
     struct spmv_tri_precond *tri = nullptr;  // SSOR / ILU0: the two triangular solves (spmv_trsv.hip); owned, inv is NULL
     struct spmv_fsai_precond *fsai = nullptr;  // FSAI: the handles of G and G^T (spmv_fsai.hip); owned, inv is NULL
+    struct spmv_amg_precond *amg = nullptr;    // AMG: the hierarchy and its level vectors (spmv_amg.hip); owned, inv is NULL
 };
 
 // spmv_trsv.hip: z = M^-1 r by P's two solves on stream s (flags as pc_apply: a stopped solver's launches return)
@@ -196,12 +197,36 @@ int precond_fsai_apply(const spmv_precond *P, const void *r, void *z, hipStream_
 int precond_fsai_apply_multi(const spmv_precond *P, int k, const void *R, void *Z, void *work, hipStream_t s);
 void precond_fsai_free(struct spmv_fsai_precond *fp);
 int precond_fsai_factors(const spmv_precond *P, int which, int *row_ptr, int *col, void *val);
+// spmv_amg.hip: z = one V(1,1) cycle on r by P's own launches on stream s, the level vectors P's own (as FSAI's, they do
+// not look at a solver's flags)
+int precond_amg_apply(const spmv_precond *P, const void *r, void *z, hipStream_t s);
+// the same for rows x k row-major R and Z; work: precond_amg_work_values(P) * k values (the level vectors; the part
+// behind each vector's values zero), P's own vectors are not used
+int precond_amg_apply_multi(const spmv_precond *P, int k, const void *R, void *Z, void *work, hipStream_t s);
+long long precond_amg_work_values(const spmv_precond *P);
+void precond_amg_free(struct spmv_amg_precond *ap);
 
-// SSOR, ILU(0) and FSAI take a path of their own wherever Jacobi / block-Jacobi are told apart by P->block: an apply
-// through P's own launches (precond_own_apply), then one pass for whatever dots the solver needs
-inline bool precond_has_own_apply(const spmv_precond *P) { return P && (P->tri != nullptr || P->fsai != nullptr); }
+// SSOR, ILU(0), FSAI and AMG take a path of their own wherever Jacobi / block-Jacobi are told apart by P->block: an
+// apply through P's own launches (precond_own_apply), then one pass for whatever dots the solver needs
+inline bool precond_has_own_apply(const spmv_precond *P) {
+    return P && (P->tri != nullptr || P->fsai != nullptr || P->amg != nullptr);
+}
 inline int precond_own_apply(const spmv_precond *P, const void *r, void *z, const int *flags, hipStream_t s) {
-    return P->fsai ? precond_fsai_apply(P, r, z, s) : precond_tri_apply(P, r, z, flags, s);
+    return P->amg ? precond_amg_apply(P, r, z, s) : P->fsai ? precond_fsai_apply(P, r, z, s)
+                                                             : precond_tri_apply(P, r, z, flags, s);
+}
+// FSAI and AMG apply to k vectors through products alone; both need a workspace of precond_work_bytes(P, k)
+inline bool precond_has_own_apply_multi(const spmv_precond *P) { return P && (P->fsai != nullptr || P->amg != nullptr); }
+inline int precond_own_apply_multi(const spmv_precond *P, int k, const void *R, void *Z, void *work, hipStream_t s) {
+    return P->amg ? precond_amg_apply_multi(P, k, R, Z, work, s) : precond_fsai_apply_multi(P, k, R, Z, work, s);
+}
+// bytes of that workspace for k columns: 0 for Jacobi and block-Jacobi, FSAI's G R with a line tail, the level vectors
+// of AMG; -1 for SSOR and ILU(0), which have no k-wide apply
+inline long long precond_work_bytes(const spmv_precond *P, int k) {
+    if (P->tri) return -1;
+    if (P->amg) return std::max<long long>(precond_amg_work_values(P) * k * P->value_bytes, 16);
+    if (P->fsai) return std::max<long long>((long long)P->rows * k * P->value_bytes, 16) + kLineBytes;
+    return 0;
 }
 
 // z = M^-1 r on P's rows (r, z at local row 0) on stream s; flags / part as pc_apply; grid 0: by the row count

@@ -16,8 +16,8 @@
 // (library-owned, all-gathered in place of p and s), x moves along them, and r stays the true residual.  Jacobi is
 // fused into the s and p updates (bcg_jac_update_s / _p, with D^-1 copied to global row indexing so the 16-byte pieces
 // line up); a block-Jacobi apply is a pc_apply pass after bcg_update_s / bcg_update_p, an SSOR or ILU(0) apply its two
-// triangular solves (spmv_trsv.hip) in the same place, an FSAI apply its two SpMVs (spmv_fsai.hip).  P = NULL takes the
-// unpreconditioned path: exactly csr_bicgstab's launches.
+// triangular solves (spmv_trsv.hip) in the same place, an FSAI apply its two SpMVs (spmv_fsai.hip), an AMG apply its
+// V-cycle (spmv_amg.hip).  P = NULL takes the unpreconditioned path: exactly csr_bicgstab's launches.
 #include "spmv_internal.hpp"
 
 #include "bicgstab_kernels.hpp"

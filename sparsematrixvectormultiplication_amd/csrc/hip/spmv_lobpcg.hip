@@ -107,7 +107,7 @@ int lob_hook_check(long long n, int k, int nb, const void *const *S, const void 
 struct LobBuffers {
     double *X, *W, *P, *AX, *AW, *AP;
     double *R;     // with a preconditioner: the residual, W is M^-1 R
-    void *work;    // FSAI's G R
+    void *work;    // FSAI's G R, AMG's level vectors
     double *theta, *coef, *res_part, *res_sum, *gram_part, *gram_out, *an_part, *an_out;
 };
 
@@ -235,7 +235,7 @@ int lob_body(spmv_csr_dev *m, const spmv_precond *pc, int k, int iters, double t
     b.AW = scope.alloc<double>(vec_bytes);
     b.AP = scope.alloc<double>(vec_bytes);
     b.R = pc ? scope.alloc<double>(vec_bytes) : nullptr;
-    b.work = pc && pc->fsai ? scope.alloc(vec_bytes) : nullptr;
+    b.work = precond_has_own_apply_multi(pc) ? scope.alloc((size_t)precond_work_bytes(pc, k)) : nullptr;
     b.theta = scope.alloc<double>(kLobMaxK * sizeof(double));
     b.coef = scope.alloc<double>((size_t)2 * 48 * kLobMaxK * sizeof(double));
     b.res_part = scope.alloc<double>((size_t)kMcgBlocks * kLobMaxK * sizeof(double));

@@ -17,7 +17,7 @@
 //   TRI     x += alpha p, r -= alpha q (6), then SSOR's / ILU(0)'s two solves (spmv_trsv.hip), then pcg_dots: r.r and
 //           r.z by the walk and the fold of the other modes (2 more reads); the solves' last kernel is a level of a few
 //           rows, so the dots are a pass of their own rather than fused into it; FSAI's two SpMVs (spmv_fsai.hip) take
-//           the same path: its launches are the handles' own, which make no dots
+//           the same path: its launches are the handles' own, which make no dots; so does AMG's V-cycle (spmv_amg.hip)
 //
 // pcg_dot (p.q, 2 values) and pcg_update_p (p = z + beta p, 3) complete the step: fp64 Jacobi PCG moves 13 values =
 // 104 B per row against csr_cg's 11 (88 B).  The scalars and the stop state never leave the device; after a stop the

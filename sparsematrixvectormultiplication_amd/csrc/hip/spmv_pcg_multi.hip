@@ -14,6 +14,7 @@
 //   JACOBI  the same with z = D^-1 r fused in, partials of r.r and r.z
 //   BLOCK   x += alpha p, r -= alpha q, then mpc_apply: Z = M^-1 R with the partials of r.r and r.z
 //   FSAI    x += alpha p, r -= alpha q, then Z = G^T (G R), two SpMMs through P's handles, then mpcg_dots
+//   AMG     the same with Z = one V(1,1) cycle on R (spmv_amg.hip), then mpcg_dots
 //
 // SSOR and ILU(0) are refused: their triangular solves take one right-hand side.  Every column carries its own scalars,
 // stop state, steps and status on the device; a stopped column still rides in the SpMMs and keeps x, r, z and p.
@@ -24,7 +25,9 @@
 namespace {
 
 // the mode of mpcg_update_x_r: block-Jacobi and FSAI apply after it
-int mpcg_mode(const spmv_precond *P) { return !P ? kMpcgNone : !P->fsai && P->block == 1 ? kMpcgJacobi : kMpcgApply; }
+int mpcg_mode(const spmv_precond *P) {
+    return !P ? kMpcgNone : !precond_has_own_apply(P) && P->block == 1 ? kMpcgJacobi : kMpcgApply;
+}
 
 // SSOR / ILU(0): -1 with a message naming `what`
 int mpcg_refuse_tri(const spmv_precond *P, const char *what) {
@@ -46,7 +49,7 @@ void mpc_launch(const spmv_precond *P, int k, const void *R, void *Z, const int 
 template <typename T>
 int mpc_apply_on(const spmv_precond *P, int k, const void *R, void *Z, void *work, hipStream_t s) {
     if (!P->rows) return 0;
-    if (P->fsai) return precond_fsai_apply_multi(P, k, R, Z, work, s);
+    if (precond_has_own_apply_multi(P)) return precond_own_apply_multi(P, k, R, Z, work, s);
     constexpr int W = 16 / sizeof(T);
     const bool wide = (size_t)k * sizeof(T) % 16 == 0 && (((uintptr_t)R | (uintptr_t)Z) & 15) == 0;
     const int grid = solver_grid(kMcgBlocks, P->rows, kBlock >> mcg_column_lanes(k, wide ? W : 1));
@@ -65,7 +68,7 @@ int mpc_apply_check(const spmv_precond *P, int k, const void *R, const void *Z, 
 }
 
 struct MpcgBuffers {
-    void *P, *Q, *X, *R, *Z, *work;  // Z is R without a preconditioner; work: FSAI's G R
+    void *P, *Q, *X, *R, *Z, *work;  // Z is R without a preconditioner; work: FSAI's G R, AMG's level vectors
     double *s, *part_rr, *part_rz, *gath, *hrr, *hrz;
     int *flags;
 };
@@ -95,11 +98,11 @@ int mpcg_run(spmv_csr_dev *m, const spmv_precond *pc, int k, int iters, double t
     auto reduce_dots = [&] { return reduce(b.part_rr, kMpcgRrNew) || (!z_is_r && reduce(b.part_rz, kMpcgRzNew)); };
     // after the x / r update of the modes that do not fuse their apply: Z = M^-1 R and the two sets of partials
     auto apply_dots = [&](const int *flags) {
-        if (!pc->fsai) {
+        if (!precond_has_own_apply_multi(pc)) {
             mpc_launch<T, V, true>(pc, k, R, Z, flags, b.part_rr, b.part_rz, grid, g_stream);
             return 0;
         }
-        if (precond_fsai_apply_multi(pc, k, R, Z, b.work, g_stream)) return -1;
+        if (precond_own_apply_multi(pc, k, R, Z, b.work, g_stream)) return -1;
         hipLaunchKernelGGL((mpcg_dots<T, V>), g, blk, 0, g_stream, n, k, cl, (const T *)R, (const T *)Z, b.part_rr, b.part_rz);
         return 0;
     };
@@ -167,7 +170,7 @@ int mpcg_body(spmv_csr_dev *m, const spmv_precond *pc, int k, int iters, double 
     b.X = scope.alloc(q_bytes);
     b.R = scope.alloc(r_bytes);
     b.Z = pc ? scope.alloc(r_bytes) : b.R;
-    b.work = pc && pc->fsai ? scope.alloc(r_bytes) : nullptr;
+    b.work = precond_has_own_apply_multi(pc) ? scope.alloc((size_t)precond_work_bytes(pc, k)) : nullptr;
     b.s = scope.alloc<double>(kMpcgSlots * kMcgMaxK * sizeof(double));
     b.part_rr = scope.alloc<double>((size_t)2 * kMcgBlocks * kMcgMaxK * sizeof(double));
     b.part_rz = b.part_rr ? b.part_rr + (size_t)kMcgBlocks * kMcgMaxK : nullptr;
@@ -222,6 +225,8 @@ extern "C" int spmv_hip_precond_apply_multi_on(const spmv_precond *P, int k, con
     if (mpc_apply_check(P, k, d_R, d_Z, "precond_apply_multi_on")) return -1;
     if (P->fsai && P->rows && !d_work)
         return fail("precond_apply_multi_on: an FSAI apply needs d_work (rows x k values and one 128-byte line)");
+    if (P->amg && P->rows && !d_work)
+        return fail("precond_apply_multi_on: an AMG apply needs d_work (spmv_hip_precond_work_bytes: its level vectors)");
     if (((uintptr_t)d_R | (uintptr_t)d_Z | (uintptr_t)d_work) % (uintptr_t)P->value_bytes)
         return fail("precond_apply_multi_on: R, Z and work must be aligned to %d bytes", P->value_bytes);
     hipStream_t s = stream ? (hipStream_t)stream : g_stream;
@@ -236,7 +241,7 @@ extern "C" int spmv_hip_precond_apply_multi(const spmv_precond *P, int k, const 
         SolverScope scope;
         void *R = scope.alloc(padded);
         void *Z = scope.alloc(padded);
-        void *work = P->fsai ? scope.alloc(padded) : nullptr;
+        void *work = precond_has_own_apply_multi(P) ? scope.alloc((size_t)precond_work_bytes(P, k)) : nullptr;
         hipError_t e = scope.err;
         if (e == hipSuccess && bytes) e = hipMemcpyAsync(R, R_host, bytes, hipMemcpyHostToDevice, g_stream);
         if (e != hipSuccess) return solver_setup_failed("precond_apply_multi", e);
@@ -248,4 +253,13 @@ extern "C" int spmv_hip_precond_apply_multi(const spmv_precond *P, int k, const 
         if (e != hipSuccess) return solver_run_failed("precond_apply_multi", e);
         return 0;
     });
+}
+
+extern "C" int spmv_hip_precond_work_bytes(const spmv_precond *P, int k, long long *bytes) {
+    if (!P || !bytes) return fail("precond_work_bytes: bad arguments");
+    *bytes = -1;
+    if (k < 1 || k > kMcgMaxK) return fail("precond_work_bytes: k = %d, must be in [1, %d]", k, kMcgMaxK);
+    if (mpcg_refuse_tri(P, "precond_work_bytes")) return -1;
+    *bytes = precond_work_bytes(P, k);
+    return 0;
 }

@@ -26,9 +26,16 @@ MINRES_RAN_ALL, MINRES_CONVERGED, MINRES_BREAKDOWN = 0, 1, 2
 # CsrDevice.lobpcg: info["status"] (SPMV_LOBPCG_* of include/spmv_hip.h); its limits
 LOBPCG_RAN_ALL, LOBPCG_CONVERGED, LOBPCG_BREAKDOWN = 0, 1, 2
 LOBPCG_MAX_K, LOBPCG_DROP = 16, 1e-10
-PRECOND_JACOBI, PRECOND_BLOCK_JACOBI, PRECOND_SSOR, PRECOND_ILU0, PRECOND_FSAI = 1, 2, 3, 4, 5
+PRECOND_JACOBI, PRECOND_BLOCK_JACOBI, PRECOND_SSOR, PRECOND_ILU0, PRECOND_FSAI, PRECOND_AMG = 1, 2, 3, 4, 5, 6
 PRECOND_KINDS = {"jacobi": PRECOND_JACOBI, "block_jacobi": PRECOND_BLOCK_JACOBI, "ssor": PRECOND_SSOR,
-                 "ilu0": PRECOND_ILU0, "fsai": PRECOND_FSAI}
+                 "ilu0": PRECOND_ILU0, "fsai": PRECOND_FSAI, "amg": PRECOND_AMG}
+# the AMG hierarchy (SPMV_AMG_*): what a level reader returns, a level's kind, the limits of the setup
+AMG_A, AMG_P, AMG_R, AMG_INV, AMG_T = 0, 1, 2, 3, 4
+AMG_NOT_COARSEST, AMG_DIRECT, AMG_SMOOTH = 0, 1, 2
+AMG_MAX_LEVELS, AMG_MAX_COARSE_ROWS, AMG_CHAIN_ROWS, AMG_CHAIN_ENTRIES = 16, 256, 256, 4096
+PRECOND_AMG_INFO = ("levels", "first_chained", "launches", "coarsest", "complexity_x1000", "download_us", "setup_us",
+                    "upload_us", "chain")  # then rows[16] and entries[16] per level
+PRECOND_AMG_INFO_WORDS = len(PRECOND_AMG_INFO) + 2 * AMG_MAX_LEVELS
 # CsrDevice.triangular / the SSOR and ILU(0) preconditioners (SPMV_TRSV_*, SPMV_ORDER_*)
 TRSV_LOWER, TRSV_UPPER, TRSV_NONUNIT, TRSV_UNIT = 0, 1, 0, 1
 ORDER_NATURAL, ORDER_MULTICOLOR = 0, 1
@@ -422,14 +429,18 @@ class CsrDevice(_Handle):
             raise ValueError(f"the preconditioner covers rows [{precond.row0}, {precond.row0 + precond.rows}), "
                              f"the handle rows [{row0}, {row1})")
 
-    def preconditioner(self, kind="jacobi", block=1, omega=1.0, ordering="natural", cap=32) -> "Preconditioner":
+    def preconditioner(self, kind="jacobi", block=1, omega=1.0, ordering="natural", cap=32, theta=0.08, coarse_rows=64,
+                       max_levels=16, chain=True) -> "Preconditioner":
         """A preconditioner of this handle's rows; it owns its arrays.  kind "jacobi" (block 1) or "block_jacobi"
         (block in [1, 32]): built on the device (spmv_hip_csr_precond_build).  kind "ssor" (0 < omega < 2; 1 is
         symmetric Gauss-Seidel) or "ilu0": two sparse triangular solves (spmv_hip_csr_precond_build_tri), block 1;
         ordering "natural", or "multicolor": of the rows reordered by a greedy colouring (few dependency levels, more
         steps).  kind "fsai": a sparse lower-triangular G with G^T G ~ A^-1 on the pattern of the lower triangle, at
         most cap (in [1, 32]) entries per row, applied as two SpMVs (spmv_hip_csr_precond_build_fsai); block 1,
-        ordering "natural"."""
+        ordering "natural".  kind "amg": smoothed-aggregation multigrid, one V(1,1) cycle per apply
+        (spmv_hip_csr_precond_build_amg): strength threshold theta in [0, 1), a coarsest level of at most coarse_rows
+        (in [1, 256]) rows solved by its dense inverse, at most max_levels (in [1, 16]) levels, chain: the small
+        levels in one launch (the same bits either way); block 1, ordering "natural"."""
         if kind not in PRECOND_KINDS:
             raise ValueError(f"kind must be one of {sorted(PRECOND_KINDS)}, got {kind!r}")
         if isinstance(block, bool) or int(block) != block or not 1 <= int(block) <= 32:
@@ -448,6 +459,10 @@ class CsrDevice(_Handle):
             if isinstance(cap, bool) or int(cap) != cap or not 1 <= int(cap) <= 32:
                 raise ValueError(f"cap must be an integer in [1, 32], got {cap!r}")
             return Preconditioner(self, PRECOND_FSAI, 1, cap=int(cap))
+        if kind == "amg":
+            _check_amg_args(theta, coarse_rows, max_levels)
+            return Preconditioner(self, PRECOND_AMG, 1, amg=(float(theta), int(coarse_rows), int(max_levels),
+                                                             int(bool(chain))))
         return Preconditioner(self, PRECOND_KINDS[kind], int(block))
 
     def triangular(self, lower=True, unit_diagonal=False, ordering="natural") -> "TriangularSolver":
@@ -481,7 +496,7 @@ class CsrDevice(_Handle):
     def pcg_multi(self, B, iters, tol=0.0, precond=None, bounds=None):
         """k independent preconditioned CG recurrences from x0 = 0 that share one SpMM per step
         (spmv_hip_csr_pcg_multi), for the k columns of a C-contiguous B (M x k, 1 <= k <= 64) of the handle's dtype.
-        precond: a Jacobi, block-Jacobi or FSAI Preconditioner of this handle, or None (cg_multi's bits); SSOR and
+        precond: a Jacobi, block-Jacobi, FSAI or AMG Preconditioner of this handle, or None (cg_multi's bits); SSOR and
         ILU(0) take one right-hand side and are refused.  Every column stops on its own, by the rules of pcg; tol > 0
         also ends the loop early once every column has stopped.  Returns (X (M, k), r.r history (iters + 1, k), r.z
         history (iters + 1, k), info {"steps": int array [k], "status": int array [k] (PCG_*)}, ms)."""
@@ -547,7 +562,7 @@ class CsrDevice(_Handle):
 
     def lobpcg(self, k, iters, tol=0.0, precond=None, X0=None, largest=False, seed=0):
         """LOBPCG (spmv_hip_csr_lobpcg) for the k smallest (largest=True: largest) eigenpairs of a symmetric fp64 A,
-        1 <= k <= 16, n >= 4 k.  precond: a Jacobi, block-Jacobi or FSAI Preconditioner of this handle (smallest only),
+        1 <= k <= 16, n >= 4 k.  precond: a Jacobi, block-Jacobi, FSAI or AMG Preconditioner of this handle (smallest only),
         or None.  X0: n x k starting block (None: np.random.default_rng(seed).standard_normal((n, k))).  Stops as
         converged once tol > 0 and every residual norm <= tol ||A||_inf; tol = 0 runs exactly `iters` steps (the host
         reads the Gram matrices in every step either way).  Returns (w [k] ascending (largest: descending), X (n, k),
@@ -792,16 +807,85 @@ class TriangularSolver(_Handle):
                "spmv_hip_trsv_solve_on")
 
 
+def _check_amg_args(theta, coarse_rows, max_levels):
+    if not np.isfinite(float(theta)) or not 0.0 <= float(theta) < 1.0:
+        raise ValueError(f"theta must lie in [0, 1), got {theta!r}")
+    if isinstance(coarse_rows, bool) or int(coarse_rows) != coarse_rows or not 1 <= int(coarse_rows) <= AMG_MAX_COARSE_ROWS:
+        raise ValueError(f"coarse_rows must be an integer in [1, {AMG_MAX_COARSE_ROWS}], got {coarse_rows!r}")
+    if isinstance(max_levels, bool) or int(max_levels) != max_levels or not 1 <= int(max_levels) <= AMG_MAX_LEVELS:
+        raise ValueError(f"max_levels must be an integer in [1, {AMG_MAX_LEVELS}], got {max_levels!r}")
+
+
+def _amg_levels(read, levels, dtype, with_t):
+    """The levels of an AMG hierarchy through a reader read(level, which, row_ptr, col, val, scalars) (the plan's on
+    the host, a Preconditioner's on the device)."""
+    out = []
+    for lv in range(levels):
+        sc = np.zeros(5)
+        dp = sc.ctypes.data_as(nat.c_double_p)
+        read(lv, AMG_A, None, None, None, dp)
+        entry = {"w": float(sc[0]), "rho": float(sc[1]), "kind": int(sc[2]), "rows": int(sc[3]), "aggregates": int(sc[4])}
+        names = [("A", AMG_A, entry["rows"])]
+        if entry["kind"] == AMG_NOT_COARSEST:
+            names += [("P", AMG_P, entry["rows"]), ("R", AMG_R, entry["aggregates"])]
+            if with_t:
+                names.append(("T", AMG_T, entry["rows"]))
+        elif entry["kind"] == AMG_DIRECT:
+            names.append(("inv", AMG_INV, entry["rows"]))
+        for name, which, rows in names:
+            rp = np.zeros(rows + 1, dtype=np.int32)
+            read(lv, which, rp.ctypes.data_as(nat.c_int_p), None, None, None)
+            col = np.zeros(max(int(rp[-1]), 1), dtype=np.int32)
+            val = np.zeros(max(int(rp[-1]), 1), dtype=dtype)
+            read(lv, which, rp.ctypes.data_as(nat.c_int_p), col.ctypes.data_as(nat.c_int_p),
+                 val.ctypes.data_as(nat.c_double_p if with_t else C.c_void_p), None)
+            entry[name] = (rp, col[:rp[-1]], val[:rp[-1]])
+        out.append(entry)
+    return out
+
+
+def amg_plan(row_ptr, col, val, theta=0.08, coarse_rows=64, max_levels=16) -> list:
+    """The host setup of the AMG preconditioner alone (spmv_amg_plan_build; no device needed) on an n x n CSR matrix
+    with canonical rows (ascending columns, no repeats): the levels as Preconditioner.levels() returns them, in fp64,
+    with "T" (the aggregates: T[i, agg(i)] = 1) beside "P" and "R".  A refusal raises SpmvHipError with the setup's
+    message (the row at level 0, the level below it)."""
+    _check_amg_args(theta, coarse_rows, max_levels)
+    rp = np.ascontiguousarray(row_ptr, dtype=np.int32)
+    col = np.ascontiguousarray(col, dtype=np.int32)
+    val = np.ascontiguousarray(val, dtype=np.float64)
+    if rp.ndim != 1 or rp.size < 1 or col.shape != val.shape or col.ndim != 1 or col.size < int(rp[-1]):
+        raise ValueError("row_ptr (n + 1), col and val (row_ptr[n] each) do not fit together")
+    L = nat.lib()
+    plan = C.c_void_p()
+
+    def check(rc):
+        if rc != 0:
+            raise SpmvHipError(L.spmv_amg_plan_error().decode())
+
+    check(L.spmv_amg_plan_build(rp.size - 1, rp.ctypes.data_as(nat.c_int_p), col.ctypes.data_as(nat.c_int_p),
+                                val.ctypes.data_as(nat.c_double_p), float(theta), int(coarse_rows), int(max_levels),
+                                C.byref(plan)))
+    try:
+        return _amg_levels(lambda *a: check(L.spmv_amg_plan_level(plan, *a)), L.spmv_amg_plan_levels(plan), np.float64,
+                           True)
+    finally:
+        L.spmv_amg_plan_free(plan)
+
+
 class Preconditioner(_Handle):
-    """M^-1 of a Jacobi, block-Jacobi, SSOR, ILU(0) or FSAI preconditioner of a CsrDevice's rows, resident in HBM
+    """M^-1 of a Jacobi, block-Jacobi, SSOR, ILU(0), FSAI or AMG preconditioner of a CsrDevice's rows, resident in HBM
     (CsrDevice.preconditioner).  It owns its arrays: the handle it was built from may be freed first."""
 
     _free = "spmv_hip_precond_free"
 
     def __init__(self, dev: CsrDevice, kind: int, block: int, omega: float = 1.0, ordering: int = ORDER_NATURAL,
-                 cap: int = 32):
+                 cap: int = 32, amg=None):
         super().__init__()
-        if kind == PRECOND_FSAI:
+        if kind == PRECOND_AMG:
+            theta, coarse_rows, max_levels, chain = amg
+            _check(nat.lib().spmv_hip_csr_precond_build_amg(dev.h, theta, coarse_rows, max_levels, chain,
+                                                            C.byref(self.h)), "spmv_hip_csr_precond_build_amg")
+        elif kind == PRECOND_FSAI:
             _check(nat.lib().spmv_hip_csr_precond_build_fsai(dev.h, int(cap), C.byref(self.h)),
                    "spmv_hip_csr_precond_build_fsai")
         elif kind in (PRECOND_SSOR, PRECOND_ILU0):
@@ -834,7 +918,7 @@ class Preconditioner(_Handle):
 
     def apply_multi(self, R):
         """Z = M^-1 R for the k columns of a C-contiguous R (rows x k, 1 <= k <= 64) of the handle's dtype
-        (spmv_hip_precond_apply_multi); Jacobi, block-Jacobi and FSAI."""
+        (spmv_hip_precond_apply_multi); Jacobi, block-Jacobi, FSAI and AMG."""
         R = _check_columns(R, self.rows, self.dtype, "R", "preconditioner")
         Z = np.zeros(R.shape, dtype=self.dtype)
         _check(nat.lib().spmv_hip_precond_apply_multi(self.h, int(R.shape[1]), R.ctypes.data_as(C.c_void_p),
@@ -843,7 +927,8 @@ class Preconditioner(_Handle):
 
     def apply_multi_on(self, d_R: int, d_Z: int, k: int, d_work: int = 0, stream: int = 0):
         """The same on row-major rows x k device arrays, asynchronous on `stream` (0 = the library's).  FSAI needs
-        d_work, rows x k values and one 128-byte line; the other kinds ignore it.  Jacobi and block-Jacobi move 16-byte
+        d_work, rows x k values and one 128-byte line, AMG its level vectors (work_bytes(k), zeroed once); the other
+        kinds ignore it.  Jacobi and block-Jacobi move 16-byte
         pieces when a row of k values is whole pieces and d_R, d_Z are 16-byte aligned, single elements otherwise (the
         same bits)."""
         if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= 64:
@@ -851,6 +936,33 @@ class Preconditioner(_Handle):
         _check(nat.lib().spmv_hip_precond_apply_multi_on(self.h, int(k), C.c_void_p(d_R), C.c_void_p(d_Z),
                                                          C.c_void_p(d_work), C.c_void_p(stream)),
                "spmv_hip_precond_apply_multi_on")
+
+    def work_bytes(self, k: int) -> int:
+        """Bytes of d_work that apply_multi_on needs for k columns (spmv_hip_precond_work_bytes): 0 for Jacobi and
+        block-Jacobi; SSOR and ILU(0) have no k-wide apply and are refused."""
+        out = C.c_longlong(0)
+        _check(nat.lib().spmv_hip_precond_work_bytes(self.h, int(k), C.byref(out)), "spmv_hip_precond_work_bytes")
+        return int(out.value)
+
+    def amg_info(self) -> dict:
+        """AMG: levels, the first level of the chained tail (-1: none), launches per apply, the coarsest kind (AMG_DIRECT
+        or AMG_SMOOTH), operator complexity x 1000, microseconds of download, host setup and upload, chain, and the
+        rows and the entries of A_l per level."""
+        out = (C.c_int * PRECOND_AMG_INFO_WORDS)()
+        _check(nat.lib().spmv_hip_precond_amg_info(self.h, out), "spmv_hip_precond_amg_info")
+        info = dict(zip(PRECOND_AMG_INFO, (int(v) for v in out)))
+        n, base = info["levels"], len(PRECOND_AMG_INFO)
+        info["rows"] = [int(v) for v in out[base:base + n]]
+        info["entries"] = [int(v) for v in out[base + AMG_MAX_LEVELS:base + AMG_MAX_LEVELS + n]]
+        return info
+
+    def levels(self) -> list:
+        """AMG: what the device holds, level by level: {"w", "rho", "kind" (AMG_*), "rows", "aggregates", "A", and "P",
+        "R" (not on the coarsest level) or "inv" (a DIRECT coarsest level: its dense inverse, row by row)}, every
+        operator a (row_ptr, col, val) triple with values of the handle's dtype."""
+        fn = nat.lib().spmv_hip_precond_amg_level
+        return _amg_levels(lambda *a: _check(fn(self.h, *a), "spmv_hip_precond_amg_level"), self.amg_info()["levels"],
+                           self.dtype, False)
 
     def tri_info(self) -> dict:
         """SSOR / ILU(0): levels, launches, widest and median level of the forward and the backward solve, colours
