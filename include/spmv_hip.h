@@ -280,6 +280,41 @@ int spmv_hip_csr_download(const spmv_csr_dev *m, int *row_ptr, int *col, void *v
  * (tiles-only), M * value_bytes (the transpose's x) beyond the kernels' 32-bit gather range.  *out stays NULL on
  * failure. */
 int spmv_hip_csr_transpose(const spmv_csr_dev *m, spmv_csr_dev **out);
+/* C = A B of two whole CSR handles of the same dtype (A: M x K, B: K x N), built on the device, as a new M x N handle.
+ * The rows of A and B may be unsorted and may repeat a (row, column) pair.  C has canonical rows (columns ascending, no
+ * repeats) and a structural pattern: (i, c) is present exactly when some entry a_ij and some entry b_jc exist; a sum
+ * that cancels to 0.0 stays.  The value is that of the serial loop
+ *     for e in row i of A, in entry order:  j = colA[e], a = (double)valA[e]
+ *         for f in row j of B, in entry order:  c = colB[f], p = a * (double)valB[f]      (one rounded product)
+ *             acc[c] = p if c is new in row i, else acc[c] + p                              (one rounded sum)
+ * rounded once to the handle's dtype: the same additions in the same order, never a fused multiply-add, no atomics,
+ * so two calls give the same bytes and the result is what the AMG setup's host product (host/amg_plan.c) computes.
+ * Non-finite values reach exactly the entries whose sums contain them.
+ *   block_products   the on-chip tier's cap: rows are cut into blocks of at most this many products (and 4096 rows)
+ *                    that one workgroup expands, sorts and compresses in LDS.  0: auto (4096); a power of two in
+ *                    [64, 4096]; -1: no on-chip tier.  A row with more products (with -1: with any) is a long row
+ *   chunk_products   long rows go through HBM (expansion, one stable radix sort, compress) in chunks of whole rows of
+ *                    at most this many products (a row larger than that is a chunk of its own).  0: auto (2^23), else >= 64
+ * Both passes run twice, once for the rows' entry counts (keys only) and once for columns and values, so C's arrays are
+ * allocated at their exact size and the workspace is the counts, the block list and one chunk.
+ * C is an ordinary handle (upload's plans, its own arrays, independent of A and B, which are not modified).
+ *   stats (8, may be NULL)  products, entries of C, on-chip blocks with products, rows in them, long rows, chunks, the
+ *                           largest row's products, the largest row's entries
+ *   ms (4, may be NULL)     host milliseconds of count, symbolic, numeric, adopt
+ * -1 with a message (*out NULL, A and B usable): NULL argument, A's columns != B's rows, different dtypes, a row-range
+ * or tiles-only handle, block_products / chunk_products outside the above, more entries in C than a handle indexes,
+ * N * value_bytes beyond the kernels' 32-bit gather range, a failed allocation. */
+int spmv_hip_csr_spgemm(const spmv_csr_dev *a, const spmv_csr_dev *b, int block_products, long long chunk_products,
+                        spmv_csr_dev **out, long long *stats, double *ms);
+/* The row plan of that product (host only; no device needed) from the rows' product counts.  The rows are cut in order
+ * into n_blocks contiguous blocks [block_row[k], block_row[k + 1]) that partition [0, M).  A row with more than
+ * block_products products (0: 4096; -1: any product at all) is a long row: it is the last row of its block, is listed
+ * in long_row (ascending) and is left to the global tier.  The other rows of a block hold at most block_products products
+ * together, and a block has at most max_rows rows (1 .. 4096), its long row included.  block_row has M + 1 entries and
+ * long_row M.  -1: NULL argument, M < 0, a negative count, block_products not 0, -1 or a power of two in [64, 4096],
+ * max_rows outside [1, 4096]. */
+int spmv_spgemm_plan(int M, const long long *products, int block_products, int max_rows, int *block_row, int *n_blocks,
+                     int *long_row, int *n_long);
 /* convenience over the kept struct */
 int spmv_hip_csr_upload_matrix(const CSRMatrix *csr, spmv_csr_dev **out);
 void spmv_hip_csr_free(spmv_csr_dev *m);

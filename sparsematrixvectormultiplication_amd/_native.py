@@ -226,6 +226,9 @@ _PROTOTYPES = {
     "spmv_hip_csr_bicgstab": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, c_int_p, C.c_void_p, C.c_void_p,
                                         c_double_p, c_int_p, c_float_p]),
     "spmv_hip_csr_transpose": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "spmv_hip_csr_spgemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.POINTER(C.c_void_p),
+                                      C.POINTER(C.c_longlong), c_double_p]),
+    "spmv_spgemm_plan": (C.c_int, [C.c_int, C.POINTER(C.c_longlong), C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p]),
     "spmv_hip_csr_precond_build": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "spmv_hip_precond_free": (None, [C.c_void_p]),
     "spmv_hip_precond_info": (C.c_int, [C.c_void_p, c_int_p]),

@@ -48,6 +48,10 @@ PRECOND_TRI_INFO = ("forward_levels", "forward_launches", "forward_widest", "for
 PRECOND_FSAI_INFO = ("cap", "entries", "truncated_rows", "widest", "plan_g", "plan_gt", "analysis_us", "build_us",
                      "upload_us")
 FSAI_PLANS = ("gather", "x_window", "x_window_pattern", "csr_tile")  # fsai_info()["plan_g"], ["plan_gt"]
+# CsrDevice.matmul: the result's matmul_info (the stats and the time split of spmv_hip_csr_spgemm)
+MATMUL_STATS = ("products", "nz", "blocks", "block_rows", "long_rows", "chunks", "max_row_products", "max_row_nz")
+MATMUL_MS = ("count", "symbolic", "numeric", "adopt")
+SPGEMM_MAX_ROWS = 4096
 CSR_STREAM_KERNELS = ("csr_stream", "csr_stream_local", "csr_stream_short", "csr_tile")
 HLL_LDS_KERNELS = ("hll_lds", "hll_lds_local", "csr_tile (HLL slab rows)")
 CSR_VARIANTS = {"thread_row": CSR_THREAD_ROW, "wave_row": CSR_WAVE_ROW, "subwave": CSR_SUBWAVE,
@@ -248,6 +252,28 @@ class CsrDevice(_Handle):
         _check(nat.lib().spmv_hip_csr_transpose(self.h, C.byref(out.h)), "spmv_hip_csr_transpose")
         out.M, out.N, out.dtype = self.N, self.M, self.dtype
         return out
+
+    def matmul(self, other: "CsrDevice", block_products: int = 0, chunk_products: int = 0) -> "CsrDevice":
+        """C = self @ other as a new handle (spmv_hip_csr_spgemm): both whole matrices of one dtype.  C has canonical rows
+        (ascending columns, no repeats), a structural pattern (a sum that cancels to 0.0 stays) and, bit for bit, the
+        values of the serial loop in include/spmv_hip.h: every product and sum a separate rounded double operation in
+        entry order, rounded once to the dtype.  block_products: the on-chip tier's cap (0 = auto = 4096, a power of two
+        in [64, 4096], -1 = every row through the global tier); chunk_products: the global tier's workspace in products
+        (0 = auto, else >= 64).  C.matmul_info holds the stats (MATMUL_STATS) and "ms" (MATMUL_MS) of this product."""
+        if not isinstance(other, CsrDevice):
+            raise TypeError("matmul takes a CsrDevice")
+        out = CsrDevice.__new__(CsrDevice)
+        _Handle.__init__(out)
+        stats, ms = (C.c_longlong * len(MATMUL_STATS))(), (C.c_double * len(MATMUL_MS))()
+        _check(nat.lib().spmv_hip_csr_spgemm(self.h, other.h, int(block_products), int(chunk_products), C.byref(out.h),
+                                             stats, ms), "spmv_hip_csr_spgemm")
+        out.M, out.N, out.dtype = self.M, other.N, self.dtype
+        out.matmul_info = dict(zip(MATMUL_STATS, (int(v) for v in stats)))
+        out.matmul_info["ms"] = dict(zip(MATMUL_MS, (float(v) for v in ms)))
+        return out
+
+    def __matmul__(self, other):
+        return self.matmul(other) if isinstance(other, CsrDevice) else NotImplemented
 
     def download(self):
         """(row_ptr, col_idx, values) of the handle's rows, from the device."""
@@ -805,6 +831,26 @@ class TriangularSolver(_Handle):
         """The same on device vectors (b and x must not overlap), asynchronous on `stream` (0 = the library's)."""
         _check(nat.lib().spmv_hip_trsv_solve_on(self.h, C.c_void_p(d_b), C.c_void_p(d_x), C.c_void_p(stream)),
                "spmv_hip_trsv_solve_on")
+
+
+def spgemm_plan(products, block_products, max_rows=SPGEMM_MAX_ROWS):
+    """The row plan of CsrDevice.matmul (spmv_spgemm_plan; no device needed) from the rows' product counts:
+    (block_row, long_rows).  Blocks k = rows [block_row[k], block_row[k + 1]) partition the rows in order; a long row
+    (more than block_products products; with -1 any product) is the last row of its block and is listed in long_rows;
+    the other rows of a block hold at most block_products products (0 = 4096) and a block at most max_rows rows."""
+    products = np.ascontiguousarray(products, dtype=np.int64)
+    if products.ndim != 1:
+        raise ValueError("products must be one-dimensional")
+    M = products.size
+    block_row, long_row = np.zeros(M + 1, dtype=np.int32), np.zeros(max(M, 1), dtype=np.int32)
+    nb, nl = C.c_int(), C.c_int()
+    rc = nat.lib().spmv_spgemm_plan(M, products.ctypes.data_as(C.POINTER(C.c_longlong)), int(block_products), int(max_rows),
+                                    block_row.ctypes.data_as(nat.c_int_p), C.byref(nb), long_row.ctypes.data_as(nat.c_int_p),
+                                    C.byref(nl))
+    if rc != 0:
+        raise ValueError(f"spgemm_plan refused block_products = {block_products}, max_rows = {max_rows} "
+                         f"(0, -1 or a power of two in [64, 4096]; 1 .. 4096 rows; counts >= 0)")
+    return block_row[:nb.value + 1].copy(), long_row[:nl.value].copy()
 
 
 def _check_amg_args(theta, coarse_rows, max_levels):
