@@ -205,8 +205,7 @@ int spmv_hip_gather_probe(int value_bytes, size_t table_bytes, int waves_per_cu,
  *   read at launch
  *     "stream_kind"   -1 (auto: x-window kernel when the handle has a plan, csr_tile when it has tiles, else
  *                     csr_stream) | 5 x-window | 6 csr_tile |
- *                     0 csr_stream; only in a `make EXPERIMENTAL=1` build: 1 row walk | 2 persistent pipe |
- *                     3 persistent row walk | 4 loader/consumer ring | 10..17 ablation probes (measurement only)
+ *                     0 csr_stream; any other value is an error
  *     "place_tries"   (12) read at upload: how many other placements of the value array a handle that streams >= 128 MiB of
  *                     values tries (a fresh allocation each, the kernel timed 2 + 6 launches on it), keeping the fastest.
  *                     Round 3 found the x-window kernel's time on the headline matrix to depend on WHERE the values lie:
@@ -215,8 +214,7 @@ int spmv_hip_gather_probe(int value_bytes, size_t table_bytes, int waves_per_cu,
  *     "stream_nt" 0/1, "local_nt" -1 (auto) / 0 / 1   non-temporal hint on the streamed arrays
  *     "stream_xcd"    blocks per XCD run: 0 default (16 for the x-window kernels, dispatch order otherwise),
  *                     -1 one contiguous eighth per XCD, n > 0 runs of n
- *     "stream_block"  256 | 512 | 1024 threads (csr_stream at 4096 / 8192), "pipe_wgs_per_cu" 1..8,
- *     "probe_mask"    table size - 1 of the folded gather probe
+ *     "stream_block"  256 | 512 | 1024 threads (csr_stream at 4096 / 8192)
  *     "gather_mode"   all-gatherv: 0 grouped broadcasts | 1 padded all-gather + scatter (see spmv_hip_comm_autotune) */
 int spmv_hip_set_tuning(const char *key, int value);
 

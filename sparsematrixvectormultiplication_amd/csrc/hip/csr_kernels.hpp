@@ -19,7 +19,6 @@
 //                    kernel that reaches the HBM roofline on stencil matrices
 //                    (nlpkkt-like: 83-89 % of 8 TB/s).
 //   csr_long_pieces / csr_long_finish   rows longer than a block's stage.
-// Ablations and the other stream variants: csr_kernels_experimental.hpp.
 //
 // The path is a bandwidth-bound gather (0.17 flop/byte in fp64): no MFMA.
 #pragma once

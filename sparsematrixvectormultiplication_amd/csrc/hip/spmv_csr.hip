@@ -4,6 +4,7 @@
 // :285-317, :682-685).
 #include "spmv_internal.hpp"
 
+#include "launch_dispatch.hpp"
 #include "upload_ops.hpp"
 
 #include "tile_plan.hpp"
@@ -954,14 +955,7 @@ int csr_upload_impl(int M, int N, const int *row_ptr, const int *col_idx, const 
     // enough workgroups to fill 256 CUs (measured: cant-like 2048, nlpkkt-like 4096)
     m->stream_cap = have_local ? lcap : (g_stream_cap ? g_stream_cap : (nz >= (16LL << 20) ? 4096 : 2048));
     m->local_cap = lcap;
-    // the ring kernel stages at most kRingRows - 1 rows per block; only worth it when such
-    // blocks are still (nearly) full, i.e. rows are not tiny
     int rows_cap = kStreamRowsCap;
-#ifdef SPMV_EXPERIMENTAL
-    static_assert(kRingRows + 64 <= kRowPtrPad, "row_ptr padding covers the ring kernel's staged segment");
-    m->ring_ok = m->stream_cap == kRingCap && Ml > 0 && (double)nz / Ml >= 1.25 * kRingCap / (kRingRows - 1);
-    if (m->ring_ok) rows_cap = kRingRows - 1;
-#endif
     // Skewed rows (gather kernels): a block's rows are summed by lane groups sized for the NUMBER of rows in it, so in
     // a block of a few hundred short rows one row of a thousand entries is summed by a single lane while everybody else
     // waits (webbase-like stand-in, 1 M rows, 3.3 entries per row on average, 2 262 in the longest: 73 us; with its rows
@@ -1786,9 +1780,7 @@ extern "C" int spmv_hip_csr_info(const spmv_csr_dev *m, spmv_dev_info *out) {
     out->pattern_table_rows = m->pat.ptab ? m->pat.table_rows : 0;
     out->pattern_segments_stored = m->pat.ptab && m->pat.pseg ? m->pat.seg_distinct : 0;
     out->local_lists_stored = m->lbase ? m->lists_distinct : 0;
-    out->stream_kernel = m->local_blocks > 0 ? 1 : m->tile_blocks > 0 ? 3
-                         : ((m->stream_cap == 4096 || m->stream_cap == 2048) && m->M_local > 0 &&
-                            m->nz < (long long)m->M_local * (m->stream_cap / kBlock)) ? 2 : 0;
+    out->stream_kernel = m->local_blocks > 0 ? 1 : m->tile_blocks > 0 ? 3 : csr_short_rows(m) ? 2 : 0;
     if (m->local_blocks > 0)  // (a pattern plan: the tables and 4 bytes per row instead of 2 bytes per entry)
         // (a pattern plan: the segments instead of the slots; a block whose segment did not fit reads its table, rinfo
         // and row_ptr -- counted as its share of the tables)
@@ -1845,6 +1837,171 @@ void launch_vector(const spmv_csr_dev *m, const T *x, T *y, hipStream_t s) {
                        m->row_ptr, m->col, (const T *)m->val, x, y);
 }
 
+// the split-row pair: 8192-entry pieces into `partial`, then every row's slots added in slot order
+template <typename T>
+void launch_split_rows(const spmv_csr_dev *m, int num_pieces, const int4 *pieces, int num_rows, const int4 *rows,
+                       const T *x, T *y, hipStream_t s) {
+    hipLaunchKernelGGL((csr_long_pieces<T, true>), dim3(num_pieces), dim3(kBlock), 0, s, num_pieces, pieces, m->col,
+                       (const T *)m->val, x, (T *)m->partial);
+    hipLaunchKernelGGL((csr_long_finish<T>), dim3(num_rows), dim3(64), 0, s, num_rows, rows, (const T *)m->partial, y);
+}
+
+// the x-window kernel over all blocks (part < 0) or the interior / boundary sub-list (part 0 / 1, csr_launch_part)
+template <typename T>
+void launch_x_window(const spmv_csr_dev *m, const T *x, T *y, hipStream_t s, int part) {
+    // runs of 16 neighbouring blocks per XCD: each L2 keeps its own window of x lines
+    // (measured flat from 8 to 128 on three matrices); stream_xcd overrides
+    const int lcount = part < 0 ? m->local_blocks : part == 0 ? m->num_interior : m->num_boundary;
+    const int *lids = part < 0 ? nullptr : part == 0 ? m->interior_ids : m->boundary_ids;
+    const int lchunk = g_stream_xcd < 0 ? (lcount + 7) / 8 : (g_stream_xcd ? g_stream_xcd : 16);
+    const int lgrid = lchunk > 0 ? (lcount + 8 * lchunk - 1) / (8 * lchunk) * (8 * lchunk) : lcount;
+    if (lcount <= 0) return;
+    const size_t lds = std::max((size_t)m->local_cap * sizeof(T), (size_t)m->local_stage_lines * kLineBytes);
+    // a pattern plan: the slots are rebuilt in LDS (behind the stage) from the block's pattern table, not read
+    // entry by entry
+    const bool patterns = m->pat.ptab && g_local_patterns != 0;
+    const size_t pat_lds = lds + ((size_t)m->local_cap + 8) * sizeof(unsigned short) + (size_t)m->pat.seg_max * sizeof(uint4);
+    // streamed-once hint only when the matrix cannot live in the 256 MiB Infinity Cache anyway
+    // (cant-like, 53 MB: 10.9 us without it, 11.7 us with; fem-large: 160 vs 151 us)
+    const bool lnt = g_local_nt < 0 ? m->nz * (long long)(sizeof(T) + 2) > (128LL << 20) : g_local_nt != 0;
+    with_value<1024, 3072, 2048>(m->local_cap, [&](auto cap) {
+        with_flag(lnt, [&](auto nt) {
+            constexpr int CAP = decltype(cap)::value;
+            constexpr bool NT = decltype(nt)::value;
+            if (patterns)
+                hipLaunchKernelGGL((csr_stream_local<T, NT, CAP, false, true>), dim3(lgrid), dim3(kBlock), pat_lds, s, lcount, lchunk,
+                                   lids, m->ldesc4, m->ldesc, m->lines, m->row_ptr, m->lcol, (const T *)m->val, x, y,
+                                   (unsigned long long *)nullptr, 0, m->pat.pdesc, m->pat.rinfo, m->pat.ptab, (int)lds, m->pat.sdesc,
+                                   (const uint4 *)m->pat.pseg, m->lbase);
+            else
+                hipLaunchKernelGGL((csr_stream_local<T, NT, CAP>), dim3(lgrid), dim3(kBlock), lds, s, lcount, lchunk, lids,
+                                   m->ldesc4, m->ldesc, m->lines, m->row_ptr, m->lcol, (const T *)m->val, x, y,
+                                   (unsigned long long *)nullptr, 0, (const int2 *)nullptr, (const unsigned *)nullptr,
+                                   (const unsigned short *)nullptr, 0, (const int2 *)nullptr, (const uint4 *)nullptr, m->lbase);
+        });
+    });
+}
+
+// what one csr_tile launch is given: filled for the handle's tiles, for their expansion and for each long_tiles tier
+template <typename T>
+struct tile_args {
+    int items, rows_per_block, stage_ok;  // workgroups' work (streams | work items), accumulators per block
+    size_t lds;
+    const int4 *work;  // long_tiles only: the work items and their slabs
+    T *slab;
+    const int *block_row, *block_pass;
+    const int4 *pass;
+    const int *tcol;
+    const unsigned short *tkey;
+    const T *tval;
+    const int *stream_block;  // the handle's own tiles only: the streams' blocks
+    const int2 *sblock_rows;
+    const T *x;
+};
+
+// (more than 64 KiB of dynamic LDS: allowed for these kernels once, at upload -- tile_allow_lds)
+template <typename T, int TRIPS, bool PACK, bool GA = false>
+void launch_csr_tile(const tile_args<T> &a, bool nt, T *y, hipStream_t s) {
+    with_flag(nt, [&](auto NT) {
+        hipLaunchKernelGGL((csr_tile<T, decltype(NT)::value, 2048, TRIPS, PACK, GA>), dim3((a.items + 7) / 8 * 8), dim3(kTileBlock),
+                           a.lds, s, a.items, a.rows_per_block, a.stage_ok, g_tile_probe, a.work, a.slab, a.block_row, a.block_pass,
+                           a.pass, a.tcol, a.tkey, a.tval, a.stream_block, a.sblock_rows, a.x, y);
+    });
+}
+
+// the tile plan: (expansion of x,) the tiles, the packed plan's remainder, the long and middle tiers, the split rows
+template <typename T>
+void launch_tiles(const spmv_csr_dev *m, const T *x, T *y, hipStream_t s) {
+    // staging copies 16-byte pieces of x: plans with gather passes fall back on gathering everything when
+    // x is not 16-byte aligned, packed plans (no gather code) load the pieces unaligned
+    const int stage_ok = ((uintptr_t)x & 15) == 0;
+    // (probe bit 3, measurement only: one workgroup per CU)
+    const size_t lds = std::max((size_t)std::max(m->tile_lds_min, g_tile_probe & 8 ? 84 * 1024 : 0),
+                                (size_t)kTileSlotBytes + (size_t)m->tile_rows * sizeof(T) +
+                                    (m->tile_packed ? (size_t)kTileTrips * kTileTripBytes  // (the packed kernel stores every trip's piece)
+                                                    : stage_ok ? (size_t)m->tile_max_win * sizeof(T) : 0));
+    const bool tnt = m->nz * (long long)(sizeof(T) + 6) > (128LL << 20);
+    const tile_args<T> own = {m->tile_streams, m->tile_rows, stage_ok, lds, nullptr, nullptr, m->tile_block_row, m->tile_block_pass,
+                              m->tile_pass, m->tcol, m->tkey, (const T *)m->tval, m->tile_stream_block, m->tile_sblock_rows, x};
+    // an expanded plan: x into the passes' segments first, then the packed kernel over x' (16-byte pieces of
+    // x: aligned x only)
+    const bool expanded = m->xe && m->expansion && m->expansion->chunks > 0 && stage_ok && g_tile_expand != 0;
+    if (expanded) {
+        hipLaunchKernelGGL((tile_expand<T>), dim3(m->expansion->chunks), dim3(kExpandBlock), 0, s, m->N, g_tile_probe,
+                           m->expansion->chunk, m->expansion->chunk_runs, m->expansion->lcol, m->expansion->group_run, m->expansion->delta, x, (T *)m->xe);
+        // (a pass's window is its own segment: 2048 values at most, one staging trip in fp32, two in fp64)
+        constexpr int kXpTrips = 2048 * (int)sizeof(T) / kTileTripBytes;
+        tile_args<T> xp = own;
+        xp.stage_ok = 1;
+        xp.lds = std::max((size_t)m->tile_lds_min, (size_t)kTileSlotBytes + (size_t)m->tile_rows * sizeof(T) +
+                                                       (size_t)kXpTrips * kTileTripBytes);
+        xp.pass = m->expansion->pass;
+        xp.tcol = m->expansion->words;
+        xp.tkey = nullptr;
+        xp.x = (const T *)m->xe;
+        launch_csr_tile<T, kXpTrips, true>(xp, tnt, y, s);
+    }
+    else if (m->tile_packed) launch_csr_tile<T, kTileTrips, true>(own, tnt, y, s);
+    else if (g_tile_gather_ahead) launch_csr_tile<T, kTileTrips, false, true>(own, tnt, y, s);  // gathers one pass early
+    else launch_csr_tile<T, kTileTrips, false>(own, tnt, y, s);
+    if (m->tile_rem_rows > 0)  // what the packed plan left out: added behind the tiles
+        hipLaunchKernelGGL((tile_remainder<T>), dim3((m->tile_rem_rows + 255) / 256), dim3(256), 0, s, m->tile_rem_rows,
+                           m->tile_rem_row, m->tile_rem_ptr, m->tile_rem_col, (const T *)m->tile_rem_val, x, y);
+    // the compacted tiers -- the long rows' own tiles, the middle tier of a scattered matrix: work items ->
+    // slabs -> y (after the ordinary tiles wrote 0 there)
+    for (const spmv_csr_dev::long_tiles *tier : {&m->lt, &m->mt}) {
+        const auto &L = *tier;
+        if (L.items <= 0) continue;
+        const size_t llds = (size_t)kTileSlotBytes + (size_t)L.rows_per_block * sizeof(T) +
+                            (L.packed ? (size_t)kTileTrips * kTileTripBytes : stage_ok ? (size_t)L.max_win * sizeof(T) : 0);
+        const tile_args<T> la = {L.items, L.rows_per_block, stage_ok, llds, (const int4 *)L.work, (T *)L.slab, L.block_row, L.block_pass,
+                                 L.pass, L.tcol, L.tkey, (const T *)L.tval, nullptr, nullptr, x};
+        if (L.packed) launch_csr_tile<T, kTileTrips, true>(la, tnt, y, s);
+        else launch_csr_tile<T, kTileTrips, false>(la, tnt, y, s);
+        hipLaunchKernelGGL((tile_slab_finish<T>), dim3((L.rows + kFinishRows - 1) / kFinishRows),
+                           dim3(kFinishRows * kFinishGroups), 0, s, L.rows,
+                           L.rows_per_block, L.block_row, L.block_of_row, L.item_first, L.row_map,
+                           (const T *)L.slab, y);
+    }
+    if (m->tile_num_long)  // rows beyond the tile limit: stripe-ordered pieces, slots added row by row
+        launch_split_rows<T>(m, m->tile_num_pieces, m->tile_pieces, m->tile_num_long, m->tile_long_rows, x, y, s);
+}
+
+// the gather stream: csr_stream at the handle's stage and the knob's block size, csr_stream_short for short rows
+template <typename T>
+void launch_gather_stream(const spmv_csr_dev *m, const T *x, T *y, hipStream_t s) {
+    // blocks per XCD run; the grid is rounded up to whole runs (a workgroup past the last block returns at once)
+    const int chunk = g_stream_xcd < 0 ? (m->num_blocks + 7) / 8 : g_stream_xcd;
+    const int grid_blocks = chunk > 0 ? (m->num_blocks + 8 * chunk - 1) / (8 * chunk) * (8 * chunk)
+                                      : m->num_blocks;
+    const int cap = m->stream_cap, blk = g_stream_block;
+    // (the (stage, block) pairs named below are the instantiations there are)
+    auto full = [&](auto cap_c, auto block_c) {
+        constexpr int CAP = decltype(cap_c)::value, BLOCK = decltype(block_c)::value;
+        with_flag(g_stream_nt, [&](auto nt) {
+            hipLaunchKernelGGL((csr_stream<T, decltype(nt)::value, CAP, BLOCK>), dim3(grid_blocks), dim3(BLOCK), 0, s,
+                               m->num_blocks, chunk, m->desc, m->row_ptr, m->col, (const T *)m->val, x, y);
+        });
+    };
+    // short rows: blocks of up to 1024 rows, row extents of all passes loaded up front
+    auto brief = [&](auto cap_c) {
+        with_flag(g_stream_nt, [&](auto nt) {
+            hipLaunchKernelGGL((csr_stream_short<T, decltype(nt)::value, decltype(cap_c)::value, 256>), dim3(grid_blocks), dim3(256), 0, s,
+                               m->num_blocks, chunk, m->desc, m->row_ptr, m->col, (const T *)m->val, x, y);
+        });
+    };
+    const bool short_rows = csr_short_rows(m);
+    if (cap == 1024) full(int_c<1024>, int_c<256>);
+    else if (cap == 3072) full(int_c<3072>, int_c<256>);
+    else if (cap == 2048 && short_rows) brief(int_c<2048>);
+    else if (cap == 2048) full(int_c<2048>, int_c<256>);
+    else if (cap == 4096 && blk == 512) full(int_c<4096>, int_c<512>);
+    else if (cap == 4096 && short_rows) brief(int_c<4096>);
+    else if (cap == 4096) full(int_c<4096>, int_c<256>);
+    else if (blk == 1024) full(int_c<8192>, int_c<1024>);
+    else full(int_c<8192>, int_c<512>);
+}
+
 template <typename T>
 int csr_launch(const spmv_csr_dev *m, int variant, const T *x, T *y_full, hipStream_t s, int part = -1) {
     if (m->M_local == 0) return 0;
@@ -1874,224 +2031,22 @@ int csr_launch(const spmv_csr_dev *m, int variant, const T *x, T *y_full, hipStr
                 default: launch_vector<T, 32>(m, x, y, s); break;
             }
             break;
-        case SPMV_CSR_STREAM: {
+        case SPMV_CSR_STREAM:
             if (m->num_blocks > 0 || m->tiles_only) {
-                const int per_xcd = (m->num_blocks + 7) / 8;
-#define SPMV_ARGS m->desc, m->row_ptr, m->col, (const T *)m->val, x, y
-#define SPMV_LAUNCH_PROD(NT, CAP, BLOCK)                                                          \
-    hipLaunchKernelGGL((csr_stream<T, NT, CAP, BLOCK>), dim3(grid_blocks), dim3(BLOCK), 0, s,      \
-                       m->num_blocks, chunk, SPMV_ARGS)
-#define SPMV_LAUNCH_FLAGS(MACRO, ...)              \
-    do {                                           \
-        if (g_stream_nt) MACRO(true, __VA_ARGS__); \
-        else MACRO(false, __VA_ARGS__);            \
-    } while (0)
-                // blocks per XCD run; a dummy empty block is harmless for the persistent kernels
-                const int chunk = g_stream_xcd < 0 ? per_xcd : g_stream_xcd;
-                const int grid_blocks = chunk > 0 ? (m->num_blocks + 8 * chunk - 1) / (8 * chunk) * (8 * chunk)
-                                                  : m->num_blocks;
-                const int cap = m->stream_cap, blk = g_stream_block;
-                // the x-window kernel reads whole aligned lines of x
-                const bool local = (g_stream_kind == -1 || g_stream_kind == 5) && m->local_blocks > 0 &&
-                                   ((uintptr_t)x & (kLineBytes - 1)) == 0;
-                // a PACKED plan copies its x slices as 16-byte pieces and has no gather code to fall back on: with an x
-                // that is not 16-byte aligned the clamp of the last piece no longer keeps the loads inside x, so such a
-                // launch goes to the gather kernels (a tiles-only handle has none: error)
-                const bool x_ok_for_tiles = !m->tile_packed || ((uintptr_t)x & 15) == 0;
-                const bool tiled = !local && m->tile_blocks > 0 && x_ok_for_tiles &&
-                                   (g_stream_kind == -1 || g_stream_kind == 6 || m->tiles_only);
-                if (m->tiles_only && !tiled)
-                    return fail(x_ok_for_tiles ? "csr_launch: a tiles-only handle has nothing else to run"
-                                               : "csr_launch: a packed tile plan needs a 16-byte aligned x");
-                if (tiled) {
-                    // staging copies 16-byte pieces of x: plans with gather passes fall back on gathering everything when
-                    // x is not 16-byte aligned, packed plans (no gather code) load the pieces unaligned
-                    const int stage_ok = ((uintptr_t)x & 15) == 0;
-                    // (probe bit 3, measurement only: one workgroup per CU)
-                    const size_t lds = std::max((size_t)std::max(m->tile_lds_min, g_tile_probe & 8 ? 84 * 1024 : 0),
-                                                (size_t)kTileSlotBytes + (size_t)m->tile_rows * sizeof(T) +
-                                                    (m->tile_packed ? (size_t)kTileTrips * kTileTripBytes  // (the packed kernel stores every trip's piece)
-                                                                    : stage_ok ? (size_t)m->tile_max_win * sizeof(T) : 0));
-                    const bool tnt = m->nz * (long long)(sizeof(T) + 6) > (128LL << 20);
-                    const int which = tnt ? 1 : 0;
-                    // (more than 64 KiB of dynamic LDS: allowed for these kernels once, at upload -- tile_allow_lds)
-#define SPMV_TILE(NT, PACK)                                                                                            \
-    hipLaunchKernelGGL((csr_tile<T, NT, 2048, kTileTrips, PACK>), dim3((m->tile_streams + 7) / 8 * 8), dim3(kTileBlock), lds, s, \
-                       m->tile_streams, m->tile_rows, stage_ok, g_tile_probe, (const int4 *)nullptr, (T *)nullptr,       \
-                       m->tile_block_row, m->tile_block_pass, m->tile_pass, m->tcol, m->tkey, (const T *)m->tval,        \
-                       m->tile_stream_block, m->tile_sblock_rows, x, y)
-#define SPMV_TILE_GA(NT)                                                                                               \
-    hipLaunchKernelGGL((csr_tile<T, NT, 2048, kTileTrips, false, true>), dim3((m->tile_streams + 7) / 8 * 8), dim3(kTileBlock), lds, s, \
-                       m->tile_streams, m->tile_rows, stage_ok, g_tile_probe, (const int4 *)nullptr, (T *)nullptr,       \
-                       m->tile_block_row, m->tile_block_pass, m->tile_pass, m->tcol, m->tkey, (const T *)m->tval,        \
-                       m->tile_stream_block, m->tile_sblock_rows, x, y)
-                    // an expanded plan: x into the passes' segments first, then the packed kernel over x' (16-byte pieces of
-                    // x: aligned x only)
-                    const bool expanded = m->xe && m->expansion && m->expansion->chunks > 0 && stage_ok && g_tile_expand != 0;
-                    if (expanded) {
-                        hipLaunchKernelGGL((tile_expand<T>), dim3(m->expansion->chunks), dim3(kExpandBlock), 0, s, m->N, g_tile_probe,
-                                           m->expansion->chunk, m->expansion->chunk_runs, m->expansion->lcol, m->expansion->group_run, m->expansion->delta, x, (T *)m->xe);
-                        // (a pass's window is its own segment: 2048 values at most, one staging trip in fp32, two in fp64)
-                        constexpr int kXpTrips = 2048 * (int)sizeof(T) / kTileTripBytes;
-                        const size_t xlds = std::max((size_t)m->tile_lds_min, (size_t)kTileSlotBytes + (size_t)m->tile_rows * sizeof(T) +
-                                                                                  (size_t)kXpTrips * kTileTripBytes);
-#define SPMV_TILE_XP(NT)                                                                                               \
-    hipLaunchKernelGGL((csr_tile<T, NT, 2048, kXpTrips, true>), dim3((m->tile_streams + 7) / 8 * 8), dim3(kTileBlock), xlds, s, \
-                       m->tile_streams, m->tile_rows, 1, g_tile_probe, (const int4 *)nullptr, (T *)nullptr,              \
-                       m->tile_block_row, m->tile_block_pass, m->expansion->pass, m->expansion->words,                   \
-                       (const unsigned short *)nullptr, (const T *)m->tval, m->tile_stream_block, m->tile_sblock_rows,   \
-                       (const T *)m->xe, y)
-                        if (which) SPMV_TILE_XP(true); else SPMV_TILE_XP(false);
-#undef SPMV_TILE_XP
-                    }
-                    else if (m->tile_packed) { if (which) SPMV_TILE(true, true); else SPMV_TILE(false, true); }
-                    else if (g_tile_gather_ahead) { if (which) SPMV_TILE_GA(true); else SPMV_TILE_GA(false); }  // gathers one pass early
-                    else { if (which) SPMV_TILE(true, false); else SPMV_TILE(false, false); }
-#undef SPMV_TILE_GA
-#undef SPMV_TILE
-                    if (m->tile_rem_rows > 0)  // what the packed plan left out: added behind the tiles
-                        hipLaunchKernelGGL((tile_remainder<T>), dim3((m->tile_rem_rows + 255) / 256), dim3(256), 0, s, m->tile_rem_rows,
-                                           m->tile_rem_row, m->tile_rem_ptr, m->tile_rem_col, (const T *)m->tile_rem_val, x, y);
-                    // the compacted tiers -- the long rows' own tiles, the middle tier of a scattered matrix: work items ->
-                    // slabs -> y (after the ordinary tiles wrote 0 there)
-                    for (const spmv_csr_dev::long_tiles *tier : {&m->lt, &m->mt}) {
-                        const auto &L = *tier;
-                        if (L.items <= 0) continue;
-                        const size_t llds = (size_t)kTileSlotBytes + (size_t)L.rows_per_block * sizeof(T) +
-                                            (L.packed ? (size_t)kTileTrips * kTileTripBytes : stage_ok ? (size_t)L.max_win * sizeof(T) : 0);
-#define SPMV_LTILE(NT, PACK)                                                                                           \
-    hipLaunchKernelGGL((csr_tile<T, NT, 2048, kTileTrips, PACK>), dim3((L.items + 7) / 8 * 8), dim3(kTileBlock), llds, s, L.items, \
-                       L.rows_per_block, stage_ok, g_tile_probe, (const int4 *)L.work, (T *)L.slab, L.block_row,        \
-                       L.block_pass, L.pass, L.tcol, L.tkey, (const T *)L.tval, (const int *)nullptr, (const int2 *)nullptr, x, y)
-                        if (L.packed) { if (which) SPMV_LTILE(true, true); else SPMV_LTILE(false, true); }
-                        else { if (which) SPMV_LTILE(true, false); else SPMV_LTILE(false, false); }
-#undef SPMV_LTILE
-                        hipLaunchKernelGGL((tile_slab_finish<T>), dim3((L.rows + kFinishRows - 1) / kFinishRows),
-                                           dim3(kFinishRows * kFinishGroups), 0, s, L.rows,
-                                           L.rows_per_block, L.block_row, L.block_of_row, L.item_first, L.row_map,
-                                           (const T *)L.slab, y);
-                    }
-                    if (m->tile_num_long) {  // rows beyond the tile limit: stripe-ordered pieces, slots added row by row
-                        hipLaunchKernelGGL((csr_long_pieces<T, true>), dim3(m->tile_num_pieces), dim3(kBlock), 0, s,
-                                           m->tile_num_pieces, m->tile_pieces, m->col, (const T *)m->val, x, (T *)m->partial);
-                        hipLaunchKernelGGL((csr_long_finish<T>), dim3(m->tile_num_long), dim3(64), 0, s, m->tile_num_long,
-                                           m->tile_long_rows, (const T *)m->partial, y);
-                    }
-                    HIP_TRY(hipGetLastError());
-                    return 0;
+                switch (csr_stream_route(m, x, part)) {
+                    case stream_route::nothing_else: return fail("csr_launch: a tiles-only handle has nothing else to run");
+                    // (other handles take such an x to the gather kernels)
+                    case stream_route::unaligned_x: return fail("csr_launch: a packed tile plan needs a 16-byte aligned x");
+                    case stream_route::tiles:  // (its own split rows included)
+                        launch_tiles<T>(m, x, y, s);
+                        HIP_TRY(hipGetLastError());
+                        return 0;
+                    case stream_route::x_window: launch_x_window<T>(m, x, y, s, part); break;
+                    case stream_route::gather: launch_gather_stream<T>(m, x, y, s); break;
                 }
-                if (local) {
-                    // runs of 16 neighbouring blocks per XCD: each L2 keeps its own window of x lines
-                    // (measured flat from 8 to 128 on three matrices); stream_xcd overrides
-                    // part < 0: all blocks; 0 / 1: the interior / boundary sub-list (csr_launch_part)
-                    const int lcount = part < 0 ? m->local_blocks : part == 0 ? m->num_interior : m->num_boundary;
-                    const int *lids = part < 0 ? nullptr : part == 0 ? m->interior_ids : m->boundary_ids;
-                    const int lchunk = g_stream_xcd < 0 ? (lcount + 7) / 8 : (g_stream_xcd ? g_stream_xcd : 16);
-                    const int lgrid = lchunk > 0 ? (lcount + 8 * lchunk - 1) / (8 * lchunk) * (8 * lchunk) : lcount;
-                    if (lcount > 0) {
-                    const size_t lds = std::max((size_t)m->local_cap * sizeof(T), (size_t)m->local_stage_lines * kLineBytes);
-                    // a pattern plan: the slots are rebuilt in LDS (behind the stage) from the block's pattern table, not read
-                    // entry by entry
-                    const bool patterns = m->pat.ptab && g_local_patterns != 0;
-                    const size_t pat_lds = lds + ((size_t)m->local_cap + 8) * sizeof(unsigned short) + (size_t)m->pat.seg_max * sizeof(uint4);
-#define SPMV_LOCAL(NT, CAP)                                                                                   \
-    do {                                                                                                      \
-        if (patterns)                                                                                         \
-            hipLaunchKernelGGL((csr_stream_local<T, NT, CAP, false, true>), dim3(lgrid), dim3(kBlock), pat_lds, s, lcount, lchunk, \
-                               lids, m->ldesc4, m->ldesc, m->lines, m->row_ptr, m->lcol, (const T *)m->val, x, y, \
-                               (unsigned long long *)nullptr, 0, m->pat.pdesc, m->pat.rinfo, m->pat.ptab, (int)lds, m->pat.sdesc, (const uint4 *)m->pat.pseg, m->lbase); \
-        else                                                                                                  \
-            hipLaunchKernelGGL((csr_stream_local<T, NT, CAP>), dim3(lgrid), dim3(kBlock), lds, s, lcount, lchunk, lids, \
-                               m->ldesc4, m->ldesc, m->lines, m->row_ptr, m->lcol, (const T *)m->val, x, y,    \
-                               (unsigned long long *)nullptr, 0, (const int2 *)nullptr, (const unsigned *)nullptr, \
-                               (const unsigned short *)nullptr, 0, (const int2 *)nullptr, (const uint4 *)nullptr, m->lbase); \
-    } while (0)
-                    // streamed-once hint only when the matrix cannot live in the 256 MiB Infinity Cache anyway
-                    // (cant-like, 53 MB: 10.9 us without it, 11.7 us with; fem-large: 160 vs 151 us)
-                    const bool lnt = g_local_nt < 0 ? m->nz * (long long)(sizeof(T) + 2) > (128LL << 20) : g_local_nt != 0;
-                    if (m->local_cap == 1024) { if (lnt) SPMV_LOCAL(true, 1024); else SPMV_LOCAL(false, 1024); }
-                    else if (m->local_cap == 3072) { if (lnt) SPMV_LOCAL(true, 3072); else SPMV_LOCAL(false, 3072); }
-                    else { if (lnt) SPMV_LOCAL(true, 2048); else SPMV_LOCAL(false, 2048); }
-                    }
-#undef SPMV_LOCAL
-#ifdef SPMV_EXPERIMENTAL
-                } else if (g_stream_kind == 4 && m->ring_ok) {
-                    // loader / consumer ring: one persistent 512-thread workgroup per CU
-                    const int wgs = std::max(1, std::min(g_num_cus * g_pipe_wgs_per_cu, m->num_blocks));
-                    if (g_pipe_wgs_per_cu >= 2) {
-                        if (g_stream_nt) hipLaunchKernelGGL((csr_stream_ring<T, true, 3, 2>), dim3(wgs), dim3(kRingBlock), 0, s, m->num_blocks, SPMV_ARGS);
-                        else hipLaunchKernelGGL((csr_stream_ring<T, false, 3, 2>), dim3(wgs), dim3(kRingBlock), 0, s, m->num_blocks, SPMV_ARGS);
-                    } else {
-                        if (g_stream_nt) hipLaunchKernelGGL((csr_stream_ring<T, true, 4, 3>), dim3(wgs), dim3(kRingBlock), 0, s, m->num_blocks, SPMV_ARGS);
-                        else hipLaunchKernelGGL((csr_stream_ring<T, false, 4, 3>), dim3(wgs), dim3(kRingBlock), 0, s, m->num_blocks, SPMV_ARGS);
-                    }
-                } else if (g_stream_kind >= 10 && g_stream_kind <= 17 && (cap == 2048 || cap == 4096)) {
-                    // ablation probes (measurement only; y is not A x)
-#define SPMV_PROBE(CAP, MODE) hipLaunchKernelGGL((csr_probe<T, true, CAP, MODE>), dim3(grid_blocks), dim3(kBlock), 0, s, m->num_blocks, chunk, g_probe_mask, SPMV_ARGS)
-                    const int mode = g_stream_kind - 10;
-                    if (cap == 2048) { if (mode == 0) SPMV_PROBE(2048, 0); else if (mode == 1) SPMV_PROBE(2048, 1); else if (mode == 2) SPMV_PROBE(2048, 2); else if (mode == 3) SPMV_PROBE(2048, 3); else if (mode == 5) SPMV_PROBE(2048, 5); else SPMV_PROBE(2048, 7); }
-                    else { if (mode == 0) SPMV_PROBE(4096, 0); else if (mode == 1) SPMV_PROBE(4096, 1); else if (mode == 2) SPMV_PROBE(4096, 2); else if (mode == 3) SPMV_PROBE(4096, 3); else if (mode == 5) SPMV_PROBE(4096, 5); else SPMV_PROBE(4096, 7); }
-#undef SPMV_PROBE
-                } else if (g_stream_kind == 2 && cap <= 4096) {
-                    // persistent grid: what is resident at once (at least two blocks each)
-                    int wgs = std::max(8, std::min(g_num_cus * g_pipe_wgs_per_cu, (m->num_blocks + 1) / 2) / 8 * 8);
-                    if (cap == 2048) {
-                        if (g_stream_nt) hipLaunchKernelGGL((csr_stream_pipe<T, true, 2048>), dim3(wgs), dim3(kBlock), 0, s, m->num_blocks, chunk, SPMV_ARGS);
-                        else hipLaunchKernelGGL((csr_stream_pipe<T, false, 2048>), dim3(wgs), dim3(kBlock), 0, s, m->num_blocks, chunk, SPMV_ARGS);
-                    } else {
-                        if (g_stream_nt) hipLaunchKernelGGL((csr_stream_pipe<T, true, 4096>), dim3(wgs), dim3(kBlock), 0, s, m->num_blocks, chunk, SPMV_ARGS);
-                        else hipLaunchKernelGGL((csr_stream_pipe<T, false, 4096>), dim3(wgs), dim3(kBlock), 0, s, m->num_blocks, chunk, SPMV_ARGS);
-                    }
-                } else if ((g_stream_kind == 1 || g_stream_kind == 3) && cap <= 4096) {
-                    // kind 1: one block per workgroup; kind 3: persistent grid-stride
-                    const bool persist = g_stream_kind == 3;
-                    const int wgs = persist ? std::max(8, std::min(g_num_cus * g_pipe_wgs_per_cu, m->num_blocks) / 8 * 8)
-                                            : grid_blocks;
-#define SPMV_WALK(NT, CAP, P) hipLaunchKernelGGL((csr_stream_walk<T, NT, CAP, P>), dim3(wgs), dim3(kBlock), 0, s, m->num_blocks, chunk, SPMV_ARGS)
-                    if (cap == 2048) {
-                        if (persist) { if (g_stream_nt) SPMV_WALK(true, 2048, true); else SPMV_WALK(false, 2048, true); }
-                        else { if (g_stream_nt) SPMV_WALK(true, 2048, false); else SPMV_WALK(false, 2048, false); }
-                    } else {
-                        if (persist) { if (g_stream_nt) SPMV_WALK(true, 4096, true); else SPMV_WALK(false, 4096, true); }
-                        else { if (g_stream_nt) SPMV_WALK(true, 4096, false); else SPMV_WALK(false, 4096, false); }
-                    }
-#undef SPMV_WALK
-#endif
-                } else if (cap == 1024) {
-                    SPMV_LAUNCH_FLAGS(SPMV_LAUNCH_PROD, 1024, 256);
-                } else if (cap == 3072) {
-                    SPMV_LAUNCH_FLAGS(SPMV_LAUNCH_PROD, 3072, 256);
-                } else if (cap == 2048 && m->nz < (long long)m->M_local * (2048 / kBlock)) {
-                    if (g_stream_nt) hipLaunchKernelGGL((csr_stream_short<T, true, 2048, 256>), dim3(grid_blocks), dim3(256), 0, s, m->num_blocks, chunk, SPMV_ARGS);
-                    else hipLaunchKernelGGL((csr_stream_short<T, false, 2048, 256>), dim3(grid_blocks), dim3(256), 0, s, m->num_blocks, chunk, SPMV_ARGS);
-                } else if (cap == 2048) {
-                    SPMV_LAUNCH_FLAGS(SPMV_LAUNCH_PROD, 2048, 256);
-                } else if (cap == 4096 && blk == 512) {
-                    SPMV_LAUNCH_FLAGS(SPMV_LAUNCH_PROD, 4096, 512);
-                } else if (cap == 4096 && m->nz < (long long)m->M_local * (4096 / kBlock)) {
-                    // short rows: blocks of up to 1024 rows, row extents of all passes loaded up front
-                    if (g_stream_nt) hipLaunchKernelGGL((csr_stream_short<T, true, 4096, 256>), dim3(grid_blocks), dim3(256), 0, s, m->num_blocks, chunk, SPMV_ARGS);
-                    else hipLaunchKernelGGL((csr_stream_short<T, false, 4096, 256>), dim3(grid_blocks), dim3(256), 0, s, m->num_blocks, chunk, SPMV_ARGS);
-                } else if (cap == 4096) {
-                    SPMV_LAUNCH_FLAGS(SPMV_LAUNCH_PROD, 4096, 256);
-                } else if (blk == 1024) {
-                    SPMV_LAUNCH_FLAGS(SPMV_LAUNCH_PROD, 8192, 1024);
-                } else {
-                    SPMV_LAUNCH_FLAGS(SPMV_LAUNCH_PROD, 8192, 512);
-                }
-#undef SPMV_LAUNCH_FLAGS
-#undef SPMV_LAUNCH_PROD
-#undef SPMV_ARGS
             }
-            if (m->num_long && part != 0) {
-                hipLaunchKernelGGL((csr_long_pieces<T, true>), dim3(m->num_partial), dim3(kBlock), 0, s,
-                                   m->num_partial, m->pieces, m->col, (const T *)m->val, x,
-                                   (T *)m->partial);
-                hipLaunchKernelGGL((csr_long_finish<T>), dim3(m->num_long), dim3(64), 0, s,
-                                   m->num_long, m->long_rows, (const T *)m->partial, y);
-            }
+            if (m->num_long && part != 0) launch_split_rows<T>(m, m->num_partial, m->pieces, m->num_long, m->long_rows, x, y, s);
             break;
-        }
         default:
             return fail("unknown CSR variant %d", variant);
     }
@@ -2111,8 +2066,7 @@ int csr_launch_any(const spmv_csr_dev *m, int variant, const void *x, void *y, h
 // csr_launch_any(STREAM): the same kernels on the same blocks, hence the same bits.  A handle without the
 // split (no x-window plan, foreign misaligned x) runs everything as part 1.
 int csr_launch_part(const spmv_csr_dev *m, int part, const void *x, void *y, hipStream_t s) {
-    const bool split_ok = m->have_split && m->local_blocks > 0 && ((uintptr_t)x & (kLineBytes - 1)) == 0 &&
-                          (g_stream_kind == -1 || g_stream_kind == 5);
+    const bool split_ok = csr_stream_route(m, x, part) == stream_route::x_window;
     if (!split_ok) return part == 0 ? 0 : csr_launch_any(m, SPMV_CSR_STREAM, x, y, s);
     if (m->value_bytes == 8) return csr_launch<double>(m, SPMV_CSR_STREAM, (const double *)x, (double *)y, s, part);
     return csr_launch<float>(m, SPMV_CSR_STREAM, (const float *)x, (float *)y, s, part);

@@ -113,9 +113,7 @@ int g_tile_long = 1;
 int g_halo_overlap = 1;
 int g_halo_split = 1;
 int g_tile_balance = 1;
-int g_pipe_wgs_per_cu = 5;
 int g_num_cus = 256;
-int g_probe_mask = 1023;
 static int g_probe_depth = 4;  // "probe_depth" tuning knob: loads in flight per lane of the stream probe (4 | 16)
 
 int fail(const char *fmt, ...) {
@@ -215,16 +213,9 @@ extern "C" int spmv_hip_set_tuning(const char *key, int value) {
     } else if (!strcmp(key, "stream_xcd")) {
         if (value < -1) return fail("set_tuning: stream_xcd must be -1, 0 or a positive run length");
         g_stream_xcd = value;
-    } else if (!strcmp(key, "probe_mask")) {
-        g_probe_mask = value;
     } else if (!strcmp(key, "stream_kind")) {
-        if ((value < -1 || value > 6) && (value < 10 || value > 17))
-            return fail("set_tuning: stream_kind must be -1..6 (or 10..17 for the ablation probes)");
-#ifndef SPMV_EXPERIMENTAL
         if (value != -1 && value != 0 && value != 5 && value != 6)
-            return fail("set_tuning: stream_kind %d is an experimental kernel; this library was built without "
-                        "EXPERIMENTAL=1 (make -C csrc EXPERIMENTAL=1)", value);
-#endif
+            return fail("set_tuning: stream_kind must be -1 (auto), 0 (csr_stream), 5 (x-window) or 6 (tiles)");
         g_stream_kind = value;
     } else if (!strcmp(key, "stream_tile")) {
         if (value < -1 || value > 1) return fail("set_tuning: stream_tile must be -1 (auto), 0 or 1");
@@ -306,9 +297,6 @@ extern "C" int spmv_hip_set_tuning(const char *key, int value) {
         g_plan_on_device = value != 0;  // takes effect at the next upload
     } else if (!strcmp(key, "stream_local")) {
         g_stream_local = value != 0;  // takes effect at the next upload
-    } else if (!strcmp(key, "pipe_wgs_per_cu")) {
-        if (value < 1 || value > 8) return fail("set_tuning: pipe_wgs_per_cu must be 1..8");
-        g_pipe_wgs_per_cu = value;
     } else {
         return fail("set_tuning: unknown key '%s'", key);
     }

@@ -3,6 +3,7 @@
 // allocations and launches of /root/reference/main_cuda.cu:369-455, :545-568, :613-637, :731-744.
 #include "spmv_internal.hpp"
 
+#include "launch_dispatch.hpp"
 #include "upload_ops.hpp"
 
 namespace {
@@ -694,8 +695,7 @@ int hll_launch(const spmv_hll_dev *m, int variant, const double *x, double *y_fu
             }
             break;
         case SPMV_HLL_LDS: {
-            if ((g_stream_kind == -1 || g_stream_kind == 5) && m->local_blocks > 0 &&
-                ((uintptr_t)x & (kLineBytes - 1)) == 0) {
+            if (x_window_runs(m->local_blocks, x)) {
                 const int lchunk = g_stream_xcd < 0 ? (m->local_blocks + 7) / 8 : (g_stream_xcd ? g_stream_xcd : 16);
                 const int lgrid = (m->local_blocks + 8 * lchunk - 1) / (8 * lchunk) * (8 * lchunk);
                 const size_t llds = std::max((size_t)2048 * sizeof(double), (size_t)m->local_stage_lines * kLineBytes);
@@ -703,38 +703,28 @@ int hll_launch(const spmv_hll_dev *m, int variant, const double *x, double *y_fu
                 // a pattern plan: the windows' slots are rebuilt in LDS (behind the stage), lja is not read
                 const bool patterns = m->pat.ptab && g_local_patterns != 0;
                 const size_t pat_lds = llds + ((size_t)2048 + 8) * sizeof(unsigned short);
-                if (patterns && lnt)
-                    hipLaunchKernelGGL((hll_lds_local<double, true, 2048, true>), dim3(lgrid), dim3(kBlock), pat_lds, s,
-                                       m->local_blocks, lchunk, m->ldesc4, m->ldesc, m->lines, m->row_seg,
-                                       m->lja, m->AS, x, y, m->pat.pdesc, m->pat.rinfo, m->pat.ptab, (int)llds);
-                else if (patterns)
-                    hipLaunchKernelGGL((hll_lds_local<double, false, 2048, true>), dim3(lgrid), dim3(kBlock), pat_lds, s,
-                                       m->local_blocks, lchunk, m->ldesc4, m->ldesc, m->lines, m->row_seg,
-                                       m->lja, m->AS, x, y, m->pat.pdesc, m->pat.rinfo, m->pat.ptab, (int)llds);
-                else if (lnt)
-                    hipLaunchKernelGGL((hll_lds_local<double, true, 2048>), dim3(lgrid), dim3(kBlock), llds, s,
-                                       m->local_blocks, lchunk, m->ldesc4, m->ldesc, m->lines, m->row_seg,
-                                       m->lja, m->AS, x, y);
-                else
-                    hipLaunchKernelGGL((hll_lds_local<double, false, 2048>), dim3(lgrid), dim3(kBlock), llds, s,
-                                       m->local_blocks, lchunk, m->ldesc4, m->ldesc, m->lines, m->row_seg,
-                                       m->lja, m->AS, x, y);
+                with_flag(lnt, [&](auto nt) {
+                    constexpr bool NT = decltype(nt)::value;
+                    if (patterns)
+                        hipLaunchKernelGGL((hll_lds_local<double, NT, 2048, true>), dim3(lgrid), dim3(kBlock), pat_lds, s,
+                                           m->local_blocks, lchunk, m->ldesc4, m->ldesc, m->lines, m->row_seg,
+                                           m->lja, m->AS, x, y, m->pat.pdesc, m->pat.rinfo, m->pat.ptab, (int)llds);
+                    else
+                        hipLaunchKernelGGL((hll_lds_local<double, NT, 2048>), dim3(lgrid), dim3(kBlock), llds, s,
+                                           m->local_blocks, lchunk, m->ldesc4, m->ldesc, m->lines, m->row_seg,
+                                           m->lja, m->AS, x, y);
+                });
                 break;
             }
-            // csr_tile over the slab's rows (a packed plan copies 16-byte pieces of x and has no gather code: a foreign x
-            // that is not 16-byte aligned goes to hll_lds below instead of being read past its end)
-            if (m->tiles && (g_stream_kind == -1 || g_stream_kind == 6) && (!m->tiles->tile_packed || ((uintptr_t)x & 15) == 0))
-                return csr_launch_any(m->tiles, SPMV_CSR_STREAM, x, y_full, s);
+            // csr_tile over the slab's rows (a packed plan with a foreign x that is not 16-byte aligned goes to hll_lds
+            // below instead of being read past its end)
+            if (m->tiles && tiles_run(m->tiles, x, false)) return csr_launch_any(m->tiles, SPMV_CSR_STREAM, x, y_full, s);
             const size_t lds = 32 + ((size_t)m->stage_slots + 2) * sizeof(double);
-#define SPMV_HLL_LDS_LAUNCH(MAXU)                                                                  \
-    hipLaunchKernelGGL((hll_lds<double, true, MAXU>), dim3(m->num_blocks), dim3(kBlock), lds, s,    \
-                       m->stage_slots, m->hdesc, m->hack_off, m->maxnz, m->JA, m->AS, x, y)
-            const int units = m->stage_slots / kStreamUnit;
-            if (units <= 2) SPMV_HLL_LDS_LAUNCH(2);
-            else if (units <= 4) SPMV_HLL_LDS_LAUNCH(4);
-            else if (units <= 6) SPMV_HLL_LDS_LAUNCH(6);
-            else SPMV_HLL_LDS_LAUNCH(8);
-#undef SPMV_HLL_LDS_LAUNCH
+            // (the instantiations stage an even number of 512-slot units: the handle's, rounded up)
+            with_value<2, 4, 6, 8>((m->stage_slots / kStreamUnit + 1) / 2 * 2, [&](auto maxu) {
+                hipLaunchKernelGGL((hll_lds<double, true, decltype(maxu)::value>), dim3(m->num_blocks), dim3(kBlock), lds, s,
+                                   m->stage_slots, m->hdesc, m->hack_off, m->maxnz, m->JA, m->AS, x, y);
+            });
             break;
         }
         default:

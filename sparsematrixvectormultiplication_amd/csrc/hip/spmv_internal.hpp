@@ -16,9 +16,6 @@
 #include <vector>
 
 #include "csr_kernels.hpp"
-#ifdef SPMV_EXPERIMENTAL  // make EXPERIMENTAL=1: the stream variants that lost their A/B + the ablation probes
-#include "csr_kernels_experimental.hpp"
-#endif
 #include "hll_kernels.hpp"
 #include "tile_kernels.hpp"
 #include "spmv_hip.h"
@@ -46,9 +43,8 @@ extern int g_gather_mode;     // all-gatherv: 0 = one ncclBroadcast per owner in
 extern int g_local_cap;       // stage of the x-window plan: 0 = auto, 1024 or 2048
 extern int g_stream_local;    // build the x-window plan at upload when it pays
 extern int g_plan_on_device;  // ... with the device kernels where they apply (0: always on the host)
-extern int g_stream_kind;     // -1 = auto (x-window kernel when the matrix has a plan, else csr_stream), 5 = x-window,
-                              // 0 = csr_stream, 1 = row walk, 2 = pipe, 3 = persistent walk, 4 = ring, 10..17 = probes
-extern int g_pipe_wgs_per_cu; // resident workgroups per CU the persistent grids are sized for
+extern int g_stream_kind;     // -1 = auto (x-window kernel or tiles when the handle has that plan, else csr_stream), 5 = x-window,
+                              // 6 = tiles, 0 = csr_stream
 extern int g_stream_tile;     // csr_tile plan at upload: -1 = auto (no x-window plan, enough rows), 0 = never, 1 = whenever no x-window plan
 extern int g_tile_rows;       // rows per block: 0 = auto, else a power of two in 256..8192
 extern int g_tile_lmax;       // rows longer than this stay with the split-row kernels
@@ -76,7 +72,6 @@ extern int g_tile_mid;        // 1: scattered plans get that tier (when it holds
 extern int g_place_tries;     // other placements of the value array upload tries for large handles (0: none)
 extern int g_tile_plan_on_device;  // 1: the csr_tile plan is built by kernels (tile_plan_device.hpp), 0: by host threads (tile_plan.hpp)
 extern int g_num_cus;
-extern int g_probe_mask;      // csr_probe: table size - 1 (entries) of the folded gather
 
 int fail(const char *fmt, ...);  // records the message for spmv_hip_last_error(), returns -1
 int need_device();               // 0, or -1 when spmv_hip_init() has not succeeded
@@ -232,7 +227,6 @@ struct spmv_csr_dev {
     void *spmm_partial = nullptr;  // the k-wide partial sums of the pieces for SpMM (spmv_spmm.hip): grows only
     size_t spmm_partial_bytes = 0;
     int stream_cap = 2048;
-    bool ring_ok = false;  // blocks respect the ring kernel's row limit
     // stream kernel with the x window in LDS (csr_stream_local): own blocks, 16-bit local columns
     int4 *ldesc4 = nullptr;           // [local_blocks] like desc
     int2 *ldesc = nullptr;            // [local_blocks] {first line in `lines`, line count}

@@ -90,36 +90,34 @@ def test_stream_kernel_block_shapes_repeatable(gpu, oracle, mean, dtype):
         y_ref = oracle.csr_f32_accum64(row_ptr, col, val, x)
     item = np.dtype(dtype).itemsize
     try:
-        # (the row-walk / pipe / ring variants live behind `make EXPERIMENTAL=1` since round 2)
         for cap, walk, blk in ((2048, 0, 256), (4096, 0, 256), (4096, 0, 512), (8192, 0, 512), (8192, 0, 1024),
                                (1024, 0, 256), (3072, 0, 256)):
             set_tuning("stream_cap", cap)
             with sp.CsrDevice(M, N, row_ptr, col, val) as dev:
                 dev.set_x(x)
-                if True:
-                    set_tuning("stream_kind", walk)
-                    set_tuning("stream_block", blk if blk in (256, 512, 1024) else 256)
-                    set_tuning("pipe_wgs_per_cu", 2 if blk == 257 else (1 if walk == 4 else 5))
-                    first = None
-                    for rep in range(4):
-                        sp.lib().spmv_hip_memset(dev.y_ptr, 0xFF, M * item)  # NaN pattern
-                        dev.run(sp.CSR_STREAM)
-                        y = dev.get_y()
-                        if dtype == np.float64:
-                            assert_parity(y, y_ref, row_ptr, col, val, x,
-                                          what=f"cap={cap} kind={walk} block={blk} rep={rep}")
-                        else:
-                            err = np.max(np.abs(y.astype(np.float64) - y_ref)) / np.max(np.abs(y_ref))
-                            assert err <= FP32_NORMWISE_RTOL, f"cap={cap} kind={walk}: {err:.3e}"
-                            assert_parity_f32(y, y_ref, row_ptr, col, val, x, what=f"cap={cap} kind={walk} rep={rep}")
-                        if first is None:
-                            first = y
-                        assert y.tobytes() == first.tobytes(), "result changed between launches"
+                set_tuning("stream_kind", walk)
+                set_tuning("stream_block", blk if blk in (256, 512, 1024) else 256)
+                first = None
+                for rep in range(4):
+                    set_tuning("stream_nt", int(rep != 3))  # (the last launch without the streamed-once hint: same bits)
+                    sp.lib().spmv_hip_memset(dev.y_ptr, 0xFF, M * item)  # NaN pattern
+                    dev.run(sp.CSR_STREAM)
+                    y = dev.get_y()
+                    if dtype == np.float64:
+                        assert_parity(y, y_ref, row_ptr, col, val, x,
+                                      what=f"cap={cap} kind={walk} block={blk} rep={rep}")
+                    else:
+                        err = np.max(np.abs(y.astype(np.float64) - y_ref)) / np.max(np.abs(y_ref))
+                        assert err <= FP32_NORMWISE_RTOL, f"cap={cap} kind={walk}: {err:.3e}"
+                        assert_parity_f32(y, y_ref, row_ptr, col, val, x, what=f"cap={cap} kind={walk} rep={rep}")
+                    if first is None:
+                        first = y
+                    assert y.tobytes() == first.tobytes(), "result changed between launches"
     finally:
         set_tuning("stream_cap", 0)
         set_tuning("stream_kind", -1)
         set_tuning("stream_block", 256)
-        set_tuning("pipe_wgs_per_cu", 5)
+        set_tuning("stream_nt", 1)
 
 
 def test_csr_long_rows_are_split_and_summed(gpu, oracle):
@@ -408,6 +406,32 @@ def test_full_size_hll_equals_csr_fem_like(gpu, oracle):
             for got, want in zip(a, b):
                 assert got.tobytes() == want.tobytes()
             assert built.spmv(x, sp.HLL_LDS).tobytes() == hdev.spmv(x, sp.HLL_LDS).tobytes()
+        # the gather kernel on the same slab: from 16 Mi slots on its windows fill the 4096-slot stage (hll_lds<.., 8>)
+        from sparsematrixvectormultiplication_amd.device import set_tuning
+        try:
+            set_tuning("stream_kind", 0)
+            y_hll = hdev.spmv(x, sp.HLL_LDS)
+        finally:
+            set_tuning("stream_kind", -1)
+        assert np.max(np.abs(y_hll - y_csr)) <= 1e-12 * scale
+        assert_parity(y_hll[lo:hi], ref, rp, col[e0:e1], val[e0:e1], x, what="hll_lds rows sample")
+    # the stage in between: 16 Mi slots in rows of 1500, two rows a window = 3000 slots, six units (hll_lds<.., 6>)
+    M, L = 11_200, 1500
+    N = 7 * M + 3 * L
+    row_ptr = (np.arange(M + 1, dtype=np.int64) * L).astype(np.int32)
+    col = (7 * np.arange(M, dtype=np.int32)[:, None] + 3 * np.arange(L, dtype=np.int32)[None, :]).ravel()
+    val, x = rng.uniform(-1, 1, M * L), rng.uniform(-1, 1, N)
+    try:
+        set_tuning("stream_local", 0)
+        set_tuning("stream_tile", 0)
+        with sp.CsrDevice(M, N, row_ptr, col, val) as cdev, sp.HllDevice.from_csr_device(cdev) as hdev:
+            info = hdev.info()
+            assert info["slots"] == M * L >= 16 << 20 and info["stream_kernel"] == 0 and info["stream_blocks"] == M // 2, info
+            y_hll = hdev.spmv(x, sp.HLL_LDS)
+    finally:
+        set_tuning("stream_local", 1)
+        set_tuning("stream_tile", -1)
+    assert_parity(y_hll, oracle.csr_serial(row_ptr, col, val, x), row_ptr, col, val, x, what="hll_lds six units")
 
 
 # ------------------------------------------- HLL built on the device (N1)

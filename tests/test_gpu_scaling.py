@@ -235,10 +235,12 @@ def test_csr_stream_short(gpu, oracle, dtype):
     rng = np.random.default_rng(103)
     M, N, rp, col = short_rows(rng)
     case = Case(rng, M, N, rp, col, dtype)
-    info = check_spmv(oracle, case, csr_maker(case), {"stream_cap": 2048, "stream_local": 0, "stream_tile": 0},
-                      lambda i: i["stream_kernel"] == 2 and i["local_blocks"] == 0, sp.CSR_STREAM, "csr_stream_short",
-                      launch_knobs=XCD + [{"stream_nt": 0}])
-    assert xcd_blocks_ok(info["stream_blocks"]), info["stream_blocks"]
+    for cap in (2048, 4096):  # (the kernel's two stages)
+        info = check_spmv(oracle, case, csr_maker(case), {"stream_cap": cap, "stream_local": 0, "stream_tile": 0},
+                          lambda i: i["stream_kernel"] == 2 and i["local_blocks"] == 0, sp.CSR_STREAM,
+                          f"csr_stream_short cap={cap}", launch_knobs=XCD + [{"stream_nt": 0}])
+        if cap == 2048:
+            assert xcd_blocks_ok(info["stream_blocks"]), info["stream_blocks"]
 
 
 @DTYPES
@@ -543,4 +545,9 @@ def test_full_size_powerlaw_fp32_every_row(gpu, oracle):
         assert info["tile_entries"] + info["tile_long_entries"] + info["tile_mid_entries"] == info["nz"]
         y0, y1 = run(d0, case.x, sp.CSR_AUTO), run(d1, case.xs, sp.CSR_AUTO)
         case.identity(y1, y0, what="powerlaw fp32")
+        # the same plan through its gather passes (no expanded x), plain and gathering one pass early: the same bits,
+        # from the instantiations with the streamed-once hint that only a handle of this size launches
+        for kv in ({"tile_expand": 0}, {"tile_expand": 0, "tile_gather_ahead": 1}):
+            with tuned(**kv):
+                assert_same_numbers(run(d1, case.xs, sp.CSR_AUTO), y1, f"powerlaw fp32 {kv}")
     case.gate(oracle, y1, case.xs, what="powerlaw fp32")

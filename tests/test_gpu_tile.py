@@ -139,6 +139,45 @@ def test_tile_kernel_expanded_x_gives_the_gather_passes_bits(gpu, oracle, dtype,
             assert dev.info()["tile_expanded_entries"] == 0
 
 
+def test_tile_kernels_above_the_streamed_once_threshold_fp64(gpu, oracle):
+    """From 128 MiB of tile data on (9.6 M fp64 entries) csr_tile loads its entries with the streamed-once hint: other
+    instantiations of the kernel.  The smallest handles that get there, 15 entries in each of 650 000 rows: columns
+    spread over x (the expanded plan, then the same handle through its gather passes, plain and one pass early: the
+    same bits) and a band (the packed plan)."""
+    rng = np.random.default_rng(78)
+    M, L = 650_000, 15
+    assert M * L * (8 + 6) > 128 << 20
+    rp = (np.arange(M + 1, dtype=np.int64) * L).astype(np.int32)
+    val = rng.uniform(-1, 1, M * L)
+    r, j = np.arange(M, dtype=np.int64)[:, None], np.arange(L, dtype=np.int64)[None, :]
+    N = 3_000_000
+    col = (j * (N // L) + r * 7919 % (N // L)).astype(np.int32).ravel()   # ascending in a row, rows far apart in x
+    x = rng.uniform(-1, 1, N)
+    with tuned(stream_tile=1, tile_rows=1024, tile_expand=1, tile_density=0, tile_pack=0, stream_local=0):
+        with sp.CsrDevice(M, N, rp, col, val) as dev:
+            info = dev.info()
+            assert info["stream_kernel"] == 3 and info["tile_staged_entries"] == 0
+            assert info["tile_expanded_entries"] >= info["tile_entries"] == M * L
+            y = dev.spmv(x, sp.CSR_STREAM)
+            assert_parity(y, oracle.csr_serial(rp, col, val, x), rp, col, val, x, what="expanded, streamed once")
+            try:
+                set_tuning("tile_expand", 0)
+                assert dev.spmv(x, sp.CSR_STREAM).tobytes() == y.tobytes(), "gather passes"
+                set_tuning("tile_gather_ahead", 1)
+                assert dev.spmv(x, sp.CSR_STREAM).tobytes() == y.tobytes(), "gather passes, one pass early"
+            finally:
+                set_tuning("tile_gather_ahead", 0)
+    N = M + 3 * L
+    col = (r + 3 * j).astype(np.int32).ravel()
+    x = rng.uniform(-1, 1, N)
+    with tuned(stream_tile=1, tile_rows=2048, stream_local=0):
+        with sp.CsrDevice(M, N, rp, col, val) as dev:
+            info = dev.info()
+            assert info["stream_kernel"] == 3 and info["tile_staged_entries"] > 0.5 * info["tile_entries"]
+            assert_parity(dev.spmv(x, sp.CSR_STREAM), oracle.csr_serial(rp, col, val, x), rp, col, val, x,
+                          what="packed, streamed once")
+
+
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 @pytest.mark.parametrize("pack", [1, 0])
 @pytest.mark.parametrize("mean,sigma", [(3, 1500), (30, 9000), (12, 200)])

@@ -272,3 +272,20 @@ def test_tile_auto_plan_decisions():
     finally:
         for k, v in (("tile_places", 0), ("stream_tile", -1), ("tile_fit", 1), ("tile_streams", 1)):
             set_tuning(k, v)
+
+
+def test_stream_kind_and_removed_tuning_keys():
+    """"stream_kind" takes -1, 0, 5 and 6 only, and setting it still works after a refusal; the keys of the removed
+    stream kernels are unknown keys.  spmv_hip_set_tuning needs no device."""
+    from sparsematrixvectormultiplication_amd.device import set_tuning
+    try:
+        for kind in (1, 2, 3, 4, 7, *range(10, 18)):
+            with pytest.raises(sp.SpmvHipError, match="stream_kind must be -1"):
+                set_tuning("stream_kind", kind)
+        for kind in (0, 5, 6, -1):
+            set_tuning("stream_kind", kind)
+        for key, value in (("pipe_wgs_per_cu", 5), ("probe_mask", 1023)):
+            with pytest.raises(sp.SpmvHipError, match=f"unknown key '{key}'"):
+                set_tuning(key, value)
+    finally:
+        set_tuning("stream_kind", -1)

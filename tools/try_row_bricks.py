@@ -45,7 +45,7 @@ for name, brick in (("natural", None), ("16x4x4", (16, 4, 4)), ("8x8x4", (8, 8, 
     with sp.CsrDevice(M, M, rp, c, v) as dev:
         dev.set_x(x)
         best = []
-        for kind, nm in ((0, "prod"), (1, "walk")):
+        for kind, nm in ((0, "prod"),):
             set_tuning("stream_kind", kind)
             ms = np.concatenate([dev.time(sp.CSR_STREAM, 2, 20, zero_y=False) for _ in range(3)])
             best.append(f"{nm} {ms.mean() * 1e3:6.1f} us ({dev.info()['algo_bytes'] / ms.mean() / 1e6 / 80:.1f} %)")

@@ -50,14 +50,6 @@ arms += [("x-window (local) cap=2048", dict(stream_kind=5, local_nt=1, stream_xc
          ("x-window (local) cap=2048 xcd=-1", dict(stream_kind=5, local_nt=1, stream_xcd=-1), "local2048", sp.CSR_STREAM),
          ] + [(f"x-window (local) cap=2048 xcd={c}", dict(stream_kind=5, local_nt=1, stream_xcd=c), "local2048", sp.CSR_STREAM)
               for c in (8, 64)]
-if os.environ.get("TUNE_ALL"):
-    arms += [(f"walk cap={cap}", dict(stream_kind=1, stream_nt=1), cap, sp.CSR_STREAM) for cap in (2048, 4096)]
-    arms += [(f"RING cap=2048 wgs/cu={w} nt={nt}", dict(stream_kind=4, stream_nt=nt, pipe_wgs_per_cu=w), 2048, sp.CSR_STREAM)
-             for w in (1, 2) for nt in (1, 0)]
-    arms += [(f"pipe cap={cap} wgs/cu={w} nt={nt}", dict(stream_kind=2, stream_nt=nt, pipe_wgs_per_cu=w), cap, sp.CSR_STREAM)
-             for cap in (2048, 4096) for w in (4,) for nt in (1,)]
-arms += [(f"PROBE cap=4096 " + name, dict(stream_kind=10 + mode), 4096, sp.CSR_STREAM)
-         for mode, name in ((0, "stream only"), (3, "all (= prod)"))]
 arms += [("subwave", {}, 2048, sp.CSR_SUBWAVE), ("wave_row", {}, 2048, sp.CSR_WAVE_ROW)]
 res = {a[0]: [] for a in arms}
 for r in range(rounds):
