@@ -34,7 +34,7 @@ inline bool x_window_runs(int local_blocks, const void *x) {
 
 // a PACKED tile plan copies its x slices as 16-byte pieces and has no gather code to fall back on: with an x that is
 // not 16-byte aligned the clamp of the last piece no longer keeps the loads inside x
-inline bool tiles_take_x(const spmv_csr_dev *m, const void *x) { return !m->tile_packed || ((uintptr_t)x & 15) == 0; }
+inline bool tiles_take_x(const spmv_csr_dev *m, const void *x) { return !m->tile.packed || ((uintptr_t)x & 15) == 0; }
 
 // (forced: a tiles-only handle has nothing else, whatever the knob says)
 inline bool tiles_run(const spmv_csr_dev *m, const void *x, bool forced) {
@@ -47,7 +47,7 @@ enum class stream_route { x_window, tiles, gather, nothing_else, unaligned_x }; 
 // that has the split can run (anything else: csr_launch_part runs everything as part 1)
 inline stream_route csr_stream_route(const spmv_csr_dev *m, const void *x, int part) {
     const bool local = x_window_runs(m->local_blocks, x) && (part < 0 || m->have_split);
-    const bool tiled = !local && m->tile_blocks > 0 && tiles_run(m, x, m->tiles_only);
+    const bool tiled = !local && m->tile.blocks > 0 && tiles_run(m, x, m->tiles_only);
     if (m->tiles_only && !tiled) return tiles_take_x(m, x) ? stream_route::nothing_else : stream_route::unaligned_x;
     return tiled ? stream_route::tiles : local ? stream_route::x_window : stream_route::gather;
 }

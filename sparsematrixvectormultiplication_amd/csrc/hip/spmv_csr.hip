@@ -1,5 +1,5 @@
 // spmv_csr.hip -- CSR side of the C-ABI: upload-time preprocessing (workgroup blocks, the
-// x-window plan, split long rows), kernel launchers, timing.  Replaces the device code of the
+// x-window plan, split long rows; the tile plans: tile_upload.hpp), kernel launchers, timing.  Replaces the device code of the
 // reference's per-matrix CSR section (/root/reference/main_cuda.cu:135-145, :149-166, :212-238,
 // :285-317, :682-685).
 #include "spmv_internal.hpp"
@@ -7,8 +7,7 @@
 #include "launch_dispatch.hpp"
 #include "upload_ops.hpp"
 
-#include "tile_plan.hpp"
-#include "tile_plan_device.hpp"
+#include "tile_upload.hpp"
 
 // ----------------------------------------------------------- CSR: upload
 namespace {
@@ -50,513 +49,6 @@ void csr_build_blocks(int M, const int *rp, int cap, int rows_cap, std::vector<i
     }
 }
 
-
-// Pieces of the rows marked in `split` for a tiled handle: cut where the column crosses a stripe of
-// `stripe_cols` columns (and every kLongPiece entries), slots numbered row by row (csr_long_finish adds a
-// row's slots in that order), but the pieces themselves ordered stripe by stripe: the launch then sweeps
-// x one L2-sized stripe at a time instead of gathering from all of it at once.
-void build_striped_pieces(int M, const int *rp, const int *col, const std::vector<unsigned char> &split,
-                          int stripe_cols, std::vector<int4> &pieces, std::vector<int4> &long_rows) {
-    struct Tagged {
-        int stripe;
-        int4 d;
-    };
-    std::vector<Tagged> tmp;
-    long_rows.clear();
-    for (int r = 0; r < M; ++r) {
-        if (!split[r]) continue;
-        const int first_slot = (int)tmp.size();
-        int e = rp[r];
-        const int end = rp[r + 1];
-        while (e < end) {
-            const int s = col[e] / stripe_cols;
-            int f = e + 1;
-            while (f < end && f - e < kLongPiece && col[f] / stripe_cols == s) ++f;
-            tmp.push_back(Tagged{s, int4{r, e, f, (int)tmp.size()}});
-            e = f;
-        }
-        long_rows.push_back(int4{r, first_slot, (int)tmp.size() - first_slot, 0});
-    }
-    std::stable_sort(tmp.begin(), tmp.end(), [](const Tagged &a, const Tagged &b) { return a.stripe < b.stripe; });
-    pieces.resize(tmp.size());
-    for (size_t k = 0; k < tmp.size(); ++k) pieces[k] = tmp[k].d;
-}
-
-// Long-row tile plan.  In: `split` marks the rows the ordinary tiles left out.  Those of them shorter than 2^21
-// entries are compacted (rows[v] = the v-th such row) and given a tile plan of their own with pos_bits = 21;
-// `split` keeps only what this plan does not take.  A block's passes are cut into work items of about equal pass
-// counts, a few thousand in all.  false: nothing to do (fewer than 2^20 entries in such rows).
-// build(rows, begin, len, pack, plan): tile_build over the compacted rows with pos_bits = 21 -- on the host or on the device
-// (len_lo, len_hi]: which of the marked rows this plan takes; kPosBits / kRowsPerBlock: 21 / 2048 for the long rows
-// (up to 2^21 - 1 entries each), 17 / as tall as the LDS takes for the middle tier of a scattered matrix
-template <typename T, typename Build>
-bool build_long_tiles(int M, int N, const int *rp, const int *row_len, int chunk,
-                      std::vector<unsigned char> &split, TilePlan<T> &plan, std::vector<int> &rows,
-                      std::vector<int4> &work, std::vector<int> &item_first, bool &packed, Build build,
-                      int len_lo = 0, int len_hi = (1 << 21) - 1, int kPosBits = 21, int kRowsPerBlock = 2048, int items = 0) {
-    if (items <= 0) items = g_tile_items;
-    rows.clear();
-    long long entries = 0;
-    for (int r = 0; r < M; ++r)
-        if (split[(size_t)r] && row_len[r] > len_lo && row_len[r] <= len_hi) {
-            rows.push_back(r);
-            entries += row_len[r];
-        }
-    if (rows.empty() || (entries < (1LL << 20) && g_tile_long < 2)) return false;  // (2: whatever the size, tests)
-    std::vector<int> vbegin(rows.size()), vlen(rows.size());
-    for (size_t v = 0; v < rows.size(); ++v) {
-        vbegin[v] = rp[rows[v]];
-        vlen[v] = row_len[rows[v]];
-    }
-    // packed (every pass staged) unless that leaves passes of a few entries each
-    packed = g_tile_pack != 0;
-    if (!build((int)rows.size(), vbegin.data(), vlen.data(), kRowsPerBlock, len_hi, kPosBits, packed, plan)) return false;
-    if (packed && plan.entries < (long long)plan.pass_desc.size() * (chunk / 8)) {
-        packed = false;
-        if (!build((int)rows.size(), vbegin.data(), vlen.data(), kRowsPerBlock, len_hi, kPosBits, false, plan)) return false;
-    }
-    for (int r : rows) split[(size_t)r] = 0;
-    // work items: ~tile_items (1008: two rounds of the 512 places) of them over all blocks, at least 4 passes each
-    const long long passes = (long long)plan.pass_desc.size();
-    const int per_item = (int)std::max<long long>(4, (passes + items - 1) / items);
-    work.clear();
-    item_first.assign(1, 0);
-    for (int b = 0; b < plan.num_blocks; ++b) {
-        for (int p = plan.block_pass[(size_t)b]; p < plan.block_pass[(size_t)b + 1]; p += per_item)
-            work.push_back(int4{b, p, std::min(p + per_item, plan.block_pass[(size_t)b + 1]), (int)work.size()});
-        item_first.push_back((int)work.size());
-    }
-    return true;
-}
-
-// Everything the tile plans of one handle consist of on the host, between planning and upload.
-template <typename T>
-struct TileBuild {
-    TilePlan<T> tiles, ltiles;
-    bool have_tiles = false, have_long_tiles = false, scattered = false;
-    bool packed = false;     // the ordinary tiles are a packed plan: every pass staged (never for scattered matrices)
-    bool lt_packed = false;  // ... the long rows' tiles
-    std::vector<int4> tile_pieces, tile_long, lt_work;
-    std::vector<int> lt_rows, lt_item_first;
-    // the middle tier of a scattered matrix (rows of g_tile_mid_lo < entries <= tile_lmax): the same kind of plan
-    TilePlan<T> mtiles;
-    bool have_mid_tiles = false, mt_packed = false;
-    std::vector<int4> mt_work;
-    std::vector<int> mt_rows, mt_item_first;
-    std::shared_ptr<TileDevArrays<T>> mtiles_dev;
-    // plans built on the device (tile_plan_device.hpp) keep their entry arrays there: the handle adopts them
-    std::shared_ptr<TileDevArrays<T>> tiles_dev, ltiles_dev;
-    std::string dev_error;  // a device build that failed with a HIP error (the host builder took over)
-};
-
-// The tile plans for rows given as (first entry, length) pairs over host arrays col / val -- a CSR matrix's rows, or
-// the rows of an HLL slab (spmv_hll.hip).  rp: the CSR row pointer when the rows ARE a CSR matrix's (then rows that
-// neither plan takes go to stripe-cut split-row pieces), nullptr otherwise (then such rows veto the plan).
-//
-// Rows per block (auto): two regimes, told apart on a sample of the rows.
-//  * banded (most entries in passes that can be staged): 32 KiB of accumulators (4096 fp64 / 8192 fp32 rows), so
-//    that two workgroups with their 32 KiB x slices share a CU (road-like, wide band: measured best of 2048 / 4096 /
-//    8192);
-//  * scattered (gather passes): what matters is that a pass spans little of x (the band all blocks gather from
-//    together must fit L2), that the blocks run in few rounds (a new round starts again at column 0) and that not
-//    too many of them are on the way at once: the tallest blocks (up to 16384 rows) that still leave ~2 per CU, ONE
-//    workgroup per CU.  Power-law matrix (fp32, 2^24 rows): 2.90 ms at 8192 rows, 1.97 ms at 16384 with one
-//    workgroup per CU, 2.39 ms with two.
-constexpr int kTileGatherMinCols = 800000;  // (auto) columns from which a tile plan with gather passes is built
-
-// din (optional): the same rows on the device (row_begin / row_len / col / val there): the plans are then built by
-// tile_build_device -- byte for byte what tile_build makes of the host arrays, which remain the fallback when a
-// device build fails with a HIP error (hcol / hval may be NULL when there is a din: then such a failure vetoes the plan).
-template <typename T>
-void tile_plan_all(int Ml, int N, const int *row_begin, const int *row_len, const int *rp, long long nz, const int *hcol,
-                   const T *hval, TileBuild<T> &tb, const TileDevInput<T> *din = nullptr) {
-    const int chunk = 2048;
-    UploadTrace trace("tile_plan_all");
-    bool dev_ok = din != nullptr;
-    std::vector<void *> dev_tmp;  // device copies of compacted row lists (long rows' plan), freed on return
-    struct FreeAll {
-        std::vector<void *> &v;
-        ~FreeAll() {
-            for (void *p : v) (void)hipFree(p);
-        }
-    } free_all{dev_tmp};
-    // one tile_build, wherever: rows [s0, s0 + rows) of the handle's row arrays (begin_h / len_h point at row s0), or --
-    // own_rows -- a row list of its own that exists on the host only
-    auto build_at = [&](int rows, const int *begin_h, const int *len_h, const int *begin_d, const int *len_d, int rpb, int lmax,
-                        int pos_bits, bool pack, long long target, int min_pass, TilePlan<T> &plan,
-                        std::shared_ptr<TileDevArrays<T>> &arrays) -> bool {
-        arrays.reset();
-        if (dev_ok) {
-            TileDevInput<T> in = *din;
-            in.row_begin = begin_d;
-            in.row_len = len_d;
-            const int rc = tile_build_device<T>(rows, N, in, len_h, rpb, lmax, g_tile_density, chunk, g_tile_balance != 0 || pos_bits != 17,
-                                                pos_bits, plan, arrays, pack, target, min_pass, tb.dev_error);
-            if (rc >= 0) return rc == 1;
-            dev_ok = false;  // a HIP error: everything from here on on the host
-            arrays.reset();
-        }
-        if (!hcol || !hval) return false;
-        return tile_build<T>(rows, N, begin_h, len_h, hcol, hval, rpb, lmax, g_tile_density, chunk, g_tile_balance != 0 || pos_bits != 17,
-                             pos_bits, plan, pack, target, min_pass);
-    };
-    std::shared_ptr<TileDevArrays<T>> probe_arrays;
-    int lmax_eff = g_tile_lmax;  // longest row of the ordinary tiles (g_tile_mid_lo once a middle tier is decided on)
-    auto build_rows = [&](int rows, int s0, int rpb, bool pack, long long target, int min_pass, TilePlan<T> &plan,
-                          std::shared_ptr<TileDevArrays<T>> &arrays) {
-        return build_at(rows, row_begin + s0, row_len + s0, din ? din->row_begin + s0 : nullptr, din ? din->row_len + s0 : nullptr, rpb,
-                        lmax_eff, 17, pack, target, min_pass, plan, arrays);
-    };
-    int rb = g_tile_rows;
-    // Which kernel: a banded matrix is built PACKED -- every pass cut at the window and staged, the sparse tails too
-    // (tile_plan.hpp) -- for the kernel instantiation without gather code, unless that leaves passes of a few entries
-    // each (entries far from the band: one window, i.e. one pass, per stray entry); anything else keeps gather passes.
-    const int banded_rows = 32768 / (int)sizeof(T);
-    // the tallest blocks a CU's LDS takes (tile_kernels.hpp): the packed kernel is built for the banded limit
-    constexpr int banded_rows_max = tile_banded_rows_max<T>();
-    constexpr int scattered_rows_max = tile_scattered_rows_max<T>();
-    bool want_pack = g_tile_pack != 0;
-    // (... or slices several times the size of the entries they serve: 32 KiB of x out of L2 for a few hundred entries
-    // costs as much as gathering them, measured on 30 uniformly random columns per row of a 1 M-column matrix)
-    auto pack_pays = [&](const TilePlan<T> &p) {
-        return p.entries >= (long long)p.pass_desc.size() * (chunk / 8) &&
-               p.staged_cols * (long long)sizeof(T) <= 2 * p.entries * (long long)(4 + sizeof(T));
-    };
-    {
-        // a slice of the matrix from its middle (rows keep their global columns)
-        const int srows = rb ? rb : banded_rows;
-        const int sample = std::min(Ml, 8 * srows), s0 = (Ml - sample) / 2;
-        TilePlan<T> probe;
-        const bool ok = build_rows(sample, s0, srows, false, 0, 0, probe, probe_arrays);
-        const bool banded = ok && probe.staged_entries * 2 >= probe.entries;
-        if (!rb) {
-            if (banded) {
-                rb = banded_rows;
-            } else {
-                rb = 16384;
-                while (rb > 2048 && (long long)Ml < 448LL * rb) rb >>= 1;  // at least ~1.75 blocks per CU
-                rb = std::min(rb, scattered_rows_max);
-                tb.scattered = true;
-            }
-        }
-        want_pack = want_pack && banded && rb <= banded_rows_max;
-        if (want_pack) {  // the same slice as a packed plan
-            const bool pok = build_rows(sample, s0, srows, true, 0, 0, probe, probe_arrays);
-            want_pack = pok && pack_pays(probe);
-        }
-        probe_arrays.reset();
-    }
-    trace.mark("sample probes");
-    tb.packed = want_pack && !tb.scattered;
-    // The middle tier (round 3).  In a scattered plan every entry is a gathered value, and the gathers are what the
-    // kernel waits for (config 5: 0.91 of 1.19 ms for the rows of up to 1024 entries).  Rows of more than mid_lo
-    // entries, compacted into blocks as tall as the LDS takes (16384 fp32 rows), put enough entries into every
-    // 32 KiB column range for the PACKED kernel: their x look-ups move to LDS like the long rows' -- when there are
-    // enough of them (2^22 entries) for the extra launch and its slabs to pay.
-    bool want_mid = false;
-    // where the tier starts: the taller the blocks (fp32: 32512 rows, fp64: 16128), the shorter the rows that still fill
-    // a column range -- config 5 (fp32): 1051 us from 128 entries on, 1031 from 96, 1023 from 64, 1014 from 48, 1046 from
-    // 32 (profiles/r3_sweep_mid_lo.txt)
-    const int mid_lo = g_tile_mid_lo > 0 ? g_tile_mid_lo : sizeof(T) == 4 ? 48 : 128;
-    if (tb.scattered && g_tile_mid && g_tile_long && !g_tile_rows && g_tile_lmax > mid_lo && g_tile_pack) {
-        long long mid_entries = 0;
-        for (int r = 0; r < Ml; ++r)
-            if (row_len[r] > mid_lo && row_len[r] <= g_tile_lmax) mid_entries += row_len[r];
-        want_mid = mid_entries >= (4LL << 20);
-        if (want_mid) lmax_eff = mid_lo;
-    }
-    // Mid-size matrices (fewer rows than kTileMinRows, but entries for four full passes on every place): only a
-    // band of dense rows pays -- the packed plan, with blocks thin enough to give every place one (their slices stay
-    // small next to their entries: 33 per row, 503 625 rows: 48.6 us in 493 blocks of 1024 rows against 68.3 us for the
-    // gather kernel and 59.5 us in 247 blocks of 2048; 50 per row, 161 070 rows: 30.8 against 39.9 us).
-    const bool mid = g_stream_tile < 0 && (long long)Ml < kTileMinRows;
-    if (mid && !tb.packed) return;
-    // (auto) tile plans pay from about 800 000 rows / columns on (kTileMinRows, kTileGatherMinCols): 5 uniformly random
-    // columns per row tie with the gather kernel at 750 000 rows (37.4 vs 37.9 us) and lose at 500 000 (28 vs 23 us); at
-    // 1.09 M rows 3 per row win 37 vs 44 us, power-law fp32 74 vs 107 us, a road-like band 24 vs 29 us.  (Before the block
-    // count was fitted to rounds the break-even was 1.5 M columns: 2 x 256 short blocks on 256 places.)
-    if (g_stream_tile < 0 && !tb.packed && N < kTileGatherMinCols) return;
-    // How many blocks: equal-work blocks finish together, so the kernel runs in ROUNDS of as many blocks as the chip
-    // holds at once (2 per CU banded, 1 scattered) and a last round of a few blocks costs a whole one -- 530 blocks on
-    // 512 places took 2 x 215 us on a dense band, 1040 on 256 five rounds instead of four on the power-law matrix.
-    // So (auto): the smallest number of rounds k for which blocks of up to the tallest height the LDS takes, closed
-    // at in_tiles / (98.5 % of k rounds' places) entries, come out as at most k rounds' worth.
-    long long target = 0;
-    if (!g_tile_rows && g_tile_balance && g_tile_fit) {
-        const int places = g_tile_places ? g_tile_places : (tb.scattered ? 1 : 2) * g_num_cus;
-        const int rows_max = tb.scattered ? scattered_rows_max : banded_rows_max;
-        long long in_tiles = 0;
-        for (int r = 0; r < Ml; ++r)
-            if (row_len[r] <= lmax_eff) in_tiles += row_len[r];
-        const long long full = std::max(1, (Ml + rb - 1) / rb);
-        const int b0 = (int)tile_cut_rows(Ml, row_len, lmax_eff, rb, std::max<long long>(chunk, (in_tiles + full - 1) / full)).size() - 1;
-        // (a matrix whose blocks fill less than 90 % of one round keeps them: thinner blocks would each read more of x)
-        const int kmax = mid ? 1 : b0 * 10LL > places * 9LL ? (b0 + places - 1) / places : 0;
-        for (int k = 1; k <= kmax; ++k) {
-            const long long want = (long long)k * places * 197 / 200;
-            const long long t = std::max<long long>(chunk, (in_tiles + want - 1) / want);
-            const int b = (int)tile_cut_rows(Ml, row_len, lmax_eff, rows_max, t).size() - 1;
-            if (b <= k * places) {
-                rb = rows_max;
-                target = t;
-                break;
-            }
-        }
-    }
-    trace.mark("block count fit");
-    tb.have_tiles = build_rows(Ml, 0, rb, tb.packed, target,
-                               // (its extra launch costs ~2 us: not for matrices whose whole product takes 25)
-                               nz >= (16LL << 20) || g_stream_tile == 1 ? g_tile_min_pass : 0, tb.tiles, tb.tiles_dev);
-    // (the remainder is for a few per cent of far-out entries: more than 4 % and the plan is rebuilt without one)
-    if (tb.have_tiles && tb.packed && (long long)tb.tiles.rem_row.size() * 25 > tb.tiles.entries)
-        tb.have_tiles = build_rows(Ml, 0, rb, tb.packed, target, 0, tb.tiles, tb.tiles_dev);
-    // (the whole matrix may differ from the sample)
-    if (tb.have_tiles && tb.packed && !pack_pays(tb.tiles)) {
-        tb.packed = false;
-        if (g_stream_tile < 0 && N < kTileGatherMinCols) {
-            tb.have_tiles = false;
-            return;
-        }
-        tb.have_tiles = build_rows(Ml, 0, rb, false, target, 0, tb.tiles, tb.tiles_dev);
-    }
-    // (auto) a matrix made mostly of rows beyond the tile limit gains nothing without the long rows' plan
-    if (tb.have_tiles && g_stream_tile < 0 && !g_tile_long && tb.tiles.entries * 2 < nz) tb.have_tiles = false;
-    if (!tb.have_tiles) return;
-    trace.mark("ordinary tiles");
-    // one workgroup per place of the chip walks several blocks back to back (tile_streams 0: one workgroup per block)
-    // (tile_places: tests walk long streams on small matrices)
-    tile_make_streams(tb.tiles, !g_tile_streams ? 0x3fffffff : g_tile_places ? g_tile_places : (tb.scattered ? 1 : 2) * g_num_cus);
-    // The rows beyond the tile limit, compacted: their own row blocks (<= 2048 of them each), same passes -- so many
-    // entries per column range that every pass is staged: the long rows' x lookups happen in LDS at the HBM streaming
-    // rate instead of going through the gather path -- and a block's passes dealt out to many workgroups.
-    std::vector<unsigned char> leftover = tb.tiles.split;
-    if (g_tile_long)
-        tb.have_long_tiles = build_long_tiles<T>(
-            Ml, N, row_begin, row_len, chunk, leftover, tb.ltiles, tb.lt_rows, tb.lt_work, tb.lt_item_first, tb.lt_packed,
-            [&](int rows, const int *begin_h, const int *len_h, int rpb, int lmax, int pos_bits, bool pack, TilePlan<T> &plan) {
-                int *d_begin = nullptr, *d_len = nullptr;
-                if (dev_ok) {  // the compacted row list exists on the host only: a device copy for this build
-                    if (upload_array(&d_begin, begin_h, (size_t)rows, 1) == 0) dev_tmp.push_back(d_begin);
-                    else dev_ok = false;
-                    if (dev_ok && upload_array(&d_len, len_h, (size_t)rows, 1) == 0) dev_tmp.push_back(d_len);
-                    else dev_ok = false;
-                }
-                return build_at(rows, begin_h, len_h, d_begin, d_len, rpb, lmax, pos_bits, pack, 0, 0, plan, tb.ltiles_dev);
-            },
-            want_mid ? g_tile_lmax : 0);  // (with a middle tier the long rows' plan starts behind it)
-    // the middle tier: what the ordinary tiles left out up to tile_lmax (the long rows' plan has taken the rest)
-    if (want_mid && tb.have_tiles)
-        tb.have_mid_tiles = build_long_tiles<T>(
-            Ml, N, row_begin, row_len, chunk, leftover, tb.mtiles, tb.mt_rows, tb.mt_work, tb.mt_item_first, tb.mt_packed,
-            [&](int rows, const int *begin_h, const int *len_h, int rpb, int lmax, int pos_bits, bool pack, TilePlan<T> &plan) {
-                if (!pack) return false;  // (a middle tier with gather passes would be the ordinary tiles again, plus slabs)
-                int *d_begin = nullptr, *d_len = nullptr;
-                if (dev_ok) {
-                    if (upload_array(&d_begin, begin_h, (size_t)rows, 1) == 0) dev_tmp.push_back(d_begin);
-                    else dev_ok = false;
-                    if (dev_ok && upload_array(&d_len, len_h, (size_t)rows, 1) == 0) dev_tmp.push_back(d_len);
-                    else dev_ok = false;
-                }
-                return build_at(rows, begin_h, len_h, d_begin, d_len, rpb, lmax, pos_bits, pack, 0, 0, plan, tb.mtiles_dev);
-            },
-            // (its blocks fill a CU's LDS: one workgroup per CU, so whole rounds of the CUs -- three of them: config 5
-            // 1008 / 954 / 898 / 918 / 943 / 996 us at 256 / 512 / 768 / 1008 / 1280 / 2016 items, profiles/r3_sweep_mid_items.txt)
-            mid_lo, g_tile_lmax, 17, scattered_rows_max, g_tile_mid_items ? g_tile_mid_items : 3 * std::max(g_num_cus, 1));
-    if (want_mid && tb.have_tiles && (!tb.have_mid_tiles || !tb.mt_packed)) {
-        // the tier did not come about (its passes would average fewer than 256 entries, or its build failed): the plan
-        // without one, from the start -- the ordinary tiles then take the rows up to tile_lmax again
-        const int keep = g_tile_mid;
-        g_tile_mid = 0;
-        tb = TileBuild<T>();
-        tile_plan_all<T>(Ml, N, row_begin, row_len, rp, nz, hcol, hval, tb, din);
-        g_tile_mid = keep;
-        return;
-    }
-    trace.mark("streams, long rows' tiles");
-    bool any_left = false;
-    for (unsigned char f : leftover) any_left |= f != 0;
-    if (!any_left) return;
-    if (!rp) {  // no CSR arrays on the device to fall back on
-        tb.have_tiles = tb.have_long_tiles = false;
-        return;
-    }
-    // whatever is left (rows of 2^21 entries and more, or all long rows with tile_long = 0) stays with the split-row
-    // kernels, pieces cut at stripes of 1 MiB of x: a quarter of an XCD's L2
-    const int stripe_cols = (1 << 20) / (int)sizeof(T);
-    build_striped_pieces(Ml, rp, hcol, leftover, stripe_cols, tb.tile_pieces, tb.tile_long);
-}
-
-// csr_tile asks for up to a CU's whole LDS as dynamic shared memory; HIP wants that allowed per kernel beyond
-// 64 KiB.  Done once per value type, at upload (not at launch: a launch may sit inside a graph capture).
-template <typename T>
-int tile_allow_lds() {
-    // the attribute belongs to (function, device): spmv_hip_init may have switched devices since the last upload
-    static int done_for_device = -1;
-    const bool done = done_for_device == g_device;
-    if (done) return 0;
-    constexpr int kXpTrips = 2048 * (int)sizeof(T) / kTileTripBytes;  // the expanded plans' instantiation
-    const void *fns[8] = {(const void *)csr_tile<T, false, 2048, kXpTrips, true>, (const void *)csr_tile<T, true, 2048, kXpTrips, true>,
-                          (const void *)csr_tile<T, false, 2048, kTileTrips, false>, (const void *)csr_tile<T, true, 2048, kTileTrips, false>,
-                          (const void *)csr_tile<T, false, 2048, kTileTrips, true>, (const void *)csr_tile<T, true, 2048, kTileTrips, true>,
-                          (const void *)csr_tile<T, false, 2048, kTileTrips, false, true>,
-                          (const void *)csr_tile<T, true, 2048, kTileTrips, false, true>};
-    for (const void *fn : fns) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    done_for_device = g_device;
-    return 0;
-}
-
-// the plans' arrays -> the handle
-template <typename T>
-int tile_upload_all(spmv_csr_dev *m, const TileBuild<T> &tb) {
-    int rc = 0;
-    // the kernels need more than 64 KiB of dynamic LDS: where the device will not allow that the handle simply gets
-    // no tiles and keeps its gather kernels (return 1; the message stays in spmv_hip_last_error)
-    if ((tb.have_tiles || tb.have_long_tiles || tb.have_mid_tiles) && tile_allow_lds<T>()) return 1;
-    if (tb.have_tiles) {
-        const TilePlan<T> &tiles = tb.tiles;
-        // (the kernel walks STREAMS: descriptors in stream order, the passes / blocks of every stream, the blocks' rows)
-        rc |= upload_array(&m->tile_block_pass, tiles.stream_pass.data(), tiles.stream_pass.size(), 1);
-        if (!rc) rc |= upload_array(&m->tile_block_row, tiles.block_row.data(), tiles.block_row.size(), 1);
-        if (!rc) rc |= upload_array(&m->tile_pass, tiles.spass.data(), tiles.spass.size(), 1);
-        TileDevArrays<T> *dev = tb.tiles_dev.get();  // built on the device: the entry arrays are there already
-        if (!rc && !tiles.rem_row.empty()) {  // remainder: rows that have any, their entry ranges
-            std::vector<int> rrow, rptr;
-            for (size_t k = 0; k < tiles.rem_row.size(); ++k) {
-                if (rrow.empty() || rrow.back() != tiles.rem_row[k]) {
-                    rrow.push_back(tiles.rem_row[k]);
-                    rptr.push_back((int)k);
-                }
-            }
-            rptr.push_back((int)tiles.rem_row.size());
-            rc |= upload_array(&m->tile_rem_row, rrow.data(), rrow.size(), 0);
-            if (!rc) rc |= upload_array(&m->tile_rem_ptr, rptr.data(), rptr.size(), 0);
-            if (!rc && dev) {
-                m->tile_rem_col = dev->rem_col;
-                m->tile_rem_val = dev->rem_val;
-                dev->rem_col = nullptr;
-                dev->rem_val = nullptr;
-            }
-            if (!rc && !dev) rc |= upload_array(&m->tile_rem_col, tiles.rem_col.data(), tiles.rem_col.size(), 0);
-            if (!rc && !dev) rc |= upload_array((T **)&m->tile_rem_val, tiles.rem_val.data(), tiles.rem_val.size(), 0);
-            if (!rc) {
-                m->tile_rem_rows = (int)rrow.size();
-                m->tile_rem_entries = (long long)tiles.rem_row.size();
-                m->device_bytes += rrow.size() * 8 + tiles.rem_row.size() * (4 + sizeof(T));
-            }
-        }
-        if (!rc) rc |= upload_array(&m->tile_stream_block, tiles.stream_block.data(), tiles.stream_block.size(), 1);
-        if (!rc) rc |= upload_array(&m->tile_sblock_rows, tiles.sblock_rows.data(), tiles.sblock_rows.size(), 1);
-        const size_t tcol_count = dev ? dev->tcol_count : tiles.tcol.size(), tkey_count = dev ? dev->tkey_count : tiles.tkey.size();
-        if (!rc && dev) {
-            m->tcol = dev->tcol;
-            m->tkey = dev->tkey;
-            m->tval = dev->tval;
-            dev->tcol = nullptr;
-            dev->tkey = nullptr;
-            dev->tval = nullptr;
-        }
-        if (!rc && !dev) rc |= upload_array(&m->tcol, tiles.tcol.data(), tiles.tcol.size(), 0);
-        if (!rc && !dev) rc |= upload_array(&m->tkey, tiles.tkey.data(), tiles.tkey.size(), 0);
-        if (!rc && !dev) rc |= upload_array((T **)&m->tval, tiles.tval.data(), tiles.tval.size(), 0);
-        if (!rc && !tb.tile_long.empty()) rc |= upload_array(&m->tile_long_rows, tb.tile_long.data(), tb.tile_long.size(), 0);
-        if (!rc && !tb.tile_pieces.empty()) rc |= upload_array(&m->tile_pieces, tb.tile_pieces.data(), tb.tile_pieces.size(), 0);
-        if (!rc) {
-            m->tile_blocks = tiles.num_blocks;
-            m->tile_streams = tiles.num_streams;
-            m->tile_rows = tiles.rows_per_block;
-            m->tile_chunk = tiles.chunk;
-            m->tile_packed = tb.packed;
-            m->tile_lds_min = tb.scattered ? 84 * 1024 : 0;  // more than half a CU's LDS: one workgroup per CU
-            m->tile_passes = (int)tiles.pass_desc.size();
-            m->tile_max_win = tiles.max_win;
-            m->tile_entries = tiles.entries;
-            m->tile_staged = tiles.staged_entries;
-            m->tile_staged_cols = tiles.staged_cols;
-            m->tile_padded = (long long)tcol_count - kTileChunkMax;
-            m->tile_num_long = (int)tb.tile_long.size();
-            m->tile_num_pieces = (int)tb.tile_pieces.size();
-            m->device_bytes += tcol_count * (4 + sizeof(T)) + tkey_count * 2 + tiles.pass_desc.size() * 16 + tiles.block_pass.size() * 4 +
-                               (tb.tile_pieces.size() + tb.tile_long.size()) * 16;
-        }
-    }
-    // a compacted tier (the long rows' plan, the middle tier): block tables, work items, entry arrays, slabs
-    auto upload_tier = [&](const TilePlan<T> &ltiles, TileDevArrays<T> *ldev, const std::vector<int> &rows,
-                           const std::vector<int4> &work, const std::vector<int> &item_first, bool packed,
-                           spmv_csr_dev::long_tiles &L) {
-        std::vector<int> block_of_row(rows.size());
-        for (int b = 0; b < ltiles.num_blocks; ++b)
-            for (int v = ltiles.block_row[(size_t)b]; v < ltiles.block_row[(size_t)b + 1]; ++v) block_of_row[(size_t)v] = b;
-        rc |= upload_array(&L.block_row, ltiles.block_row.data(), ltiles.block_row.size(), 1);
-        if (!rc) rc |= upload_array(&L.block_pass, ltiles.block_pass.data(), ltiles.block_pass.size(), 1);
-        if (!rc) rc |= upload_array(&L.block_of_row, block_of_row.data(), block_of_row.size(), 1);
-        if (!rc) rc |= upload_array(&L.item_first, item_first.data(), item_first.size(), 1);
-        if (!rc) rc |= upload_array(&L.row_map, rows.data(), rows.size(), 1);
-        if (!rc) rc |= upload_array(&L.pass, ltiles.pass_desc.data(), ltiles.pass_desc.size(), 1);
-        if (!rc) rc |= upload_array(&L.work, work.data(), work.size(), 1);
-        const size_t ltcol_count = ldev ? ldev->tcol_count : ltiles.tcol.size(), ltkey_count = ldev ? ldev->tkey_count : ltiles.tkey.size();
-        if (!rc && ldev) {
-            L.tcol = ldev->tcol;
-            L.tkey = ldev->tkey;
-            L.tval = ldev->tval;
-            ldev->tcol = nullptr;
-            ldev->tkey = nullptr;
-            ldev->tval = nullptr;
-        }
-        if (!rc && !ldev) rc |= upload_array(&L.tcol, ltiles.tcol.data(), ltiles.tcol.size(), 0);
-        if (!rc && !ldev) rc |= upload_array(&L.tkey, ltiles.tkey.data(), ltiles.tkey.size(), 0);
-        if (!rc && !ldev) rc |= upload_array((T **)&L.tval, ltiles.tval.data(), ltiles.tval.size(), 0);
-        if (!rc) {
-            const size_t slab_bytes = std::max<size_t>(1, work.size()) * (size_t)ltiles.rows_per_block * sizeof(T);
-            hipError_t e = hipMalloc(&L.slab, slab_bytes);
-            if (e != hipSuccess) rc = fail("hipMalloc(slabs) failed: %s", hipGetErrorString(e));
-            m->device_bytes += slab_bytes;
-        }
-        if (!rc) {
-            L.blocks = ltiles.num_blocks;
-            L.rows = (int)rows.size();
-            L.rows_per_block = ltiles.rows_per_block;
-            L.passes = (int)ltiles.pass_desc.size();
-            L.items = (int)work.size();
-            L.max_win = ltiles.max_win;
-            L.entries = ltiles.entries;
-            L.padded = (long long)ltcol_count - kTileChunkMax;
-            L.staged = ltiles.staged_entries;
-            L.staged_cols = ltiles.staged_cols;
-            L.packed = packed;
-            m->device_bytes += ltcol_count * (4 + sizeof(T)) + ltkey_count * 2 + ltiles.pass_desc.size() * 16 + work.size() * 16 +
-                               rows.size() * 8;
-        }
-    };
-    // a plan whose passes gather (scattered columns: next to none of them dense enough to stage) runs on an expanded x:
-    // tile_expand walks the entries slice by slice of x and writes every entry's value into its pass's segment of x',
-    // which csr_tile<.., PACK> stages as that pass's window (tile_kernels.hpp).  The same products in the same order:
-    // the same bits as the gather passes.
-    // auto: plans from 2^22 entries on with fewer than a tenth of them in staged passes -- fp32 always (uniformly random
-    // columns, 2 M x 10 ... 16 M x 8: -17 ... -37 %; config 5's short rows 491 -> 141 + 180 us), fp64 when x is beyond
-    // 100 MB: an fp64 gather brings twice the bytes per line and the expansion moves twice the bytes per entry -- 4 M x
-    // 20: 518 -> 539 us, 12 M x 4: 462 -> 454, 16 M x 8: 1095 -> 939 (profiles/r3_ab_expand.txt)
-    // ("tile_expand" 0: never, 1: always)
-    const bool expand_pays = sizeof(T) == 4 || (long long)m->N * (long long)sizeof(T) >= (100LL << 20);
-    if (!rc && tb.have_tiles && !tb.packed && m->tcol && m->tile_padded > 0 &&
-        (g_tile_expand > 0 || (g_tile_expand < 0 && expand_pays && m->tile_entries >= (1 << 22) &&
-                               m->tile_staged * 10 <= m->tile_entries))) {
-        const size_t slots = (size_t)m->tile_padded;
-        m->expansion = new (std::nothrow) TileExpansion();
-        if (!m->expansion) return fail("csr_upload: out of host memory");
-        std::string err;
-        if (tile_build_expansion<T>(m->N, m->tcol, m->tkey, slots, m->tile_pass, (int)tb.tiles.spass.size(), g_stream, *m->expansion, err) < 0)
-            return fail("%s", err.c_str());
-        const size_t xe_bytes = (slots + kTileChunkMax) * sizeof(T);
-        hipError_t e = hipMalloc(&m->xe, xe_bytes);
-        if (e == hipSuccess) e = hipMemsetAsync(m->xe, 0, xe_bytes, g_stream);
-        if (e != hipSuccess) return fail("hipMalloc(expanded x) failed: %s", hipGetErrorString(e));
-        m->device_bytes += xe_bytes + (slots + 64) * 2 + (slots + kTileChunkMax) * 4 + tb.tiles.spass.size() * 16 +
-                           (size_t)m->expansion->chunks * 24 + (m->expansion->runs + m->expansion->groups) * 4;
-    }
-    if (!rc && tb.have_long_tiles) upload_tier(tb.ltiles, tb.ltiles_dev.get(), tb.lt_rows, tb.lt_work, tb.lt_item_first, tb.lt_packed, m->lt);
-    if (!rc && tb.have_mid_tiles) upload_tier(tb.mtiles, tb.mtiles_dev.get(), tb.mt_rows, tb.mt_work, tb.mt_item_first, tb.mt_packed, m->mt);
-    return rc;
-}
 
 bool csr_build_local(int M, int N, const int *rp, const int *col, long long nz, int cap, int rows_cap,
                      int line_shift, int lines_max, const std::vector<int4> &baseline, LocalPlan &plan) {
@@ -827,12 +319,17 @@ int csr_upload_impl(int M, int N, const int *row_ptr, const int *col_idx, const 
     trace.mark("column check");
     spmv_csr_dev *m = new (std::nothrow) spmv_csr_dev();
     if (!m) return fail("csr_upload: out of host memory");
-    // on failure adopted arrays go back to the caller untouched
-    auto drop = [&](spmv_csr_dev *h) {
-        if (adopt_col) h->col = nullptr;
-        if (adopt_val) h->val = nullptr;
-        spmv_hip_csr_free(h);
-    };
+    // owns the handle until it is handed out: on any failure it is freed, adopted arrays go back to the caller untouched
+    struct Drop {
+        spmv_csr_dev *h;
+        bool keep_col, keep_val;
+        ~Drop() {
+            if (!h) return;
+            if (keep_col) h->col = nullptr;
+            if (keep_val) h->val = nullptr;
+            spmv_hip_csr_free(h);
+        }
+    } drop{m, adopt_col != nullptr, adopt_val != nullptr};
     m->value_bytes = (int)sizeof(T);
     m->M_local = Ml;
     m->M_total = M;
@@ -846,10 +343,7 @@ int csr_upload_impl(int M, int N, const int *row_ptr, const int *col_idx, const 
     int max_row = 0;
     for (int r = 0; r <= Ml; ++r) rp[r] = row_ptr[row0 + r] - e0;
     for (int r = 0; r < Ml; ++r) {
-        if (rp[r + 1] < rp[r]) {
-            delete m;
-            return fail("csr_upload: row_ptr decreases at row %d", row0 + r);
-        }
+        if (rp[r + 1] < rp[r]) return fail("csr_upload: row_ptr decreases at row %d", row0 + r);
         max_row = std::max(max_row, rp[r + 1] - rp[r]);
     }
     m->max_row = max_row;
@@ -872,25 +366,17 @@ int csr_upload_impl(int M, int N, const int *row_ptr, const int *col_idx, const 
         // otherwise the host builder decides (line-limited blocks, split rows, or no plan)
         int dev = 0;
         if (g_plan_on_device && lcap == kPlanCap) {
-            if (!m->col && upload_array(&m->col, col_idx + e0, (size_t)nz, kPad)) {
-                drop(m);
-                return -1;
-            }
+            if (!m->col && upload_array(&m->col, col_idx + e0, (size_t)nz, kPad)) return -1;
             dev = csr_plan_on_device<line_shift>(m, desc, nz);
-            if (dev < 0) {
-                drop(m);
-                return -1;
-            }
+            if (dev < 0) return -1;
         }
         on_device = dev == 1;
         const bool refused = dev == 2;  // plainly scattered columns: no plan, and no need to ask the host builder
         std::vector<int> col_back;  // adopted arrays live on the device only: the host builder needs a copy
         if (!on_device && !refused && !col_idx) {
             col_back.resize((size_t)nz);
-            if (hipMemcpy(col_back.data(), m->col, (size_t)nz * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) {
-                drop(m);
+            if (hipMemcpy(col_back.data(), m->col, (size_t)nz * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
                 return fail("csr_upload: copying the columns back for the host plan failed");
-            }
         }
         have_local = on_device ||
                      (!refused &&
@@ -915,10 +401,8 @@ int csr_upload_impl(int M, int N, const int *row_ptr, const int *col_idx, const 
             col_copy.resize((size_t)nz);
             val_copy.resize((size_t)nz);
             if (hipMemcpy(col_copy.data(), m->col, (size_t)nz * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
-                hipMemcpy(val_copy.data(), m->val, (size_t)nz * sizeof(T), hipMemcpyDeviceToHost) != hipSuccess) {
-                drop(m);
+                hipMemcpy(val_copy.data(), m->val, (size_t)nz * sizeof(T), hipMemcpyDeviceToHost) != hipSuccess)
                 return fail("csr_upload: copying the matrix back for the tile plan failed");
-            }
             hcol = col_copy.data();
             hval = val_copy.data();
         }
@@ -937,7 +421,6 @@ int csr_upload_impl(int M, int N, const int *row_ptr, const int *col_idx, const 
             if (!urc) urc |= upload_array(&d_row_len, row_len.data(), row_len.size(), 1);
             if (urc) {
                 (void)hipFree(d_row_len);
-                drop(m);
                 return -1;
             }
             din.row_begin = m->row_ptr;
@@ -1022,10 +505,7 @@ int csr_upload_impl(int M, int N, const int *row_ptr, const int *col_idx, const 
         if (e == hipSuccess) e = hipMemset(m->y, 0, std::max<size_t>((size_t)M, 1) * sizeof(T));
         if (e != hipSuccess) rc = fail("hipMalloc(x/y) failed: %s", hipGetErrorString(e));
     }
-    if (rc) {
-        drop(m);
-        return -1;
-    }
+    if (rc) return -1;
     m->device_bytes = rp.size() * 4 + ((size_t)nz + kPad) * (4 + sizeof(T)) + desc.size() * 16 +
                       long_rows.size() * 16 + pieces.size() * 16 + (size_t)num_partial * sizeof(T) +
                       ((size_t)N + (size_t)M) * sizeof(T);
@@ -1044,15 +524,16 @@ int csr_upload_impl(int M, int N, const int *row_ptr, const int *col_idx, const 
     // beats the gather stream kernels by 3-10 % on every such stand-in of the reference's list (cop20k_A-size 19.2 vs
     // 21.2 us, PR02R-size 37 vs 41, amazon0302-size 12.1 vs 13.5; profiles/r2_reference_list_stand_ins.md) -- unless rows
     // are skewed (its lanes per row are fixed), and not on large ones (road-like 12 M rows: 282 vs 255 us).
-    if (!have_local && !tb.have_tiles && nz < (20LL << 20) && max_row <= std::max(64.0, 8.0 * mean))
+    if (!have_local && !tb.tiles.have && nz < (20LL << 20) && max_row <= std::max(64.0, 8.0 * mean))
         m->auto_variant = SPMV_CSR_SUBWAVE;
     trace.mark("blocks, remaining uploads, vectors");
     // the searches (upload_ops.hpp); the placement of m->val where it is large and streamed by the handle's kernel (a
     // tile plan without an x-window plan streams its own re-ordered copy)
-    const bool place = (size_t)nz * sizeof(T) >= kPlaceMinBytes && !m->tiles_only && (m->local_blocks > 0 || m->tile_blocks == 0);
+    const bool place = (size_t)nz * sizeof(T) >= kPlaceMinBytes && !m->tiles_only && (m->local_blocks > 0 || m->tile.blocks == 0);
     upload_searches(m, Ml, place ? &m->val : nullptr, ((size_t)nz + kPad) * sizeof(T),
                     [m] { return csr_launch_any(m, SPMV_CSR_AUTO, m->x, m->y, g_stream); });
     trace.mark("placement tuning");
+    drop.h = nullptr;
     *out = m;
     return 0;
 }
@@ -1362,20 +843,20 @@ static int tile_auto_plan(int M, int N, const int *rp, const int *col, long long
     TileBuild<T> tb;
     tile_plan_all<T>(M, N, rp, row_len.data(), rp, nz, col, val.data(), tb);
     for (int k = 0; k < 10; ++k) stats[k] = 0;
-    stats[0] = tb.have_tiles;
-    if (!tb.have_tiles) return 0;
+    stats[0] = tb.tiles.have;
+    if (!tb.tiles.have) return 0;
+    const TilePlan<T> &tiles = tb.tiles.plan;
     int tallest = 0;
-    for (int b = 0; b < tb.tiles.num_blocks; ++b)
-        tallest = std::max(tallest, tb.tiles.block_row[(size_t)b + 1] - tb.tiles.block_row[(size_t)b]);
-    stats[1] = tb.packed;
+    for (int b = 0; b < tiles.num_blocks; ++b) tallest = std::max(tallest, tiles.block_row[(size_t)b + 1] - tiles.block_row[(size_t)b]);
+    stats[1] = tb.tiles.packed;
     stats[2] = tb.scattered;
-    stats[3] = tb.tiles.rows_per_block;
-    stats[4] = tb.tiles.num_blocks;
-    stats[5] = tb.tiles.num_streams;
-    stats[6] = (long long)tb.tiles.pass_desc.size();
+    stats[3] = tiles.rows_per_block;
+    stats[4] = tiles.num_blocks;
+    stats[5] = tiles.num_streams;
+    stats[6] = (long long)tiles.pass_desc.size();
     stats[7] = tallest;
-    stats[8] = tb.have_long_tiles ? (long long)tb.lt_work.size() : 0;
-    stats[9] = tb.tiles.entries;
+    stats[8] = tb.lt.have ? (long long)tb.lt.work.size() : 0;
+    stats[9] = tiles.entries;
     return 0;
 }
 
@@ -1406,6 +887,8 @@ int csr_adopt_f32(int M, int N, const int *row_ptr_host, int *d_col, float *d_va
 // how an HLL slab whose columns are too scattered for the x-window plan gets csr_tile (spmv_hll.hip).  The rows
 // are rows [row0, row0 + M_local) of a matrix with M_total rows; launched with the caller's x and full-length y.
 // *out stays NULL (return 0) when the rows get no plan.
+// (Defined here, behind the uploads above, and not with the rest of the tile orchestration in tile_upload.hpp: the order in
+// which this translation unit first names tile_plan_all<float> and <double> is the order of their kernels in its code object.)
 int csr_tiles_from_rows_f64(int M_local, int M_total, int row0, int N, const int *row_begin, const int *row_len,
                             long long entries, const int *col, const double *val, spmv_csr_dev **out,
                             const int *d_col, const double *d_val) {
@@ -1430,7 +913,7 @@ int csr_tiles_from_rows_f64(int M_local, int M_total, int row0, int N, const int
         tile_plan_all<double>(M_local, N, row_begin, row_len, nullptr, entries, col, val, tb, on_dev ? &din : nullptr);
         (void)hipFree(d_begin);
         (void)hipFree(d_len);
-        if (!tb.have_tiles) return 0;
+        if (!tb.tiles.have) return 0;
         spmv_csr_dev *m = new (std::nothrow) spmv_csr_dev();
         if (!m) return fail("hll tile plan: out of host memory");
         m->value_bytes = 8;
@@ -1478,6 +961,13 @@ extern "C" int spmv_hip_csr_upload_matrix(const CSRMatrix *csr, spmv_csr_dev **o
     return spmv_hip_csr_upload(csr->M, csr->N, csr->row_ptr, csr->col_idx, csr->values, 0, csr->M, out);
 }
 
+// (here: the expansion is a complete type in this translation unit)
+void OwnTiles::release() {
+    free_all(arrays());
+    delete expansion;
+    *this = OwnTiles();
+}
+
 extern "C" void spmv_hip_csr_free(spmv_csr_dev *m) {
     if (!m) return;
     spmv_hip_csr_free(m->own_part);
@@ -1496,48 +986,11 @@ extern "C" void spmv_hip_csr_free(spmv_csr_dev *m) {
     (void)hipFree(m->lbase);
     (void)hipFree(m->lcol);
     m->pat.release();
-    for (spmv_csr_dev::long_tiles *tier : {&m->mt}) {
-        (void)hipFree(tier->block_row);
-        (void)hipFree(tier->block_pass);
-        (void)hipFree(tier->block_of_row);
-        (void)hipFree(tier->item_first);
-        (void)hipFree(tier->row_map);
-        (void)hipFree(tier->pass);
-        (void)hipFree(tier->work);
-        (void)hipFree(tier->tcol);
-        (void)hipFree(tier->tkey);
-        (void)hipFree(tier->tval);
-        (void)hipFree(tier->slab);
-    }
-    (void)hipFree(m->lt.block_row);
-    (void)hipFree(m->lt.block_pass);
-    (void)hipFree(m->lt.block_of_row);
-    (void)hipFree(m->lt.item_first);
-    (void)hipFree(m->lt.row_map);
-    (void)hipFree(m->lt.pass);
-    (void)hipFree(m->lt.work);
-    (void)hipFree(m->lt.tcol);
-    (void)hipFree(m->lt.tkey);
-    (void)hipFree(m->lt.tval);
-    (void)hipFree(m->lt.slab);
+    m->tile.release();
+    m->lt.release();
+    m->mt.release();
     (void)hipFree(m->interior_ids);
     (void)hipFree(m->boundary_ids);
-    (void)hipFree(m->tile_block_pass);
-    (void)hipFree(m->tile_block_row);
-    (void)hipFree(m->tile_pass);
-    (void)hipFree(m->tile_rem_row);
-    (void)hipFree(m->tile_rem_ptr);
-    (void)hipFree(m->tile_rem_col);
-    (void)hipFree(m->tile_rem_val);
-    (void)hipFree(m->tile_stream_block);
-    (void)hipFree(m->tile_sblock_rows);
-    (void)hipFree(m->tcol);
-    (void)hipFree(m->tkey);
-    (void)hipFree(m->tval);
-    (void)hipFree(m->xe);
-    delete m->expansion;
-    (void)hipFree(m->tile_long_rows);
-    (void)hipFree(m->tile_pieces);
     (void)hipFree(m->long_rows);
     (void)hipFree(m->pieces);
     (void)hipFree(m->partial);
@@ -1676,33 +1129,19 @@ extern "C" int spmv_hip_csr_stamp_blocks(spmv_csr_dev *m, int warm, unsigned lon
 // out[2 k] = elements, out[2 k + 1] = FNV-1a of the bytes of array k, in the order tcol, tkey, tval, pass descriptors
 // (stream order), stream_pass, block_row, stream_block, sblock_rows, rem_row, rem_ptr, rem_col, rem_val, then the long
 // rows' plan: tcol, tkey, tval, pass, block_row, block_pass, work, item_first, row_map, block_of_row, and the same ten
-// for the middle tier.  32 arrays.
+// for the middle tier: the tiers' own lists (arrays(), spmv_internal.hpp) without what they mark as scratch.  32 arrays.
 int csr_tile_digest(const spmv_csr_dev *m, unsigned long long *out) {
     if (need_device()) return -1;
     if (!m || !out) return fail("csr_tile_digest: NULL argument");
     HIP_TRY(hipStreamSynchronize(g_stream));
     const size_t vb = (size_t)m->value_bytes;
-    struct Arr { const void *p; size_t count, elem; };
-    const size_t tpad = m->tile_blocks > 0 ? (size_t)m->tile_padded + kTileChunkMax : 0;
-    std::vector<Arr> arrs = {
-        {m->tcol, tpad, 4}, {m->tkey, m->tile_packed ? (tpad ? (size_t)kTileChunkMax : 0) : tpad, 2}, {m->tval, tpad, vb},
-        {m->tile_pass, (size_t)m->tile_passes, 16}, {m->tile_block_pass, m->tile_blocks > 0 ? (size_t)m->tile_streams + 1 : 0, 4},
-        {m->tile_block_row, m->tile_blocks > 0 ? (size_t)m->tile_blocks + 1 : 0, 4},
-        {m->tile_stream_block, m->tile_blocks > 0 ? (size_t)m->tile_streams + 1 : 0, 4}, {m->tile_sblock_rows, (size_t)m->tile_blocks, 8},
-        {m->tile_rem_row, (size_t)m->tile_rem_rows, 4}, {m->tile_rem_ptr, m->tile_rem_rows > 0 ? (size_t)m->tile_rem_rows + 1 : 0, 4},
-        {m->tile_rem_col, (size_t)m->tile_rem_entries, 4}, {m->tile_rem_val, (size_t)m->tile_rem_entries, vb}};
-    for (const spmv_csr_dev::long_tiles *tier : {&m->lt, &m->mt}) {
-        const auto &L = *tier;
-        const size_t lpad = L.items > 0 ? (size_t)L.padded + kTileChunkMax : 0;
-        const Arr more[10] = {{L.tcol, lpad, 4}, {L.tkey, L.packed ? (lpad ? (size_t)kTileChunkMax : 0) : lpad, 2}, {L.tval, lpad, vb},
-                              {L.pass, (size_t)L.passes, 16}, {L.block_row, L.items > 0 ? (size_t)L.blocks + 1 : 0, 4},
-                              {L.block_pass, L.items > 0 ? (size_t)L.blocks + 1 : 0, 4}, {L.work, (size_t)L.items, 16},
-                              {L.item_first, L.items > 0 ? (size_t)L.blocks + 1 : 0, 4}, {L.row_map, (size_t)L.rows, 4},
-                              {L.block_of_row, (size_t)L.rows, 4}};
-        arrs.insert(arrs.end(), more, more + 10);
-    }
+    std::vector<TileArr> arrs;
+    for (const std::vector<TileArr> &tier : {m->tile.arrays(vb), m->lt.arrays(vb), m->mt.arrays(vb)})
+        for (const TileArr &a : tier)
+            if (a.elem) arrs.push_back(a);
+    if (arrs.size() * 2 != 64) return fail("csr_tile_digest: %zu arrays do not fill the 64-word digest", arrs.size());
     std::vector<unsigned char> buf;
-    for (int k = 0; k < 32; ++k) {
+    for (size_t k = 0; k < arrs.size(); ++k) {
         const size_t bytes = arrs[k].p ? arrs[k].count * arrs[k].elem : 0;
         unsigned long long h = 1469598103934665603ull;
         if (bytes) {
@@ -1754,15 +1193,16 @@ extern "C" int spmv_hip_csr_info(const spmv_csr_dev *m, spmv_dev_info *out) {
     out->local_blocks = m->local_blocks;
     out->local_stage_lines = m->local_stage_lines;
     out->local_lines = m->local_lines;
-    out->tile_blocks = m->tile_blocks;
-    out->tile_passes = m->tile_passes;
-    out->tile_entries = m->tile_entries + m->tile_rem_entries;
-    out->tile_remainder_entries = m->tile_rem_entries;
-    out->tile_staged_entries = m->tile_staged;
-    out->tile_split_rows = m->tile_num_long;
+    const OwnTiles &t = m->tile;
+    out->tile_blocks = t.blocks;
+    out->tile_passes = t.passes;
+    out->tile_entries = t.entries + t.rem_entries;
+    out->tile_remainder_entries = t.rem_entries;
+    out->tile_staged_entries = t.staged;
+    out->tile_split_rows = t.num_long;
     out->tile_long_rows = m->lt.rows;
     out->tile_long_entries = m->lt.entries;
-    out->tile_staged_cols = m->tile_staged_cols + m->lt.staged_cols + m->mt.staged_cols;
+    out->tile_staged_cols = t.staged_cols + m->lt.staged_cols + m->mt.staged_cols;
     out->tile_long_items = m->lt.items;
     out->tile_mid_rows = m->mt.rows;
     out->tile_mid_entries = m->mt.entries;
@@ -1771,7 +1211,7 @@ extern "C" int spmv_hip_csr_info(const spmv_csr_dev *m, spmv_dev_info *out) {
     out->place_first_us = m->place_first_us;
     out->place_best_us = m->place_best_us;
     out->val_address = (unsigned long long)(uintptr_t)m->val;
-    out->tile_expanded_entries = m->xe && m->expansion ? (long long)m->expansion->entries : 0;
+    out->tile_expanded_entries = t.xe && t.expansion ? (long long)t.expansion->entries : 0;
     out->pattern_slots = m->pat.ptab ? m->pat.slots : 0;
     out->pattern_with_us = m->pat.with_us;
     out->pattern_without_us = m->pat.without_us;
@@ -1780,7 +1220,7 @@ extern "C" int spmv_hip_csr_info(const spmv_csr_dev *m, spmv_dev_info *out) {
     out->pattern_table_rows = m->pat.ptab ? m->pat.table_rows : 0;
     out->pattern_segments_stored = m->pat.ptab && m->pat.pseg ? m->pat.seg_distinct : 0;
     out->local_lists_stored = m->lbase ? m->lists_distinct : 0;
-    out->stream_kernel = m->local_blocks > 0 ? 1 : m->tile_blocks > 0 ? 3 : csr_short_rows(m) ? 2 : 0;
+    out->stream_kernel = m->local_blocks > 0 ? 1 : t.blocks > 0 ? 3 : csr_short_rows(m) ? 2 : 0;
     if (m->local_blocks > 0)  // (a pattern plan: the tables and 4 bytes per row instead of 2 bytes per entry)
         // (a pattern plan: the segments instead of the slots; a block whose segment did not fit reads its table, rinfo
         // and row_ptr -- counted as its share of the tables)
@@ -1789,20 +1229,20 @@ extern "C" int spmv_hip_csr_info(const spmv_csr_dev *m, spmv_dev_info *out) {
                                                   : 2 * m->nz + 4LL * (m->M_local + 1)) +
                             (m->lbase ? 4 * m->lines_stored + 4LL * m->local_blocks : 4 * m->local_lines) +
                             24LL * m->local_blocks + vb * m->M_local + vb * m->N;
-    else if (m->tile_blocks > 0) {  // tiles: 4-byte column + 2-byte key + value per (padded) entry; rows beyond the limit as CSR
-        out->stream_bytes = m->tile_padded * (vb + 6) - (m->tile_packed ? 2 : 0) * m->tile_staged + 16LL * m->tile_passes +
-                            4LL * m->tile_blocks +
-                            std::max<long long>(0, m->nz - m->tile_entries - m->tile_rem_entries - m->lt.entries - m->mt.entries) * (vb + 4) +
-                            m->tile_rem_entries * (vb + 4) + 16LL * m->tile_num_pieces + vb * m->M_local + vb * m->N;
+    else if (t.blocks > 0) {  // tiles: 4-byte column + 2-byte key + value per (padded) entry; rows beyond the limit as CSR
+        // a tier's entries and descriptors
+        auto tier_bytes = [vb](const TileTier &tier) { return tier.padded * (vb + 6) - (tier.packed ? 2 : 0) * tier.staged + 16LL * tier.passes; };
+        out->stream_bytes = tier_bytes(t) + 4LL * t.blocks +
+                            std::max<long long>(0, m->nz - t.entries - t.rem_entries - m->lt.entries - m->mt.entries) * (vb + 4) +
+                            t.rem_entries * (vb + 4) + 16LL * t.num_pieces + vb * m->M_local + vb * m->N;
         // an expanded plan: tile_expand reads 2 bytes per entry (+ 4 per run and per 64 entries) and writes its x value,
         // csr_tile reads that value as its window and a packed column word where it read column and key; every chunk
         // copies its 32 KiB slice of x (out of L2 mostly)
-        if (m->xe && m->expansion)
-            out->stream_bytes += (long long)m->expansion->entries * (2 * vb) + 24LL * m->expansion->chunks +
-                                 4LL * (long long)(m->expansion->runs + m->expansion->groups);
-        for (const spmv_csr_dev::long_tiles *tier : {&m->lt, &m->mt})  // entries, descriptors, slabs written and read
-            out->stream_bytes += tier->padded * (vb + 6) - (tier->packed ? 2 : 0) * tier->staged + 16LL * tier->passes +
-                                 2 * vb * (long long)tier->items * tier->rows_per_block;
+        if (t.xe && t.expansion)
+            out->stream_bytes += (long long)t.expansion->entries * (2 * vb) + 24LL * t.expansion->chunks +
+                                 4LL * (long long)(t.expansion->runs + t.expansion->groups);
+        for (const CompactTiles *tier : {&m->lt, &m->mt})  // ... slabs written and read
+            out->stream_bytes += tier_bytes(*tier) + 2 * vb * (long long)tier->items * tier->rows_per_block;
     }
     return 0;
 }
@@ -1882,12 +1322,12 @@ void launch_x_window(const spmv_csr_dev *m, const T *x, T *y, hipStream_t s, int
     });
 }
 
-// what one csr_tile launch is given: filled for the handle's tiles, for their expansion and for each long_tiles tier
+// what one csr_tile launch is given: filled for the handle's tiles, for their expansion and for each compacted tier
 template <typename T>
 struct tile_args {
     int items, rows_per_block, stage_ok;  // workgroups' work (streams | work items), accumulators per block
     size_t lds;
-    const int4 *work;  // long_tiles only: the work items and their slabs
+    const int4 *work;  // compacted tiers only: the work items and their slabs
     T *slab;
     const int *block_row, *block_pass;
     const int4 *pass;
@@ -1909,53 +1349,66 @@ void launch_csr_tile(const tile_args<T> &a, bool nt, T *y, hipStream_t s) {
     });
 }
 
+// the LDS of one csr_tile workgroup over a tier: slots, accumulators, and the staged window (the packed kernel stores every
+// trip's piece; a plan with gather passes stages its widest window when x can be staged at all)
+template <typename T>
+size_t tile_lds(const TileTier &t, int stage_ok) {
+    return (size_t)kTileSlotBytes + (size_t)t.rows_per_block * sizeof(T) +
+           (t.packed ? (size_t)kTileTrips * kTileTripBytes : stage_ok ? (size_t)t.max_win * sizeof(T) : 0);
+}
+
+// what every tier gives a launch; items / work / slab / streams are the caller's
+template <typename T>
+tile_args<T> tile_args_of(const TileTier &t, int items, int stage_ok, size_t lds, const T *x) {
+    return {items, t.rows_per_block, stage_ok, lds, nullptr, nullptr, t.block_row, t.block_pass, t.pass, t.tcol, t.tkey, (const T *)t.tval,
+            nullptr, nullptr, x};
+}
+
 // the tile plan: (expansion of x,) the tiles, the packed plan's remainder, the long and middle tiers, the split rows
 template <typename T>
 void launch_tiles(const spmv_csr_dev *m, const T *x, T *y, hipStream_t s) {
+    const OwnTiles &t = m->tile;
     // staging copies 16-byte pieces of x: plans with gather passes fall back on gathering everything when
     // x is not 16-byte aligned, packed plans (no gather code) load the pieces unaligned
     const int stage_ok = ((uintptr_t)x & 15) == 0;
     // (probe bit 3, measurement only: one workgroup per CU)
-    const size_t lds = std::max((size_t)std::max(m->tile_lds_min, g_tile_probe & 8 ? 84 * 1024 : 0),
-                                (size_t)kTileSlotBytes + (size_t)m->tile_rows * sizeof(T) +
-                                    (m->tile_packed ? (size_t)kTileTrips * kTileTripBytes  // (the packed kernel stores every trip's piece)
-                                                    : stage_ok ? (size_t)m->tile_max_win * sizeof(T) : 0));
+    const size_t lds = std::max((size_t)std::max(t.lds_min, g_tile_probe & 8 ? 84 * 1024 : 0), tile_lds<T>(t, stage_ok));
     const bool tnt = m->nz * (long long)(sizeof(T) + 6) > (128LL << 20);
-    const tile_args<T> own = {m->tile_streams, m->tile_rows, stage_ok, lds, nullptr, nullptr, m->tile_block_row, m->tile_block_pass,
-                              m->tile_pass, m->tcol, m->tkey, (const T *)m->tval, m->tile_stream_block, m->tile_sblock_rows, x};
+    tile_args<T> own = tile_args_of<T>(t, t.streams, stage_ok, lds, x);
+    own.stream_block = t.stream_block;
+    own.sblock_rows = t.sblock_rows;
     // an expanded plan: x into the passes' segments first, then the packed kernel over x' (16-byte pieces of
     // x: aligned x only)
-    const bool expanded = m->xe && m->expansion && m->expansion->chunks > 0 && stage_ok && g_tile_expand != 0;
+    const bool expanded = t.xe && t.expansion && t.expansion->chunks > 0 && stage_ok && g_tile_expand != 0;
     if (expanded) {
-        hipLaunchKernelGGL((tile_expand<T>), dim3(m->expansion->chunks), dim3(kExpandBlock), 0, s, m->N, g_tile_probe,
-                           m->expansion->chunk, m->expansion->chunk_runs, m->expansion->lcol, m->expansion->group_run, m->expansion->delta, x, (T *)m->xe);
+        hipLaunchKernelGGL((tile_expand<T>), dim3(t.expansion->chunks), dim3(kExpandBlock), 0, s, m->N, g_tile_probe,
+                           t.expansion->chunk, t.expansion->chunk_runs, t.expansion->lcol, t.expansion->group_run, t.expansion->delta, x, (T *)t.xe);
         // (a pass's window is its own segment: 2048 values at most, one staging trip in fp32, two in fp64)
         constexpr int kXpTrips = 2048 * (int)sizeof(T) / kTileTripBytes;
         tile_args<T> xp = own;
         xp.stage_ok = 1;
-        xp.lds = std::max((size_t)m->tile_lds_min, (size_t)kTileSlotBytes + (size_t)m->tile_rows * sizeof(T) +
-                                                       (size_t)kXpTrips * kTileTripBytes);
-        xp.pass = m->expansion->pass;
-        xp.tcol = m->expansion->words;
+        xp.lds = std::max((size_t)t.lds_min, (size_t)kTileSlotBytes + (size_t)t.rows_per_block * sizeof(T) +
+                                                 (size_t)kXpTrips * kTileTripBytes);
+        xp.pass = t.expansion->pass;
+        xp.tcol = t.expansion->words;
         xp.tkey = nullptr;
-        xp.x = (const T *)m->xe;
+        xp.x = (const T *)t.xe;
         launch_csr_tile<T, kXpTrips, true>(xp, tnt, y, s);
     }
-    else if (m->tile_packed) launch_csr_tile<T, kTileTrips, true>(own, tnt, y, s);
+    else if (t.packed) launch_csr_tile<T, kTileTrips, true>(own, tnt, y, s);
     else if (g_tile_gather_ahead) launch_csr_tile<T, kTileTrips, false, true>(own, tnt, y, s);  // gathers one pass early
     else launch_csr_tile<T, kTileTrips, false>(own, tnt, y, s);
-    if (m->tile_rem_rows > 0)  // what the packed plan left out: added behind the tiles
-        hipLaunchKernelGGL((tile_remainder<T>), dim3((m->tile_rem_rows + 255) / 256), dim3(256), 0, s, m->tile_rem_rows,
-                           m->tile_rem_row, m->tile_rem_ptr, m->tile_rem_col, (const T *)m->tile_rem_val, x, y);
+    if (t.rem_rows > 0)  // what the packed plan left out: added behind the tiles
+        hipLaunchKernelGGL((tile_remainder<T>), dim3((t.rem_rows + 255) / 256), dim3(256), 0, s, t.rem_rows,
+                           t.rem_row, t.rem_ptr, t.rem_col, (const T *)t.rem_val, x, y);
     // the compacted tiers -- the long rows' own tiles, the middle tier of a scattered matrix: work items ->
     // slabs -> y (after the ordinary tiles wrote 0 there)
-    for (const spmv_csr_dev::long_tiles *tier : {&m->lt, &m->mt}) {
-        const auto &L = *tier;
+    for (const CompactTiles *tier : {&m->lt, &m->mt}) {
+        const CompactTiles &L = *tier;
         if (L.items <= 0) continue;
-        const size_t llds = (size_t)kTileSlotBytes + (size_t)L.rows_per_block * sizeof(T) +
-                            (L.packed ? (size_t)kTileTrips * kTileTripBytes : stage_ok ? (size_t)L.max_win * sizeof(T) : 0);
-        const tile_args<T> la = {L.items, L.rows_per_block, stage_ok, llds, (const int4 *)L.work, (T *)L.slab, L.block_row, L.block_pass,
-                                 L.pass, L.tcol, L.tkey, (const T *)L.tval, nullptr, nullptr, x};
+        tile_args<T> la = tile_args_of<T>(L, L.items, stage_ok, tile_lds<T>(L, stage_ok), x);
+        la.work = L.work;
+        la.slab = (T *)L.slab;
         if (L.packed) launch_csr_tile<T, kTileTrips, true>(la, tnt, y, s);
         else launch_csr_tile<T, kTileTrips, false>(la, tnt, y, s);
         hipLaunchKernelGGL((tile_slab_finish<T>), dim3((L.rows + kFinishRows - 1) / kFinishRows),
@@ -1963,8 +1416,8 @@ void launch_tiles(const spmv_csr_dev *m, const T *x, T *y, hipStream_t s) {
                            L.rows_per_block, L.block_row, L.block_of_row, L.item_first, L.row_map,
                            (const T *)L.slab, y);
     }
-    if (m->tile_num_long)  // rows beyond the tile limit: stripe-ordered pieces, slots added row by row
-        launch_split_rows<T>(m, m->tile_num_pieces, m->tile_pieces, m->tile_num_long, m->tile_long_rows, x, y, s);
+    if (t.num_long)  // rows beyond the tile limit: stripe-ordered pieces, slots added row by row
+        launch_split_rows<T>(m, t.num_pieces, t.pieces, t.num_long, t.long_rows, x, y, s);
 }
 
 // the gather stream: csr_stream at the handle's stage and the knob's block size, csr_stream_short for short rows

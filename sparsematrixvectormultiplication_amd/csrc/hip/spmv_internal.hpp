@@ -207,6 +207,85 @@ struct PatternPlan {
         seg_distinct = 0;
     }
 };
+// The tile plans of a handle (csr_tile, tile_kernels.hpp): up to three tiers of the same kind of plan, launched by the
+// same kernel.  TileTier is what every tier has; each tier lists its device arrays ONCE, in arrays(): release() frees
+// that list and the digest (csr_tile_digest) hashes it, so an array cannot be in one and not in the other.
+struct TileArr {
+    void *p;
+    size_t count, elem;  // elements and bytes per element for the digest; elem 0: scratch or derived, freed but not digested
+};
+struct TileTier {
+    int *tcol = nullptr;              // [padded + kTileChunkMax]
+    unsigned short *tkey = nullptr;
+    void *tval = nullptr;
+    int4 *pass = nullptr;             // [passes] (the ordinary tiles: in stream order)
+    int *block_row = nullptr;         // [blocks + 1] first row of every block
+    int *block_pass = nullptr;        // [blocks + 1] (the ordinary tiles: [streams + 1], first pass of every stream)
+    int blocks = 0;                   // 0: no tiles
+    int rows_per_block = 0;
+    int passes = 0;
+    int max_win = 0;                  // widest staged window (columns)
+    long long entries = 0, padded = 0, staged = 0, staged_cols = 0;
+    bool packed = false;              // stageable passes hold packed column words (kernel instantiation with the decode)
+
+    // the entry arrays and the pass descriptors, as every tier's digest begins (live: the tier exists; vb: bytes per value)
+    std::vector<TileArr> entry_arrays(bool live, size_t vb) const {
+        const size_t pad = live ? (size_t)padded + kTileChunkMax : 0;
+        // (a packed plan's keys: padding only)
+        return {{tcol, pad, 4}, {tkey, packed ? (pad ? (size_t)kTileChunkMax : 0) : pad, 2}, {tval, pad, vb}, {pass, (size_t)passes, 16}};
+    }
+    static void free_all(const std::vector<TileArr> &arrs) {
+        for (const TileArr &a : arrs) (void)hipFree(a.p);
+    }
+};
+// the ordinary tiles: 2-D tiles (row-block accumulators in LDS x column passes), for matrices without an x-window plan
+struct OwnTiles : TileTier {
+    int lds_min = 0;                  // LDS bytes to ask for at least (scattered matrices: one workgroup per CU)
+    int rem_rows = 0;                 // rows with remainder entries (windows too sparse for a pass), tile_remainder
+    long long rem_entries = 0;
+    int *rem_row = nullptr, *rem_ptr = nullptr, *rem_col = nullptr;  // [rows], [rows + 1], [entries]
+    void *rem_val = nullptr;
+    int streams = 0;                  // workgroups of the csr_tile launch: each walks the blocks of one stream
+    int *stream_block = nullptr;      // [streams + 1] first block (in sblock_rows) of every stream
+    int2 *sblock_rows = nullptr;      // [blocks] {first row, rows} in stream order
+    // the expansion of x for a plan with gather passes (round 3; tile_kernels.hpp, XE): x value per tile entry, written
+    // by tile_expand ahead of every csr_tile launch of this handle, and what tile_expand walks
+    void *xe = nullptr;               // [padded + kTileChunkMax]
+    spmv::TileExpansion *expansion = nullptr;
+    int4 *long_rows = nullptr;        // rows beyond the tile limit {row, first slot, pieces, 0} ...
+    int4 *pieces = nullptr;           // ... and their pieces, cut at column stripes, stripe by stripe
+    int num_long = 0, num_pieces = 0;
+
+    std::vector<TileArr> arrays(size_t vb = 0) const {
+        std::vector<TileArr> a = entry_arrays(blocks > 0, vb);
+        const size_t per_stream = blocks > 0 ? (size_t)streams + 1 : 0;
+        a.insert(a.end(), {{block_pass, per_stream, 4}, {block_row, blocks > 0 ? (size_t)blocks + 1 : 0, 4}, {stream_block, per_stream, 4},
+                           {sblock_rows, (size_t)blocks, 8}, {rem_row, (size_t)rem_rows, 4}, {rem_ptr, rem_rows > 0 ? (size_t)rem_rows + 1 : 0, 4},
+                           {rem_col, (size_t)rem_entries, 4}, {rem_val, (size_t)rem_entries, vb}, {xe, 0, 0}, {long_rows, 0, 0}, {pieces, 0, 0}});
+        return a;
+    }
+    void release();  // spmv_csr.hip (the expansion is a complete type there)
+};
+// a compacted tier: rows picked out of the matrix into row blocks of their own; a block's passes are dealt out to
+// several workgroups (work items), each leaves its accumulators in a slab
+struct CompactTiles : TileTier {
+    int rows = 0, items = 0;
+    int4 *work = nullptr;
+    int *item_first = nullptr, *row_map = nullptr, *block_of_row = nullptr;
+    void *slab = nullptr;
+
+    std::vector<TileArr> arrays(size_t vb = 0) const {
+        std::vector<TileArr> a = entry_arrays(items > 0, vb);
+        const size_t per_block = items > 0 ? (size_t)blocks + 1 : 0;
+        a.insert(a.end(), {{block_row, per_block, 4}, {block_pass, per_block, 4}, {work, (size_t)items, 16}, {item_first, per_block, 4},
+                           {row_map, (size_t)rows, 4}, {block_of_row, (size_t)rows, 4}, {slab, 0, 0}});
+        return a;
+    }
+    void release() {
+        free_all(arrays());
+        *this = CompactTiles();
+    }
+};
 struct spmv_csr_dev {
     int value_bytes = 8;
     int M_local = 0, M_total = 0, N = 0, row0 = 0;
@@ -251,49 +330,10 @@ struct spmv_csr_dev {
     spmv_csr_dev *own_part = nullptr, *halo_part = nullptr;
     long long own_entries = 0, halo_entries = 0;
     bool tiles_only = false;  // a handle made of tile plans alone (the tile side of an HLL handle): STREAM only
-    // csr_tile (2-D tiles: row-block accumulators in LDS x column passes), for matrices without an x-window plan
-    int tile_blocks = 0;              // 0: no tiles
-    int tile_rows = 0;                // rows per block
-    int tile_chunk = 0;               // entries per pass at most (2048)
-    bool tile_packed = false;         // stageable passes hold packed column words (kernel instantiation with the decode)
-    int tile_lds_min = 0;             // LDS bytes to ask for at least (scattered matrices: one workgroup per CU)
-    int tile_passes = 0;
-    int tile_max_win = 0;             // widest staged window (columns)
-    long long tile_entries = 0, tile_staged = 0, tile_staged_cols = 0, tile_padded = 0;
-    int *tile_block_row = nullptr;    // [tile_blocks + 1] first row of every block
-    int *tile_block_pass = nullptr;   // [tile_blocks + 1]
-    int4 *tile_pass = nullptr;        // [tile_passes] in stream order
-    int tile_rem_rows = 0;            // rows with remainder entries (windows too sparse for a pass), tile_remainder
-    long long tile_rem_entries = 0;
-    int *tile_rem_row = nullptr, *tile_rem_ptr = nullptr, *tile_rem_col = nullptr;  // [rows], [rows + 1], [entries]
-    void *tile_rem_val = nullptr;
-    int tile_streams = 0;             // workgroups of the csr_tile launch: each walks the blocks of one stream
-    int *tile_stream_block = nullptr; // [tile_streams + 1] first block (in tile_sblock_rows) of every stream
-    int2 *tile_sblock_rows = nullptr; // [tile_blocks] {first row, rows} in stream order
-    int *tcol = nullptr;              // [tile_padded + kTileChunkMax]
-    unsigned short *tkey = nullptr;
-    void *tval = nullptr;
-    // the expansion of x for a plan with gather passes (round 3; tile_kernels.hpp, XE): x value per tile entry, written
-    // by tile_expand ahead of every csr_tile launch of this handle, and what tile_expand walks
-    void *xe = nullptr;               // [tile_padded + kTileChunkMax]
-    spmv::TileExpansion *expansion = nullptr;
-    // long-row tile plan: the rows beyond the tile limit, compacted into their own row blocks; a block's passes
-    // are dealt out to several workgroups (work items), each leaves its accumulators in a slab
-    struct long_tiles {
-        int blocks = 0, rows = 0, rows_per_block = 0, passes = 0, items = 0, max_win = 0;
-        long long entries = 0, padded = 0, staged = 0, staged_cols = 0;
-        bool packed = false;
-        int *block_row = nullptr, *block_pass = nullptr, *block_of_row = nullptr, *item_first = nullptr, *row_map = nullptr;
-        int4 *pass = nullptr, *work = nullptr;
-        int *tcol = nullptr;
-        unsigned short *tkey = nullptr;
-        void *tval = nullptr, *slab = nullptr;
-    } lt, mt;  // lt: rows beyond tile_lmax (2048 compacted rows per block); mt (round 3): the MIDDLE tier of a scattered
-               // matrix, rows of tile_mid_lo < entries <= tile_lmax in blocks as tall as the LDS takes, so that their
-               // column ranges hold enough entries to be staged as well
-    int4 *tile_long_rows = nullptr;   // rows beyond the tile limit {row, first slot, pieces, 0} ...
-    int4 *tile_pieces = nullptr;      // ... and their pieces, cut at column stripes, stripe by stripe
-    int tile_num_long = 0, tile_num_pieces = 0;
+    OwnTiles tile;     // csr_tile plan of a handle without an x-window plan
+    CompactTiles lt;   // rows beyond tile_lmax (2048 compacted rows per block)
+    CompactTiles mt;   // (round 3) the MIDDLE tier of a scattered matrix, rows of tile_mid_lo < entries <= tile_lmax in blocks
+                       // as tall as the LDS takes, so that their column ranges hold enough entries to be staged as well
     // heuristics
     int lanes_per_row = 16;
     int auto_variant = SPMV_CSR_STREAM;

@@ -303,7 +303,8 @@ def test_tile_plan_built_on_the_device_is_the_host_plan(gpu, oracle, dtype):
     segmented sort, greedy cuts per row block, per-pass re-sort, remainder) is BYTE FOR BYTE the plan tile_plan.hpp
     builds on host threads -- every array of both plans (ordinary tiles and the long rows' own), on scattered columns
     (gather passes), a band (packed plan), a band with stray entries (packed plan + remainder), skewed rows (long-row
-    plan, split rows), empty rows and empty blocks, blocks of a single pass; and the device-built plan runs right."""
+    plan, split rows), empty rows and empty blocks, blocks of a single pass, a scattered matrix's middle tier, an expanded x;
+    and the device-built plan runs right."""
     rng = np.random.default_rng(71)
     cases = []
     M, N = 9001, 2_000_003
@@ -330,11 +331,28 @@ def test_tile_plan_built_on_the_device_is_the_host_plan(gpu, oracle, dtype):
     M, N = 3000, 50_000
     rp, col, val = scattered(rng, M, N, 3, sigma=300, dtype=dtype)   # blocks that hold a single pass in CSR order
     cases.append(("short rows, one pass per block", M, N, rp, col, val, dict(stream_tile=1, tile_rows=256, stream_local=0)))
+    # The tiers whose entry arrays either move in from the device builder or are uploaded from the host builder's, and the
+    # expansion built from either: the generator, sizes and knobs of test_gpu_scaling.py::tile_cases' "mid tier" (the
+    # smallest that put 2^22 entries into the tier's rows) and "expanded x".  (A generator of their own: the cases above
+    # keep their inputs.)
+    rng2 = np.random.default_rng(72)
+    M, mean, N = (70_000, 80, 1 << 25) if dtype == np.float32 else (60_000, 150, 1 << 25)
+    rp, col, val = scattered(rng2, M, N, mean, dtype=dtype)
+    cases.append(("mid tier", M, N, rp, col, val, dict(stream_tile=1)))
+    M, N = 9001, 2_000_003
+    lens = rng2.poisson(14, M)
+    lens[::997] = 3000
+    rp, col, val = scattered(rng2, M, N, 0, dtype=dtype, lens=lens)
+    cases.append(("expanded x", M, N, rp, col, val, dict(stream_tile=1, tile_rows=1024, tile_expand=1, tile_lmax=4096, tile_density=0,
+                                                         tile_pack=0, stream_local=0)))
+    must_build = {"mid tier": "tile_mid_rows", "expanded x": "tile_expanded_entries"}   # (not passed by not building the thing)
     for what, M, N, rp, col, val, knobs in cases:
         with tuned(**knobs):
             host, device = digests_by_builder(lambda: sp.CsrDevice(M, N, rp, col, val))
             assert host[1]["stream_kernel"] == 3, what
             assert_same_plan(host, device, what)
+            if what in must_build:
+                assert host[1][must_build[what]] > 0 and device[1][must_build[what]] > 0, (what, host[1], device[1])
             x = rng.uniform(-1, 1, N).astype(dtype)
             with tuned(tile_plan_on_device=1):
                 with sp.CsrDevice(M, N, rp, col, val) as dev:
