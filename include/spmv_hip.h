@@ -313,6 +313,36 @@ int spmv_hip_csr_spgemm(const spmv_csr_dev *a, const spmv_csr_dev *b, int block_
  * max_rows outside [1, 4096]. */
 int spmv_spgemm_plan(int M, const long long *products, int block_products, int max_rows, int *block_row, int *n_blocks,
                      int *long_row, int *n_long);
+/* C = alpha A + beta B of two whole M x N CSR handles of the same dtype T, built on the device, as a new M x N handle;
+ * with b = NULL, C = alpha canon(A).  a == b is allowed.
+ *   canon(X)   X with canonical rows (columns ascending, no repeats): the value at (i, c) is the serial sum in double of
+ *              row i's entries with column c, in entry order (the first entry starts the sum, every addition one rounded
+ *              operation), rounded once to T.  It is the product X I of spmv_hip_csr_spgemm, byte for byte.
+ *   C          canonical rows on the union of the patterns of canon(A) and canon(B).  The pattern is structural: A - A
+ *              keeps A's pattern with zero values, beta = 0 keeps B's entries.  With a' and b' the values of canon(A) and
+ *              canon(B):  both present: T(fl(fl(alpha a') + fl(beta b')));  A alone: T(fl(alpha a'));  B alone:
+ *              T(fl(beta b')).  Every product and sum is one rounded double operation, never a fused multiply-add, and
+ *              there are no atomics in the values: two calls give the same bytes.  Non-finite values reach exactly the
+ *              entries whose formula contains them; alpha = 0 gets no shortcut (0 * inf is NaN at that entry alone).
+ *   method     0: auto (an operand whose rows are not canonical goes through the product's tiers as X I first, then the
+ *              merge); 1: merge only (an operand that is not canonical is refused); 2: both operands through X I first
+ *   lanes      lanes per row of the merge kernels: 0 = auto (from the mean of len A_i + len B_i), else a power of two
+ *              in [1, 64]
+ *   long_row   the combined length len A_i + len B_i from which a row gets a whole workgroup: 0 = auto (32 trips of the
+ *              row's lanes, between 256 and 2048), else >= 1
+ * The canonical check (one pass over row_ptr and col of each operand) runs on every call.  The merge runs twice, once for
+ * the rows' entry counts (every entry of A looks its column up in B's row) and once for columns and values (every entry
+ * computes its own final position), so C's arrays are allocated at their exact size.
+ * C is an ordinary handle (upload's plans, its own arrays, independent of A and B, which are not modified).
+ *   stats (6, may be NULL)  entries of C, entries present in both operands, A found canonical (0 / 1), B found canonical
+ *                           (1 when absent), long rows, the largest row's entries
+ *   ms (5, may be NULL)     host milliseconds of check, canonical, symbolic, numeric, adopt
+ * -1 with a message (*out NULL, A and B usable): a or out NULL, different shapes, different dtypes, a row-range or
+ * tiles-only handle, alpha or beta not finite, method / lanes / long_row outside the above, method 1 on an operand that is
+ * not canonical (the message names it and its first offending row), more entries in C than a handle indexes, a failed
+ * allocation. */
+int spmv_hip_csr_add(const spmv_csr_dev *a, double alpha, const spmv_csr_dev *b /* may be NULL */, double beta,
+                     int method, int lanes, int long_row, spmv_csr_dev **out, long long *stats, double *ms);
 /* convenience over the kept struct */
 int spmv_hip_csr_upload_matrix(const CSRMatrix *csr, spmv_csr_dev **out);
 void spmv_hip_csr_free(spmv_csr_dev *m);

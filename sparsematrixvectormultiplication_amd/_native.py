@@ -228,6 +228,8 @@ _PROTOTYPES = {
     "spmv_hip_csr_transpose": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "spmv_hip_csr_spgemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.POINTER(C.c_void_p),
                                       C.POINTER(C.c_longlong), c_double_p]),
+    "spmv_hip_csr_add": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int,
+                                   C.POINTER(C.c_void_p), C.POINTER(C.c_longlong), c_double_p]),
     "spmv_spgemm_plan": (C.c_int, [C.c_int, C.POINTER(C.c_longlong), C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p]),
     "spmv_hip_csr_precond_build": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "spmv_hip_precond_free": (None, [C.c_void_p]),

@@ -46,12 +46,6 @@ void fsai_launch(int count, const int *rows, const int *a_rp, const int *a_col, 
                        g_rp, g_col, g_val, status);
 }
 
-template <typename T>
-int csr_adopt(int M, int N, const int *row_ptr_host, int *d_col, T *d_val, spmv_csr_dev **out) {
-    if constexpr (sizeof(T) == 8) return csr_adopt_f64(M, N, row_ptr_host, d_col, d_val, out);
-    else return csr_adopt_f32(M, N, row_ptr_host, d_col, d_val, out);
-}
-
 // the device arrays of one build: freed on every path, an exception's (host out of memory under guarded()) included;
 // d_col / d_val are set to NULL once G's handle owns them
 template <typename T>

@@ -400,6 +400,19 @@ struct LocalPlan {
 // on success only); col / val carry kPad zeroed entries behind the last one
 int csr_adopt_f64(int M, int N, const int *row_ptr_host, int *d_col, double *d_val, spmv_csr_dev **out);
 int csr_adopt_f32(int M, int N, const int *row_ptr_host, int *d_col, float *d_val, spmv_csr_dev **out);
+// ... by the value type
+template <typename T>
+int csr_adopt(int M, int N, const int *row_ptr_host, int *d_col, T *d_val, spmv_csr_dev **out) {
+    if constexpr (sizeof(T) == 8) return csr_adopt_f64(M, N, row_ptr_host, d_col, d_val, out);
+    else return csr_adopt_f32(M, N, row_ptr_host, d_col, d_val, out);
+}
+// device memory freed on every way out of a function
+struct DevBuf {
+    void *p = nullptr;
+    ~DevBuf() { (void)hipFree(p); }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 16)); }
+    template <typename U> U *as() const { return static_cast<U *>(p); }
+};
 // spmv_csr.hip: tile plans alone for rows given as (first entry, length) over host arrays (an HLL slab's rows);
 // *out = NULL when the rows get no plan
 // (col / val: host copies of the rows' arrays, or NULL when d_col / d_val -- the same arrays on the device -- are given

@@ -22,19 +22,6 @@ namespace {
 constexpr int kSgMaxGrid = 1 << 16;            // grid cap (blocks and rows stride over the workgroups beyond it)
 constexpr long long kSgAutoChunk = 1LL << 23;  // products of a chunk (auto): 32 bytes of workspace each
 
-struct DevBuf {  // device memory freed on every way out
-    void *p = nullptr;
-    ~DevBuf() { (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 16)); }
-    template <typename U> U *as() const { return static_cast<U *>(p); }
-};
-
-template <typename T>
-int csr_adopt(int M, int N, const int *row_ptr_host, int *d_col, T *d_val, spmv_csr_dev **out) {
-    if constexpr (sizeof(T) == 8) return csr_adopt_f64(M, N, row_ptr_host, d_col, d_val, out);
-    else return csr_adopt_f32(M, N, row_ptr_host, d_col, d_val, out);
-}
-
 // the on-chip kernels ask for up to 64 KiB of dynamic LDS beside their static scratch: HIP wants that allowed per kernel
 template <typename T>
 int sg_allow_lds() {

@@ -56,12 +56,6 @@ __global__ __launch_bounds__(kBlock) void tr_row_ptr(long long nz, int N, const 
 }
 
 template <typename T>
-int csr_adopt(int M, int N, const int *row_ptr_host, int *d_col, T *d_val, spmv_csr_dev **out) {
-    if constexpr (sizeof(T) == 8) return csr_adopt_f64(M, N, row_ptr_host, d_col, d_val, out);
-    else return csr_adopt_f32(M, N, row_ptr_host, d_col, d_val, out);
-}
-
-template <typename T>
 int transpose_body(const spmv_csr_dev *m, spmv_csr_dev **out) {
     const int M = m->M_total, N = m->N;
     const long long nz = m->nz;

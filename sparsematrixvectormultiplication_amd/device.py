@@ -52,6 +52,10 @@ FSAI_PLANS = ("gather", "x_window", "x_window_pattern", "csr_tile")  # fsai_info
 MATMUL_STATS = ("products", "nz", "blocks", "block_rows", "long_rows", "chunks", "max_row_products", "max_row_nz")
 MATMUL_MS = ("count", "symbolic", "numeric", "adopt")
 SPGEMM_MAX_ROWS = 4096
+# CsrDevice.add: the result's add_info (the stats and the time split of spmv_hip_csr_add)
+ADD_STATS = ("nz", "matches", "a_canonical", "b_canonical", "long_rows", "max_row_nz")
+ADD_MS = ("check", "canonical", "symbolic", "numeric", "adopt")
+ADD_METHODS = {"auto": 0, "merge": 1, "canonical": 2}
 CSR_STREAM_KERNELS = ("csr_stream", "csr_stream_local", "csr_stream_short", "csr_tile")
 HLL_LDS_KERNELS = ("hll_lds", "hll_lds_local", "csr_tile (HLL slab rows)")
 CSR_VARIANTS = {"thread_row": CSR_THREAD_ROW, "wave_row": CSR_WAVE_ROW, "subwave": CSR_SUBWAVE,
@@ -274,6 +278,58 @@ class CsrDevice(_Handle):
 
     def __matmul__(self, other):
         return self.matmul(other) if isinstance(other, CsrDevice) else NotImplemented
+
+    def add(self, other: "CsrDevice" = None, alpha: float = 1.0, beta: float = 1.0, method: str = "auto", lanes: int = 0,
+            long_row: int = 0) -> "CsrDevice":
+        """C = alpha * self + beta * other as a new handle (spmv_hip_csr_add): both whole matrices of one shape and dtype;
+        other = None gives alpha * canon(self).  C has canonical rows (ascending columns, no repeats) on the union of the
+        two patterns (structural: a sum that cancels to 0.0 stays) and, bit for bit, the values of the definition in
+        include/spmv_hip.h: repeated pairs added in entry order first, then every product and sum a separate rounded
+        double operation, rounded once to the dtype.  method: "auto" (operands with unsorted rows or repeats go through
+        the product's tiers first), "merge" (canonical operands only) or "canonical" (both through the product first);
+        lanes: lanes per row of the merge (0 = auto, else a power of two in [1, 64]); long_row: the combined row length
+        from which a row gets a workgroup (0 = auto).  C.add_info holds the stats (ADD_STATS) and "ms" (ADD_MS)."""
+        if other is not None and not isinstance(other, CsrDevice):
+            raise TypeError("add takes a CsrDevice or None")
+        for name, m in (("self", self), ("other", other)):
+            if m is not None and m._own_rows() != (0, m.M):
+                raise ValueError(f"add: {name} holds rows {m._own_rows()} of {m.M}; only whole matrices add")
+        if other is not None and (other.M, other.N) != (self.M, self.N):
+            raise ValueError(f"add: self is {self.M} x {self.N} and other is {other.M} x {other.N}")
+        if other is not None and np.dtype(other.dtype) != np.dtype(self.dtype):
+            raise ValueError(f"add: self holds {np.dtype(self.dtype)} and other {np.dtype(other.dtype)}")
+        alpha, beta = float(alpha), float(beta)
+        if not (np.isfinite(alpha) and np.isfinite(beta)):
+            raise ValueError(f"add: alpha = {alpha}, beta = {beta}; both must be finite")
+        if method not in ADD_METHODS:
+            raise ValueError(f"add: method = {method!r}; one of {sorted(ADD_METHODS)}")
+        lanes, long_row = int(lanes), int(long_row)
+        if lanes != 0 and (lanes < 1 or lanes > 64 or lanes & (lanes - 1)):
+            raise ValueError(f"add: lanes = {lanes}; 0 (auto) or a power of two in [1, 64]")
+        if long_row < 0 or long_row > 0x7fffffff:
+            raise ValueError(f"add: long_row = {long_row}; 0 (auto) or a positive row length")
+        out = CsrDevice.__new__(CsrDevice)
+        _Handle.__init__(out)
+        stats, ms = (C.c_longlong * len(ADD_STATS))(), (C.c_double * len(ADD_MS))()
+        _check(nat.lib().spmv_hip_csr_add(self.h, alpha, other.h if other is not None else None, beta, ADD_METHODS[method],
+                                          lanes, long_row, C.byref(out.h), stats, ms), "spmv_hip_csr_add")
+        out.M, out.N, out.dtype = self.M, self.N, self.dtype
+        out.add_info = dict(zip(ADD_STATS, (int(v) for v in stats)))
+        out.add_info["ms"] = dict(zip(ADD_MS, (float(v) for v in ms)))
+        return out
+
+    def canonical(self) -> "CsrDevice":
+        """canon(self) as a new handle: sorted rows, repeated (row, column) pairs added in entry order (add(None))."""
+        return self.add(None)
+
+    def __add__(self, other):
+        return self.add(other) if isinstance(other, CsrDevice) else NotImplemented
+
+    def __sub__(self, other):
+        return self.add(other, 1.0, -1.0) if isinstance(other, CsrDevice) else NotImplemented
+
+    def __neg__(self):
+        return self.add(None, -1.0)
 
     def download(self):
         """(row_ptr, col_idx, values) of the handle's rows, from the device."""
@@ -831,6 +887,16 @@ class TriangularSolver(_Handle):
         """The same on device vectors (b and x must not overlap), asynchronous on `stream` (0 = the library's)."""
         _check(nat.lib().spmv_hip_trsv_solve_on(self.h, C.c_void_p(d_b), C.c_void_p(d_x), C.c_void_p(stream)),
                "spmv_hip_trsv_solve_on")
+
+
+def identity(n, dtype=np.float64) -> CsrDevice:
+    """I_n as a handle (a plain upload), for A + sigma I: A.add(sp.identity(n), beta=sigma)."""
+    n = int(n)
+    if n < 0:
+        raise ValueError(f"identity: n = {n}")
+    if np.dtype(dtype) not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError(f"identity: dtype {np.dtype(dtype)}; float64 or float32")
+    return CsrDevice(n, n, np.arange(n + 1, dtype=np.int32), np.arange(n, dtype=np.int32), np.ones(n, dtype=dtype))
 
 
 def spgemm_plan(products, block_products, max_rows=SPGEMM_MAX_ROWS):
