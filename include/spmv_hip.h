@@ -124,6 +124,8 @@ typedef struct {
                                           blocks ("local_share"; 0: no segments) */
     long long local_lists_stored;   /* CSR: line lists held in memory: lists that are equal relative to their first line are
                                        stored once, each block adds its own first line (0: every block holds absolute ids) */
+    long long local_lines_stored;   /* CSR: line ids the handle's list array holds (local_lines where every block keeps its own
+                                       list; fewer once equal lists are shared), without the kernel's zeroed tail */
 } spmv_dev_info;
 
 /* ---- device ------------------------------------------------------------ */

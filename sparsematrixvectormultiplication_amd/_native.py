@@ -60,7 +60,8 @@ class DevInfo(C.Structure):
                 ("val_address", C.c_ulonglong), ("tile_expanded_entries", C.c_longlong),
                 ("pattern_slots", C.c_longlong), ("pattern_with_us", C.c_float), ("pattern_without_us", C.c_float),
                 ("pattern_segment_max", C.c_int), ("pattern_segment_cap", C.c_int), ("pattern_table_rows", C.c_longlong),
-                ("pattern_segments_stored", C.c_longlong), ("local_lists_stored", C.c_longlong)]
+                ("pattern_segments_stored", C.c_longlong), ("local_lists_stored", C.c_longlong),
+                ("local_lines_stored", C.c_longlong)]
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}

@@ -1220,6 +1220,7 @@ extern "C" int spmv_hip_csr_info(const spmv_csr_dev *m, spmv_dev_info *out) {
     out->pattern_table_rows = m->pat.ptab ? m->pat.table_rows : 0;
     out->pattern_segments_stored = m->pat.ptab && m->pat.pseg ? m->pat.seg_distinct : 0;
     out->local_lists_stored = m->lbase ? m->lists_distinct : 0;
+    out->local_lines_stored = m->local_blocks > 0 ? (m->lbase ? m->lines_stored : m->local_lines) : 0;
     out->stream_kernel = m->local_blocks > 0 ? 1 : t.blocks > 0 ? 3 : csr_short_rows(m) ? 2 : 0;
     if (m->local_blocks > 0)  // (a pattern plan: the tables and 4 bytes per row instead of 2 bytes per entry)
         // (a pattern plan: the segments instead of the slots; a block whose segment did not fit reads its table, rinfo

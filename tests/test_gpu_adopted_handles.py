@@ -1,0 +1,590 @@
+"""Handles that were built on the device against an upload of the same arrays.
+
+Five places build a CSR matrix on the device and hand bare device arrays to csr_upload_impl through csr_adopt:
+CsrDevice.from_coo, transpose(), matmul(), add() / canonical(), and the FSAI preconditioner's factors G and G^T.  Their
+own tests check the arrays they produce; here every producer is made to yield exactly the bytes of a target, and the
+handle is held to its TWIN, sp.CsrDevice(M, N, rp, col, val) of that target under the same knobs (assert_twin):
+
+  1. h.download() is the target, bit for bit (else the producer is wrong, not the handle);
+  2. the same plan: info() on every key but the six that hold a time or an address, tile_digest() (32 arrays), and the
+     x-window arrays behind addresses() (ldesc4, lcol, lines) byte for byte;
+  3. the kPad entries behind col and val are zero bytes on both (the stream and LDS kernels stage from them);
+  4. every CSR variant on a uniform and a wide-range x, y pre-filled with 0xFF: the twin's bytes, and inside the suite's
+     gates against the oracle (which catches both handles being wrong alike);
+  5. downstream: spmm (k = 3), the HLL conversion (fp64: spmv_hip_hll_from_csr takes no fp32 handle), and for square
+     targets the interior / boundary and the column splits.
+
+Steps 2 and 5 run under local_patterns = 1, place_tries = 0: the only two upload decisions that are timed
+(upload_searches, upload_ops.hpp) are then not taken, and nothing compared depends on a clock.  One more pass per target
+under the default knobs asserts 1, 3 and 4 only: the pattern kernel and the slot stream give the same bits, a placement
+moves none.
+
+The targets, each the smallest that reaches its branch of csr_upload_impl's adopt path, the branch asserted from info():
+  T1 x-window plan, built on the device from the adopted columns -- and under plan_on_device = 0 by the host builder on
+     the columns copied back (col_back);
+  T2 a band with rows that alone touch more than 256 lines: the device builder declines, the host builder hands those
+     rows to the split-row kernels (csr_plan_check's sixth value, checked on the host).  banded_csr's far_frac moves a
+     quarter of a row's entries half a matrix away, which a row of a dozen entries cannot turn into more than 256 lines,
+     and the host builder hands rows over from 2^20 entries on only: hence 66 000 rows and a few wide rows;
+  T3 a long row inside an x-window matrix;
+  T4 tile plan, ordinary tier, built by host threads and by the device builder on the arrays copied back (col_copy /
+     val_copy);
+  T5 tile plan with the long rows' tier;  T6 tile plan on an expanded x;
+  T7 no plan, the lane-group kernel;  T8 rows split by skew (from 2^20 entries on);
+  T9 edges: no entries, 1 x 1, only the last row holds entries, one column.
+Not covered, both for their size: the middle tile tier (2^22 entries in its rows: 60 000 rows of 150 entries, by
+test_gpu_tile.py) and the placement search of an adopted value array (kPlaceMinBytes = 128 MiB of values: 16.8 M fp64
+entries).  Neither fits a test of a few seconds per producer.
+
+Then the consumers that keep state (solver steps, ILU(0) and AMG builds, CGLS with a device-built transpose) on a symmetric
+positive definite matrix (synth.fem_like's pattern under a dominant diagonal) built through transpose, matmul and add, and
+the FSAI apply against the two products on uploads of its factors.
+
+A dirty buffer of the result's size is allocated, filled with 0xFF and freed before every producer call, so that a
+producer that forgets to zero a tail is likely (not certain) to show it."""
+import contextlib
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import sparsematrixvectormultiplication_amd as sp
+from _util import assert_parity, assert_parity_f32, banded_csr, coo_from_csr, random_csr, wide_range
+from sparsematrixvectormultiplication_amd import synth
+from sparsematrixvectormultiplication_amd.device import set_tuning
+from test_gpu_tile import scattered, tuned
+from test_gpu_transpose import transpose_ref
+
+pytestmark = pytest.mark.gpu
+
+DTYPES = [np.float64, np.float32]
+KPAD = 8192 + 64        # kPad of csrc/hip/spmv_internal.hpp: the zeroed entries behind col and val
+# info() keys that hold a time or an address
+TIMED = ("place_tries", "place_first_us", "place_best_us", "val_address", "pattern_with_us", "pattern_without_us")
+PINNED = dict(local_patterns=1, place_tries=0)
+LOCAL_DEFAULTS = {"local_patterns": -1, "plan_on_device": 1}    # the knobs test_gpu_tile.py's tuned() does not know
+
+
+@contextlib.contextmanager
+def under(**knobs):
+    """The knobs set for the block, the library's defaults after it (tuned() for the keys it resets, the rest here)."""
+    local = {k: v for k, v in knobs.items() if k in LOCAL_DEFAULTS}
+    try:
+        with tuned(**{k: v for k, v in knobs.items() if k not in LOCAL_DEFAULTS}):
+            for k, v in local.items():
+                set_tuning(k, v)
+            yield
+    finally:
+        for k in local:
+            set_tuning(k, LOCAL_DEFAULTS[k])
+
+
+# ---------------------------------------------------------------- targets: ascending rows without repeats
+def distinct(rp, col, val):
+    """The matrix without the entries that repeat their predecessor's (row, column); rows are sorted already."""
+    rows = np.repeat(np.arange(len(rp) - 1), np.diff(rp))
+    keep = np.ones(len(col), dtype=bool)
+    keep[1:] = (rows[1:] != rows[:-1]) | (col[1:] != col[:-1])
+    out = np.zeros(len(rp), dtype=np.int64)
+    np.add.at(out, rows[keep] + 1, 1)
+    return np.cumsum(out).astype(np.int32), col[keep], val[keep]
+
+
+def with_rows(rp, col, val, new_rows, rng):
+    """The matrix with row r replaced by the sorted columns new_rows[r]"""
+    M = len(rp) - 1
+    lens = np.diff(rp).astype(np.int64)
+    for r, c in new_rows.items():
+        lens[r] = len(c)
+    out = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    ncol, nval = np.empty(out[-1], dtype=np.int32), np.empty(out[-1], dtype=val.dtype)
+    rows = np.repeat(np.arange(M), np.diff(rp))
+    kept = ~np.isin(rows, list(new_rows))
+    pos = out[rows[kept]] + (np.flatnonzero(kept) - rp[rows[kept]])
+    ncol[pos], nval[pos] = col[kept], val[kept]
+    for r, c in new_rows.items():
+        ncol[out[r]:out[r + 1]] = c
+        nval[out[r]:out[r + 1]] = rng.uniform(-1, 1, len(c)).astype(val.dtype)
+    return out, ncol, nval
+
+
+def t1():
+    return (20_000, 20_000) + banded_csr(np.random.default_rng(101), 20_000, 20_000, 9, 150)
+
+
+T2_ROWS, T2_WIDE_EVERY, T2_WIDE = 66_000, 3000, 600
+
+
+def t2():
+    """66 000 rows of about 16 entries in a band (a fiftieth of them with a cluster half a matrix away), every 3000th row
+    600 entries anywhere: more than 256 lines of x in fp64 and in fp32, and 1.06 M entries."""
+    rng = np.random.default_rng(102)
+    M = N = T2_ROWS
+    rp, col, val = banded_csr(rng, M, N, 16, 150, far_frac=0.02)
+    wide = {r: np.sort(rng.choice(N, T2_WIDE, replace=False)).astype(np.int32) for r in range(7, M, T2_WIDE_EVERY)}
+    rp, col, val = with_rows(rp, col, val, wide, rng)
+    assert rp[-1] >= 1 << 20
+    for value_bytes in (8, 4):
+        stats = sp.csr_plan_check(M, N, rp, col, value_bytes)   # host only: the plan upload's host builder makes
+        assert stats["local_blocks"] > 0 and stats["split_rows"] == len(wide) and stats["long_rows"] == len(wide), stats
+    return M, N, rp, col, val
+
+
+def t3():
+    rng = np.random.default_rng(103)
+    M, N, rp, col, val = target_of("T1", np.float64)
+    long_row = np.sort(rng.choice(N, 5000, replace=False)).astype(np.int32)
+    return (M, N) + with_rows(rp, col, val, {M // 2: long_row}, rng)
+
+
+def t4():
+    return (3000, 50_000) + distinct(*scattered(np.random.default_rng(104), 3000, 50_000, 3, sigma=300))
+
+
+def t5():
+    """test_gpu_tile.py's "skewed, auto block height" """
+    rng = np.random.default_rng(105)
+    M, N = 6500, 3_000_000
+    lens = np.minimum((1.08 / rng.random(M)).astype(np.int64), 60000)
+    lens[rng.random(M) < 0.1] = 0
+    lens[1000:1700] = 0
+    lens[[11, 3000, 6499]] = [50000, 5000, 900]
+    return (M, N) + distinct(*scattered(rng, M, N, 0, lens=lens))
+
+
+def t6():
+    """test_gpu_tile.py's "expanded x" """
+    rng = np.random.default_rng(106)
+    M, N = 9001, 2_000_003
+    lens = rng.poisson(14, M)
+    lens[::997] = 3000
+    lens[5] = 0
+    return (M, N) + distinct(*scattered(rng, M, N, 0, lens=lens))
+
+
+def t7():
+    return (20_000, 20_000) + random_csr(np.random.default_rng(107), 20_000, 20_000, 8)
+
+
+T8_ROWS, T8_LONG_EVERY = 220_000, 1000
+
+
+def t8():
+    rng = np.random.default_rng(108)
+    lens = rng.poisson(5, T8_ROWS)
+    lens[::T8_LONG_EVERY] = 1500
+    M, N, (rp, col, val) = T8_ROWS, T8_ROWS, distinct(*scattered(rng, T8_ROWS, T8_ROWS, 0, lens=lens))
+    assert rp[-1] >= 1 << 20 and np.all(np.diff(rp)[::T8_LONG_EVERY] > 1400)
+    return M, N, rp, col, val
+
+
+def t9_empty():
+    return 5, 7, np.zeros(6, np.int32), np.zeros(0, np.int32), np.zeros(0)
+
+
+def t9_one():
+    return 1, 1, np.array([0, 1], np.int32), np.zeros(1, np.int32), np.array([-0.75])
+
+
+def t9_last_row():
+    rp = np.zeros(4001, np.int32)
+    rp[-1] = 5
+    return 4000, 4000, rp, np.array([0, 17, 2048, 3998, 3999], np.int32), np.array([0.5, -0.25, 0.875, -1.0, 0.125])
+
+
+def t9_one_column():
+    M = 3000
+    return M, 1, np.arange(M + 1, dtype=np.int32), np.zeros(M, np.int32), np.random.default_rng(109).uniform(-1, 1, M)
+
+
+def x_window(info, pinned):
+    assert info["local_blocks"] > 0 and info["stream_kernel"] == 1, info
+    if pinned:
+        assert info["pattern_slots"] > 0, info
+
+
+def branch_t1(info, pinned):
+    x_window(info, pinned)
+    assert info["long_rows"] == 0, info
+
+
+def branch_t2(info, pinned):
+    x_window(info, pinned)
+    assert info["long_rows"] == len(range(7, T2_ROWS, T2_WIDE_EVERY)), info   # the rows handed over, none long by length
+
+
+def branch_t3(info, pinned):
+    x_window(info, pinned)
+    assert info["long_rows"] == 1, info
+
+
+def branch_t4(info, pinned):
+    assert info["stream_kernel"] == 3 and info["local_blocks"] == 0 and info["tile_blocks"] > 0, info
+
+
+def branch_t5(info, pinned):
+    assert info["stream_kernel"] == 3 and info["tile_long_rows"] > 0, info
+
+
+def branch_t6(info, pinned):
+    assert info["stream_kernel"] == 3 and info["tile_expanded_entries"] > 0, info
+
+
+def branch_t7(info, pinned):
+    assert info["local_blocks"] == 0 and info["tile_blocks"] == 0 and info["auto_variant"] == sp.CSR_SUBWAVE, info
+
+
+def branch_t8(info, pinned):
+    assert info["local_blocks"] == 0 and info["tile_blocks"] == 0, info
+    assert info["long_rows"] == len(range(0, T8_ROWS, T8_LONG_EVERY)), info
+
+
+def branch_none(info, pinned):
+    assert info["tile_blocks"] == 0, info
+
+
+TILE_T5 = dict(stream_tile=1, tile_lmax=40, tile_long=2, tile_places=64)
+TILE_T6 = dict(stream_tile=1, tile_rows=1024, tile_expand=1, tile_lmax=4096, tile_density=0, tile_pack=0, stream_local=0)
+# name: (target, the knobs that lead to its branch, the branch)
+CASES = {
+    "T1": (t1, {}, branch_t1),
+    "T1-host-plan": (t1, dict(plan_on_device=0), branch_t1),
+    "T2": (t2, {}, branch_t2),
+    "T3": (t3, {}, branch_t3),
+    "T4-host-tiles": (t4, dict(stream_tile=1, tile_rows=256, stream_local=0, tile_plan_on_device=0), branch_t4),
+    "T4-device-tiles": (t4, dict(stream_tile=1, tile_rows=256, stream_local=0, tile_plan_on_device=1), branch_t4),
+    "T5": (t5, TILE_T5, branch_t5),
+    "T6": (t6, TILE_T6, branch_t6),
+    "T7": (t7, dict(stream_tile=0), branch_t7),
+    "T8": (t8, dict(stream_tile=0), branch_t8),
+    "T9-empty": (t9_empty, {}, branch_none),
+    "T9-1x1": (t9_one, {}, branch_none),
+    "T9-last-row": (t9_last_row, {}, branch_none),
+    "T9-one-column": (t9_one_column, {}, branch_none),
+}
+
+_STRUCTURES, _INPUTS, _TWINS = {}, {}, {}
+
+
+def target_of(case, dtype):
+    """(M, N, rp, col, val of dtype): built once per generator, the fp32 target the fp64 one's values rounded"""
+    make = CASES[case][0]
+    if make not in _STRUCTURES:
+        _STRUCTURES[make] = make()
+    M, N, rp, col, val = _STRUCTURES[make]
+    return M, N, rp, col, val.astype(dtype)
+
+
+def inputs_of(case, dtype, oracle):
+    """(x_list, their oracle products, X of 3 columns) of the case's target: once per (generator, dtype)"""
+    key = (CASES[case][0], np.dtype(dtype))
+    if key not in _INPUTS:
+        M, N, rp, col, val = target_of(case, dtype)
+        rng = np.random.default_rng(7 * M + N)
+        xs = [rng.uniform(-1, 1, N).astype(dtype), wide_range(rng, N, dtype)]
+        ref = oracle.csr_serial if dtype == np.float64 else oracle.csr_f32_accum64
+        _INPUTS[key] = (xs, [ref(rp, col, val, x) for x in xs], rng.uniform(-1, 1, (N, 3)).astype(dtype))
+    return _INPUTS[key]
+
+
+# ---------------------------------------------------------------- producers: target -> a handle holding its bytes
+def upload(M, N, rp, col, val):
+    return sp.CsrDevice(M, N, rp, col, val)
+
+
+def select(M, rp, col, val, mask):
+    rows = np.repeat(np.arange(M), np.diff(rp))
+    out = np.zeros(M + 1, dtype=np.int64)
+    np.add.at(out, rows[mask] + 1, 1)
+    return np.cumsum(out).astype(np.int32), col[mask], val[mask]
+
+
+def sources_from_coo(M, N, rp, col, val):
+    rows, cols, vals = coo_from_csr(rp, col, val)
+    order = np.argsort(np.random.default_rng(M).permutation(M)[rows], kind="stable")   # rows shuffled, a row's order kept
+    return (rows[order], cols[order], vals[order])
+
+
+def sources_transpose(M, N, rp, col, val):
+    return (upload(N, M, *transpose_ref(M, N, rp, col, val)),)
+
+
+def sources_matmul(M, N, rp, col, val):
+    return sp.identity(M, val.dtype), upload(M, N, rp, col, val)
+
+
+def sources_add(M, N, rp, col, val):
+    even = col % 2 == 0
+    return upload(M, N, *select(M, rp, col, val, even)), upload(M, N, *select(M, rp, col, val, ~even))
+
+
+def sources_canonical(M, N, rp, col, val):
+    rows = np.repeat(np.arange(M), np.diff(rp))
+    back = rp[rows].astype(np.int64) + rp[rows + 1] - 1 - np.arange(len(col))    # every row's entries reversed
+    rcol, rval = np.empty_like(col), np.empty_like(val)
+    rcol[back], rval[back] = col, val
+    return (upload(M, N, rp, rcol, rval),)
+
+
+# name: (what the producer reads (uploaded under the default knobs), the call that adopts under the case's knobs)
+PRODUCERS = {
+    "from_coo": (sources_from_coo, lambda tgt, I, J, v: sp.CsrDevice.from_coo(tgt[0], tgt[1], I, J, v)),
+    "transpose": (sources_transpose, lambda tgt, at: at.transpose()),
+    "matmul": (sources_matmul, lambda tgt, eye, a: eye.matmul(a)),
+    "add": (sources_add, lambda tgt, even, odd: even.add(odd)),
+    "canonical": (sources_canonical, lambda tgt, a: a.canonical()),
+}
+# (from_coo: fp64 only, the entry point has no fp32 form)
+PRODUCER_CASES = [(p, d) for p in PRODUCERS for d in DTYPES if not (p == "from_coo" and d == np.float32)]
+
+
+def dirty_allocations(nz, itemsize):
+    """Two buffers of the sizes a producer is about to allocate for col and val, filled with 0xFF and freed: a recycled
+    allocation is then dirty (likely, not certain: nothing is asserted about reuse)."""
+    L, bufs = sp.lib(), []
+    for size in ((nz + KPAD) * 4, (nz + KPAD) * itemsize):
+        p = C.c_void_p()
+        assert L.spmv_hip_malloc(C.byref(p), size) == 0 and L.spmv_hip_memset(p, 0xFF, size) == 0
+        bufs.append(p)
+    sp.hip_sync()
+    for p in bufs:
+        assert L.spmv_hip_free(p) == 0
+
+
+@contextlib.contextmanager
+def produced(producer, tgt, knobs):
+    """The handle the producer makes of tgt: its operands uploaded under the default knobs, the adopting call under knobs"""
+    make_sources, call = PRODUCERS[producer]
+    sources = make_sources(*tgt)
+    h = None
+    try:
+        with under(**knobs):
+            dirty_allocations(len(tgt[3]), tgt[4].itemsize)
+            h = call(tgt, *sources)
+            yield h
+    finally:
+        for s in (h,) + tuple(sources):
+            if isinstance(s, sp.CsrDevice):
+                s.close()
+
+
+# ---------------------------------------------------------------- the twin check
+def read_device(address, nbytes):
+    buf = np.zeros(max(nbytes, 1), dtype=np.uint8)
+    if nbytes:
+        assert address, "a NULL device array"
+        assert sp.lib().spmv_hip_memcpy_d2h(buf.ctypes.data_as(C.c_void_p), C.c_void_p(address), nbytes) == 0
+    return buf[:nbytes].tobytes()
+
+
+def launched(dev, x, run):
+    """y of run() on x, every byte of y set before the launch"""
+    assert sp.lib().spmv_hip_memset(dev.y_ptr, 0xFF, dev.M * x.itemsize) == 0
+    dev.set_x(x)
+    run()
+    sp.hip_sync()
+    return dev.get_y()
+
+
+def observe(dev, tgt, xs, X3, full):
+    """Everything that is compared between a handle and its twin; full: the plan and the consumers as well"""
+    M, N, rp, col, val = tgt
+    info, adr, item = dev.info(), dev.addresses(), val.itemsize
+    seen = {"pad col": read_device(adr["col"] + 4 * info["nz"], 4 * KPAD),
+            "pad val": read_device(adr["val"] + item * info["nz"], item * KPAD)}
+    for name, variant in sp.CSR_VARIANTS.items():
+        for k, x in enumerate(xs):
+            seen[f"y {name} x{k}"] = launched(dev, x, lambda: dev.run(variant))
+    if not full:
+        return seen
+    seen["info"] = {k: v for k, v in info.items() if k not in TIMED}
+    seen["tile_digest"] = dev.tile_digest()
+    seen["ldesc4"] = read_device(adr["ldesc4"], 16 * info["local_blocks"])
+    seen["lcol"] = read_device(adr["lcol"], 2 * info["nz"] if info["local_blocks"] else 0)
+    seen["lines"] = read_device(adr["lines"], 4 * info["local_lines_stored"])
+    seen["spmm"] = dev.spmm(X3)
+    if val.dtype == np.float64:
+        with sp.HllDevice.from_csr_device(dev) as hll:
+            assert sp.lib().spmv_hip_memset(hll.y_ptr, 0xFF, M * 8) == 0
+            seen["hll y"] = hll.spmv(xs[0], sp.HLL_AUTO)
+    if M == N:
+        seen["split_interior"] = dev.split_interior()
+        seen["y run_part"] = launched(dev, xs[0], lambda: (dev.run_part(0), dev.run_part(1)))
+        seen["split_columns"] = dev.split_columns(M // 4, 3 * M // 4)
+        seen["y run_split"] = launched(dev, xs[0], lambda: (dev.run_split(0), dev.run_split(1)))
+    return seen
+
+
+def same(a, b):
+    if isinstance(a, np.ndarray):
+        return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+    return a == b
+
+
+def assert_twin(h, target, x_list, what, oracle=None, y_refs=None, X3=None, twin_seen=None, full=True):
+    """h, a handle some producer built, against target = (M, N, rp, col, val): the arrays it must hold, and everything
+    an upload of them (twin_seen: what observe() saw of it; None: uploaded here, under the knobs in force) gives."""
+    M, N, rp, col, val = target
+    got = h.download()
+    for name, g, w in zip(("row_ptr", "col", "val"), got, (rp, col, val)):
+        assert g.dtype == w.dtype and g.shape == w.shape and g.tobytes() == w.tobytes(), \
+            f"{what}: the PRODUCER is wrong, not the handle: {name} is not the target's"
+    if X3 is None:
+        X3 = np.random.default_rng(3).uniform(-1, 1, (N, 3)).astype(val.dtype)
+    if twin_seen is None:
+        with sp.CsrDevice(M, N, rp, col, val) as twin:
+            twin_seen = observe(twin, target, x_list, X3, full)
+    seen = observe(h, target, x_list, X3, full)
+    for key in ("pad col", "pad val"):
+        for who, bytes_ in (("the adopted handle", seen[key]), ("the twin", twin_seen[key])):
+            assert bytes_ == bytes(len(bytes_)), f"{what}: {key}: {who}'s {KPAD} entries behind the array are not all zero"
+    assert seen.keys() == twin_seen.keys(), what
+    if full:
+        for k in seen["info"]:
+            assert seen["info"][k] == twin_seen["info"][k], \
+                f"{what}: info()[{k!r}] is {seen['info'][k]} on the adopted handle, {twin_seen['info'][k]} on the twin"
+    for key in seen:
+        assert same(seen[key], twin_seen[key]), f"{what}: {key} differs between the adopted handle and its twin"
+    if oracle is not None:
+        for name in sp.CSR_VARIANTS:
+            for k, x in enumerate(x_list):
+                y, label = seen[f"y {name} x{k}"], f"{what} {name} x{k}"
+                if val.dtype == np.float64:
+                    assert_parity(y, y_refs[k], rp, col, val, x, what=label)
+                else:
+                    assert_parity_f32(y, y_refs[k], rp, col, val, x, what=label)
+    return seen
+
+
+def twin_of(case, dtype, oracle, pinned):
+    """what observe() sees of the case's twin under its knobs: uploaded once per (case, dtype, pinned)"""
+    key = (case, np.dtype(dtype), pinned)
+    if key not in _TWINS:
+        tgt = target_of(case, dtype)
+        xs, _, X3 = inputs_of(case, dtype, oracle)
+        with under(**CASES[case][1], **(PINNED if pinned else {})):
+            with sp.CsrDevice(*tgt) as twin:
+                CASES[case][2](twin.info(), pinned)
+                _TWINS[key] = observe(twin, tgt, xs, X3, pinned)
+    return _TWINS[key]
+
+
+@pytest.mark.parametrize("producer,dtype", PRODUCER_CASES)
+@pytest.mark.parametrize("case", list(CASES))
+def test_adopted_handle_is_the_upload_of_its_arrays(gpu, oracle, case, producer, dtype):
+    tgt = target_of(case, dtype)
+    xs, y_refs, X3 = inputs_of(case, dtype, oracle)
+    twin_seen = twin_of(case, dtype, oracle, True)
+    with produced(producer, tgt, dict(CASES[case][1], **PINNED)) as h:
+        CASES[case][2](h.info(), True)
+        assert_twin(h, tgt, xs, f"{case} {producer} {np.dtype(dtype).name}", oracle, y_refs, X3, twin_seen)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("case", list(CASES))
+def test_adopted_handle_under_the_default_knobs(gpu, oracle, case, dtype):
+    """the searches left on (auto pattern plan, the placement's tries): the arrays, the pad and the bits only"""
+    tgt = target_of(case, dtype)
+    xs, y_refs, X3 = inputs_of(case, dtype, oracle)
+    twin_seen = twin_of(case, dtype, oracle, False)
+    for producer in PRODUCERS:
+        if (producer, dtype) in PRODUCER_CASES:
+            with produced(producer, tgt, CASES[case][1]) as h:
+                CASES[case][2](h.info(), False)
+                assert_twin(h, tgt, xs, f"{case} {producer} {np.dtype(dtype).name}, default knobs", oracle, y_refs, X3,
+                            twin_seen, full=False)
+
+
+# ---------------------------------------------------------------- consumers that keep state
+def spd_target(dtype):
+    """synth.fem_like((6, 6, 40), 1) -- symmetric (test_gpu_transpose.py), but with diagonal entries of either sign, which
+    the AMG setup refuses -- with a diagonal that dominates: the same pattern, symmetric positive definite"""
+    M, rp, col, val = synth.fem_like((6, 6, 40), 1)
+    rp, col, val = symmetric_dominant(M, rp, col, val)
+    return M, M, rp, col, val.astype(dtype)
+
+
+def same_results(a, b, what):
+    """two results of a solver or a reader: arrays and dicts of arrays by their bytes, times left out"""
+    if isinstance(a, (tuple, list)):
+        assert len(a) == len(b), what
+        for k, (u, v) in enumerate(zip(a, b)):
+            same_results(u, v, f"{what}[{k}]")
+    elif isinstance(a, dict):
+        assert a.keys() == b.keys(), what
+        for k in a:
+            same_results(a[k], b[k], f"{what}[{k!r}]")
+    elif isinstance(a, np.ndarray):
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), f"{what} differs"
+    else:
+        assert a == b, f"{what}: {a!r} vs {b!r}"
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("producer", ["transpose", "matmul", "add"])
+def test_solvers_and_preconditioner_builds_on_an_adopted_handle(gpu, producer, dtype):
+    tgt = spd_target(dtype)
+    M = tgt[0]
+    rng = np.random.default_rng(31)
+    b, B = rng.uniform(-1, 1, M).astype(dtype), rng.uniform(-1, 1, (M, 3)).astype(dtype)
+    xs = [rng.uniform(-1, 1, M).astype(dtype), wide_range(rng, M, dtype)]
+
+    def consume(dev):
+        out = {}
+        with dev.preconditioner("jacobi") as J:
+            out["pcg"] = dev.pcg(b, 5, precond=J)[:4]             # (the last element of each result: milliseconds)
+        out["bicgstab"] = dev.bicgstab(b, 5)[:3]
+        out["cg_multi"] = dev.cg_multi(B, 5)[:3]
+        with dev.preconditioner("ilu0") as P:
+            out["ilu0"] = P.factors()
+        with dev.preconditioner("amg") as P:
+            out["amg"] = P.levels()
+        with dev.transpose() as at:
+            out["cgls"] = dev.cgls(b, 5, at=at)[:4]
+        return out
+
+    with produced(producer, tgt, PINNED) as h:
+        what = f"fem-like {producer} {np.dtype(dtype).name}"
+        assert_twin(h, tgt, xs, what)
+        with sp.CsrDevice(*tgt) as twin:
+            same_results(consume(h), consume(twin), what)
+
+
+def symmetric_dominant(M, rp, col, val):
+    """A + A^T on the union of the two patterns with a diagonal that dominates: symmetric positive definite"""
+    rows = np.repeat(np.arange(M, dtype=np.int64), np.diff(rp))
+    i, j, v = np.concatenate([rows, col]), np.concatenate([col, rows]), np.concatenate([val, val])
+    off = i != j
+    key, first = np.unique(i[off] * M + j[off], return_index=True)
+    i, j, v = key // M, key % M, v[off][first]
+    low = i > j                                                   # one value per pair, mirrored
+    i, j, v = np.concatenate([i[low], j[low]]), np.concatenate([j[low], i[low]]), np.concatenate([v[low], v[low]])
+    diag = np.zeros(M)
+    np.add.at(diag, i, np.abs(v))
+    i, j, v = np.concatenate([i, np.arange(M)]), np.concatenate([j, np.arange(M)]), np.concatenate([v, diag + 1.0])
+    order = np.lexsort((j, i))
+    out = np.zeros(M + 1, dtype=np.int64)
+    np.add.at(out, i + 1, 1)
+    return np.cumsum(out).astype(np.int32), j[order].astype(np.int32), v[order]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("name", ["T1, symmetric and dominant", "one row"])
+def test_fsai_apply_is_the_two_products_on_uploads_of_its_factors(gpu, name, dtype):
+    """The fifth adopt site: G adopted from the build's arrays, G^T its device transpose.  The apply is their two AUTO
+    launches, so it must give the bytes of the same two launches on uploads of the factors it returns."""
+    if name == "one row":
+        M, rp, col, val = 1, np.array([0, 1], np.int32), np.zeros(1, np.int32), np.array([2.0])
+    else:
+        M = target_of("T1", np.float64)[0]
+        rp, col, val = symmetric_dominant(M, *target_of("T1", np.float64)[2:])
+    val = val.astype(dtype)
+    rng = np.random.default_rng(41)
+    with under(**PINNED):
+        with sp.CsrDevice(M, M, rp, col, val) as dev:
+            dirty_allocations(len(col), val.itemsize)
+            with dev.preconditioner("fsai") as P:
+                Gf, Uf = P.factors()
+                with sp.CsrDevice(M, M, *Gf) as G, sp.CsrDevice(M, M, *Uf) as U:
+                    for r in (rng.uniform(-1, 1, M).astype(dtype), wide_range(rng, M, dtype)):
+                        assert P.apply(r).tobytes() == U.spmv(G.spmv(r)).tobytes(), f"{name} {np.dtype(dtype).name}"
