@@ -784,9 +784,32 @@ int spmv_fsai_plan(int n, const int *row_ptr, const int *col, const double *val,
  *                                    (n_l + 1 entries; R: aggregates + 1) and scalars; else all.
  *   spmv_amg_plan_build / _levels / _level / _free / _error   the host setup alone (no device needed) on canonical rows
  *                                    (ascending columns in [0, n) without repeats, else -1): the same reader in fp64,
- *                                    with which = SPMV_AMG_T as well; _error is the message of this thread's last -1. */
+ *                                    with which = SPMV_AMG_T as well; _error is the message of this thread's last -1.
+ * The setup on the device (opt-in; the host setup above is the definition and stays the default):
+ *   spmv_hip_csr_precond_build_amg_device   the same preconditioner, byte for byte: for every handle, dtype and argument
+ *                                    set on which spmv_hip_csr_precond_build_amg succeeds it holds the same row_ptr, col
+ *                                    and val of every A_l, P_l and R_l, the same dense inverse, w, rho, kinds, rows,
+ *                                    aggregates and g; where that refuses, this refuses with the same message (*out
+ *                                    stays NULL, the HIP error state clean, the handle working).  The hierarchy is made in
+ *                                    fp64 on the device from the canonical block (an fp32 handle's values widened) and
+ *                                    rounded once at the end.  Per level: row statistics (d, rho, the lowest bad
+ *                                    diagonal); the strength graph by a filter, a radix sort of both directions of every
+ *                                    strong entry and a pass that drops repeats; the aggregation on the host (serial by
+ *                                    definition, about 1 % of the host setup); P = T - diag(w / d) A T, R = P^T and
+ *                                    A_{l+1} = R (A P) by the cores of spmv_hip_csr_spgemm and spmv_hip_csr_transpose,
+ *                                    which are defined as the host setup's sums and order; the dense inverse of a DIRECT
+ *                                    level on the host.  block_products goes to all three products of a level: 0 (auto),
+ *                                    -1 (global tier only) or a power of two in [64, 4096], as in spmv_hip_csr_spgemm;
+ *                                    the other arguments are refused as spmv_hip_csr_precond_build_amg refuses them.
+ *                                    Of spmv_hip_precond_amg_info's three times the first is the download, the second the
+ *                                    device setup, the third level 0's upload and the workspace.
+ *   spmv_hip_precond_amg_setup_info  info[SPMV_PRECOND_AMG_SETUP_INFO_WORDS] = the setup (0 host, 1 device), then
+ *                                    microseconds of the device setup's phases over all levels: row statistics, strength
+ *                                    graph, aggregation (host), A T with the smoothing of P, transpose, A P, R (A P),
+ *                                    coarsest inverse (host), rounding to the dtype.  A host-built P: 0 and zeros. */
 enum { SPMV_PRECOND_AMG = 6 };
 enum { SPMV_PRECOND_AMG_INFO_WORDS = 41 };
+enum { SPMV_PRECOND_AMG_SETUP_INFO_WORDS = 10 };
 enum { SPMV_AMG_A = 0, SPMV_AMG_P = 1, SPMV_AMG_R = 2, SPMV_AMG_INV = 3, SPMV_AMG_T = 4 };
 enum { SPMV_AMG_NOT_COARSEST = 0, SPMV_AMG_DIRECT = 1, SPMV_AMG_SMOOTH = 2 };
 typedef struct spmv_amg_plan spmv_amg_plan;
@@ -799,7 +822,10 @@ void spmv_amg_plan_free(spmv_amg_plan *plan);
 const char *spmv_amg_plan_error(void);
 int spmv_hip_csr_precond_build_amg(const spmv_csr_dev *m, double theta, int coarse_rows, int max_levels, int chain,
                                    spmv_precond **out);
+int spmv_hip_csr_precond_build_amg_device(const spmv_csr_dev *m, double theta, int coarse_rows, int max_levels,
+                                          int chain, int block_products, spmv_precond **out);
 int spmv_hip_precond_amg_info(const spmv_precond *P, int *info);
+int spmv_hip_precond_amg_setup_info(const spmv_precond *P, int *info);
 int spmv_hip_precond_amg_level(const spmv_precond *P, int level, int which, int *row_ptr, int *col, void *val,
                                double *scalars);
 int spmv_hip_precond_work_bytes(const spmv_precond *P, int k, long long *bytes);

@@ -260,7 +260,10 @@ _PROTOTYPES = {
     "spmv_amg_plan_error": (C.c_char_p, []),
     "spmv_hip_csr_precond_build_amg": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int,
                                                  C.POINTER(C.c_void_p)]),
+    "spmv_hip_csr_precond_build_amg_device": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                        C.POINTER(C.c_void_p)]),
     "spmv_hip_precond_amg_info": (C.c_int, [C.c_void_p, c_int_p]),
+    "spmv_hip_precond_amg_setup_info": (C.c_int, [C.c_void_p, c_int_p]),
     "spmv_hip_precond_amg_level": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_int_p, C.c_void_p, c_double_p]),
     "spmv_hip_precond_work_bytes": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_longlong)]),
     "spmv_hip_csr_pcg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, c_int_p, C.c_void_p,

@@ -1,5 +1,6 @@
 // spmv_amg.hip -- the smoothed-aggregation AMG preconditioner of a CSR handle: one V(1,1) cycle per apply
-// (include/spmv_hip.h; the kernels are in amg_kernels.hpp, the setup in host/amg_plan.c).
+// (include/spmv_hip.h; the kernels are in amg_kernels.hpp, the setup in host/amg_plan.c).  spmv_amg_setup.hip makes the
+// same object with the setup on the device; what the two share (the object, amg_finish, amg_wrap) is in amg_levels.hpp.
 //
 // The build, once per object:
 //   1. the handle's diagonal block is downloaded and made canonical (canon_rows.hpp), as the triangular and FSAI builds do;
@@ -27,76 +28,19 @@
 // and 32 rows behind the vector's last: for k columns the vector is at k off_v, 128-byte aligned, with a line tail the
 // x-window kernels may read (zero in P's own workspace; a caller's d_work should be zeroed once).  An apply allocates
 // nothing and reads nothing back.
-#include "spmv_internal.hpp"
+#include "amg_levels.hpp"
 
-#include <cmath>
 #include <memory>
 
-#include "amg_kernels.hpp"
 #include "canon_rows.hpp"
-#include "precond_kernels.hpp"
 
 namespace {
 
 constexpr int kAmgSpmv = 100;  // a host-side pass: out = A_0 in through the level-0 handle
 
-struct AmgOp {  // a CSR operator of P's own: values of the handle's dtype
-    int *rp = nullptr, *col = nullptr;
-    void *val = nullptr;
-    int rows = 0, G = 1;
-    long long nz = 0;
-    void release() {
-        (void)hipFree(rp), (void)hipFree(col), (void)hipFree(val);
-        rp = col = nullptr, val = nullptr;
-    }
-};
-
-// lanes per row of an operator: the largest power of two <= its mean row, at most 32
-int amg_lanes(long long nz, int rows) {
-    const long long mean = rows ? nz / rows : 0;
-    return pow2_floor((int)std::min<long long>(std::max<long long>(mean, 1), 32));
-}
-
-}  // namespace
-
-struct spmv_amg_precond {
-    int levels = 0, chain = 1, first_chained = -1, launches = 0, coarsest = 0;
-    spmv_csr_dev *A0 = nullptr;  // level 0 when it is not DIRECT
-    AmgOp A[kAmgMaxLevels], P[kAmgMaxLevels], R[kAmgMaxLevels], inv;
-    double *g[kAmgMaxLevels] = {};
-    double w[kAmgMaxLevels] = {}, rho[kAmgMaxLevels] = {};
-    int kind[kAmgMaxLevels] = {}, n[kAmgMaxLevels] = {}, na[kAmgMaxLevels] = {};
-    long long a_nz[kAmgMaxLevels] = {};
-    std::vector<AmgStep> steps;
-    AmgStep *d_steps = nullptr;
-    int tail0 = -1, tail1 = -1;    // the passes of the chained tail
-    long long work_values = 0;     // values of all level vectors at k = 1
-    void *work = nullptr;          // P's own, for one right-hand side
-    int us[3] = {0, 0, 0};
-    ~spmv_amg_precond() {
-        spmv_hip_csr_free(A0);
-        for (int l = 0; l < kAmgMaxLevels; ++l) {
-            A[l].release(), P[l].release(), R[l].release();
-            (void)hipFree(g[l]);
-        }
-        inv.release();
-        (void)hipFree(d_steps);
-        (void)hipFree(work);
-        (void)hipGetLastError();
-    }
-};
-
-namespace {
-
 struct PlanGuard {
     spmv_amg_plan *p = nullptr;
     ~PlanGuard() { spmv_amg_plan_free(p); }
-};
-
-// one operator of the plan on the host: fp64
-struct HostOp {
-    std::vector<int> rp, col;
-    std::vector<double> val;
 };
 
 int plan_read(const spmv_amg_plan *plan, int level, int which, int rows, HostOp &h) {
@@ -108,24 +52,6 @@ int plan_read(const spmv_amg_plan *plan, int level, int which, int rows, HostOp 
     if (spmv_amg_plan_level(plan, level, which, h.rp.data(), h.col.data(), h.val.data(), nullptr))
         return fail("%s", spmv_amg_plan_error());
     h.col.resize(nz), h.val.resize(nz);
-    return 0;
-}
-
-template <typename T>
-int op_upload(const HostOp &h, int rows, AmgOp &op, const char *what, int level) {
-    const size_t nz = h.col.size();
-    std::vector<T> v(nz);
-    for (size_t e = 0; e < nz; ++e) {
-        v[e] = (T)h.val[e];
-        if (!std::isfinite((double)v[e]))
-            return fail("csr_precond_build_amg: level %d: an entry of %s is not finite in the handle's dtype", level, what);
-    }
-    op.rows = rows;
-    op.nz = (long long)nz;
-    op.G = amg_lanes(op.nz, rows);
-    if (upload_array(&op.rp, h.rp.data(), (size_t)rows + 1, 0) || upload_array(&op.col, h.col.data(), nz, 4) ||
-        upload_array((T **)&op.val, v.data(), nz, 4))
-        return -1;
     return 0;
 }
 
@@ -193,8 +119,7 @@ int amg_build(const spmv_csr_dev *m, double theta, int coarse_rows, int max_leve
     const double t1 = now_ms();
     PlanGuard plan;
     if (spmv_amg_plan_build(n, A.rp.data(), A.col.data(), A.val.data(), theta, coarse_rows, max_levels, &plan.p))
-        return fail("csr_precond_build_amg (local rows; the handle's first row is global row %d): %s", m->row0,
-                    spmv_amg_plan_error());
+        return fail(kAmgMsgPlan, m->row0, spmv_amg_plan_error());
     const double t2 = now_ms();
     std::unique_ptr<spmv_amg_precond> ap(new spmv_amg_precond);
     ap->levels = spmv_amg_plan_levels(plan.p);
@@ -214,8 +139,7 @@ int amg_build(const spmv_csr_dev *m, double theta, int coarse_rows, int max_leve
                 if (h.col[e] == i) g[i] = ap->w[l] / (double)(T)h.val[e];
         for (int i = 0; i < nl; ++i)
             if (!std::isfinite(g[i]))
-                return fail("csr_precond_build_amg: level %d: the diagonal of row %d is not finite and > 0 in the handle's "
-                            "dtype", l, i);
+                return fail(kAmgMsgDiagonal, l, i);
         if (to_device(&ap->g[l], g)) return -1;
         if (l == 0 && ap->kind[0] != SPMV_AMG_DIRECT) {
             int rc;
@@ -226,53 +150,21 @@ int amg_build(const spmv_csr_dev *m, double theta, int coarse_rows, int max_leve
                 rc = spmv_hip_csr_upload_f32(n, n, h.rp.data(), h.col.data(), v.data(), 0, n, &ap->A0);
             }
             if (rc) return -1;
-        } else if (op_upload<T>(h, nl, ap->A[l], "A", l)) {
+        } else if (amg_op_upload<T>(h, nl, ap->A[l], "A", l)) {
             return -1;
         }
         if (ap->kind[l] == SPMV_AMG_DIRECT) {
-            if (plan_read(plan.p, l, SPMV_AMG_INV, nl, h) || op_upload<T>(h, nl, ap->inv, "the inverse", l)) return -1;
+            if (plan_read(plan.p, l, SPMV_AMG_INV, nl, h) || amg_op_upload<T>(h, nl, ap->inv, "the inverse", l)) return -1;
         } else if (ap->kind[l] == SPMV_AMG_NOT_COARSEST) {
-            if (plan_read(plan.p, l, SPMV_AMG_P, nl, h) || op_upload<T>(h, nl, ap->P[l], "P", l)) return -1;
-            if (plan_read(plan.p, l, SPMV_AMG_R, ap->na[l], h) || op_upload<T>(h, ap->na[l], ap->R[l], "R", l)) return -1;
+            if (plan_read(plan.p, l, SPMV_AMG_P, nl, h) || amg_op_upload<T>(h, nl, ap->P[l], "P", l)) return -1;
+            if (plan_read(plan.p, l, SPMV_AMG_R, ap->na[l], h) || amg_op_upload<T>(h, ap->na[l], ap->R[l], "R", l)) return -1;
         }
     }
-    if (ap->levels) {
-        ap->coarsest = ap->kind[ap->levels - 1];
-        CycleWriter cw{ap.get(), {}, 0};
-        cw.emit(0, kAmgVecR);
-        ap->work_values = std::max<long long>(cw.next, 32);
-        // the chained tail: the passes of the levels from the first narrow one below 0 on
-        int lc = -1;
-        for (int l = 1; l < ap->levels && lc < 0; ++l)
-            if (ap->n[l] <= kAmgChainRows && ap->a_nz[l] <= kAmgChainEntries) lc = l;
-        if (ap->levels == 1 && ap->coarsest == SPMV_AMG_DIRECT) lc = 0;
-        const int ns = (int)ap->steps.size();
-        if (lc >= 0 && ap->chain) {
-            ap->first_chained = lc;
-            for (int q = 0; q < ns; ++q)
-                if (cw.level_of[q] >= lc) {
-                    if (ap->tail0 < 0) ap->tail0 = q;
-                    ap->tail1 = q + 1;
-                }
-        }
-        ap->launches = ns - (ap->tail0 >= 0 ? ap->tail1 - ap->tail0 - 1 : 0);
-        if (upload_array(&ap->d_steps, ap->steps.data(), (size_t)ns, 0)) return -1;
-        const size_t bytes = (size_t)ap->work_values * sizeof(T);
-        hipError_t e = hipMalloc(&ap->work, bytes);
-        if (e == hipSuccess) e = hipMemset(ap->work, 0, bytes);
-        if (e != hipSuccess) return fail("csr_precond_build_amg: allocation failed: %s", hipGetErrorString(e));
-    }
+    if (amg_finish(ap.get(), (int)sizeof(T))) return -1;
     ap->us[0] = (int)((t1 - t0) * 1e3);
     ap->us[1] = (int)((t2 - t1) * 1e3);
     ap->us[2] = (int)((now_ms() - t2) * 1e3);
-    spmv_precond *P = new spmv_precond;
-    P->kind = SPMV_PRECOND_AMG;
-    P->block = 1;
-    P->rows = n;
-    P->row0 = m->row0;
-    P->value_bytes = (int)sizeof(T);
-    P->amg = ap.release();
-    *out = P;
+    *out = amg_wrap(ap.release(), n, m->row0, (int)sizeof(T));
     return 0;
 }
 
@@ -301,6 +193,46 @@ int amg_run(const spmv_amg_precond *ap, int k, const void *R, void *Z, void *wor
 }
 
 }  // namespace
+
+int amg_finish(spmv_amg_precond *ap, int value_bytes) {
+    if (!ap->levels) return 0;
+    ap->coarsest = ap->kind[ap->levels - 1];
+    CycleWriter cw{ap, {}, 0};
+    cw.emit(0, kAmgVecR);
+    ap->work_values = std::max<long long>(cw.next, 32);
+    // the chained tail: the passes of the levels from the first narrow one below 0 on
+    int lc = -1;
+    for (int l = 1; l < ap->levels && lc < 0; ++l)
+        if (ap->n[l] <= kAmgChainRows && ap->a_nz[l] <= kAmgChainEntries) lc = l;
+    if (ap->levels == 1 && ap->coarsest == SPMV_AMG_DIRECT) lc = 0;
+    const int ns = (int)ap->steps.size();
+    if (lc >= 0 && ap->chain) {
+        ap->first_chained = lc;
+        for (int q = 0; q < ns; ++q)
+            if (cw.level_of[q] >= lc) {
+                if (ap->tail0 < 0) ap->tail0 = q;
+                ap->tail1 = q + 1;
+            }
+    }
+    ap->launches = ns - (ap->tail0 >= 0 ? ap->tail1 - ap->tail0 - 1 : 0);
+    if (upload_array(&ap->d_steps, ap->steps.data(), (size_t)ns, 0)) return -1;
+    const size_t bytes = (size_t)ap->work_values * (size_t)value_bytes;
+    hipError_t e = hipMalloc(&ap->work, bytes);
+    if (e == hipSuccess) e = hipMemset(ap->work, 0, bytes);
+    if (e != hipSuccess) return fail("csr_precond_build_amg: allocation failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+spmv_precond *amg_wrap(spmv_amg_precond *ap, int rows, int row0, int value_bytes) {
+    spmv_precond *P = new spmv_precond;
+    P->kind = SPMV_PRECOND_AMG;
+    P->block = 1;
+    P->rows = rows;
+    P->row0 = row0;
+    P->value_bytes = value_bytes;
+    P->amg = ap;
+    return P;
+}
 
 void precond_amg_free(spmv_amg_precond *ap) { delete ap; }
 

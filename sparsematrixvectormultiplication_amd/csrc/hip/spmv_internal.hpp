@@ -413,6 +413,36 @@ struct DevBuf {
     hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 16)); }
     template <typename U> U *as() const { return static_cast<U *>(p); }
 };
+// Bare CSR arrays on the device: what the product and the transpose cores take and hand back, and what the AMG device
+// setup (spmv_amg_setup.hip) keeps of a level.  Not a handle: no plans, no vectors.  release() frees what it points at,
+// so a DevCsr that only LOOKS at a handle's arrays (csr_view) is never released.
+struct DevCsr {
+    int rows = 0, cols = 0;
+    long long nz = 0;
+    int *rp = nullptr, *col = nullptr;  // [rows + 1], [nz (+ kPad zeroed entries where a core made them)]
+    void *val = nullptr;
+    void release() {
+        (void)hipFree(rp), (void)hipFree(col), (void)hipFree(val);
+        rp = col = nullptr, val = nullptr;
+    }
+};
+inline DevCsr csr_view(const spmv_csr_dev *m) {
+    DevCsr v;
+    v.rows = m->M_total, v.cols = m->N, v.nz = m->nz, v.rp = m->row_ptr, v.col = m->col, v.val = m->val;
+    return v;
+}
+// spmv_spgemm.hip: C = A B on bare arrays (values of value_bytes bytes; the definition of spmv_hip_csr_spgemm).  On
+// success C owns its three arrays (col / val with kPad zeroed entries behind, ready for csr_adopt), rp_host is C's
+// row_ptr, stats[8] the stats of spmv_hip_csr_spgemm and ms[0..2] count / symbolic / numeric; on -1 C is empty.
+int spgemm_core(int value_bytes, const DevCsr &A, const DevCsr &B, int block_products, long long chunk_products, DevCsr *C,
+                std::vector<int> &rp_host, long long *stats, double *ms);
+int spgemm_max_block_products();  // the cap of the on-chip tier (spgemm_kernels.hpp: kSgMaxProducts)
+// block_products as spmv_hip_csr_spgemm takes it: 0 (auto), -1 (no on-chip tier) or a power of two in [64, cap]
+inline bool spgemm_block_products_ok(int bp) {
+    return bp == 0 || bp == -1 || (bp >= 64 && bp <= spgemm_max_block_products() && (bp & (bp - 1)) == 0);
+}
+// spmv_transpose.hip: At = A^T on bare arrays, the same way
+int transpose_core(int value_bytes, const DevCsr &A, DevCsr *At, std::vector<int> &rp_host);
 // spmv_csr.hip: tile plans alone for rows given as (first entry, length) over host arrays (an HLL slab's rows);
 // *out = NULL when the rows get no plan
 // (col / val: host copies of the rows' arrays, or NULL when d_col / d_val -- the same arrays on the device -- are given

@@ -10,6 +10,9 @@
 //              radix_sort_pairs on the bits in use and sg_row_compress
 //   adopt      csr_adopt_*: C is an ordinary handle with upload's plans
 //
+// Everything in front of the adopt is spgemm_core, on bare device arrays: the AMG device setup (spmv_amg_setup.hip) forms
+// its products with it and keeps the arrays.
+//
 // The workspace is the per-row counts, the block list and one chunk's keys and products (twice: the sort's output).
 #include "spmv_internal.hpp"
 
@@ -44,16 +47,18 @@ struct Chunk {
     long long products = 0;
 };
 
+// the product on bare arrays: everything but the adopt
 template <typename T>
-int spgemm_body(const spmv_csr_dev *a, const spmv_csr_dev *b, int block_products, long long chunk_products,
-                spmv_csr_dev **out, long long *stats, double *ms) {
-    const int M = a->M_total, N = b->N;
+int spgemm_core_t(const DevCsr &A, const DevCsr &B, int block_products, long long chunk_products, DevCsr *C,
+                  std::vector<int> &rp, long long *stats, double *ms) {
+    const DevCsr *a = &A, *b = &B;
+    const int M = a->rows, N = b->cols;
     const int cap = block_products == 0 ? kSgMaxProducts : block_products;  // -1: no on-chip tier
     const long long chunk_cap = chunk_products ? chunk_products : kSgAutoChunk;
     const T *valA = static_cast<const T *>(a->val), *valB = static_cast<const T *>(b->val);
     UploadTrace trace("csr_spgemm");
     double t0 = UploadTrace::now();
-    double split[4] = {0, 0, 0, 0};
+    double split[3] = {0, 0, 0};
     auto lap = [&](int k) {
         const double t = UploadTrace::now();
         split[k] = (t - t0) * 1e3;
@@ -71,7 +76,7 @@ int spgemm_body(const spmv_csr_dev *a, const spmv_csr_dev *b, int block_products
     if (M) {
         constexpr int kRows = kBlock / kSgCountLanes;
         const int grid = (int)std::min<long long>(kSgMaxGrid, ((long long)M + kRows - 1) / kRows);
-        hipLaunchKernelGGL(sg_count, dim3(grid), dim3(kBlock), 0, g_stream, M, a->row_ptr, a->col, b->row_ptr,
+        hipLaunchKernelGGL(sg_count, dim3(grid), dim3(kBlock), 0, g_stream, M, a->rp, a->col, b->rp,
                            d_products.as<long long>());
         e = hipGetLastError();
         if (e == hipSuccess)
@@ -115,7 +120,7 @@ int spgemm_body(const spmv_csr_dev *a, const spmv_csr_dev *b, int block_products
     for (const Chunk &c : chunks) chunk_max = std::max(chunk_max, c.products);
 
     // ---- workspace
-    DevBuf d_desc, d_lrows, d_off, d_kin, d_kout, d_vin, d_vout, d_tmp, d_rpC;
+    DevBuf d_desc, d_lrows, d_off, d_kin, d_kout, d_vin, d_vout, d_tmp, d_rpC;  // (d_rpC: handed to C at the end)
     const unsigned col_bits = bits_for((unsigned long long)N);
     size_t tmp_bytes = 0;
     e = d_desc.alloc(desc.size() * sizeof(int4));
@@ -149,11 +154,11 @@ int spgemm_body(const spmv_csr_dev *a, const spmv_csr_dev *b, int block_products
         if (desc.empty()) return;
         if (numeric)
             hipLaunchKernelGGL((sg_block<T, true>), dim3(bgrid), dim3(kBlock), (size_t)cap * 16, g_stream, (int)desc.size(), cap,
-                               d_desc.as<int4>(), a->row_ptr, a->col, valA, b->row_ptr, b->col, valB, d_products.as<long long>(),
+                               d_desc.as<int4>(), a->rp, a->col, valA, b->rp, b->col, valB, d_products.as<long long>(),
                                d_cnt.as<int>(), d_rpC.as<int>(), d_colC, d_valC);
         else
             hipLaunchKernelGGL((sg_block<T, false>), dim3(bgrid), dim3(kBlock), (size_t)cap * 12, g_stream, (int)desc.size(), cap,
-                               d_desc.as<int4>(), a->row_ptr, a->col, valA, b->row_ptr, b->col, valB, d_products.as<long long>(),
+                               d_desc.as<int4>(), a->rp, a->col, valA, b->rp, b->col, valB, d_products.as<long long>(),
                                d_cnt.as<int>(), d_rpC.as<int>(), d_colC, d_valC);
     };
     auto run_chunks = [&](bool numeric) -> hipError_t {
@@ -167,7 +172,7 @@ int spgemm_body(const spmv_csr_dev *a, const spmv_csr_dev *b, int block_products
             hipError_t err;
             if (numeric) {
                 hipLaunchKernelGGL((sg_expand<T, true>), dim3(grid), dim3(kBlock), 0, g_stream, ch.rows, rows, o, (int)col_bits,
-                                   a->row_ptr, a->col, valA, b->row_ptr, b->col, valB, kin, d_vin.as<double>());
+                                   a->rp, a->col, valA, b->rp, b->col, valB, kin, d_vin.as<double>());
                 size_t bytes = tmp_bytes;
                 err = rocprim::radix_sort_pairs(d_tmp.p, bytes, kin, kout, d_vin.as<double>(), d_vout.as<double>(),
                                                 (size_t)ch.products, 0u, bits, g_stream);
@@ -176,7 +181,7 @@ int spgemm_body(const spmv_csr_dev *a, const spmv_csr_dev *b, int block_products
                                    (1ull << col_bits) - 1, kout, d_vout.as<double>(), d_rpC.as<int>(), d_colC, d_valC);
             } else {
                 hipLaunchKernelGGL((sg_expand<T, false>), dim3(grid), dim3(kBlock), 0, g_stream, ch.rows, rows, o, (int)col_bits,
-                                   a->row_ptr, a->col, valA, b->row_ptr, b->col, valB, kin, (double *)nullptr);
+                                   a->rp, a->col, valA, b->rp, b->col, valB, kin, (double *)nullptr);
                 size_t bytes = tmp_bytes;
                 err = rocprim::radix_sort_keys(d_tmp.p, bytes, kin, kout, (size_t)ch.products, 0u, bits, g_stream);
                 if (err != hipSuccess) return err;
@@ -187,7 +192,8 @@ int spgemm_body(const spmv_csr_dev *a, const spmv_csr_dev *b, int block_products
     };
 
     // ---- symbolic
-    std::vector<int> rp((size_t)M + 1, 0), cnt((size_t)M, 0);
+    std::vector<int> cnt((size_t)M, 0);
+    rp.assign((size_t)M + 1, 0);
     run_blocks(false);
     e = run_chunks(false);
     if (e == hipSuccess && M)
@@ -230,9 +236,10 @@ int spgemm_body(const spmv_csr_dev *a, const spmv_csr_dev *b, int block_products
         }
         lap(2);
         trace.mark("numeric");
-        rc = csr_adopt<T>(M, N, rp.data(), d_colC, d_valC, out);
-        if (rc == 0) d_colC = nullptr, d_valC = nullptr;  // the handle owns them now
-        lap(3);
+        C->rows = M, C->cols = N, C->nz = nz;
+        C->rp = d_rpC.as<int>(), C->col = d_colC, C->val = d_valC;  // C owns them now
+        d_rpC.p = nullptr, d_colC = nullptr, d_valC = nullptr;
+        rc = 0;
     } while (0);
     (void)hipFree(d_colC);
     (void)hipFree(d_valC);
@@ -242,6 +249,25 @@ int spgemm_body(const spmv_csr_dev *a, const spmv_csr_dev *b, int block_products
         const long long s[8] = {total, nz, (long long)desc.size(), block_rows, n_long, (long long)chunks.size(), widest, widest_nz};
         std::copy(s, s + 8, stats);
     }
+    if (ms) std::copy(split, split + 3, ms);
+    return 0;
+}
+
+// core, then the adopt: C is an ordinary handle with upload's plans
+template <typename T>
+int spgemm_body(const spmv_csr_dev *a, const spmv_csr_dev *b, int block_products, long long chunk_products,
+                spmv_csr_dev **out, long long *stats, double *ms) {
+    DevCsr C;
+    std::vector<int> rp;
+    double split[4] = {0, 0, 0, 0};
+    if (spgemm_core_t<T>(csr_view(a), csr_view(b), block_products, chunk_products, &C, rp, stats, split)) return -1;
+    const double t0 = UploadTrace::now();
+    const int rc = csr_adopt<T>(C.rows, C.cols, rp.data(), C.col, static_cast<T *>(C.val), out);
+    if (rc == 0) C.col = nullptr, C.val = nullptr;  // the handle owns them now
+    C.release();
+    (void)hipGetLastError();
+    split[3] = (UploadTrace::now() - t0) * 1e3;
+    if (rc) return rc;
     if (ms) std::copy(split, split + 4, ms);
     return 0;
 }
@@ -249,6 +275,14 @@ int spgemm_body(const spmv_csr_dev *a, const spmv_csr_dev *b, int block_products
 bool whole(const spmv_csr_dev *m) { return m->row0 == 0 && m->M_local == m->M_total; }
 
 }  // namespace
+
+int spgemm_max_block_products() { return kSgMaxProducts; }
+
+int spgemm_core(int value_bytes, const DevCsr &A, const DevCsr &B, int block_products, long long chunk_products, DevCsr *C,
+                std::vector<int> &rp_host, long long *stats, double *ms) {
+    return value_bytes == 8 ? spgemm_core_t<double>(A, B, block_products, chunk_products, C, rp_host, stats, ms)
+                            : spgemm_core_t<float>(A, B, block_products, chunk_products, C, rp_host, stats, ms);
+}
 
 extern "C" int spmv_hip_csr_spgemm(const spmv_csr_dev *a, const spmv_csr_dev *b, int block_products, long long chunk_products,
                                    spmv_csr_dev **out, long long *stats, double *ms) {
@@ -268,8 +302,7 @@ extern "C" int spmv_hip_csr_spgemm(const spmv_csr_dev *a, const spmv_csr_dev *b,
     if (a->value_bytes != b->value_bytes)
         return fail("csr_spgemm: A holds %d-byte values and B %d-byte values; the dtypes must agree", a->value_bytes,
                     b->value_bytes);
-    if (block_products != 0 && block_products != -1 &&
-        (block_products < 64 || block_products > kSgMaxProducts || (block_products & (block_products - 1)) != 0))
+    if (!spgemm_block_products_ok(block_products))
         return fail("csr_spgemm: block_products = %d; 0 (auto), -1 (no on-chip tier) or a power of two in [64, %d]",
                     block_products, kSgMaxProducts);
     if (chunk_products != 0 && chunk_products < 64)

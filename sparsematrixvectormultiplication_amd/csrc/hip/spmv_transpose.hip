@@ -7,6 +7,7 @@
 //   tr_gather       colT[k] = row, valT[k] = val[e] at every sorted position: values are moved, never combined
 //   tr_row_ptr      row_ptr of A^T from the sorted columns (columns without entries included)
 //
+// Everything in front of the adopt is transpose_core, on bare device arrays (the AMG device setup calls it too).
 // The columns of A are the sort's key input as they are; only the N + 1 row pointers of A^T cross to the host, and
 // the arrays go to csr_upload_impl through the adopt path, so A^T gets every plan and search an upload gives.
 #include "spmv_internal.hpp"
@@ -55,9 +56,11 @@ __global__ __launch_bounds__(kBlock) void tr_row_ptr(long long nz, int N, const 
     for (int q = prev + 1; q <= c; ++q) row_ptr[q] = (int)e;  // usually zero or one iteration
 }
 
+// the transpose on bare arrays: everything but the adopt
 template <typename T>
-int transpose_body(const spmv_csr_dev *m, spmv_csr_dev **out) {
-    const int M = m->M_total, N = m->N;
+int transpose_core_t(const DevCsr &A, DevCsr *At, std::vector<int> &rp) {
+    const DevCsr *m = &A;
+    const int M = m->rows, N = m->cols;
     const long long nz = m->nz;
     const size_t n = (size_t)nz, n1 = std::max<size_t>(n, 1);
     unsigned long long *d_pin = nullptr, *d_pout = nullptr;
@@ -65,7 +68,7 @@ int transpose_body(const spmv_csr_dev *m, spmv_csr_dev **out) {
     int *d_colT = nullptr, *d_rpT = nullptr;
     T *d_valT = nullptr;
     void *d_tmp = nullptr;
-    std::vector<int> rp((size_t)N + 1, 0);
+    rp.assign((size_t)N + 1, 0);
     UploadTrace trace("csr_transpose");  // SPMV_TRACE_UPLOAD=1: the build here, then upload's own phases
     int rc = -1;
     do {
@@ -80,7 +83,7 @@ int transpose_body(const spmv_csr_dev *m, spmv_csr_dev **out) {
         if (e != hipSuccess) { fail("csr_transpose: allocation failed: %s", hipGetErrorString(e)); break; }
         if (n) {
             const int rgrid = (int)std::min<long long>(kTrMaxGrid, ((long long)M + kTrWaves - 1) / kTrWaves);
-            hipLaunchKernelGGL(tr_make_pairs, dim3(rgrid), dim3(kBlock), 0, g_stream, M, m->row_ptr, d_pin);
+            hipLaunchKernelGGL(tr_make_pairs, dim3(rgrid), dim3(kBlock), 0, g_stream, M, m->rp, d_pin);
             // only the bits a column index can use (a matrix of one column: a single bit, every key 0)
             unsigned col_bits = 1;
             while (col_bits < 32 && (1ull << col_bits) < (unsigned long long)N) ++col_bits;
@@ -102,8 +105,10 @@ int transpose_body(const spmv_csr_dev *m, spmv_csr_dev **out) {
         if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
         if (e != hipSuccess) { fail("csr_transpose: build failed: %s", hipGetErrorString(e)); break; }
         trace.mark("device build");
-        rc = csr_adopt<T>(N, M, rp.data(), d_colT, d_valT, out);
-        if (rc == 0) d_colT = nullptr, d_valT = nullptr;  // the handle owns them now
+        At->rows = N, At->cols = M, At->nz = nz;
+        At->rp = d_rpT, At->col = d_colT, At->val = d_valT;  // At owns them now
+        d_rpT = nullptr, d_colT = nullptr, d_valT = nullptr;
+        rc = 0;
     } while (0);
     (void)hipFree(d_pin);
     (void)hipFree(d_pout);
@@ -116,7 +121,24 @@ int transpose_body(const spmv_csr_dev *m, spmv_csr_dev **out) {
     return rc;
 }
 
+// core, then the adopt: A^T is an ordinary handle with upload's plans
+template <typename T>
+int transpose_body(const spmv_csr_dev *m, spmv_csr_dev **out) {
+    DevCsr At;
+    std::vector<int> rp;
+    if (transpose_core_t<T>(csr_view(m), &At, rp)) return -1;
+    const int rc = csr_adopt<T>(At.rows, At.cols, rp.data(), At.col, static_cast<T *>(At.val), out);
+    if (rc == 0) At.col = nullptr, At.val = nullptr;  // the handle owns them now
+    At.release();
+    (void)hipGetLastError();
+    return rc;
+}
+
 }  // namespace
+
+int transpose_core(int value_bytes, const DevCsr &A, DevCsr *At, std::vector<int> &rp_host) {
+    return value_bytes == 8 ? transpose_core_t<double>(A, At, rp_host) : transpose_core_t<float>(A, At, rp_host);
+}
 
 extern "C" int spmv_hip_csr_transpose(const spmv_csr_dev *m, spmv_csr_dev **out) {
     if (need_device()) return -1;

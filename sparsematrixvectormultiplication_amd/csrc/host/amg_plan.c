@@ -25,13 +25,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "amg_plan_parts.h"
 #include "spmv_hip.h"
-
-typedef struct {
-    int rows, cols;
-    int *rp, *col;
-    double *val;
-} amg_csr;
 
 typedef struct {
     amg_csr A, P, R, T;
@@ -159,8 +154,9 @@ static int csr_transpose(const amg_csr *A, amg_csr *B) {
     return 0;
 }
 
-/* inv = A^-1 dense by Gauss-Jordan on [A | I] with partial pivoting; 1: a zero or non-finite pivot; -1: no memory */
-static int dense_inverse(const amg_csr *A, double **out) {
+/* inv = A^-1 dense by Gauss-Jordan on [A | I] with partial pivoting; 1: a zero or non-finite pivot; -1: no memory
+ * (amg_plan_parts.h: the device setup calls it too) */
+int amg_dense_inverse(const amg_csr *A, double **out) {
     const int n = A->rows, w = 2 * n;
     double *aug = calloc((size_t)n * w + 1, sizeof(double));
     double *inv = malloc(((size_t)n * n + 1) * sizeof(double));
@@ -252,8 +248,9 @@ static int strength_graph(const amg_csr *A, const double *d, double theta, int *
     return 0;
 }
 
-/* agg[n] (-1: in no aggregate); returns the number of aggregates, -1 without memory */
-static int aggregate(int n, const int *s_rp, const int *s_col, int *agg) {
+/* agg[n] (-1: in no aggregate); returns the number of aggregates, -1 without memory (amg_plan_parts.h: the device
+ * setup calls it too) */
+int amg_aggregate(int n, const int *s_rp, const int *s_col, int *agg) {
     int na = 0;
     int *after_a = malloc(((size_t)n + 1) * sizeof(int));
     if (!after_a) return -1;
@@ -360,9 +357,9 @@ int spmv_amg_plan_build(int n, const int *row_ptr, const int *col, const double 
                 sum += fabs(A->val[e]);
             }
             if (!have || !isfinite(di) || !(di > 0.0)) {
-                const char *why = !have ? "has no diagonal entry" : "has a diagonal that is not finite and > 0";
-                if (l == 0) rc = refuse("amg_plan_build: row %d %s", i, why);
-                else rc = refuse("amg_plan_build: level %d: row %d of the coarse matrix %s", l, i, why);
+                const char *why = !have ? AMG_WHY_NO_DIAGONAL : AMG_WHY_BAD_DIAGONAL;
+                if (l == 0) rc = refuse(AMG_REFUSE_ROW, i, why);
+                else rc = refuse(AMG_REFUSE_COARSE_ROW, l, i, why);
                 break;
             }
             d[i] = di;
@@ -371,23 +368,22 @@ int spmv_amg_plan_build(int n, const int *row_ptr, const int *col, const double 
         }
         if (rc) break;
         if (!isfinite(rho) || !(rho > 0.0)) {
-            rc = refuse("amg_plan_build: level %d: an entry of the matrix is not finite", l);
+            rc = refuse(AMG_REFUSE_NOT_FINITE, l);
             break;
         }
         L->rho = rho;
         L->w = 4.0 / (3.0 * rho);
         if (nl <= coarse_rows) {
             L->kind = SPMV_AMG_DIRECT;
-            const int bad = dense_inverse(A, &L->inv);
+            const int bad = amg_dense_inverse(A, &L->inv);
             if (bad < 0) goto nomem;
-            if (bad) rc = refuse("amg_plan_build: level %d: a zero or non-finite pivot, the coarsest matrix (%d rows) "
-                                 "is singular", l, nl);
+            if (bad) rc = refuse(AMG_REFUSE_PIVOT, l, nl);
             break;
         }
         L->kind = SPMV_AMG_SMOOTH;
         if (l + 1 == max_levels) break;
         if (strength_graph(A, d, theta, s_rp, &s_col)) goto nomem;
-        const int na = aggregate(nl, s_rp, s_col, agg);
+        const int na = amg_aggregate(nl, s_rp, s_col, agg);
         if (na < 0) goto nomem;
         if (na == 0 || 10LL * na > 9LL * nl) break;
         L->kind = SPMV_AMG_NOT_COARSEST;
@@ -411,7 +407,7 @@ int spmv_amg_plan_build(int n, const int *row_ptr, const int *col, const double 
 nomem:
     free(d), free(s_rp), free(s_col), free(agg);
     spmv_amg_plan_free(p);
-    return refuse("amg_plan_build: out of host memory, or a product beyond int range");
+    return refuse(AMG_REFUSE_MEMORY);
 }
 
 int spmv_amg_plan_levels(const spmv_amg_plan *p) { return p ? p->levels : -1; }

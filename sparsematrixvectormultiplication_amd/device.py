@@ -36,6 +36,12 @@ AMG_MAX_LEVELS, AMG_MAX_COARSE_ROWS, AMG_CHAIN_ROWS, AMG_CHAIN_ENTRIES = 16, 256
 PRECOND_AMG_INFO = ("levels", "first_chained", "launches", "coarsest", "complexity_x1000", "download_us", "setup_us",
                     "upload_us", "chain")  # then rows[16] and entries[16] per level
 PRECOND_AMG_INFO_WORDS = len(PRECOND_AMG_INFO) + 2 * AMG_MAX_LEVELS
+# the AMG setups, and what spmv_hip_precond_amg_setup_info returns: the setup, then the device setup's phases
+AMG_SETUPS = {"host": 0, "device": 1}
+PRECOND_AMG_SETUP_INFO = ("setup", "stats_us", "strength_us", "aggregate_us", "tentative_us", "transpose_us", "ap_us",
+                          "rap_us", "inverse_us", "round_us")
+PRECOND_AMG_SETUP_INFO_WORDS = len(PRECOND_AMG_SETUP_INFO)
+SPGEMM_MAX_BLOCK_PRODUCTS = 4096
 # CsrDevice.triangular / the SSOR and ILU(0) preconditioners (SPMV_TRSV_*, SPMV_ORDER_*)
 TRSV_LOWER, TRSV_UPPER, TRSV_NONUNIT, TRSV_UNIT = 0, 1, 0, 1
 ORDER_NATURAL, ORDER_MULTICOLOR = 0, 1
@@ -512,7 +518,7 @@ class CsrDevice(_Handle):
                              f"the handle rows [{row0}, {row1})")
 
     def preconditioner(self, kind="jacobi", block=1, omega=1.0, ordering="natural", cap=32, theta=0.08, coarse_rows=64,
-                       max_levels=16, chain=True) -> "Preconditioner":
+                       max_levels=16, chain=True, setup="host", block_products=0) -> "Preconditioner":
         """A preconditioner of this handle's rows; it owns its arrays.  kind "jacobi" (block 1) or "block_jacobi"
         (block in [1, 32]): built on the device (spmv_hip_csr_precond_build).  kind "ssor" (0 < omega < 2; 1 is
         symmetric Gauss-Seidel) or "ilu0": two sparse triangular solves (spmv_hip_csr_precond_build_tri), block 1;
@@ -522,7 +528,10 @@ class CsrDevice(_Handle):
         ordering "natural".  kind "amg": smoothed-aggregation multigrid, one V(1,1) cycle per apply
         (spmv_hip_csr_precond_build_amg): strength threshold theta in [0, 1), a coarsest level of at most coarse_rows
         (in [1, 256]) rows solved by its dense inverse, at most max_levels (in [1, 16]) levels, chain: the small
-        levels in one launch (the same bits either way); block 1, ordering "natural"."""
+        levels in one launch (the same bits either way); block 1, ordering "natural".  setup "host" (the default) makes
+        the hierarchy on the host, "device" on the device (spmv_hip_csr_precond_build_amg_device): the same
+        preconditioner byte for byte; block_products (device setup only) goes to its sparse products as in matmul: 0,
+        -1 or a power of two in [64, 4096]."""
         if kind not in PRECOND_KINDS:
             raise ValueError(f"kind must be one of {sorted(PRECOND_KINDS)}, got {kind!r}")
         if isinstance(block, bool) or int(block) != block or not 1 <= int(block) <= 32:
@@ -543,8 +552,9 @@ class CsrDevice(_Handle):
             return Preconditioner(self, PRECOND_FSAI, 1, cap=int(cap))
         if kind == "amg":
             _check_amg_args(theta, coarse_rows, max_levels)
+            _check_amg_setup(setup, block_products)
             return Preconditioner(self, PRECOND_AMG, 1, amg=(float(theta), int(coarse_rows), int(max_levels),
-                                                             int(bool(chain))))
+                                                             int(bool(chain)), AMG_SETUPS[setup], int(block_products)))
         return Preconditioner(self, PRECOND_KINDS[kind], int(block))
 
     def triangular(self, lower=True, unit_diagonal=False, ordering="natural") -> "TriangularSolver":
@@ -928,6 +938,18 @@ def _check_amg_args(theta, coarse_rows, max_levels):
         raise ValueError(f"max_levels must be an integer in [1, {AMG_MAX_LEVELS}], got {max_levels!r}")
 
 
+def _check_amg_setup(setup, block_products):
+    if not isinstance(setup, str) or setup not in AMG_SETUPS:
+        raise ValueError(f"setup must be one of {sorted(AMG_SETUPS)}, got {setup!r}")
+    bp = block_products
+    if isinstance(bp, bool) or int(bp) != bp or not (bp in (0, -1) or (64 <= bp <= SPGEMM_MAX_BLOCK_PRODUCTS
+                                                                         and int(bp) & (int(bp) - 1) == 0)):
+        raise ValueError(f"block_products must be 0 (auto), -1 (global tier only) or a power of two in "
+                         f"[64, {SPGEMM_MAX_BLOCK_PRODUCTS}], got {bp!r}")
+    if setup == "host" and int(bp) != 0:
+        raise ValueError(f"block_products belongs to setup='device'; the host setup forms no device products, got {bp!r}")
+
+
 def _amg_levels(read, levels, dtype, with_t):
     """The levels of an AMG hierarchy through a reader read(level, which, row_ptr, col, val, scalars) (the plan's on
     the host, a Preconditioner's on the device)."""
@@ -994,9 +1016,14 @@ class Preconditioner(_Handle):
                  cap: int = 32, amg=None):
         super().__init__()
         if kind == PRECOND_AMG:
-            theta, coarse_rows, max_levels, chain = amg
-            _check(nat.lib().spmv_hip_csr_precond_build_amg(dev.h, theta, coarse_rows, max_levels, chain,
-                                                            C.byref(self.h)), "spmv_hip_csr_precond_build_amg")
+            theta, coarse_rows, max_levels, chain, on_device, block_products = amg
+            if on_device:
+                _check(nat.lib().spmv_hip_csr_precond_build_amg_device(dev.h, theta, coarse_rows, max_levels, chain,
+                                                                       block_products, C.byref(self.h)),
+                       "spmv_hip_csr_precond_build_amg_device")
+            else:
+                _check(nat.lib().spmv_hip_csr_precond_build_amg(dev.h, theta, coarse_rows, max_levels, chain,
+                                                                C.byref(self.h)), "spmv_hip_csr_precond_build_amg")
         elif kind == PRECOND_FSAI:
             _check(nat.lib().spmv_hip_csr_precond_build_fsai(dev.h, int(cap), C.byref(self.h)),
                    "spmv_hip_csr_precond_build_fsai")
@@ -1067,6 +1094,14 @@ class Preconditioner(_Handle):
         info["rows"] = [int(v) for v in out[base:base + n]]
         info["entries"] = [int(v) for v in out[base + AMG_MAX_LEVELS:base + AMG_MAX_LEVELS + n]]
         return info
+
+    def amg_setup_info(self) -> dict:
+        """AMG: "setup" (0: the host setup, 1: the device setup) and the microseconds of the device setup's phases over
+        all levels: row statistics, strength graph, aggregation (host), A T with the smoothing, transpose, A P,
+        R (A P), coarsest inverse (host), rounding to the dtype; zeros for a host-built preconditioner."""
+        out = (C.c_int * PRECOND_AMG_SETUP_INFO_WORDS)()
+        _check(nat.lib().spmv_hip_precond_amg_setup_info(self.h, out), "spmv_hip_precond_amg_setup_info")
+        return dict(zip(PRECOND_AMG_SETUP_INFO, (int(v) for v in out)))
 
     def levels(self) -> list:
         """AMG: what the device holds, level by level: {"w", "rho", "kind" (AMG_*), "rows", "aggregates", "A", and "P",

@@ -15,8 +15,13 @@ and AMG; on the million-row matrix lobpcg at k = 8 to 1e-8 within 400 steps with
 --max-entries: a matrix with more entries than this (millions) gets no AMG (the host setup forms R A P on one thread);
 its table then holds the other kinds alone.
 
+--setup: the AMG build alone, setup="host" against setup="device" on the same handle in the same process: three builds
+of each (alternating), the build wall time and the Preconditioner.amg_info() split as the median with the smallest and
+largest, the device setup's phases (Preconditioner.amg_setup_info()), and whether the two hold the same bytes (every
+level's operators and scalars, and one apply); exit status 1 if they do not.
+
 usage: time_amg.py [--matrices million,convdiff,fembig] [--steps 200] [--reps 20] [--window 30] [--limit 420]
-       [--max-entries 200] [--out FILE]"""
+       [--max-entries 200] [--setup] [--out FILE]"""
 import argparse
 import os
 import subprocess
@@ -143,6 +148,70 @@ def one(key, S, R, window_ms, max_entries, out_path):
             emit()
 
 
+def one_setup(key, out_path):
+    import sparsematrixvectormultiplication_amd as sp
+    from time_bicgstab import settle
+    from time_trsv import MATRICES
+
+    sp.hip_init(0)
+    name, cus, _ = sp.device_name()
+
+    def emit(line=""):
+        print(line, flush=True)
+        if out_path:
+            with open(out_path, "a") as f:
+                f.write(line + "\n")
+
+    title, make, method = MATRICES[key]
+    M, rp, col, val = make()
+    emit(f"## {key}: {title}, {M / 1e6:.2f} M rows, {int(rp[-1]) / 1e6:.1f} M entries")
+    emit()
+    emit(f"device: {name.strip()} ({cus} CUs)")
+    emit()
+    spread = lambda v: f"{sorted(v)[1]:.1f} ({min(v):.1f} .. {max(v):.1f})"  # noqa: E731
+    phases = [k for k in sp.device.PRECOND_AMG_SETUP_INFO if k != "setup"]
+    with sp.CsrDevice(M, M, rp, col, val) as dev:
+        settle(dev)
+        runs = {"host": [], "device": []}
+        shape = {}
+        for _ in range(3):
+            for setup in ("host", "device"):
+                t0 = time.perf_counter()
+                with dev.preconditioner("amg", setup=setup) as P:
+                    wall = (time.perf_counter() - t0) * 1e3
+                    f, g = P.amg_info(), P.amg_setup_info()
+                    assert g["setup"] == sp.device.AMG_SETUPS[setup]
+                    runs[setup].append((wall, f, g))
+                    shape[setup] = (f["rows"], f["entries"], f["launches"], f["first_chained"], f["coarsest"])
+        same = shape["host"] == shape["device"]
+        with dev.preconditioner("amg", setup="host") as Ph, dev.preconditioner("amg", setup="device") as Pd:
+            b = np.random.default_rng(7).uniform(-1, 1, M)
+            same = same and Ph.apply(b).tobytes() == Pd.apply(b).tobytes()
+            for lh, ld in zip(Ph.levels(), Pd.levels()):        # every operator and scalar of every level, byte for byte
+                same = same and sorted(lh) == sorted(ld) and all(
+                    np.array(u).tobytes() == np.array(v).tobytes()
+                    for k in lh for u, v in zip(*[x[k] if isinstance(x[k], tuple) else (x[k],) for x in (lh, ld)]))
+        f = runs["host"][0][1]
+        emit(f"levels {f['levels']}, rows per level {' '.join(str(r) for r in f['rows'])}, operator complexity "
+             f"{f['complexity_x1000'] / 1e3:.3f}; the two setups hold the same bytes (every operator, w, rho and kind of "
+             f"every level, and one apply): {'yes' if same else 'NO'}")
+        emit()
+        emit("| setup | build wall ms (min .. max of 3) | download + canonical rows ms | setup ms | uploads ms |")
+        emit("|---|---|---|---|---|")
+        for setup in ("host", "device"):
+            r = runs[setup]
+            emit(f"| {setup} | {spread([w for w, _, _ in r])} | " +
+                 " | ".join(spread([f[k] / 1e3 for _, f, _ in r]) for k in ("download_us", "setup_us", "upload_us")) + " |")
+        emit()
+        emit("| device setup phase | ms (min .. max of 3) |")
+        emit("|---|---|")
+        for k in phases:
+            emit(f"| {k[:-3]} | {spread([g[k] / 1e3 for _, _, g in runs['device']])} |")
+        emit(f"| all phases | {spread([sum(g[k] for k in phases) / 1e3 for _, _, g in runs['device']])} |")
+        emit()
+    return 0 if same else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--matrices", default="million,convdiff,fembig")
@@ -151,14 +220,20 @@ def main():
     ap.add_argument("--window", type=float, default=30.0, help="milliseconds one timed run of applies lasts at least")
     ap.add_argument("--limit", type=int, default=420, help="seconds one matrix may take")
     ap.add_argument("--max-entries", type=float, default=200.0, help="millions of entries up to which AMG is built")
+    ap.add_argument("--setup", action="store_true", help="time the AMG build alone: host setup against device setup")
     ap.add_argument("--out", default=None)
     ap.add_argument("--one", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.one:
+        if args.setup:
+            return one_setup(args.one, args.out)
         one(args.one, args.steps, args.reps, args.window, args.max_entries, args.out)
         return 0
-    head = (f"fp64; applies: host time over windows of at least {args.window:g} ms of asynchronous calls; solver steps: "
-            f"device time of up to {args.steps} steps with tol = 0; every figure the median of three repeats in one process")
+    if args.setup:
+        head = "fp64; three builds of each setup in one process, alternating; the median with the smallest and largest"
+    else:
+        head = (f"fp64; applies: host time over windows of at least {args.window:g} ms of asynchronous calls; solver steps: "
+                f"device time of up to {args.steps} steps with tol = 0; every figure the median of three repeats in one process")
     print(head, flush=True)
     if args.out:
         with open(args.out, "a") as f:
@@ -166,6 +241,7 @@ def main():
     for key in args.matrices.split(","):
         cmd = [sys.executable, os.path.abspath(__file__), "--one", key, "--steps", str(args.steps), "--reps",
                str(args.reps), "--window", str(args.window), "--max-entries", str(args.max_entries)]
+        cmd += ["--setup"] if args.setup else []
         cmd += ["--out", args.out] if args.out else []
         try:                     # the child writes its lines itself, as they come
             rc = subprocess.run(cmd, timeout=args.limit).returncode
