@@ -67,7 +67,6 @@ inline int first_missing_diag(const Canon &B) {
 
 inline int handle_ok(const spmv_csr_dev *m, const char *what) {
     if (m->M_total != m->N) return fail("%s: needs a square matrix (%d x %d)", what, m->M_total, m->N);
-    if (m->tiles_only || !m->row_ptr || (m->nz > 0 && (!m->col || !m->val)))
-        return fail("%s: the handle does not hold its CSR arrays", what);
+    if (!csr_holds_arrays(m)) return fail("%s: the handle does not hold its CSR arrays", what);
     return 0;
 }

@@ -23,6 +23,7 @@
 // strength graph (twice: the sort's output) and the product core's workspace; each is freed as soon as the next step has
 // what it needs.  amg_finish (spmv_amg.hip) then makes the cycle, the tail and the workspace as for a host-built P.
 #include "amg_levels.hpp"
+#include "algebra_ops.hpp"
 
 #include <climits>
 #include <memory>
@@ -35,21 +36,11 @@
 
 namespace {
 
-struct CsrGuard {  // a level's fp64 arrays, freed on every way out
-    DevCsr m;
-    ~CsrGuard() { m.release(); }
-    void reset() { m.release(), m = DevCsr(); }
-};
-
 int grid_for(long long items, int per_block = kBlock) {
     return (int)std::max<long long>(1, std::min<long long>(kAsMaxGrid, (items + per_block - 1) / per_block));
 }
 
-unsigned bits_for(unsigned long long n) {  // bits that hold 0 .. n - 1 (at least one)
-    unsigned bits = 1;
-    while (bits < 63 && (1ull << bits) < n) ++bits;
-    return bits;
-}
+using algebra::bits_for;
 
 template <typename V>
 int upload_async(V *dst, const V *src, size_t count) {
@@ -63,13 +54,12 @@ int download(V *dst, const V *src, size_t count) {  // waits for the stream: wha
     return 0;
 }
 
-// bare fp64 device arrays of host CSR arrays
+// bare fp64 device arrays of host CSR arrays (a level's own: no pad behind the entries)
 int csr_to_device(int rows, int cols, const int *rp, const int *col, const double *val, DevCsr &out) {
     const size_t nz = (size_t)rp[rows];
-    out.rows = rows, out.cols = cols, out.nz = (long long)nz;
-    HIP_TRY(hipMalloc((void **)&out.rp, ((size_t)rows + 1) * sizeof(int)));
-    HIP_TRY(hipMalloc((void **)&out.col, std::max<size_t>(nz, 4) * sizeof(int)));
-    HIP_TRY(hipMalloc(&out.val, std::max<size_t>(nz, 4) * sizeof(double)));
+    out = DevCsr(rows, cols);
+    HIP_TRY(out.alloc_rp());
+    HIP_TRY(out.alloc_entries<double>((long long)nz, 0, g_stream));
     if (upload_async(out.rp, rp, (size_t)rows + 1) || upload_async(out.col, col, nz) ||
         upload_async((double *)out.val, val, nz))
         return -1;
@@ -78,7 +68,7 @@ int csr_to_device(int rows, int cols, const int *rp, const int *col, const doubl
 }
 
 // the strength graph of A on the host: s_rp[n + 1], s_col; 1: more edges than an int counts
-int strength_graph(const DevCsr &A, const double *d, double theta, std::vector<int> &s_rp, std::vector<int> &s_col) {
+int strength_graph(const CsrView &A, const double *d, double theta, std::vector<int> &s_rp, std::vector<int> &s_col) {
     const int n = A.rows;
     const unsigned col_bits = bits_for((unsigned long long)n);
     DevBuf d_cnt, d_off, d_tmp;
@@ -195,13 +185,13 @@ int amg_build_device(const spmv_csr_dev *m, double theta, int coarse_rows, int m
     HIP_TRY(d_flags.alloc(kFlags * sizeof(int)));
     HIP_TRY(d_res.alloc(kAsStatWords * sizeof(unsigned long long)));
 
-    CsrGuard cur;
-    if (n && csr_to_device(n, n, A.rp.data(), A.col.data(), A.val.data(), cur.m)) return -1;
+    DevCsr cur;  // A_l in fp64; like every level's arrays below, freed on every way out
+    if (n && csr_to_device(n, n, A.rp.data(), A.col.data(), A.val.data(), cur)) return -1;
     for (int l = 0; n && l < kAmgMaxLevels; ++l) {
-        const int nl = cur.m.rows;
+        const int nl = cur.rows;
         ap->levels = l + 1;
         ap->n[l] = nl;
-        ap->a_nz[l] = cur.m.nz;
+        ap->a_nz[l] = cur.nz;
         t_lap = now_ms();
 
         // ---- row statistics
@@ -210,8 +200,8 @@ int amg_build_device(const spmv_csr_dev *m, double theta, int coarse_rows, int m
         const unsigned long long res0[kAsStatWords] = {~0ull, 0, 0};
         unsigned long long res[kAsStatWords];
         if (upload_async(d_res.as<unsigned long long>(), res0, kAsStatWords)) return -1;
-        hipLaunchKernelGGL(as_row_stats, dim3(grid_for(nl)), dim3(kBlock), 0, g_stream, nl, cur.m.rp, cur.m.col,
-                           (const double *)cur.m.val, d_d.as<double>(), d_res.as<unsigned long long>());
+        hipLaunchKernelGGL(as_row_stats, dim3(grid_for(nl)), dim3(kBlock), 0, g_stream, nl, cur.rp, cur.col,
+                           (const double *)cur.val, d_d.as<double>(), d_res.as<unsigned long long>());
         HIP_TRY(hipGetLastError());
         if (download(res, d_res.as<unsigned long long>(), kAsStatWords) || lap(kAmgPhStats)) return -1;
         if (res[kAsBadRow] != ~0ull) {
@@ -232,7 +222,7 @@ int amg_build_device(const spmv_csr_dev *m, double theta, int coarse_rows, int m
         int na = 0;
         if (kind == SPMV_AMG_SMOOTH && l + 1 < max_levels) {
             std::vector<int> s_rp, s_col;
-            const int over = strength_graph(cur.m, d_d.as<double>(), theta, s_rp, s_col);
+            const int over = strength_graph(cur.view(), d_d.as<double>(), theta, s_rp, s_col);
             if (over > 0) return plan_refusal("%s", AMG_REFUSE_MEMORY);
             if (over || lap(kAmgPhStrength)) return -1;
             agg.assign((size_t)nl + 1, -1);
@@ -252,7 +242,7 @@ int amg_build_device(const spmv_csr_dev *m, double theta, int coarse_rows, int m
         HIP_TRY(hipMalloc((void **)&ap->g[l], std::max<size_t>((size_t)nl, 4) * sizeof(double)));
         hipLaunchKernelGGL((as_g<T>), dim3(grid_for(nl)), dim3(kBlock), 0, g_stream, nl, d_d.as<double>(), w, ap->g[l],
                            d_flags.as<int>() + kFlagG);
-        if (!(l == 0 && kind != SPMV_AMG_DIRECT) && round_op<T>(cur.m, false, ap->A[l], d_flags.as<int>() + kFlagA)) return -1;
+        if (!(l == 0 && kind != SPMV_AMG_DIRECT) && round_op<T>(cur, false, ap->A[l], d_flags.as<int>() + kFlagA)) return -1;
         if (lap(kAmgPhRound)) return -1;
 
         if (kind == SPMV_AMG_DIRECT) {
@@ -261,11 +251,11 @@ int amg_build_device(const spmv_csr_dev *m, double theta, int coarse_rows, int m
             if (flags[kFlagA]) defer(kAmgMsgEntry, l, "A");
             HostOp h;
             h.rp.assign((size_t)nl + 1, 0);
-            if (download(h.rp.data(), cur.m.rp, (size_t)nl + 1)) return -1;
+            if (download(h.rp.data(), cur.rp, (size_t)nl + 1)) return -1;
             const size_t nz = (size_t)h.rp[(size_t)nl];
             h.col.assign(nz + 1, 0), h.val.assign(nz + 1, 0.0);
-            HIP_TRY(hipMemcpyAsync(h.col.data(), cur.m.col, nz * sizeof(int), hipMemcpyDeviceToHost, g_stream));
-            if (download(h.val.data(), (const double *)cur.m.val, nz)) return -1;
+            HIP_TRY(hipMemcpyAsync(h.col.data(), cur.col, nz * sizeof(int), hipMemcpyDeviceToHost, g_stream));
+            if (download(h.val.data(), (const double *)cur.val, nz)) return -1;
             const amg_csr Al = {nl, nl, h.rp.data(), h.col.data(), h.val.data()};
             double *inv_raw = nullptr;
             const int bad = amg_dense_inverse(&Al, &inv_raw);
@@ -291,7 +281,7 @@ int amg_build_device(const spmv_csr_dev *m, double theta, int coarse_rows, int m
         }
 
         // ---- T from agg (host), P = T - diag(w / d) A T
-        CsrGuard Tm, Pm, Rm, APm, next;
+        DevCsr Tm, Pm, Rm, APm, next;
         std::vector<int> rp_host;
         DevBuf d_agg;
         {
@@ -305,34 +295,32 @@ int amg_build_device(const spmv_csr_dev *m, double theta, int coarse_rows, int m
             t_col.push_back(0);
             HIP_TRY(d_agg.alloc((size_t)nl * sizeof(int)));
             if (upload_async(d_agg.as<int>(), agg.data(), (size_t)nl) ||
-                csr_to_device(nl, na, t_rp.data(), t_col.data(), ones.data(), Tm.m))
+                csr_to_device(nl, na, t_rp.data(), t_col.data(), ones.data(), Tm))
                 return -1;
         }
-        if (spgemm_core(8, cur.m, Tm.m, block_products, 0, &Pm.m, rp_host, nullptr, nullptr)) return -1;
-        Tm.reset();
-        hipLaunchKernelGGL(as_smooth, dim3(grid_for(nl, kBlock / kAsSmoothLanes)), dim3(kBlock), 0, g_stream, nl, Pm.m.rp,
-                           Pm.m.col, (double *)Pm.m.val, d_agg.as<int>(), d_d.as<double>(), w);
+        if (spgemm_core(8, cur.view(), Tm.view(), block_products, 0, Pm, rp_host, nullptr, nullptr)) return -1;
+        Tm = DevCsr();
+        hipLaunchKernelGGL(as_smooth, dim3(grid_for(nl, kBlock / kAsSmoothLanes)), dim3(kBlock), 0, g_stream, nl, Pm.rp,
+                           Pm.col, (double *)Pm.val, d_agg.as<int>(), d_d.as<double>(), w);
         HIP_TRY(hipGetLastError());
         if (lap(kAmgPhTentative)) return -1;
         // ---- R = P^T, A_{l+1} = R (A P)
-        if (transpose_core(8, Pm.m, &Rm.m, rp_host) || lap(kAmgPhTranspose)) return -1;
-        if (spgemm_core(8, cur.m, Pm.m, block_products, 0, &APm.m, rp_host, nullptr, nullptr) || lap(kAmgPhAP)) return -1;
-        if (spgemm_core(8, Rm.m, APm.m, block_products, 0, &next.m, rp_host, nullptr, nullptr) || lap(kAmgPhRAP)) return -1;
-        APm.reset();
+        if (transpose_core(8, Pm.view(), Rm, rp_host) || lap(kAmgPhTranspose)) return -1;
+        if (spgemm_core(8, cur.view(), Pm.view(), block_products, 0, APm, rp_host, nullptr, nullptr) || lap(kAmgPhAP)) return -1;
+        if (spgemm_core(8, Rm.view(), APm.view(), block_products, 0, next, rp_host, nullptr, nullptr) || lap(kAmgPhRAP)) return -1;
+        APm = DevCsr();
         // ---- P_l and R_l in the handle's dtype
-        if (round_op<T>(Pm.m, true, ap->P[l], d_flags.as<int>() + kFlagP) ||
-            round_op<T>(Rm.m, true, ap->R[l], d_flags.as<int>() + kFlagR) || download(flags, d_flags.as<int>(), kFlags))
+        if (round_op<T>(Pm, true, ap->P[l], d_flags.as<int>() + kFlagP) ||
+            round_op<T>(Rm, true, ap->R[l], d_flags.as<int>() + kFlagR) || download(flags, d_flags.as<int>(), kFlags))
             return -1;
         if (flags[kFlagG] != INT_MAX) defer(kAmgMsgDiagonal, l, flags[kFlagG]);
         if (flags[kFlagA]) defer(kAmgMsgEntry, l, "A");
         if (flags[kFlagP]) defer(kAmgMsgEntry, l, "P");
         if (flags[kFlagR]) defer(kAmgMsgEntry, l, "R");
         if (lap(kAmgPhRound)) return -1;
-        cur.m.release();
-        cur.m = next.m;
-        next.m = DevCsr();
+        cur = std::move(next);
     }
-    cur.reset();
+    cur = DevCsr();
     if (!deferred.empty()) return fail("%s", deferred.c_str());
     const double t2 = now_ms();
     // level 0 is the ordinary upload of the canonical block, as in the host setup

@@ -1,8 +1,9 @@
 // spmv_coo.hip -- COO -> CSR on the device: the reference's convert_in_csr
 // (src/csr_matrix.c:63-126: histogram, scan, scatter in file order, per-row quicksort on the host)
 // as upload of the triplets + one stable radix sort by (row, column) + two small kernels.  The sort
-// is rocPRIM's (a ROCm library routine; nothing on the SpMV path goes through it).
-#include "spmv_internal.hpp"
+// is rocPRIM's (a ROCm library routine; nothing on the SpMV path goes through it).  The build's arrays are DevBuf and an
+// owning DevCsr, the adopt and the sort width are the handle producers' (algebra_ops.hpp).
+#include "algebra_ops.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -46,69 +47,48 @@ static int spmv_hip_csr_from_coo_body(int M, int N, long long nz, const int *I, 
     if (need_device()) return -1;
     if (!out) return fail("csr_from_coo: out is NULL");
     *out = nullptr;
-    if (M < 0 || N < 0 || nz < 0 || nz > 0x7fffffffLL - kPad || (nz > 0 && (!I || !J || !val)))
+    if (M < 0 || N < 0 || nz < 0 || nz > kMaxEntries || (nz > 0 && (!I || !J || !val)))
         return fail("csr_from_coo: bad arguments");
-    int *d_I = nullptr, *d_J = nullptr, *d_col = nullptr, *d_rp = nullptr;
-    double *d_vin = nullptr, *d_val = nullptr;
-    unsigned long long *d_kin = nullptr, *d_kout = nullptr, *d_bad = nullptr;
-    void *d_tmp = nullptr;
+    const size_t n = (size_t)nz;
+    ClearHipError clear;
+    DevBuf d_I, d_J, d_vin, d_kin, d_kout, d_bad, d_tmp;
+    DevCsr C(M, N);
     std::vector<int> rp((size_t)M + 1, 0);
-    int rc = -1;
-    do {
-        const size_t n = (size_t)nz, n1 = std::max<size_t>(n, 1);
-        hipError_t e = hipMalloc((void **)&d_I, n1 * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void **)&d_J, n1 * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void **)&d_vin, n1 * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void **)&d_kin, n1 * sizeof(unsigned long long));
-        if (e == hipSuccess) e = hipMalloc((void **)&d_kout, n1 * sizeof(unsigned long long));
-        if (e == hipSuccess) e = hipMalloc((void **)&d_val, (n + kPad) * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void **)&d_col, (n + kPad) * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void **)&d_rp, ((size_t)M + 1) * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void **)&d_bad, sizeof(unsigned long long));
-        if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0xFF, sizeof(unsigned long long), g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_val + n, 0, kPad * sizeof(double), g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_col + n, 0, kPad * sizeof(int), g_stream);
-        if (e == hipSuccess && n) e = hipMemcpyAsync(d_I, I, n * sizeof(int), hipMemcpyHostToDevice, g_stream);
-        if (e == hipSuccess && n) e = hipMemcpyAsync(d_J, J, n * sizeof(int), hipMemcpyHostToDevice, g_stream);
-        if (e == hipSuccess && n) e = hipMemcpyAsync(d_vin, val, n * sizeof(double), hipMemcpyHostToDevice, g_stream);
-        if (e != hipSuccess) { fail("csr_from_coo: allocation / upload failed: %s", hipGetErrorString(e)); break; }
-        const int grid = (int)((nz + kBlock) / kBlock);  // covers e == nz as well
-        if (n) {
-            hipLaunchKernelGGL(coo_make_keys, dim3(grid), dim3(kBlock), 0, g_stream, nz, M, N, d_I, d_J, d_kin, d_bad);
-            // only the bits that can differ: 32 of the column + those of the row
-            unsigned row_bits = 1;
-            while (row_bits < 32 && (1ull << row_bits) < (unsigned long long)std::max(M, 1)) ++row_bits;
-            size_t tmp_bytes = 0;
-            e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_kin, d_kout, d_vin, d_val, n, 0u, 32u + row_bits, g_stream);
-            if (e == hipSuccess) e = hipMalloc(&d_tmp, std::max<size_t>(tmp_bytes, 16));
-            if (e == hipSuccess)
-                e = rocprim::radix_sort_pairs(d_tmp, tmp_bytes, d_kin, d_kout, d_vin, d_val, n, 0u, 32u + row_bits, g_stream);
-            if (e != hipSuccess) { fail("csr_from_coo: sort failed: %s", hipGetErrorString(e)); break; }
-        }
-        hipLaunchKernelGGL(coo_split_keys, dim3(grid), dim3(kBlock), 0, g_stream, nz, M, d_kout, d_col, d_rp);
-        unsigned long long bad = 0;
-        e = hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, g_stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(rp.data(), d_rp, rp.size() * sizeof(int), hipMemcpyDeviceToHost, g_stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-        if (e != hipSuccess) { fail("csr_from_coo: build failed: %s", hipGetErrorString(e)); break; }
-        if (bad != ~0ull) {
-            fail("csr_from_coo: entry %llu (%d, %d) is outside the %d x %d matrix", bad, I[bad], J[bad], M, N);
-            break;
-        }
-        rc = csr_adopt_f64(M, N, rp.data(), d_col, d_val, out);
-        if (rc == 0) d_col = nullptr, d_val = nullptr;  // the handle owns them now
-    } while (0);
-    (void)hipFree(d_I);
-    (void)hipFree(d_J);
-    (void)hipFree(d_vin);
-    (void)hipFree(d_kin);
-    (void)hipFree(d_kout);
-    (void)hipFree(d_rp);
-    (void)hipFree(d_bad);
-    (void)hipFree(d_tmp);
-    (void)hipFree(d_col);
-    (void)hipFree(d_val);
-    return rc;
+    hipError_t e = d_I.alloc(n * sizeof(int));
+    if (e == hipSuccess) e = d_J.alloc(n * sizeof(int));
+    if (e == hipSuccess) e = d_vin.alloc(n * sizeof(double));
+    if (e == hipSuccess) e = d_kin.alloc(n * sizeof(unsigned long long));
+    if (e == hipSuccess) e = d_kout.alloc(n * sizeof(unsigned long long));
+    if (e == hipSuccess) e = C.alloc_entries<double>(nz, kPad, g_stream);
+    if (e == hipSuccess) e = C.alloc_rp();
+    if (e == hipSuccess) e = d_bad.alloc(sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemsetAsync(d_bad.p, 0xFF, sizeof(unsigned long long), g_stream);
+    if (e == hipSuccess && n) e = hipMemcpyAsync(d_I.p, I, n * sizeof(int), hipMemcpyHostToDevice, g_stream);
+    if (e == hipSuccess && n) e = hipMemcpyAsync(d_J.p, J, n * sizeof(int), hipMemcpyHostToDevice, g_stream);
+    if (e == hipSuccess && n) e = hipMemcpyAsync(d_vin.p, val, n * sizeof(double), hipMemcpyHostToDevice, g_stream);
+    if (e != hipSuccess) return fail("csr_from_coo: allocation / upload failed: %s", hipGetErrorString(e));
+    unsigned long long *kin = d_kin.as<unsigned long long>(), *kout = d_kout.as<unsigned long long>();
+    const int grid = (int)((nz + kBlock) / kBlock);  // covers e == nz as well
+    if (n) {
+        hipLaunchKernelGGL(coo_make_keys, dim3(grid), dim3(kBlock), 0, g_stream, nz, M, N, d_I.as<int>(), d_J.as<int>(), kin,
+                           d_bad.as<unsigned long long>());
+        // only the bits that can differ: 32 of the column + those of the row
+        const unsigned row_bits = std::min(32u, algebra::bits_for((unsigned long long)std::max(M, 1)));
+        double *vin = d_vin.as<double>(), *vout = static_cast<double *>(C.val);
+        size_t tmp_bytes = 0;
+        e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, kin, kout, vin, vout, n, 0u, 32u + row_bits, g_stream);
+        if (e == hipSuccess) e = d_tmp.alloc(tmp_bytes);
+        if (e == hipSuccess) e = rocprim::radix_sort_pairs(d_tmp.p, tmp_bytes, kin, kout, vin, vout, n, 0u, 32u + row_bits, g_stream);
+        if (e != hipSuccess) return fail("csr_from_coo: sort failed: %s", hipGetErrorString(e));
+    }
+    hipLaunchKernelGGL(coo_split_keys, dim3(grid), dim3(kBlock), 0, g_stream, nz, M, kout, C.col, C.rp);
+    unsigned long long bad = 0;
+    e = hipMemcpyAsync(&bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost, g_stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(rp.data(), C.rp, rp.size() * sizeof(int), hipMemcpyDeviceToHost, g_stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
+    if (e != hipSuccess) return fail("csr_from_coo: build failed: %s", hipGetErrorString(e));
+    if (bad != ~0ull) return fail("csr_from_coo: entry %llu (%d, %d) is outside the %d x %d matrix", bad, I[bad], J[bad], M, N);
+    return algebra::adopt<double>(std::move(C), rp, out);
 }
 
 extern "C" int spmv_hip_csr_from_coo(int M, int N, long long nz, const int *I, const int *J, const double *val,

@@ -13,11 +13,13 @@
 #include <ctime>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "csr_kernels.hpp"
 #include "hll_kernels.hpp"
 #include "tile_kernels.hpp"
+#include "row_counts.hpp"
 #include "spmv_hip.h"
 
 using namespace spmv;
@@ -106,8 +108,7 @@ int guarded(const char *what, F body) {
 }
 
 constexpr int kRowPtrPad = 384;  // entries behind row_ptr (kernels that stage whole row_ptr segments)
-constexpr int kPad = 8192 + 64;  // zero entries behind col/val: the stream / LDS kernels stage
-                                   // whole units without bounds tests (>= kStreamCapMax, kHllCap)
+// (kPad, the zero entries behind col/val: row_counts.hpp)
 
 template <typename T>
 int upload_array(T **dptr, const T *host, size_t count, size_t pad) {
@@ -413,28 +414,59 @@ struct DevBuf {
     hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 16)); }
     template <typename U> U *as() const { return static_cast<U *>(p); }
 };
-// Bare CSR arrays on the device: what the product and the transpose cores take and hand back, and what the AMG device
-// setup (spmv_amg_setup.hip) keeps of a level.  Not a handle: no plans, no vectors.  release() frees what it points at,
-// so a DevCsr that only LOOKS at a handle's arrays (csr_view) is never released.
+// Bare CSR arrays on the device, not a handle (no plans, no vectors), in two roles.  CsrView looks at arrays that belong
+// to someone else -- a handle (csr_view) or a DevCsr (view()): what the product, sum and transpose cores take.  DevCsr
+// owns its arrays and frees them when it goes: what the cores hand back, and what the AMG device setup
+// (spmv_amg_setup.hip) keeps of a level.
+struct CsrView {
+    int rows = 0, cols = 0;
+    long long nz = 0;
+    const int *rp = nullptr, *col = nullptr;  // [rows + 1], [nz]
+    const void *val = nullptr;
+};
+inline CsrView csr_view(const spmv_csr_dev *m) { return {m->M_total, m->N, m->nz, m->row_ptr, m->col, m->val}; }
+// does the handle hold the arrays csr_view shows?  (a handle made of tile plans alone does not)
+inline bool csr_holds_arrays(const spmv_csr_dev *m) {
+    return !m->tiles_only && m->row_ptr && (m->nz == 0 || (m->col && m->val));
+}
 struct DevCsr {
     int rows = 0, cols = 0;
     long long nz = 0;
-    int *rp = nullptr, *col = nullptr;  // [rows + 1], [nz (+ kPad zeroed entries where a core made them)]
+    int *rp = nullptr, *col = nullptr;  // [rows + 1], [nz + the pad they were allocated with]
     void *val = nullptr;
-    void release() {
-        (void)hipFree(rp), (void)hipFree(col), (void)hipFree(val);
-        rp = col = nullptr, val = nullptr;
+    DevCsr() = default;
+    DevCsr(int rows_, int cols_) : rows(rows_), cols(cols_) {}
+    DevCsr(DevCsr &&o) noexcept { *this = std::move(o); }
+    DevCsr &operator=(DevCsr &&o) noexcept {  // (a swap: what this held goes with o)
+        std::swap(rows, o.rows), std::swap(cols, o.cols), std::swap(nz, o.nz);
+        std::swap(rp, o.rp), std::swap(col, o.col), std::swap(val, o.val);
+        return *this;
     }
+    ~DevCsr() { (void)hipFree(rp), (void)hipFree(col), (void)hipFree(val); }
+    CsrView view() const { return {rows, cols, nz, rp, col, val}; }
+    hipError_t alloc_rp() { return hipMalloc((void **)&rp, std::max<size_t>(((size_t)rows + 1) * sizeof(int), 16)); }
+    // col and val for n entries of type T at their exact size, with `pad` zeroed entries behind (kPad: ready for csr_adopt)
+    template <typename T>
+    hipError_t alloc_entries(long long n_entries, size_t pad, hipStream_t s) {
+        const size_t n = (size_t)n_entries;
+        nz = n_entries;
+        hipError_t e = hipMalloc((void **)&col, std::max<size_t>((n + pad) * sizeof(int), 16));
+        if (e == hipSuccess) e = hipMalloc(&val, std::max<size_t>((n + pad) * sizeof(T), 16));
+        if (e == hipSuccess && pad) e = hipMemsetAsync(col + n, 0, pad * sizeof(int), s);
+        if (e == hipSuccess && pad) e = hipMemsetAsync(static_cast<T *>(val) + n, 0, pad * sizeof(T), s);
+        return e;
+    }
+    void entries_adopted() { col = nullptr, val = nullptr; }  // a handle owns them now (csr_adopt succeeded)
 };
-inline DevCsr csr_view(const spmv_csr_dev *m) {
-    DevCsr v;
-    v.rows = m->M_total, v.cols = m->N, v.nz = m->nz, v.rp = m->row_ptr, v.col = m->col, v.val = m->val;
-    return v;
-}
+// A build's way out: a failed allocation in it is reported by rc, not by the next launch.  Declared ahead of what the
+// build allocates, so that it runs behind their frees.
+struct ClearHipError {
+    ~ClearHipError() { (void)hipGetLastError(); }
+};
 // spmv_spgemm.hip: C = A B on bare arrays (values of value_bytes bytes; the definition of spmv_hip_csr_spgemm).  On
-// success C owns its three arrays (col / val with kPad zeroed entries behind, ready for csr_adopt), rp_host is C's
-// row_ptr, stats[8] the stats of spmv_hip_csr_spgemm and ms[0..2] count / symbolic / numeric; on -1 C is empty.
-int spgemm_core(int value_bytes, const DevCsr &A, const DevCsr &B, int block_products, long long chunk_products, DevCsr *C,
+// success C holds the product (col / val with kPad zeroed entries behind, ready for csr_adopt), rp_host is C's
+// row_ptr, stats[8] the stats of spmv_hip_csr_spgemm and ms[0..2] count / symbolic / numeric; on -1 C is as it was.
+int spgemm_core(int value_bytes, const CsrView &A, const CsrView &B, int block_products, long long chunk_products, DevCsr &C,
                 std::vector<int> &rp_host, long long *stats, double *ms);
 int spgemm_max_block_products();  // the cap of the on-chip tier (spgemm_kernels.hpp: kSgMaxProducts)
 // block_products as spmv_hip_csr_spgemm takes it: 0 (auto), -1 (no on-chip tier) or a power of two in [64, cap]
@@ -442,7 +474,7 @@ inline bool spgemm_block_products_ok(int bp) {
     return bp == 0 || bp == -1 || (bp >= 64 && bp <= spgemm_max_block_products() && (bp & (bp - 1)) == 0);
 }
 // spmv_transpose.hip: At = A^T on bare arrays, the same way
-int transpose_core(int value_bytes, const DevCsr &A, DevCsr *At, std::vector<int> &rp_host);
+int transpose_core(int value_bytes, const CsrView &A, DevCsr &At, std::vector<int> &rp_host);
 // spmv_csr.hip: tile plans alone for rows given as (first entry, length) over host arrays (an HLL slab's rows);
 // *out = NULL when the rows get no plan
 // (col / val: host copies of the rows' arrays, or NULL when d_col / d_val -- the same arrays on the device -- are given

@@ -10,11 +10,12 @@
 //              radix_sort_pairs on the bits in use and sg_row_compress
 //   adopt      csr_adopt_*: C is an ordinary handle with upload's plans
 //
-// Everything in front of the adopt is spgemm_core, on bare device arrays: the AMG device setup (spmv_amg_setup.hip) forms
-// its products with it and keeps the arrays.
+// Everything in front of the adopt is spgemm_core, on views of bare device arrays (algebra_ops.hpp has the frame): the AMG
+// device setup (spmv_amg_setup.hip) forms its products with it and keeps the arrays, the sum (spmv_spadd.hip) makes an
+// operand canonical with it.
 //
 // The workspace is the per-row counts, the block list and one chunk's keys and products (twice: the sort's output).
-#include "spmv_internal.hpp"
+#include "algebra_ops.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -36,11 +37,7 @@ int sg_allow_lds() {
     return 0;
 }
 
-unsigned bits_for(unsigned long long n) {  // bits that hold 0 .. n - 1 (at least one)
-    unsigned bits = 1;
-    while (bits < 63 && (1ull << bits) < n) ++bits;
-    return bits;
-}
+using algebra::bits_for;
 
 struct Chunk {
     int first = 0, rows = 0;  // in the list of long rows
@@ -49,21 +46,18 @@ struct Chunk {
 
 // the product on bare arrays: everything but the adopt
 template <typename T>
-int spgemm_core_t(const DevCsr &A, const DevCsr &B, int block_products, long long chunk_products, DevCsr *C,
+int spgemm_core_t(const CsrView &A, const CsrView &B, int block_products, long long chunk_products, DevCsr &C_out,
                   std::vector<int> &rp, long long *stats, double *ms) {
-    const DevCsr *a = &A, *b = &B;
+    const CsrView *a = &A, *b = &B;
     const int M = a->rows, N = b->cols;
     const int cap = block_products == 0 ? kSgMaxProducts : block_products;  // -1: no on-chip tier
     const long long chunk_cap = chunk_products ? chunk_products : kSgAutoChunk;
     const T *valA = static_cast<const T *>(a->val), *valB = static_cast<const T *>(b->val);
     UploadTrace trace("csr_spgemm");
-    double t0 = UploadTrace::now();
     double split[3] = {0, 0, 0};
-    auto lap = [&](int k) {
-        const double t = UploadTrace::now();
-        split[k] = (t - t0) * 1e3;
-        t0 = t;
-    };
+    algebra::PhaseTimer timer{split};
+    ClearHipError clear;
+    DevCsr C(M, N);
     if (sg_allow_lds<T>()) return -1;
 
     // ---- count
@@ -84,7 +78,7 @@ int spgemm_core_t(const DevCsr &A, const DevCsr &B, int block_products, long lon
     }
     if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
     if (e != hipSuccess) return fail("csr_spgemm: count failed: %s", hipGetErrorString(e));
-    lap(0);
+    timer.lap(0);
     trace.mark("count");
 
     // ---- plan
@@ -120,13 +114,13 @@ int spgemm_core_t(const DevCsr &A, const DevCsr &B, int block_products, long lon
     for (const Chunk &c : chunks) chunk_max = std::max(chunk_max, c.products);
 
     // ---- workspace
-    DevBuf d_desc, d_lrows, d_off, d_kin, d_kout, d_vin, d_vout, d_tmp, d_rpC;  // (d_rpC: handed to C at the end)
+    DevBuf d_desc, d_lrows, d_off, d_kin, d_kout, d_vin, d_vout, d_tmp;
     const unsigned col_bits = bits_for((unsigned long long)N);
     size_t tmp_bytes = 0;
     e = d_desc.alloc(desc.size() * sizeof(int4));
     if (e == hipSuccess) e = d_lrows.alloc((size_t)n_long * sizeof(int));
     if (e == hipSuccess) e = d_off.alloc(off.size() * sizeof(long long));
-    if (e == hipSuccess) e = d_rpC.alloc(((size_t)M + 1) * sizeof(int));
+    if (e == hipSuccess) e = C.alloc_rp();
     if (e == hipSuccess && chunk_max) {
         e = d_kin.alloc((size_t)chunk_max * 8);
         if (e == hipSuccess) e = d_kout.alloc((size_t)chunk_max * 8);
@@ -147,7 +141,7 @@ int spgemm_core_t(const DevCsr &A, const DevCsr &B, int block_products, long lon
     }
     if (e != hipSuccess) return fail("csr_spgemm: upload of the plan failed: %s", hipGetErrorString(e));
 
-    int *d_colC = nullptr;
+    int *d_colC = nullptr;  // (C's, once the symbolic pass has counted them)
     T *d_valC = nullptr;
     const int bgrid = (int)std::min<size_t>(kSgMaxGrid, desc.size());
     auto run_blocks = [&](bool numeric) {
@@ -155,11 +149,11 @@ int spgemm_core_t(const DevCsr &A, const DevCsr &B, int block_products, long lon
         if (numeric)
             hipLaunchKernelGGL((sg_block<T, true>), dim3(bgrid), dim3(kBlock), (size_t)cap * 16, g_stream, (int)desc.size(), cap,
                                d_desc.as<int4>(), a->rp, a->col, valA, b->rp, b->col, valB, d_products.as<long long>(),
-                               d_cnt.as<int>(), d_rpC.as<int>(), d_colC, d_valC);
+                               d_cnt.as<int>(), C.rp, d_colC, d_valC);
         else
             hipLaunchKernelGGL((sg_block<T, false>), dim3(bgrid), dim3(kBlock), (size_t)cap * 12, g_stream, (int)desc.size(), cap,
                                d_desc.as<int4>(), a->rp, a->col, valA, b->rp, b->col, valB, d_products.as<long long>(),
-                               d_cnt.as<int>(), d_rpC.as<int>(), d_colC, d_valC);
+                               d_cnt.as<int>(), C.rp, d_colC, d_valC);
     };
     auto run_chunks = [&](bool numeric) -> hipError_t {
         for (size_t c = 0; c < chunks.size(); ++c) {
@@ -178,7 +172,7 @@ int spgemm_core_t(const DevCsr &A, const DevCsr &B, int block_products, long lon
                                                 (size_t)ch.products, 0u, bits, g_stream);
                 if (err != hipSuccess) return err;
                 hipLaunchKernelGGL((sg_row_compress<T>), dim3(grid), dim3(kBlock), 0, g_stream, ch.rows, rows, o,
-                                   (1ull << col_bits) - 1, kout, d_vout.as<double>(), d_rpC.as<int>(), d_colC, d_valC);
+                                   (1ull << col_bits) - 1, kout, d_vout.as<double>(), C.rp, d_colC, d_valC);
             } else {
                 hipLaunchKernelGGL((sg_expand<T, false>), dim3(grid), dim3(kBlock), 0, g_stream, ch.rows, rows, o, (int)col_bits,
                                    a->rp, a->col, valA, b->rp, b->col, valB, kin, (double *)nullptr);
@@ -193,60 +187,34 @@ int spgemm_core_t(const DevCsr &A, const DevCsr &B, int block_products, long lon
 
     // ---- symbolic
     std::vector<int> cnt((size_t)M, 0);
-    rp.assign((size_t)M + 1, 0);
     run_blocks(false);
     e = run_chunks(false);
     if (e == hipSuccess && M)
         e = hipMemcpyAsync(cnt.data(), d_cnt.p, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, g_stream);
     if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
     if (e != hipSuccess) return fail("csr_spgemm: symbolic pass failed: %s", hipGetErrorString(e));
-    long long nz = 0, widest_nz = 0;
-    for (int i = 0; i < M; ++i) {
-        nz += cnt[i];
-        widest_nz = std::max<long long>(widest_nz, cnt[i]);
-        if (nz > 0x7fffffffLL - kPad)
-            return fail("csr_spgemm: C has more than %lld entries (by row %d of %d): beyond the 32-bit entry index of a handle",
-                        0x7fffffffLL - kPad, i, M);
-        rp[(size_t)i + 1] = (int)nz;
-    }
-    lap(1);
+    RowCounts counts;
+    if (algebra::row_ptr_of_counts("csr_spgemm", cnt, rp, counts)) return -1;
+    const long long nz = counts.nz;
+    timer.lap(1);
     trace.mark("symbolic");
 
     // ---- numeric
-    const size_t n = (size_t)nz;
-    int rc = -1;
-    do {
-        e = hipMalloc((void **)&d_colC, (n + kPad) * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void **)&d_valC, (n + kPad) * sizeof(T));
-        if (e == hipSuccess) e = hipMemsetAsync(d_colC + n, 0, kPad * sizeof(int), g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_valC + n, 0, kPad * sizeof(T), g_stream);
-        if (e != hipSuccess) {
-            fail("csr_spgemm: allocation of C's %lld entries failed: %s", nz, hipGetErrorString(e));
-            break;
-        }
-        e = hipMemcpyAsync(d_rpC.p, rp.data(), rp.size() * sizeof(int), hipMemcpyHostToDevice, g_stream);
-        if (e == hipSuccess) {
-            run_blocks(true);
-            e = run_chunks(true);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-        if (e != hipSuccess) {
-            fail("csr_spgemm: numeric pass failed: %s", hipGetErrorString(e));
-            break;
-        }
-        lap(2);
-        trace.mark("numeric");
-        C->rows = M, C->cols = N, C->nz = nz;
-        C->rp = d_rpC.as<int>(), C->col = d_colC, C->val = d_valC;  // C owns them now
-        d_rpC.p = nullptr, d_colC = nullptr, d_valC = nullptr;
-        rc = 0;
-    } while (0);
-    (void)hipFree(d_colC);
-    (void)hipFree(d_valC);
-    (void)hipGetLastError();  // a failed allocation above is reported by rc, not by the next launch
-    if (rc) return rc;
+    e = C.alloc_entries<T>(nz, kPad, g_stream);
+    if (e != hipSuccess) return fail("csr_spgemm: allocation of C's %lld entries failed: %s", nz, hipGetErrorString(e));
+    d_colC = C.col, d_valC = static_cast<T *>(C.val);
+    e = hipMemcpyAsync(C.rp, rp.data(), rp.size() * sizeof(int), hipMemcpyHostToDevice, g_stream);
+    if (e == hipSuccess) {
+        run_blocks(true);
+        e = run_chunks(true);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
+    if (e != hipSuccess) return fail("csr_spgemm: numeric pass failed: %s", hipGetErrorString(e));
+    timer.lap(2);
+    trace.mark("numeric");
+    C_out = std::move(C);
     if (stats) {
-        const long long s[8] = {total, nz, (long long)desc.size(), block_rows, n_long, (long long)chunks.size(), widest, widest_nz};
+        const long long s[8] = {total, nz, (long long)desc.size(), block_rows, n_long, (long long)chunks.size(), widest, counts.widest};
         std::copy(s, s + 8, stats);
     }
     if (ms) std::copy(split, split + 3, ms);
@@ -260,25 +228,21 @@ int spgemm_body(const spmv_csr_dev *a, const spmv_csr_dev *b, int block_products
     DevCsr C;
     std::vector<int> rp;
     double split[4] = {0, 0, 0, 0};
-    if (spgemm_core_t<T>(csr_view(a), csr_view(b), block_products, chunk_products, &C, rp, stats, split)) return -1;
-    const double t0 = UploadTrace::now();
-    const int rc = csr_adopt<T>(C.rows, C.cols, rp.data(), C.col, static_cast<T *>(C.val), out);
-    if (rc == 0) C.col = nullptr, C.val = nullptr;  // the handle owns them now
-    C.release();
-    (void)hipGetLastError();
-    split[3] = (UploadTrace::now() - t0) * 1e3;
+    if (spgemm_core_t<T>(csr_view(a), csr_view(b), block_products, chunk_products, C, rp, stats, split)) return -1;
+    algebra::PhaseTimer timer{split};
+    const int rc = algebra::adopt<T>(std::move(C), rp, out);
+    C = DevCsr();  // (the free of what C still holds has always been part of this phase)
+    timer.lap(3);
     if (rc) return rc;
     if (ms) std::copy(split, split + 4, ms);
     return 0;
 }
 
-bool whole(const spmv_csr_dev *m) { return m->row0 == 0 && m->M_local == m->M_total; }
-
 }  // namespace
 
 int spgemm_max_block_products() { return kSgMaxProducts; }
 
-int spgemm_core(int value_bytes, const DevCsr &A, const DevCsr &B, int block_products, long long chunk_products, DevCsr *C,
+int spgemm_core(int value_bytes, const CsrView &A, const CsrView &B, int block_products, long long chunk_products, DevCsr &C,
                 std::vector<int> &rp_host, long long *stats, double *ms) {
     return value_bytes == 8 ? spgemm_core_t<double>(A, B, block_products, chunk_products, C, rp_host, stats, ms)
                             : spgemm_core_t<float>(A, B, block_products, chunk_products, C, rp_host, stats, ms);
@@ -290,13 +254,7 @@ extern "C" int spmv_hip_csr_spgemm(const spmv_csr_dev *a, const spmv_csr_dev *b,
     if (!out) return fail("csr_spgemm: out is NULL");
     *out = nullptr;
     if (!a || !b) return fail("csr_spgemm: NULL handle (a = %p, b = %p)", (const void *)a, (const void *)b);
-    for (const spmv_csr_dev *m : {a, b}) {
-        if (!whole(m))
-            return fail("csr_spgemm: %s is a handle of rows [%d, %d) of %d; only whole matrices multiply", m == a ? "A" : "B",
-                        m->row0, m->row0 + m->M_local, m->M_total);
-        if (m->tiles_only || !m->row_ptr || (m->nz > 0 && (!m->col || !m->val)))
-            return fail("csr_spgemm: %s does not hold its CSR arrays", m == a ? "A" : "B");
-    }
+    if (algebra::operand_ok("csr_spgemm", "A", "multiply", a) || algebra::operand_ok("csr_spgemm", "B", "multiply", b)) return -1;
     if (a->N != b->M_total)
         return fail("csr_spgemm: A is %d x %d and B is %d x %d: A's columns must be B's rows", a->M_total, a->N, b->M_total, b->N);
     if (a->value_bytes != b->value_bytes)

@@ -7,10 +7,11 @@
 //   tr_gather       colT[k] = row, valT[k] = val[e] at every sorted position: values are moved, never combined
 //   tr_row_ptr      row_ptr of A^T from the sorted columns (columns without entries included)
 //
-// Everything in front of the adopt is transpose_core, on bare device arrays (the AMG device setup calls it too).
+// Everything in front of the adopt is transpose_core, on a view of bare device arrays (the AMG device setup calls it
+// too); algebra_ops.hpp has the frame the handle producers share.
 // The columns of A are the sort's key input as they are; only the N + 1 row pointers of A^T cross to the host, and
 // the arrays go to csr_upload_impl through the adopt path, so A^T gets every plan and search an upload gives.
-#include "spmv_internal.hpp"
+#include "algebra_ops.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -58,67 +59,49 @@ __global__ __launch_bounds__(kBlock) void tr_row_ptr(long long nz, int N, const 
 
 // the transpose on bare arrays: everything but the adopt
 template <typename T>
-int transpose_core_t(const DevCsr &A, DevCsr *At, std::vector<int> &rp) {
-    const DevCsr *m = &A;
+int transpose_core_t(const CsrView &A, DevCsr &At_out, std::vector<int> &rp) {
+    const CsrView *m = &A;
     const int M = m->rows, N = m->cols;
     const long long nz = m->nz;
-    const size_t n = (size_t)nz, n1 = std::max<size_t>(n, 1);
-    unsigned long long *d_pin = nullptr, *d_pout = nullptr;
-    unsigned *d_kout = nullptr;
-    int *d_colT = nullptr, *d_rpT = nullptr;
-    T *d_valT = nullptr;
-    void *d_tmp = nullptr;
+    const size_t n = (size_t)nz;
+    ClearHipError clear;
+    DevBuf d_pin, d_pout, d_kout, d_tmp;
+    DevCsr At(N, M);
     rp.assign((size_t)N + 1, 0);
     UploadTrace trace("csr_transpose");  // SPMV_TRACE_UPLOAD=1: the build here, then upload's own phases
-    int rc = -1;
-    do {
-        hipError_t e = hipMalloc((void **)&d_pin, n1 * sizeof(unsigned long long));
-        if (e == hipSuccess) e = hipMalloc((void **)&d_pout, n1 * sizeof(unsigned long long));
-        if (e == hipSuccess) e = hipMalloc((void **)&d_kout, n1 * sizeof(unsigned));
-        if (e == hipSuccess) e = hipMalloc((void **)&d_colT, (n + kPad) * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void **)&d_valT, (n + kPad) * sizeof(T));
-        if (e == hipSuccess) e = hipMalloc((void **)&d_rpT, ((size_t)N + 1) * sizeof(int));
-        if (e == hipSuccess) e = hipMemsetAsync(d_colT + n, 0, kPad * sizeof(int), g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_valT + n, 0, kPad * sizeof(T), g_stream);
-        if (e != hipSuccess) { fail("csr_transpose: allocation failed: %s", hipGetErrorString(e)); break; }
-        if (n) {
-            const int rgrid = (int)std::min<long long>(kTrMaxGrid, ((long long)M + kTrWaves - 1) / kTrWaves);
-            hipLaunchKernelGGL(tr_make_pairs, dim3(rgrid), dim3(kBlock), 0, g_stream, M, m->rp, d_pin);
-            // only the bits a column index can use (a matrix of one column: a single bit, every key 0)
-            unsigned col_bits = 1;
-            while (col_bits < 32 && (1ull << col_bits) < (unsigned long long)N) ++col_bits;
-            const unsigned *keys = reinterpret_cast<const unsigned *>(m->col);  // columns are in [0, N)
-            size_t tmp_bytes = 0;
-            e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys, d_kout, d_pin, d_pout, n, 0u, col_bits, g_stream);
-            if (e == hipSuccess) e = hipMalloc(&d_tmp, std::max<size_t>(tmp_bytes, 16));
-            if (e == hipSuccess)
-                e = rocprim::radix_sort_pairs(d_tmp, tmp_bytes, keys, d_kout, d_pin, d_pout, n, 0u, col_bits, g_stream);
-            if (e != hipSuccess) { fail("csr_transpose: sort failed: %s", hipGetErrorString(e)); break; }
-            const int egrid = (int)((nz + kBlock - 1) / kBlock);
-            hipLaunchKernelGGL((tr_gather<T>), dim3(egrid), dim3(kBlock), 0, g_stream, nz, d_pout, (const T *)m->val,
-                               d_colT, d_valT);
-        }
-        const int pgrid = (int)((nz + kBlock) / kBlock);  // covers e == nz as well
-        hipLaunchKernelGGL(tr_row_ptr, dim3(pgrid), dim3(kBlock), 0, g_stream, nz, N, d_kout, d_rpT);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(rp.data(), d_rpT, rp.size() * sizeof(int), hipMemcpyDeviceToHost, g_stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-        if (e != hipSuccess) { fail("csr_transpose: build failed: %s", hipGetErrorString(e)); break; }
-        trace.mark("device build");
-        At->rows = N, At->cols = M, At->nz = nz;
-        At->rp = d_rpT, At->col = d_colT, At->val = d_valT;  // At owns them now
-        d_rpT = nullptr, d_colT = nullptr, d_valT = nullptr;
-        rc = 0;
-    } while (0);
-    (void)hipFree(d_pin);
-    (void)hipFree(d_pout);
-    (void)hipFree(d_kout);
-    (void)hipFree(d_rpT);
-    (void)hipFree(d_tmp);
-    (void)hipFree(d_colT);
-    (void)hipFree(d_valT);
-    (void)hipGetLastError();  // a failed allocation above is reported by rc, not by the next launch
-    return rc;
+    hipError_t e = d_pin.alloc(n * sizeof(unsigned long long));
+    if (e == hipSuccess) e = d_pout.alloc(n * sizeof(unsigned long long));
+    if (e == hipSuccess) e = d_kout.alloc(n * sizeof(unsigned));
+    if (e == hipSuccess) e = At.alloc_entries<T>(nz, kPad, g_stream);
+    if (e == hipSuccess) e = At.alloc_rp();
+    if (e != hipSuccess) return fail("csr_transpose: allocation failed: %s", hipGetErrorString(e));
+    if (n) {
+        const int rgrid = (int)std::min<long long>(kTrMaxGrid, ((long long)M + kTrWaves - 1) / kTrWaves);
+        hipLaunchKernelGGL(tr_make_pairs, dim3(rgrid), dim3(kBlock), 0, g_stream, M, m->rp, d_pin.as<unsigned long long>());
+        // only the bits a column index can use (a matrix of one column: a single bit, every key 0)
+        const unsigned col_bits = std::min(32u, algebra::bits_for((unsigned long long)N));
+        const unsigned *keys = reinterpret_cast<const unsigned *>(m->col);  // columns are in [0, N)
+        size_t tmp_bytes = 0;
+        e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys, d_kout.as<unsigned>(), d_pin.as<unsigned long long>(),
+                                      d_pout.as<unsigned long long>(), n, 0u, col_bits, g_stream);
+        if (e == hipSuccess) e = d_tmp.alloc(tmp_bytes);
+        if (e == hipSuccess)
+            e = rocprim::radix_sort_pairs(d_tmp.p, tmp_bytes, keys, d_kout.as<unsigned>(), d_pin.as<unsigned long long>(),
+                                          d_pout.as<unsigned long long>(), n, 0u, col_bits, g_stream);
+        if (e != hipSuccess) return fail("csr_transpose: sort failed: %s", hipGetErrorString(e));
+        const int egrid = (int)((nz + kBlock - 1) / kBlock);
+        hipLaunchKernelGGL((tr_gather<T>), dim3(egrid), dim3(kBlock), 0, g_stream, nz, d_pout.as<unsigned long long>(),
+                           (const T *)m->val, At.col, static_cast<T *>(At.val));
+    }
+    const int pgrid = (int)((nz + kBlock) / kBlock);  // covers e == nz as well
+    hipLaunchKernelGGL(tr_row_ptr, dim3(pgrid), dim3(kBlock), 0, g_stream, nz, N, d_kout.as<unsigned>(), At.rp);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(rp.data(), At.rp, rp.size() * sizeof(int), hipMemcpyDeviceToHost, g_stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
+    if (e != hipSuccess) return fail("csr_transpose: build failed: %s", hipGetErrorString(e));
+    trace.mark("device build");
+    At_out = std::move(At);
+    return 0;
 }
 
 // core, then the adopt: A^T is an ordinary handle with upload's plans
@@ -126,17 +109,13 @@ template <typename T>
 int transpose_body(const spmv_csr_dev *m, spmv_csr_dev **out) {
     DevCsr At;
     std::vector<int> rp;
-    if (transpose_core_t<T>(csr_view(m), &At, rp)) return -1;
-    const int rc = csr_adopt<T>(At.rows, At.cols, rp.data(), At.col, static_cast<T *>(At.val), out);
-    if (rc == 0) At.col = nullptr, At.val = nullptr;  // the handle owns them now
-    At.release();
-    (void)hipGetLastError();
-    return rc;
+    if (transpose_core_t<T>(csr_view(m), At, rp)) return -1;
+    return algebra::adopt<T>(std::move(At), rp, out);
 }
 
 }  // namespace
 
-int transpose_core(int value_bytes, const DevCsr &A, DevCsr *At, std::vector<int> &rp_host) {
+int transpose_core(int value_bytes, const CsrView &A, DevCsr &At, std::vector<int> &rp_host) {
     return value_bytes == 8 ? transpose_core_t<double>(A, At, rp_host) : transpose_core_t<float>(A, At, rp_host);
 }
 
@@ -145,11 +124,7 @@ extern "C" int spmv_hip_csr_transpose(const spmv_csr_dev *m, spmv_csr_dev **out)
     if (!out) return fail("csr_transpose: out is NULL");
     *out = nullptr;
     if (!m) return fail("csr_transpose: NULL handle");
-    if (m->row0 != 0 || m->M_local != m->M_total)
-        return fail("csr_transpose: a handle of rows [%d, %d) of %d; only whole matrices transpose", m->row0,
-                    m->row0 + m->M_local, m->M_total);
-    if (m->tiles_only || !m->row_ptr || (m->nz > 0 && (!m->col || !m->val)))
-        return fail("csr_transpose: the handle does not hold its CSR arrays");
+    if (algebra::operand_ok("csr_transpose", nullptr, "transpose", m)) return -1;
     if ((unsigned long long)m->M_total * (unsigned long long)m->value_bytes >= (1ull << 32))
         return fail("csr_transpose: M = %d: the transpose's x exceeds the 32-bit gather offset range of the kernels",
                     m->M_total);

@@ -241,27 +241,29 @@ class CsrDevice(_Handle):
         return getattr(self, "row0", 0), getattr(self, "row1", self.M)
 
     @classmethod
+    def _built(cls, M, N, dtype, what, build):
+        """A whole M x N handle the library builds on the device: build(out) is the C call, out its handle argument."""
+        self = cls.__new__(cls)
+        _Handle.__init__(self)
+        _check(build(C.byref(self.h)), what)
+        self.M, self.N, self.dtype = int(M), int(N), dtype
+        return self
+
+    @classmethod
     def from_coo(cls, M, N, I, J, val):
         """CSR built on the device from COO triplets (spmv_hip_csr_from_coo); fp64."""
         I = np.ascontiguousarray(I, dtype=np.int32)
         J = np.ascontiguousarray(J, dtype=np.int32)
         val = np.ascontiguousarray(val, dtype=np.float64)
-        self = cls.__new__(cls)
-        _Handle.__init__(self)
-        _check(nat.lib().spmv_hip_csr_from_coo(int(M), int(N), len(I), I.ctypes.data_as(nat.c_int_p),
-                                               J.ctypes.data_as(nat.c_int_p), val.ctypes.data_as(nat.c_double_p),
-                                               C.byref(self.h)), "spmv_hip_csr_from_coo")
-        self.M, self.N, self.dtype = int(M), int(N), np.float64
-        return self
+        return cls._built(M, N, np.float64, "spmv_hip_csr_from_coo", lambda out: nat.lib().spmv_hip_csr_from_coo(
+            int(M), int(N), len(I), I.ctypes.data_as(nat.c_int_p), J.ctypes.data_as(nat.c_int_p),
+            val.ctypes.data_as(nat.c_double_p), out))
 
     def transpose(self) -> "CsrDevice":
         """A^T as a new handle (spmv_hip_csr_transpose): built on the device from this handle's arrays, N x M, the same
         dtype, bit-exact values; it gets the plans an upload of A^T would get and owns its arrays."""
-        out = CsrDevice.__new__(CsrDevice)
-        _Handle.__init__(out)
-        _check(nat.lib().spmv_hip_csr_transpose(self.h, C.byref(out.h)), "spmv_hip_csr_transpose")
-        out.M, out.N, out.dtype = self.N, self.M, self.dtype
-        return out
+        return CsrDevice._built(self.N, self.M, self.dtype, "spmv_hip_csr_transpose",
+                                lambda out: nat.lib().spmv_hip_csr_transpose(self.h, out))
 
     def matmul(self, other: "CsrDevice", block_products: int = 0, chunk_products: int = 0) -> "CsrDevice":
         """C = self @ other as a new handle (spmv_hip_csr_spgemm): both whole matrices of one dtype.  C has canonical rows
@@ -272,12 +274,9 @@ class CsrDevice(_Handle):
         (0 = auto, else >= 64).  C.matmul_info holds the stats (MATMUL_STATS) and "ms" (MATMUL_MS) of this product."""
         if not isinstance(other, CsrDevice):
             raise TypeError("matmul takes a CsrDevice")
-        out = CsrDevice.__new__(CsrDevice)
-        _Handle.__init__(out)
         stats, ms = (C.c_longlong * len(MATMUL_STATS))(), (C.c_double * len(MATMUL_MS))()
-        _check(nat.lib().spmv_hip_csr_spgemm(self.h, other.h, int(block_products), int(chunk_products), C.byref(out.h),
-                                             stats, ms), "spmv_hip_csr_spgemm")
-        out.M, out.N, out.dtype = self.M, other.N, self.dtype
+        out = CsrDevice._built(self.M, other.N, self.dtype, "spmv_hip_csr_spgemm", lambda out: nat.lib().spmv_hip_csr_spgemm(
+            self.h, other.h, int(block_products), int(chunk_products), out, stats, ms))
         out.matmul_info = dict(zip(MATMUL_STATS, (int(v) for v in stats)))
         out.matmul_info["ms"] = dict(zip(MATMUL_MS, (float(v) for v in ms)))
         return out
@@ -314,12 +313,9 @@ class CsrDevice(_Handle):
             raise ValueError(f"add: lanes = {lanes}; 0 (auto) or a power of two in [1, 64]")
         if long_row < 0 or long_row > 0x7fffffff:
             raise ValueError(f"add: long_row = {long_row}; 0 (auto) or a positive row length")
-        out = CsrDevice.__new__(CsrDevice)
-        _Handle.__init__(out)
         stats, ms = (C.c_longlong * len(ADD_STATS))(), (C.c_double * len(ADD_MS))()
-        _check(nat.lib().spmv_hip_csr_add(self.h, alpha, other.h if other is not None else None, beta, ADD_METHODS[method],
-                                          lanes, long_row, C.byref(out.h), stats, ms), "spmv_hip_csr_add")
-        out.M, out.N, out.dtype = self.M, self.N, self.dtype
+        out = CsrDevice._built(self.M, self.N, self.dtype, "spmv_hip_csr_add", lambda out: nat.lib().spmv_hip_csr_add(
+            self.h, alpha, other.h if other is not None else None, beta, ADD_METHODS[method], lanes, long_row, out, stats, ms))
         out.add_info = dict(zip(ADD_STATS, (int(v) for v in stats)))
         out.add_info["ms"] = dict(zip(ADD_MS, (float(v) for v in ms)))
         return out
