@@ -46,7 +46,7 @@ enum class stream_route { x_window, tiles, gather, nothing_else, unaligned_x }; 
 // part < 0: the whole product; 0 / 1: the interior / boundary sub-lists, which only an x-window launch of a handle
 // that has the split can run (anything else: csr_launch_part runs everything as part 1)
 inline stream_route csr_stream_route(const spmv_csr_dev *m, const void *x, int part) {
-    const bool local = x_window_runs(m->local_blocks, x) && (part < 0 || m->have_split);
+    const bool local = x_window_runs(m->xw.blocks, x) && (part < 0 || m->have_split);
     const bool tiled = !local && m->tile.blocks > 0 && tiles_run(m, x, m->tiles_only);
     if (m->tiles_only && !tiled) return tiles_take_x(m, x) ? stream_route::nothing_else : stream_route::unaligned_x;
     return tiled ? stream_route::tiles : local ? stream_route::x_window : stream_route::gather;

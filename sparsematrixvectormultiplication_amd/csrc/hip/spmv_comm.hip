@@ -532,13 +532,13 @@ static int spmv_hip_csr_needed_ranges_body(const spmv_csr_dev *m, int max_ranges
     if (need_device()) return -1;
     if (!m || !ranges || !count || max_ranges < 1) return fail("csr_needed_ranges: bad arguments");
     std::vector<std::pair<int, int>> r;
-    if (m->local_blocks <= 0 || m->num_long > 0) {
+    if (m->xw.blocks <= 0 || m->num_long > 0) {
         r.emplace_back(0, m->N);  // no plan, or rows outside it: everything
     } else {
         std::vector<int2> ld;
         std::vector<int> stored, lbase, lines;
         if (csr_lines_to_host(m, ld, stored, lbase)) return -1;
-        lines.reserve((size_t)m->local_lines);
+        lines.reserve((size_t)m->xw.lines_listed);
         for (size_t b = 0; b < ld.size(); ++b)
             for (int k = 0; k < ld[b].y; ++k) lines.push_back(stored[(size_t)ld[b].x + k] + lbase[b]);
         std::sort(lines.begin(), lines.end());

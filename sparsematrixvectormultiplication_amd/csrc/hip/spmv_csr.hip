@@ -49,9 +49,12 @@ void csr_build_blocks(int M, const int *rp, int cap, int rows_cap, std::vector<i
     }
 }
 
-
+// The host builder of the x-window plan (LocalPlan, spmv_internal.hpp): csr_build_blocks' cut with the line limit on top
+// (1 << line_shift elements per line).  Returns false when some row alone needs more than lines_max lines, or when the
+// line limit (rather than cap) decides so many cuts that the blocks would run mostly empty: the caller then keeps the
+// gather kernel.
 bool csr_build_local(int M, int N, const int *rp, const int *col, long long nz, int cap, int rows_cap,
-                     int line_shift, int lines_max, const std::vector<int4> &baseline, LocalPlan &plan) {
+                     int line_shift, int lines_max, const std::vector<int4> &baseline, LocalPlan<int2> &plan) {
     const int total_lines = (int)(((long long)N + (1 << line_shift) - 1) >> line_shift);
     const int line_mask = (1 << line_shift) - 1;
     std::vector<int> stamp((size_t)total_lines + 1, -1), rank((size_t)total_lines + 1, 0), cur;
@@ -144,7 +147,7 @@ int csr_plan_on_device(spmv_csr_dev *m, const std::vector<int4> &desc, long long
         len[w] = desc[w].w - desc[w].y;
         if (len[w] > kPlanCap) return 0;
     }
-    const int rc = plan_on_device<SHIFT>(m, m->col, (size_t)nz, desc, begin, len, m->lcol, m->ldesc,
+    const int rc = plan_on_device<SHIFT>(m->xw, m->col, (size_t)nz, desc, begin, len,
                                          [](int, int first, int n) { return int2{first, n}; }, nl);
     if (rc != 0 || nl.empty()) return rc;
     // Some block lists too many lines.  The host builder may still find a plan (blocks cut by lines, a few rows split) --
@@ -186,7 +189,7 @@ static int pattern_segment_cap(int value_bytes, int local_cap, int stage_lines) 
     return cap;
 }
 int csr_pattern_segment_cap(const spmv_csr_dev *m) {
-    return pattern_segment_cap(m->value_bytes, m->local_cap, m->local_stage_lines);
+    return pattern_segment_cap(m->value_bytes, m->local_cap, m->xw.stage_lines);
 }
 extern "C" int spmv_hip_csr_pattern_segment_cap(int value_bytes, int local_cap, int stage_lines) {
     if ((value_bytes != 4 && value_bytes != 8) || local_cap <= 0 || local_cap > kStreamCapMax || stage_lines < 0 ||
@@ -200,13 +203,13 @@ extern "C" int spmv_hip_csr_pattern_segment_cap(int value_bytes, int local_cap, 
 // workgroup per CU (at most the 7 the kernel's VGPRs allow).  A block whose segment is wider keeps its table.  A
 // failure drops the whole plan (and clears the last HIP error).
 void csr_pattern_segments(spmv_csr_dev *m, const std::vector<int> &count) {
-    PatternPlan &pat = m->pat;
+    PatternPlan &pat = m->xw.pat;
     if (!pat.ptab) return;
     UploadTrace trace("csr_pattern_segments");
-    const int B = m->local_blocks;
+    const int B = m->xw.blocks;
     const int cap16 = csr_pattern_segment_cap(m);
     std::vector<int4> h_desc((size_t)B);  // the blocks' row counts: the size of their segments
-    hipError_t e = hipMemcpyAsync(h_desc.data(), m->ldesc4, (size_t)B * sizeof(int4), hipMemcpyDeviceToHost, g_stream);
+    hipError_t e = hipMemcpyAsync(h_desc.data(), m->xw.ldesc4, (size_t)B * sizeof(int4), hipMemcpyDeviceToHost, g_stream);
     if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
     std::vector<int2> h_sdesc((size_t)B, make_int2(0, 0));
     long long seg_total = 0, table_rows = 0, segments = 0;
@@ -229,7 +232,7 @@ void csr_pattern_segments(spmv_csr_dev *m, const std::vector<int> &count) {
         if (e == hipSuccess) e = hipMemsetAsync(pat.pseg, 0, (size_t)seg_total * sizeof(uint4), g_stream);
         if (e == hipSuccess) e = hipMemcpyAsync(pat.sdesc, h_sdesc.data(), (size_t)B * sizeof(int2), hipMemcpyHostToDevice, g_stream);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL((pat_segment<256>), dim3(B), dim3(256), 0, g_stream, B, m->ldesc4, m->row_ptr, pat.rinfo,
+            hipLaunchKernelGGL((pat_segment<256>), dim3(B), dim3(256), 0, g_stream, B, m->xw.ldesc4, m->row_ptr, pat.rinfo,
                                pat.ptab, pat.pdesc, pat.sdesc, pat.pseg);
             e = hipGetLastError();
         }
@@ -262,23 +265,76 @@ void csr_pattern_segments(spmv_csr_dev *m, const std::vector<int> &count) {
 // its group's canonical word for word keeps its own copy.  A failure leaves the plan unshared.  What it buys on that
 // matrix: 51 MB of 893 MB per launch, and no time (profiles/plan_sharing_bench_ab.txt).
 void csr_share_plan(spmv_csr_dev *m) {
-    if (g_local_share == 0 || m->local_blocks <= 0 || !m->lines || !m->ldesc) return;
+    XWindowPlan<int2> &xw = m->xw;
+    if (g_local_share == 0 || xw.blocks <= 0 || !xw.lines || !xw.ldesc) return;
     UploadTrace trace("csr_share_plan");
     const bool weak = g_local_share == 2;
-    PatternPlan &pat = m->pat;
+    PatternPlan &pat = xw.pat;
     if (pat.pseg && pat.sdesc) {
         long long stored = 0, distinct = 0;
-        if (share_spans(pat.pseg, pat.sdesc, m->local_blocks, 0, false, weak, nullptr, stored, distinct)) {
+        if (share_spans(pat.pseg, pat.sdesc, xw.blocks, 0, false, weak, nullptr, stored, distinct)) {
             pat.seg_total = stored;
             pat.seg_distinct = distinct;
         }
     }
     long long stored = 0, distinct = 0;
-    if (share_spans(m->lines, m->ldesc, m->local_blocks, (size_t)kLocalLinesMax, true, weak, &m->lbase, stored, distinct)) {
-        m->lines_stored = stored;
-        m->lists_distinct = distinct;
+    if (share_spans(xw.lines, xw.ldesc, xw.blocks, (size_t)kLocalLinesMax, true, weak, &xw.lbase, stored, distinct)) {
+        xw.lines_stored = stored;
+        xw.lists_stored = distinct;
     }
     trace.mark("shared segments and line lists");
+}
+
+// The x-window phase of upload (csr_stream_local): own blocks at the stage m->local_cap.  One stage size per handle, so
+// that its blocks, the gather kernel's and the split long rows agree on which rows are long: a matrix that gets a plan
+// runs everything at 2048.  An explicit stream_cap other than that asks for the gather kernel's configuration and skips
+// the plan.  rp: the handle's row_ptr; col_host: its columns, or NULL when they live on the device only (m->col).
+// 1: m->xw is the plan, complete -- uploaded, with its pattern plan and the sharing pass -- and `split` marks the rows it
+// hands to the split-row kernels; 0: no plan, nothing of it allocated; -1: error.
+template <typename T>
+int csr_x_window_phase(spmv_csr_dev *m, const std::vector<int> &rp, const int *col_host, UploadTrace &trace,
+                       std::vector<unsigned char> &split) {
+    constexpr int line_shift = sizeof(T) == 8 ? 4 : 5;  // 128-byte lines
+    const int Ml = m->M_local, lcap = m->local_cap;
+    const long long nz = m->nz;
+    LocalPlan<int2> local;
+    bool have_local = false, on_device = false;
+    if (g_stream_local && nz > 0 && (g_stream_cap == 0 || g_stream_cap == lcap)) {
+        std::vector<int4> desc, pieces, long_rows;
+        csr_build_blocks(Ml, rp.data(), lcap, kStreamRowsCap, desc, pieces, long_rows);
+        // on the device when no block lists more than 256 lines (the common case for matrices that get
+        // a plan at all: then the line limit would not have moved a block boundary on the host either);
+        // otherwise the host builder decides (line-limited blocks, split rows, or no plan)
+        int dev = 0;
+        if (g_plan_on_device && lcap == kPlanCap) {
+            if (!m->col && upload_array(&m->col, col_host, (size_t)nz, kPad)) return -1;
+            dev = csr_plan_on_device<line_shift>(m, desc, nz);
+            if (dev < 0) return -1;
+        }
+        on_device = dev == 1;
+        const bool refused = dev == 2;  // plainly scattered columns: no plan, and no need to ask the host builder
+        std::vector<int> col_back;  // adopted arrays live on the device only: the host builder needs a copy
+        if (!on_device && !refused && !col_host) {
+            col_back.resize((size_t)nz);
+            if (hipMemcpy(col_back.data(), m->col, (size_t)nz * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+                return fail("csr_upload: copying the columns back for the host plan failed");
+        }
+        have_local = on_device ||
+                     (!refused && csr_build_local(Ml, m->N, rp.data(), col_host ? col_host : col_back.data(), nz, lcap,
+                                                  kStreamRowsCap, line_shift, kLocalLinesMax, desc, local));
+        if (on_device) split.assign((size_t)Ml, 0);
+        else if (have_local) split.swap(local.split);
+    }
+    trace.mark("x-window plan (or its refusal)");
+    if (!have_local) return 0;
+    if (upload_array(&m->row_ptr, rp.data(), rp.size(), (size_t)kRowPtrPad)) return -1;
+    if (!on_device && m->xw.upload(local)) return -1;
+    // the pattern plan (optional: one that cannot be built is simply not there); here, ahead of the value array, whose
+    // first placement goes with the allocations before it
+    csr_pattern_segments(m, build_pattern_tables<false>(m->xw, Ml, nz, m->value_bytes, m->row_ptr));
+    // equal segments and line lists once: before the searches, which time the plan the handle keeps
+    csr_share_plan(m);
+    return 1;
 }
 
 template <typename T>
@@ -348,43 +404,13 @@ int csr_upload_impl(int M, int N, const int *row_ptr, const int *col_idx, const 
     }
     m->max_row = max_row;
 
-    std::vector<int4> desc, pieces, long_rows;
-    // The x-window kernel first (csr_stream_local): own blocks at a 2048-entry stage.  One stage
-    // size per handle, so that its blocks, the gather kernel's and the split long rows agree on
-    // which rows are long: a matrix that gets a plan runs everything at 2048.  An explicit
-    // stream_cap other than 2048 asks for the gather kernel's configuration and skips the plan.
-    LocalPlan local;
-    bool have_local = false;
-    constexpr int line_shift = sizeof(T) == 8 ? 4 : 5;  // 128-byte lines
-    // (1024-entry blocks were tried for small matrices: cant-like 13.2 us against 11.7 us at 2048)
-    const int lcap = g_local_cap ? g_local_cap : 2048;
-    bool on_device = false;
-    if (g_stream_local && nz > 0 && (g_stream_cap == 0 || g_stream_cap == lcap)) {
-        csr_build_blocks(Ml, rp.data(), lcap, kStreamRowsCap, desc, pieces, long_rows);
-        // on the device when no block lists more than 256 lines (the common case for matrices that get
-        // a plan at all: then the line limit would not have moved a block boundary on the host either);
-        // otherwise the host builder decides (line-limited blocks, split rows, or no plan)
-        int dev = 0;
-        if (g_plan_on_device && lcap == kPlanCap) {
-            if (!m->col && upload_array(&m->col, col_idx + e0, (size_t)nz, kPad)) return -1;
-            dev = csr_plan_on_device<line_shift>(m, desc, nz);
-            if (dev < 0) return -1;
-        }
-        on_device = dev == 1;
-        const bool refused = dev == 2;  // plainly scattered columns: no plan, and no need to ask the host builder
-        std::vector<int> col_back;  // adopted arrays live on the device only: the host builder needs a copy
-        if (!on_device && !refused && !col_idx) {
-            col_back.resize((size_t)nz);
-            if (hipMemcpy(col_back.data(), m->col, (size_t)nz * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
-                return fail("csr_upload: copying the columns back for the host plan failed");
-        }
-        have_local = on_device ||
-                     (!refused &&
-                      csr_build_local(Ml, N, rp.data(), col_idx ? col_idx + e0 : col_back.data(), nz, lcap,
-                                      kStreamRowsCap, line_shift, kLocalLinesMax, desc, local));
-        if (on_device) local.split.assign((size_t)Ml, 0);
-    }
-    trace.mark("x-window plan (or its refusal)");
+    // the x-window kernel first (csr_stream_local); (1024-entry blocks were tried for small matrices: cant-like 13.2 us
+    // against 11.7 us at 2048)
+    m->local_cap = g_local_cap ? g_local_cap : 2048;
+    std::vector<unsigned char> local_split;
+    const int planned = csr_x_window_phase<T>(m, rp, col_idx ? col_idx + e0 : nullptr, trace, local_split);
+    if (planned < 0) return -1;
+    const bool have_local = planned == 1;
     // No x-window plan: columns too scattered for 256 lines per block.  Then the 2-D tiles (csr_tile):
     // row-block accumulators in LDS, the block's entries re-ordered into column passes so that all
     // workgroups sweep x together (L2-resident band), dense passes staged in LDS.  Needs enough row
@@ -436,8 +462,7 @@ int csr_upload_impl(int M, int N, const int *row_ptr, const int *col_idx, const 
     }
     // else: larger stages amortise per-workgroup latency on big matrices; small ones need
     // enough workgroups to fill 256 CUs (measured: cant-like 2048, nlpkkt-like 4096)
-    m->stream_cap = have_local ? lcap : (g_stream_cap ? g_stream_cap : (nz >= (16LL << 20) ? 4096 : 2048));
-    m->local_cap = lcap;
+    m->stream_cap = have_local ? m->local_cap : (g_stream_cap ? g_stream_cap : (nz >= (16LL << 20) ? 4096 : 2048));
     int rows_cap = kStreamRowsCap;
     // Skewed rows (gather kernels): a block's rows are summed by lane groups sized for the NUMBER of rows in it, so in
     // a block of a few hundred short rows one row of a thousand entries is summed by a single lane while everybody else
@@ -456,8 +481,9 @@ int csr_upload_impl(int M, int N, const int *row_ptr, const int *col_idx, const 
             if (!any) skew_split.clear();
         }
     }
+    std::vector<int4> desc, pieces, long_rows;
     csr_build_blocks(Ml, rp.data(), m->stream_cap, rows_cap, desc, pieces, long_rows,
-                     have_local ? &local.split : skew_split.empty() ? nullptr : &skew_split);
+                     have_local ? &local_split : skew_split.empty() ? nullptr : &skew_split);
     m->num_blocks = (int)desc.size();
     m->num_long = (int)long_rows.size();
     m->num_partial = (int)pieces.size();
@@ -465,32 +491,15 @@ int csr_upload_impl(int M, int N, const int *row_ptr, const int *col_idx, const 
 
     int rc = 0;
     if (!m->row_ptr) rc |= upload_array(&m->row_ptr, rp.data(), rp.size(), (size_t)kRowPtrPad);
-    if (!rc && have_local && !on_device) {
-        rc |= upload_array(&m->ldesc4, local.desc.data(), local.desc.size(), 1);
-        if (!rc) rc |= upload_array(&m->ldesc, local.ldesc.data(), local.ldesc.size(), 1);
-        if (!rc) rc |= upload_array(&m->lines, local.lines.data(), local.lines.size(), 0);
-        if (!rc) rc |= upload_array(&m->lcol, local.lcol.data(), local.lcol.size(), 0);
-        if (!rc) {
-            m->local_blocks = (int)local.desc.size();
-            m->local_stage_lines = local.stage_lines;
-            m->local_lines = (long long)local.lines.size() - kLocalLinesMax;
-        }
-    }
-    // the pattern plan (optional: one that cannot be built is simply not there); here, ahead of the value array, whose
-    // first placement goes with the allocations before it
-    if (!rc)
-        csr_pattern_segments(m, build_pattern_tables<false>(m->pat, m->local_blocks, m->M_local, nz, m->value_bytes,
-                                                            m->ldesc4, m->row_ptr, nullptr, m->lcol));
-    // equal segments and line lists once: before the searches below, which time the plan the handle keeps
-    if (!rc) csr_share_plan(m);
     if (!rc && !m->col) rc |= upload_array(&m->col, col_idx ? col_idx + e0 : nullptr, (size_t)nz, kPad);
     if (!rc && !m->val) rc |= upload_array((T **)&m->val, values ? values + e0 : nullptr, (size_t)nz, kPad);
     if (!rc) rc |= upload_array(&m->desc, desc.data(), desc.size(), 1);
     if (!rc && m->num_long) rc |= upload_array(&m->long_rows, long_rows.data(), long_rows.size(), 0);
     if (!rc && num_partial) rc |= upload_array(&m->pieces, pieces.data(), pieces.size(), 0);
-    const size_t bytes_before_tiles = m->device_bytes;
+    // (the tile plans add their own bytes)
+    m->rest_bytes = rp.size() * 4 + ((size_t)nz + kPad) * (4 + sizeof(T)) + desc.size() * 16 + long_rows.size() * 16 +
+                    pieces.size() * 16 + (size_t)num_partial * sizeof(T) + ((size_t)N + (size_t)M) * sizeof(T);
     if (!rc && tile_upload_all<T>(m, tb) < 0) rc = -1;  // (1 = the device refused the LDS size: no tiles, not an error)
-    const size_t tile_bytes = m->device_bytes - bytes_before_tiles;  // (device_bytes is recomputed below)
     const int partial_slots = std::max(num_partial, (int)tb.tile_pieces.size());
     if (!rc && partial_slots) {
         hipError_t e = hipMalloc(&m->partial, (size_t)partial_slots * sizeof(T));
@@ -506,13 +515,6 @@ int csr_upload_impl(int M, int N, const int *row_ptr, const int *col_idx, const 
         if (e != hipSuccess) rc = fail("hipMalloc(x/y) failed: %s", hipGetErrorString(e));
     }
     if (rc) return -1;
-    m->device_bytes = rp.size() * 4 + ((size_t)nz + kPad) * (4 + sizeof(T)) + desc.size() * 16 +
-                      long_rows.size() * 16 + pieces.size() * 16 + (size_t)num_partial * sizeof(T) +
-                      ((size_t)N + (size_t)M) * sizeof(T);
-    if (have_local)
-        m->device_bytes += (size_t)m->local_blocks * 24 + (m->lbase ? (size_t)m->local_blocks * 4 : 0) +
-                           ((size_t)(m->lbase ? m->lines_stored : m->local_lines) + kLocalLinesMax) * 4 + ((size_t)nz + kPad) * 2;
-    m->device_bytes += m->pat.bytes(Ml, m->local_blocks) + tile_bytes;
 
     // lanes per row for the SUBWAVE kernel: about half the mean row length,
     // rounded to a power of two, so that a typical row takes 1-2 passes
@@ -529,8 +531,8 @@ int csr_upload_impl(int M, int N, const int *row_ptr, const int *col_idx, const 
     trace.mark("blocks, remaining uploads, vectors");
     // the searches (upload_ops.hpp); the placement of m->val where it is large and streamed by the handle's kernel (a
     // tile plan without an x-window plan streams its own re-ordered copy)
-    const bool place = (size_t)nz * sizeof(T) >= kPlaceMinBytes && !m->tiles_only && (m->local_blocks > 0 || m->tile.blocks == 0);
-    upload_searches(m, Ml, place ? &m->val : nullptr, ((size_t)nz + kPad) * sizeof(T),
+    const bool place = (size_t)nz * sizeof(T) >= kPlaceMinBytes && !m->tiles_only && (m->xw.blocks > 0 || m->tile.blocks == 0);
+    upload_searches(m, place ? &m->val : nullptr, ((size_t)nz + kPad) * sizeof(T),
                     [m] { return csr_launch_any(m, SPMV_CSR_AUTO, m->x, m->y, g_stream); });
     trace.mark("placement tuning");
     drop.h = nullptr;
@@ -557,7 +559,7 @@ static int spmv_hip_csr_plan_check_body(int M, int N, const int *row_ptr, const 
         if ((unsigned)col_idx[e] >= (unsigned)N) return fail("plan_check: column %d outside [0, %d)", col_idx[e], N);
     const int cap = 2048, shift = value_bytes == 8 ? 4 : 5, mask = (1 << shift) - 1;
     std::vector<int4> desc, pieces, long_rows;
-    LocalPlan plan;
+    LocalPlan<int2> plan;
     csr_build_blocks(M, row_ptr, cap, kStreamRowsCap, desc, pieces, long_rows);
     const bool have = nz > 0 && csr_build_local(M, N, row_ptr, col_idx, nz, cap, kStreamRowsCap, shift,
                                                 kLocalLinesMax, desc, plan);
@@ -980,12 +982,7 @@ extern "C" void spmv_hip_csr_free(spmv_csr_dev *m) {
     (void)hipFree(m->col);
     (void)hipFree(m->val);
     (void)hipFree(m->desc);
-    (void)hipFree(m->ldesc4);
-    (void)hipFree(m->ldesc);
-    (void)hipFree(m->lines);
-    (void)hipFree(m->lbase);
-    (void)hipFree(m->lcol);
-    m->pat.release();
+    m->xw.release();
     m->tile.release();
     m->lt.release();
     m->mt.release();
@@ -1011,8 +1008,8 @@ static int relocate_impl(spmv_csr_dev *m, int which, unsigned long long align, u
     if (!m || which < 0 || which > 7) return fail("csr_relocate: bad arguments");
     if (align < 256 || (align & (align - 1)) || (offset & 255) || offset >= align)
         return fail("csr_relocate: align must be a power of two >= 256, offset a multiple of 256 below it");
-    void **fields[8] = {(void **)&m->row_ptr, (void **)&m->col, &m->val, &m->x, &m->y, (void **)&m->lcol,
-                        (void **)&m->lines, (void **)&m->ldesc4};
+    void **fields[8] = {(void **)&m->row_ptr, (void **)&m->col, &m->val, &m->x, &m->y, (void **)&m->xw.slot,
+                        (void **)&m->xw.lines, (void **)&m->xw.ldesc4};
     void **field = fields[which];
     if (!*field) return 0;  // the handle has no such array
     HIP_TRY(hipStreamSynchronize(g_stream));
@@ -1088,10 +1085,11 @@ extern "C" int spmv_hip_csr_relocate_vmm(spmv_csr_dev *m, int which, unsigned lo
 extern "C" int spmv_hip_csr_stamp_blocks(spmv_csr_dev *m, int warm, unsigned long long *stamps_host) {
     if (need_device()) return -1;
     if (!m || !stamps_host) return fail("csr_stamp_blocks: NULL argument");
-    if (m->local_blocks <= 0 || m->value_bytes != 8 || m->local_cap != 2048)
+    const XWindowPlan<int2> &p = m->xw;
+    if (p.blocks <= 0 || m->value_bytes != 8 || m->local_cap != 2048)
         return fail("csr_stamp_blocks: needs an fp64 handle with an x-window plan at the 2048-entry stage");
     unsigned long long *d = nullptr;
-    const size_t bytes = (size_t)m->local_blocks * 3 * sizeof(unsigned long long);
+    const size_t bytes = (size_t)p.blocks * 3 * sizeof(unsigned long long);
     HIP_TRY(hipMalloc((void **)&d, bytes));
     int rc = 0;
     // (warm >= 1000, measurement only: the stamped launch does not read the slot stream -- the time the kernel would take
@@ -1100,22 +1098,18 @@ extern "C" int spmv_hip_csr_stamp_blocks(spmv_csr_dev *m, int warm, unsigned lon
     warm %= 1000;
     for (int i = 0; i < warm && !rc; ++i) rc = csr_launch_any(m, SPMV_CSR_STREAM, m->x, m->y, g_stream);
     if (!rc) {
-        const int lcount = m->local_blocks;
-        const int lchunk = g_stream_xcd < 0 ? (lcount + 7) / 8 : (g_stream_xcd ? g_stream_xcd : 16);
-        const int lgrid = (lcount + 8 * lchunk - 1) / (8 * lchunk) * (8 * lchunk);
-        const size_t lds = std::max((size_t)m->local_cap * sizeof(double), (size_t)m->local_stage_lines * kLineBytes);
-        const bool lnt = g_local_nt < 0 ? m->nz * 10LL > (128LL << 20) : g_local_nt != 0;
+        const XWindowLaunch L = p.launch_shape(p.blocks, m->local_cap, 8, m->nz);
         double *y = (double *)m->y + m->row0;
-        if (lnt)
-            hipLaunchKernelGGL((csr_stream_local<double, true, 2048, true>), dim3(lgrid), dim3(kBlock), lds, g_stream, lcount, lchunk,
-                               (const int *)nullptr, m->ldesc4, m->ldesc, m->lines, m->row_ptr, m->lcol, (const double *)m->val,
+        if (L.nt)
+            hipLaunchKernelGGL((csr_stream_local<double, true, 2048, true>), dim3(L.grid), dim3(kBlock), L.lds, g_stream, p.blocks, L.chunk,
+                               (const int *)nullptr, p.ldesc4, p.ldesc, p.lines, m->row_ptr, p.slot, (const double *)m->val,
                                (const double *)m->x, y, d, probe, (const int2 *)nullptr, (const unsigned *)nullptr,
-                               (const unsigned short *)nullptr, 0, (const int2 *)nullptr, (const uint4 *)nullptr, m->lbase);
+                               (const unsigned short *)nullptr, 0, (const int2 *)nullptr, (const uint4 *)nullptr, p.lbase);
         else
-            hipLaunchKernelGGL((csr_stream_local<double, false, 2048, true>), dim3(lgrid), dim3(kBlock), lds, g_stream, lcount, lchunk,
-                               (const int *)nullptr, m->ldesc4, m->ldesc, m->lines, m->row_ptr, m->lcol, (const double *)m->val,
+            hipLaunchKernelGGL((csr_stream_local<double, false, 2048, true>), dim3(L.grid), dim3(kBlock), L.lds, g_stream, p.blocks, L.chunk,
+                               (const int *)nullptr, p.ldesc4, p.ldesc, p.lines, m->row_ptr, p.slot, (const double *)m->val,
                                (const double *)m->x, y, d, probe, (const int2 *)nullptr, (const unsigned *)nullptr,
-                               (const unsigned short *)nullptr, 0, (const int2 *)nullptr, (const uint4 *)nullptr, m->lbase);
+                               (const unsigned short *)nullptr, 0, (const int2 *)nullptr, (const uint4 *)nullptr, p.lbase);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
         if (e == hipSuccess) e = hipMemcpy(stamps_host, d, bytes, hipMemcpyDeviceToHost);
@@ -1168,7 +1162,7 @@ extern "C" int spmv_hip_csr_tile_digest(const spmv_csr_dev *m, unsigned long lon
 
 extern "C" int spmv_hip_csr_addresses(const spmv_csr_dev *m, unsigned long long *out) {
     if (!m || !out) return fail("csr_addresses: NULL argument");
-    const void *p[8] = {m->row_ptr, m->col, m->val, m->x, m->y, m->lcol, m->lines, m->ldesc4};
+    const void *p[8] = {m->row_ptr, m->col, m->val, m->x, m->y, m->xw.slot, m->xw.lines, m->xw.ldesc4};
     for (int i = 0; i < 8; ++i) out[i] = (unsigned long long)(uintptr_t)p[i];
     return 0;
 }
@@ -1189,10 +1183,12 @@ extern "C" int spmv_hip_csr_info(const spmv_csr_dev *m, spmv_dev_info *out) {
     const long long vb = m->value_bytes;
     // nnz (val + 4) + 4 (M + 1) + val M [y] + val N [x]
     out->algo_bytes = m->nz * (vb + 4) + 4LL * (m->M_local + 1) + vb * m->M_local + vb * m->N;
-    out->device_bytes = (long long)m->device_bytes;
-    out->local_blocks = m->local_blocks;
-    out->local_stage_lines = m->local_stage_lines;
-    out->local_lines = m->local_lines;
+    out->device_bytes = (long long)csr_device_bytes(m);
+    const XWindowPlan<int2> &p = m->xw;
+    const PatternPlan &pat = p.pat;
+    out->local_blocks = p.blocks;
+    out->local_stage_lines = p.stage_lines;
+    out->local_lines = p.lines_listed;
     const OwnTiles &t = m->tile;
     out->tile_blocks = t.blocks;
     out->tile_passes = t.passes;
@@ -1212,24 +1208,23 @@ extern "C" int spmv_hip_csr_info(const spmv_csr_dev *m, spmv_dev_info *out) {
     out->place_best_us = m->place_best_us;
     out->val_address = (unsigned long long)(uintptr_t)m->val;
     out->tile_expanded_entries = t.xe && t.expansion ? (long long)t.expansion->entries : 0;
-    out->pattern_slots = m->pat.ptab ? m->pat.slots : 0;
-    out->pattern_with_us = m->pat.with_us;
-    out->pattern_without_us = m->pat.without_us;
-    out->pattern_segment_max = m->pat.ptab ? 16 * m->pat.seg_max : 0;
-    out->pattern_segment_cap = 16 * m->pat.seg_cap;
-    out->pattern_table_rows = m->pat.ptab ? m->pat.table_rows : 0;
-    out->pattern_segments_stored = m->pat.ptab && m->pat.pseg ? m->pat.seg_distinct : 0;
-    out->local_lists_stored = m->lbase ? m->lists_distinct : 0;
-    out->local_lines_stored = m->local_blocks > 0 ? (m->lbase ? m->lines_stored : m->local_lines) : 0;
-    out->stream_kernel = m->local_blocks > 0 ? 1 : t.blocks > 0 ? 3 : csr_short_rows(m) ? 2 : 0;
-    if (m->local_blocks > 0)  // (a pattern plan: the tables and 4 bytes per row instead of 2 bytes per entry)
+    out->pattern_slots = pat.ptab ? pat.slots : 0;
+    out->pattern_with_us = pat.with_us;
+    out->pattern_without_us = pat.without_us;
+    out->pattern_segment_max = pat.ptab ? 16 * pat.seg_max : 0;
+    out->pattern_segment_cap = 16 * pat.seg_cap;
+    out->pattern_table_rows = pat.ptab ? pat.table_rows : 0;
+    out->pattern_segments_stored = pat.ptab && pat.pseg ? pat.seg_distinct : 0;
+    out->local_lists_stored = p.lists_stored;
+    out->local_lines_stored = p.lines_stored;
+    out->stream_kernel = p.blocks > 0 ? 1 : t.blocks > 0 ? 3 : csr_short_rows(m) ? 2 : 0;
+    if (p.blocks > 0)  // (a pattern plan: the tables and 4 bytes per row instead of 2 bytes per entry)
         // (a pattern plan: the segments instead of the slots; a block whose segment did not fit reads its table, rinfo
         // and row_ptr -- counted as its share of the tables)
-        out->stream_bytes = m->nz * vb + (m->pat.ptab ? 16 * m->pat.seg_total + 8LL * m->local_blocks +
-                                                            (2 * m->pat.slots + 8LL * m->M_local) * m->pat.table_rows / std::max(1, m->M_local)
-                                                  : 2 * m->nz + 4LL * (m->M_local + 1)) +
-                            (m->lbase ? 4 * m->lines_stored + 4LL * m->local_blocks : 4 * m->local_lines) +
-                            24LL * m->local_blocks + vb * m->M_local + vb * m->N;
+        out->stream_bytes = m->nz * vb + (pat.ptab ? 16 * pat.seg_total + 8LL * p.blocks +
+                                                         (2 * pat.slots + 8LL * m->M_local) * pat.table_rows / std::max(1, m->M_local)
+                                                   : 2 * m->nz + 4LL * (m->M_local + 1)) +
+                            4 * p.lines_stored + (p.lbase ? 4LL * p.blocks : 0) + 24LL * p.blocks + vb * m->M_local + vb * m->N;
     else if (t.blocks > 0) {  // tiles: 4-byte column + 2-byte key + value per (padded) entry; rows beyond the limit as CSR
         // a tier's entries and descriptors
         auto tier_bytes = [vb](const TileTier &tier) { return tier.padded * (vb + 6) - (tier.packed ? 2 : 0) * tier.staged + 16LL * tier.passes; };
@@ -1290,35 +1285,26 @@ void launch_split_rows(const spmv_csr_dev *m, int num_pieces, const int4 *pieces
 // the x-window kernel over all blocks (part < 0) or the interior / boundary sub-list (part 0 / 1, csr_launch_part)
 template <typename T>
 void launch_x_window(const spmv_csr_dev *m, const T *x, T *y, hipStream_t s, int part) {
-    // runs of 16 neighbouring blocks per XCD: each L2 keeps its own window of x lines
-    // (measured flat from 8 to 128 on three matrices); stream_xcd overrides
-    const int lcount = part < 0 ? m->local_blocks : part == 0 ? m->num_interior : m->num_boundary;
+    const XWindowPlan<int2> &p = m->xw;
+    const PatternPlan &pat = p.pat;
+    const int lcount = part < 0 ? p.blocks : part == 0 ? m->num_interior : m->num_boundary;
     const int *lids = part < 0 ? nullptr : part == 0 ? m->interior_ids : m->boundary_ids;
-    const int lchunk = g_stream_xcd < 0 ? (lcount + 7) / 8 : (g_stream_xcd ? g_stream_xcd : 16);
-    const int lgrid = lchunk > 0 ? (lcount + 8 * lchunk - 1) / (8 * lchunk) * (8 * lchunk) : lcount;
     if (lcount <= 0) return;
-    const size_t lds = std::max((size_t)m->local_cap * sizeof(T), (size_t)m->local_stage_lines * kLineBytes);
-    // a pattern plan: the slots are rebuilt in LDS (behind the stage) from the block's pattern table, not read
-    // entry by entry
-    const bool patterns = m->pat.ptab && g_local_patterns != 0;
-    const size_t pat_lds = lds + ((size_t)m->local_cap + 8) * sizeof(unsigned short) + (size_t)m->pat.seg_max * sizeof(uint4);
-    // streamed-once hint only when the matrix cannot live in the 256 MiB Infinity Cache anyway
-    // (cant-like, 53 MB: 10.9 us without it, 11.7 us with; fem-large: 160 vs 151 us)
-    const bool lnt = g_local_nt < 0 ? m->nz * (long long)(sizeof(T) + 2) > (128LL << 20) : g_local_nt != 0;
+    const XWindowLaunch L = p.launch_shape(lcount, m->local_cap, (int)sizeof(T), m->nz);
     with_value<1024, 3072, 2048>(m->local_cap, [&](auto cap) {
-        with_flag(lnt, [&](auto nt) {
+        with_flag(L.nt, [&](auto nt) {
             constexpr int CAP = decltype(cap)::value;
             constexpr bool NT = decltype(nt)::value;
-            if (patterns)
-                hipLaunchKernelGGL((csr_stream_local<T, NT, CAP, false, true>), dim3(lgrid), dim3(kBlock), pat_lds, s, lcount, lchunk,
-                                   lids, m->ldesc4, m->ldesc, m->lines, m->row_ptr, m->lcol, (const T *)m->val, x, y,
-                                   (unsigned long long *)nullptr, 0, m->pat.pdesc, m->pat.rinfo, m->pat.ptab, (int)lds, m->pat.sdesc,
-                                   (const uint4 *)m->pat.pseg, m->lbase);
+            if (L.patterns)
+                hipLaunchKernelGGL((csr_stream_local<T, NT, CAP, false, true>), dim3(L.grid), dim3(kBlock), L.pat_lds, s, lcount, L.chunk,
+                                   lids, p.ldesc4, p.ldesc, p.lines, m->row_ptr, p.slot, (const T *)m->val, x, y,
+                                   (unsigned long long *)nullptr, 0, pat.pdesc, pat.rinfo, pat.ptab, (int)L.lds, pat.sdesc,
+                                   (const uint4 *)pat.pseg, p.lbase);
             else
-                hipLaunchKernelGGL((csr_stream_local<T, NT, CAP>), dim3(lgrid), dim3(kBlock), lds, s, lcount, lchunk, lids,
-                                   m->ldesc4, m->ldesc, m->lines, m->row_ptr, m->lcol, (const T *)m->val, x, y,
+                hipLaunchKernelGGL((csr_stream_local<T, NT, CAP>), dim3(L.grid), dim3(kBlock), L.lds, s, lcount, L.chunk, lids,
+                                   p.ldesc4, p.ldesc, p.lines, m->row_ptr, p.slot, (const T *)m->val, x, y,
                                    (unsigned long long *)nullptr, 0, (const int2 *)nullptr, (const unsigned *)nullptr,
-                                   (const unsigned short *)nullptr, 0, (const int2 *)nullptr, (const uint4 *)nullptr, m->lbase);
+                                   (const unsigned short *)nullptr, 0, (const int2 *)nullptr, (const uint4 *)nullptr, p.lbase);
         });
     });
 }
@@ -1529,14 +1515,15 @@ int csr_launch_part(const spmv_csr_dev *m, int part, const void *x, void *y, hip
 // The handle's line lists on the host, whichever way they are stored: ld[b] = {first id in `lines`, ids}, base[b] = what
 // block b adds to its ids (0 where the lists hold absolute ids).
 int csr_lines_to_host(const spmv_csr_dev *m, std::vector<int2> &ld, std::vector<int> &lines, std::vector<int> &base) {
-    const size_t B = (size_t)m->local_blocks;
+    const XWindowPlan<int2> &p = m->xw;
+    const size_t B = (size_t)p.blocks;
     ld.resize(B);
     base.assign(B, 0);
-    lines.resize((size_t)(m->lbase ? m->lines_stored : m->local_lines));
+    lines.resize((size_t)p.lines_stored);
     HIP_TRY(hipStreamSynchronize(g_stream));
-    if (B) HIP_TRY(hipMemcpy(ld.data(), m->ldesc, B * sizeof(int2), hipMemcpyDeviceToHost));
-    if (B && m->lbase) HIP_TRY(hipMemcpy(base.data(), m->lbase, B * sizeof(int), hipMemcpyDeviceToHost));
-    if (!lines.empty()) HIP_TRY(hipMemcpy(lines.data(), m->lines, lines.size() * sizeof(int), hipMemcpyDeviceToHost));
+    if (B) HIP_TRY(hipMemcpy(ld.data(), p.ldesc, B * sizeof(int2), hipMemcpyDeviceToHost));
+    if (B && p.lbase) HIP_TRY(hipMemcpy(base.data(), p.lbase, B * sizeof(int), hipMemcpyDeviceToHost));
+    if (!lines.empty()) HIP_TRY(hipMemcpy(lines.data(), p.lines, lines.size() * sizeof(int), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -1554,13 +1541,13 @@ static int csr_split_interior_body(spmv_csr_dev *m, long long *counts) {
     m->num_interior = m->num_boundary = 0;
     m->have_split = false;
     long long e_in = 0, e_out = m->nz;
-    if (m->local_blocks > 0) {
-        const int B = m->local_blocks;
+    if (m->xw.blocks > 0) {
+        const int B = m->xw.blocks;
         std::vector<int2> ld;
         std::vector<int4> d4((size_t)B);
         std::vector<int> lines, lbase;
         if (csr_lines_to_host(m, ld, lines, lbase)) return -1;
-        HIP_TRY(hipMemcpy(d4.data(), m->ldesc4, d4.size() * sizeof(int4), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(d4.data(), m->xw.ldesc4, d4.size() * sizeof(int4), hipMemcpyDeviceToHost));
         const int per_line = kLineBytes / m->value_bytes;
         const long long own_lo = m->row0, own_hi = (long long)m->row0 + m->M_local;  // [lo, hi) of x
         std::vector<int> in_ids, out_ids;

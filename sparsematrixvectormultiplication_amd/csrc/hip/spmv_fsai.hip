@@ -67,7 +67,7 @@ struct BuildArrays {
 // the plan a handle got: 0 the gather kernels, 1 an x-window plan, 2 an x-window plan with a pattern plan, 3 csr_tile
 int plan_of(const spmv_csr_dev *m) {
     if (!m) return 0;
-    return m->local_blocks > 0 ? (m->pat.ptab ? 2 : 1) : m->tile.blocks > 0 ? 3 : 0;
+    return m->xw.blocks > 0 ? (m->xw.pat.ptab ? 2 : 1) : m->tile.blocks > 0 ? 3 : 0;
 }
 
 template <typename T>

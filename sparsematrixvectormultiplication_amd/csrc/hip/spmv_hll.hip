@@ -61,13 +61,13 @@ namespace {
 // Windows for hll_lds_local: hll_build_blocks' cut at `cap` slots with the line limit on top
 // (see csr_build_local).  ja is the flat host slab.  false: keep the gather kernel.
 bool hll_build_local(int M, int N, const long long *off, const int *mz, const int *ja, long long slots_padded,
-                     int cap, int lines_max, const std::vector<int4> &baseline, LocalPlan &plan) {
+                     int cap, int lines_max, const std::vector<int4> &baseline, LocalPlan<int4> &plan) {
     constexpr int line_shift = 4;  // fp64: 16 per 128-byte line
     const int total_lines = (int)(((long long)N + 15) >> line_shift);
     std::vector<int> stamp((size_t)total_lines + 1, -1), rank((size_t)total_lines + 1, 0), cur;
     plan.lcol.assign((size_t)slots_padded + kPad, 0);
     plan.desc.clear();
-    plan.hll_ldesc.clear();
+    plan.ldesc.clear();
     plan.lines.clear();
     int widest = 0;
     auto start_of = [&](int r) { return off[r / kHack] + (long long)(r % kHack) * mz[r / kHack]; };
@@ -104,8 +104,8 @@ bool hll_build_local(int M, int N, const long long *off, const int *mz, const in
         for (long long k = s0; k < start_of(r1 - 1) + mz[(r1 - 1) / kHack]; ++k)
             plan.lcol[k] = (unsigned short)((rank[ja[k] >> line_shift] << line_shift) | (ja[k] & 15));
         plan.desc.push_back(int4{r, r1 - r, (int)(s0 & 0xffffffffLL), (int)(s0 >> 32)});
-        plan.hll_ldesc.push_back(int4{(int)plan.lines.size(), (int)cur.size(),
-                                      (int)(start_of(r1 - 1) + mz[(r1 - 1) / kHack] - base), 0});
+        plan.ldesc.push_back(int4{(int)plan.lines.size(), (int)cur.size(),
+                                  (int)(start_of(r1 - 1) + mz[(r1 - 1) / kHack] - base), 0});
         plan.lines.insert(plan.lines.end(), cur.begin(), cur.end());
         widest = std::max(widest, (int)cur.size());
         r = r1;
@@ -159,13 +159,13 @@ __global__ __launch_bounds__(kBlock) void hll_row_segments(int num_blocks, const
 
 // row_seg for the rows of the x-window plan's windows (hack tables and window descriptors are on the device)
 int hll_fill_row_segments(spmv_hll_dev *m) {
-    HIP_TRY(hipMalloc((void **)&m->row_seg, std::max<size_t>((size_t)m->M, 1) * sizeof(unsigned)));
-    HIP_TRY(hipMemsetAsync(m->row_seg, 0, std::max<size_t>((size_t)m->M, 1) * sizeof(unsigned), g_stream));
-    hipLaunchKernelGGL(hll_row_segments, dim3(m->local_blocks), dim3(kBlock), 0, g_stream, m->local_blocks, m->ldesc4,
-                       m->hack_off, m->maxnz, m->row_seg);
+    XWindowPlan<int4> &p = m->xw;
+    HIP_TRY(hipMalloc((void **)&p.row_seg, std::max<size_t>((size_t)m->M, 1) * sizeof(unsigned)));
+    HIP_TRY(hipMemsetAsync(p.row_seg, 0, std::max<size_t>((size_t)m->M, 1) * sizeof(unsigned), g_stream));
+    hipLaunchKernelGGL(hll_row_segments, dim3(p.blocks), dim3(kBlock), 0, g_stream, p.blocks, p.ldesc4, m->hack_off, m->maxnz,
+                       p.row_seg);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(g_stream));
-    m->device_bytes += (size_t)m->M * sizeof(unsigned);
     return 0;
 }
 
@@ -213,27 +213,17 @@ int hll_finish_handle(spmv_hll_dev *m, int total_rows, int N, const std::vector<
         if (e == hipSuccess) e = hipMemset(m->y, 0, std::max<size_t>((size_t)m->M_total, 1) * sizeof(double));
         if (e != hipSuccess) rc = fail("hipMalloc(x/y) failed: %s", hipGetErrorString(e));
     }
-    m->device_bytes = off.size() * 8 + mz.size() * 4 + ((size_t)off[H] + kPad) * 12 + hdesc.size() * 16 +
-                      long_windows.size() * 4 + ((size_t)N + (size_t)total_rows) * 8;
+    m->rest_bytes = off.size() * 8 + mz.size() * 4 + ((size_t)off[H] + kPad) * 12 + hdesc.size() * 16 +
+                    long_windows.size() * 4 + ((size_t)N + (size_t)total_rows) * 8;
     // the x-window kernel: windows of 2048 slots, 16-bit local JA (needs the slab on the host)
     if (!rc && ja_host && g_stream_local && true_slots > 0) {
         std::vector<int4> plain;
-        LocalPlan local;
+        LocalPlan<int4> local;
         hll_build_blocks(total_rows, H, off.data(), mz.data(), 2048, plain);
-        if (hll_build_local(total_rows, N, off.data(), mz.data(), ja_host, off[H], 2048, kLocalLinesMax, plain, local)) {
-            rc |= upload_array(&m->ldesc4, local.desc.data(), local.desc.size(), 1);
-            if (!rc) rc |= upload_array(&m->ldesc, local.hll_ldesc.data(), local.hll_ldesc.size(), 1);
-            if (!rc) rc |= upload_array(&m->lines, local.lines.data(), local.lines.size(), 0);
-            if (!rc) rc |= upload_array(&m->lja, local.lcol.data(), local.lcol.size(), 0);
-            if (!rc) {
-                m->local_blocks = (int)local.desc.size();
-                m->local_stage_lines = local.stage_lines;
-                m->local_lines = (long long)local.lines.size() - kLocalLinesMax;
-                m->device_bytes += local.desc.size() * 32 + local.lines.size() * 4 + local.lcol.size() * 2;
-            }
-        }
+        if (hll_build_local(total_rows, N, off.data(), mz.data(), ja_host, off[H], 2048, kLocalLinesMax, plain, local))
+            rc = m->xw.upload(local);
     }
-    if (!rc && m->local_blocks > 0) rc = hll_fill_row_segments(m);
+    if (!rc && m->xw.blocks > 0) rc = hll_fill_row_segments(m);
     // no x-window plan (columns too scattered): the 2-D tiles over the slab's rows, padding slots included -- the
     // rows of hack h are maxnz[h] slots each, starting at hack_off[h] + i * maxnz[h] (needs the slab on the host)
     // (auto: not for a skewed slab -- a hack whose rows are 16 times the mean is 32 rows of mostly padding, and tiles
@@ -245,7 +235,7 @@ int hll_finish_handle(spmv_hll_dev *m, int total_rows, int N, const std::vector<
     }
     // (the plan is built on the device from the slab there; the host copies, where the caller has them, are the fallback)
     const bool slab_at_hand = (ja_host && as_host) || (g_tile_plan_on_device && m->JA && m->AS);
-    if (!rc && !skewed && m->local_blocks == 0 && slab_at_hand && true_slots > 0 && off[H] < 0x7fffffffLL) {
+    if (!rc && !skewed && m->xw.blocks == 0 && slab_at_hand && true_slots > 0 && off[H] < 0x7fffffffLL) {
         std::vector<int> row_begin((size_t)total_rows), row_len((size_t)total_rows);
         for (int r = 0; r < total_rows; ++r) {
             const int h = r / kHack;
@@ -254,7 +244,6 @@ int hll_finish_handle(spmv_hll_dev *m, int total_rows, int N, const std::vector<
         }
         rc = csr_tiles_from_rows_f64(total_rows, m->M_total, row0, N, row_begin.data(), row_len.data(), true_slots, ja_host,
                                      as_host, &m->tiles, m->JA, m->AS);
-        if (!rc && m->tiles) m->device_bytes += m->tiles->device_bytes;
     }
     const double mean = total_rows ? (double)true_slots / total_rows : 0.0;
     m->lanes_per_row = std::min(32, std::max(2, pow2_floor(std::max(2, (int)(mean / 2.0 + 0.5)))));
@@ -266,7 +255,7 @@ int hll_finish_handle(spmv_hll_dev *m, int total_rows, int N, const std::vector<
     int widest_hack = 0;
     for (int h = 0; h < H; ++h) widest_hack = std::max(widest_hack, mz[(size_t)h]);
     m->auto_variant = SPMV_HLL_LDS;
-    if (m->local_blocks == 0 && !m->tiles && true_slots < (20LL << 20) && widest_hack <= std::max(64.0, 8.0 * mean))
+    if (m->xw.blocks == 0 && !m->tiles && true_slots < (20LL << 20) && widest_hack <= std::max(64.0, 8.0 * mean))
         m->auto_variant = SPMV_HLL_SUBWAVE;
     return rc;
 }
@@ -276,15 +265,14 @@ int hll_finish_handle(spmv_hll_dev *m, int total_rows, int N, const std::vector<
 // The pattern plan (tables only) and the searches of a finished handle (upload_ops.hpp).  The placement of AS where it is
 // large and streamed by the slab's own kernels (csr_tile over the slab's rows streams its own re-ordered copy).
 static void hll_upload_searches(spmv_hll_dev *m) {
-    (void)build_pattern_tables<true>(m->pat, m->local_blocks, m->M, m->slots, 8, m->ldesc4, nullptr, m->row_seg, m->lja);
-    m->device_bytes += m->pat.bytes(m->M, m->local_blocks);
+    (void)build_pattern_tables<true>(m->xw, m->M, m->slots, 8, nullptr);
     size_t bytes = 0;
-    bool place = m->AS && (size_t)m->slots * sizeof(double) >= kPlaceMinBytes && (m->local_blocks > 0 || !m->tiles);
+    bool place = m->AS && (size_t)m->slots * sizeof(double) >= kPlaceMinBytes && (m->xw.blocks > 0 || !m->tiles);
     if (place && (hipMemPtrGetInfo(m->AS, &bytes) != hipSuccess || bytes < (size_t)m->slots * sizeof(double))) {
         (void)hipGetLastError();
         place = false;
     }
-    upload_searches(m, m->M, place ? &m->AS : nullptr, bytes,
+    upload_searches(m, place ? &m->AS : nullptr, bytes,
                     [m] { return hll_launch(m, SPMV_HLL_AUTO, m->x, m->y, g_stream); });
 }
 
@@ -315,7 +303,7 @@ static int spmv_hip_hll_plan_check_body(const HLLMatrix *hll, int total_rows, in
     }
     auto start_of = [&](int r) { return off[r / kHack] + (long long)(r % kHack) * mz[r / kHack]; };
     std::vector<int4> plain;
-    LocalPlan plan;
+    LocalPlan<int4> plan;
     hll_build_blocks(total_rows, H, off.data(), mz.data(), 2048, plain);
     int next = 0;
     for (const int4 &d : plain) {  // windows tile the rows in order
@@ -330,7 +318,7 @@ static int spmv_hip_hll_plan_check_body(const HLLMatrix *hll, int total_rows, in
         next = 0;
         for (size_t b = 0; b < plan.desc.size(); ++b) {
             const int4 &d = plan.desc[b];
-            const int4 &ld = plan.hll_ldesc[b];
+            const int4 &ld = plan.ldesc[b];
             if (d.x != next || d.y <= 0 || d.y > kStreamRowsCap) return fail("hll_plan_check: x-window window %zu out of order", b);
             next = d.x + d.y;
             const long long s0 = ((long long)d.w << 32) | (unsigned)d.z, base = s0 & ~1LL;
@@ -381,7 +369,7 @@ int hll_plan_on_device(spmv_hll_dev *m, int total_rows, const std::vector<long l
         len[w] = (int)(end - s0);
         count[w] = (int)(end - (s0 & ~1LL));
     }
-    return plan_on_device<4>(m, m->JA, (size_t)off.back(), win, begin, len, m->lja, m->ldesc,
+    return plan_on_device<4>(m->xw, m->JA, (size_t)off.back(), win, begin, len,
                              [&](int w, int first, int n) { return int4{first, n, count[w], 0}; }, nl);
 }
 
@@ -445,9 +433,6 @@ static int spmv_hip_hll_upload_part_body(const HLLMatrix *hll, int total_rows, i
     }
     if (!rc) rc |= hll_finish_handle(m, rows, N, off, mz, true_slots, true, planned ? nullptr : ja.data(), total_rows, row0,
                                      as.data());
-    if (!rc && planned)
-        m->device_bytes += (size_t)m->local_blocks * 32 + ((size_t)m->local_lines + kLocalLinesMax) * 4 +
-                           ((size_t)S + kPad) * 2;
     if (rc) {
         spmv_hip_hll_free(m);
         return -1;
@@ -535,9 +520,6 @@ static int spmv_hip_hll_from_csr_body(const spmv_csr_dev *csr, spmv_hll_dev **ou
         }
         rc = hll_finish_handle(m, M, N, off, mz, true_slots, false, ja_host.empty() ? nullptr : ja_host.data(),
                                csr->M_total, csr->row0, as_host.empty() ? nullptr : as_host.data());
-        if (!rc && planned)
-            m->device_bytes += (size_t)m->local_blocks * 32 + ((size_t)m->local_lines + kLocalLinesMax) * 4 +
-                               ((size_t)S + kPad) * 2;
     } while (0);
     if (rc) {
         spmv_hip_hll_free(m);
@@ -576,12 +558,7 @@ extern "C" void spmv_hip_hll_free(spmv_hll_dev *m) {
     (void)hipFree(m->AS);
     (void)hipFree(m->hdesc);
     (void)hipFree(m->long_windows);
-    (void)hipFree(m->ldesc4);
-    (void)hipFree(m->ldesc);
-    (void)hipFree(m->lines);
-    (void)hipFree(m->lja);
-    (void)hipFree(m->row_seg);
-    m->pat.release();
+    m->xw.release();
     spmv_hip_csr_free(m->tiles);
     (void)hipFree(m->x);
     (void)hipFree(m->y);
@@ -613,16 +590,17 @@ extern "C" int spmv_hip_hll_info(const spmv_hll_dev *m, spmv_dev_info *out) {
     out->hacks = m->hacks;
     // S (val + 4) + 12 H + val (M + N)
     out->algo_bytes = m->slots * 12 + 12LL * m->hacks + 8LL * ((long long)m->M + m->N);
-    out->device_bytes = (long long)m->device_bytes;
-    out->local_blocks = m->local_blocks;
+    out->device_bytes = (long long)hll_device_bytes(m);
+    const XWindowPlan<int4> &p = m->xw;
+    out->local_blocks = p.blocks;
     out->place_tries = m->place_tries;
     out->place_first_us = m->place_first_us;
     out->place_best_us = m->place_best_us;
     out->val_address = (unsigned long long)(uintptr_t)m->AS;
-    out->pattern_slots = m->pat.ptab ? m->pat.slots : 0;
-    out->pattern_with_us = m->pat.with_us;
-    out->pattern_without_us = m->pat.without_us;
-    out->stream_kernel = m->local_blocks > 0 ? 1 : m->tiles ? 2 : 0;
+    out->pattern_slots = p.pat.ptab ? p.pat.slots : 0;
+    out->pattern_with_us = p.pat.with_us;
+    out->pattern_without_us = p.pat.without_us;
+    out->stream_kernel = p.blocks > 0 ? 1 : m->tiles ? 2 : 0;
     if (m->tiles) {
         spmv_dev_info t;
         if (spmv_hip_csr_info(m->tiles, &t) == 0) {
@@ -638,11 +616,11 @@ extern "C" int spmv_hip_hll_info(const spmv_hll_dev *m, spmv_dev_info *out) {
             out->stream_bytes = t.stream_bytes + 12LL * m->hacks;
         }
     }
-    out->local_stage_lines = m->local_stage_lines;
-    out->local_lines = m->local_lines;
-    if (m->local_blocks > 0)  // (a pattern plan: the tables and 4 bytes per row instead of 2 bytes per slot)
-        out->stream_bytes = m->slots * 8 + (m->pat.ptab ? 2 * m->pat.slots + 4LL * m->M + 8LL * m->local_blocks : 2 * m->slots) +
-                            4 * m->local_lines + 32LL * m->local_blocks + 12LL * m->hacks + 8LL * ((long long)m->M + m->N);
+    out->local_stage_lines = p.stage_lines;
+    out->local_lines = p.lines_listed;
+    if (p.blocks > 0)  // (a pattern plan: the tables and 4 bytes per row instead of 2 bytes per slot)
+        out->stream_bytes = m->slots * 8 + (p.pat.ptab ? 2 * p.pat.slots + 4LL * m->M + 8LL * p.blocks : 2 * m->slots) +
+                            4 * p.lines_listed + 32LL * p.blocks + 12LL * m->hacks + 8LL * ((long long)m->M + m->N);
     return 0;
 }
 
@@ -695,24 +673,19 @@ int hll_launch(const spmv_hll_dev *m, int variant, const double *x, double *y_fu
             }
             break;
         case SPMV_HLL_LDS: {
-            if (x_window_runs(m->local_blocks, x)) {
-                const int lchunk = g_stream_xcd < 0 ? (m->local_blocks + 7) / 8 : (g_stream_xcd ? g_stream_xcd : 16);
-                const int lgrid = (m->local_blocks + 8 * lchunk - 1) / (8 * lchunk) * (8 * lchunk);
-                const size_t llds = std::max((size_t)2048 * sizeof(double), (size_t)m->local_stage_lines * kLineBytes);
-                const bool lnt = g_local_nt < 0 ? m->slots * 10 > (128LL << 20) : g_local_nt != 0;
-                // a pattern plan: the windows' slots are rebuilt in LDS (behind the stage), lja is not read
-                const bool patterns = m->pat.ptab && g_local_patterns != 0;
-                const size_t pat_lds = llds + ((size_t)2048 + 8) * sizeof(unsigned short);
-                with_flag(lnt, [&](auto nt) {
+            const XWindowPlan<int4> &p = m->xw;
+            if (x_window_runs(p.blocks, x)) {
+                // (a pattern plan: tables only, so no segment behind the rebuilt slots)
+                const XWindowLaunch L = p.launch_shape(p.blocks, 2048, 8, m->slots);
+                with_flag(L.nt, [&](auto nt) {
                     constexpr bool NT = decltype(nt)::value;
-                    if (patterns)
-                        hipLaunchKernelGGL((hll_lds_local<double, NT, 2048, true>), dim3(lgrid), dim3(kBlock), pat_lds, s,
-                                           m->local_blocks, lchunk, m->ldesc4, m->ldesc, m->lines, m->row_seg,
-                                           m->lja, m->AS, x, y, m->pat.pdesc, m->pat.rinfo, m->pat.ptab, (int)llds);
+                    if (L.patterns)
+                        hipLaunchKernelGGL((hll_lds_local<double, NT, 2048, true>), dim3(L.grid), dim3(kBlock), L.pat_lds, s,
+                                           p.blocks, L.chunk, p.ldesc4, p.ldesc, p.lines, p.row_seg, p.slot, m->AS, x, y,
+                                           p.pat.pdesc, p.pat.rinfo, p.pat.ptab, (int)L.lds);
                     else
-                        hipLaunchKernelGGL((hll_lds_local<double, NT, 2048>), dim3(lgrid), dim3(kBlock), llds, s,
-                                           m->local_blocks, lchunk, m->ldesc4, m->ldesc, m->lines, m->row_seg,
-                                           m->lja, m->AS, x, y);
+                        hipLaunchKernelGGL((hll_lds_local<double, NT, 2048>), dim3(L.grid), dim3(kBlock), L.lds, s, p.blocks,
+                                           L.chunk, p.ldesc4, p.ldesc, p.lines, p.row_seg, p.slot, m->AS, x, y);
                 });
                 break;
             }

@@ -6,6 +6,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <array>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -208,6 +209,90 @@ struct PatternPlan {
         seg_distinct = 0;
     }
 };
+// What a host builder of the x-window plan makes (csr_build_local, spmv_csr.hip; hll_build_local, spmv_hll.hip): blocks cut
+// like the gather kernel's with one more limit, the number of distinct x lines (128 bytes of x each) a block touches.
+// Per block the ascending list of those lines, per entry its 16-bit slot (rank of its line in the list * elements per
+// line + column % elements per line).  Desc: the kernel's line descriptor, as in XWindowPlan.
+template <typename Desc>
+struct LocalPlan {
+    std::vector<unsigned char> split;  // CSR: rows handed to the split-row kernels (too many x lines)
+    std::vector<int4> desc;
+    std::vector<Desc> ldesc;
+    std::vector<int> lines;            // kLocalLinesMax zeros behind the last list
+    std::vector<unsigned short> lcol;  // [slots + kPad]
+    int stage_lines = 0;
+};
+// how an x-window kernel is launched over some of a plan's blocks (XWindowPlan::launch_shape)
+struct XWindowLaunch {
+    int chunk, grid;      // blocks per XCD run; workgroups: whole runs on all 8 XCDs (one past the last block returns at once)
+    size_t lds, pat_lds;  // dynamic LDS without / with the pattern plan: the stage; behind it the slots and the widest segment
+    bool nt, patterns;    // non-temporal loads of the streamed arrays; the PAT instantiation
+};
+// The x-window plan of a handle (csr_stream_local, hll_lds_local): own blocks whose x lines are staged in LDS, every entry
+// a 16-bit slot in its block's staged lines.  One type for both handles; Desc is the kernel's line descriptor: int2
+// {first line in `lines`, lines} for CSR, int4 {first line, lines, slots of the window from its even base, 0} for HLL.
+// The arrays are listed ONCE, in arrays(): release() frees that list, bytes() is what they were allocated with.
+template <typename Desc>
+struct XWindowPlan {
+    int4 *ldesc4 = nullptr;           // [blocks] CSR: like desc; HLL: like hdesc
+    Desc *ldesc = nullptr;            // [blocks]
+    int *lines = nullptr;             // [lines_stored + kLocalLinesMax] x line ids, block after block, ascending inside a block
+    int *lbase = nullptr;             // [blocks] shared line lists ("local_share"): a block's list counts from its first
+                                      // line, lbase[b]; equal lists are stored once.  nullptr: the lists hold absolute ids
+    unsigned short *slot = nullptr;   // [slots + kPad] slot of each entry in its block's staged lines
+    unsigned *row_seg = nullptr;      // HLL: [rows] a row's (first slot in its window | slots << 16)
+    PatternPlan pat;                  // the pattern plan of the blocks (the kernel then does not read `slot`)
+    int blocks = 0;                   // 0: no plan (not profitable / not possible)
+    int stage_lines = 0;              // LDS stage: most lines any block lists, in steps of 32
+    long long lines_listed = 0;       // line ids the blocks list ...
+    long long lines_stored = 0;       // ... and those `lines` holds: fewer once equal lists are shared
+    long long lists_stored = 0;       // the distinct lists then; 0: every block has its own
+    long long slots = 0;              // entries `slot` was allocated for
+
+    std::array<void **, 6> arrays() {
+        return {(void **)&ldesc4, (void **)&ldesc, (void **)&lines, (void **)&lbase, (void **)&slot, (void **)&row_seg};
+    }
+    void release() {
+        for (void **p : arrays()) (void)hipFree(*p);
+        pat.release();
+        *this = XWindowPlan();
+    }
+    // what the plan holds on the device, with the pads it was allocated with (rows: the handle's)
+    size_t bytes(long long rows) const {
+        if (!ldesc4) return 0;
+        return (size_t)blocks * (16 + sizeof(Desc) + (lbase ? 4 : 0)) + ((size_t)lines_stored + kLocalLinesMax) * 4 +
+               ((size_t)slots + kPad) * 2 + (row_seg ? (size_t)rows * 4 : 0) + pat.bytes(rows, blocks);
+    }
+    // a host-built plan to the device; -1: HIP error (what is allocated by then goes with the handle)
+    int upload(const LocalPlan<Desc> &p) {
+        if (upload_array(&ldesc4, p.desc.data(), p.desc.size(), 1) || upload_array(&ldesc, p.ldesc.data(), p.ldesc.size(), 1) ||
+            upload_array(&lines, p.lines.data(), p.lines.size(), 0) || upload_array(&slot, p.lcol.data(), p.lcol.size(), 0))
+            return -1;
+        blocks = (int)p.desc.size();
+        stage_lines = p.stage_lines;
+        lines_listed = lines_stored = (long long)p.lines.size() - kLocalLinesMax;
+        slots = (long long)p.lcol.size() - kPad;
+        return 0;
+    }
+    // the launch over `count` of the blocks, at a stage of `cap` entries of value_bytes each; entries: the handle's
+    XWindowLaunch launch_shape(int count, int cap, int value_bytes, long long entries) const {
+        XWindowLaunch L;
+        // runs of 16 neighbouring blocks per XCD: each L2 keeps its own window of x lines
+        // (measured flat from 8 to 128 on three matrices); stream_xcd overrides
+        L.chunk = g_stream_xcd < 0 ? (count + 7) / 8 : (g_stream_xcd ? g_stream_xcd : 16);
+        const int round = 8 * L.chunk;
+        L.grid = round > 0 ? (count + round - 1) / round * round : count;
+        L.lds = std::max((size_t)cap * (size_t)value_bytes, (size_t)stage_lines * kLineBytes);
+        // a pattern plan: the slots are rebuilt in LDS (behind the stage) from the block's segment or table, not read
+        // entry by entry
+        L.patterns = pat.ptab && g_local_patterns != 0;
+        L.pat_lds = L.lds + ((size_t)cap + 8) * sizeof(unsigned short) + (size_t)pat.seg_max * sizeof(uint4);
+        // streamed-once hint only when the matrix cannot live in the 256 MiB Infinity Cache anyway
+        // (cant-like, 53 MB: 10.9 us without it, 11.7 us with; fem-large: 160 vs 151 us)
+        L.nt = g_local_nt < 0 ? entries * (value_bytes + 2LL) > (128LL << 20) : g_local_nt != 0;
+        return L;
+    }
+};
 // The tile plans of a handle (csr_tile, tile_kernels.hpp): up to three tiers of the same kind of plan, launched by the
 // same kernel.  TileTier is what every tier has; each tier lists its device arrays ONCE, in arrays(): release() frees
 // that list and the digest (csr_tile_digest) hashes it, so an array cannot be in one and not in the other.
@@ -308,19 +393,8 @@ struct spmv_csr_dev {
     size_t spmm_partial_bytes = 0;
     int stream_cap = 2048;
     // stream kernel with the x window in LDS (csr_stream_local): own blocks, 16-bit local columns
-    int4 *ldesc4 = nullptr;           // [local_blocks] like desc
-    int2 *ldesc = nullptr;            // [local_blocks] {first line in `lines`, line count}
-    int *lines = nullptr;             // x line ids, block after block, ascending inside a block
-    int *lbase = nullptr;             // [local_blocks] shared line lists ("local_share"): a block's list counts from its first
-                                      // line, lbase[b]; equal lists are stored once.  nullptr: the lists hold absolute ids
-    long long lines_stored = 0;       // ... then the line ids `lines` holds (local_lines: what the blocks list)
-    long long lists_distinct = 0;     // ... and the lists
-    unsigned short *lcol = nullptr;   // [nz + pad] slot of each entry in its block's staged lines
-    PatternPlan pat;                  // the pattern plan of the blocks (the kernel then does not read lcol)
-    int local_blocks = 0;            // 0: no plan (not profitable / not possible)
-    int local_stage_lines = 0;        // LDS stage: most lines any block lists, in steps of 32
+    XWindowPlan<int2> xw;
     int local_cap = 2048;
-    long long local_lines = 0;
     // N4 overlap: x-window blocks whose listed x lines all lie in this handle's own range of x (interior) / the rest
     int *interior_ids = nullptr, *boundary_ids = nullptr;
     int num_interior = 0, num_boundary = 0;
@@ -339,7 +413,7 @@ struct spmv_csr_dev {
     int lanes_per_row = 16;
     int auto_variant = SPMV_CSR_STREAM;
     int max_row = 0;
-    size_t device_bytes = 0;
+    size_t rest_bytes = 0;  // device memory but the x-window plan's (csr_device_bytes)
     int place_tries = 0;  // placement tuning at upload (tune_placement): placements timed, first / kept time
     float place_first_us = 0, place_best_us = 0;
     // arrays moved to a chosen address (spmv_hip_csr_relocate): the field points INTO `raw`, which is what gets freed
@@ -347,6 +421,9 @@ struct spmv_csr_dev {
     struct relocated { void **field; void *raw; size_t size; bool vmm = false; hipMemGenericAllocationHandle_t phys = {}; size_t mapped = 0; };
     std::vector<relocated> relocs;
 };
+
+// what info() reports as device_bytes: the x-window plan's bytes and the rest of the handle's
+inline size_t csr_device_bytes(const spmv_csr_dev *m) { return m->rest_bytes + m->xw.bytes(m->M_local); }
 
 struct spmv_hll_dev {
     int M = 0, N = 0, hacks = 0;  // rows / hacks HELD by this handle
@@ -362,40 +439,21 @@ struct spmv_hll_dev {
     int stage_slots = kHllCap;  // LDS stage of hll_lds: the largest workgroup, <= kHllCap
     int *long_windows = nullptr;  // [num_long_windows] hdesc windows of one row longer than the stage (SpMM: hll_spmm_row)
     int num_long_windows = 0;
-    // hll_lds_local (x window in LDS): own windows, 16-bit local JA
-    int4 *ldesc4 = nullptr;
-    int4 *ldesc = nullptr;  // {first line, lines, slots of the window from its even base, 0}
-    int *lines = nullptr;
-    unsigned short *lja = nullptr;
-    unsigned *row_seg = nullptr;   // [M] a row's (first slot in its window | slots << 16)
-    PatternPlan pat;               // the pattern plan of the windows (tables only): hll_lds_local<.., PAT> does not read lja
+    // hll_lds_local (x window in LDS): own windows, 16-bit local JA; row_seg is filled, the pattern plan has tables only
+    XWindowPlan<int4> xw;
     spmv_csr_dev *tiles = nullptr; // csr_tile over the slab's rows (padding slots included), when the slab gets no x-window plan
-    int local_blocks = 0, local_stage_lines = 0;
-    long long local_lines = 0;
     double *x = nullptr;
     double *y = nullptr;
     int lanes_per_row = 8;
     int auto_variant = SPMV_HLL_LDS;
-    size_t device_bytes = 0;
+    size_t rest_bytes = 0;  // device memory but the x-window plan's and the tile handle's (hll_device_bytes)
     int place_tries = 0;  // placement tuning at upload (tune_placement)
     float place_first_us = 0, place_best_us = 0;
 };
 
-// Blocks for csr_stream_local: csr_build_blocks' cut with one more limit, the number of
-// distinct x lines (1 << line_shift elements each) a block touches.  Fills, per block, the
-// ascending list of those lines and, per entry, its 16-bit slot (rank of its line in the
-// list * elements per line + column % elements per line).  Returns false when some row alone
-// needs more than lines_max lines, or when the line limit (rather than cap) decides so many
-// cuts that the blocks would run mostly empty: the caller then keeps the gather kernel.
-struct LocalPlan {
-    std::vector<unsigned char> split;  // CSR: rows handed to the split-row kernels (too many x lines)
-    std::vector<int4> desc;
-    std::vector<int4> hll_ldesc;  // HLL: {first line, lines, slots from the even base, 0}
-    std::vector<int2> ldesc;
-    std::vector<int> lines;
-    std::vector<unsigned short> lcol;
-    int stage_lines = 0;
-};
+inline size_t hll_device_bytes(const spmv_hll_dev *m) {
+    return m->rest_bytes + m->xw.bytes(m->M) + (m->tiles ? csr_device_bytes(m->tiles) : 0);
+}
 
 // spmv_csr.hip: a handle around device arrays that already hold the matrix (ownership passes to the handle
 // on success only); col / val carry kPad zeroed entries behind the last one

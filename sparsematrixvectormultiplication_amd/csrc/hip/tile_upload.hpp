@@ -422,7 +422,7 @@ int upload_own_tiles(spmv_csr_dev *m, const TileBuild<T> &tb) {
         if (adopt_or_upload(&t.rem_val, dev ? &dev->rem_val : nullptr, tiles.rem_val)) return -1;
         t.rem_rows = (int)rrow.size();
         t.rem_entries = (long long)tiles.rem_row.size();
-        m->device_bytes += rrow.size() * 8 + tiles.rem_row.size() * (4 + sizeof(T));
+        m->rest_bytes += rrow.size() * 8 + tiles.rem_row.size() * (4 + sizeof(T));
     }
     if (upload_array(&t.stream_block, tiles.stream_block.data(), tiles.stream_block.size(), 1)) return -1;
     if (upload_array(&t.sblock_rows, tiles.sblock_rows.data(), tiles.sblock_rows.size(), 1)) return -1;
@@ -434,7 +434,7 @@ int upload_own_tiles(spmv_csr_dev *m, const TileBuild<T> &tb) {
     t.lds_min = tb.scattered ? 84 * 1024 : 0;  // more than half a CU's LDS: one workgroup per CU
     t.num_long = (int)tb.tile_long.size();
     t.num_pieces = (int)tb.tile_pieces.size();
-    m->device_bytes += tcol_count * (4 + sizeof(T)) + tkey_count * 2 + tiles.pass_desc.size() * 16 + tiles.block_pass.size() * 4 +
+    m->rest_bytes += tcol_count * (4 + sizeof(T)) + tkey_count * 2 + tiles.pass_desc.size() * 16 + tiles.block_pass.size() * 4 +
                        (tb.tile_pieces.size() + tb.tile_long.size()) * 16;
     return 0;
 }
@@ -458,10 +458,10 @@ int upload_compact_tiles(spmv_csr_dev *m, const TierBuild<T> &b, CompactTiles &L
     const size_t slab_bytes = std::max<size_t>(1, b.work.size()) * (size_t)ltiles.rows_per_block * sizeof(T);
     hipError_t e = hipMalloc(&L.slab, slab_bytes);
     if (e != hipSuccess) return fail("hipMalloc(slabs) failed: %s", hipGetErrorString(e));
-    m->device_bytes += slab_bytes;
+    m->rest_bytes += slab_bytes;
     L.rows = (int)b.rows.size();
     L.items = (int)b.work.size();
-    m->device_bytes += ltcol_count * (4 + sizeof(T)) + ltkey_count * 2 + ltiles.pass_desc.size() * 16 + b.work.size() * 16 +
+    m->rest_bytes += ltcol_count * (4 + sizeof(T)) + ltkey_count * 2 + ltiles.pass_desc.size() * 16 + b.work.size() * 16 +
                        b.rows.size() * 8;
     return 0;
 }
@@ -496,7 +496,7 @@ int tile_upload_all(spmv_csr_dev *m, const TileBuild<T> &tb) {
         hipError_t e = hipMalloc(&t.xe, xe_bytes);
         if (e == hipSuccess) e = hipMemsetAsync(t.xe, 0, xe_bytes, g_stream);
         if (e != hipSuccess) return fail("hipMalloc(expanded x) failed: %s", hipGetErrorString(e));
-        m->device_bytes += xe_bytes + (slots + 64) * 2 + (slots + kTileChunkMax) * 4 + tb.tiles.plan.spass.size() * 16 +
+        m->rest_bytes += xe_bytes + (slots + 64) * 2 + (slots + kTileChunkMax) * 4 + tb.tiles.plan.spass.size() * 16 +
                            (size_t)t.expansion->chunks * 24 + (t.expansion->runs + t.expansion->groups) * 4;
     }
     if (tb.lt.have && upload_compact_tiles<T>(m, tb.lt, m->lt)) return -1;

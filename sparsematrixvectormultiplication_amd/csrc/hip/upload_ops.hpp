@@ -17,13 +17,13 @@ constexpr size_t kPlaceMinBytes = (size_t)128 << 20;  // value arrays from which
 
 // The x-window plan of the windows win[w] (plan_kernels.hpp), window w over idx[begin[w], begin[w] + len[w]) of the
 // device column array idx, at 1 << SHIFT columns per 128-byte line: the count pass, then -- when no window lists more
-// than kLocalLinesMax lines -- the line lists (m->lines), the 16-bit slots (`slot`, slots + kPad entries), the fill pass
-// and the windows' descriptors (m->ldesc4 = win; ldesc[w] = desc_of(w, first line, lines)).  nlines: every window's line
-// count.  1: the handle carries the plan; 0: some window lists too many lines; -1: HIP error.  Anything but 1 leaves
-// no plan behind.
-template <int SHIFT, typename H, typename D, typename Desc>
-int plan_on_device(H *m, const int *idx, size_t slots, const std::vector<int4> &win, const std::vector<long long> &begin,
-                   const std::vector<int> &len, unsigned short *&slot, D *&ldesc, Desc desc_of, std::vector<int> &nlines) {
+// than kLocalLinesMax lines -- the line lists, the 16-bit slots (slots + kPad entries), the fill pass and the windows'
+// descriptors (ldesc4 = win; ldesc[w] = desc_of(w, first line, lines)), all into `plan`.  nlines: every window's line
+// count.  1: `plan` is the plan; 0: some window lists too many lines; -1: HIP error.  Anything but 1 leaves no plan
+// behind.
+template <int SHIFT, typename D, typename DescOf>
+int plan_on_device(XWindowPlan<D> &plan, const int *idx, size_t slots, const std::vector<int4> &win,
+                   const std::vector<long long> &begin, const std::vector<int> &len, DescOf desc_of, std::vector<int> &nlines) {
     const int W = (int)win.size();
     if (W == 0) return 0;
     long long *d_begin = nullptr;
@@ -53,47 +53,41 @@ int plan_on_device(H *m, const int *idx, size_t slots, const std::vector<int4> &
         }
         if (!fits) { result = 0; break; }
         if (upload_array(&d_off, line_off.data(), line_off.size(), 0)) break;
-        e = hipMalloc((void **)&m->lines, ((size_t)total + kLocalLinesMax) * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void **)&slot, (slots + kPad) * sizeof(unsigned short));
-        if (e == hipSuccess) e = hipMemsetAsync(m->lines, 0, ((size_t)total + kLocalLinesMax) * sizeof(int), g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(slot, 0, (slots + kPad) * sizeof(unsigned short), g_stream);
+        e = hipMalloc((void **)&plan.lines, ((size_t)total + kLocalLinesMax) * sizeof(int));
+        if (e == hipSuccess) e = hipMalloc((void **)&plan.slot, (slots + kPad) * sizeof(unsigned short));
+        if (e == hipSuccess) e = hipMemsetAsync(plan.lines, 0, ((size_t)total + kLocalLinesMax) * sizeof(int), g_stream);
+        if (e == hipSuccess) e = hipMemsetAsync(plan.slot, 0, (slots + kPad) * sizeof(unsigned short), g_stream);
         if (e != hipSuccess) { fail("x-window plan: allocation failed: %s", hipGetErrorString(e)); break; }
         hipLaunchKernelGGL((plan_fill<SHIFT>), dim3(W), dim3(kBlock), 0, g_stream, W, d_begin, d_len, idx, d_off,
-                           m->lines, slot);
+                           plan.lines, plan.slot);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
         if (e != hipSuccess) { fail("x-window plan: fill pass failed: %s", hipGetErrorString(e)); break; }
-        if (upload_array(&m->ldesc4, win.data(), win.size(), 1) || upload_array(&ldesc, h_ldesc.data(), h_ldesc.size(), 1))
+        if (upload_array(&plan.ldesc4, win.data(), win.size(), 1) || upload_array(&plan.ldesc, h_ldesc.data(), h_ldesc.size(), 1))
             break;
-        m->local_blocks = W;
-        m->local_lines = total;
-        m->local_stage_lines = std::max(kLocalLineQuantum,
-                                        (widest + kLocalLineQuantum - 1) / kLocalLineQuantum * kLocalLineQuantum);
+        plan.blocks = W;
+        plan.lines_listed = plan.lines_stored = total;
+        plan.slots = (long long)slots;
+        plan.stage_lines = std::max(kLocalLineQuantum, (widest + kLocalLineQuantum - 1) / kLocalLineQuantum * kLocalLineQuantum);
         result = 1;
     } while (0);
     for (void *p : {(void *)d_begin, (void *)d_len, (void *)d_n, (void *)d_off}) (void)hipFree(p);
-    if (result != 1) {
-        for (void *p : {(void *)m->lines, (void *)slot, (void *)m->ldesc4, (void *)ldesc}) (void)hipFree(p);
-        m->lines = nullptr;
-        slot = nullptr;
-        m->ldesc4 = nullptr;
-        ldesc = nullptr;
-        m->local_blocks = 0;
-    }
+    if (result != 1) plan.release();
     return result;
 }
 
-// The pattern plan's tables (plan_kernels.hpp: pat_mark, pat_fill) of the blocks ldesc4[0, blocks) over their 16-bit
-// slots `slot`, a row's slots found through row_ptr, or through row_seg (ROW_SEG: HLL windows).  auto: built for streamed
-// handles (the `nt` threshold) of at least 12 slots per row, and only where the tables hold at most a quarter of the
-// slots.  Returns the elements of every block's table; pat.ptab == nullptr: no plan (not wanted, or it could not be
-// built -- then nothing is left of it and the last HIP error is cleared).
-template <bool ROW_SEG>
-std::vector<int> build_pattern_tables(PatternPlan &pat, int blocks, int rows, long long slots, int value_bytes,
-                                      const int4 *ldesc4, const int *row_ptr, const unsigned *row_seg,
-                                      const unsigned short *slot) {
+// The pattern plan's tables (plan_kernels.hpp: pat_mark, pat_fill) of the x-window plan `xw` over its 16-bit slots, a
+// row's slots found through row_ptr, or through the plan's row_seg (ROW_SEG: HLL windows); `slots` of the handle's `rows`
+// rows.  auto: built for streamed handles (the `nt` threshold) of at least 12 slots per row, and only where the tables
+// hold at most a quarter of the slots.  Returns the elements of every block's table; xw.pat.ptab == nullptr: no plan
+// (not wanted, or it could not be built -- then nothing is left of it and the last HIP error is cleared).
+template <bool ROW_SEG, typename D>
+std::vector<int> build_pattern_tables(XWindowPlan<D> &xw, int rows, long long slots, int value_bytes, const int *row_ptr) {
+    PatternPlan &pat = xw.pat;
+    const int blocks = xw.blocks;
+    const unsigned *row_seg = xw.row_seg;
     std::vector<int> count;
-    if (g_local_patterns == 0 || blocks <= 0 || rows <= 0 || !ldesc4 || !slot || (!row_ptr && !row_seg)) return count;
+    if (g_local_patterns == 0 || blocks <= 0 || rows <= 0 || !xw.ldesc4 || !xw.slot || (!row_ptr && !row_seg)) return count;
     if (g_local_patterns < 0 && (slots * (value_bytes + 2LL) <= (128LL << 20) || slots < 12LL * rows)) return count;
     int *rowflag = nullptr, *pcount = nullptr;
     long long *pbase = nullptr;
@@ -102,7 +96,7 @@ std::vector<int> build_pattern_tables(PatternPlan &pat, int blocks, int rows, lo
     if (e == hipSuccess) e = hipMalloc((void **)&pbase, (size_t)blocks * sizeof(long long));
     if (e == hipSuccess) e = hipMemsetAsync(rowflag, 0, (size_t)rows * sizeof(int), g_stream);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL((pat_mark<256, ROW_SEG>), dim3(blocks), dim3(256), 0, g_stream, blocks, ldesc4, row_ptr, slot,
+        hipLaunchKernelGGL((pat_mark<256, ROW_SEG>), dim3(blocks), dim3(256), 0, g_stream, blocks, xw.ldesc4, row_ptr, xw.slot,
                            rowflag, pcount, row_seg);
         count.assign((size_t)blocks, 0);
         e = hipMemcpyAsync(count.data(), pcount, (size_t)blocks * sizeof(int), hipMemcpyDeviceToHost, g_stream);
@@ -128,8 +122,8 @@ std::vector<int> build_pattern_tables(PatternPlan &pat, int blocks, int rows, lo
         if (e == hipSuccess)
             e = hipMemcpyAsync(pbase, base.data(), (size_t)blocks * sizeof(long long), hipMemcpyHostToDevice, g_stream);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL((pat_fill<256, ROW_SEG>), dim3(blocks), dim3(256), 0, g_stream, blocks, ldesc4, row_ptr,
-                               slot, rowflag, pbase, pat.rinfo, pat.ptab, pat.pdesc, row_seg);
+            hipLaunchKernelGGL((pat_fill<256, ROW_SEG>), dim3(blocks), dim3(256), 0, g_stream, blocks, xw.ldesc4, row_ptr,
+                               xw.slot, rowflag, pbase, pat.rinfo, pat.ptab, pat.pdesc, row_seg);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
@@ -299,8 +293,8 @@ void upload_settle(Launch launch) {
 
 // (auto) the handle's kernel with and without its pattern plan, alternately, two rounds of 2 + 6 launches each: the plan
 // stays if it is at least 2 % faster here.
-template <typename H, typename Launch>
-void tune_pattern_plan(H *m, long long rows, Launch launch) {
+template <typename Launch>
+void tune_pattern_plan(PatternPlan &pat, Launch launch) {
     UploadTimer timer;
     if (!timer.ok) return;
     auto measure = [&](int patterns, float &us) {
@@ -310,7 +304,6 @@ void tune_pattern_plan(H *m, long long rows, Launch launch) {
         g_local_patterns = keep;
         return ok;
     };
-    PatternPlan &pat = m->pat;
     bool ok = true;
     for (int round = 0; round < 2 && ok; ++round) {
         float a = 0, b = 0;
@@ -318,10 +311,7 @@ void tune_pattern_plan(H *m, long long rows, Launch launch) {
         pat.with_us = round ? std::min(pat.with_us, a) : a;
         pat.without_us = round ? std::min(pat.without_us, b) : b;
     }
-    if (!ok || pat.with_us > 0.98f * pat.without_us) {  // not faster here: the slot stream stays
-        m->device_bytes -= std::min(m->device_bytes, pat.bytes(rows, m->local_blocks));
-        pat.release();
-    }
+    if (!ok || pat.with_us > 0.98f * pat.without_us) pat.release();  // not faster here: the slot stream stays
 }
 
 // Where the value array lies decides -- for as long as the allocation lives, by a mechanism the counters at hand do not
@@ -375,15 +365,15 @@ void tune_placement(H *m, V *&val, size_t bytes, Launch launch) {
         if (p != best) (void)hipFree(p);
 }
 
-// The searches of a finished handle, in this order: settle, the pattern plan (auto; `rows` rows), the placement of the
+// The searches of a finished handle, in this order: settle, the pattern plan (auto), the placement of the
 // value array *val (`bytes` long; val == nullptr: the handle's kernel does not stream it, or it is below
 // kPlaceMinBytes).  launch() runs the handle's own kernel.  None is ever a reason to lose the handle.
 template <typename H, typename V, typename Launch>
-void upload_searches(H *m, long long rows, V **val, size_t bytes, Launch launch) {
-    const bool patterns = g_local_patterns < 0 && m->pat.ptab;
+void upload_searches(H *m, V **val, size_t bytes, Launch launch) {
+    const bool patterns = g_local_patterns < 0 && m->xw.pat.ptab;
     const bool place = val && *val && g_place_tries > 0;
     if (patterns || place) upload_settle(launch);
-    if (patterns) tune_pattern_plan(m, rows, launch);
+    if (patterns) tune_pattern_plan(m->xw.pat, launch);
     if (place) tune_placement(m, *val, bytes, launch);
 }
 

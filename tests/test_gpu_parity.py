@@ -980,8 +980,9 @@ def test_conjugate_gradients_match_the_oracle_loop(gpu, oracle):
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_plan_built_on_the_device_equals_the_host_plan(gpu, oracle, dtype):
     """plan_count / plan_fill (LDS sort + unique per block) against csr_build_local / hll_build_local: the
-    same blocks, the same number of listed lines, the same bits out of the kernels; a matrix whose
-    blocks exceed the line limit falls back to the host builder either way."""
+    same blocks, the same number of listed and stored lines and lists, the same bytes held and streamed, the
+    same bits out of the kernels; a matrix whose blocks exceed the line limit falls back to the host builder
+    either way."""
     from sparsematrixvectormultiplication_amd.device import set_tuning
     from _util import banded_csr
     rng = np.random.default_rng(77)
@@ -996,11 +997,14 @@ def test_plan_built_on_the_device_equals_the_host_plan(gpu, oracle, dtype):
                 with sp.CsrDevice(M, N, row_ptr, col, val) as dev:
                     info = dev.info()
                     y = dev.spmv(x, sp.CSR_STREAM)
-                    entry = [info["local_blocks"], info["local_lines"], info["local_stage_lines"], y.tobytes()]
+                    entry = [info["local_blocks"], info["local_lines"], info["local_stage_lines"], y.tobytes(),
+                             info["device_bytes"], info["stream_bytes"], info["local_lines_stored"],
+                             info["local_lists_stored"]]
                     if dtype == np.float64:
                         with sp.HllDevice.from_csr_device(dev) as h:
                             hi = h.info()
-                            entry += [hi["local_blocks"], hi["local_stage_lines"], h.spmv(x, sp.HLL_LDS).tobytes()]
+                            entry += [hi["local_blocks"], hi["local_stage_lines"], h.spmv(x, sp.HLL_LDS).tobytes(),
+                                      hi["device_bytes"], hi["local_lines"]]
                     got[where] = entry
         finally:
             set_tuning("plan_on_device", 1)
