@@ -345,6 +345,73 @@ int spmv_spgemm_plan(int M, const long long *products, int block_products, int m
  * allocation. */
 int spmv_hip_csr_add(const spmv_csr_dev *a, double alpha, const spmv_csr_dev *b /* may be NULL */, double beta,
                      int method, int lanes, int long_row, spmv_csr_dev **out, long long *stats, double *ms);
+/* C = P A Q^T of a whole M x N CSR handle, built on the device, as a new M x N handle of the same dtype.  row_perm (M
+ * entries) and col_perm (N entries) are host arrays; either may be NULL, the identity.  The gather convention:
+ *     C[i, j] = A[row_perm[i], col_perm[j]]
+ * Row i of C is row row_perm[i] of A.  Entry e of that row keeps its place in the row and its value bit for bit and gets
+ * the column j with col_perm[j] == col[e].  Nothing is sorted or combined: repeated pairs stay repeated and C's rows are
+ * unsorted in general (upload's plans take that; spmv_hip_csr_add with b = NULL sorts them).  Permuting C by the inverse
+ * permutations gives A's arrays exactly.  With one symmetric permutation p (C = A permuted by p, p), a system A x = b
+ * becomes C y = b[p] with x[p] = y.
+ * Each permutation is checked on the device: the first position whose value lies outside the range or repeats an
+ * earlier position is refused by name, position and value.  Only the row lengths (4 bytes per row) cross to the host.
+ * C is an ordinary handle (upload's plans, its own arrays, independent of A, which is not modified).
+ * -1 with a message (*out NULL, A usable): m or out NULL, a row-range or tiles-only handle, an array that is not a
+ * permutation, a failed allocation. */
+int spmv_hip_csr_permute(const spmv_csr_dev *m, const int *row_perm /* may be NULL */, const int *col_perm /* may be NULL */,
+                         spmv_csr_dev **out);
+/* ms[2]: host milliseconds of the device build and of the adopt of this thread's last successful spmv_hip_csr_permute */
+int spmv_hip_csr_permute_ms(double *ms);
+/* The reverse Cuthill-McKee ordering of a square matrix of n rows.  G is the graph with u ~ v iff u != v and the matrix
+ * stores an entry at (u, v) or (v, u): stored zeros count, repeats count once, the diagonal is ignored.  deg(v) is the
+ * number of neighbours of v; "smallest" means smallest (deg, index).
+ *     seq = [];  visited = {}
+ *     while some node is unvisited:
+ *         s = the smallest unvisited node
+ *         if peripheral > 0 and deg(s) > 0:
+ *             repeat at most `peripheral` times:
+ *                 t = the smallest node of the last level of a breadth-first search from s
+ *                 if depth(t) > depth(s):  s = t   else: stop
+ *                 (depth = the number of levels of the search from that node; a search reaches unvisited nodes only,
+ *                  which are s's component)
+ *         append s, mark it;  for every node v of seq from s on, in order:
+ *             append v's unvisited neighbours in ascending (deg, index), mark them
+ *     perm[i] = seq[n - 1 - i]                           new row i is old row perm[i]
+ * Isolated nodes are the smallest nodes: they come first in seq in index order and last in perm.  The reordered matrix
+ * is spmv_hip_csr_permute(m, perm, perm).
+ *   peripheral   passes of the search for a start node far from the rest, 0 .. SPMV_RCM_MAX_PERIPHERAL
+ *   stats (SPMV_RCM_STATS, may be NULL)  components (isolated nodes included), isolated nodes, levels (the expansions of
+ *                the ordering: one per level of every component that is not an isolated node), chained levels, wide levels,
+ *                launches of the searches and levels, searches run, the bandwidth max |i - j| over the stored entries
+ *                before, and max |inv[i] - inv[j]| after
+ * spmv_rcm_plan_build is the definition itself, one host thread, no device (chained levels, wide levels and launches
+ * are 0).  -1: a NULL array, n < 0, row_ptr that does not start at 0 or descends, a column outside [0, n), peripheral
+ * outside its range; -2: out of memory. */
+#define SPMV_RCM_STATS 9
+#define SPMV_RCM_MAX_PERIPHERAL 8
+int spmv_rcm_plan_build(int n, const int *row_ptr, const int *col, int peripheral, int *perm, long long *stats);
+/* The same perm, byte for byte, built on the device from a whole square handle.  The pattern of A + A^T comes from the
+ * cores of spmv_hip_csr_transpose and spmv_hip_csr_add (no handle is made).  One sort of all nodes by (deg, index) gives
+ * every node its rank, which stands for (deg, index) in all later keys, the start nodes (a cursor over the sorted list
+ * that skips visited nodes) and the isolated nodes (one pass).  Inside one search the next level in seq order is the set
+ * of unvisited neighbours of the frontier sorted by (place in seq of the earliest frontier parent, deg, index):
+ *   wide level     a kernel gives lane groups to the frontier's rows and takes an integer atomicMin of the parent's place
+ *                  into every unvisited neighbour (the result does not depend on arrival order); one radix sort of
+ *                  (parent, rank) on the bits in use; a kernel writes the places.  Four bytes cross to the host: the next
+ *                  frontier's size
+ *   chained levels a run of levels whose frontier and next frontier hold at most chain_nodes nodes is one launch of one
+ *                  workgroup: candidates in LDS, a bitonic sort, a barrier, the next level.  It stops when the frontier is
+ *                  empty or the next one is too wide, and the wide tier goes on.  chain_nodes: 0 = auto (1024), -1 = never
+ *                  chain, else a power of two in the range spmv_hip_rcm_chain_nodes reports (64 .. 4096: 8 bytes of LDS
+ *                  per node)
+ *   searches       the peripheral passes run the same expansion without the sort
+ *   ms (3, may be NULL)   host milliseconds of graph, peripheral, order
+ * Two calls give the same bytes.  -1 with a message: m NULL, perm NULL, a matrix that is not square, a row-range or
+ * tiles-only handle, peripheral or chain_nodes outside the above, a failed allocation. */
+int spmv_hip_csr_rcm(const spmv_csr_dev *m, int peripheral, int chain_nodes, int *perm, long long *stats, double *ms);
+/* the chain_nodes spmv_hip_csr_rcm takes: the smallest and largest power of two and what 0 stands for (no device needed;
+ * any pointer may be NULL) */
+int spmv_hip_rcm_chain_nodes(int *smallest, int *largest, int *automatic);
 /* convenience over the kept struct */
 int spmv_hip_csr_upload_matrix(const CSRMatrix *csr, spmv_csr_dev **out);
 void spmv_hip_csr_free(spmv_csr_dev *m);

@@ -20,6 +20,7 @@ from .device import (BICG_BREAKDOWN_OMEGA, BICG_BREAKDOWN_RHO, BICG_CONVERGED, B
                      PRECOND_AMG, PRECOND_FSAI, PRECOND_ILU0, PRECOND_SSOR, amg_plan, spgemm_plan, MATMUL_MS, MATMUL_STATS, ORDER_MULTICOLOR, ORDER_NATURAL, TRSV_LOWER, TRSV_NONUNIT,  # noqa: F401
                      TRSV_UNIT, TRSV_UPPER, Preconditioner, TriangularSolver,  # noqa: F401
                      ADD_MS, ADD_STATS, identity,  # noqa: F401
+                     PERMUTE_MS, RCM_MS, RCM_STATS, rcm_plan, rcm_chain_nodes,  # noqa: F401
                      CSR_AUTO, CSR_STREAM, CSR_SUBWAVE, CSR_THREAD_ROW, CSR_VARIANTS,  # noqa: F401
                      CSR_WAVE_ROW, HLL_AUTO, HLL_LDS, HLL_SUBWAVE, HLL_THREAD_ROW, HLL_VARIANTS,
                      CsrDevice, HllDevice, SpmvHipError, device_count, device_name, flush_cache,

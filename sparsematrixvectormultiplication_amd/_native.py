@@ -231,6 +231,11 @@ _PROTOTYPES = {
                                       C.POINTER(C.c_longlong), c_double_p]),
     "spmv_hip_csr_add": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int,
                                    C.POINTER(C.c_void_p), C.POINTER(C.c_longlong), c_double_p]),
+    "spmv_hip_csr_permute": (C.c_int, [C.c_void_p, c_int_p, c_int_p, C.POINTER(C.c_void_p)]),
+    "spmv_hip_csr_permute_ms": (C.c_int, [c_double_p]),
+    "spmv_rcm_plan_build": (C.c_int, [C.c_int, c_int_p, c_int_p, C.c_int, c_int_p, C.POINTER(C.c_longlong)]),
+    "spmv_hip_csr_rcm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, C.POINTER(C.c_longlong), c_double_p]),
+    "spmv_hip_rcm_chain_nodes": (C.c_int, [c_int_p, c_int_p, c_int_p]),
     "spmv_spgemm_plan": (C.c_int, [C.c_int, C.POINTER(C.c_longlong), C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p]),
     "spmv_hip_csr_precond_build": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "spmv_hip_precond_free": (None, [C.c_void_p]),

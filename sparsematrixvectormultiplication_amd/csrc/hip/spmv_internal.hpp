@@ -533,6 +533,10 @@ inline bool spgemm_block_products_ok(int bp) {
 }
 // spmv_transpose.hip: At = A^T on bare arrays, the same way
 int transpose_core(int value_bytes, const CsrView &A, DevCsr &At, std::vector<int> &rp_host);
+// spmv_spadd.hip: C = alpha a + beta b on bare arrays, the same way (b NULL: alpha canon(a); the arguments, stats[6] and
+// ms[0..3] -- check / canonical / symbolic / numeric -- of spmv_hip_csr_add)
+int spadd_core(int value_bytes, const CsrView *a, double alpha, const CsrView *b, double beta, int method, int lanes,
+               int long_row, DevCsr &C, std::vector<int> &rp_host, long long *stats, double *ms);
 // spmv_csr.hip: tile plans alone for rows given as (first entry, length) over host arrays (an HLL slab's rows);
 // *out = NULL when the rows get no plan
 // (col / val: host copies of the rows' arrays, or NULL when d_col / d_val -- the same arrays on the device -- are given

@@ -45,8 +45,8 @@ int canonical_of(const CsrView &x, DevCsr &out) {
 
 // the sum on bare arrays: everything but the adopt.  b: NULL (C = alpha canon(a)), or a itself (one check, one canon(a))
 template <typename T>
-int spadd_core(const CsrView *a, double alpha, const CsrView *b, double beta, int method, int lanes_arg, int long_arg,
-               DevCsr &C_out, std::vector<int> &rp, long long *stats, double *ms) {
+int spadd_core_t(const CsrView *a, double alpha, const CsrView *b, double beta, int method, int lanes_arg, int long_arg,
+                 DevCsr &C_out, std::vector<int> &rp, long long *stats, double *ms) {
     const int M = a->rows, N = a->cols;
     UploadTrace trace("csr_add");
     double split[4] = {0, 0, 0, 0};
@@ -184,7 +184,7 @@ int add_body(const spmv_csr_dev *a, double alpha, const spmv_csr_dev *b, double 
     DevCsr C;
     std::vector<int> rp;
     double split[5] = {0, 0, 0, 0, 0};
-    if (spadd_core<T>(&va, alpha, !b ? nullptr : b == a ? &va : &vb, beta, method, lanes, long_row, C, rp, stats, split)) return -1;
+    if (spadd_core_t<T>(&va, alpha, !b ? nullptr : b == a ? &va : &vb, beta, method, lanes, long_row, C, rp, stats, split)) return -1;
     algebra::PhaseTimer timer{split};
     const int rc = algebra::adopt<T>(std::move(C), rp, out);
     timer.lap(4);
@@ -194,6 +194,12 @@ int add_body(const spmv_csr_dev *a, double alpha, const spmv_csr_dev *b, double 
 }
 
 }  // namespace
+
+int spadd_core(int value_bytes, const CsrView *a, double alpha, const CsrView *b, double beta, int method, int lanes,
+               int long_row, DevCsr &C, std::vector<int> &rp_host, long long *stats, double *ms) {
+    return value_bytes == 8 ? spadd_core_t<double>(a, alpha, b, beta, method, lanes, long_row, C, rp_host, stats, ms)
+                            : spadd_core_t<float>(a, alpha, b, beta, method, lanes, long_row, C, rp_host, stats, ms);
+}
 
 extern "C" int spmv_hip_csr_add(const spmv_csr_dev *a, double alpha, const spmv_csr_dev *b, double beta, int method, int lanes,
                                 int long_row, spmv_csr_dev **out, long long *stats, double *ms) {

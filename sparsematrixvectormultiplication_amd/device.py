@@ -62,6 +62,12 @@ SPGEMM_MAX_ROWS = 4096
 ADD_STATS = ("nz", "matches", "a_canonical", "b_canonical", "long_rows", "max_row_nz")
 ADD_MS = ("check", "canonical", "symbolic", "numeric", "adopt")
 ADD_METHODS = {"auto": 0, "merge": 1, "canonical": 2}
+# CsrDevice.rcm / rcm_plan: the info (the stats of spmv_hip_csr_rcm and spmv_rcm_plan_build) and the time split
+RCM_STATS = ("components", "isolated", "levels", "chained_levels", "wide_levels", "launches", "peripheral_searches",
+             "bandwidth_before", "bandwidth_after")
+RCM_MS = ("graph", "peripheral", "order")
+RCM_MAX_PERIPHERAL = 8
+PERMUTE_MS = ("device_build", "adopt")
 CSR_STREAM_KERNELS = ("csr_stream", "csr_stream_local", "csr_stream_short", "csr_tile")
 HLL_LDS_KERNELS = ("hll_lds", "hll_lds_local", "csr_tile (HLL slab rows)")
 CSR_VARIANTS = {"thread_row": CSR_THREAD_ROW, "wave_row": CSR_WAVE_ROW, "subwave": CSR_SUBWAVE,
@@ -323,6 +329,59 @@ class CsrDevice(_Handle):
     def canonical(self) -> "CsrDevice":
         """canon(self) as a new handle: sorted rows, repeated (row, column) pairs added in entry order (add(None))."""
         return self.add(None)
+
+    def permute(self, row_perm=None, col_perm=None) -> "CsrDevice":
+        """C = P A Q^T as a new handle (spmv_hip_csr_permute): C[i, j] = A[row_perm[i], col_perm[j]].  Row i of C is row
+        row_perm[i] of this matrix, entry by entry: each keeps its place in the row and its value bit for bit and gets
+        the column j with col_perm[j] == its column.  None is the identity.  Nothing is sorted or combined (canonical()
+        sorts the rows); permuting C by the inverse permutations gives this handle's arrays exactly.  C gets the plans an
+        upload would get, owns its arrays and outlives this handle.  C.permute_info["ms"] holds PERMUTE_MS."""
+        perms = []
+        for name, perm, n in (("row_perm", row_perm, self.M), ("col_perm", col_perm, self.N)):
+            if perm is not None:
+                perm = np.asarray(perm)
+                if perm.ndim != 1 or perm.size != n:
+                    raise ValueError(f"permute: {name} has shape {perm.shape}; {n} entries are needed")
+                if not np.issubdtype(perm.dtype, np.integer):
+                    raise ValueError(f"permute: {name} holds {perm.dtype}; integers are needed")
+                if perm.size and (perm.min() < -2 ** 31 or perm.max() >= 2 ** 31):
+                    raise ValueError(f"permute: {name} holds values beyond 32 bits")
+                perm = np.ascontiguousarray(perm, dtype=np.int32)
+            perms.append(perm)
+        if self._own_rows() != (0, self.M):
+            raise SpmvHipError(f"csr_permute: a handle of rows {self._own_rows()} of {self.M}; only whole matrices permute")
+        ptr = [q.ctypes.data_as(nat.c_int_p) if q is not None else None for q in perms]
+        out = CsrDevice._built(self.M, self.N, self.dtype, "spmv_hip_csr_permute",
+                               lambda out: nat.lib().spmv_hip_csr_permute(self.h, ptr[0], ptr[1], out))
+        ms = (C.c_double * len(PERMUTE_MS))()
+        _check(nat.lib().spmv_hip_csr_permute_ms(ms), "spmv_hip_csr_permute_ms")
+        out.permute_info = {"ms": dict(zip(PERMUTE_MS, (float(v) for v in ms)))}
+        return out
+
+    def rcm(self, peripheral: int = 2, chain_nodes: int = 0):
+        """(perm, info): the reverse Cuthill-McKee ordering of this square matrix, built on the device
+        (spmv_hip_csr_rcm); perm is what rcm_plan gives on the downloaded arrays, byte for byte.  New row i is old row
+        perm[i]: the reordered matrix is permute(perm, perm).  peripheral: passes of the start-node search, 0 .. 8;
+        chain_nodes: levels of at most this many nodes run chained in one workgroup (0 = auto, -1 = never, else a power
+        of two in rcm_chain_nodes()).  info holds RCM_STATS and "ms" (RCM_MS)."""
+        peripheral, chain_nodes = int(peripheral), int(chain_nodes)
+        perm = np.zeros(self.M, dtype=np.int32)
+        stats, ms = (C.c_longlong * len(RCM_STATS))(), (C.c_double * len(RCM_MS))()
+        _check(nat.lib().spmv_hip_csr_rcm(self.h, peripheral, chain_nodes, perm.ctypes.data_as(nat.c_int_p), stats, ms),
+               "spmv_hip_csr_rcm")
+        info = dict(zip(RCM_STATS, (int(v) for v in stats)))
+        info["ms"] = dict(zip(RCM_MS, (float(v) for v in ms)))
+        return perm, info
+
+    def reordered(self, method: str = "rcm", **kw):
+        """(B, perm) with B = self.permute(perm, perm) for the ordering `method` ("rcm": perm of self.rcm(**kw)).
+        Vectors: to solve A x = b, solve B y = b[perm]; then x[perm] = y.  B.reorder_info is the ordering's info."""
+        if method != "rcm":
+            raise ValueError(f"reordered: method = {method!r}; \"rcm\" is the ordering there is")
+        perm, info = self.rcm(**kw)
+        out = self.permute(perm, perm)
+        out.reorder_info = info
+        return out, perm
 
     def __add__(self, other):
         return self.add(other) if isinstance(other, CsrDevice) else NotImplemented
@@ -923,6 +982,37 @@ def spgemm_plan(products, block_products, max_rows=SPGEMM_MAX_ROWS):
         raise ValueError(f"spgemm_plan refused block_products = {block_products}, max_rows = {max_rows} "
                          f"(0, -1 or a power of two in [64, 4096]; 1 .. 4096 rows; counts >= 0)")
     return block_row[:nb.value + 1].copy(), long_row[:nl.value].copy()
+
+
+def rcm_chain_nodes():
+    """(smallest, largest, auto): the chain_nodes CsrDevice.rcm takes beside 0 and -1 (spmv_hip_rcm_chain_nodes)."""
+    lo, hi, auto = C.c_int(), C.c_int(), C.c_int()
+    nat.lib().spmv_hip_rcm_chain_nodes(C.byref(lo), C.byref(hi), C.byref(auto))
+    return lo.value, hi.value, auto.value
+
+
+def rcm_plan(row_ptr, col, n, peripheral=2):
+    """(perm, info): the reverse Cuthill-McKee ordering of an n x n CSR pattern on one host thread (spmv_rcm_plan_build;
+    no device needed): the serial loop of include/spmv_hip.h, which CsrDevice.rcm reproduces.  New row i is old row
+    perm[i].  info holds RCM_STATS (the device's counters are 0)."""
+    n, peripheral = int(n), int(peripheral)
+    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int32)
+    col = np.ascontiguousarray(col, dtype=np.int32)
+    if n < 0 or row_ptr.ndim != 1 or row_ptr.size != n + 1:
+        raise ValueError(f"rcm_plan: row_ptr needs n + 1 = {n + 1} entries")
+    if col.ndim != 1 or col.size < int(row_ptr[-1]):
+        raise ValueError(f"rcm_plan: col holds {col.size} entries, row_ptr ends at {int(row_ptr[-1])}")
+    if not 0 <= peripheral <= RCM_MAX_PERIPHERAL:
+        raise ValueError(f"rcm_plan: peripheral = {peripheral}; 0 .. {RCM_MAX_PERIPHERAL}")
+    perm = np.zeros(n, dtype=np.int32)
+    stats = (C.c_longlong * len(RCM_STATS))()
+    rc = nat.lib().spmv_rcm_plan_build(n, row_ptr.ctypes.data_as(nat.c_int_p), col.ctypes.data_as(nat.c_int_p), peripheral,
+                                       perm.ctypes.data_as(nat.c_int_p), stats)
+    if rc == -2:
+        raise MemoryError("rcm_plan: out of memory")
+    if rc != 0:
+        raise ValueError("rcm_plan: row_ptr must start at 0 and ascend, and every column must lie in [0, n)")
+    return perm, dict(zip(RCM_STATS, (int(v) for v in stats)))
 
 
 def _check_amg_args(theta, coarse_rows, max_levels):
