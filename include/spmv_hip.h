@@ -189,6 +189,9 @@ int spmv_hip_gather_probe(int value_bytes, size_t table_bytes, int waves_per_cu,
  *                         and every distinct line list (relative to its first line) is stored once and shared by the blocks
  *                         that repeat it -- auto: on; 0 off (every block its own copy); 1 on; 2 on, with a hash of the
  *                         span's length alone, so that every group has to be told apart word by word (tests)
+ *                     "local_segment_cap" 0 | bytes (read at upload) pattern plans of CSR handles: segments wider than this
+ *                         stay tables even where the LDS budget would take them (tests: both kinds of blocks on a small
+ *                         matrix; 1: no segments at all); 0: the LDS budget alone (spmv_hip_csr_pattern_segment_cap)
  *                     "tile_mid_items" (0 = three rounds of the CUs) work items of the middle tier
  *                     "tile_expand" -1 | 0 | 1 (read at upload and at launch) a tile plan with gather passes runs on an
  *                         expanded x -- auto: from 2^22 entries on when under a tenth of them are staged, fp32 always, fp64
@@ -421,7 +424,8 @@ int spmv_hip_csr_info(const spmv_csr_dev *m, spmv_dev_info *out);
 int spmv_hip_csr_addresses(const spmv_csr_dev *m, unsigned long long *out);
 /* Measurement only: one launch of the x-window kernel (fp64, 2048-entry stage) with per-workgroup time stamps behind
  * `warm` ordinary launches: stamps[3 * b + {0, 1, 2}] = start, end (ticks of the constant 100 MHz clock), dispatch id << 8
- * | XCD of block b; stamps has 3 * local_blocks entries. */
+ * | XCD of block b; stamps has 3 * local_blocks entries.  warm + 1000: the stamped launch reads no slots (y is wrong);
+ * warm + 2000: the second word is the time the block's records were back -- the end of its head -- instead of its end. */
 int spmv_hip_csr_stamp_blocks(spmv_csr_dev *m, int warm, unsigned long long *stamps);
 /* The widest pattern-plan segment (bytes) upload lets an x-window plan keep: its LDS copy beside the stage of
    max(local_cap * value_bytes, stage_lines * 128) bytes and the (local_cap + 8) 16-bit slots must not cost a resident

@@ -771,52 +771,84 @@ __device__ __forceinline__ void local_stage_full_seg(T *stage, const int *__rest
 }
 
 // STAMP (measurement only, spmv_hip_csr_stamp_blocks): every workgroup leaves {start, end} of the constant 100 MHz
-// clock and the XCD it ran on in stamps[3 * block ..]; the product instantiation (STAMP = false) has no trace of it.
-// PAT: a pattern plan (above) -- lcol is not read.  sdesc[b] = {first uint4 of block b's segment in pseg, uint4s}; {0, 0}
-// (or no sdesc): the block's segment is wider than the LDS budget and the block takes its slots from its pattern table:
-// pdesc[b] = {first element of block b's table in ptab (a multiple of 8), elements}, rinfo per row.  stage_bytes = where
-// the LDS array of the slots begins; the segment's copy lies behind it.
-// lbase (optional): shared line lists -- block b's list holds ids relative to line lbase[b], and equal lists are one
-// copy in `lines` (so are equal segments in pseg: sdesc points where it likes).
-template <typename T, bool NT, int CAP, bool STAMP = false, bool PAT = false>
-__global__ __launch_bounds__(kBlock) void csr_stream_local(int num_blocks, int xcd_chunk,
-                                                           const int *__restrict__ ids,
-                                                           const int4 *__restrict__ desc,
-                                                           const int2 *__restrict__ ldesc,
-                                                           const int *__restrict__ lines,
-                                                           const int *__restrict__ row_ptr,
-                                                           const unsigned short *__restrict__ lcol,
-                                                           const T *__restrict__ val,
-                                                           const T *__restrict__ x, T *__restrict__ y,
-                                                           unsigned long long *__restrict__ stamps = nullptr, int probe = 0,
-                                                           const int2 *__restrict__ pdesc = nullptr,
-                                                           const unsigned *__restrict__ rinfo = nullptr,
-                                                           const unsigned short *__restrict__ ptab = nullptr, int stage_bytes = 0,
-                                                           const int2 *__restrict__ sdesc = nullptr,
-                                                           const uint4 *__restrict__ pseg = nullptr,
-                                                           const int *__restrict__ lbase = nullptr) {
-        using V2 = typename vec2<T>::type;
+// clock and the XCD it ran on in stamps[3 * block ..]; with (probe & 2) the second word is the time the block's
+// records were back (the end of the head, below) instead of its end.  The product instantiation (STAMP = false) has
+// no trace of it.
+// PAT: a pattern plan (above) -- lcol is not read.  SEGS: the plan has segments: sdesc[b] = {first uint4 of block b's
+// segment in pseg, uint4s}; {0, 0} (or !SEGS): the block's segment is wider than the LDS budget and the block takes its
+// slots from its pattern table: pdesc[b] = {first element of block b's table in ptab (a multiple of 8), elements},
+// rinfo per row.  stage_bytes = where the LDS array of the slots begins; the segment's copy lies behind it.
+// SHARED: shared line lists -- block b's list holds ids relative to line lbase[b], and equal lists are one copy in
+// `lines` (so are equal segments in pseg: sdesc points where it likes).
+// What a plan has is the launcher's word (`shape`: bit 0 SHARED, bit 1 SEGS), not a pointer tested here, and inside
+// the kernel it is a compile-time property: the kernel holds one body per shape (x_window_block below) and picks it with
+// a scalar branch on the argument.  A branch on an argument costs no memory trip; a branch in front of a LOAD does -- the
+// load is asked for only after everything in front of the branch has come back -- and the bodies have none.
+//
+// The HEAD of a block -- what stands between its start and its first vector load -- is two scalar round trips and no
+// more: the kernel's arguments (all of them at once), then the block's records desc[b], ldesc[b], sdesc[b] and lbase[b]
+// (pdesc[b] where the plan has tables only), asked for back to back behind ONE wait.  Their addresses need nothing but
+// b.  Two asm statements pin that (one in the kernel, one in the body): each takes its operands in scalar registers, so
+// every load that feeds it is issued in front of it and cannot sink into a later block of code behind another wait.
+// (ids[at], part launches only, stays one more dependent trip.)
+constexpr int kXwShared = 1, kXwSegs = 2;  // the bits of `shape`
+// A block's record, read through the constant address space: the plan's arrays are written at upload and never by a
+// kernel, and said so the load is a scalar one wherever it stands (a plain load is scalar only where the compiler can
+// prove that nothing in front of it writes memory, which it gives up behind the first of the kernel's bodies).
+typedef int rec_i2 __attribute__((ext_vector_type(2)));
+typedef int rec_i4 __attribute__((ext_vector_type(4)));
+#define SPMV_CONST_AS __attribute__((address_space(4)))
+__device__ __forceinline__ int record_load(const int *p) { return *(const SPMV_CONST_AS int *)p; }
+__device__ __forceinline__ int2 record_load(const int2 *p) {
+    const rec_i2 v = *(const SPMV_CONST_AS rec_i2 *)p;
+    return make_int2(v.x, v.y);
+}
+__device__ __forceinline__ int4 record_load(const int4 *p) {
+    const rec_i4 v = *(const SPMV_CONST_AS rec_i4 *)p;
+    return make_int4(v.x, v.y, v.z, v.w);
+}
+#undef SPMV_CONST_AS
+template <typename T, bool NT, int CAP, bool STAMP, bool PAT, bool SHARED, bool SEGS>
+__device__ __forceinline__ void x_window_block(unsigned wg, unsigned long long t_start, int num_blocks, int xcd_chunk,
+                                               const int *__restrict__ ids, const int4 *__restrict__ desc,
+                                               const int2 *__restrict__ ldesc, const int *__restrict__ lines,
+                                               const int *__restrict__ row_ptr, const unsigned short *__restrict__ lcol,
+                                               const T *__restrict__ val, const T *__restrict__ x, T *__restrict__ y,
+                                               unsigned long long *__restrict__ stamps, int probe,
+                                               const int2 *__restrict__ pdesc, const unsigned *__restrict__ rinfo,
+                                               const unsigned short *__restrict__ ptab, int stage_bytes,
+                                               const int2 *__restrict__ sdesc, const uint4 *__restrict__ pseg,
+                                               const int *__restrict__ lbase) {
+    static_assert(PAT || !SEGS, "segments belong to a pattern plan");
+    using V2 = typename vec2<T>::type;
     const bool no_slots = STAMP && (probe & 1);  // (measurement only; constant false in the product instantiation)
-    unsigned long long t_start = 0;
-    if constexpr (STAMP) t_start = __builtin_amdgcn_s_memrealtime();
+    unsigned long long t_head = 0;
     constexpr int kUnit = 2 * kBlock, kUnits = CAP / kUnit;
     // one LDS stage, used twice: first the x lines of the block, then (after every lane has
     // gathered its x values into registers) the CAP products.  max(CAP values, staged lines).
     extern __shared__ __attribute__((aligned(16))) unsigned char local_smem[];
     T *stage = reinterpret_cast<T *>(local_smem);
 
-    const int at = xcd_chunked(blockIdx.x, xcd_chunk);
+    const int at = xcd_chunked(wg, xcd_chunk);
     if (at >= num_blocks) return;
     // ids (optional): a sub-list of the blocks -- the interior or the boundary blocks of a rank (N4 overlap)
-    const int b = ids ? ids[at] : at;
+    const int b = ids ? record_load(ids + at) : at;
     const int t = threadIdx.x;
-    const int4 d = desc[b];
-    const int2 ld = ldesc[b];
-    const int r0 = d.x, nrows = d.z;
+    // the block's records, in one trip
+    const int4 d = record_load(desc + b);
+    const int2 ld = record_load(ldesc + b);
+    int2 sd = make_int2(0, 0), pd = make_int2(0, 0);
+    if constexpr (SEGS) sd = record_load(sdesc + b);
+    if constexpr (PAT && !SEGS) pd = record_load(pdesc + b);
+    int first_line = 0;
+    if constexpr (SHARED) first_line = record_load(lbase + b);
+    int nrows = d.z;  // (passes through: the row extents, the first vector loads, need it)
+    asm("" : "+s"(nrows) : "s"(d.x), "s"(d.y), "s"(d.w), "s"(ld.x), "s"(ld.y), "s"(sd.x), "s"(sd.y), "s"(pd.x), "s"(pd.y),
+        "s"(first_line));
+    if constexpr (STAMP) asm("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_head), "+s"(nrows));
+    const int r0 = d.x;
     const int base = d.y & kBaseMask;
-    int2 sd = make_int2(0, 0);
-    if (PAT && sdesc) sd = sdesc[b];
-    const bool seg = PAT && sd.y > 0;  // wave-uniform
+    const bool seg = SEGS && sd.y > 0;  // wave-uniform
 
     const int lanes = lanes_for_rows<kBlock>(nrows);
     // (only the first pass's row extents are loaded up front: keeping all passes in registers, as
@@ -832,8 +864,8 @@ __global__ __launch_bounds__(kBlock) void csr_stream_local(int num_blocks, int x
     const int rounds = (ld.y + kLocalLineQuantum - 1) / kLocalLineQuantum;    // wave-uniform, 1..8
     const int *my_lines = lines + ld.x;
     // shared line lists: the list counts from the block's first line, so x is taken from that line on (wave-uniform)
-    const bool shared_lists = lbase != nullptr;
-    if (shared_lists) x = reinterpret_cast<const T *>(reinterpret_cast<const char *>(x) + (size_t)lbase[b] * kLineBytes);
+    constexpr bool shared_lists = SHARED;
+    if constexpr (SHARED) x = reinterpret_cast<const T *>(reinterpret_cast<const char *>(x) + (size_t)first_line * kLineBytes);
     unsigned short *slots = reinterpret_cast<unsigned short *>(local_smem + stage_bytes);
     uint4 *seg_lds = reinterpret_cast<uint4 *>(local_smem + stage_bytes + (CAP + 8) * sizeof(unsigned short));
     if (seg) {
@@ -885,7 +917,7 @@ __global__ __launch_bounds__(kBlock) void csr_stream_local(int num_blocks, int x
         }
     } else if constexpr (PAT) {
         // a block whose segment is wider than the LDS budget: its pattern table (pat_ctx above)
-        const int2 pd = pdesc[b];
+        if constexpr (SEGS) pd = record_load(pdesc + b);
         pat_ctx pc;
         pc.slots = slots;
         pc.ptab8 = reinterpret_cast<const uint4 *>(ptab + pd.x);
@@ -981,11 +1013,56 @@ __global__ __launch_bounds__(kBlock) void csr_stream_local(int num_blocks, int x
         __syncthreads();
         if (threadIdx.x == 0) {
             stamps[3 * (size_t)b] = t_start;
-            stamps[3 * (size_t)b + 1] = __builtin_amdgcn_s_memrealtime();
+            stamps[3 * (size_t)b + 1] = (probe & 2) ? t_head : __builtin_amdgcn_s_memrealtime();
             // HW_REG_XCC_ID (20), bits 3:0: the XCD this workgroup ran on; next to it the dispatch id
             stamps[3 * (size_t)b + 2] = ((unsigned long long)blockIdx.x << 8) | (__builtin_amdgcn_s_getreg(20 | (3 << 11)) & 0xf);
         }
     }
+}
+
+template <typename T, bool NT, int CAP, bool STAMP = false, bool PAT = false>
+__global__ __launch_bounds__(kBlock) void csr_stream_local(int num_blocks, int xcd_chunk,
+                                                           const int *__restrict__ ids,
+                                                           const int4 *__restrict__ desc,
+                                                           const int2 *__restrict__ ldesc,
+                                                           const int *__restrict__ lines,
+                                                           const int *__restrict__ row_ptr,
+                                                           const unsigned short *__restrict__ lcol,
+                                                           const T *__restrict__ val,
+                                                           const T *__restrict__ x, T *__restrict__ y,
+                                                           unsigned long long *__restrict__ stamps = nullptr, int probe = 0,
+                                                           const int2 *__restrict__ pdesc = nullptr,
+                                                           const unsigned *__restrict__ rinfo = nullptr,
+                                                           const unsigned short *__restrict__ ptab = nullptr, int stage_bytes = 0,
+                                                           const int2 *__restrict__ sdesc = nullptr,
+                                                           const uint4 *__restrict__ pseg = nullptr,
+                                                           const int *__restrict__ lbase = nullptr, int shape = 0) {
+    unsigned long long t_start = 0;
+    // (the clock is read in asm statements that the workgroup's index and the rows pass through, which keeps each read
+    // where it stands; the builtin beside the pins makes the compiler fetch the records with vector loads)
+    unsigned wg = blockIdx.x;
+    if constexpr (STAMP) asm("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_start), "+s"(wg));
+    // the arguments, in one trip: ALL of them, used or not, so that the segment is fetched whole, in a few wide loads;
+    // xcd_chunk, which every address in the body needs, passes through
+    asm("" : "+s"(xcd_chunk) : "s"(wg), "s"(num_blocks), "s"(ids), "s"(desc), "s"(ldesc), "s"(lines), "s"(row_ptr), "s"(lcol),
+        "s"(val), "s"(x), "s"(y), "s"(stamps), "s"(probe), "s"(pdesc), "s"(rinfo), "s"(ptab), "s"(stage_bytes), "s"(sdesc),
+        "s"(pseg), "s"(lbase), "s"(shape));
+#define SPMV_XW_BODY(SHARED, SEGS)                                                                                              \
+    x_window_block<T, NT, CAP, STAMP, PAT, SHARED, SEGS>(wg, t_start, num_blocks, xcd_chunk, ids, desc, ldesc, lines, row_ptr, lcol, \
+                                                         val, x, y, stamps, probe, pdesc, rinfo, ptab, stage_bytes, sdesc, pseg, lbase)
+    if constexpr (PAT) {
+        switch (shape & (kXwShared | kXwSegs)) {  // wave-uniform: a scalar branch
+            case 0: SPMV_XW_BODY(false, false); break;
+            case kXwShared: SPMV_XW_BODY(true, false); break;
+            case kXwSegs: SPMV_XW_BODY(false, true); break;
+            default: SPMV_XW_BODY(true, true); break;
+        }
+    } else if (shape & kXwShared) {
+        SPMV_XW_BODY(true, false);
+    } else {
+        SPMV_XW_BODY(false, false);
+    }
+#undef SPMV_XW_BODY
 }
 
 // ----------------------------------------------------------------- long rows

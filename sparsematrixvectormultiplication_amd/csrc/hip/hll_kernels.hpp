@@ -288,12 +288,23 @@ __global__ __launch_bounds__(kBlock) void hll_lds_local(int num_blocks, int xcd_
     extern __shared__ __align__(16) unsigned char hll_local_lds[];
     T *stage = reinterpret_cast<T *>(hll_local_lds);  // x lines first, then the products
 
+    // the head, as in csr_stream_local (csr_kernels.hpp): the arguments in one scalar round trip, then the window's
+    // records -- desc[b], ldesc[b] and, with a pattern plan, pdesc[b] -- back to back behind one wait; the two asm
+    // statements pin the loads that feed them in front of them
+    asm("" : "+s"(xcd_chunk) : "s"(num_blocks), "s"(desc), "s"(ldesc), "s"(lines), "s"(row_seg), "s"(lja), "s"(AS), "s"(x),
+        "s"(y), "s"(pdesc), "s"(rinfo), "s"(ptab), "s"(stage_bytes));
     const int b = xcd_chunked(blockIdx.x, xcd_chunk);
     if (b >= num_blocks) return;
     const int t = threadIdx.x;
     const int4 d = desc[b];
     const int4 ld = ldesc[b];  // {first line, lines, slots of the window counted from its even base, -}
-    const int row_first = d.x, nrows = d.y;
+    int2 pd = make_int2(0, 0);
+    if constexpr (PAT) pd = pdesc[b];
+    int nrows = d.y;  // (passes through: the row's segment word, the first vector load, needs it)
+    // (every word of every record, the unused ld.w too: a register that is dead while its load is in flight is reused
+    // at once, and the write to it waits for the load)
+    asm("" : "+s"(nrows) : "s"(d.x), "s"(d.z), "s"(d.w), "s"(ld.x), "s"(ld.y), "s"(ld.z), "s"(ld.w), "s"(pd.x), "s"(pd.y));
+    const int row_first = d.x;
     const long long first_slot = ((long long)d.w << 32) | (unsigned)d.z;
     const long long base = first_slot & ~1LL;
 
@@ -321,7 +332,6 @@ __global__ __launch_bounds__(kBlock) void hll_lds_local(int num_blocks, int xcd_
     const unsigned short *wj = lja + base;
     const T *wa = AS + base;
     if constexpr (PAT) {
-        const int2 pd = pdesc[b];
         pat_ctx pc;
         pc.slots = reinterpret_cast<unsigned short *>(hll_local_lds + stage_bytes);
         pc.ptab8 = reinterpret_cast<const uint4 *>(ptab + pd.x);

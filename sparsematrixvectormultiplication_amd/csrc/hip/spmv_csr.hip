@@ -189,7 +189,8 @@ static int pattern_segment_cap(int value_bytes, int local_cap, int stage_lines) 
     return cap;
 }
 int csr_pattern_segment_cap(const spmv_csr_dev *m) {
-    return pattern_segment_cap(m->value_bytes, m->local_cap, m->xw.stage_lines);
+    const int cap = pattern_segment_cap(m->value_bytes, m->local_cap, m->xw.stage_lines);
+    return g_local_segment_cap > 0 ? std::min(cap, g_local_segment_cap / (int)sizeof(uint4)) : cap;  // ("local_segment_cap")
 }
 extern "C" int spmv_hip_csr_pattern_segment_cap(int value_bytes, int local_cap, int stage_lines) {
     if ((value_bytes != 4 && value_bytes != 8) || local_cap <= 0 || local_cap > kStreamCapMax || stage_lines < 0 ||
@@ -1094,22 +1095,21 @@ extern "C" int spmv_hip_csr_stamp_blocks(spmv_csr_dev *m, int warm, unsigned lon
     int rc = 0;
     // (warm >= 1000, measurement only: the stamped launch does not read the slot stream -- the time the kernel would take
     // if the slots came from a per-block pattern; y is then wrong)
-    const int probe = warm >= 1000 ? 1 : 0;
+    // (warm >= 2000, i.e. probe & 2: the second word of every stamp is the time the block's records were back -- the end
+    // of its head -- instead of its end; y stays right)
+    const int probe = warm / 1000 & 3;
     warm %= 1000;
     for (int i = 0; i < warm && !rc; ++i) rc = csr_launch_any(m, SPMV_CSR_STREAM, m->x, m->y, g_stream);
     if (!rc) {
         const XWindowLaunch L = p.launch_shape(p.blocks, m->local_cap, 8, m->nz);
         double *y = (double *)m->y + m->row0;
-        if (L.nt)
-            hipLaunchKernelGGL((csr_stream_local<double, true, 2048, true>), dim3(L.grid), dim3(kBlock), L.lds, g_stream, p.blocks, L.chunk,
-                               (const int *)nullptr, p.ldesc4, p.ldesc, p.lines, m->row_ptr, p.slot, (const double *)m->val,
-                               (const double *)m->x, y, d, probe, (const int2 *)nullptr, (const unsigned *)nullptr,
-                               (const unsigned short *)nullptr, 0, (const int2 *)nullptr, (const uint4 *)nullptr, p.lbase);
-        else
-            hipLaunchKernelGGL((csr_stream_local<double, false, 2048, true>), dim3(L.grid), dim3(kBlock), L.lds, g_stream, p.blocks, L.chunk,
-                               (const int *)nullptr, p.ldesc4, p.ldesc, p.lines, m->row_ptr, p.slot, (const double *)m->val,
-                               (const double *)m->x, y, d, probe, (const int2 *)nullptr, (const unsigned *)nullptr,
-                               (const unsigned short *)nullptr, 0, (const int2 *)nullptr, (const uint4 *)nullptr, p.lbase);
+        with_flag(L.nt, [&](auto nt) {
+            hipLaunchKernelGGL((csr_stream_local<double, decltype(nt)::value, 2048, true>), dim3(L.grid), dim3(kBlock), L.lds, g_stream,
+                               p.blocks, L.chunk, (const int *)nullptr, p.ldesc4, p.ldesc, p.lines, m->row_ptr, p.slot,
+                               (const double *)m->val, (const double *)m->x, y, d, probe, (const int2 *)nullptr,
+                               (const unsigned *)nullptr, (const unsigned short *)nullptr, 0, (const int2 *)nullptr,
+                               (const uint4 *)nullptr, p.lbase, p.lbase ? kXwShared : 0);
+        });
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
         if (e == hipSuccess) e = hipMemcpy(stamps_host, d, bytes, hipMemcpyDeviceToHost);
@@ -1291,6 +1291,9 @@ void launch_x_window(const spmv_csr_dev *m, const T *x, T *y, hipStream_t s, int
     const int *lids = part < 0 ? nullptr : part == 0 ? m->interior_ids : m->boundary_ids;
     if (lcount <= 0) return;
     const XWindowLaunch L = p.launch_shape(lcount, m->local_cap, (int)sizeof(T), m->nz);
+    // what the plan has is said here, in `shape` (the kernel tests no pointer and runs the body compiled for that
+    // shape): shared line lists, and -- a pattern plan -- segments (sdesc and pseg are allocated together)
+    const int shape = (p.lbase ? kXwShared : 0) | (L.patterns && pat.sdesc && pat.pseg ? kXwSegs : 0);
     with_value<1024, 3072, 2048>(m->local_cap, [&](auto cap) {
         with_flag(L.nt, [&](auto nt) {
             constexpr int CAP = decltype(cap)::value;
@@ -1299,12 +1302,12 @@ void launch_x_window(const spmv_csr_dev *m, const T *x, T *y, hipStream_t s, int
                 hipLaunchKernelGGL((csr_stream_local<T, NT, CAP, false, true>), dim3(L.grid), dim3(kBlock), L.pat_lds, s, lcount, L.chunk,
                                    lids, p.ldesc4, p.ldesc, p.lines, m->row_ptr, p.slot, (const T *)m->val, x, y,
                                    (unsigned long long *)nullptr, 0, pat.pdesc, pat.rinfo, pat.ptab, (int)L.lds, pat.sdesc,
-                                   (const uint4 *)pat.pseg, p.lbase);
+                                   (const uint4 *)pat.pseg, p.lbase, shape);
             else
                 hipLaunchKernelGGL((csr_stream_local<T, NT, CAP>), dim3(L.grid), dim3(kBlock), L.lds, s, lcount, L.chunk, lids,
                                    p.ldesc4, p.ldesc, p.lines, m->row_ptr, p.slot, (const T *)m->val, x, y,
                                    (unsigned long long *)nullptr, 0, (const int2 *)nullptr, (const unsigned *)nullptr,
-                                   (const unsigned short *)nullptr, 0, (const int2 *)nullptr, (const uint4 *)nullptr, p.lbase);
+                                   (const unsigned short *)nullptr, 0, (const int2 *)nullptr, (const uint4 *)nullptr, p.lbase, shape);
         });
     });
 }

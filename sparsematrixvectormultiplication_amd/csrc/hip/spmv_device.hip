@@ -106,6 +106,7 @@ int g_tile_places = 0;
 int g_tile_min_pass = 256;
 int g_local_patterns = -1;
 int g_local_share = -1;
+int g_local_segment_cap = 0;
 int g_tile_mid_items = 0;
 int g_tile_items = 1008;  // two rounds of the 512 places: 1.222 ms on the power-law matrix against 1.248 with 4096, 1.231 with 504
 int g_tile_pack = 1;
@@ -252,6 +253,9 @@ extern "C" int spmv_hip_set_tuning(const char *key, int value) {
     } else if (!strcmp(key, "local_share")) {
         if (value < -1 || value > 2) return fail("set_tuning: local_share must be -1 (auto: on), 0, 1 or 2 (on, hashing the length only)");
         g_local_share = value;  // takes effect at the next upload
+    } else if (!strcmp(key, "local_segment_cap")) {
+        if (value < 0) return fail("set_tuning: local_segment_cap must be 0 (the LDS budget's) or a number of bytes");
+        g_local_segment_cap = value;  // takes effect at the next upload
     } else if (!strcmp(key, "tile_mid_items")) {
         if (value < 0 || value > 65536) return fail("set_tuning: tile_mid_items must be 0 (auto: three rounds of the CUs) .. 65536");
         g_tile_mid_items = value;

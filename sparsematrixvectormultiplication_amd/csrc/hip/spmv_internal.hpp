@@ -67,7 +67,8 @@ extern int g_tile_long;       // 1: the rows beyond the tile limit get a tile pl
 extern int g_tile_pack;       // 1: passes that can be staged store head | row | column offset in one 32-bit word (no key read)
 extern int g_tile_density;    // a pass is staged when it holds at least one entry per this many columns of its window
 extern int g_tile_mid_lo;     // a scattered matrix's rows longer than this (up to tile_lmax) form the middle tier ("tile_mid_lo")
-extern int g_local_share;     // x-window plans: equal segments / relative line lists stored once: -1 auto (on), 0 off, 1 on, 2 on with a hash of the length only ("local_share")
+extern int g_local_segment_cap;  // pattern plans of CSR handles: no segment wider than this many bytes; 0: the LDS budget's cap ("local_segment_cap")
+extern int g_local_share;    // x-window plans: equal segments / relative line lists stored once: -1 auto (on), 0 off, 1 on, 2 on with a hash of the length only ("local_share")
 extern int g_local_patterns;  // x-window plans: -1 auto (a pattern plan where it holds a quarter of the slots at most), 0 never, 1 always ("local_patterns")
 extern int g_tile_expand;     // plans with gather passes: -1 auto, 0 never, 1 always: x expanded into entry order ahead of csr_tile ("tile_expand")
 extern int g_tile_gather_ahead;  // 1: plans with gather passes run the csr_tile instantiation that gathers one pass early
