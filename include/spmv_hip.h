@@ -840,7 +840,8 @@ int spmv_fsai_plan(int n, const int *row_ptr, const int *col, const double *val,
  *                                    Jacobi and block-Jacobi, rows x k values (at least 16 bytes) and a 128-byte line
  *                                    for FSAI, the sum of the level vectors for AMG (every vector n_l rounded up to 32 rows
  *                                    plus 32 rows, times k values; the part behind a vector's values should be zero:
- *                                    the x-window kernels read whole 128-byte lines); -1 for SSOR and ILU(0)
+ *                                    the x-window kernels read whole 128-byte lines), the three arrays of
+ *                                    CHEBYSHEV (below); -1 for SSOR and ILU(0)
  *   spmv_hip_csr_precond_build_amg   -1 (*out stays NULL, the HIP error state stays clean, the handle still works): the
  *                                    refusals above, a parameter out of range, a non-square or tiles-only handle
  *   spmv_hip_precond_amg_info        info[SPMV_PRECOND_AMG_INFO_WORDS] = levels, the first chained level (-1: none),
@@ -900,6 +901,60 @@ int spmv_hip_precond_amg_setup_info(const spmv_precond *P, int *info);
 int spmv_hip_precond_amg_level(const spmv_precond *P, int level, int which, int *row_ptr, int *col, void *val,
                                double *scalars);
 int spmv_hip_precond_work_bytes(const spmv_precond *P, int k, long long *bytes);
+/* A Chebyshev polynomial in the Jacobi-scaled matrix (the same spmv_precond type: info (block = 1), apply, apply_on,
+ * apply_multi, apply_multi_on, free; spmv_hip_csr_pcg, _pbicgstab, _minres, _pcg_multi and _lobpcg take it): m = degree
+ * steps of Jacobi-preconditioned Chebyshev iteration on A z = r from z = 0, A the handle's own diagonal block made
+ * canonical as for the triangular, FSAI and AMG builds (local columns, sorted rows, repeats added in entry order in
+ * fp64).  With T the handle's dtype, g_i = T(1 / a_ii) and [lmin, lmax] the interval of D^-1 A the polynomial is fitted to:
+ *   theta = (lmax + lmin) / 2;  delta = (lmax - lmin) / 2;  sigma = theta / delta
+ *   rho_0 = 1 / sigma;  a_0 = 0;  b_0 = 1 / theta
+ *   for j = 1 .. m-1:  rho_j = 1 / (2 sigma - rho_{j-1});  a_j = rho_j rho_{j-1};  b_j = 2 rho_j / delta
+ *   step 0:        d = b_0 g.r;                          z = d
+ *   step j >= 1:   q = A z;   d = a_j d + b_j g.(r - q);  z = z + d
+ * The coefficients are computed on the host in double, each line one rounded operation in the order written, none
+ * fused.  The vector passes compute in double from the stored values and round once to T for every value they store; z
+ * takes the rounded d.  1 - t p(t) = T_m((theta - t) / delta) / T_m(sigma), so M^-1 = p(D^-1 A) D^-1 is symmetric for a
+ * symmetric A and positive definite whenever the spectrum of D^-1 A lies in (0, lmax]; an lmax that is too small can make
+ * it indefinite at even degree, and spmv_hip_csr_pcg then reports SPMV_PCG_BREAKDOWN as for any indefinite M.  Degree 1 is
+ * Jacobi times 1 / theta.  For a nonsymmetric A the same formula is used (an interval, no ellipse) and serves
+ * spmv_hip_csr_pbicgstab from the right.
+ * lmax = 0: the Gershgorin bound max_i sum_j |a_ij| / a_ii of the canonical block in fp64, the sums in stored order (the
+ * rho_0 of the AMG setup, computed by the same function): a true upper bound, so M stays positive definite.  lmin = 0:
+ * lmax / ratio.  Explicit values are taken as given.
+ * On the device A is P's own upload of the canonical block rounded to T (an ordinary whole rows x rows handle with
+ * whatever plan upload picks: A z runs through its AUTO launch, for k vectors through spmv_hip_csr_spmm_on), so P may
+ * outlive the handle it was built from, and on a row-range handle it is the polynomial of the diagonal block.  P owns
+ * z, d and q, each with the 128-byte tail the x-window kernels read: one P serves one stream at a time.  No product
+ * reads a caller's buffer: the iterate lives in P's z and the last pass writes the caller's z (with degree 1 it is the
+ * only pass).  An apply is m - 1 products and m element-wise launches (16-byte pieces when r and z are 16-byte aligned,
+ * single values otherwise: the same bits); no LDS, no atomics, no reduction: two applies give the same bits.  r and z
+ * must not overlap.  The launches do not look at a solver's stop state: after a stop they rewrite z with the bits it
+ * holds.  For k right-hand sides the three vectors live in the caller's d_work (spmv_hip_precond_work_bytes: three
+ * arrays of rows x k values rounded up to whole 128-byte lines plus one line each); column j's values do not depend on
+ * j or k, and k = 1 runs the launches of the one-wide apply.
+ *   spmv_chebyshev_coefficients            a[degree], b[degree] of the loop above (no device needed); -1: a NULL array,
+ *                                          degree outside [1, SPMV_CHEBYSHEV_MAX_DEGREE], lmin or lmax not finite,
+ *                                          lmin <= 0 or lmin >= lmax
+ *   spmv_hip_csr_precond_build_chebyshev   -1 (*out stays NULL, the HIP error state stays clean, the handle still works):
+ *                                          a row without a diagonal entry, or whose diagonal is not positive or not finite
+ *                                          (the first such row, local and global, is named), a non-square or tiles-only
+ *                                          handle; degree outside [1, 32], ratio <= 1 or not finite, lmax < 0 or not
+ *                                          finite, lmin < 0 or not finite, lmin >= lmax after the defaults (the value and
+ *                                          the allowed range are named)
+ *   spmv_hip_precond_cheb_info             info[SPMV_PRECOND_CHEB_INFO_WORDS] = degree, lmin, lmax, the Gershgorin bound
+ *                                          (also when lmax was given), products per apply (degree - 1), the plan of P's
+ *                                          upload (0 gather kernels, 1 x-window, 2 x-window with a pattern plan, 3
+ *                                          csr_tile), microseconds of download with canonical rows and the bound, and of
+ *                                          the upload with the vectors
+ * Not here: eigenvalue estimates (power iteration, Lanczos), Chebyshev smoothing inside the AMG cycle, a product fused
+ * with the recurrence, the solvers' dots fused into the last pass, HLL handles, an ellipse for nonsymmetric spectra, a
+ * halo exchange. */
+enum { SPMV_PRECOND_CHEBYSHEV = 7 };
+enum { SPMV_PRECOND_CHEB_INFO_WORDS = 8, SPMV_CHEBYSHEV_MAX_DEGREE = 32 };
+int spmv_chebyshev_coefficients(int degree, double lmin, double lmax, double *a, double *b);
+int spmv_hip_csr_precond_build_chebyshev(const spmv_csr_dev *m, int degree, double lmin, double lmax, double ratio,
+                                         spmv_precond **out);
+int spmv_hip_precond_cheb_info(const spmv_precond *P, double *info);
 /* Preconditioned CG for a symmetric positive definite A and M, x0 = 0 (P = NULL: M = I, z is r itself):
  *   r = b, z = M^-1 r, p = z, rz = r.z, rr0 = r.r
  *   each step: q = A p, alpha = rz / p.q, x += alpha p, r -= alpha q, z = M^-1 r, rz' = r.z, rr = r.r,
@@ -924,7 +979,7 @@ int spmv_hip_csr_pcg(spmv_csr_dev *m, const spmv_precond *P, int variant, int it
  * in the layout of spmv_hip_csr_cg_multi.  B, X and every loop vector are row-major n x k; the product is
  * spmv_hip_csr_spmm_on on library-owned P (N x k) and Q (M_total x k).  The communicator, the bounds scaled by k, the
  * all-gatherv of P and the dot products added in rank order are those of spmv_hip_csr_cg_multi.
- * P: NULL, JACOBI, BLOCK_JACOBI, FSAI or AMG.  Jacobi is fused into the x / r update with both dots; a block-Jacobi apply is
+ * P: NULL, JACOBI, BLOCK_JACOBI, FSAI, AMG or CHEBYSHEV.  Jacobi is fused into the x / r update with both dots; a block-Jacobi apply is
  * a pass of its own that makes the dots; an FSAI apply is Z = G^T (G R), two SpMMs through P's handles, an AMG apply its
  * V-cycle on k columns, then one pass for the dots.  SSOR and ILU0 are refused: their triangular solves take one right-hand side.
  * Column j's sums add in an order that does not depend on j: permuting the columns of B permutes X, both histories,
@@ -950,7 +1005,7 @@ int spmv_hip_csr_pcg(spmv_csr_dev *m, const spmv_precond *P, int variant, int it
  *                                    is not touched.  The Jacobi and block-Jacobi kernels move 16-byte pieces of a
  *                                    row when k values are whole pieces AND d_R and d_Z are 16-byte aligned; else they
  *                                    move single elements (the same bits, more instructions).  -1: k outside [1, 64],
- *                                    arrays not aligned to the element size, FSAI or AMG without d_work, SSOR or ILU0.
+ *                                    arrays not aligned to the element size, FSAI, AMG or CHEBYSHEV without d_work, SSOR or ILU0.
  *   spmv_hip_precond_apply_multi     the same on host arrays of rows x k values: allocates, copies, syncs */
 int spmv_hip_csr_pcg_multi(spmv_csr_dev *m, const spmv_precond *P, int k, int iters, double tol, const int *bounds,
                            const void *B_host, void *X_host, double *rr_hist, double *rz_hist, int *steps, int *status,
@@ -1005,7 +1060,8 @@ int spmv_hip_csr_minres(spmv_csr_dev *m, const spmv_precond *P, int variant, int
                         const int *bounds, const void *b_host, void *x_host, double *rr_hist, int *info,
                         float *ms_total);
 /* LOBPCG (Knyazev 2001) for the k smallest (largest = 0) or largest eigenpairs of a symmetric A held by an fp64 CSR
- * handle, with an optional symmetric positive definite preconditioner (Jacobi, block-Jacobi, FSAI or AMG; smallest only).
+ * handle, with an optional symmetric positive definite preconditioner (Jacobi, block-Jacobi, FSAI, AMG or Chebyshev; smallest
+ * only).
  * Six row-major n x k arrays X, W, P, AX, AW, AP (element (i, j) at i k + j, the SpMM's layout).  Per step one SpMM
  * (spmv_hip_csr_spmm_on), one k-wide apply (spmv_hip_precond_apply_multi_on), a Gram pass and an update pass over the
  * basis S = [X | W | P], AS = [AX | AW | AP] (lobpcg_kernels.hpp), and a Rayleigh-Ritz step on the host.

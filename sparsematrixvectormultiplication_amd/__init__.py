@@ -17,7 +17,7 @@ from .device import (BICG_BREAKDOWN_OMEGA, BICG_BREAKDOWN_RHO, BICG_CONVERGED, B
                      MINRES_BREAKDOWN, MINRES_CONVERGED, MINRES_RAN_ALL,  # noqa: F401
                      LOBPCG_BREAKDOWN, LOBPCG_CONVERGED, LOBPCG_RAN_ALL, lobpcg_rr, lobpcg_gram, lobpcg_update,  # noqa: F401
                      PCG_BREAKDOWN, PCG_CONVERGED, PCG_RAN_ALL, PRECOND_BLOCK_JACOBI, PRECOND_JACOBI,  # noqa: F401
-                     PRECOND_AMG, PRECOND_FSAI, PRECOND_ILU0, PRECOND_SSOR, amg_plan, spgemm_plan, MATMUL_MS, MATMUL_STATS, ORDER_MULTICOLOR, ORDER_NATURAL, TRSV_LOWER, TRSV_NONUNIT,  # noqa: F401
+                     PRECOND_AMG, PRECOND_CHEBYSHEV, PRECOND_KINDS, chebyshev_coefficients, PRECOND_FSAI, PRECOND_ILU0, PRECOND_SSOR, amg_plan, spgemm_plan, MATMUL_MS, MATMUL_STATS, ORDER_MULTICOLOR, ORDER_NATURAL, TRSV_LOWER, TRSV_NONUNIT,  # noqa: F401
                      TRSV_UNIT, TRSV_UPPER, Preconditioner, TriangularSolver,  # noqa: F401
                      ADD_MS, ADD_STATS, identity,  # noqa: F401
                      PERMUTE_MS, RCM_MS, RCM_STATS, rcm_plan, rcm_chain_nodes,  # noqa: F401

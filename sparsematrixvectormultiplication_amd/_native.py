@@ -271,6 +271,10 @@ _PROTOTYPES = {
     "spmv_hip_precond_amg_setup_info": (C.c_int, [C.c_void_p, c_int_p]),
     "spmv_hip_precond_amg_level": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_int_p, C.c_void_p, c_double_p]),
     "spmv_hip_precond_work_bytes": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_longlong)]),
+    "spmv_chebyshev_coefficients": (C.c_int, [C.c_int, C.c_double, C.c_double, c_double_p, c_double_p]),
+    "spmv_hip_csr_precond_build_chebyshev": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double,
+                                                       C.POINTER(C.c_void_p)]),
+    "spmv_hip_precond_cheb_info": (C.c_int, [C.c_void_p, c_double_p]),
     "spmv_hip_csr_pcg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, c_int_p, C.c_void_p,
                                    C.c_void_p, c_double_p, c_double_p, c_int_p, c_float_p]),
     "spmv_hip_csr_pcg_multi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, c_int_p, C.c_void_p,

@@ -1,5 +1,6 @@
 // canon_rows.hpp -- the canonical diagonal block of a CSR handle on the host, shared by the builds that start from it
-// (spmv_trsv.hip: the triangular solves, SSOR, ILU(0); spmv_fsai.hip: FSAI).  Host code only.
+// (spmv_trsv.hip: the triangular solves, SSOR, ILU(0); spmv_fsai.hip: FSAI; spmv_amg.hip: AMG; spmv_cheb.hip:
+// CHEBYSHEV).  Host code only.
 #pragma once
 #include "spmv_internal.hpp"
 
@@ -63,6 +64,13 @@ inline int first_missing_diag(const Canon &B) {
     for (int i = 0; i < B.n; ++i)
         if (B.diag[i] < 0) return i;
     return -1;
+}
+
+// the plan a build's own upload got (fsai_info, cheb_info): 0 the gather kernels, 1 an x-window plan, 2 an x-window plan
+// with a pattern plan, 3 csr_tile
+inline int plan_of(const spmv_csr_dev *m) {
+    if (!m) return 0;
+    return m->xw.blocks > 0 ? (m->xw.pat.ptab ? 2 : 1) : m->tile.blocks > 0 ? 3 : 0;
 }
 
 inline int handle_ok(const spmv_csr_dev *m, const char *what) {

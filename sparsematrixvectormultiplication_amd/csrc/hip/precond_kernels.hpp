@@ -185,6 +185,7 @@ struct spmv_precond {
     struct spmv_tri_precond *tri = nullptr;  // SSOR / ILU0: the two triangular solves (spmv_trsv.hip); owned, inv is NULL
     struct spmv_fsai_precond *fsai = nullptr;  // FSAI: the handles of G and G^T (spmv_fsai.hip); owned, inv is NULL
     struct spmv_amg_precond *amg = nullptr;    // AMG: the hierarchy and its level vectors (spmv_amg.hip); owned, inv is NULL
+    struct spmv_cheb_precond *cheb = nullptr;  // CHEBYSHEV: its upload of the block, g and three vectors (spmv_cheb.hip); owned
 };
 
 // spmv_trsv.hip: z = M^-1 r by P's two solves on stream s (flags as pc_apply: a stopped solver's launches return)
@@ -205,25 +206,41 @@ int precond_amg_apply(const spmv_precond *P, const void *r, void *z, hipStream_t
 int precond_amg_apply_multi(const spmv_precond *P, int k, const void *R, void *Z, void *work, hipStream_t s);
 long long precond_amg_work_values(const spmv_precond *P);
 void precond_amg_free(struct spmv_amg_precond *ap);
+// spmv_cheb.hip: z = p(D^-1 A) D^-1 r, degree - 1 products of P's own handle between fused passes on stream s, the
+// iterate in P's own vectors (as FSAI's and AMG's, the launches do not look at a solver's flags)
+int precond_cheb_apply(const spmv_precond *P, const void *r, void *z, hipStream_t s);
+// the same for rows x k row-major R and Z; work: three arrays of precond_cheb_vec_bytes(P, k) bytes, P's own vectors
+// are not used (k = 1: the launches of precond_cheb_apply)
+int precond_cheb_apply_multi(const spmv_precond *P, int k, const void *R, void *Z, void *work, hipStream_t s);
+void precond_cheb_free(struct spmv_cheb_precond *cp);
+// bytes of one of the three arrays: rows x k values rounded up to whole 128-byte lines, and a line tail
+inline long long precond_cheb_vec_bytes(const spmv_precond *P, int k) {
+    const long long bytes = std::max<long long>((long long)P->rows * k * P->value_bytes, 16);
+    return (bytes + kLineBytes - 1) / kLineBytes * kLineBytes + kLineBytes;
+}
 
-// SSOR, ILU(0), FSAI and AMG take a path of their own wherever Jacobi / block-Jacobi are told apart by P->block: an
+// SSOR, ILU(0), FSAI, AMG and CHEBYSHEV take a path of their own wherever Jacobi / block-Jacobi are told apart by P->block: an
 // apply through P's own launches (precond_own_apply), then one pass for whatever dots the solver needs
 inline bool precond_has_own_apply(const spmv_precond *P) {
-    return P && (P->tri != nullptr || P->fsai != nullptr || P->amg != nullptr);
+    return P && (P->tri != nullptr || P->fsai != nullptr || P->amg != nullptr || P->cheb != nullptr);
 }
 inline int precond_own_apply(const spmv_precond *P, const void *r, void *z, const int *flags, hipStream_t s) {
-    return P->amg ? precond_amg_apply(P, r, z, s) : P->fsai ? precond_fsai_apply(P, r, z, s)
-                                                             : precond_tri_apply(P, r, z, flags, s);
+    return P->cheb ? precond_cheb_apply(P, r, z, s) : P->amg ? precond_amg_apply(P, r, z, s)
+         : P->fsai ? precond_fsai_apply(P, r, z, s) : precond_tri_apply(P, r, z, flags, s);
 }
-// FSAI and AMG apply to k vectors through products alone; both need a workspace of precond_work_bytes(P, k)
-inline bool precond_has_own_apply_multi(const spmv_precond *P) { return P && (P->fsai != nullptr || P->amg != nullptr); }
+// FSAI, AMG and CHEBYSHEV apply to k vectors through products alone; all need a workspace of precond_work_bytes(P, k)
+inline bool precond_has_own_apply_multi(const spmv_precond *P) {
+    return P && (P->fsai != nullptr || P->amg != nullptr || P->cheb != nullptr);
+}
 inline int precond_own_apply_multi(const spmv_precond *P, int k, const void *R, void *Z, void *work, hipStream_t s) {
-    return P->amg ? precond_amg_apply_multi(P, k, R, Z, work, s) : precond_fsai_apply_multi(P, k, R, Z, work, s);
+    return P->cheb ? precond_cheb_apply_multi(P, k, R, Z, work, s)
+         : P->amg ? precond_amg_apply_multi(P, k, R, Z, work, s) : precond_fsai_apply_multi(P, k, R, Z, work, s);
 }
 // bytes of that workspace for k columns: 0 for Jacobi and block-Jacobi, FSAI's G R with a line tail, the level vectors
-// of AMG; -1 for SSOR and ILU(0), which have no k-wide apply
+// of AMG, the three arrays of CHEBYSHEV; -1 for SSOR and ILU(0), which have no k-wide apply
 inline long long precond_work_bytes(const spmv_precond *P, int k) {
     if (P->tri) return -1;
+    if (P->cheb) return 3 * precond_cheb_vec_bytes(P, k);
     if (P->amg) return std::max<long long>(precond_amg_work_values(P) * k * P->value_bytes, 16);
     if (P->fsai) return std::max<long long>((long long)P->rows * k * P->value_bytes, 16) + kLineBytes;
     return 0;

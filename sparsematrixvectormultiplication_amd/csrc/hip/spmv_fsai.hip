@@ -64,12 +64,6 @@ struct BuildArrays {
     }
 };
 
-// the plan a handle got: 0 the gather kernels, 1 an x-window plan, 2 an x-window plan with a pattern plan, 3 csr_tile
-int plan_of(const spmv_csr_dev *m) {
-    if (!m) return 0;
-    return m->xw.blocks > 0 ? (m->xw.pat.ptab ? 2 : 1) : m->tile.blocks > 0 ? 3 : 0;
-}
-
 template <typename T>
 int fsai_build(const spmv_csr_dev *m, int cap, spmv_precond **out) {
     const double t0 = now_ms();

@@ -68,7 +68,8 @@ int mpc_apply_check(const spmv_precond *P, int k, const void *R, const void *Z, 
 }
 
 struct MpcgBuffers {
-    void *P, *Q, *X, *R, *Z, *work;  // Z is R without a preconditioner; work: FSAI's G R, AMG's level vectors
+    // Z is R without a preconditioner; work: FSAI's G R, AMG's level vectors, CHEBYSHEV's three arrays
+    void *P, *Q, *X, *R, *Z, *work;
     double *s, *part_rr, *part_rz, *gath, *hrr, *hrz;
     int *flags;
 };
@@ -227,6 +228,9 @@ extern "C" int spmv_hip_precond_apply_multi_on(const spmv_precond *P, int k, con
         return fail("precond_apply_multi_on: an FSAI apply needs d_work (rows x k values and one 128-byte line)");
     if (P->amg && P->rows && !d_work)
         return fail("precond_apply_multi_on: an AMG apply needs d_work (spmv_hip_precond_work_bytes: its level vectors)");
+    if (P->cheb && P->rows && !d_work)
+        return fail("precond_apply_multi_on: a CHEBYSHEV apply needs d_work (spmv_hip_precond_work_bytes: its three "
+                    "arrays)");
     if (((uintptr_t)d_R | (uintptr_t)d_Z | (uintptr_t)d_work) % (uintptr_t)P->value_bytes)
         return fail("precond_apply_multi_on: R, Z and work must be aligned to %d bytes", P->value_bytes);
     hipStream_t s = stream ? (hipStream_t)stream : g_stream;

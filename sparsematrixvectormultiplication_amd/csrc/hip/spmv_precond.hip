@@ -8,7 +8,8 @@
 //
 // SSOR and ILU(0) (spmv_hip_csr_precond_build_tri) are the same spmv_precond with P->tri set: spmv_trsv.hip builds and
 // applies them, free / info / apply / apply_on here hand them on.  FSAI (spmv_hip_csr_precond_build_fsai) likewise, with
-// P->fsai set: spmv_fsai.hip.  AMG (spmv_hip_csr_precond_build_amg) with P->amg set: spmv_amg.hip.
+// P->fsai set: spmv_fsai.hip.  AMG (spmv_hip_csr_precond_build_amg) with P->amg set: spmv_amg.hip.  CHEBYSHEV
+// (spmv_hip_csr_precond_build_chebyshev) with P->cheb set: spmv_cheb.hip.
 #include "spmv_internal.hpp"
 
 #include <climits>
@@ -131,6 +132,7 @@ extern "C" void spmv_hip_precond_free(spmv_precond *P) {
     precond_tri_free(P->tri);
     precond_fsai_free(P->fsai);
     precond_amg_free(P->amg);
+    precond_cheb_free(P->cheb);
     delete P;
 }
 

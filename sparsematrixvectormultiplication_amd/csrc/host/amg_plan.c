@@ -154,6 +154,32 @@ static int csr_transpose(const amg_csr *A, amg_csr *B) {
     return 0;
 }
 
+/* d[i] = a_ii (d NULL: not wanted) and *rho = max_i (sum_j |a_ij|) / a_ii, the sums in stored order, a NaN quotient
+ * kept.  Returns -1, or the first row whose diagonal is not stored (*missing = 1) or not finite and > 0
+ * (*missing = 0); rows behind it are not read (amg_plan_parts.h: the Chebyshev build calls it too) */
+int amg_gershgorin(const amg_csr *A, double *d, double *rho, int *missing) {
+    double top = 0.0;
+    *missing = 0;
+    for (int i = 0; i < A->rows; ++i) {
+        double di = NAN, sum = 0.0;
+        int have = 0;
+        for (int e = A->rp[i]; e < A->rp[i + 1]; ++e) {
+            if (A->col[e] == i) di = A->val[e], have = 1;
+            sum += fabs(A->val[e]);
+        }
+        if (!have || !isfinite(di) || !(di > 0.0)) {
+            *missing = !have;
+            *rho = top;
+            return i;
+        }
+        if (d) d[i] = di;
+        const double q = sum / di;
+        if (q > top || isnan(q)) top = q;
+    }
+    *rho = top;
+    return -1;
+}
+
 /* inv = A^-1 dense by Gauss-Jordan on [A | I] with partial pivoting; 1: a zero or non-finite pivot; -1: no memory
  * (amg_plan_parts.h: the device setup calls it too) */
 int amg_dense_inverse(const amg_csr *A, double **out) {
@@ -349,24 +375,14 @@ int spmv_amg_plan_build(int n, const int *row_ptr, const int *col, const double 
         agg = malloc(((size_t)nl + 1) * sizeof(int));
         if (!d || !s_rp || !agg) goto nomem;
         double rho = 0.0;
-        for (int i = 0; i < nl && !rc; ++i) {
-            double di = NAN, sum = 0.0;
-            int have = 0;
-            for (int e = A->rp[i]; e < A->rp[i + 1]; ++e) {
-                if (A->col[e] == i) di = A->val[e], have = 1;
-                sum += fabs(A->val[e]);
-            }
-            if (!have || !isfinite(di) || !(di > 0.0)) {
-                const char *why = !have ? AMG_WHY_NO_DIAGONAL : AMG_WHY_BAD_DIAGONAL;
-                if (l == 0) rc = refuse(AMG_REFUSE_ROW, i, why);
-                else rc = refuse(AMG_REFUSE_COARSE_ROW, l, i, why);
-                break;
-            }
-            d[i] = di;
-            const double q = sum / di;
-            if (q > rho || isnan(q)) rho = q;
+        int missing = 0;
+        const int bad_row = amg_gershgorin(A, d, &rho, &missing);
+        if (bad_row >= 0) {
+            const char *why = missing ? AMG_WHY_NO_DIAGONAL : AMG_WHY_BAD_DIAGONAL;
+            if (l == 0) rc = refuse(AMG_REFUSE_ROW, bad_row, why);
+            else rc = refuse(AMG_REFUSE_COARSE_ROW, l, bad_row, why);
+            break;
         }
-        if (rc) break;
         if (!isfinite(rho) || !(rho > 0.0)) {
             rc = refuse(AMG_REFUSE_NOT_FINITE, l);
             break;

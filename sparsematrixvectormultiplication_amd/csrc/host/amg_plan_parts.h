@@ -1,8 +1,9 @@
 /*
  * amg_plan_parts.h -- the parts of the AMG host setup (amg_plan.c) that the device setup (hip/spmv_amg_setup.hip) calls
- * as they are: the aggregation, which is serial by definition, and the dense inverse of the coarsest level; and the
- * texts of the setup's refusals, so that both setups refuse in the same words.  Private to the library: not installed,
- * not exported (libspmv_amd.map keeps the two functions local).
+ * as they are: the aggregation, which is serial by definition, and the dense inverse of the coarsest level; the
+ * Gershgorin bound, which the Chebyshev build (hip/spmv_cheb.hip) shares; and the texts of the setup's refusals, so that
+ * both setups refuse in the same words.  Private to the library: not installed, not exported (libspmv_amd.map keeps
+ * the functions local).
  */
 #ifndef SPMV_AMG_PLAN_PARTS_H
 #define SPMV_AMG_PLAN_PARTS_H
@@ -17,6 +18,10 @@ typedef struct {
     double *val;
 } amg_csr;
 
+/* d[i] = a_ii (d NULL: not wanted) and *rho = max_i (sum_j |a_ij|) / a_ii in stored order, the Gershgorin bound of
+ * D^-1 A; returns -1, or the first row whose diagonal is missing (*missing = 1) or not finite and > 0 (*missing = 0).
+ * The Chebyshev build (hip/spmv_cheb.hip) takes its automatic lmax from it */
+int amg_gershgorin(const amg_csr *A, double *d, double *rho, int *missing);
 /* agg[n] (-1: in no aggregate) from the strength graph (neighbours ascending); returns the number of aggregates, -1
  * without memory */
 int amg_aggregate(int n, const int *s_rp, const int *s_col, int *agg);

@@ -27,8 +27,12 @@ MINRES_RAN_ALL, MINRES_CONVERGED, MINRES_BREAKDOWN = 0, 1, 2
 LOBPCG_RAN_ALL, LOBPCG_CONVERGED, LOBPCG_BREAKDOWN = 0, 1, 2
 LOBPCG_MAX_K, LOBPCG_DROP = 16, 1e-10
 PRECOND_JACOBI, PRECOND_BLOCK_JACOBI, PRECOND_SSOR, PRECOND_ILU0, PRECOND_FSAI, PRECOND_AMG = 1, 2, 3, 4, 5, 6
+PRECOND_CHEBYSHEV = 7
 PRECOND_KINDS = {"jacobi": PRECOND_JACOBI, "block_jacobi": PRECOND_BLOCK_JACOBI, "ssor": PRECOND_SSOR,
-                 "ilu0": PRECOND_ILU0, "fsai": PRECOND_FSAI, "amg": PRECOND_AMG}
+                 "ilu0": PRECOND_ILU0, "fsai": PRECOND_FSAI, "amg": PRECOND_AMG, "chebyshev": PRECOND_CHEBYSHEV}
+# the Chebyshev polynomial preconditioner: its largest degree, what spmv_hip_precond_cheb_info returns (doubles)
+CHEBYSHEV_MAX_DEGREE = 32
+PRECOND_CHEB_INFO = ("degree", "lmin", "lmax", "gershgorin", "products", "plan", "download_us", "upload_us")
 # the AMG hierarchy (SPMV_AMG_*): what a level reader returns, a level's kind, the limits of the setup
 AMG_A, AMG_P, AMG_R, AMG_INV, AMG_T = 0, 1, 2, 3, 4
 AMG_NOT_COARSEST, AMG_DIRECT, AMG_SMOOTH = 0, 1, 2
@@ -573,7 +577,8 @@ class CsrDevice(_Handle):
                              f"the handle rows [{row0}, {row1})")
 
     def preconditioner(self, kind="jacobi", block=1, omega=1.0, ordering="natural", cap=32, theta=0.08, coarse_rows=64,
-                       max_levels=16, chain=True, setup="host", block_products=0) -> "Preconditioner":
+                       max_levels=16, chain=True, setup="host", block_products=0, degree=4, lmax=None, lmin=None,
+                       ratio=30.0) -> "Preconditioner":
         """A preconditioner of this handle's rows; it owns its arrays.  kind "jacobi" (block 1) or "block_jacobi"
         (block in [1, 32]): built on the device (spmv_hip_csr_precond_build).  kind "ssor" (0 < omega < 2; 1 is
         symmetric Gauss-Seidel) or "ilu0": two sparse triangular solves (spmv_hip_csr_precond_build_tri), block 1;
@@ -586,7 +591,10 @@ class CsrDevice(_Handle):
         levels in one launch (the same bits either way); block 1, ordering "natural".  setup "host" (the default) makes
         the hierarchy on the host, "device" on the device (spmv_hip_csr_precond_build_amg_device): the same
         preconditioner byte for byte; block_products (device setup only) goes to its sparse products as in matmul: 0,
-        -1 or a power of two in [64, 4096]."""
+        -1 or a power of two in [64, 4096].  kind "chebyshev": a polynomial of `degree` (in [1, 32]) in the
+        Jacobi-scaled matrix, degree - 1 SpMVs and degree element-wise passes per apply
+        (spmv_hip_csr_precond_build_chebyshev), fitted to the interval [lmin, lmax] of D^-1 A: lmax None is the
+        Gershgorin bound of the block, lmin None is lmax / ratio (ratio > 1); block 1, ordering "natural"."""
         if kind not in PRECOND_KINDS:
             raise ValueError(f"kind must be one of {sorted(PRECOND_KINDS)}, got {kind!r}")
         if isinstance(block, bool) or int(block) != block or not 1 <= int(block) <= 32:
@@ -610,6 +618,8 @@ class CsrDevice(_Handle):
             _check_amg_setup(setup, block_products)
             return Preconditioner(self, PRECOND_AMG, 1, amg=(float(theta), int(coarse_rows), int(max_levels),
                                                              int(bool(chain)), AMG_SETUPS[setup], int(block_products)))
+        if kind == "chebyshev":
+            return Preconditioner(self, PRECOND_CHEBYSHEV, 1, cheb=_check_chebyshev_args(degree, lmax, lmin, ratio))
         return Preconditioner(self, PRECOND_KINDS[kind], int(block))
 
     def triangular(self, lower=True, unit_diagonal=False, ordering="natural") -> "TriangularSolver":
@@ -643,8 +653,9 @@ class CsrDevice(_Handle):
     def pcg_multi(self, B, iters, tol=0.0, precond=None, bounds=None):
         """k independent preconditioned CG recurrences from x0 = 0 that share one SpMM per step
         (spmv_hip_csr_pcg_multi), for the k columns of a C-contiguous B (M x k, 1 <= k <= 64) of the handle's dtype.
-        precond: a Jacobi, block-Jacobi, FSAI or AMG Preconditioner of this handle, or None (cg_multi's bits); SSOR and
-        ILU(0) take one right-hand side and are refused.  Every column stops on its own, by the rules of pcg; tol > 0
+        precond: a Jacobi, block-Jacobi, FSAI, AMG or Chebyshev Preconditioner of this handle, or None (cg_multi's
+        bits); SSOR and ILU(0) take one right-hand side and are refused.  Every column stops on its own, by the rules
+        of pcg; tol > 0
         also ends the loop early once every column has stopped.  Returns (X (M, k), r.r history (iters + 1, k), r.z
         history (iters + 1, k), info {"steps": int array [k], "status": int array [k] (PCG_*)}, ms)."""
         B = _check_columns(B, self.M, self.dtype, "B", "handle")
@@ -709,8 +720,9 @@ class CsrDevice(_Handle):
 
     def lobpcg(self, k, iters, tol=0.0, precond=None, X0=None, largest=False, seed=0):
         """LOBPCG (spmv_hip_csr_lobpcg) for the k smallest (largest=True: largest) eigenpairs of a symmetric fp64 A,
-        1 <= k <= 16, n >= 4 k.  precond: a Jacobi, block-Jacobi, FSAI or AMG Preconditioner of this handle (smallest only),
-        or None.  X0: n x k starting block (None: np.random.default_rng(seed).standard_normal((n, k))).  Stops as
+        1 <= k <= 16, n >= 4 k.  precond: a Jacobi, block-Jacobi, FSAI, AMG or Chebyshev Preconditioner of this handle
+        (smallest only), or None.  X0: n x k starting block (None:
+        np.random.default_rng(seed).standard_normal((n, k))).  Stops as
         converged once tol > 0 and every residual norm <= tol ||A||_inf; tol = 0 runs exactly `iters` steps (the host
         reads the Gram matrices in every step either way).  Returns (w [k] ascending (largest: descending), X (n, k),
         theta history (iters + 1, k), residual-norm history (iters + 1, k), info {"steps", "status" (LOBPCG_*),
@@ -1064,6 +1076,41 @@ def _amg_levels(read, levels, dtype, with_t):
     return out
 
 
+def _check_chebyshev_args(degree, lmax, lmin, ratio):
+    """(degree, lmin, lmax, ratio) as the library takes them (None: 0.0, the default), or ValueError"""
+    if isinstance(degree, bool) or not isinstance(degree, (int, float, np.integer, np.floating)) or \
+            not np.isfinite(float(degree)) or int(degree) != degree or not 1 <= int(degree) <= CHEBYSHEV_MAX_DEGREE:
+        raise ValueError(f"degree must be an integer in [1, {CHEBYSHEV_MAX_DEGREE}], got {degree!r}")
+    bounds = {}
+    for name, v in (("lmax", lmax), ("lmin", lmin)):
+        v = 0.0 if v is None else v
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or \
+                not np.isfinite(float(v)) or float(v) < 0.0:
+            raise ValueError(f"{name} must be None or finite and >= 0, got {v!r}")
+        bounds[name] = float(v)
+    if bounds["lmax"] > 0.0 and bounds["lmin"] > 0.0 and bounds["lmin"] >= bounds["lmax"]:
+        raise ValueError(f"lmin must be below lmax, got lmin = {lmin!r}, lmax = {lmax!r}")
+    if isinstance(ratio, bool) or not isinstance(ratio, (int, float, np.integer, np.floating)) or \
+            not np.isfinite(float(ratio)) or not float(ratio) > 1.0:
+        raise ValueError(f"ratio must be finite and > 1, got {ratio!r}")
+    return int(degree), bounds["lmin"], bounds["lmax"], float(ratio)
+
+
+def chebyshev_coefficients(degree, lmin, lmax):
+    """(a, b): the coefficients of the Chebyshev polynomial preconditioner of `degree` on [lmin, lmax]
+    (spmv_chebyshev_coefficients; no device needed), 0 < lmin < lmax:
+    theta = (lmax + lmin) / 2, delta = (lmax - lmin) / 2, sigma = theta / delta, rho_0 = 1 / sigma, a_0 = 0,
+    b_0 = 1 / theta, then rho_j = 1 / (2 sigma - rho_{j-1}), a_j = rho_j rho_{j-1}, b_j = 2 rho_j / delta."""
+    degree, lmin, lmax, _ = _check_chebyshev_args(degree, lmax, lmin, 2.0)
+    if not 0.0 < lmin < lmax:
+        raise ValueError(f"the interval must satisfy 0 < lmin < lmax, got [{lmin!r}, {lmax!r}]")
+    a, b = np.zeros(degree), np.zeros(degree)
+    if nat.lib().spmv_chebyshev_coefficients(degree, lmin, lmax, a.ctypes.data_as(nat.c_double_p),
+                                             b.ctypes.data_as(nat.c_double_p)) != 0:
+        raise ValueError(f"no coefficients for degree {degree} on [{lmin!r}, {lmax!r}]")
+    return a, b
+
+
 def amg_plan(row_ptr, col, val, theta=0.08, coarse_rows=64, max_levels=16) -> list:
     """The host setup of the AMG preconditioner alone (spmv_amg_plan_build; no device needed) on an n x n CSR matrix
     with canonical rows (ascending columns, no repeats): the levels as Preconditioner.levels() returns them, in fp64,
@@ -1093,15 +1140,19 @@ def amg_plan(row_ptr, col, val, theta=0.08, coarse_rows=64, max_levels=16) -> li
 
 
 class Preconditioner(_Handle):
-    """M^-1 of a Jacobi, block-Jacobi, SSOR, ILU(0), FSAI or AMG preconditioner of a CsrDevice's rows, resident in HBM
-    (CsrDevice.preconditioner).  It owns its arrays: the handle it was built from may be freed first."""
+    """M^-1 of a Jacobi, block-Jacobi, SSOR, ILU(0), FSAI, AMG or Chebyshev preconditioner of a CsrDevice's rows,
+    resident in HBM (CsrDevice.preconditioner).  It owns its arrays: the handle it was built from may be freed first."""
 
     _free = "spmv_hip_precond_free"
 
     def __init__(self, dev: CsrDevice, kind: int, block: int, omega: float = 1.0, ordering: int = ORDER_NATURAL,
-                 cap: int = 32, amg=None):
+                 cap: int = 32, amg=None, cheb=None):
         super().__init__()
-        if kind == PRECOND_AMG:
+        if kind == PRECOND_CHEBYSHEV:
+            degree, lmin, lmax, ratio = cheb
+            _check(nat.lib().spmv_hip_csr_precond_build_chebyshev(dev.h, degree, lmin, lmax, ratio, C.byref(self.h)),
+                   "spmv_hip_csr_precond_build_chebyshev")
+        elif kind == PRECOND_AMG:
             theta, coarse_rows, max_levels, chain, on_device, block_products = amg
             if on_device:
                 _check(nat.lib().spmv_hip_csr_precond_build_amg_device(dev.h, theta, coarse_rows, max_levels, chain,
@@ -1143,7 +1194,7 @@ class Preconditioner(_Handle):
 
     def apply_multi(self, R):
         """Z = M^-1 R for the k columns of a C-contiguous R (rows x k, 1 <= k <= 64) of the handle's dtype
-        (spmv_hip_precond_apply_multi); Jacobi, block-Jacobi, FSAI and AMG."""
+        (spmv_hip_precond_apply_multi); Jacobi, block-Jacobi, FSAI, AMG and Chebyshev."""
         R = _check_columns(R, self.rows, self.dtype, "R", "preconditioner")
         Z = np.zeros(R.shape, dtype=self.dtype)
         _check(nat.lib().spmv_hip_precond_apply_multi(self.h, int(R.shape[1]), R.ctypes.data_as(C.c_void_p),
@@ -1152,8 +1203,8 @@ class Preconditioner(_Handle):
 
     def apply_multi_on(self, d_R: int, d_Z: int, k: int, d_work: int = 0, stream: int = 0):
         """The same on row-major rows x k device arrays, asynchronous on `stream` (0 = the library's).  FSAI needs
-        d_work, rows x k values and one 128-byte line, AMG its level vectors (work_bytes(k), zeroed once); the other
-        kinds ignore it.  Jacobi and block-Jacobi move 16-byte
+        d_work, rows x k values and one 128-byte line, AMG its level vectors (work_bytes(k), zeroed once), Chebyshev
+        its three arrays (work_bytes(k)); the other kinds ignore it.  Jacobi and block-Jacobi move 16-byte
         pieces when a row of k values is whole pieces and d_R, d_Z are 16-byte aligned, single elements otherwise (the
         same bits)."""
         if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= 64:
@@ -1196,6 +1247,17 @@ class Preconditioner(_Handle):
         fn = nat.lib().spmv_hip_precond_amg_level
         return _amg_levels(lambda *a: _check(fn(self.h, *a), "spmv_hip_precond_amg_level"), self.amg_info()["levels"],
                            self.dtype, False)
+
+    def cheb_info(self) -> dict:
+        """Chebyshev: the degree, lmin and lmax as used, the Gershgorin bound of the block (also when lmax was given),
+        the products per apply (degree - 1), the plan of the preconditioner's own upload (an index into FSAI_PLANS),
+        microseconds of download with the canonical rows and the bound, and of the upload with the vectors."""
+        out = (C.c_double * len(PRECOND_CHEB_INFO))()
+        _check(nat.lib().spmv_hip_precond_cheb_info(self.h, out), "spmv_hip_precond_cheb_info")
+        info = dict(zip(PRECOND_CHEB_INFO, (float(v) for v in out)))
+        for key in ("degree", "products", "plan", "download_us", "upload_us"):
+            info[key] = int(info[key])
+        return info
 
     def tri_info(self) -> dict:
         """SSOR / ILU(0): levels, launches, widest and median level of the forward and the backward solve, colours
