@@ -156,72 +156,89 @@ int spmv_hip_stream_probe_at(const void *dptr, size_t bytes, int warmup, int ite
  * kernel (csr_tile's gather passes, the gather stream kernels on scattered columns), as the stream probe is the
  * ceiling of a streaming one. */
 int spmv_hip_gather_probe(int value_bytes, size_t table_bytes, int waves_per_cu, double *values_per_s);
-/* Kernel tuning knobs, for A/B measurements (defaults are the measured best; also settable through the
- * environment, SPMV_TUNING="key=value,...", read by spmv_hip_init):
+/* Kernel tuning knobs, for A/B measurements.  Every key is listed here with its default, the measured best, in
+ * parentheses.  Also settable through the environment, SPMV_TUNING="key=value,...", read by spmv_hip_init (items
+ * without '=' are skipped, the first refused one fails the init).  A refused value leaves the knob as it was; booleans
+ * (1 | 0) store value != 0.  None of the three entry points below needs a device.
  *   read at upload
- *     "stream_cap"    0 (auto) | 1024 | 2048 | 3072 | 4096 | 8192 entries staged per workgroup of the gather stream
+ *     "stream_cap" (0)  0 (auto) | 1024 | 2048 | 3072 | 4096 | 8192 entries staged per workgroup of the gather stream
  *                     kernel; a value other than the x-window stage skips the x-window plan
- *     "stream_local"  1 | 0   build the x-window plan (16-bit local columns + line lists) when the matrix allows
- *     "plan_on_device" 1 | 0  build that plan with the device kernels where they apply (every block within the
+ *     "stream_local" (1)  1 | 0   build the x-window plan (16-bit local columns + line lists) when the matrix allows
+ *     "plan_on_device" (1)  1 | 0  build that plan with the device kernels where they apply (every block within the
  *                     line limit), else / otherwise on the host
- *     "local_cap"     0 (auto = 2048) | 1024 | 2048 | 3072   stage of the x-window kernels (3072: +0.5..3 % on the
+ *     "local_cap" (0)  0 (auto = 2048) | 1024 | 2048 | 3072   stage of the x-window kernels (3072: +0.5..3 % on the
  *                     nlpkkt-like matrix depending on the box, -8 % on the cant-like one)
- *     "skew_rows"     1 | 0   handles that run the gather kernels give rows longer than max(128, 16 x the average
+ *     "skew_rows" (1)  1 | 0   handles that run the gather kernels give rows longer than max(128, 16 x the average
  *                     row) to the split-row kernels (one workgroup per row piece) instead of leaving each to one lane
- *     "stream_tile"   -1 (auto) | 0 | 1   build the 2-D tile plan (csr_tile) when the matrix gets no x-window plan;
- *                     "tile_rows" 0 (auto: 32 KiB of accumulators for banded matrices, as many rows as the LDS takes for
- *                     scattered ones: 16128 fp64 / 32512 fp32) | a multiple of 256 in 256..32768 rows per block; "tile_lmax" (1536) longest row kept in
- *                     the ordinary tiles; "tile_density" (4) columns per entry up to which a pass is staged in LDS;
- *                     "tile_balance" 1 | 0 row blocks of equal entry / row counts; "tile_long" 1 | 0 | 2 a tile plan of
+ *     "stream_tile" (-1)  -1 (auto) | 0 | 1   build the 2-D tile plan (csr_tile) when the matrix gets no x-window plan;
+ *                     "tile_rows" (0) 0 (auto: 32 KiB of accumulators for banded matrices, as many rows as the LDS takes for
+ *                     scattered ones: 16128 fp64 / 32512 fp32) | a multiple of 256 in 256..32768 rows per block;
+ *                     "tile_lmax" (1536) 1..65536 longest row kept in the ordinary tiles;
+ *                     "tile_density" (4) 0..4096 columns per entry up to which a pass is staged in LDS (0: never);
+ *                     "tile_balance" (1) 1 | 0 row blocks of equal entry / row counts; "tile_long" (1) 1 | 0 | 2 a tile plan of
  *                     their own for the rows beyond tile_lmax (0: split-row kernels, 2: however few they are);
- *                     "tile_fit" 1 | 0 (with tile_rows 0) the number of row blocks is fitted to whole rounds of the
+ *                     "tile_fit" (1) 1 | 0 (with tile_rows 0) the number of row blocks is fitted to whole rounds of the
  *                     workgroups the chip holds at once (512 banded / 256 scattered), blocks up to the tallest the LDS takes;
- *                     "tile_streams" 1 | 0 one csr_tile workgroup per place of the chip walks several row blocks back to
- *                     back (0: one workgroup per block); "tile_places" 0 (the chip's: 2 or 1 per CU) | a multiple of 8: how
- *                     many workgroups the streams and the block count are made for (tests); "tile_items" (1008) work items the long rows' passes are dealt out to;
- *                     "tile_min_pass" (256) a packed plan's windows with fewer entries than this, and fewer than one per
+ *                     "tile_streams" (1) 1 | 0 one csr_tile workgroup per place of the chip walks several row blocks back to
+ *                     back (0: one workgroup per block); "tile_places" (0) 0 (the chip's: 2 or 1 per CU) | a multiple of 8 up
+ *                     to 4096: how many workgroups the streams and the block count are made for (tests);
+ *                     "tile_items" (1008) 8..65536 work items the long rows' passes are dealt out to;
+ *                     "tile_min_pass" (256) 0..2048 a packed plan's windows with fewer entries than this, and fewer than one per
  *                     16 columns, go to the remainder kernel instead of being a pass (0: no remainder);
- *                     "local_patterns" -1 | 0 | 1 (read at upload and at launch) x-window plans: the kernel rebuilds a block's
+ *                     "local_patterns" (-1) -1 | 0 | 1 (read at upload and at launch; a value below -1 stores -1, above 1
+ *                         stores 1) x-window plans: the kernel rebuilds a block's
  *                         slots from a pattern table instead of reading them -- auto: built for streamed matrices of at least
  *                         12 entries per row whose tables hold at most a quarter of the slots, then kept only if upload
  *                         measures its kernel at least 2 % faster with it on this handle; 0 never; 1 always
- *                     "local_share" -1 | 0 | 1 | 2 (read at upload) x-window plans of CSR handles: every distinct pattern segment
+ *                     "local_share" (-1) -1 | 0 | 1 | 2 (read at upload) x-window plans of CSR handles: every distinct pattern segment
  *                         and every distinct line list (relative to its first line) is stored once and shared by the blocks
  *                         that repeat it -- auto: on; 0 off (every block its own copy); 1 on; 2 on, with a hash of the
  *                         span's length alone, so that every group has to be told apart word by word (tests)
- *                     "local_segment_cap" 0 | bytes (read at upload) pattern plans of CSR handles: segments wider than this
+ *                     "local_segment_cap" (0) 0 | bytes (read at upload) pattern plans of CSR handles: segments wider than this
  *                         stay tables even where the LDS budget would take them (tests: both kinds of blocks on a small
  *                         matrix; 1: no segments at all); 0: the LDS budget alone (spmv_hip_csr_pattern_segment_cap)
- *                     "tile_mid_items" (0 = three rounds of the CUs) work items of the middle tier
- *                     "tile_expand" -1 | 0 | 1 (read at upload and at launch) a tile plan with gather passes runs on an
+ *                     "tile_mid_items" (0) 0 (three rounds of the CUs) .. 65536 work items of the middle tier
+ *                     "tile_expand" (-1) -1 | 0 | 1 (read at upload and at launch; normalised like local_patterns) a tile plan
+ *                         with gather passes runs on an
  *                         expanded x -- auto: from 2^22 entries on when under a tenth of them are staged, fp32 always, fp64
  *                         when x is beyond 100 MB; 0 never; 1 always
- *                     "tile_gather_ahead" 0 | 1 (read at launch) plans with gather passes send a pass's gathers out one pass
+ *                     "tile_gather_ahead" (0) 0 | 1 (read at launch) plans with gather passes send a pass's gathers out one pass
  *                     early (twice as many in flight per CU) -- measured to buy nothing (1113 vs 1108 us on config 5, 514.9 vs
  *                     514.8 on uniformly random columns: profiles/r3_ab_gather_ahead.txt), hence off;
- *                     "tile_mid" 1 | 0 a scattered plan gives its rows of more than "tile_mid_lo" entries (0 = auto: 48 for fp32,
- *                     128 for fp64; up to tile_lmax) a tier of their own -- compacted, blocks as tall as the LDS takes, every
- *                     pass staged -- when they hold >= 2^22 entries;
- *                     "tile_plan_on_device" 1 | 0 the plan is built by kernels from the CSR arrays in HBM (round 3) or by host
+ *                     "tile_mid" (1) 1 | 0 a scattered plan gives its rows of more than "tile_mid_lo" (0) entries (0 = auto: 48 for
+ *                     fp32, 128 for fp64; else 8..1024; up to tile_lmax) a tier of their own -- compacted, blocks as tall as the
+ *                     LDS takes, every pass staged -- when they hold >= 2^22 entries;
+ *                     "tile_plan_on_device" (1) 1 | 0 the plan is built by kernels from the CSR arrays in HBM (round 3) or by host
  *                     threads; the two builders give the same bytes;
- *                     "tile_pack" 1 | 0 banded matrices get the PACKED plan (every pass cut at the 32 KiB window and
+ *                     "tile_pack" (1) 1 | 0 banded matrices get the PACKED plan (every pass cut at the 32 KiB window and
  *                     staged, keys in the column words, kernel instantiation without gather code) unless its passes
  *                     would average fewer than 256 entries; 0: always the plan with gather passes
- *   read at launch
- *     "stream_kind"   -1 (auto: x-window kernel when the handle has a plan, csr_tile when it has tiles, else
- *                     csr_stream) | 5 x-window | 6 csr_tile |
- *                     0 csr_stream; any other value is an error
- *     "place_tries"   (12) read at upload: how many other placements of the value array a handle that streams >= 128 MiB of
+ *     "place_tries" (12)  0..16: how many other placements of the value array a handle that streams >= 128 MiB of
  *                     values tries (a fresh allocation each, the kernel timed 2 + 6 launches on it), keeping the fastest.
  *                     Round 3 found the x-window kernel's time on the headline matrix to depend on WHERE the values lie:
  *                     the same matrix runs in 182-187 or in 199-205 us, deterministically per address
  *                     (profiles/r3_placement_*.txt); 0 keeps what hipMalloc gave first
- *     "stream_nt" 0/1, "local_nt" -1 (auto) / 0 / 1   non-temporal hint on the streamed arrays
- *     "stream_xcd"    blocks per XCD run: 0 default (16 for the x-window kernels, dispatch order otherwise),
+ *   read at launch
+ *     "stream_kind" (-1)  -1 (auto: x-window kernel when the handle has a plan, csr_tile when it has tiles, else
+ *                     csr_stream) | 5 x-window | 6 csr_tile |
+ *                     0 csr_stream; any other value is an error
+ *     "stream_nt" (1) 1 | 0, "local_nt" (-1) -1 (auto) | 0 | 1   non-temporal hint on the streamed arrays
+ *     "stream_xcd" (0)  blocks per XCD run: 0 default (16 for the x-window kernels, dispatch order otherwise),
  *                     -1 one contiguous eighth per XCD, n > 0 runs of n
- *     "stream_block"  256 | 512 | 1024 threads (csr_stream at 4096 / 8192)
- *     "gather_mode"   all-gatherv: 0 grouped broadcasts | 1 padded all-gather + scatter (see spmv_hip_comm_autotune) */
+ *     "stream_block" (256)  256 | 512 | 1024 threads (csr_stream at 4096 / 8192)
+ *     "gather_mode" (0)  all-gatherv: 0 grouped broadcasts | 1 padded all-gather + scatter (see spmv_hip_comm_autotune)
+ *   read by the multi-rank halo code
+ *     "halo_split" (1)  1 | 0   spmv_hip_comm_halo_setup splits the handle by columns (1) or by whole blocks only (0)
+ *     "halo_overlap" (1)  1 | 0   the power iteration with halo exchanges beside the interior blocks (1) or strictly in order (0)
+ *   measurement only
+ *     "tile_probe" (0)  stores value & 15: bit 0 csr_tile does loads, staging and barriers only, bit 1 no gathers, bit 2 no
+ *                     run sums (y is then wrong), bit 3 one workgroup per CU
+ *     "probe_depth" (4)  4 | 16 loads in flight per lane of spmv_hip_stream_probe */
 int spmv_hip_set_tuning(const char *key, int value);
+/* the value a knob holds now; -1 for an unknown key or a NULL argument */
+int spmv_hip_get_tuning(const char *key, int *value);
+/* the key of knob `index` (0, 1, ...: every key set_tuning takes, once), NULL past the last */
+const char *spmv_hip_tuning_key(int index);
 
 /* raw device buffers, for callers that keep x / y on the device themselves */
 int spmv_hip_malloc(void **dptr, size_t bytes);

@@ -24,4 +24,5 @@ from .device import (BICG_BREAKDOWN_OMEGA, BICG_BREAKDOWN_RHO, BICG_CONVERGED, B
                      CSR_AUTO, CSR_STREAM, CSR_SUBWAVE, CSR_THREAD_ROW, CSR_VARIANTS,  # noqa: F401
                      CSR_WAVE_ROW, HLL_AUTO, HLL_LDS, HLL_SUBWAVE, HLL_THREAD_ROW, HLL_VARIANTS,
                      CsrDevice, HllDevice, SpmvHipError, device_count, device_name, flush_cache,
-                     hip_init, hip_stream, hip_sync, box_state, stream_probe, stream_probe_at, gather_probe, set_tuning)
+                     hip_init, hip_stream, hip_sync, box_state, stream_probe, stream_probe_at, gather_probe, set_tuning,
+                     get_tuning, tuning_values, tuning)

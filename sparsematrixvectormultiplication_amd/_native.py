@@ -164,6 +164,8 @@ _PROTOTYPES = {
     "spmv_hip_csr_relocate": (C.c_int, [C.c_void_p, C.c_int, C.c_ulonglong, C.c_ulonglong]),
     "spmv_hip_csr_relocate_vmm": (C.c_int, [C.c_void_p, C.c_int, C.c_ulonglong, C.c_ulonglong]),
     "spmv_hip_set_tuning": (C.c_int, [C.c_char_p, C.c_int]),
+    "spmv_hip_get_tuning": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
+    "spmv_hip_tuning_key": (C.c_char_p, [C.c_int]),
     "spmv_hip_malloc": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t]),
     "spmv_hip_free": (C.c_int, [C.c_void_p]),
     "spmv_hip_memcpy_h2d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),

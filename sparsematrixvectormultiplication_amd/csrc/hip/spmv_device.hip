@@ -78,44 +78,7 @@ static size_t g_flush_bytes = 0;
 ncclComm_t g_comm = nullptr;
 int g_comm_rank = 0, g_comm_size = 1;
 
-int g_stream_cap = 0;
-int g_stream_block = 256;
-int g_stream_nt = 1;
-int g_local_nt = -1;
-int g_stream_xcd = 0;
-int g_gather_mode = 0;
-int g_local_cap = 0;
-int g_stream_local = 1;
-int g_plan_on_device = 1;
-int g_stream_kind = -1;
-int g_stream_tile = -1;
-int g_tile_rows = 0;
-int g_tile_lmax = 1536;  // (1024 until round 3: config 5 1016 us at 1024, 1000 at 1536, 1001 at 2048; with the expanded short rows 942 / 927 / 930)
-int g_tile_density = 4;
-int g_tile_plan_on_device = 1;
-int g_place_tries = 12;
-int g_tile_mid = 1;
-int g_tile_mid_lo = 0;  // 0: auto (48 entries for fp32, 128 for fp64)
-int g_tile_gather_ahead = 0;  // measured: no gain (profiles/r3_ab_gather_ahead.txt)
-int g_tile_expand = -1;       // plans with gather passes run on an expanded x (tile_expand + csr_tile<.., XE>): auto
-int g_tile_probe = 0;
-int g_skew_rows = 1;
-int g_tile_fit = 1;
-int g_tile_streams = 1;
-int g_tile_places = 0;
-int g_tile_min_pass = 256;
-int g_local_patterns = -1;
-int g_local_share = -1;
-int g_local_segment_cap = 0;
-int g_tile_mid_items = 0;
-int g_tile_items = 1008;  // two rounds of the 512 places: 1.222 ms on the power-law matrix against 1.248 with 4096, 1.231 with 504
-int g_tile_pack = 1;
-int g_tile_long = 1;
-int g_halo_overlap = 1;
-int g_halo_split = 1;
-int g_tile_balance = 1;
 int g_num_cus = 256;
-static int g_probe_depth = 4;  // "probe_depth" tuning knob: loads in flight per lane of the stream probe (4 | 16)
 
 int fail(const char *fmt, ...) {
     va_list ap;
@@ -199,112 +162,92 @@ extern "C" int spmv_hip_shutdown(void) {
     return 0;
 }
 
+// ------------------------------------------------------------------ tuning knobs
+// One row per knob (the variables: tuning.hpp).  take(v): is v legal?  It may normalise v.
+// A refused value leaves the knob as it was.  None of this needs a device.
+namespace {
+struct Knob {
+    const char *key;
+    int *var;
+    bool (*take)(int &v);
+    const char *refusal;  // what set_tuning says when take() refuses
+};
+bool as_bool(int &v) { return v = v != 0, true; }
+bool as_tri(int &v) { return v = v < 0 ? -1 : v != 0, true; }  // -1 auto | 0 | 1
+template <int LO, int HI>
+bool in_range(int &v) { return v >= LO && v <= HI; }
+
+const Knob kKnobs[] = {
+    {"stream_cap", &g_stream_cap, [](int &v) { return v == 0 || v == 1024 || v == 2048 || v == 3072 || v == 4096 || v == 8192; },
+     "set_tuning: stream_cap must be 0 (auto), 1024, 2048, 3072, 4096 or 8192"},
+    {"stream_block", &g_stream_block, [](int &v) { return v == 256 || v == 512 || v == 1024; }, "set_tuning: stream_block must be 256, 512 or 1024"},
+    {"stream_nt", &g_stream_nt, as_bool, nullptr},
+    {"stream_xcd", &g_stream_xcd, [](int &v) { return v >= -1; }, "set_tuning: stream_xcd must be -1, 0 or a positive run length"},
+    {"stream_kind", &g_stream_kind, [](int &v) { return v == -1 || v == 0 || v == 5 || v == 6; },
+     "set_tuning: stream_kind must be -1 (auto), 0 (csr_stream), 5 (x-window) or 6 (tiles)"},
+    {"stream_tile", &g_stream_tile, in_range<-1, 1>, "set_tuning: stream_tile must be -1 (auto), 0 or 1"},
+    {"tile_lmax", &g_tile_lmax, in_range<1, 65536>, "set_tuning: tile_lmax must be 1..65536"},
+    {"tile_rows", &g_tile_rows, [](int &v) { return v == 0 || (v >= 256 && v <= kTileRowsMax && !(v & 255)); },
+     "set_tuning: tile_rows must be 0 (auto) or a multiple of 256 in 256..%d"},  // (%d: kTileRowsMax)
+    {"halo_split", &g_halo_split, as_bool, nullptr},
+    {"halo_overlap", &g_halo_overlap, as_bool, nullptr},
+    {"tile_pack", &g_tile_pack, as_bool, nullptr},
+    {"tile_long", &g_tile_long, in_range<0, 2>, "set_tuning: tile_long must be 0, 1 (rows with >= 2^20 entries together) or 2 (always)"},
+    {"tile_balance", &g_tile_balance, as_bool, nullptr},
+    {"tile_min_pass", &g_tile_min_pass, in_range<0, 2048>, "set_tuning: tile_min_pass must be 0 (no remainder) .. 2048"},
+    {"tile_places", &g_tile_places, [](int &v) { return v >= 0 && v <= 4096 && !(v & 7); },
+     "set_tuning: tile_places must be 0 (the chip's) or a multiple of 8 up to 4096"},
+    {"tile_items", &g_tile_items, in_range<8, 65536>, "set_tuning: tile_items must be 8..65536"},
+    {"local_patterns", &g_local_patterns, as_tri, nullptr},
+    {"local_share", &g_local_share, in_range<-1, 2>, "set_tuning: local_share must be -1 (auto: on), 0, 1 or 2 (on, hashing the length only)"},
+    {"local_segment_cap", &g_local_segment_cap, [](int &v) { return v >= 0; },
+     "set_tuning: local_segment_cap must be 0 (the LDS budget's) or a number of bytes"},
+    {"tile_mid_items", &g_tile_mid_items, in_range<0, 65536>, "set_tuning: tile_mid_items must be 0 (auto: three rounds of the CUs) .. 65536"},
+    {"tile_streams", &g_tile_streams, as_bool, nullptr},
+    {"tile_fit", &g_tile_fit, as_bool, nullptr},
+    {"skew_rows", &g_skew_rows, as_bool, nullptr},
+    {"tile_probe", &g_tile_probe, [](int &v) { return v &= 15, true; }, nullptr},
+    {"probe_depth", &g_probe_depth, [](int &v) { return v == 4 || v == 16; }, "set_tuning: probe_depth must be 4 or 16"},
+    {"tile_gather_ahead", &g_tile_gather_ahead, as_bool, nullptr},
+    {"tile_expand", &g_tile_expand, as_tri, nullptr},
+    {"tile_mid_lo", &g_tile_mid_lo, [](int &v) { return v == 0 || (v >= 8 && v <= 1024); }, "set_tuning: tile_mid_lo must be 0 (auto) or 8..1024"},
+    {"tile_mid", &g_tile_mid, as_bool, nullptr},
+    {"place_tries", &g_place_tries, in_range<0, 16>, "set_tuning: place_tries must be 0..16"},
+    {"tile_plan_on_device", &g_tile_plan_on_device, as_bool, nullptr},
+    {"tile_density", &g_tile_density, in_range<0, 4096>, "set_tuning: tile_density must be 0 (never stage) .. 4096"},
+    {"gather_mode", &g_gather_mode, in_range<0, 1>, "set_tuning: gather_mode must be 0 (broadcasts) or 1 (padded all-gather)"},
+    {"local_nt", &g_local_nt, in_range<-1, 1>, "set_tuning: local_nt must be -1 (auto), 0 or 1"},
+    {"local_cap", &g_local_cap, [](int &v) { return v == 0 || v == 1024 || v == 2048 || v == 3072; }, "set_tuning: local_cap must be 0, 1024, 2048 or 3072"},
+    {"plan_on_device", &g_plan_on_device, as_bool, nullptr},
+    {"stream_local", &g_stream_local, as_bool, nullptr},
+};
+
+const Knob *find_knob(const char *key) {
+    for (const Knob &k : kKnobs)
+        if (!strcmp(key, k.key)) return &k;
+    return nullptr;
+}
+}  // namespace
+
 extern "C" int spmv_hip_set_tuning(const char *key, int value) {
     if (!key) return fail("set_tuning: NULL key");
-    if (!strcmp(key, "stream_cap")) {
-        if (value != 0 && value != 1024 && value != 2048 && value != 3072 && value != 4096 && value != 8192)
-            return fail("set_tuning: stream_cap must be 0 (auto), 1024, 2048, 3072, 4096 or 8192");
-        g_stream_cap = value;
-    } else if (!strcmp(key, "stream_block")) {
-        if (value != 256 && value != 512 && value != 1024)
-            return fail("set_tuning: stream_block must be 256, 512 or 1024");
-        g_stream_block = value;
-    } else if (!strcmp(key, "stream_nt")) {
-        g_stream_nt = value != 0;
-    } else if (!strcmp(key, "stream_xcd")) {
-        if (value < -1) return fail("set_tuning: stream_xcd must be -1, 0 or a positive run length");
-        g_stream_xcd = value;
-    } else if (!strcmp(key, "stream_kind")) {
-        if (value != -1 && value != 0 && value != 5 && value != 6)
-            return fail("set_tuning: stream_kind must be -1 (auto), 0 (csr_stream), 5 (x-window) or 6 (tiles)");
-        g_stream_kind = value;
-    } else if (!strcmp(key, "stream_tile")) {
-        if (value < -1 || value > 1) return fail("set_tuning: stream_tile must be -1 (auto), 0 or 1");
-        g_stream_tile = value;
-    } else if (!strcmp(key, "tile_lmax")) {
-        if (value < 1 || value > 65536) return fail("set_tuning: tile_lmax must be 1..65536");
-        g_tile_lmax = value;
-    } else if (!strcmp(key, "tile_rows")) {
-        if (value != 0 && (value < 256 || value > kTileRowsMax || (value & 255)))
-            return fail("set_tuning: tile_rows must be 0 (auto) or a multiple of 256 in 256..%d", kTileRowsMax);
-        g_tile_rows = value;
-    } else if (!strcmp(key, "halo_split")) {
-        g_halo_split = value != 0;  // read by spmv_hip_comm_halo_setup
-    } else if (!strcmp(key, "halo_overlap")) {
-        g_halo_overlap = value != 0;
-    } else if (!strcmp(key, "tile_pack")) {
-        g_tile_pack = value != 0;
-    } else if (!strcmp(key, "tile_long")) {
-        if (value < 0 || value > 2) return fail("set_tuning: tile_long must be 0, 1 (rows with >= 2^20 entries together) or 2 (always)");
-        g_tile_long = value;
-    } else if (!strcmp(key, "tile_balance")) {
-        g_tile_balance = value != 0;
-    } else if (!strcmp(key, "tile_min_pass")) {
-        if (value < 0 || value > 2048) return fail("set_tuning: tile_min_pass must be 0 (no remainder) .. 2048");
-        g_tile_min_pass = value;
-    } else if (!strcmp(key, "tile_places")) {
-        if (value < 0 || (value & 7) || value > 4096) return fail("set_tuning: tile_places must be 0 (the chip's) or a multiple of 8 up to 4096");
-        g_tile_places = value;
-    } else if (!strcmp(key, "tile_items")) {
-        if (value < 8 || value > 65536) return fail("set_tuning: tile_items must be 8..65536");
-        g_tile_items = value;
-    } else if (!strcmp(key, "local_patterns")) {
-        g_local_patterns = value < 0 ? -1 : value != 0;  // read at upload (the plan) and at launch (0: the slot stream)
-    } else if (!strcmp(key, "local_share")) {
-        if (value < -1 || value > 2) return fail("set_tuning: local_share must be -1 (auto: on), 0, 1 or 2 (on, hashing the length only)");
-        g_local_share = value;  // takes effect at the next upload
-    } else if (!strcmp(key, "local_segment_cap")) {
-        if (value < 0) return fail("set_tuning: local_segment_cap must be 0 (the LDS budget's) or a number of bytes");
-        g_local_segment_cap = value;  // takes effect at the next upload
-    } else if (!strcmp(key, "tile_mid_items")) {
-        if (value < 0 || value > 65536) return fail("set_tuning: tile_mid_items must be 0 (auto: three rounds of the CUs) .. 65536");
-        g_tile_mid_items = value;
-    } else if (!strcmp(key, "tile_streams")) {
-        g_tile_streams = value != 0;
-    } else if (!strcmp(key, "tile_fit")) {
-        g_tile_fit = value != 0;
-    } else if (!strcmp(key, "skew_rows")) {
-        g_skew_rows = value != 0;
-    } else if (!strcmp(key, "tile_probe")) {
-        g_tile_probe = value & 15;
-    } else if (!strcmp(key, "probe_depth")) {
-        if (value != 4 && value != 16) return fail("set_tuning: probe_depth must be 4 or 16");
-        g_probe_depth = value;
-    } else if (!strcmp(key, "tile_gather_ahead")) {
-        g_tile_gather_ahead = value != 0;  // read at launch
-    } else if (!strcmp(key, "tile_expand")) {
-        g_tile_expand = value < 0 ? -1 : value != 0;  // read at upload (the plan) and at launch (0: the gather passes)
-    } else if (!strcmp(key, "tile_mid_lo")) {
-        if (value != 0 && (value < 8 || value > 1024)) return fail("set_tuning: tile_mid_lo must be 0 (auto) or 8..1024");
-        g_tile_mid_lo = value;  // takes effect at the next upload
-    } else if (!strcmp(key, "tile_mid")) {
-        g_tile_mid = value != 0;  // takes effect at the next upload
-    } else if (!strcmp(key, "place_tries")) {
-        if (value < 0 || value > 16) return fail("set_tuning: place_tries must be 0..16");
-        g_place_tries = value;  // takes effect at the next upload
-    } else if (!strcmp(key, "tile_plan_on_device")) {
-        g_tile_plan_on_device = value != 0;  // takes effect at the next upload
-    } else if (!strcmp(key, "tile_density")) {
-        if (value < 0 || value > 4096) return fail("set_tuning: tile_density must be 0 (never stage) .. 4096");
-        g_tile_density = value;
-    } else if (!strcmp(key, "gather_mode")) {
-        if (value != 0 && value != 1) return fail("set_tuning: gather_mode must be 0 (broadcasts) or 1 (padded all-gather)");
-        g_gather_mode = value;
-    } else if (!strcmp(key, "local_nt")) {
-        if (value < -1 || value > 1) return fail("set_tuning: local_nt must be -1 (auto), 0 or 1");
-        g_local_nt = value;
-    } else if (!strcmp(key, "local_cap")) {
-        if (value != 0 && value != 1024 && value != 2048 && value != 3072)
-            return fail("set_tuning: local_cap must be 0, 1024, 2048 or 3072");
-        g_local_cap = value;  // takes effect at the next upload
-    } else if (!strcmp(key, "plan_on_device")) {
-        g_plan_on_device = value != 0;  // takes effect at the next upload
-    } else if (!strcmp(key, "stream_local")) {
-        g_stream_local = value != 0;  // takes effect at the next upload
-    } else {
-        return fail("set_tuning: unknown key '%s'", key);
-    }
+    const Knob *k = find_knob(key);
+    if (!k) return fail("set_tuning: unknown key '%s'", key);
+    if (!k->take(value)) return fail(k->refusal, kTileRowsMax);  // (the argument: for the one %d among the refusals)
+    *k->var = value;
     return 0;
+}
+
+extern "C" int spmv_hip_get_tuning(const char *key, int *value) {
+    if (!key || !value) return fail("get_tuning: NULL argument");
+    const Knob *k = find_knob(key);
+    if (!k) return fail("get_tuning: unknown key '%s'", key);
+    *value = *k->var;
+    return 0;
+}
+
+extern "C" const char *spmv_hip_tuning_key(int index) {
+    return index >= 0 && (size_t)index < sizeof kKnobs / sizeof kKnobs[0] ? kKnobs[index].key : nullptr;
 }
 
 extern "C" int spmv_hip_sync(void) {

@@ -21,6 +21,7 @@
 #include "hll_kernels.hpp"
 #include "tile_kernels.hpp"
 #include "row_counts.hpp"
+#include "tuning.hpp"  // the tuning knobs, g_stream_cap .. g_stream_local
 #include "spmv_hip.h"
 
 using namespace spmv;
@@ -33,48 +34,10 @@ extern ncclComm_t g_comm;
 extern int g_comm_rank, g_comm_size;
 constexpr int kMaxRanks = 64;  // widest communicator: the all-gatherv's bounds, the solvers' gathered sums
 
-// kernel tuning knobs (spmv_hip_set_tuning); defaults are the measured best
-extern int g_stream_cap;      // nnz staged per stream workgroup (fixed at upload); 0 = by matrix size
-extern int g_stream_block;    // threads per csr_stream workgroup
-extern int g_stream_nt;       // non-temporal loads for col/val in the gather stream kernels
-extern int g_local_nt;        // same for the x-window kernels: -1 = auto (off while the matrix fits the Infinity Cache)
-extern int g_stream_xcd;      // blocks per XCD run (xcd_chunked); 0 = default, -1 = one contiguous eighth per XCD
-extern int g_halo_split;      // halo setup splits the handle by columns (1) or by blocks only (0)
 extern bool g_halo_ready;     // spmv_hip_comm_halo_setup has made this rank's send / receive segments
-extern int g_halo_overlap;    // power iteration with halo: exchange beside the interior blocks (1) or strictly in order (0)
-extern int g_gather_mode;     // all-gatherv: 0 = one ncclBroadcast per owner in a group, 1 = padded ncclAllGather + scatter
-extern int g_local_cap;       // stage of the x-window plan: 0 = auto, 1024 or 2048
-extern int g_stream_local;    // build the x-window plan at upload when it pays
-extern int g_plan_on_device;  // ... with the device kernels where they apply (0: always on the host)
-extern int g_stream_kind;     // -1 = auto (x-window kernel or tiles when the handle has that plan, else csr_stream), 5 = x-window,
-                              // 6 = tiles, 0 = csr_stream
-extern int g_stream_tile;     // csr_tile plan at upload: -1 = auto (no x-window plan, enough rows), 0 = never, 1 = whenever no x-window plan
-extern int g_tile_rows;       // rows per block: 0 = auto, else a power of two in 256..8192
-extern int g_tile_lmax;       // rows longer than this stay with the split-row kernels
-constexpr long long kTileMidEntries = 4LL << 20;  // (auto) ... or, for a band of dense rows, entries from which it gets one (packed plans only)
+constexpr long long kTileMidEntries = 4LL << 20;  // (auto) entries from which a scattered plan's middle tier, or a band of dense rows (packed plans only), gets a tier
 constexpr long long kSplitMinEntries = 1LL << 20;  // entries from which rows may be handed to the split-row kernels (two more launches)
 constexpr long long kTileMinRows = 800000;  // (auto) rows from which a handle without an x-window plan gets a tile plan
-extern int g_tile_min_pass;   // windows of a packed plan with fewer entries than this (and sparser than 1 per 16 columns) go to the remainder; 0: none
-extern int g_tile_places;     // 0: the chip's (2 or 1 workgroups per CU) | the number of workgroup places the streams / the block count are made for
-extern int g_tile_mid_items;  // work items of the middle tier (0: three rounds of the CUs)
-extern int g_tile_items;      // work items the long rows' passes are dealt out to (about)
-extern int g_tile_streams;    // 1: one csr_tile workgroup per place of the chip walks several row blocks back to back
-extern int g_tile_fit;        // 1: (auto rows) the number of row blocks is fitted to whole rounds of the chip's workgroup places
-extern int g_skew_rows;       // 1: gather-kernel handles hand rows far longer than the average to the split-row kernels
-extern int g_tile_probe;      // measurement only: bit 0 loads, staging and barriers only, bit 1 no gathers, bit 2 no run sums (y is then wrong), bit 3 one workgroup per CU
-extern int g_tile_balance;    // 1: row blocks of about equal entry counts (keeps the workgroups in step), 0: equal row counts
-extern int g_tile_long;       // 1: the rows beyond the tile limit get a tile plan of their own (compacted rows, work items, slabs)
-extern int g_tile_pack;       // 1: passes that can be staged store head | row | column offset in one 32-bit word (no key read)
-extern int g_tile_density;    // a pass is staged when it holds at least one entry per this many columns of its window
-extern int g_tile_mid_lo;     // a scattered matrix's rows longer than this (up to tile_lmax) form the middle tier ("tile_mid_lo")
-extern int g_local_segment_cap;  // pattern plans of CSR handles: no segment wider than this many bytes; 0: the LDS budget's cap ("local_segment_cap")
-extern int g_local_share;    // x-window plans: equal segments / relative line lists stored once: -1 auto (on), 0 off, 1 on, 2 on with a hash of the length only ("local_share")
-extern int g_local_patterns;  // x-window plans: -1 auto (a pattern plan where it holds a quarter of the slots at most), 0 never, 1 always ("local_patterns")
-extern int g_tile_expand;     // plans with gather passes: -1 auto, 0 never, 1 always: x expanded into entry order ahead of csr_tile ("tile_expand")
-extern int g_tile_gather_ahead;  // 1: plans with gather passes run the csr_tile instantiation that gathers one pass early
-extern int g_tile_mid;        // 1: scattered plans get that tier (when it holds >= 2^22 entries), 0: never
-extern int g_place_tries;     // other placements of the value array upload tries for large handles (0: none)
-extern int g_tile_plan_on_device;  // 1: the csr_tile plan is built by kernels (tile_plan_device.hpp), 0: by host threads (tile_plan.hpp)
 extern int g_num_cus;
 
 int fail(const char *fmt, ...);  // records the message for spmv_hip_last_error(), returns -1

@@ -6,6 +6,7 @@ fetch y (:183).  No CPU fallback anywhere: a failed C call raises.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -194,8 +195,41 @@ def box_state(probe_bytes: int = 1 << 30) -> dict:
 
 
 def set_tuning(key: str, value: int) -> None:
-    """A/B knobs of the stream kernel: stream_cap (at upload), stream_nt, stream_xcd."""
+    """Set one tuning knob (the keys, their values and defaults: include/spmv_hip.h).  A refused value raises and
+    leaves the knob as it was.  Code that should put the knob back afterwards uses tuning()."""
     _check(nat.lib().spmv_hip_set_tuning(key.encode(), int(value)), "spmv_hip_set_tuning")
+
+
+def get_tuning(key: str) -> int:
+    """The value a tuning knob holds now."""
+    value = C.c_int()
+    _check(nat.lib().spmv_hip_get_tuning(key.encode(), C.byref(value)), "spmv_hip_get_tuning")
+    return value.value
+
+
+def tuning_values() -> dict:
+    """{key: current value} of every tuning knob, in the library's order."""
+    out, index = {}, 0
+    while (key := nat.lib().spmv_hip_tuning_key(index)) is not None:
+        out[key.decode()] = get_tuning(key.decode())
+        index += 1
+    return out
+
+
+@contextlib.contextmanager
+def tuning(**knobs):
+    """with tuning(tile_rows=256, stream_kind=6): ... -- the knobs set in the order given; on the way out, also by an
+    exception or a refused knob, those that were set get the values they held before (not the defaults), last first."""
+    saved = []
+    try:
+        for key, value in knobs.items():
+            before = get_tuning(key)
+            set_tuning(key, value)
+            saved.append((key, before))
+        yield
+    finally:
+        for key, before in reversed(saved):
+            set_tuning(key, before)
 
 
 class _Handle:

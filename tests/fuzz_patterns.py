@@ -11,7 +11,6 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import sparsematrixvectormultiplication_amd as sp  # noqa: E402
-from sparsematrixvectormultiplication_amd.device import set_tuning  # noqa: E402
 
 
 def make_case(rng, case):
@@ -60,34 +59,29 @@ def run(cases=60, seed=2027, oracle=None):
         val = rng.uniform(-1, 1, len(col)).astype(dtype)
         x = rng.uniform(-1, 1, N).astype(dtype)
         r0, r1 = (0, M) if case % 6 else (M // 4, 3 * M // 4)
-        set_tuning("local_patterns", 1)
-        try:
-            with sp.CsrDevice(M, N, rp, col, val, row0=r0, row1=r1) as dev:
-                info = dev.info()
-                if not info["local_blocks"]:
-                    continue
-                with_plan += info["pattern_slots"] > 0
-                sp.lib().spmv_hip_memset(dev.y_ptr, 0xFF, M * x.itemsize)
-                y1 = dev.spmv(x, sp.CSR_STREAM)[r0:r1].copy()
-                set_tuning("local_patterns", 0)
+        with sp.tuning(local_patterns=1), sp.CsrDevice(M, N, rp, col, val, row0=r0, row1=r1) as dev:
+            info = dev.info()
+            if not info["local_blocks"]:
+                continue
+            with_plan += info["pattern_slots"] > 0
+            sp.lib().spmv_hip_memset(dev.y_ptr, 0xFF, M * x.itemsize)
+            y1 = dev.spmv(x, sp.CSR_STREAM)[r0:r1].copy()
+            with sp.tuning(local_patterns=0):
                 y0 = dev.spmv(x, sp.CSR_STREAM)[r0:r1].copy()
-                assert y1.tobytes() == y0.tobytes(), f"case {case}: M={M} N={N} nnz={len(col)} {np.dtype(dtype).name} rows [{r0}, {r1})"
-                if oracle is not None:
-                    ref = (oracle.csr_serial if dtype == np.float64 else oracle.csr_f32_accum64)(rp, col, val, x)[r0:r1]
-                    tol = 1e-10 if dtype == np.float64 else 1e-5
-                    assert np.max(np.abs(y1.astype(np.float64) - ref)) <= tol * max(np.max(np.abs(ref)), 1e-300), f"case {case}"
-                # the HLL twin on the slab built from this handle (fp64, whole matrices)
-                if dtype == np.float64 and (r0, r1) == (0, M) and case % 2 == 0:
-                    set_tuning("local_patterns", 1)
-                    with sp.HllDevice.from_csr_device(dev) as hdev:
-                        if hdev.info()["local_blocks"] and hdev.info()["pattern_slots"]:
-                            h1 = hdev.spmv(x, sp.HLL_LDS).copy()
-                            set_tuning("local_patterns", 0)
+            assert y1.tobytes() == y0.tobytes(), f"case {case}: M={M} N={N} nnz={len(col)} {np.dtype(dtype).name} rows [{r0}, {r1})"
+            if oracle is not None:
+                ref = (oracle.csr_serial if dtype == np.float64 else oracle.csr_f32_accum64)(rp, col, val, x)[r0:r1]
+                tol = 1e-10 if dtype == np.float64 else 1e-5
+                assert np.max(np.abs(y1.astype(np.float64) - ref)) <= tol * max(np.max(np.abs(ref)), 1e-300), f"case {case}"
+            # the HLL twin on the slab built from this handle (fp64, whole matrices)
+            if dtype == np.float64 and (r0, r1) == (0, M) and case % 2 == 0:
+                with sp.HllDevice.from_csr_device(dev) as hdev:
+                    if hdev.info()["local_blocks"] and hdev.info()["pattern_slots"]:
+                        h1 = hdev.spmv(x, sp.HLL_LDS).copy()
+                        with sp.tuning(local_patterns=0):
                             h0 = hdev.spmv(x, sp.HLL_LDS).copy()
-                            assert h1.tobytes() == h0.tobytes(), f"HLL case {case}: M={M} N={N} nnz={len(col)}"
-                            hll_with_plan[0] += 1
-        finally:
-            set_tuning("local_patterns", -1)
+                        assert h1.tobytes() == h0.tobytes(), f"HLL case {case}: M={M} N={N} nnz={len(col)}"
+                        hll_with_plan[0] += 1
     run.hll_with_plan = hll_with_plan[0]
     return with_plan
 

@@ -51,8 +51,7 @@ import pytest
 import sparsematrixvectormultiplication_amd as sp
 from _util import assert_parity, assert_parity_f32, banded_csr, coo_from_csr, random_csr, wide_range
 from sparsematrixvectormultiplication_amd import synth
-from sparsematrixvectormultiplication_amd.device import set_tuning
-from test_gpu_tile import scattered, tuned
+from test_gpu_tile import scattered
 from test_gpu_transpose import transpose_ref
 
 pytestmark = pytest.mark.gpu
@@ -62,21 +61,6 @@ KPAD = 8192 + 64        # kPad of csrc/hip/spmv_internal.hpp: the zeroed entries
 # info() keys that hold a time or an address
 TIMED = ("place_tries", "place_first_us", "place_best_us", "val_address", "pattern_with_us", "pattern_without_us")
 PINNED = dict(local_patterns=1, place_tries=0)
-LOCAL_DEFAULTS = {"local_patterns": -1, "plan_on_device": 1}    # the knobs test_gpu_tile.py's tuned() does not know
-
-
-@contextlib.contextmanager
-def under(**knobs):
-    """The knobs set for the block, the library's defaults after it (tuned() for the keys it resets, the rest here)."""
-    local = {k: v for k, v in knobs.items() if k in LOCAL_DEFAULTS}
-    try:
-        with tuned(**{k: v for k, v in knobs.items() if k not in LOCAL_DEFAULTS}):
-            for k, v in local.items():
-                set_tuning(k, v)
-            yield
-    finally:
-        for k in local:
-            set_tuning(k, LOCAL_DEFAULTS[k])
 
 
 # ---------------------------------------------------------------- targets: ascending rows without repeats
@@ -358,7 +342,7 @@ def produced(producer, tgt, knobs):
     sources = make_sources(*tgt)
     h = None
     try:
-        with under(**knobs):
+        with sp.tuning(**knobs):
             dirty_allocations(len(tgt[3]), tgt[4].itemsize)
             h = call(tgt, *sources)
             yield h
@@ -462,7 +446,7 @@ def twin_of(case, dtype, oracle, pinned):
     if key not in _TWINS:
         tgt = target_of(case, dtype)
         xs, _, X3 = inputs_of(case, dtype, oracle)
-        with under(**CASES[case][1], **(PINNED if pinned else {})):
+        with sp.tuning(**CASES[case][1], **(PINNED if pinned else {})):
             with sp.CsrDevice(*tgt) as twin:
                 CASES[case][2](twin.info(), pinned)
                 _TWINS[key] = observe(twin, tgt, xs, X3, pinned)
@@ -580,7 +564,7 @@ def test_fsai_apply_is_the_two_products_on_uploads_of_its_factors(gpu, name, dty
         rp, col, val = symmetric_dominant(M, *target_of("T1", np.float64)[2:])
     val = val.astype(dtype)
     rng = np.random.default_rng(41)
-    with under(**PINNED):
+    with sp.tuning(**PINNED):
         with sp.CsrDevice(M, M, rp, col, val) as dev:
             dirty_allocations(len(col), val.itemsize)
             with dev.preconditioner("fsai") as P:

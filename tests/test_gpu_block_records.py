@@ -9,7 +9,6 @@ import pytest
 
 import sparsematrixvectormultiplication_amd as sp
 from sparsematrixvectormultiplication_amd import synth
-from sparsematrixvectormultiplication_amd.device import set_tuning
 from _util import assert_parity, assert_parity_f32
 from test_gpu_plan_sharing import cut_blocks
 
@@ -23,13 +22,11 @@ MATRICES = {"kkt 8x8x8": lambda: synth.kkt_like((8, 8, 8), 5),
 
 @pytest.fixture
 def forced():
-    set_tuning("local_cap", CAP)
-    yield
-    set_tuning("local_patterns", -1)
-    set_tuning("local_cap", 0)
-    set_tuning("local_share", -1)
-    set_tuning("local_segment_cap", 0)
-    set_tuning("stream_xcd", 0)
+    """local_cap CAP for the test; the knobs the tests set themselves are as they were after it, also when a failed test
+    leaves combinations() unfinished."""
+    others = ("local_patterns", "local_share", "local_segment_cap", "stream_xcd")
+    with sp.tuning(local_cap=CAP, **{k: sp.get_tuning(k) for k in others}):
+        yield
 
 
 def blocks_of(rp, lo, hi):
@@ -73,10 +70,9 @@ def combinations(M, rp, col, val, lo, hi):
     for patterns in (1, 0):
         for share in (0, 1):
             for cap in (("budget", "below widest", "none") if patterns else ("budget",)):
-                set_tuning("local_patterns", patterns)
-                set_tuning("local_share", share)
-                set_tuning("local_segment_cap", {"budget": 0, "none": 1}.get(cap) if cap != "below widest" else widest - 16)
-                with sp.CsrDevice(M, M, rp, col, val, row0=lo, row1=hi) as dev:
+                segment_cap = {"budget": 0, "none": 1}.get(cap) if cap != "below widest" else widest - 16
+                with sp.tuning(local_patterns=patterns, local_share=share, local_segment_cap=segment_cap), \
+                        sp.CsrDevice(M, M, rp, col, val, row0=lo, row1=hi) as dev:
                     info = dev.info()
                     name = f"patterns {patterns} share {share} segments {cap}"
                     assert info["local_blocks"] == len(blocks_of(rp, lo, hi)), (name, info["local_blocks"])
@@ -93,7 +89,6 @@ def combinations(M, rp, col, val, lo, hi):
                         elif len(blocks_of(rp, lo, hi)) > 1:
                             assert 0 < rows <= hi - lo and info["pattern_segment_max"] < widest, (name, info)
                     yield name, info, dev
-    set_tuning("local_patterns", 1)
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
@@ -147,15 +142,15 @@ def test_grid_edges(gpu, oracle, forced, shape, dtype):
     blocks, short = {"one block": (1, True), "8 run - 1": (8 * run - 1, False), "8 run + 1": (8 * run + 1, False),
                      "8 run": (8 * run, False), "short last block": (5, True)}[shape]
     hi = rows_for_blocks(rp, blocks, short)
-    set_tuning("stream_xcd", 0 if shape == "one block" else run)
     want = None
-    for name, info, dev in combinations(M, rp, col, val, 0, hi):
-        what = f"{shape} {np.dtype(dtype).name} rows [0, {hi}) {name}"
-        assert info["local_blocks"] == blocks, (what, info["local_blocks"])
-        y = product(dev, x, 0, hi)
-        gate(y, ref, rp, col, val, x, 0, hi, what)
-        want = y.tobytes() if want is None else want
-        assert y.tobytes() == want, what
+    with sp.tuning(stream_xcd=0 if shape == "one block" else run):
+        for name, info, dev in combinations(M, rp, col, val, 0, hi):
+            what = f"{shape} {np.dtype(dtype).name} rows [0, {hi}) {name}"
+            assert info["local_blocks"] == blocks, (what, info["local_blocks"])
+            y = product(dev, x, 0, hi)
+            gate(y, ref, rp, col, val, x, 0, hi, what)
+            want = y.tobytes() if want is None else want
+            assert y.tobytes() == want, what
 
 
 def test_stamps_of_the_head(gpu, forced):
@@ -165,9 +160,7 @@ def test_stamps_of_the_head(gpu, forced):
     M, rp, col, val = synth.kkt_like((12, 10, 9), 5)
     x = rng.uniform(-1, 1, M)
     for share in (0, 1):
-        set_tuning("local_patterns", 1)
-        set_tuning("local_share", share)
-        with sp.CsrDevice(M, M, rp, col, val) as dev:
+        with sp.tuning(local_patterns=1, local_share=share), sp.CsrDevice(M, M, rp, col, val) as dev:
             want = dev.spmv(x, sp.CSR_STREAM).tobytes()
             start, end, _, _ = dev.stamp_blocks(1)
             start2, head, _, xcd = dev.stamp_blocks(2001)

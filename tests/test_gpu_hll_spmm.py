@@ -18,26 +18,6 @@ pytestmark = pytest.mark.gpu
 KS = (1, 2, 3, 4, 7, 8, 9, 16, 33, 64)
 
 
-class tuned:
-    """set_tuning for the duration of a with-block; the defaults come back in a finally."""
-    DEFAULTS = {"stream_local": 1, "stream_tile": -1, "tile_rows": 0, "local_patterns": -1}
-
-    def __init__(self, **kv):
-        self.kv = kv
-
-    def __enter__(self):
-        try:
-            for k, v in self.kv.items():
-                sp.set_tuning(k, v)
-        except BaseException:
-            self.__exit__()
-            raise
-
-    def __exit__(self, *exc):
-        for k in self.kv:
-            sp.set_tuning(k, self.DEFAULTS[k])
-
-
 class DeviceBuffer:
     """spmv_hip_malloc'd bytes, freed on exit."""
 
@@ -180,7 +160,7 @@ def test_hll_spmm_on_handles_with_every_plan_kind(gpu, oracle):
     rng = np.random.default_rng(3)
     for what, M, N, rp, col, val, knobs, has_plan in _plan_cases():
         hll = hll_of(M, N, rp, col, val)
-        with tuned(**knobs):
+        with sp.tuning(**knobs):
             dev = sp.HllDevice(hll)
         with dev:
             info = dev.info()

@@ -79,7 +79,6 @@ def test_stream_kernel_block_shapes_repeatable(gpu, oracle, mean, dtype):
     length across all regimes, both stage sizes and both second halves, launch
     repeatedly into a poisoned y: every row must be written, with the same value
     each time (regression: idle lanes once stored zeros over live rows)."""
-    from sparsematrixvectormultiplication_amd.device import set_tuning
     rng = np.random.default_rng(1000 + mean)
     M, N = 6000, 7000
     row_ptr, col, val = random_csr(rng, M, N, mean, 4 * mean + 4, 0.03, dtype=dtype)
@@ -89,20 +88,17 @@ def test_stream_kernel_block_shapes_repeatable(gpu, oracle, mean, dtype):
     else:
         y_ref = oracle.csr_f32_accum64(row_ptr, col, val, x)
     item = np.dtype(dtype).itemsize
-    try:
-        for cap, walk, blk in ((2048, 0, 256), (4096, 0, 256), (4096, 0, 512), (8192, 0, 512), (8192, 0, 1024),
-                               (1024, 0, 256), (3072, 0, 256)):
-            set_tuning("stream_cap", cap)
-            with sp.CsrDevice(M, N, row_ptr, col, val) as dev:
-                dev.set_x(x)
-                set_tuning("stream_kind", walk)
-                set_tuning("stream_block", blk if blk in (256, 512, 1024) else 256)
+    for cap, walk, blk in ((2048, 0, 256), (4096, 0, 256), (4096, 0, 512), (8192, 0, 512), (8192, 0, 1024),
+                           (1024, 0, 256), (3072, 0, 256)):
+        with sp.tuning(stream_cap=cap), sp.CsrDevice(M, N, row_ptr, col, val) as dev:
+            dev.set_x(x)
+            with sp.tuning(stream_kind=walk, stream_block=blk if blk in (256, 512, 1024) else 256):
                 first = None
                 for rep in range(4):
-                    set_tuning("stream_nt", int(rep != 3))  # (the last launch without the streamed-once hint: same bits)
-                    sp.lib().spmv_hip_memset(dev.y_ptr, 0xFF, M * item)  # NaN pattern
-                    dev.run(sp.CSR_STREAM)
-                    y = dev.get_y()
+                    with sp.tuning(stream_nt=int(rep != 3)):  # (the last launch without the streamed-once hint: same bits)
+                        sp.lib().spmv_hip_memset(dev.y_ptr, 0xFF, M * item)  # NaN pattern
+                        dev.run(sp.CSR_STREAM)
+                        y = dev.get_y()
                     if dtype == np.float64:
                         assert_parity(y, y_ref, row_ptr, col, val, x,
                                       what=f"cap={cap} kind={walk} block={blk} rep={rep}")
@@ -113,11 +109,6 @@ def test_stream_kernel_block_shapes_repeatable(gpu, oracle, mean, dtype):
                     if first is None:
                         first = y
                     assert y.tobytes() == first.tobytes(), "result changed between launches"
-    finally:
-        set_tuning("stream_cap", 0)
-        set_tuning("stream_kind", -1)
-        set_tuning("stream_block", 256)
-        set_tuning("stream_nt", 1)
 
 
 def test_csr_long_rows_are_split_and_summed(gpu, oracle):
@@ -130,20 +121,15 @@ def test_csr_long_rows_are_split_and_summed(gpu, oracle):
     val = rng.uniform(-1, 1, row_ptr[-1])
     x = rng.uniform(-1, 1, N)
     y_ref = oracle.csr_serial(row_ptr, col, val, x)
-    from sparsematrixvectormultiplication_amd.device import set_tuning
-    try:
-        for cap, expect_long in ((2048, 7), (4096, 4), (8192, 3)):
-            set_tuning("stream_cap", cap)
-            with sp.CsrDevice(M, N, row_ptr, col, val) as dev:
-                assert dev.info()["long_rows"] == expect_long
-                for vname, variant in CSR_V:
-                    assert_parity(dev.spmv(x, variant), y_ref, row_ptr, col, val, x,
-                                  what=f"long-{vname}-cap{cap}")
-                # repeated launches reuse the partial-sum scratch
-                dev.run(sp.CSR_STREAM)
-                assert_parity(dev.get_y(), y_ref, row_ptr, col, val, x, what="long-rerun")
-    finally:
-        set_tuning("stream_cap", 0)
+    for cap, expect_long in ((2048, 7), (4096, 4), (8192, 3)):
+        with sp.tuning(stream_cap=cap), sp.CsrDevice(M, N, row_ptr, col, val) as dev:
+            assert dev.info()["long_rows"] == expect_long
+            for vname, variant in CSR_V:
+                assert_parity(dev.spmv(x, variant), y_ref, row_ptr, col, val, x,
+                              what=f"long-{vname}-cap{cap}")
+            # repeated launches reuse the partial-sum scratch
+            dev.run(sp.CSR_STREAM)
+            assert_parity(dev.get_y(), y_ref, row_ptr, col, val, x, what="long-rerun")
 
 
 def test_csr_degenerate_shapes(gpu, oracle):
@@ -407,12 +393,8 @@ def test_full_size_hll_equals_csr_fem_like(gpu, oracle):
                 assert got.tobytes() == want.tobytes()
             assert built.spmv(x, sp.HLL_LDS).tobytes() == hdev.spmv(x, sp.HLL_LDS).tobytes()
         # the gather kernel on the same slab: from 16 Mi slots on its windows fill the 4096-slot stage (hll_lds<.., 8>)
-        from sparsematrixvectormultiplication_amd.device import set_tuning
-        try:
-            set_tuning("stream_kind", 0)
+        with sp.tuning(stream_kind=0):
             y_hll = hdev.spmv(x, sp.HLL_LDS)
-        finally:
-            set_tuning("stream_kind", -1)
         assert np.max(np.abs(y_hll - y_csr)) <= 1e-12 * scale
         assert_parity(y_hll[lo:hi], ref, rp, col[e0:e1], val[e0:e1], x, what="hll_lds rows sample")
     # the stage in between: 16 Mi slots in rows of 1500, two rows a window = 3000 slots, six units (hll_lds<.., 6>)
@@ -421,16 +403,11 @@ def test_full_size_hll_equals_csr_fem_like(gpu, oracle):
     row_ptr = (np.arange(M + 1, dtype=np.int64) * L).astype(np.int32)
     col = (7 * np.arange(M, dtype=np.int32)[:, None] + 3 * np.arange(L, dtype=np.int32)[None, :]).ravel()
     val, x = rng.uniform(-1, 1, M * L), rng.uniform(-1, 1, N)
-    try:
-        set_tuning("stream_local", 0)
-        set_tuning("stream_tile", 0)
+    with sp.tuning(stream_local=0, stream_tile=0):
         with sp.CsrDevice(M, N, row_ptr, col, val) as cdev, sp.HllDevice.from_csr_device(cdev) as hdev:
             info = hdev.info()
             assert info["slots"] == M * L >= 16 << 20 and info["stream_kernel"] == 0 and info["stream_blocks"] == M // 2, info
             y_hll = hdev.spmv(x, sp.HLL_LDS)
-    finally:
-        set_tuning("stream_local", 1)
-        set_tuning("stream_tile", -1)
     assert_parity(y_hll, oracle.csr_serial(row_ptr, col, val, x), row_ptr, col, val, x, what="hll_lds six units")
 
 
@@ -524,7 +501,6 @@ def test_x_window_stream_kernel_matches_oracle_and_gather_kernel(gpu, oracle, dt
     blocks cut by the line limit, partial last blocks.  Checked against the oracle and, bit
     for bit, against csr_stream (same products, same summation order), launched repeatedly
     into a poisoned y."""
-    from sparsematrixvectormultiplication_amd.device import set_tuning
     from _util import banded_csr
     rng = np.random.default_rng(4000 + mean)
     M, N = 5003, 5600
@@ -533,33 +509,28 @@ def test_x_window_stream_kernel_matches_oracle_and_gather_kernel(gpu, oracle, dt
     y_ref = oracle.csr_serial(row_ptr, col, val, x) if dtype == np.float64 else \
         oracle.csr_f32_accum64(row_ptr, col, val, x)
     item = np.dtype(dtype).itemsize
-    try:
-        set_tuning("local_cap", lcap)
-        with sp.CsrDevice(M, N, row_ptr, col, val) as dev:
-            info = dev.info()
-            assert info["local_blocks"] > 0, "banded matrix should get an x-window plan"
-            assert 32 <= info["local_stage_lines"] <= 256 and info["local_stage_lines"] % 32 == 0
-            assert info["stream_bytes"] < info["algo_bytes"]
-            dev.set_x(x)
-            set_tuning("stream_kind", 0)
+    with sp.tuning(local_cap=lcap), sp.CsrDevice(M, N, row_ptr, col, val) as dev:
+        info = dev.info()
+        assert info["local_blocks"] > 0, "banded matrix should get an x-window plan"
+        assert 32 <= info["local_stage_lines"] <= 256 and info["local_stage_lines"] % 32 == 0
+        assert info["stream_bytes"] < info["algo_bytes"]
+        dev.set_x(x)
+        with sp.tuning(stream_kind=0):
             dev.run(sp.CSR_STREAM)
             y_gather = dev.get_y()
-            for kind in (5, -1):
-                set_tuning("stream_kind", kind)
+        for kind in (5, -1):
+            with sp.tuning(stream_kind=kind):
                 for rep in range(3):
                     sp.lib().spmv_hip_memset(dev.y_ptr, 0xFF, M * item)
                     dev.run(sp.CSR_STREAM)
                     y = dev.get_y()
                     assert y.tobytes() == y_gather.tobytes(), f"kind={kind} rep={rep} differs from csr_stream"
-            if dtype == np.float64:
-                assert_parity(y, y_ref, row_ptr, col, val, x, what=f"x-window mean={mean}")
-            else:
-                err = np.max(np.abs(y.astype(np.float64) - y_ref)) / np.max(np.abs(y_ref))
-                assert err <= FP32_NORMWISE_RTOL
-                assert_parity_f32(y, y_ref, row_ptr, col, val, x, what=f"x-window mean={mean}")
-    finally:
-        set_tuning("local_cap", 0)
-        set_tuning("stream_kind", -1)
+        if dtype == np.float64:
+            assert_parity(y, y_ref, row_ptr, col, val, x, what=f"x-window mean={mean}")
+        else:
+            err = np.max(np.abs(y.astype(np.float64) - y_ref)) / np.max(np.abs(y_ref))
+            assert err <= FP32_NORMWISE_RTOL
+            assert_parity_f32(y, y_ref, row_ptr, col, val, x, what=f"x-window mean={mean}")
 
 
 def test_x_window_plan_is_refused_for_scattered_columns(gpu, oracle):
@@ -740,7 +711,6 @@ def test_x_window_kernel_with_long_rows_row_blocks_and_foreign_x(gpu, oracle):
 def test_hll_x_window_kernel_matches_oracle(gpu, oracle, mean, band, empty, far):
     """hll_lds_local (x lines staged in LDS, 16-bit local JA) on banded matrices: windows cut
     by slots, by the line limit and by the row cap; padding slots; M not a multiple of 32."""
-    from sparsematrixvectormultiplication_amd.device import set_tuning
     from _util import banded_csr
     rng = np.random.default_rng(6000 + mean)
     M, N = 4099, 4500
@@ -749,30 +719,26 @@ def test_hll_x_window_kernel_matches_oracle(gpu, oracle, mean, band, empty, far)
     hll = sp.convert_to_hll(sp.PreMatrix.from_arrays(M, N, r, c, v))
     x = rng.uniform(-1, 1, N)
     y_ref = oracle.csr_serial(row_ptr, col, val, x)
-    try:
-        with sp.HllDevice(hll) as dev:
-            info = dev.info()
-            assert info["local_blocks"] > 0 and 0 < info["stream_bytes"] < info["algo_bytes"]
-            dev.set_x(x)
-            set_tuning("stream_kind", 0)
+    with sp.HllDevice(hll) as dev:
+        info = dev.info()
+        assert info["local_blocks"] > 0 and 0 < info["stream_bytes"] < info["algo_bytes"]
+        dev.set_x(x)
+        with sp.tuning(stream_kind=0):
             dev.run(sp.HLL_LDS)
             y_gather = dev.get_y()
             assert_parity(y_gather, y_ref, row_ptr, col, val, x, what="hll_lds")
-            set_tuning("stream_kind", -1)
-            first = None
-            for rep in range(3):
-                sp.lib().spmv_hip_memset(dev.y_ptr, 0xFF, M * 8)
-                dev.run(sp.HLL_LDS)
-                y = dev.get_y()
-                assert_parity(y, y_ref, row_ptr, col, val, x, what=f"hll_lds_local mean={mean} rep={rep}")
-                first = y if first is None else first
-                assert y.tobytes() == first.tobytes()
-        # the slab built on the device gets the same plan and the same bits
-        with sp.CsrDevice(M, N, row_ptr, col, val) as cdev, sp.HllDevice.from_csr_device(cdev) as built:
-            assert built.info()["local_blocks"] == info["local_blocks"]
-            assert built.spmv(x, sp.HLL_LDS).tobytes() == first.tobytes()
-    finally:
-        set_tuning("stream_kind", -1)
+        first = None
+        for rep in range(3):
+            sp.lib().spmv_hip_memset(dev.y_ptr, 0xFF, M * 8)
+            dev.run(sp.HLL_LDS)
+            y = dev.get_y()
+            assert_parity(y, y_ref, row_ptr, col, val, x, what=f"hll_lds_local mean={mean} rep={rep}")
+            first = y if first is None else first
+            assert y.tobytes() == first.tobytes()
+    # the slab built on the device gets the same plan and the same bits
+    with sp.CsrDevice(M, N, row_ptr, col, val) as cdev, sp.HllDevice.from_csr_device(cdev) as built:
+        assert built.info()["local_blocks"] == info["local_blocks"]
+        assert built.spmv(x, sp.HLL_LDS).tobytes() == first.tobytes()
 
 
 # ------------------------------------------- HLL hack ranges (multi-GPU shares)
@@ -983,7 +949,6 @@ def test_plan_built_on_the_device_equals_the_host_plan(gpu, oracle, dtype):
     same blocks, the same number of listed and stored lines and lists, the same bytes held and streamed, the
     same bits out of the kernels; a matrix whose blocks exceed the line limit falls back to the host builder
     either way."""
-    from sparsematrixvectormultiplication_amd.device import set_tuning
     from _util import banded_csr
     rng = np.random.default_rng(77)
     M, N = 9001, 9300
@@ -991,23 +956,19 @@ def test_plan_built_on_the_device_equals_the_host_plan(gpu, oracle, dtype):
         row_ptr, col, val = banded_csr(rng, M, N, mean, band, empty, dtype=dtype)
         x = rng.uniform(-1, 1, N).astype(dtype)
         got = {}
-        try:
-            for where in (1, 0):
-                set_tuning("plan_on_device", where)
-                with sp.CsrDevice(M, N, row_ptr, col, val) as dev:
-                    info = dev.info()
-                    y = dev.spmv(x, sp.CSR_STREAM)
-                    entry = [info["local_blocks"], info["local_lines"], info["local_stage_lines"], y.tobytes(),
-                             info["device_bytes"], info["stream_bytes"], info["local_lines_stored"],
-                             info["local_lists_stored"]]
-                    if dtype == np.float64:
-                        with sp.HllDevice.from_csr_device(dev) as h:
-                            hi = h.info()
-                            entry += [hi["local_blocks"], hi["local_stage_lines"], h.spmv(x, sp.HLL_LDS).tobytes(),
-                                      hi["device_bytes"], hi["local_lines"]]
-                    got[where] = entry
-        finally:
-            set_tuning("plan_on_device", 1)
+        for where in (1, 0):
+            with sp.tuning(plan_on_device=where), sp.CsrDevice(M, N, row_ptr, col, val) as dev:
+                info = dev.info()
+                y = dev.spmv(x, sp.CSR_STREAM)
+                entry = [info["local_blocks"], info["local_lines"], info["local_stage_lines"], y.tobytes(),
+                         info["device_bytes"], info["stream_bytes"], info["local_lines_stored"],
+                         info["local_lists_stored"]]
+                if dtype == np.float64:
+                    with sp.HllDevice.from_csr_device(dev) as h:
+                        hi = h.info()
+                        entry += [hi["local_blocks"], hi["local_stage_lines"], h.spmv(x, sp.HLL_LDS).tobytes(),
+                                  hi["device_bytes"], hi["local_lines"]]
+                got[where] = entry
         assert got[1][0] > 0, "banded matrix should get a plan"
         assert got[1] == got[0], f"device-built plan differs from the host-built one (mean={mean})"
     # blocks beyond the line limit: the device pass reports it, the host builder takes over (and cuts by lines)
@@ -1286,31 +1247,27 @@ def test_pattern_plan_rebuilds_the_slots_bit_for_bit(gpu, oracle, dtype):
     stencil (auto: plan kept), a band with random columns (auto: not kept; forced: every row its own pattern), blocks of
     very short rows (several row passes per block), empty rows, a row block of a bigger matrix."""
     from sparsematrixvectormultiplication_amd import synth
-    from sparsematrixvectormultiplication_amd.device import set_tuning
     from _util import banded_csr
     rng = np.random.default_rng(91)
 
     def run(M, N, rp, col, val, forced, expect_plan, row0=0, row1=None):
         x = rng.uniform(-1, 1, N).astype(dtype)
         ref = (oracle.csr_serial if dtype == np.float64 else oracle.csr_f32_accum64)(rp, col, val, x)
-        set_tuning("local_patterns", 1 if forced else -1)
-        try:
-            with sp.CsrDevice(M, N, rp, col, val, row0=row0, row1=M if row1 is None else row1) as dev:
-                info = dev.info()
-                assert info["local_blocks"] > 0
-                if expect_plan is not None:
-                    assert (info["pattern_slots"] > 0) == expect_plan, info["pattern_slots"]
-                lo, hi = row0, M if row1 is None else row1
-                sp.lib().spmv_hip_memset(dev.y_ptr, 0xFF, M * x.itemsize)
-                y = dev.spmv(x, sp.CSR_STREAM)[lo:hi].copy()
-                tol = 1e-10 if dtype == np.float64 else 1e-5
-                assert np.max(np.abs(y.astype(np.float64) - ref[lo:hi])) <= tol * max(np.max(np.abs(ref)), 1e-300)
-                set_tuning("local_patterns", 0)                   # the same handle through the slot stream
+        with sp.tuning(local_patterns=1 if forced else -1), \
+                sp.CsrDevice(M, N, rp, col, val, row0=row0, row1=M if row1 is None else row1) as dev:
+            info = dev.info()
+            assert info["local_blocks"] > 0
+            if expect_plan is not None:
+                assert (info["pattern_slots"] > 0) == expect_plan, info["pattern_slots"]
+            lo, hi = row0, M if row1 is None else row1
+            sp.lib().spmv_hip_memset(dev.y_ptr, 0xFF, M * x.itemsize)
+            y = dev.spmv(x, sp.CSR_STREAM)[lo:hi].copy()
+            tol = 1e-10 if dtype == np.float64 else 1e-5
+            assert np.max(np.abs(y.astype(np.float64) - ref[lo:hi])) <= tol * max(np.max(np.abs(ref)), 1e-300)
+            with sp.tuning(local_patterns=0):                     # the same handle through the slot stream
                 y0 = dev.spmv(x, sp.CSR_STREAM)[lo:hi].copy()
-                assert y.tobytes() == y0.tobytes()
-                return info
-        finally:
-            set_tuning("local_patterns", -1)
+            assert y.tobytes() == y0.tobytes()
+            return info
 
     M, rp, col, val = synth.kkt_like((24, 24, 25), 5)
     val = val.astype(dtype)
@@ -1344,7 +1301,6 @@ def test_hll_pattern_plan_rebuilds_the_slots_bit_for_bit(gpu, oracle):
     the 16-bit slot stream: the same bits; both builders of the slab (host, from a resident CSR handle); hacks of
     different lengths, empty rows, a hack range of a bigger matrix."""
     from sparsematrixvectormultiplication_amd import synth
-    from sparsematrixvectormultiplication_amd.device import set_tuning
     rng = np.random.default_rng(93)
     M, rp, col, val = synth.kkt_like((24, 24, 25), 5)
     x = rng.uniform(-1, 1, M)
@@ -1356,13 +1312,11 @@ def test_hll_pattern_plan_rebuilds_the_slots_bit_for_bit(gpu, oracle):
         sp.lib().spmv_hip_memset(dev.y_ptr, 0xFF, M * 8)
         y = dev.spmv(x, sp.HLL_LDS)[lo:hi].copy()
         assert np.max(np.abs(y - ref[lo:hi])) <= 1e-10 * np.max(np.abs(ref))
-        set_tuning("local_patterns", 0)                           # the same handle through the slot stream
-        y0 = dev.spmv(x, sp.HLL_LDS)[lo:hi].copy()
-        set_tuning("local_patterns", 1)
+        with sp.tuning(local_patterns=0):                         # the same handle through the slot stream
+            y0 = dev.spmv(x, sp.HLL_LDS)[lo:hi].copy()
         assert y.tobytes() == y0.tobytes()
 
-    set_tuning("local_patterns", 1)
-    try:
+    with sp.tuning(local_patterns=1):
         hll = sp.convert_to_hll(sp.PreMatrix.from_arrays(M, M, np.repeat(np.arange(M, dtype=np.int32), np.diff(rp)), col, val))
         with sp.HllDevice(hll) as dev:
             check(dev)
@@ -1395,10 +1349,8 @@ def test_hll_pattern_plan_rebuilds_the_slots_bit_for_bit(gpu, oracle):
             assert dev3.info()["pattern_slots"] > 0
             y = dev3.spmv(x2, sp.HLL_LDS)
             assert np.max(np.abs(y - ref2)) <= 1e-10 * np.max(np.abs(ref2))
-            set_tuning("local_patterns", 0)
-            assert dev3.spmv(x2, sp.HLL_LDS).tobytes() == y.tobytes()
-    finally:
-        set_tuning("local_patterns", -1)
+            with sp.tuning(local_patterns=0):
+                assert dev3.spmv(x2, sp.HLL_LDS).tobytes() == y.tobytes()
 
 
 def test_pattern_plan_fuzz(gpu, oracle):
@@ -1429,14 +1381,10 @@ def test_power_iteration_halo_single_rank_communicator(gpu):
             dev.set_x(x0)
             lam_halo, ms = dev.power_iterate_halo(4)       # exchange on the second stream beside the interior blocks
             assert ms > 0 and lam_halo == lam_plain and dev.get_x().tobytes() == x_plain.tobytes()
-            from sparsematrixvectormultiplication_amd.device import set_tuning
-            set_tuning("halo_overlap", 0)                  # strictly in order: the same bits
-            try:
+            with sp.tuning(halo_overlap=0):                # strictly in order: the same bits
                 dev.set_x(x0)
                 lam_serial, _ = dev.power_iterate_halo(4)
                 assert lam_serial == lam_plain and dev.get_x().tobytes() == x_plain.tobytes()
-            finally:
-                set_tuning("halo_overlap", 1)
             # the loop over a column-split handle (what halo setup makes on a KKT-like cut at world size > 1; here made
             # by hand, a world of one has no halo): two launches per product, overlapped or in order the same bits, and
             # the plain loop's result within the tolerance (a row's two partial sums are added in another order)
@@ -1446,12 +1394,9 @@ def test_power_iteration_halo_single_rank_communicator(gpu):
             x_split = dev.get_x()
             assert abs(lam_split - lam_plain) <= 1e-10 * abs(lam_plain)
             assert np.max(np.abs(x_split - x_plain) / np.maximum(np.abs(x_plain), 1e-300)) <= 1e-10
-            set_tuning("halo_overlap", 0)
-            try:
+            with sp.tuning(halo_overlap=0):
                 dev.set_x(x0)
                 lam_split_serial, _ = dev.power_iterate_halo(4)
                 assert lam_split_serial == lam_split and dev.get_x().tobytes() == x_split.tobytes()
-            finally:
-                set_tuning("halo_overlap", 1)
         finally:
             comm.close()

@@ -7,7 +7,6 @@ import pytest
 
 import sparsematrixvectormultiplication_amd as sp
 from sparsematrixvectormultiplication_amd import synth
-from sparsematrixvectormultiplication_amd.device import set_tuning
 
 pytestmark = pytest.mark.gpu
 
@@ -44,16 +43,15 @@ def both(dev, x, run=None):
     """y of the segment kernel and of the slot-stream kernel on the same handle."""
     out = []
     for p in (1, 0):
-        set_tuning("local_patterns", p)
-        sp.lib().spmv_hip_memset(dev.y_ptr, 0xFF, dev.M * x.itemsize)
-        if run is None:
-            out.append(dev.spmv(x, sp.CSR_STREAM).copy())
-        else:
-            dev.set_x(x)
-            run(dev)
-            sp.hip_sync()
-            out.append(dev.get_y().copy())
-    set_tuning("local_patterns", 1)
+        with sp.tuning(local_patterns=p):
+            sp.lib().spmv_hip_memset(dev.y_ptr, 0xFF, dev.M * x.itemsize)
+            if run is None:
+                out.append(dev.spmv(x, sp.CSR_STREAM).copy())
+            else:
+                dev.set_x(x)
+                run(dev)
+                sp.hip_sync()
+                out.append(dev.get_y().copy())
     return out
 
 
@@ -70,12 +68,8 @@ def check_budget(info, dtype):
 
 @pytest.fixture
 def forced():
-    set_tuning("local_patterns", 1)
-    set_tuning("local_cap", 2048)
-    yield
-    set_tuning("local_patterns", -1)
-    set_tuning("local_cap", 0)
-    set_tuning("stream_xcd", 0)
+    with sp.tuning(local_patterns=1, local_cap=2048):
+        yield
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
@@ -114,10 +108,10 @@ def test_segment_under_stream_xcd(gpu, forced, xcd):
     x = rng.uniform(-1, 1, M)
     with sp.CsrDevice(M, M, rp, col, val) as dev:
         assert dev.info()["pattern_slots"] > 0
-        set_tuning("stream_xcd", 0)
-        base, _ = both(dev, x)
-        set_tuning("stream_xcd", xcd)
-        y, y0 = both(dev, x)
+        with sp.tuning(stream_xcd=0):
+            base, _ = both(dev, x)
+        with sp.tuning(stream_xcd=xcd):
+            y, y0 = both(dev, x)
         assert y.tobytes() == y0.tobytes() == base.tobytes()
 
 
@@ -130,8 +124,8 @@ def test_segment_on_the_block_sub_lists(gpu, forced):
     x = rng.uniform(-1, 1, n)
     with sp.CsrDevice(M, M, rp, col, val, lo, hi) as dev:
         assert dev.info()["pattern_slots"] > 0
-        set_tuning("local_patterns", 1)
-        whole = dev.spmv(x, sp.CSR_STREAM)[lo:hi].copy()
+        with sp.tuning(local_patterns=1):
+            whole = dev.spmv(x, sp.CSR_STREAM)[lo:hi].copy()
         counts = dev.split_interior()
         assert counts["interior_blocks"] > 0 and counts["boundary_blocks"] > 0
         dev.split_columns(lo, hi)
@@ -175,9 +169,8 @@ def test_hll_patterns_unchanged(gpu, oracle, forced):
     with sp.HllDevice(hll) as dev:
         assert dev.info()["local_blocks"] > 0 and dev.info()["pattern_slots"] > 0
         y = dev.spmv(x, sp.HLL_LDS).copy()
-        set_tuning("local_patterns", 0)
-        y0 = dev.spmv(x, sp.HLL_LDS).copy()
-        set_tuning("local_patterns", 1)
+        with sp.tuning(local_patterns=0):
+            y0 = dev.spmv(x, sp.HLL_LDS).copy()
         assert y.tobytes() == y0.tobytes()
         ref = oracle.csr_serial(rp, col, val, x)
         assert np.max(np.abs(y - ref)) <= 1e-10 * np.max(np.abs(ref))
@@ -195,10 +188,8 @@ def test_device_bytes_count_the_pattern_plan(gpu, forced):
     for name, upload in uploads.items():
         infos = []
         for p in (1, 0):
-            set_tuning("local_patterns", p)
-            with upload() as dev:
+            with sp.tuning(local_patterns=p), upload() as dev:
                 infos.append(dev.info())
-        set_tuning("local_patterns", 1)
         with_plan, without = infos
         assert with_plan["local_blocks"] > 0 and with_plan["pattern_slots"] > 0 and without["pattern_slots"] == 0, name
         tables = 2 * (with_plan["pattern_slots"] + 1024) + 4 * M + 8 * with_plan["local_blocks"]

@@ -7,7 +7,6 @@ import pytest
 
 import sparsematrixvectormultiplication_amd as sp
 from sparsematrixvectormultiplication_amd import synth
-from sparsematrixvectormultiplication_amd.device import set_tuning
 
 pytestmark = pytest.mark.gpu
 
@@ -20,12 +19,8 @@ KKT = (12, 12, 56)
 
 @pytest.fixture
 def forced():
-    set_tuning("local_patterns", 1)
-    set_tuning("local_cap", CAP)
-    yield
-    set_tuning("local_patterns", -1)
-    set_tuning("local_cap", 0)
-    set_tuning("local_share", -1)
+    with sp.tuning(local_patterns=1, local_cap=CAP):
+        yield
 
 
 def cut_blocks(rp):
@@ -104,21 +99,19 @@ def uploads(M, rp, col, val, x, lo=0, hi=None, run=None):
     """{local_share: (info, y of the pattern kernel, y of the slot stream)} of fresh uploads of rows [lo, hi)."""
     hi, out = M if hi is None else hi, {}
     for share in (1, 0, 2):
-        set_tuning("local_share", share)
-        with sp.CsrDevice(M, M, rp, col, val, row0=lo, row1=hi) as dev:
+        with sp.tuning(local_share=share), sp.CsrDevice(M, M, rp, col, val, row0=lo, row1=hi) as dev:
             info, ys = dev.info(), []
             assert info["local_blocks"] > 0 and info["pattern_slots"] > 0, info
             for patterns in (1, 0):
-                set_tuning("local_patterns", patterns)
-                sp.lib().spmv_hip_memset(dev.y_ptr, 0xFF, dev.M * x.itemsize)
-                if run is None:
-                    ys.append(dev.spmv(x, sp.CSR_STREAM)[lo:hi].copy())
-                else:
-                    dev.set_x(x)
-                    run(dev)
-                    sp.hip_sync()
-                    ys.append(dev.get_y()[lo:hi].copy())
-            set_tuning("local_patterns", 1)
+                with sp.tuning(local_patterns=patterns):
+                    sp.lib().spmv_hip_memset(dev.y_ptr, 0xFF, dev.M * x.itemsize)
+                    if run is None:
+                        ys.append(dev.spmv(x, sp.CSR_STREAM)[lo:hi].copy())
+                    else:
+                        dev.set_x(x)
+                        run(dev)
+                        sp.hip_sync()
+                        ys.append(dev.get_y()[lo:hi].copy())
             out[share] = (info, ys[0], ys[1])
     return out
 
@@ -222,8 +215,7 @@ def test_hll_x_window_handles_are_unchanged(gpu, oracle, forced):
     hll = sp.convert_to_hll(sp.PreMatrix.from_arrays(M, M, np.repeat(np.arange(M, dtype=np.int32), np.diff(rp)), col, val))
     got = {}
     for share in (1, 0):
-        set_tuning("local_share", share)
-        with sp.HllDevice(hll) as dev:
+        with sp.tuning(local_share=share), sp.HllDevice(hll) as dev:
             info = dev.info()
             assert info["local_blocks"] > 0 and info["pattern_slots"] > 0
             got[share] = (info["device_bytes"], info["stream_bytes"], dev.spmv(x, sp.HLL_LDS).tobytes())

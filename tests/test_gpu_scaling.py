@@ -30,29 +30,6 @@ F64, F32 = np.float64, np.float32
 DTYPES = pytest.mark.parametrize("dtype", [F64, F32], ids=["f64", "f32"])
 
 
-class tuned:
-    """set_tuning for the duration of a with-block; every key it sets goes back to its default after."""
-    DEFAULTS = {"stream_tile": -1, "tile_rows": 0, "tile_lmax": 1536, "tile_density": 4, "stream_kind": -1, "tile_long": 1,
-                "tile_pack": 1, "stream_local": 1, "tile_expand": -1, "stream_cap": 0, "local_cap": 0, "local_patterns": -1,
-                "skew_rows": 1, "tile_items": 1008, "stream_xcd": 0, "stream_nt": 1, "local_nt": -1,
-                "tile_gather_ahead": 0}
-
-    def __init__(self, **kv):
-        self.kv = kv
-
-    def __enter__(self):
-        try:
-            for k, v in self.kv.items():
-                sp.set_tuning(k, v)
-        except BaseException:
-            self.__exit__()
-            raise
-
-    def __exit__(self, *exc):
-        for k in self.kv:
-            sp.set_tuning(k, self.DEFAULTS[k])
-
-
 PLAN_KEYS = ("stream_kernel", "local_blocks", "local_lines", "local_stage_lines", "long_rows", "stream_blocks", "slots",
              "hacks", "pattern_slots", "auto_variant", "lanes_per_row", "nz")
 
@@ -104,7 +81,7 @@ def pair(make, knobs):
     knobs = dict(knobs)
     knobs.setdefault("local_patterns", 0)
     assert knobs["local_patterns"] in (0, 1)
-    with tuned(**knobs):
+    with sp.tuning(**knobs):
         with make("plain") as d0, make("scaled") as d1:
             i0, i1 = d0.info(), d1.info()
             assert plan(i0) == plan(i1), "the two handles of one structure report different plans"
@@ -130,7 +107,7 @@ def check_spmv(oracle, case, make, knobs, fingerprint, variant, what, rows=None,
         case.gate(oracle, y1, case.xs, rows, what)
         case.identity(y1, y0, rows, what)
         for kv in launch_knobs:
-            with tuned(**kv):
+            with sp.tuning(**kv):
                 assert_same_numbers(run(d1, case.xs, variant)[slice(*(rows or (0, case.M)))],
                                     y1[slice(*(rows or (0, case.M)))], f"{what} {kv}")
         return info
@@ -548,6 +525,6 @@ def test_full_size_powerlaw_fp32_every_row(gpu, oracle):
         # the same plan through its gather passes (no expanded x), plain and gathering one pass early: the same bits,
         # from the instantiations with the streamed-once hint that only a handle of this size launches
         for kv in ({"tile_expand": 0}, {"tile_expand": 0, "tile_gather_ahead": 1}):
-            with tuned(**kv):
+            with sp.tuning(**kv):
                 assert_same_numbers(run(d1, case.xs, sp.CSR_AUTO), y1, f"powerlaw fp32 {kv}")
     case.gate(oracle, y1, case.xs, what="powerlaw fp32")

@@ -46,7 +46,7 @@ import sparsematrixvectormultiplication_amd as sp
 import test_solver_routes_host as H
 from _util import assert_parity, assert_parity_f32
 from test_gpu_bicgstab import bicgstab_ref
-from test_gpu_scaling import plan, tuned
+from test_gpu_scaling import plan
 from test_gpu_solver_sizes import differences
 
 pytestmark = pytest.mark.gpu
@@ -274,7 +274,7 @@ def handles(route_id, kind, dtype, transpose=False, jacobi=False, cheb=False, na
     lens = np.diff(rp)
     made = []
     try:
-        with tuned(**r["upload"]):
+        with sp.tuning(**r["upload"]):
             dev = sp.CsrDevice(M, N, rp, col, H.held(name, kind, dtype))
             made.append(dev)
             info = dev.info()
@@ -291,7 +291,7 @@ def handles(route_id, kind, dtype, transpose=False, jacobi=False, cheb=False, na
             if cheb:
                 P = dev.preconditioner("chebyshev", degree=CHEB_DEGREE)
                 made.append(P)
-        with tuned(**r["launch"]):
+        with sp.tuning(**r["launch"]):
             yield dev, at, J, P
     finally:
         for obj in reversed(made):

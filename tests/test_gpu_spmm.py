@@ -16,22 +16,6 @@ K_F64 = (1, 2, 3, 4, 7, 8, 9, 16, 33, 64)
 K_F32 = (1, 2, 4, 5, 8, 33)
 
 
-class tuned:
-    """set_tuning for the duration of a with-block (back to the defaults after)."""
-    DEFAULTS = {"local_patterns": -1, "stream_tile": -1}
-
-    def __init__(self, **kv):
-        self.kv = kv
-
-    def __enter__(self):
-        for k, v in self.kv.items():
-            sp.set_tuning(k, v)
-
-    def __exit__(self, *exc):
-        for k in self.kv:
-            sp.set_tuning(k, self.DEFAULTS[k])
-
-
 def check_columns(oracle, Y, X, rp, col, val, what, rows=None):
     """Every column of Y against the oracle on the same column of X (rows: the handle's row range)."""
     lo, hi = rows if rows is not None else (0, len(rp) - 1)
@@ -142,7 +126,7 @@ def _plan_cases():
 def test_spmm_on_handles_with_every_plan_kind(gpu, oracle):
     rng = np.random.default_rng(3)
     for what, M, N, rp, col, val, knobs, has_plan in _plan_cases():
-        with tuned(**knobs):
+        with sp.tuning(**knobs):
             dev = sp.CsrDevice(M, N, rp, col, val)
         with dev:
             info = dev.info()

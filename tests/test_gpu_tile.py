@@ -10,7 +10,6 @@ import pytest
 import sparsematrixvectormultiplication_amd as sp
 from _util import FP32_NORMWISE_RTOL, assert_parity, assert_parity_f32
 from conftest import GOLDEN_CASES, golden_path, load_golden
-from sparsematrixvectormultiplication_amd.device import set_tuning
 
 pytestmark = pytest.mark.gpu
 
@@ -25,23 +24,6 @@ def scattered(rng, M, N, mean, sigma=None, dtype=np.float64, lens=None):
         col = np.clip(rows * (N - 1) // max(M - 1, 1) + np.rint(rng.normal(0, sigma, rp[-1])).astype(np.int64), 0, N - 1)
     order = np.lexsort((col, rows))
     return rp, col[order].astype(np.int32), rng.uniform(-1, 1, rp[-1]).astype(dtype)
-
-
-class tuned:
-    def __init__(self, **kv):
-        self.kv = kv
-
-    def __enter__(self):
-        for k, v in self.kv.items():
-            set_tuning(k, v)
-
-    def __exit__(self, *exc):
-        defaults = {"stream_tile": -1, "tile_rows": 0, "tile_lmax": 1536, "tile_density": 4, "stream_kind": -1,
-                    "tile_balance": 1, "tile_long": 1, "tile_pack": 1, "stream_local": 1, "tile_places": 0,
-                    "tile_streams": 1, "tile_fit": 1, "tile_plan_on_device": 1, "place_tries": 12, "tile_min_pass": 256, "tile_mid": 1,
-                    "tile_expand": -1}
-        for k in self.kv:
-            set_tuning(k, defaults[k])
 
 
 def check(dev, x, y_ref, rp, col, val, dtype, what):
@@ -76,7 +58,7 @@ def test_tile_kernel_gather_passes_uniform_columns(gpu, oracle, dtype, rows):
     rp, col, val = scattered(rng, M, N, 18, dtype=dtype)
     x = rng.uniform(-1, 1, N).astype(dtype)
     y_ref = reference(oracle, rp, col, val, x, dtype)
-    with tuned(stream_tile=1, tile_rows=rows):
+    with sp.tuning(stream_tile=1, tile_rows=rows):
         with sp.CsrDevice(M, N, rp, col, val) as dev:
             info = dev.info()
             assert info["stream_kernel"] == 3 and info["tile_blocks"] >= (M + rows - 1) // rows
@@ -85,7 +67,7 @@ def test_tile_kernel_gather_passes_uniform_columns(gpu, oracle, dtype, rows):
                 assert info["tile_passes"] > info["tile_blocks"]   # several column passes per block
             y = check(dev, x, y_ref, rp, col, val, dtype, f"uniform rows={rows}")
             # the gather kernel on the same handle agrees within the gate too
-            with tuned(stream_kind=0):
+            with sp.tuning(stream_kind=0):
                 y0 = dev.spmv(x, sp.CSR_STREAM)
             scale = np.max(np.abs(y_ref))
             assert np.max(np.abs(y.astype(np.float64) - y0)) <= (1e-10 if dtype == np.float64 else 1e-5) * scale
@@ -107,16 +89,15 @@ def test_tile_kernel_expanded_x_gives_the_gather_passes_bits(gpu, oracle, dtype,
     rp, col, val = scattered(rng, M, N, 14, dtype=dtype, lens=lens)
     x = rng.uniform(-1, 1, N).astype(dtype)
     y_ref = reference(oracle, rp, col, val, x, dtype)
-    with tuned(stream_tile=1, tile_rows=1024, tile_expand=1, tile_lmax=4096, tile_density=0, tile_pack=0, stream_local=0):
+    with sp.tuning(stream_tile=1, tile_rows=1024, tile_expand=1, tile_lmax=4096, tile_density=0, tile_pack=0, stream_local=0):
         with sp.CsrDevice(M, N, rp, col, val) as dev:
             info = dev.info()
             assert info["stream_kernel"] == 3 and info["tile_staged_entries"] == 0
             assert info["tile_expanded_entries"] >= info["tile_entries"] == rp[-1]
             y = check(dev, x, y_ref, rp, col, val, dtype, f"expanded N={N}")
-            set_tuning("tile_expand", 0)                  # the same handle, the gather passes
-            y_gather = check(dev, x, y_ref, rp, col, val, dtype, f"gather N={N}")
-            assert y.tobytes() == y_gather.tobytes()
-            set_tuning("tile_expand", 1)
+            with sp.tuning(tile_expand=0):                # the same handle, the gather passes
+                y_gather = check(dev, x, y_ref, rp, col, val, dtype, f"gather N={N}")
+                assert y.tobytes() == y_gather.tobytes()
             # a foreign, misaligned x: the expansion copies 16-byte pieces -- such a launch takes the gather passes
             L, item = sp.lib(), x.itemsize
             buf, ybuf = C.c_void_p(), C.c_void_p()
@@ -134,7 +115,7 @@ def test_tile_kernel_expanded_x_gives_the_gather_passes_bits(gpu, oracle, dtype,
                 L.spmv_hip_free(buf)
                 L.spmv_hip_free(ybuf)
     # auto: a small plan is not expanded
-    with tuned(stream_tile=1, tile_rows=1024):
+    with sp.tuning(stream_tile=1, tile_rows=1024):
         with sp.CsrDevice(M, N, rp, col, val) as dev:
             assert dev.info()["tile_expanded_entries"] == 0
 
@@ -153,24 +134,21 @@ def test_tile_kernels_above_the_streamed_once_threshold_fp64(gpu, oracle):
     N = 3_000_000
     col = (j * (N // L) + r * 7919 % (N // L)).astype(np.int32).ravel()   # ascending in a row, rows far apart in x
     x = rng.uniform(-1, 1, N)
-    with tuned(stream_tile=1, tile_rows=1024, tile_expand=1, tile_density=0, tile_pack=0, stream_local=0):
+    with sp.tuning(stream_tile=1, tile_rows=1024, tile_expand=1, tile_density=0, tile_pack=0, stream_local=0):
         with sp.CsrDevice(M, N, rp, col, val) as dev:
             info = dev.info()
             assert info["stream_kernel"] == 3 and info["tile_staged_entries"] == 0
             assert info["tile_expanded_entries"] >= info["tile_entries"] == M * L
             y = dev.spmv(x, sp.CSR_STREAM)
             assert_parity(y, oracle.csr_serial(rp, col, val, x), rp, col, val, x, what="expanded, streamed once")
-            try:
-                set_tuning("tile_expand", 0)
+            with sp.tuning(tile_expand=0):
                 assert dev.spmv(x, sp.CSR_STREAM).tobytes() == y.tobytes(), "gather passes"
-                set_tuning("tile_gather_ahead", 1)
-                assert dev.spmv(x, sp.CSR_STREAM).tobytes() == y.tobytes(), "gather passes, one pass early"
-            finally:
-                set_tuning("tile_gather_ahead", 0)
+                with sp.tuning(tile_gather_ahead=1):
+                    assert dev.spmv(x, sp.CSR_STREAM).tobytes() == y.tobytes(), "gather passes, one pass early"
     N = M + 3 * L
     col = (r + 3 * j).astype(np.int32).ravel()
     x = rng.uniform(-1, 1, N)
-    with tuned(stream_tile=1, tile_rows=2048, stream_local=0):
+    with sp.tuning(stream_tile=1, tile_rows=2048, stream_local=0):
         with sp.CsrDevice(M, N, rp, col, val) as dev:
             info = dev.info()
             assert info["stream_kernel"] == 3 and info["tile_staged_entries"] > 0.5 * info["tile_entries"]
@@ -188,7 +166,7 @@ def test_tile_kernel_staged_passes_banded_columns(gpu, oracle, dtype, mean, sigm
     x = rng.uniform(-1, 1, N).astype(dtype)
     y_ref = reference(oracle, rp, col, val, x, dtype)
     # (the narrowest of these bands would get an x-window plan: switched off, the tile kernel is what is under test)
-    with tuned(stream_tile=1, tile_rows=2048, tile_pack=pack, stream_local=0):
+    with sp.tuning(stream_tile=1, tile_rows=2048, tile_pack=pack, stream_local=0):
         with sp.CsrDevice(M, N, rp, col, val) as dev:
             info = dev.info()
             assert info["local_blocks"] == 0
@@ -217,7 +195,7 @@ def test_tile_kernel_packed_plan_outliers_and_fallback(gpu, oracle, dtype, far, 
     y_ref = reference(oracle, rp, col, val, x, dtype)
     item = np.dtype(dtype).itemsize
     L = sp.lib()
-    with tuned(stream_tile=1, tile_rows=2048):
+    with sp.tuning(stream_tile=1, tile_rows=2048):
         with sp.CsrDevice(M, N, rp, col, val) as dev:
             info = dev.info()
             assert info["stream_kernel"] == 3 and info["tile_entries"] == rp[-1]
@@ -259,7 +237,7 @@ def test_tile_kernel_skewed_rows_sub_runs_and_split_rows(gpu, oracle, dtype):
     x = rng.uniform(-1, 1, N).astype(dtype)
     y_ref = reference(oracle, rp, col, val, x, dtype)
     for lmax, balance, long_plan in ((16384, 1, 0), (700, 1, 0), (700, 0, 2), (40, 1, 2), (16384, 1, 2)):
-        with tuned(stream_tile=1, tile_rows=512, tile_lmax=lmax, tile_balance=balance, tile_long=long_plan):
+        with sp.tuning(stream_tile=1, tile_rows=512, tile_lmax=lmax, tile_balance=balance, tile_long=long_plan):
             with sp.CsrDevice(M, N, rp, col, val) as dev:
                 info = dev.info()
                 assert info["stream_kernel"] == 3 and info["tile_entries"] == int(lens[lens <= lmax].sum())
@@ -281,7 +259,7 @@ def digests_by_builder(make_handle):
     """the handle's tile-plan digest with the plan built by host threads and by the device kernels"""
     out = []
     for on_device in (0, 1):
-        with tuned(tile_plan_on_device=on_device):
+        with sp.tuning(tile_plan_on_device=on_device):
             with make_handle() as dev:
                 out.append((dev.tile_digest(), dev.info()))
     return out
@@ -347,14 +325,14 @@ def test_tile_plan_built_on_the_device_is_the_host_plan(gpu, oracle, dtype):
                                                          tile_pack=0, stream_local=0)))
     must_build = {"mid tier": "tile_mid_rows", "expanded x": "tile_expanded_entries"}   # (not passed by not building the thing)
     for what, M, N, rp, col, val, knobs in cases:
-        with tuned(**knobs):
+        with sp.tuning(**knobs):
             host, device = digests_by_builder(lambda: sp.CsrDevice(M, N, rp, col, val))
             assert host[1]["stream_kernel"] == 3, what
             assert_same_plan(host, device, what)
             if what in must_build:
                 assert host[1][must_build[what]] > 0 and device[1][must_build[what]] > 0, (what, host[1], device[1])
             x = rng.uniform(-1, 1, N).astype(dtype)
-            with tuned(tile_plan_on_device=1):
+            with sp.tuning(tile_plan_on_device=1):
                 with sp.CsrDevice(M, N, rp, col, val) as dev:
                     check(dev, x, reference(oracle, rp, col, val, x, dtype), rp, col, val, dtype, what + " (device-built plan)")
 
@@ -368,7 +346,7 @@ def test_hll_tile_plan_built_on_the_device_is_the_host_plan(gpu, oracle):
     rp, col, val = scattered(rng, M, N, 16)
     r, c, v = coo_from_csr(rp, col, val)
     hll = sp.convert_to_hll(sp.PreMatrix.from_arrays(M, N, r, c, v))
-    with tuned(stream_tile=1, tile_rows=1024, stream_local=0):
+    with sp.tuning(stream_tile=1, tile_rows=1024, stream_local=0):
         host, device = digests_by_builder(lambda: sp.HllDevice(hll))
         assert host[1]["stream_kernel"] == 2
         assert_same_plan(host, device, "hll slab")
@@ -387,7 +365,7 @@ def test_tile_kernel_row_block_handle_and_foreign_x(gpu, oracle):
     x = rng.uniform(-1, 1, N)
     y_ref = oracle.csr_serial(rp, col, val, x)
     L = sp.lib()
-    with tuned(stream_tile=1, tile_rows=1024):
+    with sp.tuning(stream_tile=1, tile_rows=1024):
         with sp.CsrDevice(M, N, rp, col, val, row0=5000, row1=27001) as part:
             assert part.info()["stream_kernel"] == 3
             y = part.spmv(x, sp.CSR_STREAM)
@@ -416,7 +394,7 @@ def test_tile_kernel_on_reference_golden(gpu, name):
     """The reference's own fixtures through the tile kernel (forced; tiny matrices: one block)."""
     g = load_golden(name)
     csr = sp.convert_in_csr(sp.read_matrix_market(golden_path(name)))
-    with tuned(stream_tile=1, tile_rows=256, tile_lmax=100):
+    with sp.tuning(stream_tile=1, tile_rows=256, tile_lmax=100):
         with sp.CsrDevice.from_host(csr) as dev:
             if csr.nz and not dev.info()["local_blocks"]:
                 assert dev.info()["stream_kernel"] == 3
@@ -438,7 +416,7 @@ def test_hll_slab_rows_through_the_tile_kernel(gpu, oracle, mean, sigma):
     y_ref = oracle.csr_serial(rp, col, val, x)
     r, c, v = coo_from_csr(rp, col, val)
     hll = sp.convert_to_hll(sp.PreMatrix.from_arrays(M, N, r, c, v))
-    with tuned(stream_tile=1, tile_rows=1024, stream_local=0):  # (no x-window plan: the tile kernel is under test)
+    with sp.tuning(stream_tile=1, tile_rows=1024, stream_local=0):  # (no x-window plan: the tile kernel is under test)
         with sp.HllDevice(hll) as dev:
             info = dev.info()
             assert info["local_blocks"] == 0
@@ -450,7 +428,7 @@ def test_hll_slab_rows_through_the_tile_kernel(gpu, oracle, mean, sigma):
                 assert_parity(y, y_ref, rp, col, val, x, what=f"hll tiles rep={rep}")
                 first = y if first is None else first
                 assert y.tobytes() == first.tobytes()
-            with tuned(stream_kind=0):
+            with sp.tuning(stream_kind=0):
                 assert_parity(dev.spmv(x, sp.HLL_LDS), y_ref, rp, col, val, x, what="hll_lds on the same handle")
             for vname, variant in sorted(sp.HLL_VARIANTS.items()):
                 assert_parity(dev.spmv(x, variant), y_ref, rp, col, val, x, what=f"hll {vname}")
@@ -476,7 +454,7 @@ def test_tile_kernel_inside_a_graph_replay_and_power_iteration(gpu, oracle):
     rp, col, val = scattered(rng, M, N, 10, sigma=3000)
     x = rng.uniform(0.5, 1.0, N)
     y_ref = oracle.csr_serial(rp, col, val, x)
-    with tuned(stream_tile=1, tile_rows=1024):
+    with sp.tuning(stream_tile=1, tile_rows=1024):
         with sp.CsrDevice(M, N, rp, col, val) as dev:
             assert dev.info()["stream_kernel"] == 3
             dev.set_x(x)
@@ -526,7 +504,7 @@ def test_tile_kernel_random_shapes(gpu, oracle):
             rows_per_block = 0
         # (tile_expand 1: plans with gather passes run on an expanded x whatever their size and type -- mixed plans with
         # staged passes, empty blocks and single-entry passes included)
-        with tuned(stream_tile=1, stream_local=0, tile_rows=rows_per_block, tile_pack=int(case % 6 != 5),
+        with sp.tuning(stream_tile=1, stream_local=0, tile_rows=rows_per_block, tile_pack=int(case % 6 != 5),
                    tile_lmax=int(rng.choice([64, 1024])), tile_places=places, tile_streams=int(case % 11 != 10),
                    tile_expand=int(case % 2)):
             with sp.CsrDevice(M, N, rp, col, val) as dev:

@@ -223,12 +223,8 @@ def test_tile_auto_plan_decisions():
     and the number of row blocks is fitted to whole rounds of the workgroup places (here 16 places, so that a small
     matrix shows it): at most k x places blocks with the last round at least 90 % full, every block within the
     tallest the LDS takes, every block in exactly one stream."""
-    from sparsematrixvectormultiplication_amd.device import set_tuning
     rng = np.random.default_rng(5)
-    try:
-        set_tuning("tile_places", 16)
-        # a band, forced (the auto rule wants 2^20 rows)
-        set_tuning("stream_tile", 1)
+    with sp.tuning(tile_places=16, stream_tile=1):   # a band, forced (the auto rule wants 2^20 rows)
         M = N = 300_000
         rp, col = _scattered(rng, M, N, 5, sigma=900)
         st = sp.csr_tile_auto_plan(M, N, rp, col, 8)
@@ -239,14 +235,12 @@ def test_tile_auto_plan_decisions():
         st32 = sp.csr_tile_auto_plan(M, N, rp, col, 4)
         assert st32["packed"] and st32["rows_per_block"] == 12032
         # the same without the fitting: blocks of 4096 fp64 rows
-        set_tuning("tile_fit", 0)
-        plain = sp.csr_tile_auto_plan(M, N, rp, col, 8)
+        with sp.tuning(tile_fit=0):
+            plain = sp.csr_tile_auto_plan(M, N, rp, col, 8)
         assert plain["rows_per_block"] == 4096 and plain["blocks"] >= M // 4096
-        set_tuning("tile_fit", 1)
         # one workgroup per block
-        set_tuning("tile_streams", 0)
-        assert sp.csr_tile_auto_plan(M, N, rp, col, 8)["streams"] >= st["blocks"]
-        set_tuning("tile_streams", 1)
+        with sp.tuning(tile_streams=0):
+            assert sp.csr_tile_auto_plan(M, N, rp, col, 8)["streams"] >= st["blocks"]
         # scattered columns: gather passes, one workgroup per CU geometry, blocks as tall as the LDS takes
         M, N = 200_000, 2_000_000
         rp, col = _scattered(rng, M, N, 6)
@@ -255,29 +249,26 @@ def test_tile_auto_plan_decisions():
         rounds = -(-sc["blocks"] // 16)
         assert sc["blocks"] <= rounds * 16
         # auto: scattered columns get tiles from 800 000 rows and columns on ...
-        set_tuning("stream_tile", -1)
-        assert sp.csr_tile_auto_plan(M, N, rp, col, 8)["tiles"] == 0      # 200 000 rows
-        M = 900_000
-        rp2, col2 = _scattered(rng, M, 900_000, 3)
-        big = sp.csr_tile_auto_plan(M, 900_000, rp2, col2, 8)
-        assert big["tiles"] == 1 and not big["packed"]
-        rp2, col2 = _scattered(rng, M, 600_000, 3)
-        assert sp.csr_tile_auto_plan(M, 600_000, rp2, col2, 8)["tiles"] == 0
-        # ... a band of dense rows already from 4 Mi entries on: packed, one thin block per place
-        M = N = 80_000
-        rp3, col3 = _scattered(rng, M, N, 60, sigma=700)
-        mid = sp.csr_tile_auto_plan(M, N, rp3, col3, 8)
-        assert mid["tiles"] == 1 and mid["packed"] and 14 <= mid["blocks"] <= 16 and mid["tallest_block"] < 0.1 * M, mid
-
-    finally:
-        for k, v in (("tile_places", 0), ("stream_tile", -1), ("tile_fit", 1), ("tile_streams", 1)):
-            set_tuning(k, v)
+        with sp.tuning(stream_tile=-1):
+            assert sp.csr_tile_auto_plan(M, N, rp, col, 8)["tiles"] == 0      # 200 000 rows
+            M = 900_000
+            rp2, col2 = _scattered(rng, M, 900_000, 3)
+            big = sp.csr_tile_auto_plan(M, 900_000, rp2, col2, 8)
+            assert big["tiles"] == 1 and not big["packed"]
+            rp2, col2 = _scattered(rng, M, 600_000, 3)
+            assert sp.csr_tile_auto_plan(M, 600_000, rp2, col2, 8)["tiles"] == 0
+            # ... a band of dense rows already from 4 Mi entries on: packed, one thin block per place
+            M = N = 80_000
+            rp3, col3 = _scattered(rng, M, N, 60, sigma=700)
+            mid = sp.csr_tile_auto_plan(M, N, rp3, col3, 8)
+            assert mid["tiles"] == 1 and mid["packed"] and 14 <= mid["blocks"] <= 16 and mid["tallest_block"] < 0.1 * M, mid
 
 
 def test_stream_kind_and_removed_tuning_keys():
     """"stream_kind" takes -1, 0, 5 and 6 only, and setting it still works after a refusal; the keys of the removed
     stream kernels are unknown keys.  spmv_hip_set_tuning needs no device."""
     from sparsematrixvectormultiplication_amd.device import set_tuning
+    before = sp.get_tuning("stream_kind")
     try:
         for kind in (1, 2, 3, 4, 7, *range(10, 18)):
             with pytest.raises(sp.SpmvHipError, match="stream_kind must be -1"):
@@ -288,4 +279,4 @@ def test_stream_kind_and_removed_tuning_keys():
             with pytest.raises(sp.SpmvHipError, match=f"unknown key '{key}'"):
                 set_tuning(key, value)
     finally:
-        set_tuning("stream_kind", -1)
+        set_tuning("stream_kind", before)

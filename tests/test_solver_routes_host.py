@@ -33,7 +33,7 @@ import scipy.sparse as sps
 import sparsematrixvectormultiplication_amd as sp
 import test_gpu_solver_sizes as sizes
 from test_gpu_minres import minres_ref
-from test_gpu_scaling import scattered, stray, tuned
+from test_gpu_scaling import scattered, stray
 from test_gpu_solver_sizes import differences, reference, rounded_loop
 
 LD = np.longdouble
@@ -368,7 +368,7 @@ def test_tile_plans_decided_on_the_host(route):
     M, N, rp, col = matrix(name)
     lens = np.diff(rp)
     for vb in (8, 4):
-        with tuned(**knobs):
+        with sp.tuning(**knobs):
             st = sp.csr_tile_auto_plan(M, N, rp, col, vb)
         assert st["tiles"] == 1 and st["rows_per_block"] == knobs["tile_rows"], st
         assert st["packed"] == int(route in ("tile-packed", "tile-remainder")), st
