@@ -1,7 +1,8 @@
 // amg_levels.hpp -- the AMG preconditioner object as the device holds it, and what its two setups share: the host setup
 // (spmv_amg.hip: amg_build, from host/amg_plan.c's plan) and the device setup (spmv_amg_setup.hip) both fill the
 // per-level operators, g and the scalars of a spmv_amg_precond and then call amg_finish, which writes the cycle's passes,
-// picks the chained tail and makes the workspace, and amg_wrap.  Host code only.
+// picks the chained tail and makes the workspace, and amg_wrap; both entry points begin with amg_check_args and read the
+// object of a finished P through amg_of.  Host code only.
 #pragma once
 #include "spmv_internal.hpp"
 
@@ -94,5 +95,17 @@ int amg_op_upload(const HostOp &h, int rows, AmgOp &op, const char *what, int le
 // spmv_amg.hip: the levels of ap are filled (levels, kind, n, na, a_nz, the operators, g, A0): the passes of the cycle,
 // the chained tail, the launches and the zeroed workspace for one right-hand side of value_bytes-byte values
 int amg_finish(spmv_amg_precond *ap, int value_bytes);
-// ... and the preconditioner object around it (takes ap)
-spmv_precond *amg_wrap(spmv_amg_precond *ap, int rows, int row0, int value_bytes);
+// ... and the preconditioner object of handle m around it (takes ap)
+spmv_precond *amg_wrap(const spmv_csr_dev *m, spmv_amg_precond *ap, size_t value_bytes);
+// P's hierarchy, or NULL with the refusal "<what>: kind K is not AMG"
+const spmv_amg_precond *amg_of(const spmv_precond *P, const char *what);
+
+// the argument checks of both setups' entry points, in the host setup's words
+inline int amg_check_args(double theta, int coarse_rows, int max_levels) {
+    if (!(theta >= 0.0 && theta < 1.0)) return fail("csr_precond_build_amg: theta = %g, must be in [0, 1)", theta);
+    if (coarse_rows < 1 || coarse_rows > kAmgChainRows)
+        return fail("csr_precond_build_amg: coarse_rows = %d, must be in [1, %d]", coarse_rows, kAmgChainRows);
+    if (max_levels < 1 || max_levels > kAmgMaxLevels)
+        return fail("csr_precond_build_amg: max_levels = %d, must be in [1, %d]", max_levels, kAmgMaxLevels);
+    return 0;
+}

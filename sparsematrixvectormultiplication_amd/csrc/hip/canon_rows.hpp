@@ -72,9 +72,3 @@ inline int plan_of(const spmv_csr_dev *m) {
     if (!m) return 0;
     return m->xw.blocks > 0 ? (m->xw.pat.ptab ? 2 : 1) : m->tile.blocks > 0 ? 3 : 0;
 }
-
-inline int handle_ok(const spmv_csr_dev *m, const char *what) {
-    if (m->M_total != m->N) return fail("%s: needs a square matrix (%d x %d)", what, m->M_total, m->N);
-    if (!csr_holds_arrays(m)) return fail("%s: the handle does not hold its CSR arrays", what);
-    return 0;
-}

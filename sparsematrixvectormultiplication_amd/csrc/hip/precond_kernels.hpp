@@ -1,5 +1,8 @@
 // precond_kernels.hpp -- the kernels of the Jacobi and block-Jacobi preconditioners on CSR handles
-// (spmv_precond.hip builds them; csr_pcg and csr_pbicgstab apply them) (gfx950).
+// (spmv_precond.hip builds them; csr_pcg and csr_pbicgstab apply them) (gfx950), and below them the preconditioner
+// object of every kind: the table a kind family with launches of its own fills in (precond_family), what the solvers
+// ask of it (precond_path, precond_apply, precond_work_bytes, precond_refuse_one_wide) and the frame of every build
+// entry point (precond_build_frame, precond_new).
 //
 // P covers the handle's own rows [row0, row0 + n) in blocks of b consecutive rows from row0 (the last block may be
 // shorter, bk = min(b, n - k b) rows).  Local row i = global row row0 + i sits in block k = i / b at place ii = i % b.
@@ -177,73 +180,97 @@ __global__ __launch_bounds__(kBlock) void pc_apply(long long n, int b, const T *
 }  // namespace spmv
 
 // ---------------------------------------------------------------- the preconditioner object (include/spmv_hip.h)
-struct spmv_precond {
-    int kind = 0, block = 1;  // SPMV_PRECOND_*; rows per block (1 for JACOBI)
-    int rows = 0, row0 = 0;   // the handle's own rows [row0, row0 + rows)
-    int value_bytes = 8;      // the handle's dtype
-    void *inv = nullptr;      // ceil(rows / block) * block^2 values of that dtype (layout above); owned
-    struct spmv_tri_precond *tri = nullptr;  // SSOR / ILU0: the two triangular solves (spmv_trsv.hip); owned, inv is NULL
-    struct spmv_fsai_precond *fsai = nullptr;  // FSAI: the handles of G and G^T (spmv_fsai.hip); owned, inv is NULL
-    struct spmv_amg_precond *amg = nullptr;    // AMG: the hierarchy and its level vectors (spmv_amg.hip); owned, inv is NULL
-    struct spmv_cheb_precond *cheb = nullptr;  // CHEBYSHEV: its upload of the block, g and three vectors (spmv_cheb.hip); owned
+struct spmv_precond;
+
+// What a kind family with launches of its own -- SSOR / ILU(0), FSAI, AMG, CHEBYSHEV -- gives the shared code: one
+// static const instance in the file that owns the family, the only file that knows what P->impl points to.
+struct precond_family {
+    const char *name;       // the end of "<entry point>: kind K is not <name>" (precond_impl)
+    const char *work_text;  // what spmv_hip_precond_apply_multi_on says of a missing d_work
+    // z = M^-1 r by the family's launches on stream s.  flags as pc_apply: SSOR's / ILU(0)'s solves return once a solver
+    // has stopped.  FSAI, AMG and CHEBYSHEV do not look at them: their launches are handles' own, and after a stop r no
+    // longer changes, so z is rewritten with the bits it holds.
+    int (*apply)(const spmv_precond *P, const void *r, void *z, const int *flags, hipStream_t s);
+    // the same for rows x k row-major R and Z through products alone, P's own vectors not used (k = 1: the bits of
+    // apply); work: work_bytes(P, k) bytes.  NULL (both): the family takes one right-hand side
+    int (*apply_multi)(const spmv_precond *P, int k, const void *R, void *Z, void *work, hipStream_t s);
+    long long (*work_bytes)(const spmv_precond *P, int k);
+    // spmv_hip_precond_factors past its argument checks; NULL: the family has no factors
+    int (*factors)(const spmv_precond *P, int which, int *row_ptr, int *col, void *val);
+    void (*free)(void *impl);
 };
 
-// spmv_trsv.hip: z = M^-1 r by P's two solves on stream s (flags as pc_apply: a stopped solver's launches return)
-int precond_tri_apply(const spmv_precond *P, const void *r, void *z, const int *flags, hipStream_t s);
-void precond_tri_free(struct spmv_tri_precond *tp);
-// spmv_fsai.hip: z = G^T (G r) by the two handles' own launches on stream s (they do not look at a solver's flags: after
-// a stop r no longer changes, so z is rewritten with the bits it holds)
-int precond_fsai_apply(const spmv_precond *P, const void *r, void *z, hipStream_t s);
-// the same for rows x k row-major R and Z: two SpMMs; work: rows x k values and one 128-byte line, P's t is not used
-int precond_fsai_apply_multi(const spmv_precond *P, int k, const void *R, void *Z, void *work, hipStream_t s);
-void precond_fsai_free(struct spmv_fsai_precond *fp);
-int precond_fsai_factors(const spmv_precond *P, int which, int *row_ptr, int *col, void *val);
-// spmv_amg.hip: z = one V(1,1) cycle on r by P's own launches on stream s, the level vectors P's own (as FSAI's, they do
-// not look at a solver's flags)
-int precond_amg_apply(const spmv_precond *P, const void *r, void *z, hipStream_t s);
-// the same for rows x k row-major R and Z; work: precond_amg_work_values(P) * k values (the level vectors; the part
-// behind each vector's values zero), P's own vectors are not used
-int precond_amg_apply_multi(const spmv_precond *P, int k, const void *R, void *Z, void *work, hipStream_t s);
-long long precond_amg_work_values(const spmv_precond *P);
-void precond_amg_free(struct spmv_amg_precond *ap);
-// spmv_cheb.hip: z = p(D^-1 A) D^-1 r, degree - 1 products of P's own handle between fused passes on stream s, the
-// iterate in P's own vectors (as FSAI's and AMG's, the launches do not look at a solver's flags)
-int precond_cheb_apply(const spmv_precond *P, const void *r, void *z, hipStream_t s);
-// the same for rows x k row-major R and Z; work: three arrays of precond_cheb_vec_bytes(P, k) bytes, P's own vectors
-// are not used (k = 1: the launches of precond_cheb_apply)
-int precond_cheb_apply_multi(const spmv_precond *P, int k, const void *R, void *Z, void *work, hipStream_t s);
-void precond_cheb_free(struct spmv_cheb_precond *cp);
-// bytes of one of the three arrays: rows x k values rounded up to whole 128-byte lines, and a line tail
-inline long long precond_cheb_vec_bytes(const spmv_precond *P, int k) {
-    const long long bytes = std::max<long long>((long long)P->rows * k * P->value_bytes, 16);
-    return (bytes + kLineBytes - 1) / kLineBytes * kLineBytes + kLineBytes;
+struct spmv_precond {
+    int kind = 0, block = 1;  // SPMV_PRECOND_*; rows per block (1 for all but BLOCK_JACOBI)
+    int rows = 0, row0 = 0;   // the handle's own rows [row0, row0 + rows)
+    int value_bytes = 8;      // the handle's dtype
+    void *inv = nullptr;      // JACOBI / BLOCK_JACOBI: ceil(rows / block) * block^2 values of that dtype (layout above); owned
+    void *impl = nullptr;     // the other kinds: the family's own object; owned, inv is NULL
+    const precond_family *family = nullptr;  // NULL: JACOBI / BLOCK_JACOBI, applied by pc_apply / mpc_apply
+};
+
+// the object every build ends with: the five fields from the handle, and the family's payload
+inline spmv_precond *precond_new(const spmv_csr_dev *m, int kind, int block, size_t value_bytes,
+                                 const precond_family *family = nullptr, void *impl = nullptr) {
+    spmv_precond *P = new spmv_precond;
+    P->kind = kind;
+    P->block = block;
+    P->rows = m->M_local;
+    P->row0 = m->row0;
+    P->value_bytes = (int)value_bytes;
+    P->family = family;
+    P->impl = impl;
+    return P;
 }
 
-// SSOR, ILU(0), FSAI, AMG and CHEBYSHEV take a path of their own wherever Jacobi / block-Jacobi are told apart by P->block: an
-// apply through P's own launches (precond_own_apply), then one pass for whatever dots the solver needs
-inline bool precond_has_own_apply(const spmv_precond *P) {
-    return P && (P->tri != nullptr || P->fsai != nullptr || P->amg != nullptr || P->cheb != nullptr);
+// P's payload for a reader of family f (the *_info entry points); NULL with the refusal when P is of another kind
+inline void *precond_impl(const spmv_precond *P, const precond_family *f, const char *what) {
+    if (P->family == f) return P->impl;
+    fail("%s: kind %d is not %s", what, P->kind, f->name);
+    return nullptr;
 }
-inline int precond_own_apply(const spmv_precond *P, const void *r, void *z, const int *flags, hipStream_t s) {
-    return P->cheb ? precond_cheb_apply(P, r, z, s) : P->amg ? precond_amg_apply(P, r, z, s)
-         : P->fsai ? precond_fsai_apply(P, r, z, s) : precond_tri_apply(P, r, z, flags, s);
+
+// The one question a solver asks.  kPathJacobi: D^-1 fuses into the solver's update kernels; kPathBlock: a pc_apply /
+// mpc_apply pass (which can carry the dots); kPathOwn: the family's launches, then a pass of the solver's for its dots.
+enum PrecondPath { kPathNone = 0, kPathJacobi = 1, kPathBlock = 2, kPathOwn = 3 };
+inline PrecondPath precond_path(const spmv_precond *P) {
+    return !P ? kPathNone : P->family ? kPathOwn : P->block == 1 ? kPathJacobi : kPathBlock;
 }
-// FSAI, AMG and CHEBYSHEV apply to k vectors through products alone; all need a workspace of precond_work_bytes(P, k)
-inline bool precond_has_own_apply_multi(const spmv_precond *P) {
-    return P && (P->fsai != nullptr || P->amg != nullptr || P->cheb != nullptr);
-}
-inline int precond_own_apply_multi(const spmv_precond *P, int k, const void *R, void *Z, void *work, hipStream_t s) {
-    return P->cheb ? precond_cheb_apply_multi(P, k, R, Z, work, s)
-         : P->amg ? precond_amg_apply_multi(P, k, R, Z, work, s) : precond_fsai_apply_multi(P, k, R, Z, work, s);
-}
-// bytes of that workspace for k columns: 0 for Jacobi and block-Jacobi, FSAI's G R with a line tail, the level vectors
-// of AMG, the three arrays of CHEBYSHEV; -1 for SSOR and ILU(0), which have no k-wide apply
+
+// bytes of the workspace of a k-wide apply: 0 without P and for Jacobi and block-Jacobi, else the family's (FSAI's G R
+// with a line tail, the level vectors of AMG, the three arrays of CHEBYSHEV); -1 where there is no k-wide apply
 inline long long precond_work_bytes(const spmv_precond *P, int k) {
-    if (P->tri) return -1;
-    if (P->cheb) return 3 * precond_cheb_vec_bytes(P, k);
-    if (P->amg) return std::max<long long>(precond_amg_work_values(P) * k * P->value_bytes, 16);
-    if (P->fsai) return std::max<long long>((long long)P->rows * k * P->value_bytes, 16) + kLineBytes;
+    if (!P || !P->family) return 0;
+    return P->family->apply_multi ? P->family->work_bytes(P, k) : -1;
+}
+// that workspace from a solver's scope; NULL where the kind needs none
+inline void *precond_work_alloc(SolverScope &scope, const spmv_precond *P, int k) {
+    const long long bytes = precond_work_bytes(P, k);
+    return bytes > 0 ? scope.alloc((size_t)bytes) : nullptr;
+}
+
+// a kind without a k-wide apply (SSOR, ILU(0)): -1 with the one sentence, naming `what`
+inline int precond_refuse_one_wide(const spmv_precond *P, const char *what) {
+    if (P->family && !P->family->apply_multi)
+        return fail("%s: an SSOR or ILU(0) preconditioner is two triangular solves, and those take one right-hand side", what);
     return 0;
+}
+
+// The frame of every spmv_hip_csr_precond_build*: the device, the two NULL refusals, the kind's own argument checks
+// (check() != 0: refused, the message is set), the handle, then build(T(), &P) with T the handle's dtype under guarded().
+// A refused build or a failed allocation is reported by the return value, not by the next launch.
+template <typename Check, typename Build>
+int precond_build_frame(const char *what, const spmv_csr_dev *m, spmv_precond **out, Check check, Build build) {
+    if (need_device()) return -1;
+    if (!out) return fail("%s: out is NULL", what);
+    *out = nullptr;
+    if (!m) return fail("%s: NULL handle", what);
+    if (check() || handle_ok(m, what)) return -1;
+    spmv_precond *P = nullptr;
+    const int rc = solver_dispatch(what, m->value_bytes, [&](auto t) { return build(t, &P); });
+    (void)hipGetLastError();
+    if (!rc) *out = P;
+    return rc;
 }
 
 // z = M^-1 r on P's rows (r, z at local row 0) on stream s; flags / part as pc_apply; grid 0: by the row count
@@ -254,6 +281,14 @@ void precond_launch(const spmv_precond *P, const void *r, void *z, const int *fl
     if (!grid) grid = solver_grid(kPcBlocks, n, kBlock);
     hipLaunchKernelGGL((pc_apply<T, DOTS>), dim3(grid), dim3(kBlock), 0, s, n, P->block, (const T *)P->inv,
                        (const T *)r, (T *)z, flags, part);
+}
+
+// z = M^-1 r outside the fused paths: the family's own launches, or a pc_apply pass on the row count's grid
+template <typename T>
+int precond_apply(const spmv_precond *P, const void *r, void *z, const int *flags, hipStream_t s) {
+    if (P->family) return P->family->apply(P, r, z, flags, s);
+    precond_launch<T, false>(P, r, z, flags, nullptr, 0, s);
+    return 0;
 }
 
 // P fits handle m (its rows, first row and dtype); else -1 with a message naming `what`

@@ -164,7 +164,7 @@ int amg_build(const spmv_csr_dev *m, double theta, int coarse_rows, int max_leve
     ap->us[0] = (int)((t1 - t0) * 1e3);
     ap->us[1] = (int)((t2 - t1) * 1e3);
     ap->us[2] = (int)((now_ms() - t2) * 1e3);
-    *out = amg_wrap(ap.release(), n, m->row0, (int)sizeof(T));
+    *out = amg_wrap(m, ap.release(), sizeof(T));
     return 0;
 }
 
@@ -191,6 +191,30 @@ int amg_run(const spmv_amg_precond *ap, int k, const void *R, void *Z, void *wor
     HIP_TRY(hipGetLastError());
     return 0;
 }
+
+// z = one V(1,1) cycle on r by P's own launches on stream s, the level vectors P's own (as FSAI's, they do not look at a
+// solver's flags)
+int amg_apply(const spmv_precond *P, const void *r, void *z, const int *, hipStream_t s) {
+    const spmv_amg_precond *ap = (const spmv_amg_precond *)P->impl;
+    if (!P->rows) return 0;
+    return P->value_bytes == 8 ? amg_run<double>(ap, 1, r, z, ap->work, s) : amg_run<float>(ap, 1, r, z, ap->work, s);
+}
+
+// Z = M^-1 R for rows x k row-major R and Z; work: work_values * k values (the level vectors; the part behind each
+// vector's values zero), P's own vectors are not used
+int amg_apply_multi(const spmv_precond *P, int k, const void *R, void *Z, void *work, hipStream_t s) {
+    const spmv_amg_precond *ap = (const spmv_amg_precond *)P->impl;
+    if (!P->rows) return 0;
+    return P->value_bytes == 8 ? amg_run<double>(ap, k, R, Z, work, s) : amg_run<float>(ap, k, R, Z, work, s);
+}
+
+long long amg_work_bytes(const spmv_precond *P, int k) {
+    return std::max<long long>(((const spmv_amg_precond *)P->impl)->work_values * k * P->value_bytes, 16);
+}
+
+const precond_family kAmgFamily = {"AMG", "an AMG apply needs d_work (spmv_hip_precond_work_bytes: its level vectors)",
+                                   amg_apply, amg_apply_multi, amg_work_bytes, nullptr,
+                                   [](void *impl) { delete (spmv_amg_precond *)impl; }};
 
 }  // namespace
 
@@ -223,59 +247,26 @@ int amg_finish(spmv_amg_precond *ap, int value_bytes) {
     return 0;
 }
 
-spmv_precond *amg_wrap(spmv_amg_precond *ap, int rows, int row0, int value_bytes) {
-    spmv_precond *P = new spmv_precond;
-    P->kind = SPMV_PRECOND_AMG;
-    P->block = 1;
-    P->rows = rows;
-    P->row0 = row0;
-    P->value_bytes = value_bytes;
-    P->amg = ap;
-    return P;
+spmv_precond *amg_wrap(const spmv_csr_dev *m, spmv_amg_precond *ap, size_t value_bytes) {
+    return precond_new(m, SPMV_PRECOND_AMG, 1, value_bytes, &kAmgFamily, ap);
 }
 
-void precond_amg_free(spmv_amg_precond *ap) { delete ap; }
-
-int precond_amg_apply(const spmv_precond *P, const void *r, void *z, hipStream_t s) {
-    if (!P->rows) return 0;
-    return P->value_bytes == 8 ? amg_run<double>(P->amg, 1, r, z, P->amg->work, s)
-                               : amg_run<float>(P->amg, 1, r, z, P->amg->work, s);
+const spmv_amg_precond *amg_of(const spmv_precond *P, const char *what) {
+    return (const spmv_amg_precond *)precond_impl(P, &kAmgFamily, what);
 }
-
-// Z = M^-1 R for rows x k row-major R and Z; work: precond_amg_work_values(P) * k values, P's own vectors are not used
-int precond_amg_apply_multi(const spmv_precond *P, int k, const void *R, void *Z, void *work, hipStream_t s) {
-    if (!P->rows) return 0;
-    return P->value_bytes == 8 ? amg_run<double>(P->amg, k, R, Z, work, s) : amg_run<float>(P->amg, k, R, Z, work, s);
-}
-
-long long precond_amg_work_values(const spmv_precond *P) { return P->amg->work_values; }
 
 extern "C" int spmv_hip_csr_precond_build_amg(const spmv_csr_dev *m, double theta, int coarse_rows, int max_levels,
                                               int chain, spmv_precond **out) {
-    if (need_device()) return -1;
-    if (!out) return fail("csr_precond_build_amg: out is NULL");
-    *out = nullptr;
-    if (!m) return fail("csr_precond_build_amg: NULL handle");
-    if (!(theta >= 0.0 && theta < 1.0)) return fail("csr_precond_build_amg: theta = %g, must be in [0, 1)", theta);
-    if (coarse_rows < 1 || coarse_rows > kAmgChainRows)
-        return fail("csr_precond_build_amg: coarse_rows = %d, must be in [1, %d]", coarse_rows, kAmgChainRows);
-    if (max_levels < 1 || max_levels > kAmgMaxLevels)
-        return fail("csr_precond_build_amg: max_levels = %d, must be in [1, %d]", max_levels, kAmgMaxLevels);
-    if (handle_ok(m, "csr_precond_build_amg")) return -1;
-    spmv_precond *P = nullptr;
-    const int rc = guarded("csr_precond_build_amg", [&] {
-        return m->value_bytes == 8 ? amg_build<double>(m, theta, coarse_rows, max_levels, chain, &P)
-                                   : amg_build<float>(m, theta, coarse_rows, max_levels, chain, &P);
+    auto check = [&] { return amg_check_args(theta, coarse_rows, max_levels); };
+    return precond_build_frame("csr_precond_build_amg", m, out, check, [&](auto t, spmv_precond **P) {
+        return amg_build<decltype(t)>(m, theta, coarse_rows, max_levels, chain, P);
     });
-    (void)hipGetLastError();
-    if (!rc) *out = P;
-    return rc;
 }
 
 extern "C" int spmv_hip_precond_amg_info(const spmv_precond *P, int *info) {
     if (!P || !info) return fail("precond_amg_info: bad arguments");
-    if (!P->amg) return fail("precond_amg_info: kind %d is not AMG", P->kind);
-    const spmv_amg_precond *ap = P->amg;
+    const spmv_amg_precond *ap = amg_of(P, "precond_amg_info");
+    if (!ap) return -1;
     long long total = 0;
     for (int l = 0; l < ap->levels; ++l) total += ap->a_nz[l];
     std::fill(info, info + SPMV_PRECOND_AMG_INFO_WORDS, 0);
@@ -297,8 +288,8 @@ extern "C" int spmv_hip_precond_amg_level(const spmv_precond *P, int level, int 
                                           double *scalars) {
     if (need_device()) return -1;
     if (!P) return fail("precond_amg_level: bad arguments");
-    if (!P->amg) return fail("precond_amg_level: kind %d is not AMG", P->kind);
-    const spmv_amg_precond *ap = P->amg;
+    const spmv_amg_precond *ap = amg_of(P, "precond_amg_level");
+    if (!ap) return -1;
     if (level < 0 || level >= ap->levels) return fail("precond_amg_level: no level %d (the hierarchy has %d)", level, ap->levels);
     if (scalars) {
         scalars[0] = ap->w[level], scalars[1] = ap->rho[level], scalars[2] = ap->kind[level];

@@ -339,7 +339,7 @@ int amg_build_device(const spmv_csr_dev *m, double theta, int coarse_rows, int m
     ap->us[0] = (int)((t1 - t0) * 1e3);
     ap->us[1] = (int)((t2 - t1) * 1e3);
     ap->us[2] = (int)((now_ms() - t2) * 1e3);
-    *out = amg_wrap(ap.release(), n, m->row0, (int)sizeof(T));
+    *out = amg_wrap(m, ap.release(), sizeof(T));
     return 0;
 }
 
@@ -347,33 +347,24 @@ int amg_build_device(const spmv_csr_dev *m, double theta, int coarse_rows, int m
 
 extern "C" int spmv_hip_csr_precond_build_amg_device(const spmv_csr_dev *m, double theta, int coarse_rows, int max_levels,
                                                      int chain, int block_products, spmv_precond **out) {
-    if (need_device()) return -1;
-    if (!out) return fail("csr_precond_build_amg: out is NULL");
-    *out = nullptr;
-    if (!m) return fail("csr_precond_build_amg: NULL handle");
-    if (!(theta >= 0.0 && theta < 1.0)) return fail("csr_precond_build_amg: theta = %g, must be in [0, 1)", theta);
-    if (coarse_rows < 1 || coarse_rows > kAmgChainRows)
-        return fail("csr_precond_build_amg: coarse_rows = %d, must be in [1, %d]", coarse_rows, kAmgChainRows);
-    if (max_levels < 1 || max_levels > kAmgMaxLevels)
-        return fail("csr_precond_build_amg: max_levels = %d, must be in [1, %d]", max_levels, kAmgMaxLevels);
-    if (!spgemm_block_products_ok(block_products))
-        return fail("csr_precond_build_amg_device: block_products = %d; 0 (auto), -1 (no on-chip tier) or a power of two in "
-                    "[64, %d]", block_products, spgemm_max_block_products());
-    if (handle_ok(m, "csr_precond_build_amg")) return -1;
-    spmv_precond *P = nullptr;
-    const int rc = guarded("csr_precond_build_amg", [&] {
-        return m->value_bytes == 8 ? amg_build_device<double>(m, theta, coarse_rows, max_levels, chain, block_products, &P)
-                                   : amg_build_device<float>(m, theta, coarse_rows, max_levels, chain, block_products, &P);
+    // (the host setup's prefix throughout, so that both setups refuse in the same words; block_products is this one's own)
+    auto check = [&] {
+        if (amg_check_args(theta, coarse_rows, max_levels)) return -1;
+        if (!spgemm_block_products_ok(block_products))
+            return fail("csr_precond_build_amg_device: block_products = %d; 0 (auto), -1 (no on-chip tier) or a power of two "
+                        "in [64, %d]", block_products, spgemm_max_block_products());
+        return 0;
+    };
+    return precond_build_frame("csr_precond_build_amg", m, out, check, [&](auto t, spmv_precond **P) {
+        return amg_build_device<decltype(t)>(m, theta, coarse_rows, max_levels, chain, block_products, P);
     });
-    (void)hipGetLastError();
-    if (!rc) *out = P;
-    return rc;
 }
 
 extern "C" int spmv_hip_precond_amg_setup_info(const spmv_precond *P, int *info) {
     if (!P || !info) return fail("precond_amg_setup_info: bad arguments");
-    if (!P->amg) return fail("precond_amg_setup_info: kind %d is not AMG", P->kind);
-    info[0] = P->amg->setup;
-    for (int p = 0; p < kAmgPhases; ++p) info[1 + p] = P->amg->setup == kAmgSetupDevice ? P->amg->phase_us[p] : 0;
+    const spmv_amg_precond *ap = amg_of(P, "precond_amg_setup_info");
+    if (!ap) return -1;
+    info[0] = ap->setup;
+    for (int p = 0; p < kAmgPhases; ++p) info[1 + p] = ap->setup == kAmgSetupDevice ? ap->phase_us[p] : 0;
     return 0;
 }

@@ -15,9 +15,8 @@
 // spmv_hip_csr_pbicgstab runs the same loop right-preconditioned: p^ = M^-1 p and s^ = M^-1 s are the products' inputs
 // (library-owned, all-gathered in place of p and s), x moves along them, and r stays the true residual.  Jacobi is
 // fused into the s and p updates (bcg_jac_update_s / _p, with D^-1 copied to global row indexing so the 16-byte pieces
-// line up); a block-Jacobi apply is a pc_apply pass after bcg_update_s / bcg_update_p, an SSOR or ILU(0) apply its two
-// triangular solves (spmv_trsv.hip) in the same place, an FSAI apply its two SpMVs (spmv_fsai.hip), an AMG apply its
-// V-cycle (spmv_amg.hip).  P = NULL takes the unpreconditioned path: exactly csr_bicgstab's launches.
+// line up); every other kind is a precond_apply after bcg_update_s / bcg_update_p: a pc_apply pass for block-Jacobi,
+// the kind's own launches for the rest.  P = NULL takes the unpreconditioned path: exactly csr_bicgstab's launches.
 #include "spmv_internal.hpp"
 
 #include "bicgstab_kernels.hpp"
@@ -51,21 +50,13 @@ int bcg_run(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, doub
     hipLaunchKernelGGL((bcg_dot2<T, V>), g, blk, 0, g_stream, lo, hi, fl, (const T *)r, (const T *)rhat, b.part);
     if (reduce(2, kBcgRho)) return -1;
     hipLaunchKernelGGL(bcg_start, dim3(1), dim3(1), 0, g_stream, b.sc, b.flags, b.hist, iters);
-    // with P: the products read p^ and s^; Jacobi fuses into the updates, a block apply follows them
-    const bool tri = precond_has_own_apply(P), jac = P && !tri && P->block == 1, blockwise = P && !tri && P->block > 1;
-    // the apply that follows an update: a pc_apply pass, or SSOR's / ILU(0)'s two solves, or FSAI's two SpMVs
-    auto apply_after = [&](const T *in, T *out) {
-        if (blockwise) precond_launch<T, false>(P, in, out, fl, nullptr, 0, g_stream);
-        return tri ? precond_own_apply(P, in, out, fl, g_stream) : 0;
-    };
+    // with P: the products read p^ and s^; Jacobi fuses into the updates, every other kind's apply follows them
+    const bool jac = precond_path(P) == kPathJacobi;
+    auto apply_after = [&](const T *in, T *out) { return P ? precond_apply<T>(P, in, out, fl, g_stream) : 0; };
     T *ph = P ? (T *)b.ph : p, *sh = P ? (T *)b.sh : s;
     const T *dinv = (const T *)b.dinv;
     const long long own = lo;  // P's local row 0 in the global vectors
-    if (tri) {
-        if (precond_own_apply(P, p + own, ph + own, fl, g_stream)) return -1;  // p^ = M^-1 b
-    } else if (P) {
-        precond_launch<T, false>(P, p + own, ph + own, fl, nullptr, 0, g_stream);
-    }
+    if (apply_after(p + own, ph + own)) return -1;  // p^ = M^-1 b (Jacobi too: the updates fuse it from step 1 on)
     if (g_comm && spmv_hip_comm_allgatherv(ph, bounds, m->value_bytes, g_stream)) return -1;
     *steps_run = iters;
     for (int k = 1; k <= iters; ++k) {
@@ -141,7 +132,7 @@ int bcg_body(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, dou
     if (P) {
         b.ph = scope.alloc(in_bytes);
         b.sh = scope.alloc(in_bytes);
-        if (!precond_has_own_apply(P) && P->block == 1) b.dinv = scope.alloc(vec_bytes);
+        if (precond_path(P) == kPathJacobi) b.dinv = scope.alloc(vec_bytes);
     }
     // r = r^ = p = b on this rank's rows (the rest of p arrives by the all-gatherv)
     const size_t own_off = (size_t)m->row0 * vb, own_bytes = n_own * vb;

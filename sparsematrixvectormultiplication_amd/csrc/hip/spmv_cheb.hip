@@ -45,6 +45,7 @@ struct spmv_cheb_precond {
 namespace {
 
 constexpr const char *kWhat = "csr_precond_build_chebyshev";
+extern const precond_family kChebFamily;  // behind the functions it names
 static_assert(kChebMaxDegree == SPMV_CHEBYSHEV_MAX_DEGREE, "the header's limit is the coefficient arrays' size");
 
 // col / val of the block on their way into P's handle: freed unless the handle took them
@@ -117,14 +118,7 @@ int cheb_build(const spmv_csr_dev *m, int degree, double lmin, double lmax, doub
     }
     cp->download_us = (int)((t1 - t0) * 1e3);
     cp->upload_us = (int)((now_ms() - t1) * 1e3);
-    spmv_precond *P = new spmv_precond;
-    P->kind = SPMV_PRECOND_CHEBYSHEV;
-    P->block = 1;
-    P->rows = n;
-    P->row0 = m->row0;
-    P->value_bytes = (int)sizeof(T);
-    P->cheb = cp.release();
-    *out = P;
+    *out = precond_new(m, SPMV_PRECOND_CHEBYSHEV, 1, sizeof(T), &kChebFamily, cp.release());
     return 0;
 }
 
@@ -175,12 +169,10 @@ int cheb_run(const spmv_cheb_precond *cp, long long n, int k, const T *R, T *Zou
     return 0;
 }
 
-}  // namespace
-
-void precond_cheb_free(spmv_cheb_precond *cp) { delete cp; }
-
-int precond_cheb_apply(const spmv_precond *P, const void *r, void *z, hipStream_t s) {
-    const spmv_cheb_precond *cp = P->cheb;
+// z = p(D^-1 A) D^-1 r, degree - 1 products of P's own handle between fused passes on stream s, the iterate in P's own
+// vectors (as FSAI's and AMG's, the launches do not look at a solver's flags)
+int cheb_apply(const spmv_precond *P, const void *r, void *z, const int *, hipStream_t s) {
+    const spmv_cheb_precond *cp = (const spmv_cheb_precond *)P->impl;
     if (!P->rows) return 0;
     if (P->value_bytes == 8)
         return cheb_run<double>(cp, P->rows, 1, (const double *)r, (double *)z, (double *)cp->z, (double *)cp->d,
@@ -188,12 +180,18 @@ int precond_cheb_apply(const spmv_precond *P, const void *r, void *z, hipStream_
     return cheb_run<float>(cp, P->rows, 1, (const float *)r, (float *)z, (float *)cp->z, (float *)cp->d, (float *)cp->q, s);
 }
 
-// Z = M^-1 R for rows x k row-major R and Z.  work: three arrays of precond_cheb_vec_bytes(P, k) bytes -- Z's iterate,
-// D and Q = A Z --, P's own vectors are not used
-int precond_cheb_apply_multi(const spmv_precond *P, int k, const void *R, void *Z, void *work, hipStream_t s) {
-    const spmv_cheb_precond *cp = P->cheb;
+// bytes of one of the three arrays of a k-wide apply: rows x k values rounded up to whole 128-byte lines, and a line tail
+long long cheb_vec_bytes(const spmv_precond *P, int k) {
+    const long long bytes = std::max<long long>((long long)P->rows * k * P->value_bytes, 16);
+    return (bytes + kLineBytes - 1) / kLineBytes * kLineBytes + kLineBytes;
+}
+
+// Z = M^-1 R for rows x k row-major R and Z.  work: three arrays of cheb_vec_bytes(P, k) bytes -- Z's iterate, D and
+// Q = A Z --, P's own vectors are not used (k = 1: the launches of cheb_apply)
+int cheb_apply_multi(const spmv_precond *P, int k, const void *R, void *Z, void *work, hipStream_t s) {
+    const spmv_cheb_precond *cp = (const spmv_cheb_precond *)P->impl;
     if (!P->rows) return 0;
-    const long long stride = precond_cheb_vec_bytes(P, k);
+    const long long stride = cheb_vec_bytes(P, k);
     char *w = (char *)work;
     if (P->value_bytes == 8)
         return cheb_run<double>(cp, P->rows, k, (const double *)R, (double *)Z, (double *)w, (double *)(w + stride),
@@ -202,34 +200,34 @@ int precond_cheb_apply_multi(const spmv_precond *P, int k, const void *R, void *
                            (float *)(w + 2 * stride), s);
 }
 
+const precond_family kChebFamily = {
+    "CHEBYSHEV", "a CHEBYSHEV apply needs d_work (spmv_hip_precond_work_bytes: its three arrays)", cheb_apply, cheb_apply_multi,
+    [](const spmv_precond *P, int k) { return 3 * cheb_vec_bytes(P, k); }, nullptr,
+    [](void *impl) { delete (spmv_cheb_precond *)impl; }};
+
+}  // namespace
+
 extern "C" int spmv_hip_csr_precond_build_chebyshev(const spmv_csr_dev *m, int degree, double lmin, double lmax,
                                                     double ratio, spmv_precond **out) {
-    if (need_device()) return -1;
-    if (!out) return fail("%s: out is NULL", kWhat);
-    *out = nullptr;
-    if (!m) return fail("%s: NULL handle", kWhat);
-    if (degree < 1 || degree > kChebMaxDegree)
-        return fail("%s: degree = %d, must be in [1, %d]", kWhat, degree, kChebMaxDegree);
-    if (!std::isfinite(ratio) || !(ratio > 1.0)) return fail("%s: ratio = %g, must be finite and > 1", kWhat, ratio);
-    if (!std::isfinite(lmax) || lmax < 0.0)
-        return fail("%s: lmax = %g, must be finite and >= 0 (0: the Gershgorin bound)", kWhat, lmax);
-    if (!std::isfinite(lmin) || lmin < 0.0)
-        return fail("%s: lmin = %g, must be finite and >= 0 (0: lmax / ratio)", kWhat, lmin);
-    if (handle_ok(m, kWhat)) return -1;
-    spmv_precond *P = nullptr;
-    const int rc = guarded(kWhat, [&] {
-        return m->value_bytes == 8 ? cheb_build<double>(m, degree, lmin, lmax, ratio, &P)
-                                   : cheb_build<float>(m, degree, lmin, lmax, ratio, &P);
+    auto check = [&] {
+        if (degree < 1 || degree > kChebMaxDegree)
+            return fail("%s: degree = %d, must be in [1, %d]", kWhat, degree, kChebMaxDegree);
+        if (!std::isfinite(ratio) || !(ratio > 1.0)) return fail("%s: ratio = %g, must be finite and > 1", kWhat, ratio);
+        if (!std::isfinite(lmax) || lmax < 0.0)
+            return fail("%s: lmax = %g, must be finite and >= 0 (0: the Gershgorin bound)", kWhat, lmax);
+        if (!std::isfinite(lmin) || lmin < 0.0)
+            return fail("%s: lmin = %g, must be finite and >= 0 (0: lmax / ratio)", kWhat, lmin);
+        return 0;
+    };
+    return precond_build_frame(kWhat, m, out, check, [&](auto t, spmv_precond **P) {
+        return cheb_build<decltype(t)>(m, degree, lmin, lmax, ratio, P);
     });
-    (void)hipGetLastError();
-    if (!rc) *out = P;
-    return rc;
 }
 
 extern "C" int spmv_hip_precond_cheb_info(const spmv_precond *P, double *info) {
     if (!P || !info) return fail("precond_cheb_info: bad arguments");
-    if (!P->cheb) return fail("precond_cheb_info: kind %d is not CHEBYSHEV", P->kind);
-    const spmv_cheb_precond *cp = P->cheb;
+    const spmv_cheb_precond *cp = (const spmv_cheb_precond *)precond_impl(P, &kChebFamily, "precond_cheb_info");
+    if (!cp) return -1;
     const double v[SPMV_PRECOND_CHEB_INFO_WORDS] = {(double)cp->degree, cp->lmin, cp->lmax, cp->gershgorin,
                                                     (double)(cp->degree - 1), (double)plan_of(cp->A),
                                                     (double)cp->download_us, (double)cp->upload_us};

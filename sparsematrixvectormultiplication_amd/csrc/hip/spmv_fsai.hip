@@ -36,6 +36,8 @@ struct spmv_fsai_precond {
 
 namespace {
 
+extern const precond_family kFsaiFamily;  // behind the functions it names
+
 template <typename T, int W>
 void fsai_launch(int count, const int *rows, const int *a_rp, const int *a_col, const double *a_val, const int *g_rp,
                  const int *g_col, T *g_val, int *status) {
@@ -152,40 +154,32 @@ int fsai_build(const spmv_csr_dev *m, int cap, spmv_precond **out) {
     fp->entries = counts[0];
     fp->truncated = (int)counts[1];
     fp->widest = (int)counts[2];
-    spmv_precond *P = new spmv_precond;
-    P->kind = SPMV_PRECOND_FSAI;
-    P->block = 1;
-    P->rows = n;
-    P->row0 = m->row0;
-    P->value_bytes = (int)sizeof(T);
-    P->fsai = fp.release();
-    *out = P;
+    *out = precond_new(m, SPMV_PRECOND_FSAI, 1, sizeof(T), &kFsaiFamily, fp.release());
     return 0;
 }
 
-}  // namespace
-
-void precond_fsai_free(spmv_fsai_precond *fp) { delete fp; }
-
-int precond_fsai_apply(const spmv_precond *P, const void *r, void *z, hipStream_t s) {
-    const spmv_fsai_precond *fp = P->fsai;
+// z = G^T (G r) by the two handles' own launches on stream s (they do not look at a solver's flags: after a stop r no
+// longer changes, so z is rewritten with the bits it holds)
+int fsai_apply(const spmv_precond *P, const void *r, void *z, const int *, hipStream_t s) {
+    const spmv_fsai_precond *fp = (const spmv_fsai_precond *)P->impl;
     if (!P->rows) return 0;
     if (csr_launch_any(fp->G, SPMV_CSR_AUTO, r, fp->t, s)) return -1;
     return csr_launch_any(fp->Gt, SPMV_CSR_AUTO, fp->t, z, s);
 }
 
 // Z = G^T (G R) for rows x k row-major R: two SpMMs through the same two handles (k = 1: their AUTO launches, the bits
-// of precond_fsai_apply).  work (rows x k values and a line tail) stands in for P's own t, which is not touched.
-int precond_fsai_apply_multi(const spmv_precond *P, int k, const void *R, void *Z, void *work, hipStream_t s) {
-    const spmv_fsai_precond *fp = P->fsai;
+// of fsai_apply).  work (rows x k values and a line tail) stands in for P's own t, which is not touched.
+int fsai_apply_multi(const spmv_precond *P, int k, const void *R, void *Z, void *work, hipStream_t s) {
+    const spmv_fsai_precond *fp = (const spmv_fsai_precond *)P->impl;
     if (!P->rows) return 0;
     if (spmv_hip_csr_spmm_on(fp->G, k, R, work, s)) return -1;
     return spmv_hip_csr_spmm_on(fp->Gt, k, work, Z, s);
 }
 
 // G (which = SPMV_FACTOR_L) or G^T as their handles hold them: columns ascending, values of the handle's dtype
-int precond_fsai_factors(const spmv_precond *P, int which, int *row_ptr, int *col, void *val) {
-    const spmv_csr_dev *h = which == SPMV_FACTOR_L ? P->fsai->G : P->fsai->Gt;
+int fsai_factors(const spmv_precond *P, int which, int *row_ptr, int *col, void *val) {
+    const spmv_fsai_precond *fp = (const spmv_fsai_precond *)P->impl;
+    const spmv_csr_dev *h = which == SPMV_FACTOR_L ? fp->G : fp->Gt;
     const size_t n = (size_t)P->rows, nz = h ? (size_t)h->nz : 0;
     row_ptr[0] = 0;
     if (!h) return 0;
@@ -195,26 +189,29 @@ int precond_fsai_factors(const spmv_precond *P, int which, int *row_ptr, int *co
     return 0;
 }
 
+long long fsai_work_bytes(const spmv_precond *P, int k) {
+    return std::max<long long>((long long)P->rows * k * P->value_bytes, 16) + kLineBytes;
+}
+
+const precond_family kFsaiFamily = {"FSAI", "an FSAI apply needs d_work (rows x k values and one 128-byte line)",
+                                    fsai_apply, fsai_apply_multi, fsai_work_bytes, fsai_factors,
+                                    [](void *impl) { delete (spmv_fsai_precond *)impl; }};
+
+}  // namespace
+
 extern "C" int spmv_hip_csr_precond_build_fsai(const spmv_csr_dev *m, int cap, spmv_precond **out) {
-    if (need_device()) return -1;
-    if (!out) return fail("csr_precond_build_fsai: out is NULL");
-    *out = nullptr;
-    if (!m) return fail("csr_precond_build_fsai: NULL handle");
-    if (cap < 1 || cap > kFsaiMaxCap) return fail("csr_precond_build_fsai: cap = %d, must be in [1, %d]", cap, kFsaiMaxCap);
-    if (handle_ok(m, "csr_precond_build_fsai")) return -1;
-    spmv_precond *P = nullptr;
-    const int rc = guarded("csr_precond_build_fsai", [&] {
-        return m->value_bytes == 8 ? fsai_build<double>(m, cap, &P) : fsai_build<float>(m, cap, &P);
+    auto check = [&] {
+        return cap < 1 || cap > kFsaiMaxCap ? fail("csr_precond_build_fsai: cap = %d, must be in [1, %d]", cap, kFsaiMaxCap) : 0;
+    };
+    return precond_build_frame("csr_precond_build_fsai", m, out, check, [&](auto t, spmv_precond **P) {
+        return fsai_build<decltype(t)>(m, cap, P);
     });
-    (void)hipGetLastError();
-    if (!rc) *out = P;
-    return rc;
 }
 
 extern "C" int spmv_hip_precond_fsai_info(const spmv_precond *P, int *info) {
     if (!P || !info) return fail("precond_fsai_info: bad arguments");
-    if (!P->fsai) return fail("precond_fsai_info: kind %d is not FSAI", P->kind);
-    const spmv_fsai_precond *fp = P->fsai;
+    const spmv_fsai_precond *fp = (const spmv_fsai_precond *)precond_impl(P, &kFsaiFamily, "precond_fsai_info");
+    if (!fp) return -1;
     const int v[SPMV_PRECOND_FSAI_INFO_WORDS] = {fp->cap, (int)fp->entries, fp->truncated, fp->widest, plan_of(fp->G),
                                                  plan_of(fp->Gt), fp->analysis_us, fp->build_us, fp->upload_us};
     std::copy(v, v + SPMV_PRECOND_FSAI_INFO_WORDS, info);

@@ -451,6 +451,12 @@ inline CsrView csr_view(const spmv_csr_dev *m) { return {m->M_total, m->N, m->nz
 inline bool csr_holds_arrays(const spmv_csr_dev *m) {
     return !m->tiles_only && m->row_ptr && (m->nz == 0 || (m->col && m->val));
 }
+// what the triangular and the preconditioner builds ask of a handle; else -1 with a message naming `what`
+inline int handle_ok(const spmv_csr_dev *m, const char *what) {
+    if (m->M_total != m->N) return fail("%s: needs a square matrix (%d x %d)", what, m->M_total, m->N);
+    if (!csr_holds_arrays(m)) return fail("%s: the handle does not hold its CSR arrays", what);
+    return 0;
+}
 struct DevCsr {
     int rows = 0, cols = 0;
     long long nz = 0;

@@ -107,7 +107,7 @@ int lob_hook_check(long long n, int k, int nb, const void *const *S, const void 
 struct LobBuffers {
     double *X, *W, *P, *AX, *AW, *AP;
     double *R;     // with a preconditioner: the residual, W is M^-1 R
-    void *work;    // FSAI's G R, AMG's level vectors
+    void *work;    // the workspace of the k-wide apply (precond_work_bytes)
     double *theta, *coef, *res_part, *res_sum, *gram_part, *gram_out, *an_part, *an_out;
 };
 
@@ -235,7 +235,7 @@ int lob_body(spmv_csr_dev *m, const spmv_precond *pc, int k, int iters, double t
     b.AW = scope.alloc<double>(vec_bytes);
     b.AP = scope.alloc<double>(vec_bytes);
     b.R = pc ? scope.alloc<double>(vec_bytes) : nullptr;
-    b.work = precond_has_own_apply_multi(pc) ? scope.alloc((size_t)precond_work_bytes(pc, k)) : nullptr;
+    b.work = precond_work_alloc(scope, pc, k);
     b.theta = scope.alloc<double>(kLobMaxK * sizeof(double));
     b.coef = scope.alloc<double>((size_t)2 * 48 * kLobMaxK * sizeof(double));
     b.res_part = scope.alloc<double>((size_t)kMcgBlocks * kLobMaxK * sizeof(double));
@@ -292,8 +292,7 @@ extern "C" int spmv_hip_csr_lobpcg(spmv_csr_dev *m, const spmv_precond *P, int k
     else if (solver_check_steps(what, iters, tol)) rc = -1;
     else if ((long long)m->M_total * k > 0x7fffffffLL)
         rc = fail("%s: n * k = %lld values is beyond int range", what, (long long)m->M_total * k);
-    else if (P && P->tri)
-        rc = fail("%s: an SSOR or ILU(0) preconditioner is two triangular solves, and those take one right-hand side", what);
+    else if (P && precond_refuse_one_wide(P, what)) rc = -1;
     else if (P && largest) rc = fail("%s: a preconditioner serves the smallest eigenvalues only", what);
     else if (P) rc = precond_matches(m, P, what);
     if (rc) return rc;

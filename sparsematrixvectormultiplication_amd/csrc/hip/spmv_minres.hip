@@ -13,8 +13,8 @@
 // all-gathered with the row bounds after mr_update (one exchange per step) and every reduction is all-gathered and
 // added in rank order, as csr_bicgstab does: every rank holds the same bits and stops at the same step.
 //
-// With a preconditioner y = M^-1 r2 is an apply of its own after mr_lanczos_b -- a pc_apply pass for Jacobi and
-// block-Jacobi, the two triangular solves of SSOR and ILU(0), FSAI's two SpMVs -- followed by mr_dot for r2.y.
+// With a preconditioner y = M^-1 r2 is an apply of its own after mr_lanczos_b (precond_apply: a pc_apply pass for Jacobi
+// and block-Jacobi, the kind's own launches for the rest) followed by mr_dot for r2.y.
 // Without one y is r2 itself and mr_lanczos_b's t.t is bb: no apply, no extra dot.
 #include "spmv_internal.hpp"
 
@@ -49,13 +49,8 @@ int mr_run(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, doubl
         return solver_reduce(b.part, grid, 1, b.sc + slot, b.sc + kMrLocal, b.gath, "csr_minres");
     };
     // y = M^-1 r on this rank's rows and bb = r.y in slot kMrBb
-    const bool tri = precond_has_own_apply(P);
     auto apply_and_dot = [&](const T *r) {
-        if (tri) {
-            if (precond_own_apply(P, r + own, yb + own, fl, g_stream)) return -1;
-        } else {
-            precond_launch<T, false>(P, r + own, yb + own, fl, nullptr, 0, g_stream);
-        }
+        if (precond_apply<T>(P, r + own, yb + own, fl, g_stream)) return -1;
         hipLaunchKernelGGL((mr_dot<T, V>), g, blk, 0, g_stream, lo, hi, fl, r, (const T *)yb, b.part);
         return reduce(kMrBb);
     };

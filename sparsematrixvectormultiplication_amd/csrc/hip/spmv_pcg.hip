@@ -8,16 +8,16 @@
 // The layout and the walk are csr_cg's: p is the handle's x (all-gathered with the bounds when a communicator exists),
 // q its y, x / r / z hold this rank's rows at local index, the lanes walk single rows (PieceLane with V = 1) on
 // csr_cg's grid, and the dots fold as csr_cg's do.  That is what makes P = NULL (z is r) and Jacobi with a unit
-// diagonal give csr_cg's bits.  The modes of the x / r update:
+// diagonal give csr_cg's bits.  The paths of the x / r update (precond_path):
 //
 //   NONE    x += alpha p, r -= alpha q, partials of r.r twice (z is r)                    6 values moved per row
 //   JACOBI  the same and z = D^-1 r (one more read, one more write), partials of r.r, r.z  8
 //   BLOCK   x += alpha p, r -= alpha q (6), then pc_apply: z = M^-1 r with r.r and r.z    b + 2 more (L2 serves r's
 //           repeats inside a block)
-//   TRI     x += alpha p, r -= alpha q (6), then SSOR's / ILU(0)'s two solves (spmv_trsv.hip), then pcg_dots: r.r and
-//           r.z by the walk and the fold of the other modes (2 more reads); the solves' last kernel is a level of a few
-//           rows, so the dots are a pass of their own rather than fused into it; FSAI's two SpMVs (spmv_fsai.hip) take
-//           the same path: its launches are the handles' own, which make no dots; so does AMG's V-cycle (spmv_amg.hip)
+//   OWN     x += alpha p, r -= alpha q (6), then the kind's own launches -- SSOR's / ILU(0)'s two solves (spmv_trsv.hip),
+//           FSAI's two SpMVs (spmv_fsai.hip), AMG's V-cycle (spmv_amg.hip), CHEBYSHEV's passes (spmv_cheb.hip) --, then
+//           pcg_dots: r.r and r.z by the walk and the fold of the other paths (2 more reads); the solves' last kernel is
+//           a level of a few rows and the other kinds' launches are handles' own, so the dots are a pass of their own
 //
 // pcg_dot (p.q, 2 values) and pcg_update_p (p = z + beta p, 3) complete the step: fp64 Jacobi PCG moves 13 values =
 // 104 B per row against csr_cg's 11 (88 B).  The scalars and the stop state never leave the device; after a stop the
@@ -32,7 +32,6 @@ namespace {
 constexpr int kPcgRr = 0, kPcgRz = 1, kPcgPq = 2, kPcgRrNew = 3, kPcgRzNew = 4, kPcgAlpha = 5, kPcgBeta = 6,
               kPcgRr0 = 7, kPcgLastRr = 8, kPcgLastRz = 9, kPcgLocal = 10, kPcgSlots = 16;
 // the int words: the stop flags of solver_ops.hpp
-constexpr int kModeNone = 0, kModeJacobi = 1, kModeBlock = 2, kModeTri = 3;
 
 // partials of a.b on [0, n): dot_partial of spmv_cg.hip with the stop check
 template <typename T>
@@ -94,17 +93,17 @@ __global__ __launch_bounds__(kBlock) void pcg_update_x_r(long long n, const int 
         x[k] = (T)((double)x[k] + alpha * (double)p[k]);
         const T rk = (T)((double)r[k] - alpha * (double)q[k]);
         r[k] = rk;
-        if constexpr (MODE == kModeNone) {
+        if constexpr (MODE == kPathNone) {
             acc[0] += (double)rk * (double)rk;
             acc[1] = acc[0];
-        } else if constexpr (MODE == kModeJacobi) {
+        } else if constexpr (MODE == kPathJacobi) {
             const T zk = (T)((double)dinv[k] * (double)rk);
             z[k] = zk;
             acc[0] += (double)rk * (double)rk;
             acc[1] += (double)rk * (double)zk;
         }
     }
-    if constexpr (MODE != kModeBlock) block_partials<2>(acc, part);
+    if constexpr (MODE != kPathBlock) block_partials<2>(acc, part);
 }
 
 // p = z + beta p on this rank's rows
@@ -193,7 +192,7 @@ int pcg_run(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, doub
             const PcgBuffers &b, int *steps_run) {
     const long long n = m->M_local;
     const int grid = solver_grid(kNormBlocks, n, kBlock);
-    const int mode = !P ? kModeNone : precond_has_own_apply(P) ? kModeTri : P->block == 1 ? kModeJacobi : kModeBlock;
+    const PrecondPath mode = precond_path(P);
     const double tol2 = tol * tol;
     T *p_own = (T *)m->x + m->row0, *q_own = (T *)m->y + m->row0, *x_own = (T *)b.x + m->row0;
     T *r = (T *)b.r, *z = (T *)b.z;
@@ -204,14 +203,14 @@ int pcg_run(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, doub
         return solver_reduce(b.part, grid, nv, b.sc + slot, b.sc + kPcgLocal, b.gath, "csr_pcg");
     };
     // z = M^-1 r, rr0 = r.r, rz = r.z with r = b; p = z (the own range of the handle's x; the rest by the exchange)
-    if (mode == kModeNone)
+    if (mode == kPathNone)
         hipLaunchKernelGGL((pcg_start_dots<T, false>), g, blk, 0, g_stream, n, dinv, (const T *)r, z, b.part);
-    else if (mode == kModeJacobi)
+    else if (mode == kPathJacobi)
         hipLaunchKernelGGL((pcg_start_dots<T, true>), g, blk, 0, g_stream, n, dinv, (const T *)r, z, b.part);
-    else if (mode == kModeBlock)
+    else if (mode == kPathBlock)
         precond_launch<T, true>(P, r, z, nullptr, b.part, grid, g_stream);
     else {
-        if (precond_own_apply(P, r, z, nullptr, g_stream)) return -1;
+        if (P->family->apply(P, r, z, nullptr, g_stream)) return -1;
         hipLaunchKernelGGL((pcg_dots<T>), g, blk, 0, g_stream, n, (const int *)nullptr, (const T *)r, (const T *)z, b.part);
     }
     if (reduce(2, kPcgRr)) return -1;
@@ -224,19 +223,19 @@ int pcg_run(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, doub
         hipLaunchKernelGGL((pcg_dot<T>), g, blk, 0, g_stream, n, fl, (const T *)p_own, (const T *)q_own, b.part);
         if (reduce(1, kPcgPq)) return -1;
         hipLaunchKernelGGL(pcg_set_alpha, dim3(1), dim3(1), 0, g_stream, b.sc, b.flags, t);
-        if (mode == kModeNone) {
-            hipLaunchKernelGGL((pcg_update_x_r<T, kModeNone>), g, blk, 0, g_stream, n, fl, (const double *)b.sc,
+        if (mode == kPathNone) {
+            hipLaunchKernelGGL((pcg_update_x_r<T, kPathNone>), g, blk, 0, g_stream, n, fl, (const double *)b.sc,
                                (const T *)p_own, (const T *)q_own, dinv, x_own, r, z, b.part);
-        } else if (mode == kModeJacobi) {
-            hipLaunchKernelGGL((pcg_update_x_r<T, kModeJacobi>), g, blk, 0, g_stream, n, fl, (const double *)b.sc,
+        } else if (mode == kPathJacobi) {
+            hipLaunchKernelGGL((pcg_update_x_r<T, kPathJacobi>), g, blk, 0, g_stream, n, fl, (const double *)b.sc,
                                (const T *)p_own, (const T *)q_own, dinv, x_own, r, z, b.part);
         } else {
-            hipLaunchKernelGGL((pcg_update_x_r<T, kModeBlock>), g, blk, 0, g_stream, n, fl, (const double *)b.sc,
+            hipLaunchKernelGGL((pcg_update_x_r<T, kPathBlock>), g, blk, 0, g_stream, n, fl, (const double *)b.sc,
                                (const T *)p_own, (const T *)q_own, dinv, x_own, r, z, b.part);
-            if (mode == kModeBlock) {
+            if (mode == kPathBlock) {
                 precond_launch<T, true>(P, r, z, fl, b.part, grid, g_stream);
             } else {
-                if (precond_own_apply(P, r, z, fl, g_stream)) return -1;
+                if (P->family->apply(P, r, z, fl, g_stream)) return -1;
                 hipLaunchKernelGGL((pcg_dots<T>), g, blk, 0, g_stream, n, fl, (const T *)r, (const T *)z, b.part);
             }
         }

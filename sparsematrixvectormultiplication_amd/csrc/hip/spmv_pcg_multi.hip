@@ -7,34 +7,22 @@
 //                p_j = z_j + beta_j p_j
 //
 // The loop of csr_pcg with the layout of csr_cg_multi: P (N x k, the SpMM's input, all-gathered with the bounds scaled
-// by k when a communicator exists), Q, X (M_total x k), R and Z (this rank's rows) are row-major.  The modes of the
-// x / r update:
+// by k when a communicator exists), Q, X (M_total x k), R and Z (this rank's rows) are row-major.  The paths of the
+// x / r update (precond_path):
 //
 //   NONE    x += alpha p, r -= alpha q and the partials of r.r (z is r): cg_multi's step, cg_multi's bits
 //   JACOBI  the same with z = D^-1 r fused in, partials of r.r and r.z
 //   BLOCK   x += alpha p, r -= alpha q, then mpc_apply: Z = M^-1 R with the partials of r.r and r.z
-//   FSAI    x += alpha p, r -= alpha q, then Z = G^T (G R), two SpMMs through P's handles, then mpcg_dots
-//   AMG     the same with Z = one V(1,1) cycle on R (spmv_amg.hip), then mpcg_dots
+//   OWN     x += alpha p, r -= alpha q, then the kind's k-wide apply through products alone (FSAI: Z = G^T (G R), two
+//           SpMMs through P's handles; AMG: one V(1,1) cycle on R; CHEBYSHEV: its passes), then mpcg_dots
 //
-// SSOR and ILU(0) are refused: their triangular solves take one right-hand side.  Every column carries its own scalars,
+// A kind without a k-wide apply is refused (precond_refuse_one_wide).  Every column carries its own scalars,
 // stop state, steps and status on the device; a stopped column still rides in the SpMMs and keeps x, r, z and p.
 #include "spmv_internal.hpp"
 
 #include "pcg_multi_kernels.hpp"
 
 namespace {
-
-// the mode of mpcg_update_x_r: block-Jacobi and FSAI apply after it
-int mpcg_mode(const spmv_precond *P) {
-    return !P ? kMpcgNone : !precond_has_own_apply(P) && P->block == 1 ? kMpcgJacobi : kMpcgApply;
-}
-
-// SSOR / ILU(0): -1 with a message naming `what`
-int mpcg_refuse_tri(const spmv_precond *P, const char *what) {
-    if (P->tri)
-        return fail("%s: an SSOR or ILU(0) preconditioner is two triangular solves, and those take one right-hand side", what);
-    return 0;
-}
 
 // Z = M^-1 R for Jacobi / block-Jacobi on stream s, V values per lane; DOTS, flags and the partials as mpc_apply
 template <typename T, int V, bool DOTS>
@@ -45,11 +33,12 @@ void mpc_launch(const spmv_precond *P, int k, const void *R, void *Z, const int 
                        (const T *)P->inv, (const T *)R, (T *)Z, flags, part_rr, part_rz);
 }
 
-// the apply outside a solve: any kind but SSOR / ILU(0); 16-byte pieces when the rows and both arrays allow them
+// the k-wide apply outside a solve (csr_lobpcg's too, through spmv_hip_precond_apply_multi_on): any kind with one; a
+// family's own launches, or mpc_apply in 16-byte pieces when the rows and both arrays allow them
 template <typename T>
 int mpc_apply_on(const spmv_precond *P, int k, const void *R, void *Z, void *work, hipStream_t s) {
     if (!P->rows) return 0;
-    if (precond_has_own_apply_multi(P)) return precond_own_apply_multi(P, k, R, Z, work, s);
+    if (P->family) return P->family->apply_multi(P, k, R, Z, work, s);
     constexpr int W = 16 / sizeof(T);
     const bool wide = (size_t)k * sizeof(T) % 16 == 0 && (((uintptr_t)R | (uintptr_t)Z) & 15) == 0;
     const int grid = solver_grid(kMcgBlocks, P->rows, kBlock >> mcg_column_lanes(k, wide ? W : 1));
@@ -64,7 +53,7 @@ int mpc_apply_check(const spmv_precond *P, int k, const void *R, const void *Z, 
     if (k > kMcgMaxK) return fail("%s: k = %d, must be in [1, %d]", what, k, kMcgMaxK);
     if ((long long)P->rows * k > 0x7fffffffLL)
         return fail("%s: rows * k = %lld values is beyond int range", what, (long long)P->rows * k);
-    return mpcg_refuse_tri(P, what);
+    return precond_refuse_one_wide(P, what);
 }
 
 struct MpcgBuffers {
@@ -82,7 +71,8 @@ int mpcg_run(spmv_csr_dev *m, const spmv_precond *pc, int k, int iters, double t
     const int cl = mcg_column_lanes(k, V);
     const int cap = k == 1 ? kNormBlocks : kMcgBlocks;  // k = 1: csr_pcg's workgroups, csr_pcg's bits
     const int grid = solver_grid(cap, n, kBlock >> cl);
-    const int mode = mpcg_mode(pc), z_is_r = mode == kMpcgNone;
+    const PrecondPath path = precond_path(pc);
+    const int z_is_r = path == kPathNone;
     const double tol2 = tol * tol;
     T *P = (T *)b.P, *p_own = P + m->row0 * kk, *q_own = (T *)b.Q + m->row0 * kk, *x_own = (T *)b.X + m->row0 * kk;
     T *R = (T *)b.R, *Z = (T *)b.Z;
@@ -97,20 +87,20 @@ int mpcg_run(spmv_csr_dev *m, const spmv_precond *pc, int k, int iters, double t
     };
     // r.r -> kMpcgRrNew, and with a preconditioner r.z -> kMpcgRzNew
     auto reduce_dots = [&] { return reduce(b.part_rr, kMpcgRrNew) || (!z_is_r && reduce(b.part_rz, kMpcgRzNew)); };
-    // after the x / r update of the modes that do not fuse their apply: Z = M^-1 R and the two sets of partials
+    // after the x / r update of the paths that do not fuse their apply: Z = M^-1 R and the two sets of partials
     auto apply_dots = [&](const int *flags) {
-        if (!precond_has_own_apply_multi(pc)) {
+        if (path == kPathBlock) {
             mpc_launch<T, V, true>(pc, k, R, Z, flags, b.part_rr, b.part_rz, grid, g_stream);
             return 0;
         }
-        if (precond_own_apply_multi(pc, k, R, Z, b.work, g_stream)) return -1;
+        if (pc->family->apply_multi(pc, k, R, Z, b.work, g_stream)) return -1;
         hipLaunchKernelGGL((mpcg_dots<T, V>), g, blk, 0, g_stream, n, k, cl, (const T *)R, (const T *)Z, b.part_rr, b.part_rz);
         return 0;
     };
     // Z = M^-1 R, rr0 = r.r, rz = r.z with R = B; P = Z (its own range; the rest by the all-gatherv)
-    if (mode == kMpcgNone)
+    if (path == kPathNone)
         hipLaunchKernelGGL((mpcg_start_dots<T, V, false>), g, blk, 0, g_stream, n, k, cl, dinv, (const T *)R, Z, b.part_rr, b.part_rz);
-    else if (mode == kMpcgJacobi)
+    else if (path == kPathJacobi)
         hipLaunchKernelGGL((mpcg_start_dots<T, V, true>), g, blk, 0, g_stream, n, k, cl, dinv, (const T *)R, Z, b.part_rr, b.part_rz);
     else if (apply_dots(nullptr))
         return -1;
@@ -125,10 +115,10 @@ int mpcg_run(spmv_csr_dev *m, const spmv_precond *pc, int k, int iters, double t
                            b.part_rr);
         if (reduce(b.part_rr, kMcgPq)) return -1;
         hipLaunchKernelGGL(mpcg_set_alpha, dim3(1), dim3(64), 0, g_stream, b.s, b.flags, k, t);
-        if (mode == kMpcgNone) {
+        if (path == kPathNone) {
             hipLaunchKernelGGL((mpcg_update_x_r<T, V, kMpcgNone>), g, blk, 0, g_stream, n, k, cl, sc, fl, (const T *)p_own,
                                (const T *)q_own, dinv, x_own, R, Z, b.part_rr, b.part_rz);
-        } else if (mode == kMpcgJacobi) {
+        } else if (path == kPathJacobi) {
             hipLaunchKernelGGL((mpcg_update_x_r<T, V, kMpcgJacobi>), g, blk, 0, g_stream, n, k, cl, sc, fl, (const T *)p_own,
                                (const T *)q_own, dinv, x_own, R, Z, b.part_rr, b.part_rz);
         } else {
@@ -171,7 +161,7 @@ int mpcg_body(spmv_csr_dev *m, const spmv_precond *pc, int k, int iters, double 
     b.X = scope.alloc(q_bytes);
     b.R = scope.alloc(r_bytes);
     b.Z = pc ? scope.alloc(r_bytes) : b.R;
-    b.work = precond_has_own_apply_multi(pc) ? scope.alloc((size_t)precond_work_bytes(pc, k)) : nullptr;
+    b.work = precond_work_alloc(scope, pc, k);
     b.s = scope.alloc<double>(kMpcgSlots * kMcgMaxK * sizeof(double));
     b.part_rr = scope.alloc<double>((size_t)2 * kMcgBlocks * kMcgMaxK * sizeof(double));
     b.part_rz = b.part_rr ? b.part_rr + (size_t)kMcgBlocks * kMcgMaxK : nullptr;
@@ -214,7 +204,7 @@ extern "C" int spmv_hip_csr_pcg_multi(spmv_csr_dev *m, const spmv_precond *P, in
     if ((long long)m->M_total * k > 0x7fffffffLL)
         return fail("%s: n * k = %lld values is beyond int range", what, (long long)m->M_total * k);
     if (solver_check_rows(what, m, bounds)) return -1;
-    if (P && (mpcg_refuse_tri(P, what) || precond_matches(m, P, what))) return -1;
+    if (P && (precond_refuse_one_wide(P, what) || precond_matches(m, P, what))) return -1;
     return solver_dispatch(what, m->value_bytes, [&](auto t) {
         return mpcg_body<decltype(t)>(m, P, k, iters, tol, bounds, B_host, X_host, rr_hist, rz_hist, steps, status, ms_total);
     });
@@ -224,13 +214,7 @@ extern "C" int spmv_hip_precond_apply_multi_on(const spmv_precond *P, int k, con
                                                void *stream) {
     if (need_device()) return -1;
     if (mpc_apply_check(P, k, d_R, d_Z, "precond_apply_multi_on")) return -1;
-    if (P->fsai && P->rows && !d_work)
-        return fail("precond_apply_multi_on: an FSAI apply needs d_work (rows x k values and one 128-byte line)");
-    if (P->amg && P->rows && !d_work)
-        return fail("precond_apply_multi_on: an AMG apply needs d_work (spmv_hip_precond_work_bytes: its level vectors)");
-    if (P->cheb && P->rows && !d_work)
-        return fail("precond_apply_multi_on: a CHEBYSHEV apply needs d_work (spmv_hip_precond_work_bytes: its three "
-                    "arrays)");
+    if (P->family && P->rows && !d_work) return fail("precond_apply_multi_on: %s", P->family->work_text);
     if (((uintptr_t)d_R | (uintptr_t)d_Z | (uintptr_t)d_work) % (uintptr_t)P->value_bytes)
         return fail("precond_apply_multi_on: R, Z and work must be aligned to %d bytes", P->value_bytes);
     hipStream_t s = stream ? (hipStream_t)stream : g_stream;
@@ -245,7 +229,7 @@ extern "C" int spmv_hip_precond_apply_multi(const spmv_precond *P, int k, const 
         SolverScope scope;
         void *R = scope.alloc(padded);
         void *Z = scope.alloc(padded);
-        void *work = precond_has_own_apply_multi(P) ? scope.alloc((size_t)precond_work_bytes(P, k)) : nullptr;
+        void *work = precond_work_alloc(scope, P, k);
         hipError_t e = scope.err;
         if (e == hipSuccess && bytes) e = hipMemcpyAsync(R, R_host, bytes, hipMemcpyHostToDevice, g_stream);
         if (e != hipSuccess) return solver_setup_failed("precond_apply_multi", e);
@@ -263,7 +247,7 @@ extern "C" int spmv_hip_precond_work_bytes(const spmv_precond *P, int k, long lo
     if (!P || !bytes) return fail("precond_work_bytes: bad arguments");
     *bytes = -1;
     if (k < 1 || k > kMcgMaxK) return fail("precond_work_bytes: k = %d, must be in [1, %d]", k, kMcgMaxK);
-    if (mpcg_refuse_tri(P, "precond_work_bytes")) return -1;
+    if (precond_refuse_one_wide(P, "precond_work_bytes")) return -1;
     *bytes = precond_work_bytes(P, k);
     return 0;
 }

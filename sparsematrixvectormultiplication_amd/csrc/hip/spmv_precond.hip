@@ -6,10 +6,10 @@
 // the host: the first row without its diagonal entry and the first bad row or block.  The fp64 blocks are a temporary
 // of ceil(rows / b) b^2 doubles, freed on every path.
 //
-// SSOR and ILU(0) (spmv_hip_csr_precond_build_tri) are the same spmv_precond with P->tri set: spmv_trsv.hip builds and
-// applies them, free / info / apply / apply_on here hand them on.  FSAI (spmv_hip_csr_precond_build_fsai) likewise, with
-// P->fsai set: spmv_fsai.hip.  AMG (spmv_hip_csr_precond_build_amg) with P->amg set: spmv_amg.hip.  CHEBYSHEV
-// (spmv_hip_csr_precond_build_chebyshev) with P->cheb set: spmv_cheb.hip.
+// The other kinds are the same spmv_precond with a family table and the family's own object in P->impl
+// (precond_kernels.hpp), built and applied by the file that owns the family: SSOR and ILU(0) in spmv_trsv.hip, FSAI in
+// spmv_fsai.hip, AMG in spmv_amg.hip and spmv_amg_setup.hip, CHEBYSHEV in spmv_cheb.hip.  free / info / apply /
+// apply_on / factors here go through the table and name no kind.
 #include "spmv_internal.hpp"
 
 #include <climits>
@@ -78,29 +78,21 @@ int precond_build(const spmv_csr_dev *m, int kind, int b, spmv_precond **out) {
                                                                                     (long long)(h[1] + 1) * b, n));
             break;
         }
-        spmv_precond *P = new spmv_precond;
-        P->kind = kind;
-        P->block = b;
-        P->rows = n;
-        P->row0 = m->row0;
-        P->value_bytes = (int)sizeof(T);
-        P->inv = inv;
+        *out = precond_new(m, kind, b, sizeof(T));
+        (*out)->inv = inv;
         inv = nullptr;  // P owns it now
-        *out = P;
         rc = 0;
     } while (0);
     (void)hipFree(D);
     (void)hipFree(bad);
     (void)hipFree(inv);
-    (void)hipGetLastError();  // a refused build or a failed allocation is reported by rc, not by the next launch
     return rc;
 }
 
 int precond_apply_launch(const spmv_precond *P, const void *d_r, void *d_z, hipStream_t s) {
     if (!P->rows) return 0;
-    if (precond_has_own_apply(P)) return precond_own_apply(P, d_r, d_z, nullptr, s);
-    if (P->value_bytes == 8) precond_launch<double, false>(P, d_r, d_z, nullptr, nullptr, 0, s);
-    else precond_launch<float, false>(P, d_r, d_z, nullptr, nullptr, 0, s);
+    if (P->value_bytes == 8 ? precond_apply<double>(P, d_r, d_z, nullptr, s) : precond_apply<float>(P, d_r, d_z, nullptr, s))
+        return -1;
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -108,31 +100,23 @@ int precond_apply_launch(const spmv_precond *P, const void *d_r, void *d_z, hipS
 }  // namespace
 
 extern "C" int spmv_hip_csr_precond_build(const spmv_csr_dev *m, int kind, int block, spmv_precond **out) {
-    if (need_device()) return -1;
-    if (!out) return fail("csr_precond_build: out is NULL");
-    *out = nullptr;
-    if (!m) return fail("csr_precond_build: NULL handle");
-    if (kind != SPMV_PRECOND_JACOBI && kind != SPMV_PRECOND_BLOCK_JACOBI)
-        return fail("csr_precond_build: kind = %d, must be SPMV_PRECOND_JACOBI or SPMV_PRECOND_BLOCK_JACOBI", kind);
-    if (kind == SPMV_PRECOND_JACOBI && block != 1) return fail("csr_precond_build: JACOBI takes block = 1, not %d", block);
-    if (block < 1 || block > kPcMaxBlock)
-        return fail("csr_precond_build: block = %d, must be in [1, %d]", block, kPcMaxBlock);
-    if (m->M_total != m->N) return fail("csr_precond_build: needs a square matrix (%d x %d)", m->M_total, m->N);
-    if (m->tiles_only || !m->row_ptr || (m->nz > 0 && (!m->col || !m->val)))
-        return fail("csr_precond_build: the handle does not hold its CSR arrays");
-    return guarded("csr_precond_build", [&] {
-        return m->value_bytes == 8 ? precond_build<double>(m, kind, block, out)
-                                   : precond_build<float>(m, kind, block, out);
+    auto check = [&] {
+        if (kind != SPMV_PRECOND_JACOBI && kind != SPMV_PRECOND_BLOCK_JACOBI)
+            return fail("csr_precond_build: kind = %d, must be SPMV_PRECOND_JACOBI or SPMV_PRECOND_BLOCK_JACOBI", kind);
+        if (kind == SPMV_PRECOND_JACOBI && block != 1) return fail("csr_precond_build: JACOBI takes block = 1, not %d", block);
+        if (block < 1 || block > kPcMaxBlock)
+            return fail("csr_precond_build: block = %d, must be in [1, %d]", block, kPcMaxBlock);
+        return 0;
+    };
+    return precond_build_frame("csr_precond_build", m, out, check, [&](auto t, spmv_precond **P) {
+        return precond_build<decltype(t)>(m, kind, block, P);
     });
 }
 
 extern "C" void spmv_hip_precond_free(spmv_precond *P) {
     if (!P) return;
     (void)hipFree(P->inv);
-    precond_tri_free(P->tri);
-    precond_fsai_free(P->fsai);
-    precond_amg_free(P->amg);
-    precond_cheb_free(P->cheb);
+    if (P->family) P->family->free(P->impl);
     delete P;
 }
 
@@ -171,4 +155,14 @@ extern "C" int spmv_hip_precond_apply(const spmv_precond *P, const void *r_host,
         if (e != hipSuccess) return fail("precond_apply: run failed: %s", hipGetErrorString(e));
         return 0;
     });
+}
+
+// L (which = SPMV_FACTOR_L) or U of a kind that has factors, as the family's table returns them.  Call with
+// col = val = NULL for row_ptr alone (row_ptr[rows] = the entries to allocate), then with all three.
+extern "C" int spmv_hip_precond_factors(const spmv_precond *P, int which, int *row_ptr, int *col, void *val) {
+    if (need_device()) return -1;
+    if (!P || !row_ptr || (!col) != (!val)) return fail("precond_factors: bad arguments");
+    if (!P->family || !P->family->factors) return fail("precond_factors: kind %d has no factors", P->kind);
+    if (which != SPMV_FACTOR_L && which != SPMV_FACTOR_U) return fail("precond_factors: which = %d", which);
+    return guarded("precond_factors", [&] { return P->family->factors(P, which, row_ptr, col, val); });
 }

@@ -191,6 +191,8 @@ struct spmv_tri_precond {
 
 namespace {
 
+extern const precond_family kTriFamily;  // at the end of the file, behind the functions it names
+
 template <typename T>
 int trsv_build(const spmv_csr_dev *m, int uplo, int diag, spmv_trsv **out) {
     const double t0 = now_ms();
@@ -328,14 +330,7 @@ int tri_precond_build(const spmv_csr_dev *m, int kind, int ordering, double omeg
     tp->analysis_us = (int)((t1 - t0) * 1e3);
     tp->factor_us = (int)((t2 - t1) * 1e3);
     tp->upload_us = (int)((now_ms() - t2) * 1e3);
-    spmv_precond *P = new spmv_precond;
-    P->kind = kind;
-    P->block = 1;
-    P->rows = n;
-    P->row0 = m->row0;
-    P->value_bytes = (int)sizeof(T);
-    P->tri = tp.release();
-    *out = P;
+    *out = precond_new(m, kind, 1, sizeof(T), &kTriFamily, tp.release());
     return 0;
 }
 
@@ -356,12 +351,9 @@ int trsv_solve_host(const spmv_trsv *S, const void *b_host, void *x_host) {
     return 0;
 }
 
-}  // namespace
-
-void precond_tri_free(spmv_tri_precond *tp) { delete tp; }
-
-int precond_tri_apply(const spmv_precond *P, const void *r, void *z, const int *flags, hipStream_t s) {
-    const spmv_tri_precond *tp = P->tri;
+// z = M^-1 r by P's two solves on stream s (flags as pc_apply: a stopped solver's launches return)
+int tri_precond_apply(const spmv_precond *P, const void *r, void *z, const int *flags, hipStream_t s) {
+    const spmv_tri_precond *tp = (const spmv_tri_precond *)P->impl;
     if (!P->rows) return 0;
     if (P->value_bytes == 8) {
         tri_launch<double, false>(tp->fwd, 1.0, flags, (const double *)r, (double *)tp->y, s);
@@ -375,6 +367,8 @@ int precond_tri_apply(const spmv_precond *P, const void *r, void *z, const int *
     HIP_TRY(hipGetLastError());
     return 0;
 }
+
+}  // namespace
 
 extern "C" int spmv_hip_csr_trsv_build(const spmv_csr_dev *m, int uplo, int diag, int ordering, spmv_trsv **out) {
     if (need_device()) return -1;
@@ -430,31 +424,24 @@ extern "C" int spmv_hip_trsv_solve(const spmv_trsv *S, const void *b_host, void 
 
 extern "C" int spmv_hip_csr_precond_build_tri(const spmv_csr_dev *m, int kind, int ordering, double omega,
                                               spmv_precond **out) {
-    if (need_device()) return -1;
-    if (!out) return fail("csr_precond_build_tri: out is NULL");
-    *out = nullptr;
-    if (!m) return fail("csr_precond_build_tri: NULL handle");
-    if (kind != SPMV_PRECOND_SSOR && kind != SPMV_PRECOND_ILU0)
-        return fail("csr_precond_build_tri: kind = %d, must be SPMV_PRECOND_SSOR or SPMV_PRECOND_ILU0", kind);
-    if (ordering != SPMV_ORDER_NATURAL && ordering != SPMV_ORDER_MULTICOLOR)
-        return fail("csr_precond_build_tri: ordering = %d, must be SPMV_ORDER_NATURAL or SPMV_ORDER_MULTICOLOR", ordering);
-    if (kind == SPMV_PRECOND_SSOR && !(omega > 0.0 && omega < 2.0))
-        return fail("csr_precond_build_tri: omega = %g, SSOR needs 0 < omega < 2", omega);
-    if (handle_ok(m, "csr_precond_build_tri")) return -1;
-    spmv_precond *P = nullptr;
-    const int rc = guarded("csr_precond_build_tri", [&] {
-        return m->value_bytes == 8 ? tri_precond_build<double>(m, kind, ordering, omega, &P)
-                                   : tri_precond_build<float>(m, kind, ordering, omega, &P);
+    auto check = [&] {
+        if (kind != SPMV_PRECOND_SSOR && kind != SPMV_PRECOND_ILU0)
+            return fail("csr_precond_build_tri: kind = %d, must be SPMV_PRECOND_SSOR or SPMV_PRECOND_ILU0", kind);
+        if (ordering != SPMV_ORDER_NATURAL && ordering != SPMV_ORDER_MULTICOLOR)
+            return fail("csr_precond_build_tri: ordering = %d, must be SPMV_ORDER_NATURAL or SPMV_ORDER_MULTICOLOR", ordering);
+        if (kind == SPMV_PRECOND_SSOR && !(omega > 0.0 && omega < 2.0))
+            return fail("csr_precond_build_tri: omega = %g, SSOR needs 0 < omega < 2", omega);
+        return 0;
+    };
+    return precond_build_frame("csr_precond_build_tri", m, out, check, [&](auto t, spmv_precond **P) {
+        return tri_precond_build<decltype(t)>(m, kind, ordering, omega, P);
     });
-    (void)hipGetLastError();  // a refused build is reported by rc, not by the next launch
-    if (!rc) *out = P;
-    return rc;
 }
 
 extern "C" int spmv_hip_precond_tri_info(const spmv_precond *P, int *info) {
     if (!P || !info) return fail("precond_tri_info: bad arguments");
-    if (!P->tri) return fail("precond_tri_info: kind %d is not made of triangular solves", P->kind);
-    const spmv_tri_precond *tp = P->tri;
+    const spmv_tri_precond *tp = (const spmv_tri_precond *)precond_impl(P, &kTriFamily, "precond_tri_info");
+    if (!tp) return -1;
     const int v[SPMV_PRECOND_TRI_INFO_WORDS] = {tp->fwd.levels, tp->fwd.launches, tp->fwd.widest, tp->fwd.median,
                                                 tp->bwd.levels, tp->bwd.launches, tp->bwd.widest, tp->bwd.median,
                                                 tp->colours, (int)(tp->fwd.entries + P->rows), (int)(tp->bwd.entries + P->rows),
@@ -463,12 +450,14 @@ extern "C" int spmv_hip_precond_tri_info(const spmv_precond *P, int *info) {
     return 0;
 }
 
-// L (which = SPMV_FACTOR_L) or U of P in the handle's numbering, both with their diagonal, columns ascending.  Call
-// with col = val = NULL for row_ptr alone (row_ptr[rows] = the entries to allocate), then with all three.  The strict
-// triangle is read back from the device's level-ordered copy (P keeps no host copy of it); only the diagonal is P's.
+namespace {
+
+// L (which = SPMV_FACTOR_L) or U of P in the handle's numbering, both with their diagonal, columns ascending (col =
+// val = NULL: row_ptr alone).  The strict triangle is read back from the device's level-ordered copy (P keeps no host
+// copy of it); only the diagonal is P's.
 template <typename T>
-static int factors_body(const spmv_precond *P, bool lower, int *row_ptr, int *col, T *val) {
-    const spmv_tri_precond *tp = P->tri;
+int factors_body(const spmv_precond *P, bool lower, int *row_ptr, int *col, T *val) {
+    const spmv_tri_precond *tp = (const spmv_tri_precond *)P->impl;
     const TriDev &t = lower ? tp->fwd : tp->bwd;
     const int n = P->rows;
     const size_t nz = (size_t)t.entries;
@@ -505,14 +494,13 @@ static int factors_body(const spmv_precond *P, bool lower, int *row_ptr, int *co
     return 0;
 }
 
-extern "C" int spmv_hip_precond_factors(const spmv_precond *P, int which, int *row_ptr, int *col, void *val) {
-    if (need_device()) return -1;
-    if (!P || !row_ptr || (!col) != (!val)) return fail("precond_factors: bad arguments");
-    if (!P->tri && !P->fsai) return fail("precond_factors: kind %d has no factors", P->kind);
-    if (which != SPMV_FACTOR_L && which != SPMV_FACTOR_U) return fail("precond_factors: which = %d", which);
-    if (P->fsai) return guarded("precond_factors", [&] { return precond_fsai_factors(P, which, row_ptr, col, val); });
-    return guarded("precond_factors", [&] {
-        return P->value_bytes == 8 ? factors_body<double>(P, which == SPMV_FACTOR_L, row_ptr, col, (double *)val)
-                                   : factors_body<float>(P, which == SPMV_FACTOR_L, row_ptr, col, (float *)val);
-    });
+int tri_precond_factors(const spmv_precond *P, int which, int *row_ptr, int *col, void *val) {
+    return P->value_bytes == 8 ? factors_body<double>(P, which == SPMV_FACTOR_L, row_ptr, col, (double *)val)
+                               : factors_body<float>(P, which == SPMV_FACTOR_L, row_ptr, col, (float *)val);
 }
+
+// two solves take one right-hand side: no k-wide apply, no workspace
+const precond_family kTriFamily = {"made of triangular solves", nullptr, tri_precond_apply, nullptr, nullptr, tri_precond_factors,
+                                   [](void *impl) { delete (spmv_tri_precond *)impl; }};
+
+}  // namespace

@@ -640,21 +640,25 @@ class CsrDevice(_Handle):
         if kind in ("ssor", "ilu0"):
             if not np.isfinite(float(omega)) or not 0.0 < float(omega) < 2.0:
                 raise ValueError(f"omega must lie in (0, 2), got {omega!r}")
-            return Preconditioner(self, PRECOND_KINDS[kind], 1, float(omega), ORDERINGS[ordering])
+            return Preconditioner(self, "spmv_hip_csr_precond_build_tri", PRECOND_KINDS[kind], ORDERINGS[ordering],
+                                  float(omega))
         if ordering != "natural":
             raise ValueError(f"{kind} takes ordering = 'natural', got {ordering!r}")
         if kind == "fsai":
             if isinstance(cap, bool) or int(cap) != cap or not 1 <= int(cap) <= 32:
                 raise ValueError(f"cap must be an integer in [1, 32], got {cap!r}")
-            return Preconditioner(self, PRECOND_FSAI, 1, cap=int(cap))
+            return Preconditioner(self, "spmv_hip_csr_precond_build_fsai", int(cap))
         if kind == "amg":
             _check_amg_args(theta, coarse_rows, max_levels)
             _check_amg_setup(setup, block_products)
-            return Preconditioner(self, PRECOND_AMG, 1, amg=(float(theta), int(coarse_rows), int(max_levels),
-                                                             int(bool(chain)), AMG_SETUPS[setup], int(block_products)))
+            args = (float(theta), int(coarse_rows), int(max_levels), int(bool(chain)))
+            if AMG_SETUPS[setup]:
+                return Preconditioner(self, "spmv_hip_csr_precond_build_amg_device", *args, int(block_products))
+            return Preconditioner(self, "spmv_hip_csr_precond_build_amg", *args)
         if kind == "chebyshev":
-            return Preconditioner(self, PRECOND_CHEBYSHEV, 1, cheb=_check_chebyshev_args(degree, lmax, lmin, ratio))
-        return Preconditioner(self, PRECOND_KINDS[kind], int(block))
+            return Preconditioner(self, "spmv_hip_csr_precond_build_chebyshev",
+                                  *_check_chebyshev_args(degree, lmax, lmin, ratio))
+        return Preconditioner(self, "spmv_hip_csr_precond_build", PRECOND_KINDS[kind], int(block))
 
     def triangular(self, lower=True, unit_diagonal=False, ordering="natural") -> "TriangularSolver":
         """The lower (upper) triangle of this handle's diagonal block as a solver of T x = b on the device
@@ -1179,31 +1183,11 @@ class Preconditioner(_Handle):
 
     _free = "spmv_hip_precond_free"
 
-    def __init__(self, dev: CsrDevice, kind: int, block: int, omega: float = 1.0, ordering: int = ORDER_NATURAL,
-                 cap: int = 32, amg=None, cheb=None):
+    def __init__(self, dev: CsrDevice, entry_point: str, *args):
+        """The build entry point `entry_point` of the library on dev's handle, with the arguments that stand between
+        the handle and the result in its prototype (CsrDevice.preconditioner has checked them)."""
         super().__init__()
-        if kind == PRECOND_CHEBYSHEV:
-            degree, lmin, lmax, ratio = cheb
-            _check(nat.lib().spmv_hip_csr_precond_build_chebyshev(dev.h, degree, lmin, lmax, ratio, C.byref(self.h)),
-                   "spmv_hip_csr_precond_build_chebyshev")
-        elif kind == PRECOND_AMG:
-            theta, coarse_rows, max_levels, chain, on_device, block_products = amg
-            if on_device:
-                _check(nat.lib().spmv_hip_csr_precond_build_amg_device(dev.h, theta, coarse_rows, max_levels, chain,
-                                                                       block_products, C.byref(self.h)),
-                       "spmv_hip_csr_precond_build_amg_device")
-            else:
-                _check(nat.lib().spmv_hip_csr_precond_build_amg(dev.h, theta, coarse_rows, max_levels, chain,
-                                                                C.byref(self.h)), "spmv_hip_csr_precond_build_amg")
-        elif kind == PRECOND_FSAI:
-            _check(nat.lib().spmv_hip_csr_precond_build_fsai(dev.h, int(cap), C.byref(self.h)),
-                   "spmv_hip_csr_precond_build_fsai")
-        elif kind in (PRECOND_SSOR, PRECOND_ILU0):
-            _check(nat.lib().spmv_hip_csr_precond_build_tri(dev.h, int(kind), int(ordering), float(omega),
-                                                            C.byref(self.h)), "spmv_hip_csr_precond_build_tri")
-        else:
-            _check(nat.lib().spmv_hip_csr_precond_build(dev.h, int(kind), int(block), C.byref(self.h)),
-                   "spmv_hip_csr_precond_build")
+        _check(getattr(nat.lib(), entry_point)(dev.h, *args, C.byref(self.h)), entry_point)
         info = self.info()
         self.kind, self.block, self.rows, self.row0 = info["kind"], info["block"], info["rows"], info["row0"]
         self.dtype = np.float64 if info["value_bytes"] == 8 else np.float32
