@@ -1,7 +1,7 @@
 // spmv_csr.hip -- CSR side of the C-ABI: upload-time preprocessing (workgroup blocks, the
 // x-window plan, split long rows; the tile plans: tile_upload.hpp), kernel launchers, timing.  Replaces the device code of the
-// reference's per-matrix CSR section (/root/reference/main_cuda.cu:135-145, :149-166, :212-238,
-// :285-317, :682-685).
+// reference's per-matrix CSR section (its main_cuda.cu, lines 135-145, 149-166, 212-238, 285-317
+// and 682-685).
 #include "spmv_internal.hpp"
 
 #include "launch_dispatch.hpp"
@@ -289,12 +289,12 @@ void csr_share_plan(spmv_csr_dev *m) {
 // The x-window phase of upload (csr_stream_local): own blocks at the stage m->local_cap.  One stage size per handle, so
 // that its blocks, the gather kernel's and the split long rows agree on which rows are long: a matrix that gets a plan
 // runs everything at 2048.  An explicit stream_cap other than that asks for the gather kernel's configuration and skips
-// the plan.  rp: the handle's row_ptr; col_host: its columns, or NULL when they live on the device only (m->col).
+// the plan.  rp: the handle's row_ptr, `rows` the same on its way to the device; col: the handle's columns.
 // 1: m->xw is the plan, complete -- uploaded, with its pattern plan and the sharing pass -- and `split` marks the rows it
 // hands to the split-row kernels; 0: no plan, nothing of it allocated; -1: error.
 template <typename T>
-int csr_x_window_phase(spmv_csr_dev *m, const std::vector<int> &rp, const int *col_host, UploadTrace &trace,
-                       std::vector<unsigned char> &split) {
+int csr_x_window_phase(spmv_csr_dev *m, const std::vector<int> &rp, UploadSource<int> &rows, UploadSource<int> &col,
+                       UploadTrace &trace, std::vector<unsigned char> &split) {
     constexpr int line_shift = sizeof(T) == 8 ? 4 : 5;  // 128-byte lines
     const int Ml = m->M_local, lcap = m->local_cap;
     const long long nz = m->nz;
@@ -308,44 +308,36 @@ int csr_x_window_phase(spmv_csr_dev *m, const std::vector<int> &rp, const int *c
         // otherwise the host builder decides (line-limited blocks, split rows, or no plan)
         int dev = 0;
         if (g_plan_on_device && lcap == kPlanCap) {
-            if (!m->col && upload_array(&m->col, col_host, (size_t)nz, kPad)) return -1;
+            if (col.device_view()) return -1;
             dev = csr_plan_on_device<line_shift>(m, desc, nz);
             if (dev < 0) return -1;
         }
-        on_device = dev == 1;
-        const bool refused = dev == 2;  // plainly scattered columns: no plan, and no need to ask the host builder
-        std::vector<int> col_back;  // adopted arrays live on the device only: the host builder needs a copy
-        if (!on_device && !refused && !col_host) {
-            col_back.resize((size_t)nz);
-            if (hipMemcpy(col_back.data(), m->col, (size_t)nz * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
-                return fail("csr_upload: copying the columns back for the host plan failed");
+        on_device = have_local = dev == 1;
+        if (dev == 0) {  // (2: plainly scattered columns -- no plan, and no need to ask the host builder)
+            const int *col_host = col.host_view("csr_upload: copying the columns back for the host plan failed");
+            if (!col_host) return -1;
+            have_local = csr_build_local(Ml, m->N, rp.data(), col_host, nz, lcap, kStreamRowsCap, line_shift, kLocalLinesMax, desc, local);
         }
-        have_local = on_device ||
-                     (!refused && csr_build_local(Ml, m->N, rp.data(), col_host ? col_host : col_back.data(), nz, lcap,
-                                                  kStreamRowsCap, line_shift, kLocalLinesMax, desc, local));
         if (on_device) split.assign((size_t)Ml, 0);
         else if (have_local) split.swap(local.split);
     }
     trace.mark("x-window plan (or its refusal)");
     if (!have_local) return 0;
-    if (upload_array(&m->row_ptr, rp.data(), rp.size(), (size_t)kRowPtrPad)) return -1;
+    if (rows.device_view()) return -1;
     if (!on_device && m->xw.upload(local)) return -1;
-    // the pattern plan (optional: one that cannot be built is simply not there); here, ahead of the value array, whose
-    // first placement goes with the allocations before it
+    // the pattern plan (optional: one that cannot be built is simply not there); all of the plan ahead of the value
+    // array (the allocation order above csr_upload_impl)
     csr_pattern_segments(m, build_pattern_tables<false>(m->xw, Ml, nz, m->value_bytes, m->row_ptr));
     // equal segments and line lists once: before the searches, which time the plan the handle keeps
     csr_share_plan(m);
     return 1;
 }
 
+// The checks of upload, all ahead of the handle.  rp: rows [row0, row1) of row_ptr, rebased to 0.  Returns the longest
+// row, or -1.
 template <typename T>
-int csr_upload_impl(int M, int N, const int *row_ptr, const int *col_idx, const T *values, int row0,
-                    int row1, spmv_csr_dev **out, int *adopt_col = nullptr, T *adopt_val = nullptr) {
-    // adopt_col / adopt_val: device arrays of row_ptr[row1] - row_ptr[row0] (+ kPad zeroed) entries that the
-    // handle takes over instead of uploading col_idx / values (which are then NULL); columns already checked
-    if (need_device()) return -1;
-    if (!out) return fail("csr_upload: out is NULL");
-    *out = nullptr;
+int csr_upload_checks(int M, int N, const int *row_ptr, int row0, int row1, const MatrixSource<T> &from, UploadTrace &trace,
+                      std::vector<int> &rp) {
     if (M < 0 || N < 0 || !row_ptr) return fail("csr_upload: bad arguments");
     if (row0 < 0 || row1 < row0 || row1 > M) return fail("csr_upload: bad row range [%d, %d) of %d", row0, row1, M);
     const int Ml = row1 - row0;
@@ -353,11 +345,11 @@ int csr_upload_impl(int M, int N, const int *row_ptr, const int *col_idx, const 
     const long long nz = (long long)e1 - e0;
     if (nz < 0) return fail("csr_upload: row_ptr is not monotone");
     if (nz > 0x7fffffffLL - kPad) return fail("csr_upload: %lld entries exceed the 32-bit entry index of the kernels", nz);
-    if (nz > 0 && !adopt_col && (!col_idx || !values)) return fail("csr_upload: col_idx / values are NULL");
-    UploadTrace trace("csr_upload");
+    if (nz > 0 && !from.col.adopted && !from.on_host()) return fail("csr_upload: col_idx / values are NULL");
     if ((unsigned long long)N * sizeof(T) >= (1ull << 32))
         return fail("csr_upload: N = %d exceeds the 32-bit gather offset range of the kernels", N);
-    // a column index outside [0, N) would make the kernels gather out of bounds
+    // a column index outside [0, N) would make the kernels gather out of bounds (adopted columns are checked already)
+    const int *col_idx = from.col.host;
     if (col_idx && e1 > e0) {  // (a few threads: one pass over 2.6e8 indices is 0.15 s of a 1 s upload on one core)
         const int threads = (long long)e1 - e0 >= (1 << 22) ? (int)std::min(8u, std::max(1u, std::thread::hardware_concurrency())) : 1;
         std::vector<long long> first_bad((size_t)threads, -1);
@@ -372,99 +364,67 @@ int csr_upload_impl(int M, int N, const int *row_ptr, const int *col_idx, const 
         for (long long e : first_bad)
             if (e >= 0) return fail("csr_upload: column index %d at entry %lld is outside [0, %d)", col_idx[e], e, N);
     }
-
     trace.mark("column check");
-    spmv_csr_dev *m = new (std::nothrow) spmv_csr_dev();
-    if (!m) return fail("csr_upload: out of host memory");
-    // owns the handle until it is handed out: on any failure it is freed, adopted arrays go back to the caller untouched
-    struct Drop {
-        spmv_csr_dev *h;
-        bool keep_col, keep_val;
-        ~Drop() {
-            if (!h) return;
-            if (keep_col) h->col = nullptr;
-            if (keep_val) h->val = nullptr;
-            spmv_hip_csr_free(h);
-        }
-    } drop{m, adopt_col != nullptr, adopt_val != nullptr};
-    m->value_bytes = (int)sizeof(T);
-    m->M_local = Ml;
-    m->M_total = M;
-    m->N = N;
-    m->row0 = row0;
-    m->nz = nz;
-    m->col = adopt_col;
-    m->val = adopt_val;
-
-    std::vector<int> rp((size_t)Ml + 1);
+    rp.resize((size_t)Ml + 1);
     int max_row = 0;
     for (int r = 0; r <= Ml; ++r) rp[r] = row_ptr[row0 + r] - e0;
     for (int r = 0; r < Ml; ++r) {
         if (rp[r + 1] < rp[r]) return fail("csr_upload: row_ptr decreases at row %d", row0 + r);
         max_row = std::max(max_row, rp[r + 1] - rp[r]);
     }
-    m->max_row = max_row;
+    return max_row;
+}
 
-    // the x-window kernel first (csr_stream_local); (1024-entry blocks were tried for small matrices: cant-like 13.2 us
-    // against 11.7 us at 2048)
-    m->local_cap = g_local_cap ? g_local_cap : 2048;
-    std::vector<unsigned char> local_split;
-    const int planned = csr_x_window_phase<T>(m, rp, col_idx ? col_idx + e0 : nullptr, trace, local_split);
-    if (planned < 0) return -1;
-    const bool have_local = planned == 1;
-    // No x-window plan: columns too scattered for 256 lines per block.  Then the 2-D tiles (csr_tile):
-    // row-block accumulators in LDS, the block's entries re-ordered into column passes so that all
-    // workgroups sweep x together (L2-resident band), dense passes staged in LDS.  Needs enough row
-    // blocks to fill the chip; rows longer than tile_lmax stay with the split-row kernels, their
-    // pieces cut at column stripes.
-    TileBuild<T> tb;
-    if (!have_local && nz > 0 && g_stream_tile != 0 && g_stream_cap == 0 &&
-        (g_stream_tile == 1 || (long long)Ml >= kTileMinRows || nz >= kTileMidEntries)) {
-        std::vector<int> col_copy;
-        std::vector<T> val_copy;
-        const int *hcol = col_idx ? col_idx + e0 : nullptr;
-        const T *hval = values ? values + e0 : nullptr;
-        if (!hcol) {  // adopted arrays live on the device only
-            col_copy.resize((size_t)nz);
-            val_copy.resize((size_t)nz);
-            if (hipMemcpy(col_copy.data(), m->col, (size_t)nz * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
-                hipMemcpy(val_copy.data(), m->val, (size_t)nz * sizeof(T), hipMemcpyDeviceToHost) != hipSuccess)
-                return fail("csr_upload: copying the matrix back for the tile plan failed");
-            hcol = col_copy.data();
-            hval = val_copy.data();
-        }
-        std::vector<int> row_len((size_t)Ml);
-        for (int r = 0; r < Ml; ++r) row_len[(size_t)r] = rp[(size_t)r + 1] - rp[(size_t)r];
-        // the plan is built on the device from the CSR arrays there (tile_plan_device.hpp; "tile_plan_on_device" 0: on
-        // host threads, tile_plan.hpp -- the two give the same bytes): the matrix goes up first
-        TileDevInput<T> din;
-        int *d_row_len = nullptr;
-        bool on_dev = g_tile_plan_on_device != 0;
-        if (on_dev) {
-            int urc = 0;
-            if (!m->col) urc |= upload_array(&m->col, col_idx ? col_idx + e0 : nullptr, (size_t)nz, kPad);
-            if (!urc && !m->val) urc |= upload_array((T **)&m->val, values ? values + e0 : nullptr, (size_t)nz, kPad);
-            if (!urc && !m->row_ptr) urc |= upload_array(&m->row_ptr, rp.data(), rp.size(), (size_t)kRowPtrPad);
-            if (!urc) urc |= upload_array(&d_row_len, row_len.data(), row_len.size(), 1);
-            if (urc) {
-                (void)hipFree(d_row_len);
-                return -1;
-            }
-            din.row_begin = m->row_ptr;
-            din.row_len = d_row_len;
-            din.col = m->col;
-            din.val = (const T *)m->val;
-            din.stream = g_stream;
-        }
-        trace.mark("matrix to the device");
-        tile_plan_all<T>(Ml, N, rp.data(), row_len.data(), rp.data(), nz, hcol, hval, tb, on_dev ? &din : nullptr);
-        (void)hipFree(d_row_len);
-        trace.mark("tile plans");
+// The tile phase of upload, for a handle without an x-window plan (columns too scattered for 256 lines per block): the
+// 2-D tiles (csr_tile) -- row-block accumulators in LDS, the block's entries re-ordered into column passes so that all
+// workgroups sweep x together (L2-resident band), dense passes staged in LDS.  Needs enough row blocks to fill the chip;
+// rows longer than tile_lmax stay with the split-row kernels, their pieces cut at column stripes.  tb: the plans, for
+// csr_blocks_and_uploads to put into the handle.  -1: error.
+template <typename T>
+int csr_tile_phase(spmv_csr_dev *m, const std::vector<int> &rp, UploadSource<int> &rows, MatrixSource<T> &src, UploadTrace &trace,
+                   TileBuild<T> &tb) {
+    const int Ml = m->M_local;
+    const long long nz = m->nz;
+    if (nz <= 0 || g_stream_tile == 0 || g_stream_cap != 0) return 0;
+    if (g_stream_tile != 1 && (long long)Ml < kTileMinRows && nz < kTileMidEntries) return 0;
+    // (the host arrays: the host builder's input, the device builder's fallback, and what the stripe-cut pieces are cut from)
+    const char *no_copy = "csr_upload: copying the matrix back for the tile plan failed";
+    const int *hcol = src.col.host_view(no_copy);
+    const T *hval = hcol ? src.val.host_view(no_copy) : nullptr;
+    if (!hcol || !hval) return -1;
+    std::vector<int> row_len((size_t)Ml);
+    for (int r = 0; r < Ml; ++r) row_len[(size_t)r] = rp[(size_t)r + 1] - rp[(size_t)r];
+    // the plan is built on the device from the CSR arrays there (tile_plan_device.hpp; "tile_plan_on_device" 0: on
+    // host threads, tile_plan.hpp -- the two give the same bytes): the matrix goes up first
+    TileDevInput<T> din;
+    DevBuf d_row_len;
+    const bool on_dev = g_tile_plan_on_device != 0;
+    if (on_dev) {
+        if (src.col.device_view() || src.val.device_view() || rows.device_view() ||
+            upload_array((int **)&d_row_len.p, row_len.data(), row_len.size(), 1))
+            return -1;
+        din.row_begin = m->row_ptr;
+        din.row_len = d_row_len.as<int>();
+        din.col = m->col;
+        din.val = (const T *)m->val;
+        din.stream = g_stream;
     }
-    // else: larger stages amortise per-workgroup latency on big matrices; small ones need
-    // enough workgroups to fill 256 CUs (measured: cant-like 2048, nlpkkt-like 4096)
-    m->stream_cap = have_local ? m->local_cap : (g_stream_cap ? g_stream_cap : (nz >= (16LL << 20) ? 4096 : 2048));
-    int rows_cap = kStreamRowsCap;
+    trace.mark("matrix to the device");
+    tile_plan_all<T>(Ml, m->N, rp.data(), row_len.data(), rp.data(), nz, hcol, hval, tb, on_dev ? &din : nullptr);
+    trace.mark("tile plans");
+    return 0;
+}
+
+// The workgroup blocks and split rows of the gather kernels, then whatever of the handle is not on the device yet.
+// split: the rows the x-window plan hands to the split-row kernels (nullptr: no plan); tb: the tile phase's plans.
+template <typename T>
+int csr_blocks_and_uploads(spmv_csr_dev *m, const std::vector<int> &rp, UploadSource<int> &rows, MatrixSource<T> &src,
+                           const std::vector<unsigned char> *split, TileBuild<T> &tb) {
+    const int Ml = m->M_local;
+    const long long nz = m->nz;
+    // larger stages amortise per-workgroup latency on big matrices; small ones need enough workgroups to fill 256 CUs
+    // (measured: cant-like 2048, nlpkkt-like 4096); a matrix with an x-window plan runs everything at the plan's stage
+    m->stream_cap = split ? m->local_cap : (g_stream_cap ? g_stream_cap : (nz >= (16LL << 20) ? 4096 : 2048));
     // Skewed rows (gather kernels): a block's rows are summed by lane groups sized for the NUMBER of rows in it, so in
     // a block of a few hundred short rows one row of a thousand entries is summed by a single lane while everybody else
     // waits (webbase-like stand-in, 1 M rows, 3.3 entries per row on average, 2 262 in the longest: 73 us; with its rows
@@ -472,72 +432,111 @@ int csr_upload_impl(int M, int N, const int *row_ptr, const int *col_idx, const 
     // Rows longer than max(128, 16 x the average row) count as long there -- from 2^20 entries on: the two extra
     // launches of the split-row kernels cost ~5 us, more than a small matrix's whole product.
     std::vector<unsigned char> skew_split;
-    if (!have_local && g_skew_rows && Ml > 0 && nz >= (1LL << 20)) {
+    if (!split && g_skew_rows && Ml > 0 && nz >= (1LL << 20)) {
         const long long limit = std::max<long long>(128, 16 * (nz / Ml));
         if (limit < m->stream_cap - 3) {
             bool any = false;
             skew_split.assign((size_t)Ml, 0);
             for (int r = 0; r < Ml; ++r)
                 if (rp[(size_t)r + 1] - rp[(size_t)r] > limit) skew_split[(size_t)r] = 1, any = true;
-            if (!any) skew_split.clear();
+            if (any) split = &skew_split;
         }
     }
     std::vector<int4> desc, pieces, long_rows;
-    csr_build_blocks(Ml, rp.data(), m->stream_cap, rows_cap, desc, pieces, long_rows,
-                     have_local ? &local_split : skew_split.empty() ? nullptr : &skew_split);
+    csr_build_blocks(Ml, rp.data(), m->stream_cap, kStreamRowsCap, desc, pieces, long_rows, split);
     m->num_blocks = (int)desc.size();
     m->num_long = (int)long_rows.size();
     m->num_partial = (int)pieces.size();
-    const int num_partial = m->num_partial;
-
-    int rc = 0;
-    if (!m->row_ptr) rc |= upload_array(&m->row_ptr, rp.data(), rp.size(), (size_t)kRowPtrPad);
-    if (!rc && !m->col) rc |= upload_array(&m->col, col_idx ? col_idx + e0 : nullptr, (size_t)nz, kPad);
-    if (!rc && !m->val) rc |= upload_array((T **)&m->val, values ? values + e0 : nullptr, (size_t)nz, kPad);
-    if (!rc) rc |= upload_array(&m->desc, desc.data(), desc.size(), 1);
-    if (!rc && m->num_long) rc |= upload_array(&m->long_rows, long_rows.data(), long_rows.size(), 0);
-    if (!rc && num_partial) rc |= upload_array(&m->pieces, pieces.data(), pieces.size(), 0);
     // (the tile plans add their own bytes)
     m->rest_bytes = rp.size() * 4 + ((size_t)nz + kPad) * (4 + sizeof(T)) + desc.size() * 16 + long_rows.size() * 16 +
-                    pieces.size() * 16 + (size_t)num_partial * sizeof(T) + ((size_t)N + (size_t)M) * sizeof(T);
-    if (!rc && tile_upload_all<T>(m, tb) < 0) rc = -1;  // (1 = the device refused the LDS size: no tiles, not an error)
-    const int partial_slots = std::max(num_partial, (int)tb.tile_pieces.size());
-    if (!rc && partial_slots) {
+                    pieces.size() * 16 + (size_t)m->num_partial * sizeof(T) + ((size_t)m->N + (size_t)m->M_total) * sizeof(T);
+    if (rows.device_view() || src.col.device_view() || src.val.device_view()) return -1;
+    if (upload_array(&m->desc, desc.data(), desc.size(), 1)) return -1;
+    if (m->num_long && upload_array(&m->long_rows, long_rows.data(), long_rows.size(), 0)) return -1;
+    if (m->num_partial && upload_array(&m->pieces, pieces.data(), pieces.size(), 0)) return -1;
+    if (tile_upload_all<T>(m, tb) < 0) return -1;  // (1 = the device refused the LDS size: no tiles, not an error)
+    const int partial_slots = std::max(m->num_partial, (int)tb.tile_pieces.size());
+    if (partial_slots) {
         hipError_t e = hipMalloc(&m->partial, (size_t)partial_slots * sizeof(T));
-        if (e != hipSuccess) rc = fail("hipMalloc(partial) failed: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return fail("hipMalloc(partial) failed: %s", hipGetErrorString(e));
     }
-    if (!rc) {
-        // x is read in whole 128-byte lines by csr_stream_local: room for the tail of the last one
-        const size_t x_bytes = std::max<size_t>((size_t)N, 1) * sizeof(T) + kLineBytes;
-        hipError_t e = hipMalloc(&m->x, x_bytes);
-        if (e == hipSuccess) e = hipMalloc(&m->y, std::max<size_t>((size_t)M, 1) * sizeof(T));
-        if (e == hipSuccess) e = hipMemset(m->x, 0, x_bytes);
-        if (e == hipSuccess) e = hipMemset(m->y, 0, std::max<size_t>((size_t)M, 1) * sizeof(T));
-        if (e != hipSuccess) rc = fail("hipMalloc(x/y) failed: %s", hipGetErrorString(e));
-    }
-    if (rc) return -1;
+    return 0;
+}
 
-    // lanes per row for the SUBWAVE kernel: about half the mean row length,
-    // rounded to a power of two, so that a typical row takes 1-2 passes
-    const double mean = Ml ? (double)nz / Ml : 0.0;
-    int lanes = pow2_floor(std::max(2, (int)(mean / 2.0 + 0.5)));
-    m->lanes_per_row = std::min(32, std::max(2, lanes));
+// What SPMV_CSR_AUTO runs, and the lanes per row of the lane-group kernel.
+// Mid-size matrices that get neither plan (scattered columns, below the tile plans' size): the lane-group kernel
+// beats the gather stream kernels by 3-10 % on every such stand-in of the reference's list (cop20k_A-size 19.2 vs
+// 21.2 us, PR02R-size 37 vs 41, amazon0302-size 12.1 vs 13.5; profiles/r2_reference_list_stand_ins.md) -- unless rows
+// are skewed (its lanes per row are fixed), and not on large ones (road-like 12 M rows: 282 vs 255 us).
+void csr_auto_variant(spmv_csr_dev *m, bool have_plan) {
+    const double mean = m->M_local ? (double)m->nz / m->M_local : 0.0;
+    m->lanes_per_row = lanes_for_mean_row(mean);
     m->auto_variant = SPMV_CSR_STREAM;
-    // Mid-size matrices that get neither plan (scattered columns, below the tile plans' size): the lane-group kernel
-    // beats the gather stream kernels by 3-10 % on every such stand-in of the reference's list (cop20k_A-size 19.2 vs
-    // 21.2 us, PR02R-size 37 vs 41, amazon0302-size 12.1 vs 13.5; profiles/r2_reference_list_stand_ins.md) -- unless rows
-    // are skewed (its lanes per row are fixed), and not on large ones (road-like 12 M rows: 282 vs 255 us).
-    if (!have_local && !tb.tiles.have && nz < (20LL << 20) && max_row <= std::max(64.0, 8.0 * mean))
-        m->auto_variant = SPMV_CSR_SUBWAVE;
-    trace.mark("blocks, remaining uploads, vectors");
-    // the searches (upload_ops.hpp); the placement of m->val where it is large and streamed by the handle's kernel (a
-    // tile plan without an x-window plan streams its own re-ordered copy)
-    const bool place = (size_t)nz * sizeof(T) >= kPlaceMinBytes && !m->tiles_only && (m->xw.blocks > 0 || m->tile.blocks == 0);
-    upload_searches(m, place ? &m->val : nullptr, ((size_t)nz + kPad) * sizeof(T),
+    if (!have_plan && m->nz < (20LL << 20) && m->max_row <= std::max(64.0, 8.0 * mean)) m->auto_variant = SPMV_CSR_SUBWAVE;
+}
+
+// The searches of a finished handle (upload_ops.hpp); the placement of m->val where it is large and streamed by the
+// handle's kernel (a tile plan without an x-window plan streams its own re-ordered copy).
+template <typename T>
+void csr_upload_searches(spmv_csr_dev *m) {
+    const bool place = (size_t)m->nz * sizeof(T) >= kPlaceMinBytes && !m->tiles_only && (m->xw.blocks > 0 || m->tile.blocks == 0);
+    upload_searches(m, place ? &m->val : nullptr, ((size_t)m->nz + kPad) * sizeof(T),
                     [m] { return csr_launch_any(m, SPMV_CSR_AUTO, m->x, m->y, g_stream); });
+}
+
+// Upload: the matrix `from` -- host arrays, or device arrays of row_ptr[row1] - row_ptr[row0] (+ kPad zeroed) entries
+// that the handle adopts, their columns already checked -- becomes a handle over rows [row0, row1).
+//
+// THE ORDER OF THE DEVICE ALLOCATIONS is part of the handle: where an array lands follows from what was allocated before
+// it, and the first placement of the value array decides what the x-window kernel makes of it (tune_placement,
+// upload_ops.hpp).  An array is allocated by the first phase that asks for its device view, so the order is:
+//   1. x-window phase   (a) only when the plan is tried on the device: col, the builder's scratch (freed again), then
+//                           the plan -- lines, slot, ldesc4, ldesc;
+//                       (b) only when there is a plan: row_ptr; a host-built plan's ldesc4, ldesc, lines, slot; the
+//                           pattern plan; the shared segments and line lists.
+//   2. tile phase       only without an x-window plan, and only when the tile plan is built on the device: col, val,
+//                       row_ptr (each unless it is there), the row lengths (freed again), the device builder's arrays.
+//   3. blocks, uploads  row_ptr, col, val (each unless it is there), desc, long_rows, pieces, the tile plans, partial.
+//   4. vectors          x, y.
+//   5. searches         candidates for val (tune_placement).
+// So with an x-window plan val comes behind the whole plan, and with a device-built tile plan ahead of it.
+template <typename T>
+int csr_upload_impl(int M, int N, const int *row_ptr, int row0, int row1, const MatrixSource<T> &from, spmv_csr_dev **out) {
+    if (need_device()) return -1;
+    if (!out) return fail("csr_upload: out is NULL");
+    *out = nullptr;
+    UploadTrace trace("csr_upload");
+    std::vector<int> rp;
+    const int max_row = csr_upload_checks<T>(M, N, row_ptr, row0, row1, from, trace, rp);
+    if (max_row < 0) return -1;
+
+    HandleGuard<spmv_csr_dev, spmv_hip_csr_free> guard(new (std::nothrow) spmv_csr_dev());
+    spmv_csr_dev *m = guard.h;
+    if (!m) return fail("csr_upload: out of host memory");
+    m->value_bytes = (int)sizeof(T), m->nz = rp.back(), m->max_row = max_row;
+    m->M_local = row1 - row0, m->M_total = M, m->N = N, m->row0 = row0;
+    // (1024-entry x-window blocks were tried for small matrices: cant-like 13.2 us against 11.7 us at 2048)
+    m->local_cap = g_local_cap ? g_local_cap : 2048;
+    // (behind the guard: on a failure the source goes first and takes adopted arrays out of the handle again)
+    MatrixSource<T> src(from);
+    src.bind(&m->col, (T **)&m->val, (size_t)row_ptr[row0], (size_t)m->nz, kPad);
+    UploadSource<int> rows;
+    rows.host = rp.data();
+    rows.bind(&m->row_ptr, 0, rp.size(), (size_t)kRowPtrPad);
+
+    std::vector<unsigned char> split;
+    TileBuild<T> tb;
+    const int planned = csr_x_window_phase<T>(m, rp, rows, src.col, trace, split);
+    if (planned < 0) return -1;
+    if (!planned && csr_tile_phase<T>(m, rp, rows, src, trace, tb)) return -1;
+    if (csr_blocks_and_uploads<T>(m, rp, rows, src, planned ? &split : nullptr, tb)) return -1;
+    if (alloc_vectors(&m->x, &m->y, N, M, (int)sizeof(T))) return -1;
+    csr_auto_variant(m, planned || tb.tiles.have);
+    trace.mark("blocks, remaining uploads, vectors");
+    csr_upload_searches<T>(m);
     trace.mark("placement tuning");
-    drop.h = nullptr;
-    *out = m;
+    src.keep();
+    *out = guard.release();
     return 0;
 }
 
@@ -879,11 +878,11 @@ extern "C" int spmv_hip_csr_tile_auto_plan(int M, int N, const int *row_ptr, con
 
 // a whole fp64 matrix whose col / val already sit on the device (spmv_coo.hip)
 int csr_adopt_f64(int M, int N, const int *row_ptr_host, int *d_col, double *d_val, spmv_csr_dev **out) {
-    return guarded("csr_adopt", [&] { return csr_upload_impl<double>(M, N, row_ptr_host, nullptr, nullptr, 0, M, out, d_col, d_val); });
+    return guarded("csr_adopt", [&] { return csr_upload_impl<double>(M, N, row_ptr_host, 0, M, MatrixSource<double>::adopting(d_col, d_val), out); });
 }
 // ... and its fp32 twin (spmv_transpose.hip)
 int csr_adopt_f32(int M, int N, const int *row_ptr_host, int *d_col, float *d_val, spmv_csr_dev **out) {
-    return guarded("csr_adopt", [&] { return csr_upload_impl<float>(M, N, row_ptr_host, nullptr, nullptr, 0, M, out, d_col, d_val); });
+    return guarded("csr_adopt", [&] { return csr_upload_impl<float>(M, N, row_ptr_host, 0, M, MatrixSource<float>::adopting(d_col, d_val), out); });
 }
 
 // A handle that carries NOTHING but tile plans, for rows given as (first entry, length) pairs over host arrays:
@@ -893,31 +892,39 @@ int csr_adopt_f32(int M, int N, const int *row_ptr_host, int *d_col, float *d_va
 // (Defined here, behind the uploads above, and not with the rest of the tile orchestration in tile_upload.hpp: the order in
 // which this translation unit first names tile_plan_all<float> and <double> is the order of their kernels in its code object.)
 int csr_tiles_from_rows_f64(int M_local, int M_total, int row0, int N, const int *row_begin, const int *row_len,
-                            long long entries, const int *col, const double *val, spmv_csr_dev **out,
-                            const int *d_col, const double *d_val) {
+                            long long entries, MatrixSource<double> &slab, spmv_csr_dev **out) {
     *out = nullptr;
     if (M_local <= 0 || entries <= 0 || g_stream_tile == 0) return 0;
     if (g_stream_tile < 0 && (long long)M_local < kTileMinRows && entries < kTileMidEntries) return 0;
     return guarded("hll tile plan", [&] {
         TileBuild<double> tb;
-        // d_col / d_val: the same slab on the device -- the plan is then built there (the rows' begin / length lists go up)
+        // the slab on the device: the plan is built there (the rows' begin / length lists go up), and host arrays the
+        // caller happens to have are the fallback; else by the host builder, from the host view
         TileDevInput<double> din;
         int *d_begin = nullptr, *d_len = nullptr;
-        bool on_dev = g_tile_plan_on_device != 0 && d_col && d_val;
+        bool on_dev = g_tile_plan_on_device != 0 && slab.on_device();
+        const int *col = slab.col.host;
+        const double *val = slab.val.host;
+        if (!on_dev) {
+            col = slab.col.host_view("hll_from_csr: JA download failed: %s");
+            val = col ? slab.val.host_view("hll_from_csr: AS download failed: %s") : nullptr;
+            if (!col || !val) return -1;
+        }
         if (on_dev && (upload_array(&d_begin, row_begin, (size_t)M_local, 1) || upload_array(&d_len, row_len, (size_t)M_local, 1)))
             on_dev = false;
         if (on_dev) {
             din.row_begin = d_begin;
             din.row_len = d_len;
-            din.col = d_col;
-            din.val = d_val;
+            din.col = *slab.col.field;
+            din.val = *slab.val.field;
             din.stream = g_stream;
         }
         tile_plan_all<double>(M_local, N, row_begin, row_len, nullptr, entries, col, val, tb, on_dev ? &din : nullptr);
         (void)hipFree(d_begin);
         (void)hipFree(d_len);
         if (!tb.tiles.have) return 0;
-        spmv_csr_dev *m = new (std::nothrow) spmv_csr_dev();
+        HandleGuard<spmv_csr_dev, spmv_hip_csr_free> guard(new (std::nothrow) spmv_csr_dev());
+        spmv_csr_dev *m = guard.h;
         if (!m) return fail("hll tile plan: out of host memory");
         m->value_bytes = 8;
         m->M_local = M_local;
@@ -928,11 +935,8 @@ int csr_tiles_from_rows_f64(int M_local, int M_total, int row0, int N, const int
         m->tiles_only = true;
         m->auto_variant = SPMV_CSR_STREAM;
         const int trc = tile_upload_all<double>(m, tb);
-        if (trc) {  // 1: no tiles on this device (the slab keeps hll_lds), -1: a real failure
-            spmv_hip_csr_free(m);
-            return trc < 0 ? -1 : 0;
-        }
-        *out = m;
+        if (trc) return trc < 0 ? -1 : 0;  // 1: no tiles on this device (the slab keeps hll_lds), -1: a real failure
+        *out = guard.release();
         return 0;
     });
 }
@@ -951,12 +955,12 @@ static void release_relocated(spmv_csr_dev::relocated &r) {
 
 extern "C" int spmv_hip_csr_upload(int M, int N, const int *row_ptr, const int *col_idx,
                                    const double *values, int row0, int row1, spmv_csr_dev **out) {
-    return guarded("csr_upload", [&] { return csr_upload_impl<double>(M, N, row_ptr, col_idx, values, row0, row1, out); });
+    return guarded("csr_upload", [&] { return csr_upload_impl<double>(M, N, row_ptr, row0, row1, MatrixSource<double>::on_host(col_idx, values), out); });
 }
 
 extern "C" int spmv_hip_csr_upload_f32(int M, int N, const int *row_ptr, const int *col_idx,
                                        const float *values, int row0, int row1, spmv_csr_dev **out) {
-    return guarded("csr_upload_f32", [&] { return csr_upload_impl<float>(M, N, row_ptr, col_idx, values, row0, row1, out); });
+    return guarded("csr_upload_f32", [&] { return csr_upload_impl<float>(M, N, row_ptr, row0, row1, MatrixSource<float>::on_host(col_idx, values), out); });
 }
 
 extern "C" int spmv_hip_csr_upload_matrix(const CSRMatrix *csr, spmv_csr_dev **out) {
@@ -1640,8 +1644,8 @@ int csr_split_columns_impl(spmv_csr_dev *m, int col_lo, int col_hi, long long *c
     // (the sub-handles are ordinary handles: plans, block cuts, AUTO -- but no placement search of their own)
     const int keep = g_place_tries;
     g_place_tries = 0;
-    int rc = csr_upload_impl<T>(m->M_total, m->N, rp_own.data(), c_own.data(), v_own.data(), m->row0, m->row0 + Ml, &m->own_part);
-    if (!rc) rc = csr_upload_impl<T>(m->M_total, m->N, rp_halo.data(), c_halo.data(), v_halo.data(), m->row0, m->row0 + Ml, &m->halo_part);
+    int rc = csr_upload_impl<T>(m->M_total, m->N, rp_own.data(), m->row0, m->row0 + Ml, MatrixSource<T>::on_host(c_own.data(), v_own.data()), &m->own_part);
+    if (!rc) rc = csr_upload_impl<T>(m->M_total, m->N, rp_halo.data(), m->row0, m->row0 + Ml, MatrixSource<T>::on_host(c_halo.data(), v_halo.data()), &m->halo_part);
     g_place_tries = keep;
     if (rc) {
         spmv_hip_csr_free(m->own_part);

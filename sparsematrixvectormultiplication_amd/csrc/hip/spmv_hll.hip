@@ -1,6 +1,6 @@
 // spmv_hll.hip -- HLL side of the C-ABI: the flat slab, its workgroup windows and x-window plan,
 // the device builder from a resident CSR matrix, launchers, timing.  Replaces the per-hack
-// allocations and launches of /root/reference/main_cuda.cu:369-455, :545-568, :613-637, :731-744.
+// allocations and launches of the reference's main_cuda.cu, lines 369-455, 545-568, 613-637 and 731-744.
 #include "spmv_internal.hpp"
 
 #include "launch_dispatch.hpp"
@@ -138,7 +138,6 @@ long long hll_offsets(int total_rows, const std::vector<int> &mz, std::vector<lo
     return off[H];
 }
 
-// workgroup windows, small arrays and vectors of a handle whose JA / AS are already on the device
 // row_seg[r] = (first slot of row r relative to its window's even base) | (slots of the row << 16), for the
 // rows of the x-window plan's windows: what hll_lds_local's row-sum phase needs, in one word.
 __global__ __launch_bounds__(kBlock) void hll_row_segments(int num_blocks, const int4 *__restrict__ desc,
@@ -169,21 +168,57 @@ int hll_fill_row_segments(spmv_hll_dev *m) {
     return 0;
 }
 
-int hll_finish_handle(spmv_hll_dev *m, int total_rows, int N, const std::vector<long long> &off,
-                      const std::vector<int> &mz, long long true_slots, bool upload_maxnz, const int *ja_host,
-                      int matrix_rows = -1, int row0 = 0, const double *as_host = nullptr) {
-    m->M_total = matrix_rows < 0 ? total_rows : matrix_rows;
-    m->row0 = row0;
-    const int H = (int)mz.size();
+// The pattern plan (tables only) and the searches of a finished handle (upload_ops.hpp).  The placement of AS where it is
+// large and streamed by the slab's own kernels (csr_tile over the slab's rows streams its own re-ordered copy).
+// (Ahead of hll_plan_on_device: the order in which this translation unit first names build_pattern_tables<true> and
+// plan_on_device<4> is the order of their kernels in its code object.)
+void hll_upload_searches(spmv_hll_dev *m) {
+    (void)build_pattern_tables<true>(m->xw, m->M, m->slots, 8, nullptr);
+    size_t bytes = 0;
+    bool place = m->AS && (size_t)m->slots * sizeof(double) >= kPlaceMinBytes && (m->xw.blocks > 0 || !m->tiles);
+    if (place && (hipMemPtrGetInfo(m->AS, &bytes) != hipSuccess || bytes < (size_t)m->slots * sizeof(double))) {
+        (void)hipGetLastError();
+        place = false;
+    }
+    upload_searches(m, place ? &m->AS : nullptr, bytes,
+                    [m] { return hll_launch(m, SPMV_HLL_AUTO, m->x, m->y, g_stream); });
+}
+
+// x-window plan of a device-resident slab (upload_ops.hpp): the windows of hll_build_blocks at kPlanCap slots.  Returns 1
+// when the handle now carries the plan, 0 when some window lists more than kLocalLinesMax lines (caller falls back to
+// the host builder), -1 on a HIP error.
+int hll_plan_on_device(spmv_hll_dev *m, int total_rows, const std::vector<long long> &off, const std::vector<int> &mz) {
+    std::vector<int4> win;
+    hll_build_blocks(total_rows, (int)mz.size(), off.data(), mz.data(), kPlanCap, win);
+    const int W = (int)win.size();
+    auto start_of = [&](int r) { return off[r / kHack] + (long long)(r % kHack) * mz[r / kHack]; };
+    std::vector<long long> begin((size_t)W);
+    std::vector<int> len((size_t)W), count((size_t)W), nl;
+    for (int w = 0; w < W; ++w) {
+        const int r0 = win[w].x, r1 = r0 + win[w].y - 1;
+        const long long s0 = start_of(r0), end = start_of(r1) + mz[r1 / kHack];
+        if (end - (s0 & ~1LL) > kPlanCap) return 0;  // a row that alone exceeds the stage: no plan
+        begin[w] = s0;
+        len[w] = (int)(end - s0);
+        count[w] = (int)(end - (s0 & ~1LL));
+    }
+    return plan_on_device<4>(m->xw, m->JA, (size_t)off.back(), win, begin, len,
+                             [&](int w, int first, int n) { return int4{first, n, count[w], 0}; }, nl);
+}
+
+// Everything of a handle but its slab: the x-window plan, workgroup windows, small arrays, vectors, the tile plan, the
+// heuristics.  The handle's shape (M, N, M_total, row0, slots) is set; off / mz: hack offsets and row lengths on the
+// host; slab: JA / AS, bound to the handle -- on the device already (hll_from_csr), or going there first thing.  The
+// host builders (x-window plan, tile plan) ask the slab for its host view, which only then costs hll_from_csr a copy back.
+int hll_finish_handle(spmv_hll_dev *m, const std::vector<long long> &off, const std::vector<int> &mz, MatrixSource<double> &slab) {
+    const int total_rows = m->M, N = m->N, H = (int)mz.size();
+    const long long true_slots = m->slots;
     // like the CSR stream kernel: larger stages for matrices that have plenty of work
     const int cap = true_slots >= (16LL << 20) ? kHllCap : kHllCap / 2;
     std::vector<int4> hdesc;
     const long long widest =
         std::max<long long>(2 * kStreamUnit, hll_build_blocks(total_rows, H, off.data(), mz.data(), cap, hdesc));
-    m->M = total_rows;
-    m->N = N;
     m->hacks = H;
-    m->slots = true_slots;
     // what hll_lds gets: .y = rows | slots of the window (from its even base) << 16 -- the kernel then knows how much to
     // stage without first asking the hack tables (0 in the upper half: a single row of more than 65535 slots, which has
     // its own path in the kernel)
@@ -197,35 +232,32 @@ int hll_finish_handle(spmv_hll_dev *m, int total_rows, int N, const std::vector<
         d.y |= span <= 0xffff ? (int)span << 16 : 0;
     }
     m->num_blocks = (int)hdesc.size();
-    int rc = 0;
-    if (!m->hack_off) rc |= upload_array(&m->hack_off, off.data(), off.size(), 0);
-    if (!rc && upload_maxnz) rc |= upload_array(&m->maxnz, mz.data(), mz.size(), 1);
-    if (!rc) rc |= upload_array(&m->hdesc, hdesc.data(), hdesc.size(), 1);
-    if (!rc && !long_windows.empty()) {
-        rc |= upload_array(&m->long_windows, long_windows.data(), long_windows.size(), 0);
-        if (!rc) m->num_long_windows = (int)long_windows.size();
-    }
-    if (!rc) {
-        const size_t x_bytes = std::max<size_t>((size_t)N, 1) * sizeof(double) + kLineBytes;  // whole-line reads
-        hipError_t e = hipMalloc((void **)&m->x, x_bytes);
-        if (e == hipSuccess) e = hipMalloc((void **)&m->y, std::max<size_t>((size_t)m->M_total, 1) * sizeof(double));
-        if (e == hipSuccess) e = hipMemset(m->x, 0, x_bytes);
-        if (e == hipSuccess) e = hipMemset(m->y, 0, std::max<size_t>((size_t)m->M_total, 1) * sizeof(double));
-        if (e != hipSuccess) rc = fail("hipMalloc(x/y) failed: %s", hipGetErrorString(e));
-    }
     m->rest_bytes = off.size() * 8 + mz.size() * 4 + ((size_t)off[H] + kPad) * 12 + hdesc.size() * 16 +
                     long_windows.size() * 4 + ((size_t)N + (size_t)total_rows) * 8;
-    // the x-window kernel: windows of 2048 slots, 16-bit local JA (needs the slab on the host)
-    if (!rc && ja_host && g_stream_local && true_slots > 0) {
+    if (slab.col.device_view() || slab.val.device_view()) return -1;
+    // the x-window kernel (windows of 2048 slots, 16-bit local JA): its plan on the device when every window lists at
+    // most 256 lines (then the line limit would not have moved any window boundary on the host either); otherwise the
+    // host builder decides below (line-limited windows or no plan)
+    const bool want_plan = g_stream_local && true_slots > 0;
+    if (want_plan && g_plan_on_device && hll_plan_on_device(m, total_rows, off, mz) < 0) return -1;
+    if (!m->hack_off && upload_array(&m->hack_off, off.data(), off.size(), 0)) return -1;
+    if (!m->maxnz && upload_array(&m->maxnz, mz.data(), mz.size(), 1)) return -1;
+    if (upload_array(&m->hdesc, hdesc.data(), hdesc.size(), 1)) return -1;
+    if (!long_windows.empty() && upload_array(&m->long_windows, long_windows.data(), long_windows.size(), 0)) return -1;
+    m->num_long_windows = (int)long_windows.size();
+    if (alloc_vectors((void **)&m->x, (void **)&m->y, N, m->M_total, 8)) return -1;
+    if (want_plan && m->xw.blocks == 0) {
+        const int *ja = slab.col.host_view("hll_from_csr: JA download failed: %s");
+        if (!ja) return -1;
         std::vector<int4> plain;
         LocalPlan<int4> local;
         hll_build_blocks(total_rows, H, off.data(), mz.data(), 2048, plain);
-        if (hll_build_local(total_rows, N, off.data(), mz.data(), ja_host, off[H], 2048, kLocalLinesMax, plain, local))
-            rc = m->xw.upload(local);
+        if (hll_build_local(total_rows, N, off.data(), mz.data(), ja, off[H], 2048, kLocalLinesMax, plain, local) && m->xw.upload(local))
+            return -1;
     }
-    if (!rc && m->xw.blocks > 0) rc = hll_fill_row_segments(m);
+    if (m->xw.blocks > 0 && hll_fill_row_segments(m)) return -1;
     // no x-window plan (columns too scattered): the 2-D tiles over the slab's rows, padding slots included -- the
-    // rows of hack h are maxnz[h] slots each, starting at hack_off[h] + i * maxnz[h] (needs the slab on the host)
+    // rows of hack h are maxnz[h] slots each, starting at hack_off[h] + i * maxnz[h]
     // (auto: not for a skewed slab -- a hack whose rows are 16 times the mean is 32 rows of mostly padding, and tiles
     // over such rows lose to hll_lds: webbase-like stand-in, 1 M rows, 455 vs 159 us)
     bool skewed = false;
@@ -233,20 +265,18 @@ int hll_finish_handle(spmv_hll_dev *m, int total_rows, int N, const std::vector<
         const long long mean = std::max<long long>(1, off[H] / total_rows);
         for (int h = 0; h < H && !skewed; ++h) skewed = mz[(size_t)h] > 16 * mean;
     }
-    // (the plan is built on the device from the slab there; the host copies, where the caller has them, are the fallback)
-    const bool slab_at_hand = (ja_host && as_host) || (g_tile_plan_on_device && m->JA && m->AS);
-    if (!rc && !skewed && m->xw.blocks == 0 && slab_at_hand && true_slots > 0 && off[H] < 0x7fffffffLL) {
+    if (!skewed && m->xw.blocks == 0 && true_slots > 0 && off[H] < 0x7fffffffLL) {
         std::vector<int> row_begin((size_t)total_rows), row_len((size_t)total_rows);
         for (int r = 0; r < total_rows; ++r) {
             const int h = r / kHack;
             row_len[(size_t)r] = mz[(size_t)h];
             row_begin[(size_t)r] = (int)(off[(size_t)h] + (long long)(r % kHack) * mz[(size_t)h]);
         }
-        rc = csr_tiles_from_rows_f64(total_rows, m->M_total, row0, N, row_begin.data(), row_len.data(), true_slots, ja_host,
-                                     as_host, &m->tiles, m->JA, m->AS);
+        if (csr_tiles_from_rows_f64(total_rows, m->M_total, m->row0, N, row_begin.data(), row_len.data(), true_slots, slab, &m->tiles))
+            return -1;
     }
     const double mean = total_rows ? (double)true_slots / total_rows : 0.0;
-    m->lanes_per_row = std::min(32, std::max(2, pow2_floor(std::max(2, (int)(mean / 2.0 + 0.5)))));
+    m->lanes_per_row = lanes_for_mean_row(mean);
     // Mid-size slabs that get neither plan (scattered columns, below the tile plans' size): the lane-group kernel beats
     // hll_lds by 10-27 % on every such stand-in of the reference's list (thermal1-size 6.7 vs 8.4 us, thermomech_TK-size
     // 7.2 vs 9.2, cop20k_A-size 19.1 vs 21.5, mac_econ-size 10.9 vs 12.2, amazon0302-size 12.0 vs 13.4;
@@ -257,24 +287,12 @@ int hll_finish_handle(spmv_hll_dev *m, int total_rows, int N, const std::vector<
     m->auto_variant = SPMV_HLL_LDS;
     if (m->xw.blocks == 0 && !m->tiles && true_slots < (20LL << 20) && widest_hack <= std::max(64.0, 8.0 * mean))
         m->auto_variant = SPMV_HLL_SUBWAVE;
-    return rc;
+    return 0;
 }
+
+using HllGuard = HandleGuard<spmv_hll_dev, spmv_hip_hll_free>;
 
 }  // namespace
-
-// The pattern plan (tables only) and the searches of a finished handle (upload_ops.hpp).  The placement of AS where it is
-// large and streamed by the slab's own kernels (csr_tile over the slab's rows streams its own re-ordered copy).
-static void hll_upload_searches(spmv_hll_dev *m) {
-    (void)build_pattern_tables<true>(m->xw, m->M, m->slots, 8, nullptr);
-    size_t bytes = 0;
-    bool place = m->AS && (size_t)m->slots * sizeof(double) >= kPlaceMinBytes && (m->xw.blocks > 0 || !m->tiles);
-    if (place && (hipMemPtrGetInfo(m->AS, &bytes) != hipSuccess || bytes < (size_t)m->slots * sizeof(double))) {
-        (void)hipGetLastError();
-        place = false;
-    }
-    upload_searches(m, place ? &m->AS : nullptr, bytes,
-                    [m] { return hll_launch(m, SPMV_HLL_AUTO, m->x, m->y, g_stream); });
-}
 
 // Host-only self-check of what HLL upload precomputes (flat slab offsets, workgroup windows, the
 // x-window plan); needs no device.  stats (optional, 4 ints): gather windows, x-window windows
@@ -349,32 +367,6 @@ extern "C" int spmv_hip_hll_plan_check(const HLLMatrix *hll, int total_rows, int
     return guarded("hll_plan_check", [&] { return spmv_hip_hll_plan_check_body(hll, total_rows, N, stats); });
 }
 
-namespace {
-
-// x-window plan of a device-resident slab (upload_ops.hpp): the windows of hll_build_blocks at kPlanCap slots.  Returns 1
-// when the handle now carries the plan, 0 when some window lists more than kLocalLinesMax lines (caller falls back to
-// the host builder), -1 on a HIP error.
-int hll_plan_on_device(spmv_hll_dev *m, int total_rows, const std::vector<long long> &off, const std::vector<int> &mz) {
-    std::vector<int4> win;
-    hll_build_blocks(total_rows, (int)mz.size(), off.data(), mz.data(), kPlanCap, win);
-    const int W = (int)win.size();
-    auto start_of = [&](int r) { return off[r / kHack] + (long long)(r % kHack) * mz[r / kHack]; };
-    std::vector<long long> begin((size_t)W);
-    std::vector<int> len((size_t)W), count((size_t)W), nl;
-    for (int w = 0; w < W; ++w) {
-        const int r0 = win[w].x, r1 = r0 + win[w].y - 1;
-        const long long s0 = start_of(r0), end = start_of(r1) + mz[r1 / kHack];
-        if (end - (s0 & ~1LL) > kPlanCap) return 0;  // a row that alone exceeds the stage: no plan
-        begin[w] = s0;
-        len[w] = (int)(end - s0);
-        count[w] = (int)(end - (s0 & ~1LL));
-    }
-    return plan_on_device<4>(m->xw, m->JA, (size_t)off.back(), win, begin, len,
-                             [&](int w, int first, int n) { return int4{first, n, count[w], 0}; }, nl);
-}
-
-}  // namespace
-
 // Hacks [hack0, hack1) of the matrix, i.e. rows [32 hack0, min(32 hack1, total_rows)): one
 // rank's share under the reference's hack partitioner (prepare_thread_distribution_hll,
 // src/hll_matrix.c:410-540); y stays full length, the kernels write this handle's rows.
@@ -422,23 +414,15 @@ static int spmv_hip_hll_upload_part_body(const HLLMatrix *hll, int total_rows, i
         memcpy(&ja[(size_t)off[h]], b->JA, s * sizeof(int));
         memcpy(&as[(size_t)off[h]], b->AS, s * sizeof(double));
     }
-    spmv_hll_dev *m = new (std::nothrow) spmv_hll_dev();
+    HllGuard guard(new (std::nothrow) spmv_hll_dev());
+    spmv_hll_dev *m = guard.h;
     if (!m) return fail("hll_upload: out of host memory");
-    int rc = upload_array(&m->JA, ja.data(), ja.size(), 0);
-    if (!rc) rc |= upload_array(&m->AS, as.data(), as.size(), 0);
-    int planned = 0;  // the x-window plan on the device where it applies, else by the host builder from `ja`
-    if (!rc && g_stream_local && g_plan_on_device && true_slots > 0) {
-        planned = hll_plan_on_device(m, rows, off, mz);
-        if (planned < 0) rc = -1;
-    }
-    if (!rc) rc |= hll_finish_handle(m, rows, N, off, mz, true_slots, true, planned ? nullptr : ja.data(), total_rows, row0,
-                                     as.data());
-    if (rc) {
-        spmv_hip_hll_free(m);
-        return -1;
-    }
+    m->M = rows, m->N = N, m->M_total = total_rows, m->row0 = row0, m->slots = true_slots;
+    MatrixSource<double> slab = MatrixSource<double>::on_host(ja.data(), as.data());
+    slab.bind(&m->JA, &m->AS, 0, ja.size(), 0);
+    if (hll_finish_handle(m, off, mz, slab)) return -1;
     hll_upload_searches(m);
-    *out = m;
+    *out = guard.release();
     return 0;
 }
 
@@ -462,71 +446,42 @@ static int spmv_hip_hll_from_csr_body(const spmv_csr_dev *csr, spmv_hll_dev **ou
         ((csr->row0 + csr->M_local) % kHack != 0 && csr->row0 + csr->M_local != csr->M_total))
         return fail("hll_from_csr: needs a whole fp64 CSR matrix (or a row block cut on hack boundaries)");
     const int M = csr->M_local, N = csr->N, H = (M + kHack - 1) / kHack;
-    spmv_hll_dev *m = new (std::nothrow) spmv_hll_dev();
+    HllGuard guard(new (std::nothrow) spmv_hll_dev());
+    spmv_hll_dev *m = guard.h;
     if (!m) return fail("hll_from_csr: out of host memory");
     std::vector<int> mz((size_t)H, 0);
     std::vector<long long> off;
-    long long true_slots = 0;
-    int rc = 0;
-    do {
-        hipError_t e = hipMalloc((void **)&m->maxnz, ((size_t)H + 1) * sizeof(int));
-        if (e != hipSuccess) { rc = fail("hipMalloc(maxnz) failed: %s", hipGetErrorString(e)); break; }
-        if (H > 0) {
-            hipLaunchKernelGGL(hll_hack_maxnz, dim3((H + kBlock - 1) / kBlock), dim3(kBlock), 0, g_stream, M, H,
-                               csr->row_ptr, m->maxnz);
-            e = hipMemcpyAsync(mz.data(), m->maxnz, (size_t)H * sizeof(int), hipMemcpyDeviceToHost, g_stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-            if (e != hipSuccess) { rc = fail("hll_from_csr: maxnz pass failed: %s", hipGetErrorString(e)); break; }
-        }
-        const long long S = hll_offsets(M, mz, off, true_slots);  // H-sized scan on the host
-        if (S > (1LL << 40)) { rc = fail("hll_from_csr: %lld padded slots is unreasonable", S); break; }
-        e = hipMalloc((void **)&m->JA, ((size_t)S + kPad) * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void **)&m->AS, ((size_t)S + kPad) * sizeof(double));
-        if (e == hipSuccess) e = hipMemsetAsync(m->JA, 0, ((size_t)S + kPad) * sizeof(int), g_stream);
-        if (e == hipSuccess) e = hipMemsetAsync(m->AS, 0, ((size_t)S + kPad) * sizeof(double), g_stream);
-        if (e != hipSuccess) { rc = fail("hll_from_csr: slab allocation failed: %s", hipGetErrorString(e)); break; }
-        rc = upload_array(&m->hack_off, off.data(), off.size(), 0);
-        if (rc) break;
-        if (M > 0) {
-            hipLaunchKernelGGL((hll_fill_from_csr<double>), dim3((M + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock),
-                               0, g_stream, M, csr->row_ptr, csr->col, (const double *)csr->val, m->hack_off,
-                               m->maxnz, m->JA, m->AS);
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-            if (e != hipSuccess) { rc = fail("hll_from_csr: fill failed: %s", hipGetErrorString(e)); break; }
-        }
-        // the x-window plan: on the device when every 2048-slot window lists at most 256 lines (then the
-        // line limit would not have moved any window boundary on the host either); otherwise the host
-        // builder decides (line-limited windows or no plan), from one D2H copy of JA
-        int planned = 0;
-        if (g_stream_local && g_plan_on_device && S > 0) {
-            planned = hll_plan_on_device(m, M, off, mz);
-            if (planned < 0) { rc = -1; break; }
-        }
-        std::vector<int> ja_host;
-        std::vector<double> as_host;
-        if (g_stream_local && S > 0 && !planned) {
-            ja_host.resize((size_t)S);
-            e = hipMemcpy(ja_host.data(), m->JA, (size_t)S * sizeof(int), hipMemcpyDeviceToHost);
-            if (e != hipSuccess) { rc = fail("hll_from_csr: JA download failed: %s", hipGetErrorString(e)); break; }
-            // (the values too when the tile plan of a slab without an x-window plan is to be built on the HOST:
-            // "tile_plan_on_device" 0; the device builder reads the slab where it is)
-            if (!g_tile_plan_on_device && g_stream_tile != 0 &&
-                (g_stream_tile == 1 || (long long)M >= kTileMinRows || S >= kTileMidEntries)) {
-                as_host.resize((size_t)S);
-                e = hipMemcpy(as_host.data(), m->AS, (size_t)S * sizeof(double), hipMemcpyDeviceToHost);
-                if (e != hipSuccess) { rc = fail("hll_from_csr: AS download failed: %s", hipGetErrorString(e)); break; }
-            }
-        }
-        rc = hll_finish_handle(m, M, N, off, mz, true_slots, false, ja_host.empty() ? nullptr : ja_host.data(),
-                               csr->M_total, csr->row0, as_host.empty() ? nullptr : as_host.data());
-    } while (0);
-    if (rc) {
-        spmv_hip_hll_free(m);
-        return -1;
+    hipError_t e = hipMalloc((void **)&m->maxnz, ((size_t)H + 1) * sizeof(int));
+    if (e != hipSuccess) return fail("hipMalloc(maxnz) failed: %s", hipGetErrorString(e));
+    if (H > 0) {
+        hipLaunchKernelGGL(hll_hack_maxnz, dim3((H + kBlock - 1) / kBlock), dim3(kBlock), 0, g_stream, M, H,
+                           csr->row_ptr, m->maxnz);
+        e = hipMemcpyAsync(mz.data(), m->maxnz, (size_t)H * sizeof(int), hipMemcpyDeviceToHost, g_stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
+        if (e != hipSuccess) return fail("hll_from_csr: maxnz pass failed: %s", hipGetErrorString(e));
     }
+    m->M = M, m->N = N, m->M_total = csr->M_total, m->row0 = csr->row0;
+    const long long S = hll_offsets(M, mz, off, m->slots);  // H-sized scan on the host
+    if (S > (1LL << 40)) return fail("hll_from_csr: %lld padded slots is unreasonable", S);
+    e = hipMalloc((void **)&m->JA, ((size_t)S + kPad) * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void **)&m->AS, ((size_t)S + kPad) * sizeof(double));
+    if (e == hipSuccess) e = hipMemsetAsync(m->JA, 0, ((size_t)S + kPad) * sizeof(int), g_stream);
+    if (e == hipSuccess) e = hipMemsetAsync(m->AS, 0, ((size_t)S + kPad) * sizeof(double), g_stream);
+    if (e != hipSuccess) return fail("hll_from_csr: slab allocation failed: %s", hipGetErrorString(e));
+    if (upload_array(&m->hack_off, off.data(), off.size(), 0)) return -1;
+    if (M > 0) {
+        hipLaunchKernelGGL((hll_fill_from_csr<double>), dim3((M + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock),
+                           0, g_stream, M, csr->row_ptr, csr->col, (const double *)csr->val, m->hack_off,
+                           m->maxnz, m->JA, m->AS);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
+        if (e != hipSuccess) return fail("hll_from_csr: fill failed: %s", hipGetErrorString(e));
+    }
+    MatrixSource<double> slab;  // on the device only: S slots (+ kPad zeroed) in the handle's JA / AS
+    slab.bind(&m->JA, &m->AS, 0, (size_t)S, kPad);
+    if (hll_finish_handle(m, off, mz, slab)) return -1;
     hll_upload_searches(m);
-    *out = m;
+    *out = guard.release();
     return 0;
 }
 

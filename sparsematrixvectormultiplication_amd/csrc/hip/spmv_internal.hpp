@@ -507,14 +507,6 @@ int transpose_core(int value_bytes, const CsrView &A, DevCsr &At, std::vector<in
 // ms[0..3] -- check / canonical / symbolic / numeric -- of spmv_hip_csr_add)
 int spadd_core(int value_bytes, const CsrView *a, double alpha, const CsrView *b, double beta, int method, int lanes,
                int long_row, DevCsr &C, std::vector<int> &rp_host, long long *stats, double *ms);
-// spmv_csr.hip: tile plans alone for rows given as (first entry, length) over host arrays (an HLL slab's rows);
-// *out = NULL when the rows get no plan
-// (col / val: host copies of the rows' arrays, or NULL when d_col / d_val -- the same arrays on the device -- are given
-// and the plan is built there)
-int csr_tiles_from_rows_f64(int M_local, int M_total, int row0, int N, const int *row_begin, const int *row_len,
-                            long long entries, const int *col, const double *val, spmv_csr_dev **out,
-                            const int *d_col = nullptr, const double *d_val = nullptr);
-
 // spmv_csr.hip: the line lists of the handle's x-window plan on the host: ld[b] = {first id in `lines`, ids}, base[b] =
 // what block b adds to its ids (shared lists count from the block's first line; 0 otherwise)
 int csr_lines_to_host(const spmv_csr_dev *m, std::vector<int2> &ld, std::vector<int> &lines, std::vector<int> &base);

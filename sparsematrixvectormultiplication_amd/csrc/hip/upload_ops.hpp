@@ -1,6 +1,7 @@
-// upload_ops.hpp -- what CSR upload (spmv_csr.hip) and HLL upload (spmv_hll.hip) share: the x-window plan built on the
-// device, the pattern plan's tables, and the searches that time the finished handle's own kernel (settle, the pattern
-// plan, the placement of the value array).
+// upload_ops.hpp -- what CSR upload (spmv_csr.hip) and HLL upload (spmv_hll.hip) share: the source of a matrix's entry
+// arrays (where they live, host or device, and the one way to the other side), the guard of a handle under
+// construction, the vectors, the x-window plan built on the device, the pattern plan's tables, and the searches that
+// time the finished handle's own kernel (settle, the pattern plan, the placement of the value array).
 //
 // A step that upload may do without (the pattern plan, a search) never costs the handle: when it fails, it leaves
 // nothing half-built and clears the last HIP error, which the next launch would otherwise report as its own.
@@ -10,6 +11,92 @@
 #include "spmv_internal.hpp"
 
 #include "plan_kernels.hpp"
+
+// One array of a matrix on its way into a handle, and where it lives right now: with the caller on the host (`host`), on
+// the device in the handle's field (*field: adopted from the caller, uploaded by an earlier phase, or filled by a device
+// builder), or both.  A phase of upload asks for the side it needs; it never tests the pointers itself.
+template <typename E>
+struct UploadSource {
+    const E *host = nullptr;    // the caller's array; nullptr: the array exists on the device only
+    E *adopted = nullptr;       // a device array (count + pad elements, the pad zeroed) that the handle takes over
+    E **field = nullptr;        // where the handle keeps the device array; nullptr: not bound to a handle yet
+    size_t count = 0, pad = 0;  // elements, and the zeroed elements behind them on the device
+    bool kept = false;
+    std::vector<E> back;        // the one copy back from the device (host_view)
+
+    // an adopted array is the caller's again unless the handle was handed out (keep): declared behind the handle's guard,
+    // the source goes first and takes the array out of the handle before the guard frees it
+    ~UploadSource() { if (field && adopted && !kept) *field = nullptr; }
+    // elements [first, first + n) of the caller's array go to *f (an adopted array holds exactly those)
+    void bind(E **f, size_t first, size_t n, size_t pad_behind) {
+        field = f;
+        if (host) host += first;
+        count = n, pad = pad_behind;
+        if (adopted) *f = adopted;
+    }
+    // The array on the host: the caller's, or ONE copy back from the device, kept until the upload ends.  nullptr: the
+    // copy failed and `message` is the error (it may print HIP's own text as its one %s).
+    const E *host_view(const char *message) {
+        if (host) return host;
+        if (!back.empty()) return back.data();
+        back.resize(std::max<size_t>(count, 1));
+        const hipError_t e = count ? hipMemcpy(back.data(), *field, count * sizeof(E), hipMemcpyDeviceToHost) : hipSuccess;
+        if (e == hipSuccess) return back.data();
+        back.clear();
+        fail(message, hipGetErrorString(e));
+        return nullptr;
+    }
+    // the array on the device, in the handle's field: uploaded once, a no-op when it is there already
+    int device_view() { return *field ? 0 : upload_array(field, host, count, pad); }
+};
+
+// The two entry arrays of a matrix: col / val of a CSR handle, JA / AS of an HLL slab.
+template <typename V>
+struct MatrixSource {
+    UploadSource<int> col;
+    UploadSource<V> val;
+
+    static MatrixSource on_host(const int *col_host, const V *val_host) { MatrixSource s; s.col.host = col_host, s.val.host = val_host; return s; }
+    static MatrixSource adopting(int *d_col, V *d_val) { MatrixSource s; s.col.adopted = d_col, s.val.adopted = d_val; return s; }
+    void bind(int **col_field, V **val_field, size_t first, size_t n, size_t pad_behind) {
+        col.bind(col_field, first, n, pad_behind);
+        val.bind(val_field, first, n, pad_behind);
+    }
+    bool on_host() const { return col.host && val.host; }
+    bool on_device() const { return *col.field && *val.field; }
+    void keep() { col.kept = val.kept = true; }  // the handle is handed out: it owns what it adopted
+};
+
+// spmv_csr.hip: tile plans alone for rows given as (first entry, length) over the arrays `slab` (an HLL slab's rows): built
+// on the device where the slab is there, else from its host view; *out = NULL when the rows get no plan
+int csr_tiles_from_rows_f64(int M_local, int M_total, int row0, int N, const int *row_begin, const int *row_len,
+                            long long entries, MatrixSource<double> &slab, spmv_csr_dev **out);
+
+// Owns a handle from `new` until it is handed out (release); on every other way out the handle is freed.
+template <typename H, void (*Free)(H *)>
+struct HandleGuard {
+    H *h;
+    explicit HandleGuard(H *handle) : h(handle) {}
+    HandleGuard(const HandleGuard &) = delete;
+    ~HandleGuard() { if (h) Free(h); }
+    H *release() { return std::exchange(h, nullptr); }
+};
+
+// The vectors of a handle, zeroed.  x is read in whole 128-byte lines by the x-window kernels: room for the tail of the
+// last one.
+inline int alloc_vectors(void **x, void **y, int N, int M_total, int value_bytes) {
+    const size_t x_bytes = std::max<size_t>((size_t)N, 1) * (size_t)value_bytes + kLineBytes;
+    const size_t y_bytes = std::max<size_t>((size_t)M_total, 1) * (size_t)value_bytes;
+    hipError_t e = hipMalloc(x, x_bytes);
+    if (e == hipSuccess) e = hipMalloc(y, y_bytes);
+    if (e == hipSuccess) e = hipMemset(*x, 0, x_bytes);
+    if (e == hipSuccess) e = hipMemset(*y, 0, y_bytes);
+    return e == hipSuccess ? 0 : fail("hipMalloc(x/y) failed: %s", hipGetErrorString(e));
+}
+
+// lanes per row for the lane-group (SUBWAVE) kernels: about half the mean row length, rounded down to a power of two, so
+// that a typical row takes 1-2 passes
+inline int lanes_for_mean_row(double mean) { return std::min(32, std::max(2, pow2_floor(std::max(2, (int)(mean / 2.0 + 0.5))))); }
 
 namespace {
 

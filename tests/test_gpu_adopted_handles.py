@@ -21,14 +21,14 @@ moves none.
 
 The targets, each the smallest that reaches its branch of csr_upload_impl's adopt path, the branch asserted from info():
   T1 x-window plan, built on the device from the adopted columns -- and under plan_on_device = 0 by the host builder on
-     the columns copied back (col_back);
+     the columns copied back (the source's host view, upload_ops.hpp);
   T2 a band with rows that alone touch more than 256 lines: the device builder declines, the host builder hands those
      rows to the split-row kernels (csr_plan_check's sixth value, checked on the host).  banded_csr's far_frac moves a
      quarter of a row's entries half a matrix away, which a row of a dozen entries cannot turn into more than 256 lines,
      and the host builder hands rows over from 2^20 entries on only: hence 66 000 rows and a few wide rows;
   T3 a long row inside an x-window matrix;
-  T4 tile plan, ordinary tier, built by host threads and by the device builder on the arrays copied back (col_copy /
-     val_copy);
+  T4 tile plan, ordinary tier, built by host threads and by the device builder on the arrays copied back (the same host
+     view);
   T5 tile plan with the long rows' tier;  T6 tile plan on an expanded x;
   T7 no plan, the lane-group kernel;  T8 rows split by skew (from 2^20 entries on);
   T9 edges: no entries, 1 x 1, only the last row holds entries, one column.
