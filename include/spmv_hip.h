@@ -1039,6 +1039,44 @@ int spmv_hip_precond_apply_multi(const spmv_precond *P, int k, const void *R_hos
 int spmv_hip_csr_pbicgstab(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, double tol,
                            const int *bounds, const void *b_host, void *x_host, double *rr_hist, int *info,
                            float *ms_total);
+/* k independent right-preconditioned BiCGSTAB recurrences for a square, possibly nonsymmetric A, x0 = 0, r^_j = b_j,
+ * sharing the two SpMMs of a step and the k-wide apply: the loop of spmv_hip_csr_pbicgstab with one alpha, omega, beta,
+ * rho, stop state, status, half-step flag and step count per column (not block BiCGSTAB: no k x k coefficient
+ * matrices), in the layout of spmv_hip_csr_cg_multi.  B, X and every loop vector are row-major n x k:
+ *   X = 0;  R = R^ = P = B;  P^ = M^-1 P;  rho_j = rr0_j = r_j.r_j
+ *   each step:  V = A P^ (one SpMM);  alpha_j = rho_j / r^_j.v_j;  s_j = r_j - alpha_j v_j;  S^ = M^-1 S
+ *               (s_j.s_j <= tol^2 rr0_j: x_j += alpha_j p^_j, r_j = s_j, column j stops at the half step)
+ *               T = A S^ (one SpMM);  omega_j = t_j.s_j / t_j.t_j;  x_j += alpha_j p^_j + omega_j s^_j
+ *               r_j = s_j - omega_j t_j;  rho'_j = r^_j.r_j;  rr_j = r_j.r_j
+ *               beta_j = (rho'_j / rho_j) (alpha_j / omega_j);  rho_j = rho'_j
+ *               p_j = r_j + beta_j (p_j - omega_j v_j);  P^ = M^-1 P
+ * The products are spmv_hip_csr_spmm_on on library-owned P^ and S^ (N x k); there is no `variant`: the SpMM has none
+ * and k = 1 is the handle's AUTO launch.  With a communicator P^ and S^ are all-gathered with the row bounds scaled by
+ * k (two exchanges per step) and every dot product is all-gathered and added in rank order, as in
+ * spmv_hip_csr_cg_multi; there is no halo exchange variant.
+ * P: NULL (P^ is P and S^ is S), JACOBI (fused into the s and p updates), BLOCK_JACOBI, FSAI, AMG or CHEBYSHEV (the
+ * k-wide apply of spmv_hip_precond_apply_multi_on after them).  SSOR and ILU0 are refused: their triangular solves take
+ * one right-hand side.
+ * Column j's sums add in an order that does not depend on j: permuting the columns of B permutes X, the history, steps,
+ * status and half_step bit for bit, and two calls give the same bits.  k = 1 agrees with spmv_hip_csr_pbicgstab to
+ * rounding, not bit for bit: that solver sums 16-byte pieces of rows, this one row by row.
+ * Per column, the rules of spmv_hip_csr_bicgstab: b_j = 0 converges at step 0 with x_j = 0; s_j.s_j <= tol^2 rr0_j is a
+ * converged half step (the history holds s.s, half_step[j] = 1); r_j.r_j <= tol^2 rr0_j converges; r^.v = 0, r^.r' = 0
+ * or a non-finite value is BREAKDOWN_RHO; t.s = 0, t.t = 0 or a non-finite value is BREAKDOWN_OMEGA.  A breakdown
+ * before the update leaves x_j at the last full iterate and does not count the step.  A stopped column keeps its x, r,
+ * s and p, its history repeats its last value, it still rides in the SpMMs and the applies, and nothing it holds, a NaN
+ * included, reaches another column.
+ * tol = 0: exactly `iters` steps, no host synchronisation; tol > 0: the host reads one device word every 16 steps and
+ * ends the loop once no column is active.
+ * B_host: M_total x k row-major, values of the handle's dtype (a rank reads its own rows).
+ * Out (all optional but ms_total): X_host M_total x k; rr_hist (iters + 1) x k, r.r per column before step 1 and after
+ * every step; steps[k]; status[k] (SPMV_BICG_*); half_step[k]; *ms_total device time of the loop.
+ * -1 (the HIP error state stays clean, the handle still works): k < 1 or k > 64, a non-square matrix, a tiles-only
+ * handle, n*k beyond int range, iters < 0, tol < 0 or not finite, a communicator without bounds, a row-range handle
+ * without a communicator, a P whose rows, row0 or dtype differ from the handle's, a P of kind SSOR or ILU0. */
+int spmv_hip_csr_bicgstab_multi(spmv_csr_dev *m, const spmv_precond *P, int k, int iters, double tol, const int *bounds,
+                                const void *B_host, void *X_host, double *rr_hist, int *steps, int *status,
+                                int *half_step, float *ms_total);
 /* MINRES (Paige and Saunders 1975) for (A - shift I) x = b with a symmetric, possibly indefinite A and an optional
  * symmetric positive definite preconditioner M (P = NULL: y is r2 itself), x0 = 0.  One SpMV per step through the
  * handle's launch for `variant` on library-owned v, short recurrences, fixed-order device reductions in double, fp64

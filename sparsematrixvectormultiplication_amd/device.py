@@ -735,6 +735,34 @@ class CsrDevice(_Handle):
             _check(nat.lib().spmv_hip_csr_pbicgstab(self.h, precond.h, *args), "spmv_hip_csr_pbicgstab")
         return x, hist, {"steps": int(info[0]), "status": int(info[1]), "half_step": int(info[2])}, float(ms.value)
 
+    def bicgstab_multi(self, B, iters, tol=0.0, precond=None, bounds=None):
+        """k independent right-preconditioned BiCGSTAB recurrences from x0 = 0 that share the two SpMMs of a step
+        (spmv_hip_csr_bicgstab_multi), for the k columns of a C-contiguous B (M x k, 1 <= k <= 64) of the handle's
+        dtype and a square, possibly nonsymmetric A.  precond: a Jacobi, block-Jacobi, FSAI, AMG or Chebyshev
+        Preconditioner of this handle, or None; SSOR and ILU(0) take one right-hand side and are refused.  Every
+        column stops on its own, by the rules of bicgstab; tol > 0 also ends the loop early once every column has
+        stopped.  Returns (X (M, k), r.r history (iters + 1, k), info {"steps", "status" (BICG_*), "half_step"}: int
+        arrays [k], ms)."""
+        B = _check_columns(B, self.M, self.dtype, "B", "handle")
+        _check_iters_tol(iters, tol)
+        if precond is not None:
+            self._check_precond(precond)
+        k = B.shape[1]
+        X = np.zeros((self.M, k), dtype=self.dtype)
+        hist = np.zeros((int(iters) + 1, k))
+        steps = np.zeros(k, dtype=np.int32)
+        status = np.zeros(k, dtype=np.int32)
+        half = np.zeros(k, dtype=np.int32)
+        ms = C.c_float(0)
+        _check(nat.lib().spmv_hip_csr_bicgstab_multi(self.h, None if precond is None else precond.h, int(k), int(iters),
+                                                     float(tol), _bounds_arg(bounds),
+                                                     B.ctypes.data_as(C.c_void_p), X.ctypes.data_as(C.c_void_p),
+                                                     hist.ctypes.data_as(nat.c_double_p),
+                                                     steps.ctypes.data_as(nat.c_int_p), status.ctypes.data_as(nat.c_int_p),
+                                                     half.ctypes.data_as(nat.c_int_p), C.byref(ms)),
+               "spmv_hip_csr_bicgstab_multi")
+        return X, hist, {"steps": steps, "status": status, "half_step": half}, float(ms.value)
+
     def minres(self, b, iters, tol=0.0, shift=0.0, precond=None, variant=CSR_AUTO, bounds=None):
         """MINRES from x0 = 0 (spmv_hip_csr_minres) for (A - shift I) x = b with a symmetric, possibly indefinite A:
         one SpMV per step, a residual norm that never grows.  precond: a Preconditioner of this handle that is
