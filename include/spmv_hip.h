@@ -1171,6 +1171,59 @@ int spmv_hip_lobpcg_gram(long long n, int k, int nb, const void *const *d_S, con
                          double *GB_host, double *GA_host);
 int spmv_hip_lobpcg_update(long long n, int k, int nb, const void *const *d_S, const void *const *d_AS,
                            const double *C_host, const double *Cp_host, void *d_X, void *d_P, void *d_AX, void *d_AP);
+/* Restarted GMRES(m) (Saad and Schultz 1986) for a square, possibly nonsymmetric A, right-preconditioned, x0 = 0.  It
+ * minimises the residual over the Krylov space of a cycle, so the residual estimate never grows inside a cycle, and it
+ * cannot break down on a nonsingular matrix.  One SpMV per step through the handle's launch for `variant`, one apply of
+ * P (any kind; NULL: none), classical Gram-Schmidt done twice (CGS2), always: no modified Gram-Schmidt, no switch.
+ *   x = 0;  rr0 = b.b;  hist[0] = rr0;  t = 0
+ *   rr0 == 0: CONVERGED at step 0.  rr0 not finite: BREAKDOWN at step 0.  (x = 0 either way, no cycle starts)
+ *   cycle:
+ *     r = b - A x  (the first cycle: r = b, no product);  beta = sqrt(r.r)
+ *     beta not finite: BREAKDOWN.  beta == 0: CONVERGED.
+ *     v_0 = r / beta;  g = (beta, 0, ..., 0)
+ *     for j = 0 .. restart - 1 while t < iters:
+ *        z = M^-1 v_j  (P = NULL: z is v_j itself, no copy);  w = A z
+ *        h  = V_j^T w;  w = w - V_j h            (V_j = [v_0 .. v_j])
+ *        h' = V_j^T w;  w = w - V_j h';  ww = w.w  (in the same pass);  h = h + h'
+ *        eta = sqrt(ww)
+ *        the rotations 0 .. j - 1 applied to the column (h_0 .. h_j, eta):
+ *           (h_i, h_{i+1}) = (c_i h_i + s_i h_{i+1}, -s_i h_i + c_i h_{i+1});  d = hypot(h_j, eta)
+ *        d == 0 or anything not finite: BREAKDOWN, the step is not counted
+ *        c_j = h_j / d;  s_j = eta / d;  h_j = d;  g_{j+1} = -s_j g_j;  g_j = c_j g_j;  t = t + 1;  hist[t] = g_{j+1}^2
+ *        hist[t] <= tol^2 rr0: CONVERGED  (tol = 0: only at exactly 0)
+ *        v_{j+1} = w / eta  (eta == 0 gives g_{j+1} == 0, which has converged: no division by zero)
+ *     the close of the cycle with its J counted columns (J = 0: nothing):
+ *        R y = g by back substitution in double;  u = V_{J-1} y;  x = x + M^-1 u  (P = NULL: x = x + u)
+ *     stop on CONVERGED, BREAKDOWN or t == iters (RAN_ALL); else the next cycle
+ * Vectors have the handle's dtype (fp64 or fp32); every sum and scalar is fp64.  The Hessenberg column, the rotations,
+ * g and the stop state live on the device.  An update w - V h adds its terms in index order in double and rounds each
+ * value once; a dot product adds in the fixed order of the other solvers, which depends on n alone and not on
+ * restart or on the column: two calls give the same bits, and so do two values of restart that both cover iters.
+ * hist[t] is the recurrence's ||b - A x_t||^2 (the true residual's also with P: the preconditioner is on the right).
+ * After a stop the history repeats its last value.  x only ever receives the update of fully counted columns: a
+ * breakdown leaves it at the iterate of the last counted step and no NaN is written into it.
+ * The host reads the stop state once per cycle, after the cycle's last step; nothing synchronises inside a cycle, and a
+ * stopped solve's remaining steps of that cycle return at once.  tol = 0 reads as often.
+ * The basis (restart + 1 vectors, or iters + 1 when that is fewer) is allocated per call.
+ * b_host: M_total values of the handle's dtype.  Out (all optional): x_host M_total values; rr_hist [iters + 1];
+ * info[3] = {steps counted, status (SPMV_GMRES_*), cycles started}; *ms_total device time of the solve, its reads
+ * included.
+ * -1 (the HIP error state stays clean, the handle still works): NULL m or b_host, restart outside [1, 64], iters < 0,
+ * tol < 0 or not finite, a non-square, row-range or tiles-only handle, an active communicator, a P whose rows, row0
+ * or dtype differ from the handle's, a failed allocation.
+ *   spmv_hip_gmres_dots    the dot-product pass alone on device arrays: basis vector i at d_V + i ld elements, n values
+ *                          each (the ld - n elements behind them are not read) -> h_out_host[i] = v_i.w.  Synchronous.
+ *   spmv_hip_gmres_update  the update pass alone: w = w - sum_i h_host[i] v_i in place; *ww_out_host (optional) = w.w of
+ *                          what was stored.  Synchronous.  Both: -1 for a NULL array, value_bytes not 4 or 8, n < 0,
+ *                          nvec outside [1, 64], ld < n, ld * value_bytes not a multiple of 16, an array not aligned
+ *                          to 16 bytes, an active communicator. */
+enum { SPMV_GMRES_RAN_ALL = 0, SPMV_GMRES_CONVERGED = 1, SPMV_GMRES_BREAKDOWN = 2 };
+int spmv_hip_csr_gmres(spmv_csr_dev *m, const spmv_precond *P, int variant, int restart, int iters, double tol,
+                       const void *b_host, void *x_host, double *rr_hist, int *info, float *ms_total);
+int spmv_hip_gmres_dots(const void *d_V, long long ld, int nvec, const void *d_w, long long n, int value_bytes,
+                        double *h_out_host);
+int spmv_hip_gmres_update(const void *d_V, long long ld, int nvec, const double *h_host, void *d_w, long long n,
+                          int value_bytes, double *ww_out_host);
 int spmv_hip_csr_split_interior(spmv_csr_dev *m, long long *counts);
 /* N4 overlap below block granularity (round 3).  On a KKT-coupled cut every block also lists lines of the coupling block,
  * which another rank owns: no interior BLOCKS -- but 13 of a row's 28 entries have their column in the rank's own range.

@@ -15,6 +15,7 @@ from .host import (HACK_SIZE, ITERATION_SKIP, CsrHost, HllHost, PreMatrix,  # no
 from .device import (BICG_BREAKDOWN_OMEGA, BICG_BREAKDOWN_RHO, BICG_CONVERGED, BICG_RAN_ALL,  # noqa: F401
                      CGLS_BREAKDOWN, CGLS_CONVERGED, CGLS_RAN_ALL,  # noqa: F401
                      MINRES_BREAKDOWN, MINRES_CONVERGED, MINRES_RAN_ALL,  # noqa: F401
+                     GMRES_BREAKDOWN, GMRES_CONVERGED, GMRES_RAN_ALL, GMRES_MAX_RESTART, gmres_dots, gmres_update,  # noqa: F401
                      LOBPCG_BREAKDOWN, LOBPCG_CONVERGED, LOBPCG_RAN_ALL, lobpcg_rr, lobpcg_gram, lobpcg_update,  # noqa: F401
                      PCG_BREAKDOWN, PCG_CONVERGED, PCG_RAN_ALL, PRECOND_BLOCK_JACOBI, PRECOND_JACOBI,  # noqa: F401
                      PRECOND_AMG, PRECOND_CHEBYSHEV, PRECOND_KINDS, chebyshev_coefficients, PRECOND_FSAI, PRECOND_ILU0, PRECOND_SSOR, amg_plan, spgemm_plan, MATMUL_MS, MATMUL_STATS, ORDER_MULTICOLOR, ORDER_NATURAL, TRSV_LOWER, TRSV_NONUNIT,  # noqa: F401

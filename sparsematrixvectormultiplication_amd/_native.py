@@ -300,6 +300,12 @@ _PROTOTYPES = {
                                        c_double_p, c_double_p]),
     "spmv_hip_lobpcg_update": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                          c_double_p, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spmv_hip_csr_gmres": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p,
+                                     C.c_void_p, c_double_p, c_int_p, c_float_p]),
+    "spmv_hip_gmres_dots": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_longlong, C.c_int,
+                                      c_double_p]),
+    "spmv_hip_gmres_update": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, c_double_p, C.c_void_p, C.c_longlong,
+                                        C.c_int, c_double_p]),
     "spmv_hip_csr_cgls": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                     c_double_p, c_double_p, c_int_p, c_float_p]),
     "spmv_hip_csr_needed_ranges": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_int_p]),

@@ -1,6 +1,7 @@
 // solver_ops.hpp -- what the iterated methods on CSR handles share: csr_cg and csr_cg_multi (spmv_cg.hip), csr_pcg
 // (spmv_pcg.hip), csr_pcg_multi (spmv_pcg_multi.hip), csr_bicgstab and csr_pbicgstab (spmv_bicgstab.hip), csr_minres
-// (spmv_minres.hip), csr_cgls (spmv_cgls.hip), csr_lobpcg (spmv_lobpcg.hip) and the power iterations (spmv_comm.hip).
+// (spmv_minres.hip), csr_gmres (spmv_gmres.hip), csr_cgls (spmv_cgls.hip), csr_lobpcg (spmv_lobpcg.hip) and the power
+// iterations (spmv_comm.hip).
 // For the device: the pieces a vector kernel loads and stores, the lanes' walk over them, the fixed-order reductions
 // and the stop flags.  For the host: the frame of a solve -- the refusals the entries share (solver_check_*), the
 // buffers and events (SolverScope), the start and the end of the timed part (solver_begin, solver_finish), the grid

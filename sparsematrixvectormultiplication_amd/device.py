@@ -27,6 +27,9 @@ MINRES_RAN_ALL, MINRES_CONVERGED, MINRES_BREAKDOWN = 0, 1, 2
 # CsrDevice.lobpcg: info["status"] (SPMV_LOBPCG_* of include/spmv_hip.h); its limits
 LOBPCG_RAN_ALL, LOBPCG_CONVERGED, LOBPCG_BREAKDOWN = 0, 1, 2
 LOBPCG_MAX_K, LOBPCG_DROP = 16, 1e-10
+# CsrDevice.gmres: info["status"] (SPMV_GMRES_* of include/spmv_hip.h); the widest restart
+GMRES_RAN_ALL, GMRES_CONVERGED, GMRES_BREAKDOWN = 0, 1, 2
+GMRES_MAX_RESTART = 64
 PRECOND_JACOBI, PRECOND_BLOCK_JACOBI, PRECOND_SSOR, PRECOND_ILU0, PRECOND_FSAI, PRECOND_AMG = 1, 2, 3, 4, 5, 6
 PRECOND_CHEBYSHEV = 7
 PRECOND_KINDS = {"jacobi": PRECOND_JACOBI, "block_jacobi": PRECOND_BLOCK_JACOBI, "ssor": PRECOND_SSOR,
@@ -784,6 +787,26 @@ class CsrDevice(_Handle):
                                              C.byref(ms)), "spmv_hip_csr_minres")
         return x, hist, {"steps": int(info[0]), "status": int(info[1])}, float(ms.value)
 
+    def gmres(self, b, iters, tol=0.0, restart=30, precond=None, variant=CSR_AUTO):
+        """Restarted GMRES(restart) from x0 = 0 (spmv_hip_csr_gmres) for a square, possibly nonsymmetric A held whole
+        by this handle: one SpMV per step, classical Gram-Schmidt done twice, a residual estimate that never grows
+        inside a cycle.  restart in [1, 64].  precond: a Preconditioner of this handle of any kind, applied from the
+        right (the history stays that of the true residual), or None.  Stops once the estimate <= tol^2 times b.b
+        (tol = 0: only at exactly 0), or at a breakdown; the host reads the stop state once per cycle.  Returns (x,
+        squared residual estimate history (iters + 1), info {"steps", "status" (GMRES_*), "cycles"}, ms)."""
+        b = self._check_solve_args(b, iters, tol, precond)
+        if isinstance(restart, bool) or int(restart) != restart or not 1 <= int(restart) <= GMRES_MAX_RESTART:
+            raise ValueError(f"restart must be an integer in [1, {GMRES_MAX_RESTART}], got {restart!r}")
+        x = np.zeros(self.M, dtype=self.dtype)
+        hist = np.zeros(int(iters) + 1)
+        info = np.zeros(3, dtype=np.int32)
+        ms = C.c_float(0)
+        _check(nat.lib().spmv_hip_csr_gmres(self.h, None if precond is None else precond.h, int(variant), int(restart),
+                                            int(iters), float(tol), b.ctypes.data_as(C.c_void_p),
+                                            x.ctypes.data_as(C.c_void_p), hist.ctypes.data_as(nat.c_double_p),
+                                            info.ctypes.data_as(nat.c_int_p), C.byref(ms)), "spmv_hip_csr_gmres")
+        return x, hist, {"steps": int(info[0]), "status": int(info[1]), "cycles": int(info[2])}, float(ms.value)
+
     def lobpcg(self, k, iters, tol=0.0, precond=None, X0=None, largest=False, seed=0):
         """LOBPCG (spmv_hip_csr_lobpcg) for the k smallest (largest=True: largest) eigenpairs of a symmetric fp64 A,
         1 <= k <= 16, n >= 4 k.  precond: a Jacobi, block-Jacobi, FSAI, AMG or Chebyshev Preconditioner of this handle
@@ -961,6 +984,28 @@ def lobpcg_update(n, k, nb, d_S, d_AS, Cm, Cp, d_X, d_P, d_AX, d_AP):
                                             Cm.ctypes.data_as(nat.c_double_p), Cp.ctypes.data_as(nat.c_double_p),
                                             C.c_void_p(d_X), C.c_void_p(d_P), C.c_void_p(d_AX), C.c_void_p(d_AP)),
            "spmv_hip_lobpcg_update")
+
+
+def gmres_dots(d_V, ld, nvec, d_w, n, value_bytes):
+    """The dot-product pass of gmres alone (spmv_hip_gmres_dots) on device arrays: d_V the address of nvec basis
+    vectors of n values, ld elements apart (ld * value_bytes a multiple of 16), d_w that of w.  Returns V^T w [nvec]."""
+    h = np.zeros(max(int(nvec), 1))
+    _check(nat.lib().spmv_hip_gmres_dots(C.c_void_p(d_V), int(ld), int(nvec), C.c_void_p(d_w), int(n),
+                                         int(value_bytes), h.ctypes.data_as(nat.c_double_p)), "spmv_hip_gmres_dots")
+    return h[:int(nvec)]
+
+
+def gmres_update(d_V, ld, nvec, h, d_w, n, value_bytes, want_ww=True):
+    """The update pass of gmres alone (spmv_hip_gmres_update): w <- w - V h on device arrays, each value rounded once.
+    Returns w.w of what was stored (None when not wanted)."""
+    h = np.ascontiguousarray(h, dtype=np.float64)
+    if h.shape != (int(nvec),):
+        raise ValueError(f"h must hold {nvec} values, got shape {h.shape}")
+    ww = C.c_double(0)
+    _check(nat.lib().spmv_hip_gmres_update(C.c_void_p(d_V), int(ld), int(nvec), h.ctypes.data_as(nat.c_double_p),
+                                           C.c_void_p(d_w), int(n), int(value_bytes),
+                                           C.byref(ww) if want_ww else None), "spmv_hip_gmres_update")
+    return float(ww.value) if want_ww else None
 
 
 def _bounds_arg(bounds):
