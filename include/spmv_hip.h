@@ -290,6 +290,33 @@ int spmv_hip_csr_from_coo(int M, int N, long long nz, const int *I, const int *J
 /* the handle's CSR arrays back to the host: row_ptr[M_local + 1] rebased to 0, col[nz], val[nz] (handle's
  * dtype); any pointer may be NULL */
 int spmv_hip_csr_download(const spmv_csr_dev *m, int *row_ptr, int *col, void *val);
+/* New numbers on the handle's pattern: the handle's own nz values (a row-range handle: its own rows' entries), in the
+ * handle's dtype and in its own entry order -- the order spmv_hip_csr_download returns -- from a host array, or (_on)
+ * from a device array on `stream` (NULL: the library's), without synchronising with the host once the handle's first
+ * update has been made.
+ * After the call the handle IS the upload of (its pattern, the new values) under the plan it already has: every launch
+ * (each variant, SpMM, run_part, the solvers) gives that upload's bytes, spmv_hip_csr_download returns the new values and
+ * spmv_hip_csr_tile_digest is that upload's digest under the same knobs.  Nothing an upload decides reads a value, so
+ * spmv_hip_csr_info and spmv_hip_csr_addresses do not change: the value array is written in place, where the placement
+ * search put it; the zero entries behind it and every padding slot of a tile tier stay zero.  Non-finite values are
+ * copied like any other.  Rows may be unsorted and may repeat a (row, column) pair.
+ * Cost: one copy of nz values; a handle with tile plans also regathers the tiers' value arrays (ordinary tiles, their
+ * remainder, the long rows' and the middle tier) through source maps, one int per slot, which the handle's FIRST update
+ * builds on the host from the plan it holds (one analysis: the pattern and the plans' columns and keys come back once)
+ * and the handle keeps.  An upload that is never followed by an update allocates and runs nothing for this.
+ * Objects built FROM the handle -- a transpose, an HLL conversion, a preconditioner, a column split -- hold values of
+ * their own and do not follow.
+ * A HIP error in the middle of an update (a failed copy or launch, not a refusal) leaves `val` and the tile tiers'
+ * value arrays in an undefined mix of old and new values: upload again.
+ * -1 with the handle untouched: a NULL argument; a handle made of tile plans alone; a handle that holds a column split
+ * (spmv_hip_csr_split_columns: its parts hold values of their own.  Drop it with a split over all N columns and split
+ * again after the update). */
+int spmv_hip_csr_update_values(spmv_csr_dev *m, const void *val_host);
+int spmv_hip_csr_update_values_on(spmv_csr_dev *m, const void *d_val, void *stream);
+/* counts[2] = updates made so far, bytes of the source maps on the device (0: none needed, or no update yet);
+ * us[2] = the host time of the first update's analysis, the device time of the last update (copy and gathers; waits
+ * for it), both in microseconds. */
+int spmv_hip_csr_update_info(const spmv_csr_dev *m, long long *counts, double *us);
 /* A^T of a whole CSR handle, built on the device, as a new handle of N rows and M columns with the same dtype.
  * Row j of the result holds the entries of column j of A in ascending row order.  Entries that repeat a (row, column)
  * pair keep their order in A.  Values are moved, never combined, so the arrays are a permutation of A's: bit-exact.
@@ -729,6 +756,29 @@ int spmv_hip_trsv_solve(const spmv_trsv *T, const void *b_host, void *x_host);
 int spmv_hip_trsv_solve_on(const spmv_trsv *T, const void *d_b, void *d_x, void *stream);
 int spmv_hip_trsv_info(const spmv_trsv *T, int *info);
 void spmv_hip_trsv_free(spmv_trsv *T);
+/* New values, the symbolic work kept.  m is a handle of the object's dtype, rows and row0 with the pattern the object was
+ * built from -- normally the same handle after spmv_hip_csr_update_values.  After the call the object is, byte for byte,
+ * the one a fresh build with the same arguments on a fresh upload of m's arrays gives: spmv_hip_precond_factors, every
+ * apply and solve, the infos apart from their times, and so every solver step with it.
+ *   spmv_hip_precond_refresh  JACOBI, BLOCK_JACOBI: the device build once more into an array of its own, copied over P's
+ *                             only when no row or block was refused.  SSOR, ILU0 (either ordering): no host analysis
+ *                             and no value crosses to the host but the diagonal -- the first refresh builds, once, from
+ *                             the downloaded PATTERN the map from every entry of the canonical (and permuted) diagonal
+ *                             block to the handle entries that feed it (a repeated pair: in entry order) and from there
+ *                             to the triangles' level order, and keeps the block's pattern on the device; from then on
+ *                             a refresh gathers in fp64 (repeats added in entry order), runs the build's own ILU(0)
+ *                             launches, checks the pivots and the diagonal, and scatters with one rounding to the dtype.
+ *                             FSAI, AMG, CHEBYSHEV: refused -- their pattern, hierarchy or interval is a function of
+ *                             the values: build them again.
+ *   spmv_hip_trsv_refresh     a triangular solver, lower or upper, unit or not, the same way
+ * All or nothing: the numbers are made in scratch arrays and published only behind the checks; a zero pivot, a zero or
+ * non-finite diagonal or a singular block is refused in the words of the build's refusal, with its row, and leaves the
+ * object applying exactly as before.  The pattern is checked on every call: a 64-bit digest of m's row_ptr and col is
+ * taken on the device at the object's first refresh (which, for the kinds with maps, also holds m's pattern to the
+ * triangles the object stores) and compared from then on.  -1 also: a NULL argument, a handle of other rows, row0 or
+ * dtype, a tiles-only handle.  An object that is never refreshed keeps nothing more than before. */
+int spmv_hip_precond_refresh(spmv_precond *P, const spmv_csr_dev *m);
+int spmv_hip_trsv_refresh(spmv_trsv *T, const spmv_csr_dev *m);
 /* The host analysis behind them (no device needed), on an n x n CSR pattern with local columns; columns outside [0, n)
  * are ignored, rows may be unsorted.
  *   spmv_trsv_colour  greedy first-fit colouring in natural order over the pattern of A + A^T; colour[n], order[n] =

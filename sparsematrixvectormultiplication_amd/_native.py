@@ -216,6 +216,9 @@ _PROTOTYPES = {
     "spmv_hip_csr_from_coo": (C.c_int, [C.c_int, C.c_int, C.c_longlong, c_int_p, c_int_p, c_double_p,
                                         C.POINTER(C.c_void_p)]),
     "spmv_hip_csr_download": (C.c_int, [C.c_void_p, c_int_p, c_int_p, C.c_void_p]),
+    "spmv_hip_csr_update_values": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "spmv_hip_csr_update_values_on": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spmv_hip_csr_update_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), c_double_p]),
     "spmv_hip_csr_plan_check": (C.c_int, [C.c_int, C.c_int, c_int_p, c_int_p, C.c_int, c_int_p]),
     "spmv_hip_csr_tile_plan_check": (C.c_int, [C.c_int, C.c_int, c_int_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                               C.c_int, C.c_int, C.POINTER(C.c_longlong)]),
@@ -241,6 +244,8 @@ _PROTOTYPES = {
     "spmv_spgemm_plan": (C.c_int, [C.c_int, C.POINTER(C.c_longlong), C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p]),
     "spmv_hip_csr_precond_build": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "spmv_hip_precond_free": (None, [C.c_void_p]),
+    "spmv_hip_precond_refresh": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "spmv_hip_trsv_refresh": (C.c_int, [C.c_void_p, C.c_void_p]),
     "spmv_hip_precond_info": (C.c_int, [C.c_void_p, c_int_p]),
     "spmv_hip_precond_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "spmv_hip_precond_apply_on": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

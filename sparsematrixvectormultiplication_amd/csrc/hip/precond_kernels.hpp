@@ -25,6 +25,7 @@
 // fixed c neighbouring lanes (neighbouring rows of a block) read neighbouring addresses; b = 1 is inv[i] = 1 / d_i.
 // The apply reads every stored value once: b sizeof(T) bytes of inv, plus r and z, per row.
 #pragma once
+#include "refresh_kernels.hpp"
 #include "solver_ops.hpp"
 
 namespace spmv {
@@ -198,6 +199,9 @@ struct precond_family {
     // spmv_hip_precond_factors past its argument checks; NULL: the family has no factors
     int (*factors)(const spmv_precond *P, int which, int *row_ptr, int *col, void *val);
     void (*free)(void *impl);
+    // spmv_hip_precond_refresh past the shared checks (P fits m, m's pattern is the stamp's): P from m's values, all or
+    // nothing.  NULL: the kind's pattern, hierarchy or interval is a function of the values -- refused, build it again
+    int (*refresh)(spmv_precond *P, const spmv_csr_dev *m);
 };
 
 struct spmv_precond {
@@ -207,6 +211,7 @@ struct spmv_precond {
     void *inv = nullptr;      // JACOBI / BLOCK_JACOBI: ceil(rows / block) * block^2 values of that dtype (layout above); owned
     void *impl = nullptr;     // the other kinds: the family's own object; owned, inv is NULL
     const precond_family *family = nullptr;  // NULL: JACOBI / BLOCK_JACOBI, applied by pc_apply / mpc_apply
+    PatternStamp stamp;       // the pattern of the first refresh's handle (refresh_kernels.hpp); none before it
 };
 
 // the object every build ends with: the five fields from the handle, and the family's payload

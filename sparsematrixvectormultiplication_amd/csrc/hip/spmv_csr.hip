@@ -999,6 +999,7 @@ extern "C" void spmv_hip_csr_free(spmv_csr_dev *m) {
     (void)hipFree(m->spmm_partial);
     (void)hipFree(m->x);
     (void)hipFree(m->y);
+    delete m->upd;
     delete m;
 }
 

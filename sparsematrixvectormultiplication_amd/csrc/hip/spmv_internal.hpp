@@ -336,7 +336,26 @@ struct CompactTiles : TileTier {
         *this = CompactTiles();
     }
 };
+// What a handle keeps from its first spmv_hip_csr_update_values on (spmv_update.hip): for each of the four arrays that
+// hold matrix values in the tile plans' order -- tile.tval, tile.rem_val, lt.tval, mt.tval -- the source map, one int per
+// slot: the entry of `val` the slot holds, -1 for a padding slot.  A handle that is never updated has none.
+struct UpdateState {
+    int *src[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t slots[4] = {0, 0, 0, 0};  // a tier's `padded` (a multiple of 4: passes start on multiples of 4), the remainder's entries
+    bool mapped = false;             // the analysis has run (a handle without tile plans: nothing to map)
+    long long updates = 0;
+    size_t map_bytes = 0;
+    float map_build_us = 0, last_us = 0;
+    hipEvent_t t0 = nullptr, t1 = nullptr;  // around the last update's device work; read by spmv_hip_csr_update_info
+    bool timed = false;
+    ~UpdateState() {
+        for (int *p : src) (void)hipFree(p);
+        if (t0) (void)hipEventDestroy(t0);
+        if (t1) (void)hipEventDestroy(t1);
+    }
+};
 struct spmv_csr_dev {
+    UpdateState *upd = nullptr;  // spmv_hip_csr_update_values' state; nullptr until the first update
     int value_bytes = 8;
     int M_local = 0, M_total = 0, N = 0, row0 = 0;
     long long nz = 0;

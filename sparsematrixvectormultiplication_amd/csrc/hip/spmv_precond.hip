@@ -20,8 +20,9 @@ namespace {
 
 constexpr int kPcMaxGrid = 1 << 20;  // grid cap of the build kernels (they stride beyond it)
 
+// the stored inverse of m's diagonal blocks of b rows in a new array (*inv_out, the caller's on 0); the refusals name `what`
 template <typename T>
-int precond_build(const spmv_csr_dev *m, int kind, int b, spmv_precond **out) {
+int precond_invert(const spmv_csr_dev *m, int b, const char *what, void **inv_out) {
     const int n = m->M_local;
     const long long nblocks = ((long long)n + b - 1) / b;
     const size_t entries = std::max<size_t>((size_t)nblocks * b * b, 1);
@@ -39,7 +40,7 @@ int precond_build(const spmv_csr_dev *m, int kind, int b, spmv_precond **out) {
         const int none[2] = {INT_MAX, INT_MAX};
         if (e == hipSuccess) e = hipMemcpy(bad, none, sizeof none, hipMemcpyHostToDevice);
         if (e != hipSuccess) {
-            fail("csr_precond_build: allocation failed: %s", hipGetErrorString(e));
+            fail("%s: allocation failed: %s", what, hipGetErrorString(e));
             break;
         }
         if (n) {
@@ -61,32 +62,55 @@ int precond_build(const spmv_csr_dev *m, int kind, int b, spmv_precond **out) {
         if (e == hipSuccess) e = hipMemcpyAsync(h, bad, sizeof h, hipMemcpyDeviceToHost, g_stream);
         if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
         if (e != hipSuccess) {
-            fail("csr_precond_build: build failed: %s", hipGetErrorString(e));
+            fail("%s: build failed: %s", what, hipGetErrorString(e));
             break;
         }
         if (h[0] != INT_MAX) {
-            fail("csr_precond_build: row %d (global row %d) has no diagonal entry", h[0], m->row0 + h[0]);
+            fail("%s: row %d (global row %d) has no diagonal entry", what, h[0], m->row0 + h[0]);
             break;
         }
         if (h[1] != INT_MAX) {
             if (b == 1)
-                fail("csr_precond_build: row %d (global row %d): the diagonal is zero or not finite, or so small that "
-                     "its inverse is not finite", h[1], m->row0 + h[1]);
+                fail("%s: row %d (global row %d): the diagonal is zero or not finite, or so small that "
+                     "its inverse is not finite", what, h[1], m->row0 + h[1]);
             else
-                fail("csr_precond_build: block %d (global rows [%d, %d)): a zero or non-finite pivot, or an inverse "
-                     "that is not finite", h[1], m->row0 + h[1] * b, m->row0 + (int)std::min<long long>(
-                                                                                    (long long)(h[1] + 1) * b, n));
+                fail("%s: block %d (global rows [%d, %d)): a zero or non-finite pivot, or an inverse "
+                     "that is not finite", what, h[1], m->row0 + h[1] * b, m->row0 + (int)std::min<long long>(
+                                                                                          (long long)(h[1] + 1) * b, n));
             break;
         }
-        *out = precond_new(m, kind, b, sizeof(T));
-        (*out)->inv = inv;
-        inv = nullptr;  // P owns it now
+        *inv_out = inv;
+        inv = nullptr;  // the caller's now
         rc = 0;
     } while (0);
     (void)hipFree(D);
     (void)hipFree(bad);
     (void)hipFree(inv);
     return rc;
+}
+
+template <typename T>
+int precond_build(const spmv_csr_dev *m, int kind, int b, spmv_precond **out) {
+    void *inv = nullptr;
+    if (precond_invert<T>(m, b, "csr_precond_build", &inv)) return -1;
+    *out = precond_new(m, kind, b, sizeof(T));
+    (*out)->inv = inv;  // P owns it
+    return 0;
+}
+
+// JACOBI / BLOCK_JACOBI from m's values: the device build once more into an array of its own, copied over P's only when
+// no row or block was refused
+template <typename T>
+int precond_refresh_inverse(spmv_precond *P, const spmv_csr_dev *m) {
+    void *inv = nullptr;
+    if (precond_invert<T>(m, P->block, "precond_refresh", &inv)) return -1;
+    const long long nblocks = ((long long)P->rows + P->block - 1) / P->block;
+    const size_t bytes = (size_t)nblocks * P->block * P->block * sizeof(T);
+    hipError_t e = bytes ? hipMemcpyAsync(P->inv, inv, bytes, hipMemcpyDeviceToDevice, g_stream) : hipSuccess;
+    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
+    (void)hipFree(inv);
+    if (e != hipSuccess) return fail("precond_refresh: the copy failed: %s", hipGetErrorString(e));
+    return 0;
 }
 
 int precond_apply_launch(const spmv_precond *P, const void *d_r, void *d_z, hipStream_t s) {
@@ -98,6 +122,40 @@ int precond_apply_launch(const spmv_precond *P, const void *d_r, void *d_z, hipS
 }
 
 }  // namespace
+
+// the stamp of handle m (waits for the device); -1: HIP error
+int pattern_stamp(const spmv_csr_dev *m, PatternStamp &out) {
+    DevBuf d;
+    HIP_TRY(d.alloc(sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(d.p, 0, sizeof(unsigned long long), g_stream));
+    hipLaunchKernelGGL((spmv::rf_digest<int>), dim3(spmv::rf_grid(m->M_local + 1LL)), dim3(kBlock), 0, g_stream, m->M_local + 1LL,
+                       (const int *)m->row_ptr, 0ull, d.as<unsigned long long>());
+    if (m->nz)
+        hipLaunchKernelGGL((spmv::rf_digest<int>), dim3(spmv::rf_grid(m->nz)), dim3(kBlock), 0, g_stream, (long long)m->nz,
+                           (const int *)m->col, 1ull << 31, d.as<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&out.digest, d.p, sizeof out.digest, hipMemcpyDeviceToHost, g_stream));
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    out.have = true;
+    out.nz = m->nz;
+    out.rows = m->M_local;
+    out.cols = m->N;
+    return 0;
+}
+
+// m's pattern against the stamp (taken now when there is none yet); -1 with a message naming `what`
+int pattern_check(const spmv_csr_dev *m, PatternStamp &stamp, const char *what) {
+    PatternStamp now;
+    if (pattern_stamp(m, now)) return -1;
+    if (!stamp.have) {
+        stamp = now;
+        return 0;
+    }
+    if (now.digest != stamp.digest || now.nz != stamp.nz || now.rows != stamp.rows || now.cols != stamp.cols)
+        return fail("%s: the handle's pattern is not the one this object was refreshed from first: a changed pattern "
+                    "needs a new build", what);
+    return 0;
+}
 
 extern "C" int spmv_hip_csr_precond_build(const spmv_csr_dev *m, int kind, int block, spmv_precond **out) {
     auto check = [&] {
@@ -111,6 +169,27 @@ extern "C" int spmv_hip_csr_precond_build(const spmv_csr_dev *m, int kind, int b
     return precond_build_frame("csr_precond_build", m, out, check, [&](auto t, spmv_precond **P) {
         return precond_build<decltype(t)>(m, kind, block, P);
     });
+}
+
+// P from the values m holds now (include/spmv_hip.h): the shared checks, then the kind's own refresh
+extern "C" int spmv_hip_precond_refresh(spmv_precond *P, const spmv_csr_dev *m) {
+    if (need_device()) return -1;
+    if (!P || !m) return fail("precond_refresh: NULL argument");
+    if (P->family && !P->family->refresh)
+        return fail("precond_refresh: a preconditioner of kind %d (%s) depends on the values: its pattern, hierarchy or "
+                    "interval is a function of them.  Build it again", P->kind, P->family->name);
+    if (precond_matches(m, P, "precond_refresh") || handle_ok(m, "precond_refresh")) return -1;
+    const bool stamped = P->stamp.have;
+    const int rc = guarded("precond_refresh", [&] {
+        if (pattern_check(m, P->stamp, "precond_refresh")) return -1;
+        if (P->family) return P->family->refresh(P, m);
+        return P->value_bytes == 8 ? precond_refresh_inverse<double>(P, m) : precond_refresh_inverse<float>(P, m);
+    });
+    // JACOBI / BLOCK_JACOBI keep nothing made from the pattern: a first refresh that is refused leaves no stamp behind.
+    // A family with maps keeps stamp and maps together (its refresh drops the stamp when it installs no maps).
+    if (rc && !stamped && !P->family) P->stamp = PatternStamp();
+    (void)hipGetLastError();
+    return rc;
 }
 
 extern "C" void spmv_hip_precond_free(spmv_precond *P) {

@@ -53,6 +53,24 @@ struct TriDev {  // one triangle on the device
     spmv::TrsvView view() const { return {rp, col, brow, xrow, level_ptr, level_split, val, dinv}; }
 };
 
+// What an object's first refresh builds (tri_refresh_analyse) and every later one runs on: the canonical (and, for the
+// multicolour order, permuted) diagonal block B as a pattern, which entries of the handle feed each of its entries, and
+// where each entry goes in the triangles' level order.  All on the device; an object that is never refreshed has none.
+struct TriRefresh {
+    long long nzb = 0;                      // entries of B
+    int *fp = nullptr, *feed = nullptr;     // entry e of B = the handle's entries feed[fp[e] .. fp[e + 1]) added in that order
+    int *rp = nullptr, *col = nullptr, *diag = nullptr;  // B (rp, col: ILU(0) only; diag: NULL for a unit triangular solve)
+    int *src[2] = {nullptr, nullptr};       // per slot of the lower / upper triangle's val: the entry of B
+    int *urow = nullptr;                    // the upper triangle's rows of B in its level order (the lower one's: its xrow)
+    std::vector<int> fwd_level_ptr;         // ILU(0): the forward plan's level_ptr, for the factorisation's grids
+    TriRefresh() = default;
+    TriRefresh(const TriRefresh &) = delete;
+    TriRefresh &operator=(const TriRefresh &) = delete;
+    ~TriRefresh() {
+        for (int *p : {fp, feed, rp, col, diag, src[0], src[1], urow}) (void)hipFree(p);
+    }
+};
+
 // B = Q A Q^T with row k of B = row order[k] of A
 void canon_permute(const Canon &A, const std::vector<int> &order, Canon &B) {
     const int n = A.n;
@@ -173,13 +191,17 @@ struct spmv_trsv {
     TriDev t;
     int rows = 0, row0 = 0, value_bytes = 8;
     int analysis_us = 0, upload_us = 0;
+    int uplo = SPMV_TRSV_LOWER, diag = SPMV_TRSV_NONUNIT;
+    std::unique_ptr<TriRefresh> rf;  // spmv_hip_trsv_refresh's maps, from the first refresh on
+    PatternStamp stamp;              // ... and the pattern they were made from
 };
 
 struct spmv_tri_precond {
     TriDev fwd, bwd;
     void *y = nullptr;  // the vector between the two solves
     bool scaled = false;
-    double scale = 1.0;
+    double scale = 1.0, omega = 1.0;
+    std::unique_ptr<TriRefresh> rf;  // the refresh's maps, from the first refresh on
     int colours = 0;
     int analysis_us = 0, factor_us = 0, upload_us = 0;
     bool unit_lower = false;  // ILU(0): L's diagonal is 1
@@ -217,6 +239,7 @@ int trsv_build(const spmv_csr_dev *m, int uplo, int diag, spmv_trsv **out) {
     std::unique_ptr<spmv_trsv> S(new spmv_trsv);
     if (tri_upload<T>(A, uplo, p, dinv.empty() ? nullptr : dinv.data(), nullptr, nullptr, S->t)) return -1;
     S->rows = A.n, S->row0 = m->row0, S->value_bytes = (int)sizeof(T);
+    S->uplo = uplo, S->diag = diag;
     S->analysis_us = (int)((t1 - t0) * 1e3);
     S->upload_us = (int)((now_ms() - t1) * 1e3);
     *out = S.release();
@@ -310,6 +333,7 @@ int tri_precond_build(const spmv_csr_dev *m, int kind, int ordering, double omeg
         }
         tp->scaled = true;
         tp->scale = (2.0 - omega) / omega;
+        tp->omega = omega;
     } else {
         if (ilu0_factor(B, pl, tp->order, m->row0)) return -1;
         for (int k = 0; k < n; ++k) {
@@ -332,6 +356,236 @@ int tri_precond_build(const spmv_csr_dev *m, int kind, int ordering, double omeg
     tp->upload_us = (int)((now_ms() - t2) * 1e3);
     *out = precond_new(m, kind, 1, sizeof(T), &kTriFamily, tp.release());
     return 0;
+}
+
+// ---------------------------------------------------------------- refresh: new values, the symbolic work kept
+int not_the_pattern(const char *what) {
+    return fail("%s: the handle's pattern is not the one this object was built from: a changed pattern needs a new build", what);
+}
+
+// The first refresh's analysis, a host pass over m's pattern (no value comes back): the canonical block as
+// canon_download makes it with the feeds of every entry, permuted by `order` as canon_permute does (order empty: the
+// identity), then per triangle the place of every entry in the level order the build stored -- each held to the columns
+// the triangle holds, so a handle of another pattern is refused here.  lower / upper: the triangles the object has; an
+// object with one triangle maps, gathers and keeps that triangle's entries alone (and the diagonal where it is read).
+// want_pattern: the block's rp and col go to the device as well (ILU(0) factors on them).
+int tri_refresh_analyse(const spmv_csr_dev *m, const std::vector<int> &order, const TriDev *lower, const TriDev *upper,
+                        bool want_diag, bool want_pattern, const char *what, std::unique_ptr<TriRefresh> &out) {
+    const int n = m->M_local;
+    const size_t nz = (size_t)m->nz;
+    std::vector<int> rp((size_t)n + 1, 0), col(nz);
+    HIP_TRY(hipMemcpy(rp.data(), m->row_ptr, ((size_t)n + 1) * sizeof(int), hipMemcpyDeviceToHost));
+    if (nz) HIP_TRY(hipMemcpy(col.data(), m->col, nz * sizeof(int), hipMemcpyDeviceToHost));
+    // the canonical block; A.val[e] = e, so that the permutation carries every entry's place along
+    Canon A;
+    std::vector<int> fpA(1, 0), feedA, idx;
+    A.n = n;
+    A.rp.assign((size_t)n + 1, 0);
+    A.diag.assign((size_t)n, -1);
+    for (int i = 0; i < n; ++i) {
+        idx.clear();
+        for (int e = rp[i]; e < rp[i + 1]; ++e)
+            if (col[e] >= m->row0 && col[e] < m->row0 + n) idx.push_back(e);
+        std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return col[a] < col[b]; });
+        for (size_t k = 0; k < idx.size(); ++k) {
+            const int c = col[idx[k]] - m->row0;
+            if (k && c == A.col.back()) {
+                feedA.push_back(idx[k]);
+                fpA.back() = (int)feedA.size();
+                continue;
+            }
+            if (c == i) A.diag[i] = (int)A.col.size();
+            A.val.push_back((double)A.col.size());
+            A.col.push_back(c);
+            feedA.push_back(idx[k]);
+            fpA.push_back((int)feedA.size());
+        }
+        A.rp[i + 1] = (int)A.col.size();
+    }
+    Canon B;
+    if (!order.empty()) {
+        if ((int)order.size() != n) return not_the_pattern(what);
+        canon_permute(A, order, B);
+    } else {
+        B = std::move(A);
+    }
+    if (!lower || !upper) {  // one triangle: B shrinks to its side of the diagonal
+        Canon C;
+        C.n = n;
+        C.rp.assign((size_t)n + 1, 0);
+        C.diag.assign((size_t)n, -1);
+        for (int i = 0; i < n; ++i) {
+            for (int e = B.rp[i]; e < B.rp[i + 1]; ++e) {
+                const int c = B.col[e];
+                if (c == i ? !want_diag : (lower ? c > i : c < i)) continue;
+                if (c == i) C.diag[i] = (int)C.col.size();
+                C.col.push_back(c);
+                C.val.push_back(B.val[e]);
+            }
+            C.rp[i + 1] = (int)C.col.size();
+        }
+        B = std::move(C);
+    }
+    const size_t nzb = B.col.size();
+    std::vector<int> fp(1, 0), feed;
+    feed.reserve(feedA.size());
+    for (size_t e = 0; e < nzb; ++e) {
+        const size_t a = (size_t)B.val[e];
+        feed.insert(feed.end(), feedA.begin() + fpA[a], feedA.begin() + fpA[a + 1]);
+        fp.push_back((int)feed.size());
+    }
+    if (want_diag && first_missing_diag(B) >= 0) return not_the_pattern(what);
+    std::unique_ptr<TriRefresh> rf(new TriRefresh);
+    rf->nzb = (long long)nzb;
+    std::vector<int> where((size_t)n);  // of handle row i: its row of B
+    for (int k = 0; k < n; ++k) where[order.empty() ? k : order[k]] = k;
+    for (int side = 0; side < 2; ++side) {
+        const TriDev *t = side ? upper : lower;
+        if (!t) continue;
+        if (t->n != n) return not_the_pattern(what);
+        // the lower triangle is numbered like B and its columns too; the upper one's rows and columns like the handle
+        const bool mapped = side && !order.empty();
+        std::vector<int> xrow((size_t)n), trp((size_t)n + 1, 0), tcol((size_t)t->entries), src((size_t)t->entries), rows((size_t)n);
+        if (n) HIP_TRY(hipMemcpy(xrow.data(), t->xrow, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+        if (n) HIP_TRY(hipMemcpy(trp.data(), t->rp, ((size_t)n + 1) * sizeof(int), hipMemcpyDeviceToHost));
+        if (t->entries) HIP_TRY(hipMemcpy(tcol.data(), t->col, tcol.size() * sizeof(int), hipMemcpyDeviceToHost));
+        int slot = 0;
+        for (int q = 0; q < n; ++q) {
+            if (xrow[q] < 0 || xrow[q] >= n || trp[q] != slot) return not_the_pattern(what);
+            const int i = mapped ? where[xrow[q]] : xrow[q];
+            rows[q] = i;
+            for (int e = B.rp[i]; e < B.rp[i + 1]; ++e) {
+                const int c = B.col[e];
+                if (side ? c <= i : c >= i) continue;
+                if (slot >= trp[q + 1] || tcol[slot] != (mapped ? order[c] : c)) return not_the_pattern(what);
+                src[slot++] = (int)e;
+            }
+            if (slot != trp[q + 1]) return not_the_pattern(what);
+        }
+        if ((long long)slot != t->entries) return not_the_pattern(what);
+        if (to_device(&rf->src[side], src)) return -1;
+        if (side && to_device(&rf->urow, rows)) return -1;
+    }
+    if (to_device(&rf->fp, fp) || to_device(&rf->feed, feed)) return -1;
+    if (want_pattern && (to_device(&rf->rp, B.rp) || to_device(&rf->col, B.col))) return -1;
+    if (want_diag && to_device(&rf->diag, B.diag)) return -1;
+    out = std::move(rf);
+    return 0;
+}
+
+// One refresh on the device.  W: B's values gathered from m in fp64 (ILU(0): factored in place); then the diagonal's
+// checks into scratch, and only behind them the scatters into the triangles.  mode as rf_diag (-1: a unit triangular
+// solve, no diagonal); diag_host (optional): the diagonal as P->factors returns it.  On -1 the object is as it was.
+template <typename T>
+int tri_refresh_run(const spmv_csr_dev *m, const TriRefresh &rf, TriDev *lower, TriDev *upper, int mode, double omega,
+                    const std::vector<int> &order, const char *what, std::vector<double> *diag_host) {
+    const int n = m->M_local;
+    if (!n) return 0;
+    DevBuf W, dtmp, dout, bad;
+    hipError_t e = W.alloc((size_t)rf.nzb * sizeof(double));
+    if (e == hipSuccess) e = dtmp.alloc((size_t)n * sizeof(T));
+    if (e == hipSuccess) e = dout.alloc((size_t)n * sizeof(double));
+    if (e == hipSuccess) e = bad.alloc(2 * sizeof(int));
+    const int none[2] = {INT_MAX, INT_MAX};
+    if (e == hipSuccess) e = hipMemcpyAsync(bad.p, none, sizeof none, hipMemcpyHostToDevice, g_stream);
+    if (e != hipSuccess) return fail("refresh: allocation failed: %s", hipGetErrorString(e));
+    if (rf.nzb)
+        hipLaunchKernelGGL((spmv::rf_gather<T>), dim3(spmv::rf_grid(rf.nzb)), dim3(kBlock), 0, g_stream, rf.nzb, (const int *)rf.fp,
+                           (const int *)rf.feed, (const T *)m->val, W.as<double>());
+    if (mode == 2) {  // ILU(0): the build's launches, on the forward plan
+        const TriDev &f = *lower;
+        for (size_t k = 0; k < f.plan.size(); k += 4) {
+            const int l0 = f.plan[k + 1], l1 = f.plan[k + 2];
+            if (f.plan[k]) {
+                hipLaunchKernelGGL(spmv::ilu0_chain, dim3(1), dim3(kBlock), 0, g_stream, l0, l1, (const int *)f.level_ptr,
+                                   (const int *)f.xrow, (const int *)rf.rp, (const int *)rf.col, (const int *)rf.diag,
+                                   W.as<double>(), bad.as<int>());
+            } else {
+                const int p0 = rf.fwd_level_ptr[(size_t)l0], p1 = rf.fwd_level_ptr[(size_t)l1];
+                const int grid = std::min(spmv::kTrsvBlocks, (p1 - p0 + kBlock / 64 - 1) / (kBlock / 64));
+                hipLaunchKernelGGL(spmv::ilu0_level, dim3(grid), dim3(kBlock), 0, g_stream, p0, p1, (const int *)f.xrow,
+                                   (const int *)rf.rp, (const int *)rf.col, (const int *)rf.diag, W.as<double>(), bad.as<int>());
+            }
+        }
+    }
+    std::vector<double> d_host((size_t)n);
+    int h[2] = {INT_MAX, INT_MAX};
+    if (mode >= 0)
+        hipLaunchKernelGGL((spmv::rf_diag<T>), dim3(spmv::rf_grid(n)), dim3(kBlock), 0, g_stream, n, mode, omega, (const int *)rf.diag,
+                           (const double *)W.as<double>(), dout.as<double>(), dtmp.as<T>(), bad.as<int>() + 1);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(h, bad.p, sizeof h, hipMemcpyDeviceToHost, g_stream);
+    if (e == hipSuccess && mode >= 0) e = hipMemcpyAsync(d_host.data(), dout.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, g_stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
+    if (e != hipSuccess) return fail("refresh: the factorisation failed: %s", hipGetErrorString(e));
+    auto original = [&](int k) { return order.empty() ? k : order[(size_t)k]; };
+    // the build's refusals, in the build's order and words behind the refresh's name
+    if (h[0] != INT_MAX)
+        return fail("%s: row %d (global row %d): ILU(0) meets a zero or non-finite pivot", what, original(h[0]),
+                    m->row0 + original(h[0]));
+    if (h[1] != INT_MAX) {
+        const int i = original(h[1]);
+        if (mode == 2) return fail("%s: row %d (global row %d): the pivot's inverse is not finite", what, i, m->row0 + i);
+        return fail("%s: row %d (global row %d): the diagonal is zero or not finite, or so small that its inverse is not finite",
+                    what, i, m->row0 + i);
+    }
+    // publish: one rounding to the dtype per value
+    TriDev *tri[2] = {lower, upper};
+    for (int side = 0; side < 2; ++side) {
+        TriDev *t = tri[side];
+        if (!t) continue;
+        if (t->entries)
+            hipLaunchKernelGGL((spmv::rf_scatter<T>), dim3(spmv::rf_grid(t->entries)), dim3(kBlock), 0, g_stream, t->entries,
+                               (const int *)rf.src[side], (const double *)W.as<double>(), (T *)t->val);
+        if (t->dinv)
+            hipLaunchKernelGGL((spmv::rf_pick<T>), dim3(spmv::rf_grid(n)), dim3(kBlock), 0, g_stream, (long long)n,
+                               (const int *)(side ? rf.urow : t->xrow), (const T *)dtmp.as<T>(), (T *)t->dinv);
+    }
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
+    if (e != hipSuccess) return fail("refresh: the scatter failed: %s", hipGetErrorString(e));
+    if (diag_host) *diag_host = d_host;
+    return 0;
+}
+
+// the family's refresh: SSOR and ILU(0), either ordering
+int tri_precond_refresh(spmv_precond *P, const spmv_csr_dev *m) {
+    spmv_tri_precond *tp = (spmv_tri_precond *)P->impl;
+    if (!tp->rf) {
+        // Stamp and maps live and die together: the frame has just stamped m's pattern, and whatever ends this block
+        // without maps -- a handle of another pattern, a HIP error, an exception -- takes the stamp along, so that the next
+        // refresh is held to the triangles again.  Once there are maps the stamp stays, whatever a refresh refuses.
+        struct DropStamp {
+            PatternStamp &stamp;
+            bool armed = true;
+            ~DropStamp() {
+                if (armed) stamp = PatternStamp();
+            }
+        } drop{P->stamp};
+        std::unique_ptr<TriRefresh> rf;
+        if (tri_refresh_analyse(m, tp->order, &tp->fwd, &tp->bwd, true, tp->unit_lower, "precond_refresh", rf)) return -1;
+        if (tp->unit_lower) {
+            rf->fwd_level_ptr.resize((size_t)tp->fwd.levels + 1);
+            HIP_TRY(hipMemcpy(rf->fwd_level_ptr.data(), tp->fwd.level_ptr, rf->fwd_level_ptr.size() * sizeof(int), hipMemcpyDeviceToHost));
+        }
+        tp->rf = std::move(rf);
+        drop.armed = false;
+    }
+    const int mode = tp->unit_lower ? 2 : 1;
+    const char *name = "precond_refresh";
+    return P->value_bytes == 8 ? tri_refresh_run<double>(m, *tp->rf, &tp->fwd, &tp->bwd, mode, tp->omega, tp->order, name, &tp->diag)
+                               : tri_refresh_run<float>(m, *tp->rf, &tp->fwd, &tp->bwd, mode, tp->omega, tp->order, name, &tp->diag);
+}
+
+int trsv_refresh(spmv_trsv *S, const spmv_csr_dev *m) {
+    const bool lower = S->uplo == SPMV_TRSV_LOWER, unit = S->diag == SPMV_TRSV_UNIT;
+    if (!S->rf && tri_refresh_analyse(m, {}, lower ? &S->t : nullptr, lower ? nullptr : &S->t, !unit, false, "trsv_refresh", S->rf)) {
+        S->stamp = PatternStamp();  // no maps: no stamp either (the next refresh is held to the triangle again)
+        return -1;
+    }
+    TriDev *lo = lower ? &S->t : nullptr, *up = lower ? nullptr : &S->t;
+    return S->value_bytes == 8 ? tri_refresh_run<double>(m, *S->rf, lo, up, unit ? -1 : 0, 1.0, {}, "trsv_refresh", nullptr)
+                               : tri_refresh_run<float>(m, *S->rf, lo, up, unit ? -1 : 0, 1.0, {}, "trsv_refresh", nullptr);
 }
 
 template <typename T>
@@ -391,6 +645,24 @@ extern "C" int spmv_hip_csr_trsv_build(const spmv_csr_dev *m, int uplo, int diag
 }
 
 extern "C" void spmv_hip_trsv_free(spmv_trsv *S) { delete S; }
+
+// S from the values m holds now (include/spmv_hip.h): the level order and the launch plan stay, the values and the
+// diagonal's inverses are gathered and scattered on the device; all or nothing
+extern "C" int spmv_hip_trsv_refresh(spmv_trsv *S, const spmv_csr_dev *m) {
+    if (need_device()) return -1;
+    if (!S || !m) return fail("trsv_refresh: NULL argument");
+    if (S->rows != m->M_local || S->row0 != m->row0 || S->value_bytes != m->value_bytes)
+        return fail("trsv_refresh: the solver covers rows [%d, %d) with %d-byte values, the handle rows [%d, %d) with %d",
+                    S->row0, S->row0 + S->rows, S->value_bytes, m->row0, m->row0 + m->M_local, m->value_bytes);
+    if (handle_ok(m, "trsv_refresh")) return -1;
+    const int rc = guarded("trsv_refresh", [&] {
+        if (pattern_check(m, S->stamp, "trsv_refresh")) return -1;
+        return trsv_refresh(S, m);
+    });
+    if (rc && !S->rf) S->stamp = PatternStamp();  // stamp and maps live and die together (an exception in the analysis)
+    (void)hipGetLastError();
+    return rc;
+}
 
 extern "C" int spmv_hip_trsv_info(const spmv_trsv *S, int *info) {
     if (!S || !info) return fail("trsv_info: bad arguments");
@@ -501,6 +773,6 @@ int tri_precond_factors(const spmv_precond *P, int which, int *row_ptr, int *col
 
 // two solves take one right-hand side: no k-wide apply, no workspace
 const precond_family kTriFamily = {"made of triangular solves", nullptr, tri_precond_apply, nullptr, nullptr, tri_precond_factors,
-                                   [](void *impl) { delete (spmv_tri_precond *)impl; }};
+                                   [](void *impl) { delete (spmv_tri_precond *)impl; }, tri_precond_refresh};
 
 }  // namespace

@@ -443,6 +443,36 @@ class CsrDevice(_Handle):
                                                val.ctypes.data_as(C.c_void_p)), "spmv_hip_csr_download")
         return rp, col[:info["nz"]], val[:info["nz"]]
 
+    def update_values(self, values):
+        """New numbers on the handle's pattern (spmv_hip_csr_update_values): the handle's own nz values, of its dtype and
+        in its own entry order -- the order download() returns.  The handle is then the upload of (its pattern, values)
+        under the plan it has; info() and addresses() stay as they are.  The first update of a handle with tile plans
+        pays one analysis (update_info()["map_build_us"]); a handle holding a column split is refused."""
+        values = np.asarray(values)
+        nz = self.info()["nz"]
+        if values.ndim != 1 or values.size != nz:
+            raise ValueError(f"update_values: values has shape {values.shape}; the handle holds {nz} entries")
+        if values.dtype != np.dtype(self.dtype):
+            raise ValueError(f"update_values: values holds {values.dtype}, the handle {np.dtype(self.dtype)}")
+        values = np.ascontiguousarray(values)
+        if nz == 0:     # (an empty array need not have an address)
+            values = np.zeros(1, dtype=self.dtype)
+        _check(nat.lib().spmv_hip_csr_update_values(self.h, values.ctypes.data_as(C.c_void_p)), "spmv_hip_csr_update_values")
+
+    def update_values_on(self, d_val, stream=0):
+        """update_values from a device array (its address) of the handle's nz values in the handle's dtype, on `stream`
+        (0: the library's); does not wait for the device once the handle's first update has been made."""
+        _check(nat.lib().spmv_hip_csr_update_values_on(self.h, C.c_void_p(int(getattr(d_val, "value", d_val) or 0)),
+                                                       C.c_void_p(int(stream)) if stream else None),
+               "spmv_hip_csr_update_values_on")
+
+    def update_info(self) -> dict:
+        """{"updates": made so far, "map_bytes": the source maps on the device, "map_build_us": the first update's
+        analysis, "last_us": the last update's device time (waits for it)} (spmv_hip_csr_update_info)."""
+        counts, us = (C.c_longlong * 2)(), (C.c_double * 2)()
+        _check(nat.lib().spmv_hip_csr_update_info(self.h, counts, us), "spmv_hip_csr_update_info")
+        return {"updates": int(counts[0]), "map_bytes": int(counts[1]), "map_build_us": float(us[0]), "last_us": float(us[1])}
+
     @classmethod
     def from_host(cls, csr: CsrHost, row0=0, row1=None):
         return cls(csr.M, csr.N, csr.row_ptr, csr.col_idx, csr.values, row0, row1)
@@ -1071,6 +1101,13 @@ class TriangularSolver(_Handle):
                "spmv_hip_trsv_solve")
         return x
 
+    def refresh(self, dev: CsrDevice):
+        """The solver from the values dev holds now (spmv_hip_trsv_refresh): dev is a handle of the solver's dtype, rows
+        and row0 with the pattern it was built from, normally the same handle after update_values.  The level order and
+        the launch plan stay; the solver then is, byte for byte, a fresh build on a fresh upload of dev's arrays.  All or
+        nothing: a refusal (the build's words, with its row) leaves the solver as it was."""
+        _check(nat.lib().spmv_hip_trsv_refresh(self.h, dev.h), "spmv_hip_trsv_refresh")
+
     def solve_on(self, d_b: int, d_x: int, stream: int = 0):
         """The same on device vectors (b and x must not overlap), asynchronous on `stream` (0 = the library's)."""
         _check(nat.lib().spmv_hip_trsv_solve_on(self.h, C.c_void_p(d_b), C.c_void_p(d_x), C.c_void_p(stream)),
@@ -1269,6 +1306,15 @@ class Preconditioner(_Handle):
         out = (C.c_int * 5)()
         _check(nat.lib().spmv_hip_precond_info(self.h, out), "spmv_hip_precond_info")
         return dict(zip(("kind", "block", "rows", "row0", "value_bytes"), (int(v) for v in out)))
+
+    def refresh(self, dev: CsrDevice):
+        """The preconditioner from the values dev holds now (spmv_hip_precond_refresh): dev is a handle of P's dtype,
+        rows and row0 with the pattern P was built from, normally the same handle after update_values.  Jacobi and
+        block-Jacobi rerun their device build; SSOR, ILU(0) (either ordering) keep their colouring, levels and launch
+        plans and redo the numbers on the device.  P then is, byte for byte, the fresh build with the same arguments on a
+        fresh upload of dev's arrays.  All or nothing: a refusal (the build's words, with its row) leaves P applying as
+        before.  FSAI, AMG and Chebyshev depend on the values beyond their numbers and are refused: build them again."""
+        _check(nat.lib().spmv_hip_precond_refresh(self.h, dev.h), "spmv_hip_precond_refresh")
 
     def apply(self, r):
         """z = M^-1 r for r of `rows` values (element i = row row0 + i) of the handle's dtype."""
