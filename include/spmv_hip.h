@@ -1164,6 +1164,52 @@ enum { SPMV_MINRES_RAN_ALL = 0, SPMV_MINRES_CONVERGED = 1, SPMV_MINRES_BREAKDOWN
 int spmv_hip_csr_minres(spmv_csr_dev *m, const spmv_precond *P, int variant, int iters, double tol, double shift,
                         const int *bounds, const void *b_host, void *x_host, double *rr_hist, int *info,
                         float *ms_total);
+/* k independent MINRES recurrences for (A - shift_j I) x_j = b_j with a symmetric, possibly indefinite A and an
+ * optional symmetric positive definite M, x0 = 0, sharing the one SpMM of a step and the k-wide apply: the loop of
+ * spmv_hip_csr_minres with one shift, one set of Lanczos scalars, one Givens rotation, one phibar, stop state, status
+ * and step count per column (not block MINRES: no k x k coefficient matrices), in the layout of spmv_hip_csr_cg_multi.
+ * B, X and every loop vector are row-major n x k:
+ *   R1 = R2 = B;  Y = M^-1 R2;  bb0_j = r2_j.y_j;  beta_j = sqrt(bb0_j);  phibar_j = beta_j
+ *   oldb_j = dbar_j = epsln_j = 0;  cs_j = -1;  sn_j = 0;  W = W2 = 0;  hist[0][j] = bb0_j
+ *   step t:  v_j = y_j / beta_j;  A_V = A V (one SpMM)
+ *            t_j = a_j - shift_j v_j;  if t >= 2: t_j -= (beta_j / oldb_j) r1_j
+ *            alfa_j = v_j.t_j;  t_j -= (alfa_j / beta_j) r2_j
+ *            r1_j = r2_j;  r2_j = t_j;  Y = M^-1 R2;  oldb_j = beta_j;  bb_j = r2_j.y_j;  beta_j = sqrt(bb_j)
+ *            oldeps_j = epsln_j;  delta_j = cs_j dbar_j + sn_j alfa_j;  gbar_j = sn_j dbar_j - cs_j alfa_j
+ *            epsln_j = sn_j beta_j;  dbar_j = -cs_j beta_j;  gamma_j = sqrt(gbar_j^2 + beta_j^2)
+ *            cs_j = gbar_j / gamma_j;  sn_j = beta_j / gamma_j;  phi_j = cs_j phibar_j;  phibar_j = sn_j phibar_j
+ *            w1_j = w2_j;  w2_j = w_j;  w_j = (v_j - oldeps_j w1_j - delta_j w2_j) / gamma_j;  x_j += phi_j w_j
+ *            hist[t][j] = phibar_j^2;  column j has converged when phibar_j^2 <= tol^2 bb0_j
+ * (cs, sn, dbar, phibar on the right-hand sides of one line are the values before the step.)  The product is
+ * spmv_hip_csr_spmm_on on library-owned V (N x k, with the 128-byte line tail); there is no `variant`: the SpMM has none
+ * and k = 1 is the handle's AUTO launch.  With a communicator the next V is all-gathered with the row bounds scaled by
+ * k (one exchange per step) and every dot product is all-gathered and added in rank order, as in
+ * spmv_hip_csr_cg_multi; there is no halo exchange variant.
+ * shift: k values, or NULL for all 0.  The shifts go to A alone; M is used as built.
+ * P: NULL (y is r2 and t.t is bb), JACOBI (y = D^-1 t and t.y fused into the second Lanczos pass), BLOCK_JACOBI, FSAI,
+ * AMG or CHEBYSHEV (the k-wide apply of spmv_hip_precond_apply_multi_on after it, then one pass for r2.y).  SSOR and
+ * ILU0 are refused: their triangular solves take one right-hand side.
+ * Column j's sums add in an order that does not depend on j: permuting the columns of B together with the shifts
+ * permutes X, the history, steps and status bit for bit, and two calls give the same bits.  k = 1 agrees with
+ * spmv_hip_csr_minres to rounding, not bit for bit: that solver sums 16-byte pieces of rows, this one row by row.
+ * Per column, the rules of spmv_hip_csr_minres: b_j = 0 converges at step 0 with x_j = 0; the step that converges
+ * still does its x_j += phi_j w_j (and forms no v_j: beta_j may be 0); a breakdown (bb0_j < 0 or not finite at the
+ * start; alfa_j or alfa_j / beta_j not finite; bb_j < 0, which is how an M that is not positive definite is refused;
+ * gamma_j = 0; any scalar of the rotation not finite) leaves x_j at the last full iterate and does not count the step;
+ * no NaN is written into X.  A stopped column keeps its x, r1, r2, w and v, its history repeats its last value, it
+ * still rides in the SpMMs and the applies, and nothing it holds, a NaN or Inf included, reaches another column.
+ * tol = 0: exactly `iters` steps, no host synchronisation; tol > 0: the host reads one device word every 16 steps and
+ * ends the loop once no column is active.
+ * B_host: M_total x k row-major, values of the handle's dtype (a rank reads its own rows).
+ * Out (all optional): X_host M_total x k; rr_hist (iters + 1) x k, the recurrence's r.r (with M: r.M^-1 r) per column
+ * before step 1 and after every step; steps[k]; status[k] (SPMV_MINRES_*); *ms_total device time of the loop.
+ * -1 (the HIP error state stays clean, the handle still works): k < 1 or k > 64, a non-square matrix, a tiles-only
+ * handle, n*k beyond int range, iters < 0, tol < 0 or not finite, a shift_j that is not finite, a communicator without
+ * bounds, a row-range handle without a communicator, a P whose rows, row0 or dtype differ from the handle's, a P of
+ * kind SSOR or ILU0. */
+int spmv_hip_csr_minres_multi(spmv_csr_dev *m, const spmv_precond *P, int k, int iters, double tol, const double *shift,
+                              const int *bounds, const void *B_host, void *X_host, double *rr_hist, int *steps,
+                              int *status, float *ms_total);
 /* LOBPCG (Knyazev 2001) for the k smallest (largest = 0) or largest eigenpairs of a symmetric A held by an fp64 CSR
  * handle, with an optional symmetric positive definite preconditioner (Jacobi, block-Jacobi, FSAI, AMG or Chebyshev; smallest
  * only).

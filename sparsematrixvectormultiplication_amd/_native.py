@@ -296,6 +296,8 @@ _PROTOTYPES = {
                                               c_float_p]),
     "spmv_hip_csr_minres": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, c_int_p,
                                       C.c_void_p, C.c_void_p, c_double_p, c_int_p, c_float_p]),
+    "spmv_hip_csr_minres_multi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, c_double_p, c_int_p,
+                                            C.c_void_p, C.c_void_p, c_double_p, c_int_p, c_int_p, c_float_p]),
     "spmv_hip_csr_lobpcg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, c_double_p,
                                       c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p,
                                       c_float_p, c_float_p]),

@@ -817,6 +817,40 @@ class CsrDevice(_Handle):
                                              C.byref(ms)), "spmv_hip_csr_minres")
         return x, hist, {"steps": int(info[0]), "status": int(info[1])}, float(ms.value)
 
+    def minres_multi(self, B, iters, tol=0.0, shift=0.0, precond=None, bounds=None):
+        """k independent MINRES recurrences from x0 = 0 that share one SpMM per step (spmv_hip_csr_minres_multi), for
+        (A - shift_j I) x_j = b_j with the k columns of a C-contiguous B (M x k, 1 <= k <= 64) of the handle's dtype
+        and a symmetric, possibly indefinite A.  shift: one value for every column, or k values.  precond: a Jacobi,
+        block-Jacobi, FSAI, AMG or Chebyshev Preconditioner of this handle that is symmetric positive definite, or
+        None; SSOR and ILU(0) take one right-hand side and are refused.  Every column stops on its own, by the rules
+        of minres; tol > 0 also ends the loop early once every column has stopped.  Returns (X (M, k), the
+        recurrence's r.r history (iters + 1, k), info {"steps", "status" (MINRES_*)}: int arrays [k], ms)."""
+        B = _check_columns(B, self.M, self.dtype, "B", "handle")
+        _check_iters_tol(iters, tol)
+        k = B.shape[1]
+        shifts = np.asarray(shift, dtype=np.float64)
+        if shifts.ndim == 0:
+            shifts = np.full(k, float(shifts))
+        if shifts.shape != (k,):
+            raise ValueError(f"shift must be a scalar or {k} values, got shape {shifts.shape}")
+        if not np.all(np.isfinite(shifts)):
+            raise ValueError(f"shift must be finite, got {shift}")
+        shifts = np.ascontiguousarray(shifts)
+        if precond is not None:
+            self._check_precond(precond)
+        X = np.zeros((self.M, k), dtype=self.dtype)
+        hist = np.zeros((int(iters) + 1, k))
+        steps = np.zeros(k, dtype=np.int32)
+        status = np.zeros(k, dtype=np.int32)
+        ms = C.c_float(0)
+        _check(nat.lib().spmv_hip_csr_minres_multi(self.h, None if precond is None else precond.h, int(k), int(iters),
+                                                   float(tol), shifts.ctypes.data_as(nat.c_double_p),
+                                                   _bounds_arg(bounds), B.ctypes.data_as(C.c_void_p),
+                                                   X.ctypes.data_as(C.c_void_p), hist.ctypes.data_as(nat.c_double_p),
+                                                   steps.ctypes.data_as(nat.c_int_p), status.ctypes.data_as(nat.c_int_p),
+                                                   C.byref(ms)), "spmv_hip_csr_minres_multi")
+        return X, hist, {"steps": steps, "status": status}, float(ms.value)
+
     def gmres(self, b, iters, tol=0.0, restart=30, precond=None, variant=CSR_AUTO):
         """Restarted GMRES(restart) from x0 = 0 (spmv_hip_csr_gmres) for a square, possibly nonsymmetric A held whole
         by this handle: one SpMV per step, classical Gram-Schmidt done twice, a residual estimate that never grows
